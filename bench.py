@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: sampled trajectories/sec of the RAMP energy-based diffusion sampler on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -72,7 +72,33 @@ def parse():
                          "3 = Maze3D B=4096 H=48 T=25 4k-pt cloud; 4 = Maze2D dynamic replanning B=8192 (10 high-level DDIM steps "
                          "+ 3 replans x 5, moving 1024-pt pursuer cloud, one hipGraph per replan); "
                          "5 = Maze3D B=8192/GPU H=64 T=50 8k-pt cloud")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; float32, at most "
+                         "64 MB: a larger output is replaced by a fixed seeded sample of its rows, DIR/<name>_rows.npy names them)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6      # --dump-outputs: bytes on disk, the .npy headers included
+
+
+def dump_output(outdir, name, a):
+    """Write the float32 array `a` as outdir/<name>.npy.  Above DUMP_LIMIT_BYTES it is cut to a fixed (seeded, sorted) sample of
+    its leading-axis rows, whose indices go to outdir/<name>_rows.npy.  Returns {file name: shape}."""
+    os.makedirs(outdir, exist_ok=True)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    written = {}
+    if a.nbytes > DUMP_LIMIT_BYTES - 4096:
+        k = (DUMP_LIMIT_BYTES - 4096) // (a.nbytes // a.shape[0] + 8)          # rows that fit beside their float64 indices
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=k, replace=False)).astype(np.float64)
+        a = a[rows.astype(np.int64)]
+        np.save(os.path.join(outdir, f"{name}_rows.npy"), rows)
+        written[f"{name}_rows.npy"] = list(rows.shape)
+    np.save(os.path.join(outdir, f"{name}.npy"), a)
+    written[f"{name}.npy"] = list(a.shape)
+    return written
 
 
 WORKLOADS = {   # S, H, T, 3-D?, cloud (n_obstacles, n_points), use_apf
@@ -464,6 +490,11 @@ def main():
         gather_check = rdist.verify_gather(out_local.contiguous(), out, n_total)
         if gather_check["world"] != args.gpus or not gather_check["checksum_ok"] or gather_check["ranks_seen"] != list(range(args.gpus)):
             raise SystemExit(f"bench.py: the all-gather does not show {args.gpus} ranks: {gather_check}")
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's product as its caller receives it: the gathered (n_total, H, S) trajectories, or the planner's (H, S) plan
+        name = "plan" if WL.get("dynamic") else "trajectories"
+        dumped = dump_output(args.dump_outputs, name, out.detach().float().cpu().numpy())
 
     value = n_total * args.steps / dt
     ms_per_step = dt / args.steps * 1e3
@@ -508,6 +539,8 @@ def main():
                         "strong: --batch trajectories in total over the ranks (preset config5-strong = BASELINE configs[4], 65536 "
                         "trajectories); value = trajectories of all ranks / max-over-ranks wall time either way",
     }
+    if dumped is not None:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if cold:
         steady = dt / args.steps
         cold["steady_job_s"] = steady

@@ -1,5 +1,5 @@
 import ctypes as C, os, sys
-sys.path.insert(0, "/root/repo" if os.path.isdir("/root/repo/ramp_amd") else os.getcwd())
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from ramp_amd import _lib
 lib = _lib.load_tools()
 def t(M, N, K, taps, L, mode, flags, iters=10):

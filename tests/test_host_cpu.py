@@ -107,13 +107,27 @@ def test_state_dict_contract(S, o3, n):
 
 @pytest.mark.parametrize("T", [25, 50, 100])
 def test_schedule_buffers_bitwise(T):
-    """The wrapper computes its tables with the reference's own torch expressions: bitwise equal."""
+    """The wrapper computes its tables with the reference's own torch expressions: bitwise equal.  torch's float32 sqrt / log
+    round the last bit differently on some CPUs than on the one the fixture was captured on; there the buffers that pass through
+    them must equal, bitwise, the reference's expression evaluated on this CPU from the fixture's own (bitwise-checked) operands,
+    and lie within 1 ulp of the fixture.  Every other buffer is bitwise equal to the fixture on any CPU."""
     from ramp_amd.models import StaticGaussianDiffusionModel, TemporalUnetInference
     g = np.load(f"{GOLDEN}/schedule_T{T}.npz")
     dm = StaticGaussianDiffusionModel(model=TemporalUnetInference(n_support_points=48, state_dim=4),
                                       n_diffusion_steps=T, predict_epsilon=True)
+    ac, pv = torch.from_numpy(g["alphas_cumprod"]), torch.from_numpy(g["posterior_variance"])
+    via_sqrt_log = {   # diffusion_model_static.py:62-84, on the fixture's operands
+        "sqrt_alphas_cumprod": torch.sqrt(ac), "sqrt_one_minus_alphas_cumprod": torch.sqrt(1. - ac),
+        "log_one_minus_alphas_cumprod": torch.log(1. - ac), "sqrt_recip_alphas_cumprod": torch.sqrt(1. / ac),
+        "sqrt_recipm1_alphas_cumprod": torch.sqrt(1. / ac - 1), "posterior_log_variance_clipped": torch.log(torch.clamp(pv, min=1e-20))}
+    same_rounding = all(np.array_equal(v.numpy(), g[k]) for k, v in via_sqrt_log.items())
     for k in SCHEDULE_BUFFERS:
-        assert np.array_equal(getattr(dm, k).numpy(), g[k]), k
+        got = getattr(dm, k).numpy()
+        if same_rounding or k not in via_sqrt_log:
+            assert np.array_equal(got, g[k]), k
+        else:
+            assert np.array_equal(got, via_sqrt_log[k].numpy()), k
+            assert np.abs(got.view(np.int32).astype(np.int64) - g[k].view(np.int32)).max() <= 1, k
 
 
 def test_scene_encoders_match_golden():
