@@ -29,6 +29,11 @@ What is captured:
   boundary_cases.npz          public helper methods of the sampler class + predict_epsilon=False (one p_mean_variance, a DDPM chain)
   unet2d_h48_outlier.npz      the 2-D score evaluation with outlier-channel weights (8 rows of every to_out / ff.net.2 x 2^9)
   chain_ddpm_outlier.npz      the T = 25 DDPM chain on those weights (fp32 reference run + its float64 twin)
+  unet2d_h8 / unet3d_h16 / unet2d_h24 / unets3_h32 / unets2_h56 / unets16_h64.npz
+                              every other accepted horizon and the state-width range (N = 2 rows: cond, uncond): taps at
+                              level lengths 8/4/2/1, 16/8/4/2 (3-D), 24/12/6/3, 32/16/8/4 (S = 3), 56/28/14/7 (S = 2),
+                              64/32/16/8 (S = 16)
+  chain_ddpm_h24.npz          a free-running T = 25 DDPM chain at H = 24 (B = 3)
 """
 from __future__ import annotations
 
@@ -304,6 +309,33 @@ def gen_horizon40(m40, sp40):
     chain, used = run_static(m40, sp40, T, B, cloud, noise, ddim=False, use_apf=False)
     assert used == T + 1
     save("chain_ddpm_h40.npz", chain=chain, noise=noise, cloud=cloud, T=T)
+
+
+HORIZON_CASES = (   # tag, S, H, 3-D, t, seed: the horizons and state widths the engine accepts beyond the ones above
+    ("2d_h8", 4, 8, False, 5, 31),
+    ("3d_h16", 6, 16, True, 17, 32),
+    ("2d_h24", 4, 24, False, 9, 33),
+    ("s3_h32", 3, 32, False, 2, 34),
+    ("s2_h56", 2, 56, False, 21, 35),
+    ("s16_h64", 16, 64, False, 14, 36),
+)
+
+
+def gen_horizons():
+    """One tapped score evaluation (a cond / uncond pair) at each of HORIZON_CASES, and a free-running DDPM chain at H = 24."""
+    for tag, S, H, o3, t_val, seed in HORIZON_CASES:
+        m, sp, _ = build_unet(S, H, o3)
+        cloud = synth.make_cloud(5, 50, 3, seed=44) if o3 else synth.make_cloud(6, 64, 2, seed=42)
+        gen_unet(tag, m, sp, cloud, 2, t_val, seed=seed)
+    m24, sp24, _ = build_unet(4, 24, False)
+    cloud = synth.make_cloud(6, 64, 2, seed=42)
+    m24.reset_cache()
+    latent = m24.scene_encoder(torch.from_numpy(cloud)[None])[0].detach().numpy()
+    T, B = 25, 3
+    noise = synth.make_noise((T + 1, B, 24, 4), seed=37)
+    chain, used = run_static(m24, sp24, T, B, cloud, noise, ddim=False, use_apf=False)
+    assert used == T + 1
+    save("chain_ddpm_h24.npz", chain=chain, noise=noise, cloud=cloud, latent=latent, T=T)
 
 
 def gen_fullsize_seeds(m2, sp2, m3, sp3):
@@ -837,6 +869,8 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "h40":
         m40, sp40, _ = build_unet(4, 40, False)
         gen_horizon40(m40, sp40); return
+    if len(sys.argv) > 1 and sys.argv[1] == "horizons":
+        gen_horizons(); return
     if len(sys.argv) > 1 and sys.argv[1] == "boundary":
         m2, sp2, _ = build_unet(4, 48, False)
         gen_boundary(m2, sp2); return
@@ -870,6 +904,7 @@ def main():
     print("metrics"); gen_metrics()
     print("compat"); gen_compat()
     print("horizon 40"); m40, sp40, _ = build_unet(4, 40, False); gen_horizon40(m40, sp40)
+    print("every other horizon / state width"); gen_horizons()
     print("boundary helpers / predict_epsilon=False"); gen_boundary(m2, sp2)
     print("outlier-channel weights"); gen_outlier_unet()
     print("done")

@@ -383,7 +383,7 @@ int launch_resample(const ResampleArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------
-// first conv block input (Cin = S in {4, 6}: too thin for the MFMA GEMM's float4 staging)
+// first conv block input (Cin = S in [2, 16], ramp_create's range: too thin for the MFMA GEMM's float4 staging)
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv_in_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W5,
                                                            const float* __restrict__ b5, const float* __restrict__ W1,

@@ -26,6 +26,10 @@ def rng(seed):
     (48 * 5, 32, 32, 5, 48), (24 * 7, 64, 32, 5, 24), (6 * 11, 128, 512, 5, 6), (12 * 9, 64, 128, 5, 12),
     (130, 32, 256, 1, 1), (64 * 3, 32, 32, 5, 64), (777, 160, 64, 1, 1), (12 * 50, 512, 64, 3, 12), (129, 768, 2048, 1, 1),
     (48 * 20, 256, 128, 5, 48), (1000, 128, 32, 1, 1),
+    # "same" k = 5 convolutions on samples shorter than the kernel and at odd lengths (the level lengths of H = 8, 16, 24, 32, 56):
+    # a tap that is not masked at a sample edge reads the neighbouring sample
+    (1 * 37, 64, 64, 5, 1), (2 * 29, 128, 64, 5, 2), (3 * 21, 256, 128, 5, 3), (4 * 19, 64, 32, 5, 4), (7 * 13, 256, 256, 5, 7),
+    (56 * 3, 32, 32, 5, 56),
 ])
 @pytest.mark.parametrize("backward", [False, True])
 @pytest.mark.parametrize("mode", ["fp32", "bf16x6", "bf16x6-lds", "fp16x3"])
@@ -81,7 +85,8 @@ def test_gemm_fp16x3_launch_rules_at_scale(M, N, K, resid):
     assert worst < 3e-6, worst
 
 
-@pytest.mark.parametrize("R,L,C", [(3, 48, 32), (5, 24, 64), (2, 12, 128), (7, 6, 256), (2, 64, 32), (3, 8, 256), (2, 24, 32)])
+@pytest.mark.parametrize("R,L,C", [(3, 48, 32), (5, 24, 64), (2, 12, 128), (7, 6, 256), (2, 64, 32), (3, 8, 256), (2, 24, 32),
+                                   (5, 1, 256), (3, 2, 128), (4, 7, 256)])
 @pytest.mark.parametrize("mish", [0, 1])
 def test_groupnorm_fwd_bwd(R, L, C, mish):
     g = rng(R * L + C + mish)
@@ -139,10 +144,15 @@ def test_geglu_fwd_bwd():
     assert rel(dag.cpu().numpy(), dag_ref) < 2e-6
 
 
-@pytest.mark.parametrize("L", [6, 8, 12, 16, 24, 32, 48, 64])
+# the level lengths H, H/2, H/4, H/8 of every horizon ramp_create accepts: all of RAMP_ATTN_LENGTHS (attention.hip; the CPU suite
+# checks the two lists agree)
+ATTN_LENGTHS = sorted({H >> k for H in range(8, 65, 8) for k in range(4)})
+
+
+@pytest.mark.parametrize("L", ATTN_LENGTHS)
 @pytest.mark.parametrize("R", [1, 7])
 def test_attention_fwd_bwd(L, R):
-    """4 x 64 softmax attention within each row of L tokens, forward and (dq, dk, dv)."""
+    """4 x 64 softmax attention within each row of L tokens, forward and (dq, dk, dv), at every length a horizon produces."""
     g = rng(L * 10 + R)
     qkv = g.standard_normal((R, L, 768)).astype(np.float32)
     do = g.standard_normal((R, L, 256)).astype(np.float32)

@@ -847,6 +847,27 @@ def test_ddpm_chain_at_another_horizon():
         build_unet(4, 44, False, max_rows=8).ctx()            # not a multiple of 8: refused at ramp_create, like the reference's shapes
 
 
+def test_ddpm_chain_at_horizon_24_with_the_fused_plan():
+    """n_support_points = 24 (levels of 24, 12, 6 and 3 tokens, where every sample-owning kernel applies at every level its channel
+    widths reach): the bench's launch plan (fp16x3-tkw) inside the captured graph, a free-running 25-step DDPM chain against a run of
+    the reference, hard conditions held at waypoints 0 and 23."""
+    from ramp_amd.models import StaticGaussianDiffusionModel
+    g = np.load(f"{GOLDEN}/chain_ddpm_h24.npz")
+    mode, plan = util.split_mode("fp16x3-tkw")
+    u = build_unet(4, 24, False, max_rows=64, gemm_mode=mode, launch_plan=plan)
+    dm = StaticGaussianDiffusionModel(model=u, variance_schedule="exponential", n_diffusion_steps=25, predict_epsilon=True,
+                                      compose=False, use_apf=False, sampler="ddpm", use_graph=True).eval().to("cuda")
+    chain, used = run(dm, g, g["chain"].shape[1])
+    assert used == g["noise"].shape[0] and chain.shape == g["chain"].shape
+    err = np.abs(chain - g["chain"]).max()
+    print(f"ddpm H=24 fp16x3-tkw graph: max {err:.2e}")
+    assert err < 1e-4
+    hc = synth.default_hard_conds(4, 24)
+    assert sorted(hc) == [0, 23]
+    for w in (0, 23):
+        assert np.array_equal(chain[:, :, w], np.broadcast_to(hc[w], chain[:, :, w].shape))
+
+
 def test_philox_noise_is_host_replicable_and_jobs_draw_it_inside_the_graph():
     """Throughput jobs draw N(0, I) inside the captured job (noise_source='philox': Philox4x32-10 + Box-Muller from a
     (seed, offset) device record) instead of torch.randn on the host stream (sample_functions.py:36).  (1) the stream equals

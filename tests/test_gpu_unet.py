@@ -12,6 +12,11 @@ from util import GOLDEN, build_unet, dev, rel, weights
 pytestmark = pytest.mark.gpu
 
 CASES = [("2d_h48", 4, 48, False), ("3d_h48", 6, 48, True), ("3d_h64", 6, 64, True), ("2d_h40", 4, 40, False)]
+# every other horizon ramp_create accepts (a multiple of 8 in [8, 64]) and the ends of its state-width range [2, 16]:
+# level lengths 8/4/2/1, 16/8/4/2, 24/12/6/3, 32/16/8/4, 56/28/14/7 and 64/32/16/8 (oracle/make_goldens.py horizons)
+HORIZON_CASES = [("2d_h8", 4, 8, False), ("3d_h16", 6, 16, True), ("2d_h24", 4, 24, False), ("s3_h32", 3, 32, False),
+                 ("s2_h56", 2, 56, False), ("s16_h64", 16, 64, False)]
+CASES += HORIZON_CASES
 
 
 @pytest.mark.parametrize("gemm_mode", ["fp16x3", "fp16x3-fusedff", "fp16x3-ffx", "fp16x3-tok", "fp16x3-atk", "fp16x3-tkc", "fp16x3-tkw", "fp16x3-m32", "bf16x6", "fp32"])
@@ -133,6 +138,105 @@ def test_score_chunked_batch_vs_oracle64(S, H, o3):
     sub = torch.empty((2 * 3, H, S), device="cuda")
     _lib.check(_lib.load().ramp_score(m.ctx(), _lib.ptr(xd[4:7].contiguous()), 3, 2, 24, None, _lib.ptr(sub), _lib.current_stream()))
     assert torch.equal(sub, eps[8:14])
+
+
+# Which sample-owning kernels the bench's plan (fp16x3-tkw) dispatches at each new horizon, from their predicates and the layer
+# widths of spec.py (levels H, H/2, H/4, H/8; attention inner width 256 everywhere; k = 5 convolutions with C_in, C_out in {32, 64}
+# at H and H/2, 64 x 64 at H/4 (ups.1), 128 .. 512 wide at H/4 and H/8; the input gradients swap N and K).
+#   ato / abl: ato_applicable (atk.hip) -- some level length divides 48 or 32;
+#   tkc: tkc_applicable (tkc.hip) -- a narrow level of length L >= 8 dividing 48 or 32, or 64 (not 64 x 64 channels);
+#   tkw: tkw_applicable (tkw.hip) -- a wide level with L >= 3 and 96 % L == 0 (the input gradient also needs tw_pro_variant);
+#   tklb: use_tklb -- the d(ln1) of a level abl does not take (ato_applicable false there).
+# Slot order of ramp_profile_read_kernels: 0 ffx forward, 1 ffx backward, 2 tkl, 3 tklb, 4 ato, 5 abl, 6 tkc, 7 tkw.
+DISPATCH = {   # H: (ato, abl, tkc, tkw, tklb)
+    8: (True, True, True, False, False),    # 8 | 48; tkc at L = 8; no wide level has L >= 3 (H/4 = 2, H/8 = 1), and ups.2's conv-1 input
+                                            # gradient (N = 128, K = 32, L = 4) fails tw_pro_variant (4 % 8 staged rows); 8/4/2/1 all take abl
+    16: (True, True, True, True, False),    # 16 | 48; tkc at 16 and 8; tkw at L = 4 (96 % 4 == 0); 16/8/4/2 all take abl
+    24: (True, True, True, True, False),    # every level divides 48 (abl everywhere, no tklb); tkc at 24 and 12; tkw at 6 and 3
+    32: (True, True, True, True, False),    # 32 | 32; tkc at 32, 16 and 8; tkw at 8 and 4; 32/16/8/4 all take abl
+    56: (False, False, False, False, True),  # 56/28/14/7: no level divides 48, 32 or 96 -- everything on the generic kernels
+    64: (True, True, True, True, True),     # ato from L = 32 down; tkc at 64 (NG = 4) and 32; tkw at 16 and 8; L = 64 keeps tklb
+}
+
+
+@pytest.mark.parametrize("tag,S,H,o3", HORIZON_CASES)
+def test_fused_plan_dispatches_what_the_predicates_admit(tag, S, H, o3):
+    """The bench's launch plan on one eager fp16x3 evaluation (after its calibration): the profiled kernel slots that are
+    non-zero are exactly the ones the predicates admit at this horizon (DISPATCH), so the fixture parity in fp16x3-tkw mode
+    really exercised the sample-owning kernels where they apply, and the fallback path where they do not."""
+    import ctypes as C
+    from ramp_amd import _lib
+    g = np.load(f"{GOLDEN}/unet{tag}.npz")
+    m = build_unet(S, H, o3, max_rows=8, gemm_mode="fp16x3", launch_plan=util.PLANS["tkw"])
+    N = g["x"].shape[0]
+    x = dev(g["x"]); t = torch.from_numpy(g["t"]).cuda()
+    pts = dev(g["cloud"])[None].repeat(N, 1, 1, 1)
+    m(x, t, None, obstacle_pts=pts); m(x, t, None, obstacle_pts=pts)      # forward and input-gradient call sites calibrated
+    lib = _lib.load()
+    _lib.check(lib.ramp_profile(m.ctx(), 1))
+    eps = m(x, t, None, obstacle_pts=pts).cpu().numpy()
+    ms = (C.c_double * 9)(); fl = (C.c_double * 9)(); cnt = (C.c_int64 * 9)()
+    _lib.check(lib.ramp_profile_read_kernels(m.ctx(), 9, ms, fl, cnt))
+    _lib.check(lib.ramp_profile(m.ctx(), 0))
+    assert m.score_mode() == "fp16x3"
+    counts = list(cnt)
+    print(f"{tag}: kernel launches ffx_fwd ffx_bwd tkl tklb ato abl tkc tkw other = {counts}")
+    assert counts[0] > 0 and counts[1] > 0 and counts[2] > 0, counts
+    want = dict(zip(("ato", "abl", "tkc", "tkw", "tklb"), DISPATCH[H]))
+    got = dict(ato=counts[4] > 0, abl=counts[5] > 0, tkc=counts[6] > 0, tkw=counts[7] > 0, tklb=counts[3] > 0)
+    assert got == want, (H, counts)
+    assert rel(eps, g["eps"]) < 5e-5
+
+
+_ORACLE64 = {}
+
+
+def _oracle64_batch(S, H, o3, x2, lats):
+    """float64 oracle (f, eps) of the per-horizon batch at t = 0 and 24, computed once per shape."""
+    key = (S, H, o3)
+    if key not in _ORACLE64:
+        u = O.UNetOracle(weights(S, H, o3), S, H, obstacle_3d=o3, dtype=np.float64)
+        out = {}
+        for t in (0, 24):
+            tt = np.full((x2.shape[0],), t)
+            out[t] = (u.forward_no_energy(x2, tt, lats), u.score(x2, tt, lats))
+        _ORACLE64[key] = out
+    return _ORACLE64[key]
+
+
+@pytest.mark.parametrize("gemm_mode", ["fp16x3", "fp16x3-tkw"])
+@pytest.mark.parametrize("tag,S,H,o3", HORIZON_CASES)
+def test_score_batch_at_every_horizon_vs_oracle64(tag, S, H, o3, gemm_mode):
+    """B = 7 trajectories x 2 variants (14 rows) through a context of 6 rows (chunks of 6, 6 and 2 rows) at every new horizon and
+    state width, against the float64 oracle, per ROW as well as over the batch: a max-normalised error over the whole batch cannot
+    see one wrong sample in a partial tile or a short last chunk."""
+    from ramp_amd import _lib
+    base, plan = util.split_mode(gemm_mode)
+    m = build_unet(S, H, o3, max_rows=6, gemm_mode=base, launch_plan=plan)
+    cloud = synth.make_cloud(6, 64, 2, seed=3) if not o3 else synth.make_cloud(4, 30, 3, seed=3)
+    lat = m.encode_scene(dev(cloud))
+    m.set_scene(torch.cat([lat, torch.zeros_like(lat)]), [0, 1])
+    m.prepare_time_table(25)
+    B = 7
+    x = synth.make_noise((B, H, S), seed=22)
+    xd = dev(x)
+    lats = np.tile(lat[0].cpu().numpy()[None], (2 * B, 1)); lats[1::2] = 0
+    ref = _oracle64_batch(S, H, o3, np.repeat(x, 2, axis=0), lats)
+    lib = _lib.load()
+    eps = torch.empty((2 * B, H, S), device="cuda"); f = torch.empty_like(eps)
+    _lib.check(lib.ramp_score(m.ctx(), _lib.ptr(xd), B, 2, 24, _lib.ptr(f), _lib.ptr(eps), _lib.current_stream()))
+    assert m.score_mode() == "bf16x6"                          # calibration evaluation
+    for t in (0, 24):
+        _lib.check(lib.ramp_score(m.ctx(), _lib.ptr(xd), B, 2, t, _lib.ptr(f), _lib.ptr(eps), _lib.current_stream()))
+        assert m.score_mode() == "fp16x3"
+        f64, eps64 = ref[t]
+        fh, eh = f.cpu().numpy(), eps.cpu().numpy()
+        assert rel(fh, f64) < 2e-5 and rel(eh, eps64) < 5e-5, t
+        row_f = [rel(fh[r], f64[r]) for r in range(2 * B)]
+        row_e = [rel(eh[r], eps64[r]) for r in range(2 * B)]
+        print(f"{tag} {gemm_mode} t={t}: f {rel(fh, f64):.2e} eps {rel(eh, eps64):.2e}, worst row f {max(row_f):.2e} eps {max(row_e):.2e}")
+        assert max(row_f) < 2e-5, (t, row_f)
+        assert max(row_e) < 5e-5, (t, row_e)
 
 
 def test_missing_weights_and_bad_args_fail_loudly():

@@ -399,3 +399,16 @@ def test_sampler_helper_methods_against_reference_fixture():
         d3 = cls(model=net, n_diffusion_steps=25, predict_epsilon=True, **kw)
         xr, tr, _, obr = d3.deep_repeat_tensor(x, torch.arange(3), z, pts, 2)
         assert torch.equal(xr, torch.cat([x, x])) and tr.tolist() == [0, 1, 2, 0, 1, 2] and obr.shape[0] == 2
+
+
+def test_attention_lengths_cover_every_accepted_horizon():
+    """The generic attention kernels are instantiated for a fixed list of level lengths (RAMP_ATTN_LENGTHS, attention.hip); ramp_create
+    accepts any horizon that is a multiple of 8 in [8, 64], whose levels run H, H/2, H/4 and H/8 tokens.  The two must be the same set,
+    which is also the list test_attention_fwd_bwd runs: an accepted horizon then never reaches an untested (or missing) length."""
+    src = open(os.path.join(ROOT, "ramp_amd", "csrc", "attention.hip")).read()
+    m = re.search(r"#define RAMP_ATTN_LENGTHS\(X\)((?:\s*X\(\d+\))+)", src)
+    assert m, "RAMP_ATTN_LENGTHS not found"
+    built = [int(v) for v in re.findall(r"X\((\d+)\)", m.group(1))]
+    eng = open(os.path.join(ROOT, "ramp_amd", "csrc", "engine.hip")).read()
+    assert "cfg->horizon >= 8 && cfg->horizon <= 64 && cfg->horizon % 8 == 0" in eng      # the accepted horizons this test assumes
+    assert built == sorted({H >> k for H in range(8, 65, 8) for k in range(4)}), built
