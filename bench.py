@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: sampled trajectories/sec of the RAMP energy-based diffusion sampler on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,9 +15,11 @@ Weak scaling: every rank samples its own B trajectories; value = N*B*K / max-ove
 Without a torchrun environment `python bench.py --gpus N` (N > 1) starts its own N ranks (a parent that never touches the
 GPU spawns one child per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) and exits non-zero unless all N ran.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (HIP-event timing of the dominant KERNEL,
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+the warm-up jobs, the K timed jobs, --dump-outputs.  --full adds everything else the benchmark measures, on rank 0 of a one-GPU run
+after the timed region: `solution_quality` of the last batch, `guard_trip`, `roofline` (HIP-event timing of the dominant KERNEL,
 ramp::ffx_kernel<fwd | bwd>, on its launch stream, priced against the fp16 matrix pipe it executes on; `class_frac` = the same
-for the whole split-precision GEMM class) and
+for the whole split-precision GEMM class), the bf16x6 and exact fp32-MFMA modes, configs 3 / 4 / 5 as `other_configs`, and
 `cpu_baseline` (an eager PyTorch-CPU model of the same architecture, oracle/torch_cpu.py, pinned to the reference's
 outputs, timed on this host's cores on a bounded sample; the numpy oracle's rate is reported beside it).
 """
@@ -49,8 +51,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=4096, help="trajectories per GPU (BASELINE configs[1])")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline (solution quality, guard trip, roofline, "
+                         "bf16x6 / fp32 modes, configs 3 / 4 / 5, CPU baseline); a plain run reports the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without guard trip, roofline and the bf16x6 / fp32 modes")
     ap.add_argument("--max-rows", type=int, default=0, help="network rows per chunk of a score evaluation (0: all 2 B rows at once)")
     ap.add_argument("--no-calibration-reuse", action="store_true",
                     help="diagnostic: every job calibrates itself in its first evaluation (bf16x6) instead of using the context's canonical "
@@ -66,7 +71,7 @@ def parse():
     ap.add_argument("--noise", choices=["philox", "torch"], default="philox",
                     help="philox: every job draws its N(0, I) inside its captured graph (Philox4x32-10, SURVEY 8(d)); torch: "
                          "torch.randn on the host stream + a copy into the job, like the reference")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the configs 3 / 4 / 5 sub-lines of the default run")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full without the configs 3 / 4 / 5 sub-lines")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5],
                     help="BASELINE.json config (1-based): 2 = headline Maze2D B=4096 H=48 T=25 (default); "
                          "3 = Maze3D B=4096 H=48 T=25 4k-pt cloud; 4 = Maze2D dynamic replanning B=8192 (10 high-level DDIM steps "
@@ -447,7 +452,8 @@ def main():
     if rank == 0 and world == 1 and args.config == 2:
         # SURVEY 8(d) "also report including them": what a FRESH context pays before its first trajectory -- weight upload +
         # packing (ramp_load_weight / ramp_finalize_weights), time table + scene encoding, then the first job (graph capture +
-        # the context's canonical calibration evaluation); the steady job time is added below
+        # the context's canonical calibration evaluation); the steady job time is added below.  A plain run keeps this first job
+        # too: it is what leaves graph capture and calibration out of the timed steps even at --warmup 0
         torch.cuda.synchronize(); tq = time.perf_counter()
         dm.model.ctx()
         torch.cuda.synchronize(); cold["weight_load_and_pack_s"] = time.perf_counter() - tq
@@ -511,10 +517,11 @@ def main():
                      "maxima its predecessor recorded -- for a job's first evaluation, from the context's canonical calibration (one "
                      "bf16x6 evaluation on fixed-seed Philox noise, run once, outside any job: ramp_set_calibration_reuse) -- under an "
                      "on-device range guard (fp32-level accuracy: the parity tests run in this mode); the bf16x6 and exact fp32-MFMA "
-                     "modes are timed below",
+                     "modes are timed by --full",
         "jobs_self_contained": "every timed job is independent of the jobs before it (no carried-over maxima, no bf16x6 evaluation inside a "
                                "job); the context's one canonical calibration evaluation is inside cold_start.first_job_s",
         "canonical_calibration": not args.no_calibration_reuse,
+        "full": args.full,
         "config": {"workload": {2: "BASELINE configs[1]: Maze2D static DDPM, B=4096 trajectories/GPU x 2 CFG rows, "
                                    "H=48, S=4, T=25, 1024-pt cloud, APF forward_t>20, hipGraph replay",
                                 3: "BASELINE configs[2]: Maze3D DDPM (w=5.75), B=4096/GPU x 2 CFG rows, H=48, S=6, T=25, 4000-pt cloud",
@@ -550,7 +557,7 @@ def main():
         result["cold_start"] = cold
         result["value_incl_scene_encode_and_weight_load"] = B / (cold["weight_load_and_pack_s"] + cold["time_table_and_scene_encode_s"] + steady)
         result["value_first_job_incl_everything"] = B / (cold["weight_load_and_pack_s"] + cold["time_table_and_scene_encode_s"] + cold["first_job_s"])
-    if rank == 0 and not WL["o3"] and not WL.get("dynamic"):
+    if args.full and rank == 0 and not WL["o3"] and not WL.get("dynamic"):
         # solution quality of the last timed batch, outside the timed region (on-device metrics);
         # the weights are random, so this only shows that the metric path runs at the benchmark's batch size
         from ramp_amd.metrics import Metrics
@@ -566,9 +573,9 @@ def main():
         result["solution_quality"]["metrics_ms"] = (time.perf_counter() - tq) * 1e3
         result["solution_quality"]["note"] = "random-init weights: not a planning-quality claim"
 
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_roofline:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_roofline:
         result["guard_trip"] = guard_trip_jobs(dm, B, cloud, hard_conds)
-    if rank == 0 and world == 1 and not args.no_roofline and not WL.get("dynamic"):
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and not WL.get("dynamic"):
         prof = profile_gemm(dm, B, cloud, hard_conds)
         kern = prof.pop("_kernels")
         g = prof["gemm_f32_mfma"]
@@ -626,7 +633,7 @@ def main():
         }
     elif rank == 0:
         result["roofline"] = None
-    if rank == 0 and world == 1 and not args.no_roofline and args.config == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_roofline and args.config == 2:
         # the same job with exact fp32 MFMA (v_mfma_f32_32x32x2_f32) GEMMs, one step, for reference
         del dm
         torch.cuda.empty_cache()
@@ -641,7 +648,7 @@ def main():
                            "e2e_frac_of_its_roofline": tf * 6 / PEAK_FP16_MFMA_TFLOPS if mode == "bf16x6" else tf / PEAK_FP32_MFMA_TFLOPS}
             del dm2
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_other_configs:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_other_configs:
         # BASELINE configs[2], [3], [4] (one GPU's share) in the driver's own run: 1 warm-up + 2 timed jobs each
         try:
             del dm
@@ -676,7 +683,7 @@ def main():
             del dmc, oc
             torch.cuda.empty_cache()
         WL = WORKLOADS[args.config]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 2:
         result["cpu_baseline"] = cpu_baseline(sd, cloud_np, args.cpu_sample)
     elif rank == 0:
         result["cpu_baseline"] = None

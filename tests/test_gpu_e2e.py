@@ -132,3 +132,22 @@ def test_inference_dynamic_entry_runs_to_the_end(tmp_path):
     assert np.allclose(metrics["chain_start"][0], [[-0.8, -0.8]])
     assert runner.last_chain.shape[1:] == (1, 48, 4) and bool(torch.isfinite(runner.last_chain).all())
     assert (tmp_path / "data" / "EnvSimple2D-RobotPointMass" / "contexts" / "contexts" / "context_000.pt").exists()
+
+
+def test_bench_plain_run_reports_the_headline_only(tmp_path):
+    """A plain `bench.py` run does set-up, warm-up, the timed steps and --dump-outputs, and nothing after them: none of the
+    --full measurements (solution quality, guard trip, roofline, other modes and configs, CPU baseline) is in its line."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0",
+                        "--batch", "64", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-1500:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["full"] is False and d["steps"] == 1 and d["warmup"] == 0 and d["ms_per_step"] > 0
+    assert d["value"] == pytest.approx(64 / (d["ms_per_step"] * 1e-3))
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    assert not {"solution_quality", "guard_trip", "bf16x6_mode", "fp32_mfma_mode", "other_configs"} & set(d)
+    assert np.isfinite(np.load(tmp_path / "trajectories.npy")).all()
+    assert d["dumped_outputs"]["arrays"] == {"trajectories.npy": [64, 48, 4]}
