@@ -81,8 +81,9 @@ def make_synthetic_experiment(root: str, cfg: Config3d, cloud=None, n_obstacles:
     with open(os.path.join(env_dir, "metadata.yaml"), "w") as fh:
         yaml.safe_dump({"box_sizes": [[0.26, 0.26, 0.26]] * (n_obstacles // 2), "sphere_radii": [0.1] * (n_obstacles - n_obstacles // 2),
                         "limits": [[-1.0, -1.0, -1.0], [1.0, 1.0, 1.0]]}, fh)
-    sp = make_unet_spec(cfg.state_dim, cfg.n_support_points, obstacle_3d=True)
-    dm = GaussianDiffusionModel3d(model=TemporalUnetInference(n_support_points=cfg.n_support_points, state_dim=cfg.state_dim, obstacle_3d=True),
+    sp = make_unet_spec(cfg.state_dim, cfg.n_support_points, cfg.unet_input_dim, UNET_DIM_MULTS[cfg.unet_dim_mults_option], obstacle_3d=True)
+    dm = GaussianDiffusionModel3d(model=TemporalUnetInference(n_support_points=cfg.n_support_points, state_dim=cfg.state_dim,
+                                                               unet_input_dim=cfg.unet_input_dim, dim_mults=UNET_DIM_MULTS[cfg.unet_dim_mults_option], obstacle_3d=True),
                                   variance_schedule=cfg.variance_schedule, n_diffusion_steps=cfg.n_diffusion_steps, predict_epsilon=True)
     full = dm.state_dict()
     for k, v in synth.make_unet_state_dict(sp, seed=0).items():
@@ -131,8 +132,11 @@ def main(argv=None):
     ap.add_argument("--n-samples", type=int, default=Config3d.n_samples)
     ap.add_argument("--n-diffusion-steps", type=int, default=Config3d.n_diffusion_steps)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=Config3d.unet_input_dim)
+    ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=Config3d.unet_dim_mults_option)
     args = ap.parse_args(argv)
     cfg = Config3d(); cfg.n_samples, cfg.n_diffusion_steps, cfg.model_id, cfg.seed = args.n_samples, args.n_diffusion_steps, args.model_id, args.seed
+    cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
     if args.make_synthetic:
         make_synthetic_experiment(args.make_synthetic, cfg, cloud=getattr(main, "synthetic_cloud", None))
         cfg.dataset_path = os.path.join(args.make_synthetic, "data"); cfg.trained_models_dir = os.path.join(args.make_synthetic, "models")

@@ -84,8 +84,9 @@ def make_synthetic_experiment(root: str, cfg: DynamicConfig, seed: int = 42) -> 
     # the reference reads <dataset>/<subdir>/contexts/contexts/context_XXX.pt (inference_dynamic.py:150-154)
     compat.ContextManager.save_context(torch.tensor([-0.8, -0.8]), torch.tensor([0.8, 0.8]),
                                        os.path.join(root, "data", cfg.dataset_subdir, "contexts"), cfg.dataset_subdir, 0)
-    sp = make_unet_spec(cfg.state_dim, cfg.n_support_points)
-    dm = DynamicGaussianDiffusionModel(model=TemporalUnetInference(n_support_points=cfg.n_support_points, state_dim=cfg.state_dim),
+    sp = make_unet_spec(cfg.state_dim, cfg.n_support_points, cfg.unet_input_dim, UNET_DIM_MULTS[cfg.unet_dim_mults_option])
+    dm = DynamicGaussianDiffusionModel(model=TemporalUnetInference(n_support_points=cfg.n_support_points, state_dim=cfg.state_dim,
+                                                               unet_input_dim=cfg.unet_input_dim, dim_mults=UNET_DIM_MULTS[cfg.unet_dim_mults_option]),
                                        variance_schedule=cfg.variance_schedule, n_diffusion_steps=cfg.n_diffusion_steps, predict_epsilon=True)
     full = dm.state_dict()
     for k, v in synth.make_unet_state_dict(sp, seed=0).items():
@@ -157,8 +158,11 @@ def main(argv=None):
     ap.add_argument("--make-synthetic", metavar="DIR"); ap.add_argument("--dataset-path"); ap.add_argument("--trained-models-dir")
     ap.add_argument("--model-id", default=DynamicConfig.model_id); ap.add_argument("--context", type=int, default=0)
     ap.add_argument("--n-samples", type=int, default=DynamicConfig.n_samples); ap.add_argument("--max-replans", type=int, default=DynamicConfig.max_replans)
+    ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=DynamicConfig.unet_input_dim)
+    ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=DynamicConfig.unet_dim_mults_option)
     args = ap.parse_args(argv)
     cfg = DynamicConfig(); cfg.n_samples, cfg.model_id, cfg.max_replans = args.n_samples, args.model_id, args.max_replans
+    cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
     if args.make_synthetic:
         make_synthetic_experiment(args.make_synthetic, cfg)
         cfg.dataset_path = os.path.join(args.make_synthetic, "data"); cfg.trained_models_dir = os.path.join(args.make_synthetic, "models")

@@ -85,8 +85,9 @@ def make_synthetic_experiment(root: str, cfg: StaticConfig, n_obstacles: int = 6
     with open(os.path.join(env_dir, "metadata.yaml"), "w") as fh:
         yaml.safe_dump({"box_sizes": [[0.26, 0.26]] * n_obstacles}, fh)
     compat.ContextManager.save_context(torch.tensor([-0.8, -0.8]), torch.tensor([0.8, 0.8]), env_dir, cfg.dataset_subdir, 0)
-    sp = make_unet_spec(cfg.state_dim, cfg.n_support_points)
-    dm = StaticGaussianDiffusionModel(model=TemporalUnetInference(n_support_points=cfg.n_support_points, state_dim=cfg.state_dim),
+    sp = make_unet_spec(cfg.state_dim, cfg.n_support_points, cfg.unet_input_dim, UNET_DIM_MULTS[cfg.unet_dim_mults_option])
+    dm = StaticGaussianDiffusionModel(model=TemporalUnetInference(n_support_points=cfg.n_support_points, state_dim=cfg.state_dim,
+                                                               unet_input_dim=cfg.unet_input_dim, dim_mults=UNET_DIM_MULTS[cfg.unet_dim_mults_option]),
                                       variance_schedule=cfg.variance_schedule, n_diffusion_steps=cfg.n_diffusion_steps,
                                       predict_epsilon=True)
     full = dm.state_dict()                                     # the 12 schedule buffers + scene encoder defaults
@@ -168,11 +169,14 @@ def main(argv=None):
     ap.add_argument("--sampler", choices=["ddim", "ddpm"], default=None)
     ap.add_argument("--use-apf", action="store_true")
     ap.add_argument("--n-steps-without-noise", type=int, default=StaticConfig.n_diffusion_steps_without_noise)
+    ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=StaticConfig.unet_input_dim)
+    ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=StaticConfig.unet_dim_mults_option)
     args = ap.parse_args(argv)
     cfg = StaticConfig()
     cfg.n_samples, cfg.n_diffusion_steps, cfg.sampler, cfg.use_apf = args.n_samples, args.n_diffusion_steps, args.sampler, args.use_apf
     cfg.dataset_subdir, cfg.model_id = args.dataset_subdir, args.model_id
     cfg.n_diffusion_steps_without_noise = args.n_steps_without_noise
+    cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
     if args.make_synthetic:
         make_synthetic_experiment(args.make_synthetic, cfg)
         cfg.dataset_path = os.path.join(args.make_synthetic, "data")

@@ -30,8 +30,9 @@ typedef struct ramp_ctx ramp_ctx;
 typedef struct ramp_config {
   int32_t state_dim;       /* S: 4 (Maze2D) or 6 (Maze3D)                              */
   int32_t horizon;         /* H = n_support_points: any multiple of 8 in [8, 64]       */
-  int32_t unet_input_dim;  /* 32                                                       */
-  int32_t n_levels;        /* len(dim_mults) = 4 for UNET_DIM_MULTS[1] = (1,2,4,8)      */
+  int32_t unet_input_dim;  /* C0: 16, 32 or 64 (channels C0 * dim_mults[k])           */
+  int32_t n_levels;        /* len(dim_mults): 3 for UNET_DIM_MULTS[0] = (1,2,4),        *
+                            * 4 for UNET_DIM_MULTS[1] = (1,2,4,8)                       */
   int32_t context_dim;     /* 320 (2-D scene encoder) or 256 (3-D)                     */
   int32_t max_rows;        /* capacity in network rows per chunk (rows = B * n_rp)     */
   int32_t debug_taps;      /* 1: keep per-module outputs / output-grads for ramp_debug_read */

@@ -51,15 +51,15 @@ struct ResampleArgs {
 };
 int launch_resample(const ResampleArgs& a, hipStream_t s);
 
-// first layer: x (B,H,S) -> c1 (R,H,32) [conv k5] and res (R,H,32) [1x1], row r reads x[r / n_rp]
-int launch_conv_in_fwd(const float* x, const float* W5 /*[5][S][32]*/, const float* b5, const float* W1 /*[S][32]*/,
-                       const float* b1, float* c1, float* res, int R, int n_rp, int H, int S, hipStream_t s);
+// first layer: x (B,H,S) -> c1 (R,H,C0) [conv k5] and res (R,H,C0) [1x1], row r reads x[r / n_rp]; C0 in {16, 32, 64}
+int launch_conv_in_fwd(const float* x, const float* W5 /*[5][S][C0]*/, const float* b5, const float* W1 /*[S][C0]*/,
+                       const float* b1, float* c1, float* res, int R, int n_rp, int H, int S, hipStream_t s, int C0 = 32);
 // eps[r,l,s] = sum_j sum_c dc1[r,l-j+2,c] W5[j][s][c] + sum_c dy[r,l,c] W1[s][c]
 int launch_conv_in_bwd(const float* dc1, const float* dy, const float* W5, const float* W1, float* eps,
-                       int R, int H, int S, hipStream_t s);
+                       int R, int H, int S, hipStream_t s, int C0 = 32);
 // last layer: f = a Wf^T + bf (R*H, S); da = f Wf  (the seed of the energy gradient: dE/df = f)
-int launch_conv_out(const float* a, const float* Wf /*[S][32]*/, const float* bf, float* f, float* da,
-                    int n_tok, int S, hipStream_t s);
+int launch_conv_out(const float* a, const float* Wf /*[S][C0]*/, const float* bf, float* f, float* da,
+                    int n_tok, int S, hipStream_t s, int C0 = 32);
 
 // ---- setup kernels --------------------------------------------------------------------------
 // time-bias table: tb[t][off_i + c] = Wc_i silu(temb(t)) + bc_i for every RTB i, t in [0,T)

@@ -48,7 +48,7 @@ struct RTB {
   ConvW c1, c2;
   float *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
   float *res_f = nullptr, *res_b = nullptr, *res_bias = nullptr;   // [Cout][Cin], [Cin][Cout]
-  float *w5in = nullptr, *w1in = nullptr;                           // first layer packed [5][S][32], [S][32]
+  float *w5in = nullptr, *w1in = nullptr;                           // first layer packed [5][S][C0], [S][C0]
   // activations (capacity rows)
   float *a_c1 = nullptr, *a_st1 = nullptr, *a_h = nullptr, *a_c2 = nullptr, *a_st2 = nullptr, *a_out = nullptr;
 };
@@ -271,9 +271,9 @@ int build_rtb(ramp_ctx* c, RTB& r) {
     float* raw;
     CK(get_raw(c, n + ".blocks.0.block.0.weight", {r.cout, r.cin, 5}, &raw));
     CK(get_raw(c, n + ".blocks.0.block.0.bias", {r.cout}, &r.c1.bias));
-    CK(permute3(c, raw, r.cout, r.cin, 5, 2, 1, 0, &r.w5in));            // [5][S][32]
+    CK(permute3(c, raw, r.cout, r.cin, 5, 2, 1, 0, &r.w5in));            // [5][S][C0]
     CK(get_raw(c, n + ".residual_conv.weight", {r.cout, r.cin, 1}, &raw));
-    CK(permute3(c, raw, r.cout, r.cin, 1, 2, 1, 0, &r.w1in));            // [1][S][32]
+    CK(permute3(c, raw, r.cout, r.cin, 1, 2, 1, 0, &r.w1in));            // [1][S][C0]
     CK(get_raw(c, n + ".residual_conv.bias", {r.cout}, &r.res_bias));
     r.c1.cin = r.cin; r.c1.cout = r.cout;
   } else {
@@ -350,7 +350,7 @@ struct Run {
   // attach the split-precision weight planes and the delayed-scaling slots of the next call site; returns 2 when the launch
   // will run the fp16x3 fragment kernels, 1 for bf16x6 fragments, 0 otherwise (< 0: error)
   int prep(GemmArgs& b) {
-    if (!(c->gemm_mode >= 1 && (b.N >= 128 || (c->x6_pipe && b.N >= 64)))) return 0;
+    if (!(c->gemm_mode >= 1 && (b.N >= 128 || (c->x6_pipe && b.N >= 64)) && b.K % 32 == 0)) return 0;      // (K = 16: the narrow fp32 kernel, no planes)
     auto it = c->x6.upper_bound(b.W);
     if (it == c->x6.begin()) return 0;
     --it;
@@ -406,7 +406,8 @@ struct Run {
     c->launches++;
     return rc;
   }
-  // a wide k = 5 convolution (C_out in {128, 256, 512}) with its GroupNorm fused (tkw.hip): forward = GroupNorm + Mish behind it (epi),
+  // a wide k = 5 convolution (forward: C_out in {128, 256, 512}, C_in up to 1024 from two sources; input gradient: outputs up to 1024)
+  // with its GroupNorm fused (tkw.hip): forward = GroupNorm + Mish behind it (epi),
   // input gradient = GroupNorm backward folded into the operand (pro); consumes the call site of the tile launch it replaces
   bool use_tkw(const GemmArgs& a, bool pro, bool epi) const {
     return c->tkw_min_rows > 0 && a.M >= c->tkw_min_rows && c->gemm_mode == 2 && c->phase == 2 && !c->force_x6 && c->x6_pipe && a.taps == 5 && !a.Amul &&
@@ -432,6 +433,13 @@ struct Run {
     return rc;
   }
   int gemm(const GemmArgs& a) {
+    if (a.K % 32 != 0) {      // 16-wide operands (unet_input_dim = 16): exact fp32 narrow kernel, no weight planes, no call site
+      prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, a.taps});
+      int rc = launch_gemm(a, s);
+      prof_post(c, s);
+      c->launches++;
+      return rc;
+    }
     if (const ramp_ctx::TkcW* w = tkc_planes(a)) return tkc(a, *w);
     prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, a.taps});
     GemmArgs b = a;
@@ -610,7 +618,7 @@ int rtb_forward(Run& r, RTB& m, const float* xa, int ca, const float* xb, int cb
   const float* resid;
   bool fused1 = false;
   if (m.first) {
-    LAUNCH(c, r.s, CAT_SMALLCONV, 0, launch_conv_in_fwd(x_first, m.w5in, m.c1.bias, m.w1in, m.res_bias, m.a_c1, c->t_res, R, n_rp, m.L, m.cin, r.s));
+    LAUNCH(c, r.s, CAT_SMALLCONV, 0, launch_conv_in_fwd(x_first, m.w5in, m.c1.bias, m.w1in, m.res_bias, m.a_c1, c->t_res, R, n_rp, m.L, m.cin, r.s, m.cout));
     resid = c->t_res;
   } else {
     GemmArgs a = conv5(xa, ca, m.c1.fwd, m.c1.bias, m.a_c1, m.cout, M, m.cout, m.cin, m.L, false);
@@ -680,7 +688,7 @@ int rtb_backward(Run& r, RTB& m, const float* dy, float* dxa, int ca, float* dxb
   g.dy = c->g_t2; g.x = m.a_c1; g.stats = m.a_st1; g.gamma = m.g1; g.beta = m.b1; g.dx = c->g_t1;
   if (m.first) {
     LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_bwd(g, r.s));                                                   // dc1
-    LAUNCH(c, r.s, CAT_SMALLCONV, 0, launch_conv_in_bwd(c->g_t1, dy, m.w5in, m.w1in, eps_out, R, m.L, m.cin, r.s));
+    LAUNCH(c, r.s, CAT_SMALLCONV, 0, launch_conv_in_bwd(c->g_t1, dy, m.w5in, m.w1in, eps_out, R, m.L, m.cin, r.s, m.cout));
     return 0;
   }
   const float* resid; int ldr;
@@ -899,7 +907,7 @@ int net_forward(ramp_ctx* c, const float* x_chunk, int row0, int R, int n_rp, in
   g.R = R; g.L = H; g.C = C0; g.eps = 1e-5f; g.mish = 1;
   LAUNCH(c, s, CAT_ROW, 0, launch_gn_fwd(g, s));
   }
-  LAUNCH(c, s, CAT_SMALLCONV, 0, launch_conv_out(c->a_fin_a, c->fin_w, c->fin_bias, f_out, want_grad ? c->a_fin_da : nullptr, M, c->cfg.state_dim, s));
+  LAUNCH(c, s, CAT_SMALLCONV, 0, launch_conv_out(c->a_fin_a, c->fin_w, c->fin_bias, f_out, want_grad ? c->a_fin_da : nullptr, M, c->cfg.state_dim, s, C0));
   return 0;
 }
 
@@ -1150,8 +1158,8 @@ int ramp_version(void) { return 1; }
 int ramp_create(const ramp_config* cfg, ramp_ctx** out) {
   RAMP_REQUIRE(cfg && out, "null argument");
   RAMP_REQUIRE(cfg->state_dim >= 2 && cfg->state_dim <= 16, "state_dim out of range");
-  RAMP_REQUIRE(cfg->n_levels == 4, "only UNET_DIM_MULTS[1] = (1,2,4,8) is built");
-  RAMP_REQUIRE(cfg->unet_input_dim == 32, "unet_input_dim must be 32");
+  RAMP_REQUIRE((cfg->n_levels == 3 || cfg->n_levels == 4) && (cfg->unet_input_dim == 16 || cfg->unet_input_dim == 32 || cfg->unet_input_dim == 64),
+               "network shape: n_levels in {3, 4} (UNET_DIM_MULTS[0] = (1,2,4), [1] = (1,2,4,8)) and unet_input_dim in {16, 32, 64}");
   RAMP_REQUIRE(cfg->horizon >= 8 && cfg->horizon <= 64 && cfg->horizon % 8 == 0, "horizon (n_support_points) must be a multiple of 8 in [8, 64] (three stride-2 levels; attention tiles of at most 64 tokens)");
   RAMP_REQUIRE(cfg->context_dim > 0 && cfg->context_dim <= 512, "context_dim out of range");
   RAMP_REQUIRE(cfg->max_rows >= 1, "max_rows must be positive");

@@ -1414,6 +1414,41 @@ int init_gemm_attributes() {
   return set_attr_x6<EPI_GEGLU_BWD, false>();
 }
 
+// =================================================================================================
+// Narrow reduction (K % 32 != 0: the 16-channel operands of a unet_input_dim = 16 network -- its finest-level k = 5
+// convolutions, the input gradients into 16 channels, the transformer's proj_in / d(proj_out)).  The tile kernels stage
+// 32-wide K slabs, so these launches run here instead: exact fp32 FMAs, one float4 of outputs per thread, the same
+// operand / epilogue semantics as the GEN tile kernel (taps with zero padding at segment ends, stride-2 sources, split-K
+// source, split-N / strided destination, bias, row bias, two residuals).  Every such layer is 1-2 % of that network's work.
+// =================================================================================================
+__global__ __launch_bounds__(256) void gemm_narrow_kernel(GemmArgs a) {
+  const int n4 = a.N >> 2;
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)a.M * n4) return;
+  const int m = (int)(idx / n4), n = (int)(idx - (long)m * n4) * 4;
+  const int seg = m / a.L, l = m - seg * a.L;
+  const int Lin = a.L * a.a_stride;
+  f32x4 acc = {0, 0, 0, 0};
+  for (int tap = 0; tap < a.taps; ++tap) {
+    const int ls = l * a.a_stride + a.shift0 + tap * a.shift_step;
+    if (ls < 0 || ls >= Lin) continue;
+    const long src = (long)seg * Lin + ls;
+    const float* w = a.W + ((long)tap * a.N + n) * a.K;
+    for (int k = 0; k < a.K; ++k) {
+      const float x = k < a.K1 ? a.A[src * a.lda + k] : a.A2[src * a.lda2 + (k - a.K1)];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] += x * w[(long)j * a.K + k];
+    }
+  }
+  const long orow = (long)m * a.c_rstride + a.c_roff;
+  if (a.bias) acc += *reinterpret_cast<const f32x4*>(a.bias + n);
+  if (a.rowbias) acc += *reinterpret_cast<const f32x4*>(a.rowbias + (long)a.rowvar[a.row0 + m / a.L] * a.rb_stride + n);
+  if (a.resid) acc += *reinterpret_cast<const f32x4*>(a.resid + orow * a.ldr + n);
+  if (a.resid2) acc += *reinterpret_cast<const f32x4*>(a.resid2 + orow * a.ldr2 + n);
+  if (n < a.N1) *reinterpret_cast<f32x4*>(a.C + orow * a.ldc + n) = acc;
+  else *reinterpret_cast<f32x4*>(a.C2 + orow * a.ldc2 + (n - a.N1)) = acc;
+}
+
 int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   GemmArgs a = a_in;
   if (a.A2 == nullptr) a.K1 = a.K;
@@ -1421,6 +1456,18 @@ int launch_gemm(const GemmArgs& a_in, hipStream_t s) {
   if (a.rb_stride == 0) a.rb_stride = a.N;
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   RAMP_REQUIRE(a.M > 0 && a.N > 0 && a.K > 0 && a.taps >= 1 && a.L >= 1, "bad GEMM dims");
+  if (a.K % BK != 0) {
+    RAMP_REQUIRE(a.K % 16 == 0 && a.N % 4 == 0 && a.N1 % 4 == 0 && a.epi == EPI_LINEAR && !a.Amul && a.a_stride >= 1 && a.c_rstride >= 1 &&
+                 (a.A2 == nullptr || a.K1 > 0) && (a.C2 == nullptr || a.N1 > 0),
+                 "narrow GEMM (K % 32 != 0): K a multiple of 16, N and N1 multiples of 4, linear epilogue only");
+    RAMP_REQUIRE(al16(a.C) && al16(a.C2) && al16(a.resid) && al16(a.resid2) && al16(a.bias) && al16(a.rowbias) &&
+                 a.ldc % 4 == 0 && a.ldc2 % 4 == 0 && a.ldr % 4 == 0 && a.ldr2 % 4 == 0 && a.rb_stride % 4 == 0 &&
+                 (a.rowbias == nullptr || a.rowvar != nullptr), "narrow GEMM: outputs and epilogue operands must be 16-byte aligned");
+    const long n_out = (long)a.M * (a.N / 4);
+    hipLaunchKernelGGL(gemm_narrow_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, s, a);
+    RAMP_HIP_CHECK(hipGetLastError());
+    return 0;
+  }
   RAMP_REQUIRE(a.K % BK == 0 && a.lda % 4 == 0 && a.N % 4 == 0 && a.N1 % 4 == 0,
                "K must be a multiple of 32, N, N1 and lda multiples of 4 floats");
   RAMP_REQUIRE(a.A2 == nullptr || (a.lda2 % 4 == 0 && a.K1 % BK == 0), "split-K source must start on a K tile");

@@ -5,8 +5,8 @@
 //   GEGLU fwd / dX                                     layers_attention_mini.py:38-45
 //   (4x64 softmax self-attention lives in attention.hip)
 //   Downsample1d / Upsample1d fwd / dX                 layers.py:262-277
-//   first conv (S -> 32, k5 + 1x1 residual) fwd / dX   layers.py:337-361 for downs.0.0
-//   last conv (32 -> S, 1x1) fwd + energy-gradient seed  UnetInference.py:142-145, 26-27
+//   first conv (S -> C0, k5 + 1x1 residual) fwd / dX   layers.py:337-361 for downs.0.0
+//   last conv (C0 -> S, 1x1) fwd + energy-gradient seed  UnetInference.py:142-145, 26-27
 //
 // All reductions are deterministic (fixed shuffle / LDS trees, no float atomics).
 #include "args_rows.h"
@@ -45,16 +45,24 @@ __device__ __forceinline__ float gelu_grad_f(float x) {
 // ------------------------------------------------------------------------------------------
 constexpr int GN_MAXV = 4;   // float4 slots per thread: supports L*C <= 4096
 
+// WIDE (C = 512: a wave's 64 float4 slots cover 4 of the 8 groups): the slots of the groups a wave does not hold read as
+// zero, so every group still sums the same 4 wave partials (two of them exact zeros)
+template <bool WIDE = false>
 __device__ __forceinline__ float group_reduce(float v, int gmask, float* red /*[4][8]*/, int g, int lane, int wave) {
 #pragma unroll
   for (int b = 1; b < 64; b <<= 1)
     if (!(b & gmask)) v += __shfl_xor(v, b);
   __syncthreads();                       // protect red[] reuse
+  if (WIDE) {
+    if (lane < 8) red[wave * 8 + lane] = 0.f;
+    __syncthreads();
+  }
   if ((lane & ~gmask) == 0) red[wave * 8 + g] = v;
   __syncthreads();
   return red[g] + red[8 + g] + red[16 + g] + red[24 + g];
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a) {
   __shared__ float red[32];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -70,7 +78,7 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a) {
     if (e < n4) { v[k] = xr[e]; s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]); }
   }
   const float inv_cnt = 1.f / (float)(a.L * (a.C >> 3));
-  const float mean = group_reduce(s, gmask, red, g, lane, wave) * inv_cnt;
+  const float mean = group_reduce<WIDE>(s, gmask, red, g, lane, wave) * inv_cnt;
   float ss = 0.f;
 #pragma unroll
   for (int k = 0; k < GN_MAXV; ++k) {
@@ -80,7 +88,7 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a) {
       for (int j = 0; j < 4; ++j) { const float d = v[k][j] - mean; ss += d * d; }
     }
   }
-  const float var = group_reduce(ss, gmask, red, g, lane, wave) * inv_cnt;
+  const float var = group_reduce<WIDE>(ss, gmask, red, g, lane, wave) * inv_cnt;
   const float rstd = 1.f / sqrtf(var + a.eps);
   if (a.stats && (tid < C4) && (c4 % cg4 == 0)) {   // one writer per group
     a.stats[((long)row * 8 + g) * 2 + 0] = mean;
@@ -109,6 +117,7 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a) {
   }
 }
 
+template <bool WIDE>
 __global__ __launch_bounds__(256) void gn_bwd_kernel(GnBwdArgs a) {
   __shared__ float red[32];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -141,8 +150,8 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(GnBwdArgs a) {
     }
   }
   const float inv_cnt = 1.f / (float)(a.L * (a.C >> 3));
-  const float m1 = group_reduce(s1, gmask, red, g, lane, wave) * inv_cnt;
-  const float m2 = group_reduce(s2, gmask, red, g, lane, wave) * inv_cnt;
+  const float m1 = group_reduce<WIDE>(s1, gmask, red, g, lane, wave) * inv_cnt;
+  const float m2 = group_reduce<WIDE>(s2, gmask, red, g, lane, wave) * inv_cnt;
   f32x4* dxr = reinterpret_cast<f32x4*>(a.dx + base);
   const f32x4* ar = a.add ? reinterpret_cast<const f32x4*>(a.add + base) : nullptr;
 #pragma unroll
@@ -158,21 +167,147 @@ __global__ __launch_bounds__(256) void gn_bwd_kernel(GnBwdArgs a) {
   }
 }
 
+// C = 16 (the finest level of a unet_input_dim = 16 network): two channels per group, so one float4 slot holds two groups.
+// A thread's slots all sit at channel quad c4 = tid & 3 (groups 2 c4, 2 c4 + 1); the two partial sums are reduced over the
+// lanes of the same quad, then over the 4 waves in LDS.
+__device__ __forceinline__ void group_reduce16(float& lo, float& hi, float* red /*[4][8]*/, int c4, int lane, int wave) {
+#pragma unroll
+  for (int b = 4; b < 64; b <<= 1) { lo += __shfl_xor(lo, b); hi += __shfl_xor(hi, b); }
+  __syncthreads();                       // protect red[] reuse
+  if (lane < 4) { red[wave * 8 + 2 * lane] = lo; red[wave * 8 + 2 * lane + 1] = hi; }
+  __syncthreads();
+  const int g = 2 * c4;
+  lo = red[g] + red[8 + g] + red[16 + g] + red[24 + g];
+  hi = red[g + 1] + red[9 + g] + red[17 + g] + red[25 + g];
+}
+
+__global__ __launch_bounds__(256) void gn_fwd_c16_kernel(GnArgs a) {
+  __shared__ float red[32];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n4 = a.L * 4, c4 = tid & 3;
+  const f32x4* xr = reinterpret_cast<const f32x4*>(a.x + (long)row * a.L * 16);
+  f32x4 v[GN_MAXV];
+  float lo = 0.f, hi = 0.f;
+#pragma unroll
+  for (int k = 0; k < GN_MAXV; ++k) {
+    const int e = tid + 256 * k;
+    if (e < n4) { v[k] = xr[e]; lo += v[k][0] + v[k][1]; hi += v[k][2] + v[k][3]; }
+  }
+  const float inv_cnt = 1.f / (float)(a.L * 2);
+  group_reduce16(lo, hi, red, c4, lane, wave);
+  const float mean_lo = lo * inv_cnt, mean_hi = hi * inv_cnt;
+  float sl = 0.f, sh = 0.f;
+#pragma unroll
+  for (int k = 0; k < GN_MAXV; ++k) {
+    const int e = tid + 256 * k;
+    if (e < n4) {
+      const float d0 = v[k][0] - mean_lo, d1 = v[k][1] - mean_lo, d2 = v[k][2] - mean_hi, d3 = v[k][3] - mean_hi;
+      sl += d0 * d0 + d1 * d1; sh += d2 * d2 + d3 * d3;
+    }
+  }
+  group_reduce16(sl, sh, red, c4, lane, wave);
+  const float rstd_lo = 1.f / sqrtf(sl * inv_cnt + a.eps), rstd_hi = 1.f / sqrtf(sh * inv_cnt + a.eps);
+  if (a.stats && tid < 4) {              // one writer per group
+    a.stats[((long)row * 8 + 2 * c4) * 2 + 0] = mean_lo;
+    a.stats[((long)row * 8 + 2 * c4) * 2 + 1] = rstd_lo;
+    a.stats[((long)row * 8 + 2 * c4 + 1) * 2 + 0] = mean_hi;
+    a.stats[((long)row * 8 + 2 * c4 + 1) * 2 + 1] = rstd_hi;
+  }
+  const f32x4 gam = reinterpret_cast<const f32x4*>(a.gamma)[c4];
+  const f32x4 bet = reinterpret_cast<const f32x4*>(a.beta)[c4];
+  f32x4 tb = {0, 0, 0, 0};
+  if (a.tbias) tb = reinterpret_cast<const f32x4*>(a.tbias)[c4];
+  f32x4* yr = reinterpret_cast<f32x4*>(a.y + (long)row * a.L * 16);
+  const f32x4* rr = a.resid ? reinterpret_cast<const f32x4*>(a.resid + (long)row * a.L * 16) : nullptr;
+#pragma unroll
+  for (int k = 0; k < GN_MAXV; ++k) {
+    const int e = tid + 256 * k;
+    if (e < n4) {
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float mean = j < 2 ? mean_lo : mean_hi, rstd = j < 2 ? rstd_lo : rstd_hi;
+        float n = (v[k][j] - mean) * rstd * gam[j] + bet[j];
+        if (a.mish) n = mish_f(n);
+        o[j] = n + tb[j];
+      }
+      if (rr) { const f32x4 q = rr[e]; o += q; }
+      yr[e] = o;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void gn_bwd_c16_kernel(GnBwdArgs a) {
+  __shared__ float red[32];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n4 = a.L * 4, c4 = tid & 3;
+  const long base = (long)row * a.L * 16;
+  const f32x4* xr = reinterpret_cast<const f32x4*>(a.x + base);
+  const f32x4* dyr = reinterpret_cast<const f32x4*>(a.dy + base);
+  float mean[2], rstd[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    mean[q] = a.stats[((long)row * 8 + 2 * c4 + q) * 2 + 0];
+    rstd[q] = a.stats[((long)row * 8 + 2 * c4 + q) * 2 + 1];
+  }
+  const f32x4 gam = reinterpret_cast<const f32x4*>(a.gamma)[c4];
+  const f32x4 bet = reinterpret_cast<const f32x4*>(a.beta)[c4];
+  f32x4 xh[GN_MAXV], gq[GN_MAXV];
+  float s1l = 0.f, s1h = 0.f, s2l = 0.f, s2h = 0.f;
+#pragma unroll
+  for (int k = 0; k < GN_MAXV; ++k) {
+    const int e = tid + 256 * k;
+    if (e < n4) {
+      const f32x4 xv = xr[e], dv = dyr[e];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float h = (xv[j] - mean[j >> 1]) * rstd[j >> 1];
+        float d = dv[j];
+        if (a.mish) d *= mish_grad_f(h * gam[j] + bet[j]);
+        d *= gam[j];
+        xh[k][j] = h; gq[k][j] = d;
+        if (j < 2) { s1l += d; s2l += d * h; } else { s1h += d; s2h += d * h; }
+      }
+    }
+  }
+  const float inv_cnt = 1.f / (float)(a.L * 2);
+  group_reduce16(s1l, s1h, red, c4, lane, wave);
+  group_reduce16(s2l, s2h, red, c4, lane, wave);
+  const float m1[2] = {s1l * inv_cnt, s1h * inv_cnt}, m2[2] = {s2l * inv_cnt, s2h * inv_cnt};
+  f32x4* dxr = reinterpret_cast<f32x4*>(a.dx + base);
+  const f32x4* ar = a.add ? reinterpret_cast<const f32x4*>(a.add + base) : nullptr;
+#pragma unroll
+  for (int k = 0; k < GN_MAXV; ++k) {
+    const int e = tid + 256 * k;
+    if (e < n4) {
+      f32x4 o;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) o[j] = (gq[k][j] - m1[j >> 1] - xh[k][j] * m2[j >> 1]) * rstd[j >> 1];
+      if (ar) { const f32x4 q = ar[e]; o += q; }
+      dxr[e] = o;
+    }
+  }
+}
+
 static int gn_check(int R, int L, int C) {
   RAMP_REQUIRE(R > 0 && L > 0, "empty GroupNorm");
-  RAMP_REQUIRE(C == 32 || C == 64 || C == 128 || C == 256, "GroupNorm kernel supports C in {32,64,128,256} (8 groups)");
+  RAMP_REQUIRE(C == 16 || C == 32 || C == 64 || C == 128 || C == 256 || C == 512, "GroupNorm kernel supports C in {16,32,64,128,256,512} (8 groups)");
   RAMP_REQUIRE(L * C <= GN_MAXV * 1024, "row too long for the GroupNorm kernel (L*C <= 4096)");
   return 0;
 }
 int launch_gn_fwd(const GnArgs& a, hipStream_t s) {
   if (int e = gn_check(a.R, a.L, a.C)) return e;
-  hipLaunchKernelGGL(gn_fwd_kernel, dim3(a.R), dim3(256), 0, s, a);
+  if (a.C == 16) hipLaunchKernelGGL(gn_fwd_c16_kernel, dim3(a.R), dim3(256), 0, s, a);
+  else if (a.C == 512) hipLaunchKernelGGL(gn_fwd_kernel<true>, dim3(a.R), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(gn_fwd_kernel<false>, dim3(a.R), dim3(256), 0, s, a);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
 int launch_gn_bwd(const GnBwdArgs& a, hipStream_t s) {
   if (int e = gn_check(a.R, a.L, a.C)) return e;
-  hipLaunchKernelGGL(gn_bwd_kernel, dim3(a.R), dim3(256), 0, s, a);
+  if (a.C == 16) hipLaunchKernelGGL(gn_bwd_c16_kernel, dim3(a.R), dim3(256), 0, s, a);
+  else if (a.C == 512) hipLaunchKernelGGL(gn_bwd_kernel<true>, dim3(a.R), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(gn_bwd_kernel<false>, dim3(a.R), dim3(256), 0, s, a);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -383,60 +518,66 @@ int launch_resample(const ResampleArgs& a, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------
-// first conv block input (Cin = S in [2, 16], ramp_create's range: too thin for the MFMA GEMM's float4 staging)
+// first conv block input (Cin = S in [2, 16], ramp_create's range: too thin for the MFMA GEMM's float4 staging),
+// C0 = unet_input_dim output channels
 // ------------------------------------------------------------------------------------------
+template <int C0>
 __global__ __launch_bounds__(256) void conv_in_fwd_kernel(const float* __restrict__ x, const float* __restrict__ W5,
                                                            const float* __restrict__ b5, const float* __restrict__ W1,
                                                            const float* __restrict__ b1, float* __restrict__ c1,
                                                            float* __restrict__ res, int n_rp, int H, int S) {
   extern __shared__ float sm[];
   float* xs = sm;                 // H*S
-  float* w5 = xs + H * S;         // 5*S*32
-  float* w1 = w5 + 5 * S * 32;    // S*32
+  float* w5 = xs + H * S;         // 5*S*C0
+  float* w1 = w5 + 5 * S * C0;    // S*C0
   const int row = blockIdx.x;
   const float* xr = x + (long)(row / n_rp) * H * S;
   for (int e = threadIdx.x; e < H * S; e += 256) xs[e] = xr[e];
-  for (int e = threadIdx.x; e < 5 * S * 32; e += 256) w5[e] = W5[e];
-  for (int e = threadIdx.x; e < S * 32; e += 256) w1[e] = W1[e];
+  for (int e = threadIdx.x; e < 5 * S * C0; e += 256) w5[e] = W5[e];
+  for (int e = threadIdx.x; e < S * C0; e += 256) w1[e] = W1[e];
   __syncthreads();
-  for (int idx = threadIdx.x; idx < H * 32; idx += 256) {
-    const int l = idx >> 5, co = idx & 31;
+  for (int idx = threadIdx.x; idx < H * C0; idx += 256) {
+    const int l = idx / C0, co = idx % C0;
     float acc = 0.f;
     for (int j = 0; j < 5; ++j) {
       const int src = l + j - 2;
       if (src < 0 || src >= H) continue;
-      for (int si = 0; si < S; ++si) acc += xs[src * S + si] * w5[(j * S + si) * 32 + co];
+      for (int si = 0; si < S; ++si) acc += xs[src * S + si] * w5[(j * S + si) * C0 + co];
     }
     float r = 0.f;
-    for (int si = 0; si < S; ++si) r += xs[l * S + si] * w1[si * 32 + co];
-    c1[(long)row * H * 32 + idx] = acc + b5[co];
-    res[(long)row * H * 32 + idx] = r + b1[co];
+    for (int si = 0; si < S; ++si) r += xs[l * S + si] * w1[si * C0 + co];
+    c1[(long)row * H * C0 + idx] = acc + b5[co];
+    res[(long)row * H * C0 + idx] = r + b1[co];
   }
 }
 int launch_conv_in_fwd(const float* x, const float* W5, const float* b5, const float* W1, const float* b1, float* c1,
-                       float* res, int R, int n_rp, int H, int S, hipStream_t s) {
+                       float* res, int R, int n_rp, int H, int S, hipStream_t s, int C0) {
   RAMP_REQUIRE(R > 0 && n_rp > 0 && H > 0 && S > 0 && S <= 16, "bad conv_in dims");
-  const size_t lds = (size_t)(H * S + 6 * S * 32) * sizeof(float);
-  hipLaunchKernelGGL(conv_in_fwd_kernel, dim3(R), dim3(256), lds, s, x, W5, b5, W1, b1, c1, res, n_rp, H, S);
+  RAMP_REQUIRE(C0 == 16 || C0 == 32 || C0 == 64, "conv_in: C0 in {16, 32, 64}");
+  const size_t lds = (size_t)(H * S + 6 * S * C0) * sizeof(float);
+  if (C0 == 16) hipLaunchKernelGGL(conv_in_fwd_kernel<16>, dim3(R), dim3(256), lds, s, x, W5, b5, W1, b1, c1, res, n_rp, H, S);
+  else if (C0 == 32) hipLaunchKernelGGL(conv_in_fwd_kernel<32>, dim3(R), dim3(256), lds, s, x, W5, b5, W1, b1, c1, res, n_rp, H, S);
+  else hipLaunchKernelGGL(conv_in_fwd_kernel<64>, dim3(R), dim3(256), lds, s, x, W5, b5, W1, b1, c1, res, n_rp, H, S);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
+template <int C0>
 __global__ __launch_bounds__(256) void conv_in_bwd_kernel(const float* __restrict__ dc1, const float* __restrict__ dy,
                                                            const float* __restrict__ W5, const float* __restrict__ W1,
                                                            float* __restrict__ eps, int H, int S) {
   extern __shared__ float sm[];
-  float* d1 = sm;                 // H*32
-  float* d2 = d1 + H * 32;        // H*32
-  float* w5 = d2 + H * 32;        // 5*S*32
-  float* w1 = w5 + 5 * S * 32;    // S*32
+  float* d1 = sm;                 // H*C0
+  float* d2 = d1 + H * C0;        // H*C0
+  float* w5 = d2 + H * C0;        // 5*S*C0
+  float* w1 = w5 + 5 * S * C0;    // S*C0
   const int row = blockIdx.x;
-  for (int e = threadIdx.x; e < H * 32; e += 256) {
-    d1[e] = dc1[(long)row * H * 32 + e];
-    d2[e] = dy[(long)row * H * 32 + e];
+  for (int e = threadIdx.x; e < H * C0; e += 256) {
+    d1[e] = dc1[(long)row * H * C0 + e];
+    d2[e] = dy[(long)row * H * C0 + e];
   }
-  for (int e = threadIdx.x; e < 5 * S * 32; e += 256) w5[e] = W5[e];
-  for (int e = threadIdx.x; e < S * 32; e += 256) w1[e] = W1[e];
+  for (int e = threadIdx.x; e < 5 * S * C0; e += 256) w5[e] = W5[e];
+  for (int e = threadIdx.x; e < S * C0; e += 256) w1[e] = W1[e];
   __syncthreads();
   for (int idx = threadIdx.x; idx < H * S; idx += 256) {
     const int l = idx / S, si = idx - l * S;
@@ -444,60 +585,69 @@ __global__ __launch_bounds__(256) void conv_in_bwd_kernel(const float* __restric
     for (int j = 0; j < 5; ++j) {
       const int src = l - j + 2;
       if (src < 0 || src >= H) continue;
-      for (int c = 0; c < 32; ++c) acc += d1[src * 32 + c] * w5[(j * S + si) * 32 + c];
+      for (int c = 0; c < C0; ++c) acc += d1[src * C0 + c] * w5[(j * S + si) * C0 + c];
     }
-    for (int c = 0; c < 32; ++c) acc += d2[l * 32 + c] * w1[si * 32 + c];
+    for (int c = 0; c < C0; ++c) acc += d2[l * C0 + c] * w1[si * C0 + c];
     eps[(long)row * H * S + idx] = acc;
   }
 }
 int launch_conv_in_bwd(const float* dc1, const float* dy, const float* W5, const float* W1, float* eps, int R, int H,
-                       int S, hipStream_t s) {
+                       int S, hipStream_t s, int C0) {
   RAMP_REQUIRE(R > 0 && H > 0 && S > 0 && S <= 16, "bad conv_in dims");
-  const size_t lds = (size_t)(2 * H * 32 + 6 * S * 32) * sizeof(float);
-  hipLaunchKernelGGL(conv_in_bwd_kernel, dim3(R), dim3(256), lds, s, dc1, dy, W5, W1, eps, H, S);
+  RAMP_REQUIRE(C0 == 16 || C0 == 32 || C0 == 64, "conv_in: C0 in {16, 32, 64}");
+  const size_t lds = (size_t)(2 * H * C0 + 6 * S * C0) * sizeof(float);      // <= 56 KB (H = 64, S = 16, C0 = 64)
+  if (C0 == 16) hipLaunchKernelGGL(conv_in_bwd_kernel<16>, dim3(R), dim3(256), lds, s, dc1, dy, W5, W1, eps, H, S);
+  else if (C0 == 32) hipLaunchKernelGGL(conv_in_bwd_kernel<32>, dim3(R), dim3(256), lds, s, dc1, dy, W5, W1, eps, H, S);
+  else hipLaunchKernelGGL(conv_in_bwd_kernel<64>, dim3(R), dim3(256), lds, s, dc1, dy, W5, W1, eps, H, S);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 // last 1x1 conv + seed of the energy gradient (E = 0.5 sum f^2  =>  dE/df = f)
+template <int C0>
 __global__ __launch_bounds__(256) void conv_out_kernel(const float* __restrict__ a, const float* __restrict__ Wf,
                                                         const float* __restrict__ bf, float* __restrict__ f,
                                                         float* __restrict__ da, int n_tok, int S) {
-  __shared__ float w[16 * 32];
+  constexpr int Q = C0 / 4;
+  __shared__ float w[16 * C0];
   __shared__ float b[16];
-  for (int e = threadIdx.x; e < S * 32; e += 256) w[e] = Wf[e];
+  for (int e = threadIdx.x; e < S * C0; e += 256) w[e] = Wf[e];
   if (threadIdx.x < S) b[threadIdx.x] = bf[threadIdx.x];
   __syncthreads();
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
   if (t >= n_tok) return;
-  f32x4 av[8];
+  f32x4 av[Q];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) av[q] = reinterpret_cast<const f32x4*>(a + t * 32)[q];
+  for (int q = 0; q < Q; ++q) av[q] = reinterpret_cast<const f32x4*>(a + t * C0)[q];
   float fv[16];
   for (int si = 0; si < S; ++si) {
     float acc = 0.f;
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
+    for (int q = 0; q < Q; ++q)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) acc += av[q][e] * w[si * 32 + q * 4 + e];
+      for (int e = 0; e < 4; ++e) acc += av[q][e] * w[si * C0 + q * 4 + e];
     fv[si] = acc + b[si];
     if (f) f[t * S + si] = fv[si];
   }
   if (da) {
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
+    for (int q = 0; q < Q; ++q) {
       f32x4 o = {0, 0, 0, 0};
       for (int si = 0; si < S; ++si)
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] += fv[si] * w[si * 32 + q * 4 + e];
-      reinterpret_cast<f32x4*>(da + t * 32)[q] = o;
+        for (int e = 0; e < 4; ++e) o[e] += fv[si] * w[si * C0 + q * 4 + e];
+      reinterpret_cast<f32x4*>(da + t * C0)[q] = o;
     }
   }
 }
 int launch_conv_out(const float* a, const float* Wf, const float* bf, float* f, float* da, int n_tok, int S,
-                    hipStream_t s) {
+                    hipStream_t s, int C0) {
   RAMP_REQUIRE(n_tok > 0 && S > 0 && S <= 16, "bad conv_out dims");
-  hipLaunchKernelGGL(conv_out_kernel, dim3((n_tok + 255) / 256), dim3(256), 0, s, a, Wf, bf, f, da, n_tok, S);
+  RAMP_REQUIRE(C0 == 16 || C0 == 32 || C0 == 64, "conv_out: C0 in {16, 32, 64}");
+  const dim3 grid((n_tok + 255) / 256);
+  if (C0 == 16) hipLaunchKernelGGL(conv_out_kernel<16>, grid, dim3(256), 0, s, a, Wf, bf, f, da, n_tok, S);
+  else if (C0 == 32) hipLaunchKernelGGL(conv_out_kernel<32>, grid, dim3(256), 0, s, a, Wf, bf, f, da, n_tok, S);
+  else hipLaunchKernelGGL(conv_out_kernel<64>, grid, dim3(256), 0, s, a, Wf, bf, f, da, n_tok, S);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -18,8 +18,10 @@
 //     whole sample, so mean / variance (two passes over the accumulators, like gn_fwd_kernel) never leave the wave;
 //   * the GroupNorm BACKWARD is folded into the operand staging of the input-gradient convolution: a wave stages whole samples
 //     (24 tokens = 24 / L samples), the two sums of the backward formula are in-wave shuffles.
-// Operand channels beyond 256 are staged in chunks (K = 512: the concatenated input of ups.0.0, two sources); outputs beyond 128 MB channels
-// run as passes over the same staged tile (N = 512: the split input gradient of ups.0.0).
+// Operand channels beyond 256 are staged in chunks (K = 512 / 1024: the concatenated input of ups.0.0, two sources); outputs beyond 256
+// channels run as passes of 256 over the same staged tile (N = 512 / 1024: the split input gradient of ups.0.0; EPI 2: the 512-channel
+// forward of downs.3, mid_block1/2 at unet_input_dim = 64 -- a pass holds whole 64-channel groups, one per wave, so the statistics stay
+// per pass, and the epilogue's parameter table is reloaded for each pass).
 // fp16x3 products, delayed operand scale / recorded maximum / range guard of ONE call site, like every other GEMM of the library.
 #include "args_conv.h"
 #include "tokmma.h"
@@ -32,7 +34,7 @@ namespace {
 
 constexpr int TW_TB = 96;                                   // tokens of a block tile
 constexpr int TW_NT = 3;                                    // = 32-token groups (the B operand's columns)
-constexpr int TW_SCRATCH = 4096 + 4 * 1024;                 // behind the tile: 1 KB per wave + bias / gamma / beta / time bias of <= 256 channels
+constexpr int TW_SCRATCH = 4096 + 4 * 1024;                 // behind the tile: 1 KB per wave + bias / gamma / beta / time bias of the pass's <= 256 channels
 
 __device__ __forceinline__ float tw_mish(float x) {         // rowops.hip mish_f: x n / (n + 2), n = e (e + 2), e = exp(x)
   const float e = __builtin_amdgcn_exp2f(fminf(x, 20.f) * 1.44269504088896340736f);
@@ -56,8 +58,9 @@ struct TwGeom { int KC, n_chunks, rows, xrow, n_pass; size_t lds; };
 
 }  // namespace
 
-// MB: 32-channel blocks of a wave per pass (1: N = 128, 2: N = 256 / 512); PRO > 0: GroupNorm backward folded into the operand, PRO = the wave
-// instructions of RP rows of one staging pass (3, 4, 6, 8: whole samples); EPI 1: GroupNorm + Mish behind the convolution
+// MB: 32-channel blocks of a wave per pass (1: N = 128, 2: N = 256 / 512 / 1024); PRO > 0: GroupNorm backward folded into the operand, PRO = the
+// wave instructions of RP rows of one staging pass (3, 4, 6, 8: whole samples); EPI 1: GroupNorm + Mish behind the convolution (N <= 256: a group
+// is one 32-channel block or half of one); EPI 2: the same at N = 512 (two passes of 256; a group = the wave's 64 channels of the pass)
 template <int MB, int PRO, int EPI>
 __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -80,12 +83,14 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
 
   // the tile's padding rows are zeroed once and never written again
   for (int i = tid; i < n_rows * XROW / 16; i += 256) reinterpret_cast<u32x4*>(smem)[i] = u32x4{0u, 0u, 0u, 0u};
-  float* const prm = reinterpret_cast<float*>(scr + 4096);  // EPI 1: [bias | gamma | beta | time bias] of the N <= 256 channels
-  if (EPI == 1) {
-    for (int i = tid; i < a.N; i += 256) {
-      prm[i] = a.bias[i]; prm[256 + i] = a.gamma[i]; prm[512 + i] = a.beta[i]; prm[768 + i] = a.tbias ? a.tbias[i] : 0.f;
+  float* const prm = reinterpret_cast<float*>(scr + 4096);  // EPI: [bias | gamma | beta | time bias] of the pass's <= 256 channels
+  auto load_prm = [&](int c0) __attribute__((always_inline)) {
+    for (int i = tid; i < min(a.N, 256); i += 256) {
+      const int c = c0 + i;
+      prm[i] = a.bias[c]; prm[256 + i] = a.gamma[c]; prm[512 + i] = a.beta[c]; prm[768 + i] = a.tbias ? a.tbias[c] : 0.f;
     }
-  }
+  };
+  if (EPI >= 1) load_prm(0);
   __syncthreads();
 
   // B-operand rows of this lane's tokens: token t = 32 tg + tok sits in row t + 2 (t / L) + 2
@@ -114,6 +119,8 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
 #pragma unroll 1
       for (int kc = 0; kc < n_chunks; ++kc) {
         if (pass > 0 || kc > 0 || tile != (int)blockIdx.x) __syncthreads();      // every wave is done reading the tile
+        // EPI 2: this pass's parameters (every wave is past the previous pass's epilogue; visible after the barrier behind the staging)
+        if (EPI == 2 && kc == 0 && (pass > 0 || tile != (int)blockIdx.x)) load_prm(pass * 256);
         if (n_chunks > 1 || pass == 0) {
           // ---- staging: the wave's 24 tokens x KC channels -> (optionally GroupNorm-backward) -> maximum, two scaled fp16 planes -> tile
           const int ch = kc * KC + 4 * sl;                  // this lane's four channels
@@ -324,8 +331,10 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
         }
       } else {
         // c = acc os + bias (the stash); GroupNorm statistics per (sample, group): a group (N / 8 channels) is one 32-channel block
-        // (N = 256) or half of one (N = 128: registers 0..7 / 8..15), always inside this wave's slice
-        constexpr int NGW = 2;                               // groups of this wave's slice
+        // (N = 256), half of one (N = 128: registers 0..7 / 8..15) or both blocks of the wave's pass (N = 512, EPI 2), always inside this
+        // wave's slice
+        constexpr int NGW = EPI == 2 ? 1 : 2;                // groups of this wave's slice
+        const int poff = EPI == 2 ? pass * 256 : 0;          // first channel of the pass = prm's channel 0
         const int gsz = a.N >> 3;                            // channels of a group: 32 (MB = 2) or 16 (MB = 1)
         const int n_smp = TW_TB / a.L;
         const float inv_cnt = 1.f / (float)(a.L * gsz);
@@ -333,7 +342,7 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const f32x4 b4 = *reinterpret_cast<const f32x4*>(prm + nb0 + 32 * mb + 8 * q + 4 * kh);
+            const f32x4 b4 = *reinterpret_cast<const f32x4*>(prm + nb0 - poff + 32 * mb + 8 * q + 4 * kh);
 #pragma unroll
             for (int tg = 0; tg < TW_NT; ++tg)
 #pragma unroll
@@ -350,7 +359,7 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
             for (int q = 0; q < 4; ++q)
               if (t < a.M && !(a.ablate & 4)) *reinterpret_cast<f32x4*>(a.Cst + (size_t)tk * a.N + nb0 + 32 * mb + 8 * q + 4 * kh) = quad(acc[mb][tg], q);
         }
-        // group gi of the wave: MB = 2 -> block gi, all 16 registers; MB = 1 -> block 0, registers 8 gi .. 8 gi + 7
+        // group gi of the wave: EPI 2 -> both blocks; MB = 2 -> block gi, all 16 registers; MB = 1 -> block 0, registers 8 gi .. 8 gi + 7
         float mean_t[NGW][TW_NT], rstd_t[NGW][TW_NT];
         float my_mean = 0.f, my_var = 0.f;                   // of the (group, sample) this lane sums (lane < NGW n_smp)
 #pragma unroll
@@ -360,11 +369,21 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
 #pragma unroll
             for (int tg = 0; tg < TW_NT; ++tg) {
               float s = 0.f;
+              if constexpr (EPI == 2) {
+#pragma unroll
+                for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+                  for (int i = 0; i < 16; ++i) {
+                    const float d = rnd == 0 ? acc[mb][tg][i] : acc[mb][tg][i] - mean_t[gi][tg];
+                    s += rnd == 0 ? d : d * d;
+                  }
+              } else {
 #pragma unroll
               for (int i = 0; i < (MB == 2 ? 16 : 8); ++i) {
                 const float c = MB == 2 ? acc[gi][tg][i] : acc[0][tg][8 * gi + i];
                 const float d = rnd == 0 ? c : c - mean_t[gi][tg];
                 s += rnd == 0 ? d : d * d;
+              }
               }
               s += __shfl_xor(s, 32);
               if (kh == 0) wscr[gi * TW_TB + 32 * tg + tok] = s;      // per-token sums of the group
@@ -391,7 +410,7 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
         if (lane < NGW * n_smp) {                            // statistics for the backward pass: (sample, group) -> mean, rstd
           const int gi = lane / n_smp, sm = lane - gi * n_smp;
           if (tok0 + sm * a.L < a.M) {
-            const int g = (nb0 >> 5) * (MB == 2 ? 1 : 2) + gi;                             // the group's index among the 8
+            const int g = EPI == 2 ? (nb0 >> 6) : (nb0 >> 5) * (MB == 2 ? 1 : 2) + gi;    // the group's index among the 8
             float* st = a.stats + ((size_t)(tok0 / a.L + sm) * 8 + g) * 2;
             st[0] = my_mean; st[1] = 1.f / sqrtf(my_var + a.eps);
           }
@@ -406,12 +425,12 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
               const int n = nb0 + 32 * mb + 8 * q + 4 * kh;
-              const int gi = MB == 2 ? mb : (q >> 1);
-              const f32x4 gam = *reinterpret_cast<const f32x4*>(prm + 256 + n), bet = *reinterpret_cast<const f32x4*>(prm + 512 + n);
+              const int gi = EPI == 2 ? 0 : MB == 2 ? mb : (q >> 1);
+              const f32x4 gam = *reinterpret_cast<const f32x4*>(prm + 256 + n - poff), bet = *reinterpret_cast<const f32x4*>(prm + 512 + n - poff);
               f32x4 v;
 #pragma unroll
               for (int j = 0; j < 4; ++j) v[j] = tw_mish((acc[mb][tg][4 * q + j] - mean_t[gi][tg]) * rstd_t[gi][tg] * gam[j] + bet[j]);
-              v += *reinterpret_cast<const f32x4*>(prm + 768 + n);
+              v += *reinterpret_cast<const f32x4*>(prm + 768 + n - poff);
               if (a.resid) v += *reinterpret_cast<const f32x4*>(a.resid + (size_t)tk * a.ldr + n);
               if (t < a.M && !(a.ablate & 4)) *reinterpret_cast<f32x4*>(a.Y + (size_t)tk * a.ldy + n) = v;
             }
@@ -438,8 +457,8 @@ namespace {
 // chunk of operand channels that fits the LDS with the padded tile (at most 256), the tile's rows and bytes
 bool tw_geometry(int L, int N, int K, TwGeom* g) {
   if (L < 3 || TW_TB % L != 0) return false;
-  if (!(N == 128 || N == 256 || N == 512)) return false;
-  if (K < 32 || K > 512 || (K & (K - 1)) != 0) return false;      // powers of two only: the tap / chunk indexing shifts and masks by K / 32, KC / 32 (K = 96 indexed taps up to 7)
+  if (!(N == 128 || N == 256 || N == 512 || N == 1024)) return false;
+  if (K < 32 || K > 1024 || (K & (K - 1)) != 0) return false;     // powers of two only: the tap / chunk indexing shifts and masks by K / 32, KC / 32 (K = 96 indexed taps up to 7)
   const int rows = TW_TB + 2 * (TW_TB / L + 1);
   // chunks of at most 128 operand channels: the tile (rows x (4 KC + 16) bytes) then leaves room for TWO blocks per CU (2 x 78 KB), so that one
   // block's staging / epilogue (memory latency, GroupNorm arithmetic) runs beside the other's MFMA phase -- with one wave per SIMD nothing overlaps
@@ -447,9 +466,9 @@ bool tw_geometry(int L, int N, int K, TwGeom* g) {
   while (KC > 32 && (size_t)rows * (4 * KC + 16) + TW_SCRATCH > 80 * 1024) KC >>= 1;
   if (KC < 32 || K % KC != 0) return false;
   g->KC = KC; g->n_chunks = K / KC; g->rows = rows; g->xrow = 4 * KC + 16;
-  g->n_pass = N == 512 ? 2 : 1;
+  g->n_pass = N <= 256 ? 1 : N / 256;
   g->lds = (size_t)rows * g->xrow + TW_SCRATCH;
-  return true;
+  return g->lds <= 80 * 1024;                                       // two blocks per CU
 }
 
 // the PRO template value of a GroupNorm-backward launch (0: not covered): the wave instructions of one staging pass = whole samples, at most 8
@@ -491,7 +510,7 @@ bool tkw_applicable(int M, int L, int N, int K, int pro, int epi) {
     if (tw_pro_variant(L, N, K) == 0) return false;
     if (g.n_chunks > 1 && (K / 8) > g.KC) return false;
   }
-  if (epi && N > 256) return false;                                   // (no forward layer has 512 output channels; the epilogue's parameter table holds 256)
+  if (epi && N > 512) return false;                                   // (forward layers have at most 512 output channels: EPI 2 runs two passes of 256)
   return true;
 }
 
@@ -500,7 +519,7 @@ int launch_tkw(const TkwArgs& a, hipStream_t s) {
   const int pro = a.gn_c ? 1 : 0, epi = a.Cst ? 1 : 0;
   TwGeom g;
   RAMP_REQUIRE(tkw_applicable(a.M, a.L, a.N, a.K, pro, epi) && tw_geometry(a.L, a.N, a.K, &g),
-               "tkw: C_out in {128, 256, 512}, C_in a multiple of 32 up to 512, tokens per sample >= 3 dividing 96 (24 with the GroupNorm backward), whole samples");
+               "tkw: C_out in {128, 256, 512, 1024} (<= 512 with the GroupNorm epilogue), C_in a power of two in [32, 1024], tokens per sample >= 3 dividing 96 (24 with the GroupNorm backward), whole samples");
   RAMP_REQUIRE(a.X && a.W && a.Y && (a.dir == 1 || a.dir == -1), "tkw: bad operand");
   RAMP_REQUIRE(a.K1 == a.K || (a.X2 && a.K1 > 0 && a.K1 < a.K && a.K1 % 4 == 0 && !pro), "tkw: bad operand split");
   RAMP_REQUIRE(a.N1 == a.N || (a.Y2 && a.N1 > 0 && a.N1 < a.N && a.N1 % 8 == 0 && !epi), "tkw: bad output split");
@@ -514,9 +533,10 @@ int launch_tkw(const TkwArgs& a, hipStream_t s) {
   RAMP_REQUIRE(!epi || !ranges_overlap(a.Cst, (size_t)a.M * a.N * 4, a.X, xbytes), "tkw: the stash must not overlap the operand");
   const int mbv = a.N == 128 ? 1 : 2;
   const int prov = pro ? tw_pro_variant(a.L, a.N, a.K) : 0;
-#define TW_CASE(MBV, PROV, EPIV) if (mbv == MBV && prov == PROV && epi == EPIV) return tkw_go<MBV, PROV, EPIV>(a, g, s);
+  const int epv = epi ? (a.N == 512 ? 2 : 1) : 0;
+#define TW_CASE(MBV, PROV, EPIV) if (mbv == MBV && prov == PROV && epv == EPIV) return tkw_go<MBV, PROV, EPIV>(a, g, s);
   TW_CASE(1, 0, 0) TW_CASE(1, 0, 1) TW_CASE(1, 3, 0) TW_CASE(1, 4, 0) TW_CASE(1, 6, 0) TW_CASE(1, 8, 0)
-  TW_CASE(2, 0, 0) TW_CASE(2, 0, 1) TW_CASE(2, 3, 0) TW_CASE(2, 4, 0) TW_CASE(2, 6, 0) TW_CASE(2, 8, 0)
+  TW_CASE(2, 0, 0) TW_CASE(2, 0, 1) TW_CASE(2, 0, 2) TW_CASE(2, 3, 0) TW_CASE(2, 4, 0) TW_CASE(2, 6, 0) TW_CASE(2, 8, 0)
 #undef TW_CASE
   RAMP_REQUIRE(false, "tkw: variant not built");
 }
@@ -524,7 +544,7 @@ int launch_tkw(const TkwArgs& a, hipStream_t s) {
 int init_tkw_attributes() {
 #define TW_ATTR(KV, PROV, EPIV) RAMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&KV<PROV, EPIV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
   TW_ATTR(tkw_kernel1, 0, 0); TW_ATTR(tkw_kernel1, 0, 1); TW_ATTR(tkw_kernel1, 3, 0); TW_ATTR(tkw_kernel1, 4, 0); TW_ATTR(tkw_kernel1, 6, 0); TW_ATTR(tkw_kernel1, 8, 0);
-  TW_ATTR(tkw_kernel2, 0, 0); TW_ATTR(tkw_kernel2, 0, 1); TW_ATTR(tkw_kernel2, 3, 0); TW_ATTR(tkw_kernel2, 4, 0); TW_ATTR(tkw_kernel2, 6, 0); TW_ATTR(tkw_kernel2, 8, 0);
+  TW_ATTR(tkw_kernel2, 0, 0); TW_ATTR(tkw_kernel2, 0, 1); TW_ATTR(tkw_kernel2, 0, 2); TW_ATTR(tkw_kernel2, 3, 0); TW_ATTR(tkw_kernel2, 4, 0); TW_ATTR(tkw_kernel2, 6, 0); TW_ATTR(tkw_kernel2, 8, 0);
 #undef TW_ATTR
   return 0;
 }

@@ -35,6 +35,13 @@ class TemporalUnetInference(nn.Module):
             raise NotImplementedError("only conditioning_type='attention' is on the sampler hot path")
         if time_emb_dim != 32 or attention_num_heads != 4 or attention_dim_head != 64:
             raise NotImplementedError("kernels are built for time_emb_dim=32 and 4x64 attention heads")
+        # the shapes ramp_create accepts (engine.hip), refused here with its wording before any weight is touched
+        if tuple(dim_mults) not in UNET_DIM_MULTS.values() or unet_input_dim not in (16, 32, 64):
+            raise ValueError("network shape: n_levels in {3, 4} (UNET_DIM_MULTS[0] = (1,2,4), [1] = (1,2,4,8)) and "
+                             f"unet_input_dim in {{16, 32, 64}}; got dim_mults={tuple(dim_mults)}, unet_input_dim={unet_input_dim}")
+        if n_support_points is not None and not (8 <= n_support_points <= 64 and n_support_points % 8 == 0):
+            raise ValueError("horizon (n_support_points) must be a multiple of 8 in [8, 64] (three stride-2 levels; attention "
+                             f"tiles of at most 64 tokens); got {n_support_points}")
         self.state_dim = state_dim
         self.n_support_points = n_support_points
         self.obstacle_3d = obstacle_3d
