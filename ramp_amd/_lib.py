@@ -67,6 +67,17 @@ class RampReplanState(C.Structure):
                 ("reserved", C.c_int32), ("extra_pts_host", C.c_void_p)]
 
 
+class RampProbeGemmArgs(C.Structure):
+    """ramp_probe_gemm_args (include/ramp_hip_tools.h): the operand fields of the engine's GEMM launch arguments."""
+    _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int32), ("K1", C.c_int32),
+                ("W", C.c_void_p), ("bias", C.c_void_p), ("rowbias", C.c_void_p), ("rowvar", C.c_void_p), ("row0", C.c_int32),
+                ("rb_stride", C.c_int32), ("resid", C.c_void_p), ("ldr", C.c_int32), ("resid2", C.c_void_p), ("ldr2", C.c_int32),
+                ("C", C.c_void_p), ("ldc", C.c_int32), ("C2", C.c_void_p), ("ldc2", C.c_int32), ("N1", C.c_int32),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("taps", C.c_int32), ("shift0", C.c_int32),
+                ("shift_step", C.c_int32), ("L", C.c_int32), ("a_stride", C.c_int32), ("c_rstride", C.c_int32),
+                ("c_roff", C.c_int32)]
+
+
 class RampReplanResult(C.Structure):
     _fields_ = [("n_free", C.c_int32), ("best_rank", C.c_int32), ("best_row", C.c_int32), ("fell_back", C.c_int32)]
 
@@ -148,6 +159,7 @@ PROTOTYPES = {
 TOOL_PROTOTYPES = {
     "ramp_bench_gemm": (C.c_int, [C.c_int32] * 9 + [c_f32p, C.c_void_p]),
     "ramp_stress_gemm": (C.c_int, [C.c_int32] * 8 + [c_i64p, c_f32p, C.c_void_p]),
+    "ramp_probe_gemm": (C.c_int, [C.POINTER(RampProbeGemmArgs), C.c_int32, C.c_float, c_f32p, c_i32p, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -225,6 +237,26 @@ def op_gemm(A, W, bias, resid, out, M, N, K, taps, shift0, step, L, mode="fp32",
                                    GEMM_MODES[mode], float(a_absmax_prev), C.byref(amax), C.byref(flag),
                                    current_stream()), "ramp_op_gemm_mode")
     return amax.value, flag.value
+
+
+_PROBE_TENSORS = ("A", "A2", "W", "bias", "rowbias", "rowvar", "resid", "resid2", "C", "C2")
+
+
+def probe_gemm(mode="fp32", a_absmax_prev=0.0, **fields):
+    """ramp_probe_gemm (tools library) on torch tensors: `fields` are the ramp_probe_gemm_args members (tensors for the operands,
+    ints for the rest; omitted ones are NULL / 0, except taps, L, a_stride and c_rstride, which default to 1).  Returns (rc, recorded max|A|, range
+    flag, error message or None) without raising, so that tests can check refusals too."""
+    a = RampProbeGemmArgs(taps=1, L=1, a_stride=1, c_rstride=1)
+    for k, v in fields.items():
+        setattr(a, k, ptr(v) if k in _PROBE_TENSORS else int(v))
+    amax, flag = C.c_float(0.0), C.c_int32(0)
+    tools = load_tools()
+    rc = tools.ramp_probe_gemm(C.byref(a), GEMM_MODES[mode], float(a_absmax_prev), C.byref(amax), C.byref(flag), current_stream())
+    msg = None
+    if rc != 0:
+        m = tools.ramp_last_error()
+        msg = m.decode() if m else ""
+    return rc, amax.value, flag.value, msg
 
 
 def ptr(t) -> Optional[int]:

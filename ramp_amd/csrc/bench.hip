@@ -538,5 +538,19 @@ int ramp_stress_gemm(int32_t M, int32_t N, int32_t K, int32_t taps, int32_t L, i
   return 0;
 }
 
+// probe of the GEMM operand contract: the caller's operands, every GemmArgs operand field, weights packed by the body of
+// ramp_op_gemm_mode (op_gemm_packed, ops.hip)
+int ramp_probe_gemm(const ramp_probe_gemm_args* p, int32_t mode, float a_absmax_prev, float* a_absmax_out, int32_t* range_flag_out,
+                    void* stream) {
+  RAMP_REQUIRE(p && p->A && p->W && p->C, "null argument");
+  GemmArgs a;
+  a.A = p->A; a.lda = p->lda; a.A2 = p->A2; a.lda2 = p->lda2; a.K1 = p->K1; a.W = p->W; a.bias = p->bias;
+  a.rowbias = p->rowbias; a.rowvar = p->rowvar; a.row0 = p->row0; a.rb_stride = p->rb_stride;
+  a.resid = p->resid; a.ldr = p->ldr; a.resid2 = p->resid2; a.ldr2 = p->ldr2;
+  a.C = p->C; a.ldc = p->ldc; a.C2 = p->C2; a.ldc2 = p->ldc2; a.N1 = p->N1;
+  a.M = p->M; a.N = p->N; a.K = p->K; a.taps = p->taps; a.shift0 = p->shift0; a.shift_step = p->shift_step; a.L = p->L;
+  a.a_stride = p->a_stride; a.c_rstride = p->c_rstride; a.c_roff = p->c_roff;
+  return op_gemm_packed(a, mode, a_absmax_prev, a_absmax_out, range_flag_out, as_stream(stream));
+}
 
 }  // extern "C"

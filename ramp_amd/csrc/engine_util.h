@@ -21,6 +21,14 @@
 #define CK(expr) do { int _r = (expr); if (_r != 0) return _r; } while (0)
 
 namespace ramp {
+
+// The body of ramp_op_gemm_mode for modes 0 fp32, 1 bf16x6, 2 bf16x6 (LDS-staged weights), 3 fp16x3 (ops.hip), shared with the
+// tools library's ramp_probe_gemm (bench.hip): packs a.W (raw fp32 [taps][N][K]) for `mode` as ramp_finalize_weights does,
+// launches `a`, synchronises `s` and reports the recorded max |A| and the range flag (zeros outside fp16x3).  Hidden: the
+// product library exports no new symbol for it.
+__attribute__((visibility("hidden"))) int op_gemm_packed(GemmArgs a, int mode, float a_absmax_prev, float* a_absmax_out_host,
+                                                         int32_t* range_flag_out_host, hipStream_t s);
+
 namespace {
 
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }

@@ -661,7 +661,7 @@ __device__ __forceinline__ void epilogue_wave_aux(const GemmArgs& a, f32x16 (&ac
       const int nc = nok ? n : 0;
       // the global operands of the fused math are requested before the transpose (their latency hides behind it)
       f32x4 pre0[8], pre1[EPI == EPI_GEGLU_BWD ? 8 : 1];
-      f32x4 rbv[AUX == 2 && !GEN ? 8 : 1];          // (no conv layer has a per-row-variant bias)
+      f32x4 rbv[AUX == 2 && !GEN ? 8 : 1];          // (GEN: no conv layer has a per-row-variant bias; read inline below)
       if (EPI == EPI_LINEAR) {
         if (AUX >= 1 && a.resid) {
 #pragma unroll
@@ -714,6 +714,7 @@ __device__ __forceinline__ void epilogue_wave_aux(const GemmArgs& a, f32x16 (&ac
           if (AUX == 2 && !GEN && a.rowbias) v += rbv[p];
           if (AUX >= 1 && a.resid) v += pre0[p];
           if (AUX == 2 && GEN && a.resid2) v += *reinterpret_cast<const f32x4*>(a.resid2 + orow * a.ldr2 + nc);
+          if (AUX == 2 && GEN && a.rowbias) v += *reinterpret_cast<const f32x4*>(a.rowbias + (long)a.rowvar[a.row0 + mc / a.L] * a.rb_stride + nc);
           if (ok) {
             if (!GEN || n < a.N1) *reinterpret_cast<f32x4*>(a.C + orow * a.ldc + n) = v;
             else *reinterpret_cast<f32x4*>(a.C2 + orow * a.ldc2 + (n - a.N1)) = v;

@@ -4,6 +4,57 @@
 // argument struct rebuilds this file and its own, not the sampler.
 #include "engine_util.h"
 
+namespace ramp {
+int op_gemm_packed(GemmArgs a, int mode, float a_absmax_prev, float* a_absmax_out_host, int32_t* range_flag_out_host, hipStream_t s) {
+  RAMP_REQUIRE(mode >= 0 && mode <= 3, "mode: 0 fp32, 1 bf16x6, 2 bf16x6 (LDS-staged weights), 3 fp16x3");
+  const int N = a.N, K = a.K;
+  const long n = (long)a.taps * N * K;
+  const bool frag_ok = N >= 64 && N % 32 == 0 && K % 16 == 0;
+  unsigned short* planes = nullptr; float* slots = nullptr;
+  int rc = 0;
+  if (mode == 3 && frag_ok) {
+    // the product's static weight scale: max |w| -> [2^10, 2^11)  (ramp_finalize_weights)
+    std::vector<float> hw(n);
+    RAMP_HIP_CHECK(hipMemcpy(hw.data(), a.W, n * sizeof(float), hipMemcpyDeviceToHost));
+    float mx = 0.f; for (float v : hw) mx = std::max(mx, std::fabs(v));
+    float sc = 1.f;
+    if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
+    RAMP_HIP_CHECK(hipMalloc(&planes, 2 * n * sizeof(unsigned short)));
+    RAMP_HIP_CHECK(hipMalloc(&slots, 16));
+    const float v[4] = {a_absmax_prev, 0.f, 0.f, 0.f};
+    RAMP_HIP_CHECK(hipMemcpyAsync(slots, v, 16, hipMemcpyHostToDevice, s));
+    rc = launch_pack_h3(a.W, planes, (long)a.taps * N, K, sc, s);
+    a.Wx = planes; a.wx_packed = 2; a.w_scale_inv = 1.f / sc;
+    a.a_absmax_in = a_absmax_prev > 0.f ? slots : nullptr; a.a_absmax_out = slots + 1;
+    a.range_flag = reinterpret_cast<int*>(slots + 2);
+  } else if (mode == 1 && frag_ok) {
+    RAMP_HIP_CHECK(hipMalloc(&planes, 3 * n * sizeof(unsigned short)));
+    rc = launch_pack_x6(a.W, planes, (long)a.taps * N, K, s);
+    a.Wx = planes; a.wx_packed = 1;
+  } else if ((mode == 1 || mode == 2) && N >= 128) {
+    RAMP_HIP_CHECK(hipMalloc(&planes, 3 * n * sizeof(unsigned short)));
+    rc = launch_split3(a.W, planes, n, s);
+    a.Wx = planes; a.wx_plane = n;
+  }
+  if (rc == 0) rc = launch_gemm(a, s);
+  hipError_t e = hipStreamSynchronize(s);
+  if (rc == 0 && e == hipSuccess && slots) {
+    float back[4] = {0, 0, 0, 0};
+    e = hipMemcpy(back, slots, 16, hipMemcpyDeviceToHost);
+    if (a_absmax_out_host) *a_absmax_out_host = back[1];
+    int fl; std::memcpy(&fl, &back[2], 4);
+    if (range_flag_out_host) *range_flag_out_host = fl;
+  } else {
+    if (a_absmax_out_host) *a_absmax_out_host = 0.f;
+    if (range_flag_out_host) *range_flag_out_host = 0;
+  }
+  if (planes) (void)hipFree(planes);
+  if (slots) (void)hipFree(slots);
+  RAMP_HIP_CHECK(e);
+  return rc;
+}
+}  // namespace ramp
+
 extern "C" {
 
 // ---- kernel-level entry points ---------------------------------------------------------------------
@@ -154,50 +205,7 @@ int ramp_op_gemm_mode(const float* A, const float* W, const float* bias, const f
   }
   GemmArgs a; a.A = A; a.lda = K; a.W = W; a.bias = bias; a.resid = resid; a.ldr = N; a.C = C; a.ldc = N;
   a.M = M; a.N = N; a.K = K; a.taps = taps; a.shift0 = shift0; a.shift_step = shift_step; a.L = L;
-  const long n = (long)taps * N * K;
-  const bool frag_ok = N >= 64 && N % 32 == 0 && K % 16 == 0;
-  unsigned short* planes = nullptr; float* slots = nullptr;
-  int rc = 0;
-  if (mode == 3 && frag_ok) {
-    // the product's static weight scale: max |w| -> [2^10, 2^11)  (ramp_finalize_weights)
-    std::vector<float> hw(n);
-    RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, n * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f; for (float v : hw) mx = std::max(mx, std::fabs(v));
-    float sc = 1.f;
-    if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-    RAMP_HIP_CHECK(hipMalloc(&planes, 2 * n * sizeof(unsigned short)));
-    RAMP_HIP_CHECK(hipMalloc(&slots, 16));
-    const float v[4] = {a_absmax_prev, 0.f, 0.f, 0.f};
-    RAMP_HIP_CHECK(hipMemcpyAsync(slots, v, 16, hipMemcpyHostToDevice, s));
-    rc = launch_pack_h3(W, planes, (long)taps * N, K, sc, s);
-    a.Wx = planes; a.wx_packed = 2; a.w_scale_inv = 1.f / sc;
-    a.a_absmax_in = a_absmax_prev > 0.f ? slots : nullptr; a.a_absmax_out = slots + 1;
-    a.range_flag = reinterpret_cast<int*>(slots + 2);
-  } else if (mode == 1 && frag_ok) {
-    RAMP_HIP_CHECK(hipMalloc(&planes, 3 * n * sizeof(unsigned short)));
-    rc = launch_pack_x6(W, planes, (long)taps * N, K, s);
-    a.Wx = planes; a.wx_packed = 1;
-  } else if ((mode == 1 || mode == 2) && N >= 128) {
-    RAMP_HIP_CHECK(hipMalloc(&planes, 3 * n * sizeof(unsigned short)));
-    rc = launch_split3(W, planes, n, s);
-    a.Wx = planes; a.wx_plane = n;
-  }
-  if (rc == 0) rc = launch_gemm(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (rc == 0 && e == hipSuccess && slots) {
-    float back[4] = {0, 0, 0, 0};
-    e = hipMemcpy(back, slots, 16, hipMemcpyDeviceToHost);
-    if (a_absmax_out_host) *a_absmax_out_host = back[1];
-    int fl; std::memcpy(&fl, &back[2], 4);
-    if (range_flag_out_host) *range_flag_out_host = fl;
-  } else {
-    if (a_absmax_out_host) *a_absmax_out_host = 0.f;
-    if (range_flag_out_host) *range_flag_out_host = 0;
-  }
-  if (planes) (void)hipFree(planes);
-  if (slots) (void)hipFree(slots);
-  RAMP_HIP_CHECK(e);
-  return rc;
+  return op_gemm_packed(a, mode, a_absmax_prev, a_absmax_out_host, range_flag_out_host, s);
 }
 static int op_ffx_impl(const float* z1, const float* dz, const float* W1, const float* b1, const float* W2, const float* b2,
                        const float* ln_g, const float* ln_b, int32_t M, const float* absmax_prev_host, float* z2, float* dz1,

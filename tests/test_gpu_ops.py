@@ -110,6 +110,97 @@ def test_groupnorm_fwd_bwd(R, L, C, mish):
     assert rel(dx.cpu().numpy(), dx_ref) < 5e-6
 
 
+# every GroupNorm kernel: the C = 16 kernel (two groups per float4), the 32 .. 256 kernel and its C = 512 variant (a wave holds 4 of
+# the 8 groups) at their L * C <= 4096 limit and below
+GN_SHAPES = ([(16, L) for L in (8, 16, 24, 40, 48, 56, 64, 256)] + [(512, L) for L in (1, 2, 3, 5, 6, 7, 8)] +
+             [(C, 4096 // C) for C in (32, 64, 128, 256)])
+GN_R = 5                     # rows = blocks
+U32 = 2.0 ** -24
+
+
+def gn_input(g, R, L, C, cond):
+    x = g.standard_normal((R, L, C)) * 1.5 + 0.3
+    if cond == "offset":         # |mean| / std = 2000: a one-pass variance (E x^2 - mean^2) loses all of it in fp32
+        x = 100.0 + 0.05 * g.standard_normal((R, L, C))
+    elif cond.startswith("eps"):  # even groups near-constant (variance 1e-7 << eps): rstd is set by eps
+        xg = x.reshape(R, L, 8, C // 8)
+        xg[:, :, 0::2] = 3e-4 * g.standard_normal(xg[:, :, 0::2].shape)
+    elif cond == "outlier":      # group 3 ten times its neighbours in spread and offset: leakage across groups shows
+        xg = x.reshape(R, L, 8, C // 8)
+        xg[:, :, 3] = xg[:, :, 3] * 10.0 + 5.0
+    return x.astype(np.float32)
+
+
+@pytest.mark.parametrize("cond", ["normal", "offset", "eps1e-5", "eps1e-6", "outlier"])
+def test_groupnorm_every_width_and_epilogue(cond):
+    """GroupNorm forward (+ time bias, + residual, Mish on / off) and its input gradient (+ add on / off) at every width the
+    network uses, against float64, with the per-group statistics compared too.  Bars: 3e-6 forward, 5e-6 backward, 2e-6 for
+    (mean, rstd); where |mean| * rstd = kappa is large (the offset inputs) the output bars are 8 u kappa, the rounding of the
+    fp32 mean itself, while the statistics keep 2e-6."""
+    eps = 1e-6 if cond == "eps1e-6" else 1e-5
+    lib = _lib.load()
+    worst = {"y": (0.0, None), "dx": (0.0, None), "mean": (0.0, None), "rstd": (0.0, None)}
+    for C, L in GN_SHAPES:
+        R = GN_R
+        g = rng(C * 1000 + L + len(cond))
+        x = gn_input(g, R, L, C, cond)
+        gam = (1 + 0.1 * g.standard_normal(C)).astype(np.float32); bet = (0.1 * g.standard_normal(C)).astype(np.float32)
+        tb = g.standard_normal(C).astype(np.float32); res = g.standard_normal((R, L, C)).astype(np.float32)
+        dy = g.standard_normal((R, L, C)).astype(np.float32); add = g.standard_normal((R, L, C)).astype(np.float32)
+        x64 = x.astype(np.float64)
+        n, cache = O.groupnorm_fwd(x64, gam, bet, 8, eps)
+        mean_ref = x64.reshape(R, L, 8, C // 8).mean(axis=(1, 3))
+        rstd_ref = cache[1].reshape(R, 8)
+        kappa = float((np.abs(mean_ref) * rstd_ref).max())
+        bar_y, bar_dx = max(3e-6, 8 * U32 * kappa), max(5e-6, 8 * U32 * kappa)
+        d = {k: dev(v) for k, v in dict(x=x, gam=gam, bet=bet, tb=tb, res=res, dy=dy, add=add).items()}
+        y = torch.empty((R, L, C), device="cuda"); dx = torch.empty_like(y)
+        for mish in (0, 1):
+            act = O.mish(n) if mish else n
+            dn = dy * (O.mish_grad(n) if mish else 1.0)
+            dx0 = O.groupnorm_bwd(dn, gam.astype(np.float64), cache)
+            for use_tb in (False, True):
+                for use_res in (False, True):
+                    st = torch.full((R, 8, 2), float("nan"), device="cuda")
+                    _lib.check(lib.ramp_op_groupnorm(_lib.ptr(d["x"]), _lib.ptr(d["gam"]), _lib.ptr(d["bet"]),
+                                                     _lib.ptr(d["tb"]) if use_tb else None, _lib.ptr(d["res"]) if use_res else None,
+                                                     _lib.ptr(y), _lib.ptr(st), R, L, C, eps, mish, S()))
+                    y_ref = act + (tb if use_tb else 0.0) + (res if use_res else 0.0)
+                    sth = st.cpu().numpy()
+                    tag = (C, L, mish, use_tb, use_res)
+                    for key, got, ref, bar in (("y", y.cpu().numpy(), y_ref, bar_y), ("mean", sth[..., 0], mean_ref, 2e-6),
+                                               ("rstd", sth[..., 1], rstd_ref, 2e-6)):
+                        err = rel(got, ref)
+                        worst[key] = max(worst[key], (err, tag), key=lambda t: t[0])
+                        assert err < bar, (key, tag, err, bar)
+                    for use_add in (False, True):
+                        _lib.check(lib.ramp_op_groupnorm_bwd(_lib.ptr(d["dy"]), _lib.ptr(d["x"]), _lib.ptr(st), _lib.ptr(d["gam"]),
+                                                             _lib.ptr(d["bet"]), _lib.ptr(d["add"]) if use_add else None,
+                                                             _lib.ptr(dx), R, L, C, mish, S()))
+                        err = rel(dx.cpu().numpy(), dx0 + (add if use_add else 0.0))
+                        worst["dx"] = max(worst["dx"], (err, tag + (use_add,)), key=lambda t: t[0])
+                        assert err < bar_dx, ("dx", tag, use_add, err, bar_dx)
+    print(f"groupnorm {cond}: " + ", ".join(f"{k} {v[0]:.2e} at {v[1]}" for k, v in worst.items()))
+
+
+@pytest.mark.parametrize("C,L", [(8, 4), (48, 4), (1024, 1), (512, 9), (16, 257)])
+def test_groupnorm_refuses_unsupported_widths(C, L):
+    """Widths without a kernel and rows past L * C = 4096 are refused, forward and backward, with a message naming the limit."""
+    R = 2
+    lib = _lib.load()
+    t = {k: torch.zeros(R * L * C, device="cuda") for k in ("x", "y", "dy", "dx")}
+    p = {k: torch.ones(C, device="cuda") for k in ("gam", "bet")}
+    st = torch.zeros(R * 16, device="cuda")
+    want = "L*C <= 4096" if C in (16, 512) else "C in {16,32,64,128,256,512}"
+    rc = lib.ramp_op_groupnorm(_lib.ptr(t["x"]), _lib.ptr(p["gam"]), _lib.ptr(p["bet"]), None, None, _lib.ptr(t["y"]), _lib.ptr(st),
+                               R, L, C, 1e-5, 1, S())
+    assert rc != 0 and want in lib.ramp_last_error().decode()
+    rc = lib.ramp_op_groupnorm_bwd(_lib.ptr(t["dy"]), _lib.ptr(t["x"]), _lib.ptr(st), _lib.ptr(p["gam"]), _lib.ptr(p["bet"]), None,
+                                   _lib.ptr(t["dx"]), R, L, C, 1, S())
+    assert rc != 0 and want in lib.ramp_last_error().decode()
+    assert not t["y"].any() and not t["dx"].any()
+
+
 @pytest.mark.parametrize("n_tok", [1, 5, 4097])
 def test_layernorm_fwd_bwd(n_tok):
     g = rng(n_tok)

@@ -29,7 +29,7 @@ def test_library_exports_every_declared_symbol():
     # library exports none of it, the tools library exports everything
     import subprocess
     exported = set(re.findall(r" T (ramp_[a-z0-9_]+)", subprocess.run(["nm", "-D", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout))
-    assert not [n for n in exported if n.startswith(("ramp_bench", "ramp_stress"))], "diagnostics leaked into the product library"
+    assert not [n for n in exported if n.startswith(("ramp_bench", "ramp_stress", "ramp_probe"))], "diagnostics leaked into the product library"
     assert exported == declared, (sorted(exported - declared), sorted(declared - exported))      # nothing undeclared either
     thdr = open(os.path.join(ROOT, "include", "ramp_hip_tools.h")).read()
     tdecl = set(re.findall(r"\b(ramp_[a-z0-9_]+)\s*\(", thdr)) - {"ramp_ctx"}
@@ -58,14 +58,14 @@ def test_struct_layout_matches_header():
     import subprocess, tempfile
     pairs = [("ramp_config", _lib.RampConfig), ("ramp_apf_params", _lib.RampApfParams), ("ramp_sample_params", _lib.RampSampleParams),
              ("ramp_replan_params", _lib.RampReplanParams), ("ramp_replan_state", _lib.RampReplanState),
-             ("ramp_replan_result", _lib.RampReplanResult)]
+             ("ramp_replan_result", _lib.RampReplanResult), ("ramp_probe_gemm_args", _lib.RampProbeGemmArgs)]
     body = []
     for cname, cls in pairs:
         body.append(f'printf("%zu", sizeof({cname}));')
         for fname, _ in cls._fields_:
             body.append(f'printf(" %zu", offsetof({cname}, {fname}));')
         body.append('printf("\\n");')
-    src = '#include "ramp_hip.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){' + "".join(body) + 'return 0;}\n'
+    src = '#include "ramp_hip_tools.h"\n#include <stdio.h>\n#include <stddef.h>\nint main(){' + "".join(body) + 'return 0;}\n'
     with tempfile.TemporaryDirectory() as d:
         open(os.path.join(d, "s.c"), "w").write(src)
         subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), os.path.join(d, "s.c"), "-o", os.path.join(d, "s")])
