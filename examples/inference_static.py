@@ -158,6 +158,51 @@ class StaticInference:
         return metrics
 
 
+    def run_all_experiments(self, context_idx: int):
+        """Opt-in (--all-envs): every experiment directory of the tree as ONE job (``run_inference_scenes``) instead of the reference's
+        loop of one ``run_inference`` per directory.  Returns one metrics dict per experiment, in directory order."""
+        cfg = self.config
+        if cfg.compose:
+            raise ValueError("--all-envs does not support compose")
+        torch.cuda.set_device(0)
+        base = os.path.join(cfg.dataset_path, cfg.dataset_subdir)
+        dirs = sorted((d for d in os.listdir(base) if d.isdigit()), key=int)
+        datas = [compat.load_environment_dir(os.path.join(base, d)) for d in dirs]
+        n_support_points = cfg.n_support_points
+        diffusion_configs = dict(variance_schedule=cfg.variance_schedule, n_diffusion_steps=cfg.n_diffusion_steps,
+                                 predict_epsilon=cfg.predict_epsilon, compose=False, use_apf=cfg.use_apf)
+        if cfg.sampler is not None:
+            diffusion_configs['sampler'] = cfg.sampler
+        unet_configs = dict(state_dim=cfg.state_dim, n_support_points=n_support_points, unet_input_dim=cfg.unet_input_dim,
+                            dim_mults=UNET_DIM_MULTS[cfg.unet_dim_mults_option])
+        self.model = get_model(model_class=cfg.diffusion_model_class,
+                               model=TemporalUnetInference(max_rows=2 * cfg.n_samples * len(dirs), **unet_configs),
+                               tensor_args=self.tensor_args, **diffusion_configs, **unet_configs)
+        compat.load_checkpoint(self.model, cfg.trained_models_dir, cfg.model_id, use_ema=cfg.use_ema, device="cpu")
+        self.model.eval()
+        hard_conds = []
+        for d in dirs:
+            start, goal = self.context_manager.load_context(os.path.join(base, d, 'contexts'), context_idx, self.device)
+            hard_conds.append(compat.StateGenerator.get_hard_cond_custom(torch.vstack((start, goal)), horizon=n_support_points,
+                                                                         include_velocity=cfg.include_velocity))
+        t_start_guide = ceil(cfg.start_guide_steps_fraction * self.model.n_diffusion_steps)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        trajs, traj_scene = self.model.run_inference_scenes(
+            [d['obstacle_points'] for d in datas], hard_conds, n_samples=cfg.n_samples, horizon=n_support_points, sample_fn=ddpm_sample_fn,
+            guide=None, n_guide_steps=cfg.n_guide_steps, t_start_guide=t_start_guide, noise_std_extra_schedule_fn=lambda x: 0.5,
+            n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise)
+        torch.cuda.synchronize(); elapsed = time.perf_counter() - t0
+        out = []
+        for i, data in enumerate(datas):
+            mine = trajs[traj_scene == i]
+            ci = self.metrics_calculator.compute_collision_intensity(mine, data['box_centers'], data['box_sizes'])
+            m = self.metrics_calculator.trajectory_success_and_metrics(mine, ci)
+            m['env'], m['total_time_all_envs'] = int(dirs[i]), elapsed
+            out.append(m)
+        self.last_trajectories = trajs
+        return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--make-synthetic", metavar="DIR", help="write a synthetic experiment tree (reference layout) to DIR and run on it")
@@ -168,6 +213,7 @@ def main(argv=None):
     ap.add_argument("--n-diffusion-steps", type=int, default=StaticConfig.n_diffusion_steps)
     ap.add_argument("--sampler", choices=["ddim", "ddpm"], default=None)
     ap.add_argument("--use-apf", action="store_true")
+    ap.add_argument("--all-envs", action="store_true", help="run every experiment directory of the tree as ONE job (run_inference_scenes)")
     ap.add_argument("--n-steps-without-noise", type=int, default=StaticConfig.n_diffusion_steps_without_noise)
     ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=StaticConfig.unet_input_dim)
     ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=StaticConfig.unet_dim_mults_option)
@@ -186,6 +232,11 @@ def main(argv=None):
             ap.error("--dataset-path and --trained-models-dir (or --make-synthetic DIR) are required")
         cfg.dataset_path, cfg.trained_models_dir = args.dataset_path, args.trained_models_dir
     runner = StaticInference(cfg)
+    if args.all_envs:
+        per_env = runner.run_all_experiments(args.context)
+        for m in per_env:
+            print(json.dumps({k: v for k, v in m.items() if v is None or isinstance(v, (int, float))}))
+        return per_env, runner
     metrics = runner.run_single_experiment(args.env, args.context)
     print(json.dumps({k: v for k, v in metrics.items() if v is None or isinstance(v, (int, float))}))
     return metrics, runner

@@ -105,6 +105,17 @@ int ramp_time_embedding(ramp_ctx* ctx, int32_t t, float* out32, void* stream);
 int ramp_set_scene(ramp_ctx* ctx, const float* latents, int32_t n_variants,
                    const int32_t* row_variant_host, int32_t n_rows_pattern, void* stream);
 
+/* Many scenes in one job: the loop over experiment directories of scripts/inference/inference_static.py (one cache_scene_encoding +
+ * run_inference per experiment, :113-190) as ONE batch whose rows carry their own scene.  `latents` device (n_variants, context_dim),
+ * 1 <= n_variants <= 65536 (N scene rows plus the shared all-zero unconditional row); row r of the network uses variant
+ * row_variant_host[r] (int32, HOST array, an EXPLICIT table of n_rows = B * n_rp entries, not a pattern).  Computes the
+ * cross-attention constants like ramp_set_scene and drops the captured graphs and every kept calibration like it; a later
+ * ramp_set_scene returns the context to pattern mode.  While the explicit table is in place ramp_score / ramp_sample refuse a
+ * batch with more rows than n_rows.  The launch plan is the single-scene job's: from 5 variants on, the fused kernels read the row
+ * constant from global memory instead of LDS (atk.hip, tkl.hip, tkl16.hip). */
+int ramp_set_scenes(ramp_ctx* ctx, const float* latents, int32_t n_variants, const int32_t* row_variant_host, int32_t n_rows,
+                    void* stream);
+
 /* scene_encoder(obstacle_pts) for ONE scene: ObstacleEncoderSet.forward (obstacle_encoder.py:125-152, point_dim 2,
  * latent 320) or ObstacleEncoder.forward in eval mode (obstacle_encoder3d.py:77-94, point_dim 3, latent 256).
  * cloud: device (n_obstacles, n_points, point_dim); latent_out: device (context_dim), 16-byte aligned. */
@@ -190,6 +201,20 @@ typedef struct ramp_sample_params {
  * x_out: device (B,H,S) final trajectories or NULL. */
 int ramp_sample(ramp_ctx* ctx, const ramp_sample_params* p, const float* noise, float* chain_out,
                 float* x_out, void* stream);
+/* ramp_sample over trajectories of SEVERAL scenes (the experiment loop of scripts/inference/inference_static.py:113-190 as one
+ * job; the row -> latent table comes from ramp_set_scenes): trajectory b avoids the cloud of scene traj_scene[b] in the APF hook
+ * (APFhelper.py:37-104 with that experiment's ObstacleField).  p->apf.cloud must be NULL and p->apf.n_points is ignored; window,
+ * weights, threshold, strength and passes keep their meaning.  cloud_points == NULL = APF off.  Graph capture, Philox noise, range
+ * guard, fallback modes and calibration reuse are ramp_sample's. */
+typedef struct ramp_scene_batch {
+  int32_t n_scenes;
+  int32_t reserved;
+  const int32_t* traj_scene;          /* device (B) int32: scene of each trajectory, 0 <= . < n_scenes               */
+  const float* cloud_points;          /* device (sum P, 2): the scenes' obstacle points, concatenated; NULL = APF off */
+  const int32_t* cloud_offset_host;   /* host (n_scenes + 1): first point of each scene, [0] = 0, strictly increasing */
+} ramp_scene_batch;
+int ramp_sample_scenes(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_scene_batch* scenes, const float* noise,
+                       float* chain_out, float* x_out, void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from
@@ -282,6 +307,11 @@ int ramp_select_from_costs(const int32_t* mask, const float* path_len, const flo
 /* ---- kernel-level entry points (same kernels the loops use; exported for parity tests) ---- */
 /* avoidance(trajectories, ObstacleField(cloud, thr), window, strength) in place (APFhelper.py:37-104) */
 int ramp_apf(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf_params* p, void* stream);
+/* the same with one cloud per scene (the kernel ramp_sample_scenes runs; inference_static.py:113-190, one ObstacleField per
+ * experiment): trajectory b is pushed away from scene traj_scene[b]'s points only, bit for bit what ramp_apf gives for that
+ * cloud.  p->cloud must be NULL; a trajectory whose scene index is outside [0, n_scenes) is left unchanged. */
+int ramp_apf_scenes(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf_params* p, const ramp_scene_batch* scenes,
+                    void* stream);
 /* per-trajectory APF of the dynamic planner: avoidance(trajectory, obstacle_field, is_dynamic, ...)
  * (APFhelper_dynamic.py:107-142) for B trajectories at once.  points: device (P,2) FLOAT64 (the reference's numpy
  * clouds).  window >= 0: static pass (pushes waypoints [ci-w, min(H-1, ci+w)) around the waypoint ci nearest to the
@@ -346,9 +376,10 @@ int ramp_op_ffx16(const float* z1, const float* dz, const float* W1, const float
  * projection and its input gradient -- reference layers_attention_mini.py:60-120, 130-149):
  *   Y[m][n] = sum_k pro(X)[m][k] W[n][k] + bias[n] + rowbias[rowvar[m / L]][n] + resid[m][n],  pro = LayerNorm(256) when ln_g
  * is given, identity otherwise.  X (M, 256), W (N, 256) with N a multiple of 32 (<= 768), Y / resid (M, N), rowbias
- * (n_var, N) with N == 256, all device fp32; bias / resid / rowbias / ln_g, ln_b may be NULL.  absmax_prev: the operand
- * maximum the delayed fp16 scaling assumes (0 = unscaled); *absmax_out_host the maximum recorded, *range_flag_out_host the
- * range guard.  Packs the weight on every call (tests). */
+ * (n_var, N) with N == 256 (n_var <= 4: staged in LDS; more: read from global memory in the epilogue), all device fp32;
+ * bias / resid / rowbias / ln_g, ln_b may be NULL.  absmax_prev: the operand maximum the delayed fp16 scaling assumes
+ * (0 = unscaled); *absmax_out_host the maximum recorded, *range_flag_out_host the range guard.  Packs the weight on every
+ * call (tests). */
 int ramp_op_tkl(const float* X, const float* W, const float* bias, const float* resid, const float* rowbias,
                 const int32_t* rowvar, int32_t n_var, int32_t L, const float* ln_g, const float* ln_b, int32_t M, int32_t N,
                 float absmax_prev, float* Y, float* absmax_out_host, int32_t* range_flag_out_host, void* stream);
@@ -359,8 +390,9 @@ int ramp_op_tkl16(const float* X, const float* W, const float* bias, const float
 /* Self-attention fused with its output projection (atk.hip; the product path's replacement of the attention kernel + the
  * out-projection launch -- reference layers_attention_mini.py:101-127 and :132):
  *   Y[m] = resid[m] + Wo softmax(q k^T / 8) v [m] + bias + rowbias[rowvar[m / L]],  4 heads x 64, softmax over the L tokens of
- * m's sample.  qkv (M, 768) = [q | k | v] rows, Wo (256, 256), resid / Y (M, 256), rowbias (n_var <= 4, 256), device fp32; L must
- * divide 48 or 32 and M be whole samples.  Scaling arguments as ramp_op_tkl (the operand is the attention output o). */
+ * m's sample.  qkv (M, 768) = [q | k | v] rows, Wo (256, 256), resid / Y (M, 256), rowbias (n_var, 256; n_var <= 4: staged
+ * in LDS, more: read from global memory in the epilogue), device fp32; L must divide 48 or 32 and M be whole samples.
+ * Scaling arguments as ramp_op_tkl (the operand is the attention output o). */
 int ramp_op_ato(const float* qkv, const float* Wo, const float* bias, const float* resid, const float* rowbias, const int32_t* rowvar,
                 int32_t n_var, int32_t L, int32_t M, float absmax_prev, float* Y, float* absmax_out_host, int32_t* range_flag_out_host, void* stream);
 /* Backward of the self-attention itself on sample-owning waves (atk.hip, atb_kernel; the product path's replacement of the exact-fp32

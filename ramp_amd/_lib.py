@@ -35,6 +35,12 @@ class RampApfParams(C.Structure):
                 ("passes", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RampSceneBatch(C.Structure):
+    """ramp_scene_batch: the scenes of a many-scene job (ramp_sample_scenes, ramp_apf_scenes)."""
+    _fields_ = [("n_scenes", C.c_int32), ("reserved", C.c_int32), ("traj_scene", C.c_void_p), ("cloud_points", C.c_void_p),
+                ("cloud_offset_host", c_i32p)]
+
+
 class RampSampleParams(C.Structure):
     _fields_ = [("B", C.c_int32), ("n_rp", C.c_int32), ("n_steps", C.c_int32), ("ddim", C.c_int32),
                 ("w0", C.c_double), ("w1", C.c_double),
@@ -95,12 +101,15 @@ PROTOTYPES = {
     "ramp_prepare_time_table": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "ramp_time_embedding": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ramp_set_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, C.c_int32, C.c_void_p]),
+    "ramp_set_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, C.c_int32, C.c_void_p]),
     "ramp_encode_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "ramp_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
     "ramp_score_mode": (C.c_int, [C.c_void_p, c_i32p]),
     "ramp_sample": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
+    "ramp_sample_scenes": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampSceneBatch), C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "ramp_philox_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "ramp_replan": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampReplanState), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.POINTER(RampReplanResult), C.c_void_p]),
@@ -110,6 +119,8 @@ PROTOTYPES = {
     "ramp_select_from_costs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p,
                                          C.c_void_p]),
     "ramp_apf": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampApfParams), C.c_void_p]),
+    "ramp_apf_scenes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampApfParams),
+                                  C.POINTER(RampSceneBatch), C.c_void_p]),
     "ramp_apf_dynamic": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_double,
                                    C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_hard_cond": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_i32p, C.c_void_p,

@@ -38,6 +38,11 @@ struct ApfArgs {
   const float* window = nullptr;// (2*win+1) Gaussian weights
   int B = 0, H = 0, S = 0, P = 0, win = 0;
   double thr = 0, strength = 0;
+  // one cloud per scene (a job of many scenes, ramp_sample_scenes): trajectory b avoids the points
+  // [scene_off[scene[b]], scene_off[scene[b] + 1]) of `cloud`, the scenes' clouds concatenated; P is then unused
+  const int* scene = nullptr;     // (B) scene of each trajectory, or null = one cloud of P points for all
+  const int* scene_off = nullptr; // (n_scenes + 1) first point of each scene's cloud
+  int n_scenes = 0;
 };
 int launch_apf(const ApfArgs& a, hipStream_t s);
 struct ApfDynArgs {

@@ -72,7 +72,9 @@ int ato_pack(const float* W, float scale, unsigned short* out, hipStream_t s) {
   return 0;
 }
 
-// NG: 16-token groups per wave (3: T = 48, 2: T = 32).  RB: per-row-variant constant.
+// NG: 16-token groups per wave (3: T = 48, 2: T = 32).  RB: per-row-variant constant, its rows staged in LDS (<= 4 variants) or, with ABL bit 3 (a
+// PRODUCT variant, not a diagnostic: ato_kernel<NG, true, 8>), read from global memory in the epilogue -- more variants than the LDS table holds: a job
+// of many scenes, ramp_set_scenes; 1 KB per variant and block, L2-resident.
 //
 // Schedule of a wave.  The work is a flat sequence of HEAD STEPS (tile, head): [attention of the head] -> [4 slabs of the projection: 16 output
 // features x 4, the head's 64 k] -> (head 3: epilogue of the tile).  Register budget: the 192 accumulators live in the accumulation half of
@@ -91,6 +93,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void ato_kernel(AtoArgs a, int n_tiles) {
   constexpr int T = 16 * NG;
   constexpr bool STAMP = (ABL & 1) != 0;
+  constexpr bool RBG = RB && (ABL & 8) != 0;              // the row constant stays in global memory
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -110,7 +113,7 @@ void ato_kernel(AtoArgs a, int n_tiles) {
   // tables -> LDS (published by the first slab barrier)
   float* bs = reinterpret_cast<float*>(smem + AT_BIAS);
   bs[tid] = a.bias ? a.bias[tid] : 0.f;
-  if (RB) {
+  if (RB && !RBG) {
     float* rbs = reinterpret_cast<float*>(smem + AT_RB);
     for (int v = 0; v < a.n_var; ++v) rbs[v * 256 + tid] = a.rowbias[(long)v * a.rb_stride + tid];
   }
@@ -458,19 +461,22 @@ void ato_kernel(AtoArgs a, int n_tiles) {
       for (int t = 0; t < NG; ++t) {
         const unsigned tk = (unsigned)min((int)tok0 + 16 * t + c, m_last);      // (32-bit: a 64-bit division here costs hundreds of instructions and registers)
         yoff[t] = tk * 1024u + 16u * (unsigned)g;
-        rbo[t] = RB ? a.rowvar[a.row0 + (int)(tk / (unsigned)a.L)] * 256 + 4 * g : 0;
+        rbo[t] = RB ? a.rowvar[a.row0 + (int)(tk / (unsigned)a.L)] * (RBG ? a.rb_stride : 256) + 4 * g : 0;
       }
       const char* rbase = reinterpret_cast<const char*>(a.resid);
       char* ybase = reinterpret_cast<char*>(a.Y);
       if (full) {
         // all loads of a batch first, every store unconditional (a store behind a per-lane predicate sits in its own basic block behind
         // s_waitcnt vmcnt(0): DESIGN.md section 5); 8 batches of 2 feature blocks, the loads two batches ahead of their stores
-        f32x4 rz[2][2][NG];
+        f32x4 rz[2][2][NG], rbg[2][2][RBG ? NG : 1];      // (rbg: the constants read from global memory, requested with the residual they are added to)
         auto rz_load = [&](int b2) __attribute__((always_inline)) {
 #pragma unroll
           for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int t = 0; t < NG; ++t) rz[b2 & 1][q][t] = *reinterpret_cast<const f32x4*>(rbase + yoff[t] + 64 * (2 * b2 + q));
+            for (int t = 0; t < NG; ++t) {
+              rz[b2 & 1][q][t] = *reinterpret_cast<const f32x4*>(rbase + yoff[t] + 64 * (2 * b2 + q));
+              if (RBG) rbg[b2 & 1][q][t] = *reinterpret_cast<const f32x4*>(a.rowbias + rbo[t] + 16 * (2 * b2 + q));
+            }
         };
         rz_load(0); rz_load(1);
 #pragma unroll
@@ -482,7 +488,8 @@ void ato_kernel(AtoArgs a, int n_tiles) {
 #pragma unroll
             for (int t = 0; t < NG; ++t) {
               f32x4 v = acc[nb][t] * os + bq + rz[b2 & 1][q][t];
-              if (RB) v += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + AT_RB) + rbo[t] + 16 * nb);
+              if (RBG) v += rbg[b2 & 1][q][t];
+              if (RB && !RBG) v += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + AT_RB) + rbo[t] + 16 * nb);
               *reinterpret_cast<f32x4*>(ybase + yoff[t] + 64 * nb) = v;
             }
           }
@@ -497,7 +504,8 @@ void ato_kernel(AtoArgs a, int n_tiles) {
 #pragma unroll
           for (int t = 0; t < NG; ++t) {
             f32x4 v = acc[nb][t] * os + bq + *reinterpret_cast<const f32x4*>(rbase + yoff[t] + 64 * nb);
-            if (RB) v += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + AT_RB) + rbo[t] + 16 * nb);
+            if (RB && !RBG) v += *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + AT_RB) + rbo[t] + 16 * nb);
+            if (RBG) v += *reinterpret_cast<const f32x4*>(a.rowbias + rbo[t] + 16 * nb);
             if (tok0 + 16 * t + c < a.M) *reinterpret_cast<f32x4*>(ybase + yoff[t] + 64 * nb) = v;
           }
         }
@@ -533,19 +541,27 @@ int launch_ato(const AtoArgs& a, hipStream_t s) {
   RAMP_REQUIRE(ato_applicable(a.M, a.L, &ng), "ato: tokens per sample must divide 48 or 32 (and M be whole samples)");
   RAMP_REQUIRE(a.QKV && a.W && a.resid && a.Y, "ato: null operand");
   RAMP_REQUIRE(al16(a.QKV) && al16(a.W) && al16(a.resid) && al16(a.Y) && al16(a.bias) && al16(a.rowbias), "ato: operands must be 16-byte aligned");
-  RAMP_REQUIRE(!a.rowbias || (a.rowvar && a.n_var >= 1 && a.n_var <= 4), "ato: row-variant constant needs the row -> variant table and 1 .. 4 variants");
+  RAMP_REQUIRE(!a.rowbias || (a.rowvar && a.n_var >= 1), "ato: row-variant constant needs the row -> variant table");
+  // more than 4 variants (a job of many scenes): the constants are read from global memory, 16 bytes per lane at 32-bit element offsets
+  RAMP_REQUIRE(!a.rowbias || a.n_var <= 4 || (a.rb_stride >= 256 && a.rb_stride % 4 == 0 && (long)a.n_var * a.rb_stride < (1l << 31)),
+               "ato: row-variant table in global memory needs 16-byte aligned rows and n_var * rb_stride < 2^31");
   RAMP_REQUIRE((long)a.M * 3072 < (1l << 32), "ato: 32-bit row offsets bound M to 1398100 tokens");
   RAMP_REQUIRE(!ranges_overlap(a.Y, (size_t)a.M * 1024, a.resid, (size_t)a.M * 1024) && !ranges_overlap(a.Y, (size_t)a.M * 1024, a.QKV, (size_t)a.M * 3072),
                "ato: the output must not overlap the residual or qkv");
   const int T = 16 * ng, n_tiles = (a.M + 4 * T - 1) / (4 * T);
   const int nb = std::min(n_tiles, device_cu_count());
 #define AT_GO(NGV, RBV) hipLaunchKernelGGL((ato_kernel<NGV, RBV>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles)
+  const bool many = a.rowbias && a.n_var > 4;
   if (a.stamps) {
-    RAMP_REQUIRE(ng == 3 && a.rowbias, "ato: the stamped twins exist for T = 48 with the row-variant constant");
+    RAMP_REQUIRE(ng == 3 && a.rowbias && !many, "ato: the stamped twins exist for T = 48 with the row-variant constant of at most 4 variants");
     if (a.ablate == 2) hipLaunchKernelGGL((ato_kernel<3, true, 3>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles);
     else if (a.ablate == 4) hipLaunchKernelGGL((ato_kernel<3, true, 5>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles);
     else if (a.ablate == 6) hipLaunchKernelGGL((ato_kernel<3, true, 7>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles);
     else hipLaunchKernelGGL((ato_kernel<3, true, 1>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles);
+  }
+  else if (many) {
+    if (ng == 3) hipLaunchKernelGGL((ato_kernel<3, true, 8>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles);
+    else hipLaunchKernelGGL((ato_kernel<2, true, 8>), dim3(nb), dim3(256), AT_LDS, s, a, n_tiles);
   }
   else if (ng == 3) { if (a.rowbias) AT_GO(3, true); else AT_GO(3, false); }
   else { if (a.rowbias) AT_GO(2, true); else AT_GO(2, false); }
@@ -560,6 +576,8 @@ int init_atk_attributes() {
   AT_ATTR(3, true); AT_ATTR(3, false); AT_ATTR(2, true); AT_ATTR(2, false);
 #undef AT_ATTR
   AT_ATTR3(1); AT_ATTR3(3); AT_ATTR3(5); AT_ATTR3(7);
+  AT_ATTR3(8);                                              // the many-variant product variants (row constant from global memory)
+  RAMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&ato_kernel<2, true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)AT_LDS));
   return 0;
 }
 

@@ -109,6 +109,9 @@ struct ramp_ctx {
   // time table / scene
   float* time_table = nullptr; int tt_stride = 0, tt_T = 0; float* time_temb = nullptr;
   float* cross_bias = nullptr; int n_variants = 0; int* row_variant = nullptr; int row_variant_cap = 0;
+  int cross_bias_cap = 0;            // variants the cross_bias allocation holds (n_variants: the ones the current scene table uses)
+  int rv_rows = 0;                   // > 0: the row -> variant table is an EXPLICIT one of that many rows (ramp_set_scenes); 0: a cyclic pattern over the whole capacity
+  unsigned scene_epoch = 0;          // identity of the scene table: counts ramp_set_scene / ramp_set_scenes calls
   int n_blocks_total = 0;
   // device pointer tables for setup kernels
   void* d_ptr_tables = nullptr;
@@ -118,6 +121,7 @@ struct ramp_ctx {
   unsigned long long* s_philox = nullptr;      // device {seed, offset} of a job that draws its own noise (ramp_sample_params.noise_mode 1)
   int* s_hard_idx = nullptr; float* s_hard_val = nullptr; size_t s_hard_val_cap = 0; float* s_window = nullptr;
   float* s_cloud = nullptr; size_t s_cloud_cap = 0;
+  int *s_traj_scene = nullptr, *s_scene_off = nullptr; size_t s_traj_scene_cap = 0, s_scene_off_cap = 0;      // per-scene APF of ramp_sample_scenes
   // graph cache
   hipGraphExec_t graph_exec[2] = {nullptr, nullptr}; std::string graph_key;   // [0] first evaluation calibrates, [1] it continues
   // Round 6: a job the range guard flagged is repeated IN fp16x3 (ramp_set_fallback(ctx, 2)): the guard's state after every evaluation of a
@@ -510,7 +514,7 @@ struct Run {
   // self-attention + output projection (+ bias, + the row variant's cross-attention constant, + residual) in one launch of
   // sample-owning waves (atk.hip); consumes the call site of the out-projection launch it replaces (same operand o, same maxima)
   bool use_ato(const STBlock& k, int M, int L) const {
-    return k.ato_w && c->atk_min_rows > 0 && M >= c->atk_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe && c->n_variants <= 4 &&
+    return k.ato_w && c->atk_min_rows > 0 && M >= c->atk_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe &&
            ato_applicable(M, L, nullptr);
   }
   bool use_atb(int M, int L) const {
@@ -752,7 +756,7 @@ int st_forward(Run& r, ST& m, const float* x, int share = 1) {
     GemmArgs a = lin(c->t_o, D, k.wo_f, k.bo, pre ? c->t_ln : k.a_z1, D, Mb, D, D);
     a.resid = zin; a.ldr = D; a.L = m.L;
     if (!pre) { a.rowbias = rowbias; a.rb_stride = rb_stride; a.rowvar = c->row_variant; a.row0 = r.row0; }
-    if (r.use_tkl(a) && (!a.rowbias || c->n_variants <= 4)) CK(r.tkl(a, nullptr, nullptr)); else CK(r.gemm(a));
+    if (r.use_tkl(a)) CK(r.tkl(a, nullptr, nullptr)); else CK(r.gemm(a));
     }
     if (pre) LAUNCH(c, r.s, CAT_ROW, 0, launch_expand_rows(c->t_ln, k.a_z1, R, share, m.L, D, rowbias, rb_stride, c->row_variant, r.row0, r.s));
     if (r.use_ffx(k, M)) {      // LN3 -> FF1 -> GEGLU -> FF2 -> + z1 in one launch, nothing but the stash and z2 written
@@ -1130,6 +1134,7 @@ int score_all(ramp_ctx* c, const float* x, int B, int n_rp, int t, float* f_out,
   RAMP_REQUIRE(c->cross_bias != nullptr, "ramp_set_scene has not been called");
   RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= 3, "bad batch");
   RAMP_REQUIRE(c->row_variant_cap >= B * n_rp, "row-variant table shorter than the batch (call ramp_set_scene after sizing)");
+  RAMP_REQUIRE(c->rv_rows == 0 || B * n_rp <= c->rv_rows, "the batch has more rows (B * n_rp) than the row -> variant table given to ramp_set_scenes");
   const int cap_traj = c->cfg.max_rows / n_rp;
   RAMP_REQUIRE(cap_traj >= 1, "max_rows smaller than n_rp");
   for (int b0 = 0; b0 < B; b0 += cap_traj) {
@@ -1538,43 +1543,69 @@ int ramp_time_embedding(ramp_ctx* c, int32_t t, float* out32, void* stream) {
   return 0;
 }
 
+// cross-attention constants of `n_variants` latents (cross_bias_kernel) + the row -> variant table: a cyclic pattern over the table's whole
+// capacity (n_rows == 0: ramp_set_scene) or the n_rows explicit entries (ramp_set_scenes); `table` is host memory
+static int set_scene_table(ramp_ctx* c, const float* latents, int n_variants, const int32_t* table, int n_table, int n_rows, hipStream_t s) {
+  const int nb = c->n_blocks_total;
+  if (n_variants > c->cross_bias_cap) { CK(dev_alloc(c, &c->cross_bias, (size_t)n_variants * nb * 256)); c->cross_bias_cap = n_variants; }
+  c->n_variants = n_variants;
+  std::vector<const float*> wv(nb), wo(nb), bo(nb);
+  for (auto& st : c->sts) for (int b = 0; b < 2; ++b) {
+    wv[st.blk0 + b] = st.blk[b].wv2; wo[st.blk0 + b] = st.blk[b].wo2; bo[st.blk0 + b] = st.blk[b].bo2;
+  }
+  // row -> variant table for the largest batch this context may see in one ramp_sample call
+  const int want = std::max(std::max(c->row_variant_cap, 1 << 20), n_rows);
+  if (c->row_variant_cap < want) {
+    float* p; CK(dev_alloc(c, &p, want)); c->row_variant = reinterpret_cast<int*>(p); c->row_variant_cap = want;
+  }
+  char* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, 3 * nb * sizeof(void*) + (n_rows ? 0 : n_table * sizeof(int))));
+  auto body = [&]() -> int {
+    RAMP_HIP_CHECK(hipMemcpy(d, wv.data(), nb * sizeof(void*), hipMemcpyHostToDevice));
+    RAMP_HIP_CHECK(hipMemcpy(d + nb * sizeof(void*), wo.data(), nb * sizeof(void*), hipMemcpyHostToDevice));
+    RAMP_HIP_CHECK(hipMemcpy(d + 2 * nb * sizeof(void*), bo.data(), nb * sizeof(void*), hipMemcpyHostToDevice));
+    if (!n_rows) RAMP_HIP_CHECK(hipMemcpy(d + 3 * nb * sizeof(void*), table, n_table * sizeof(int), hipMemcpyHostToDevice));
+    CK(launch_cross_bias(latents, n_variants, c->cfg.context_dim, reinterpret_cast<const float* const*>(d),
+                         reinterpret_cast<const float* const*>(d + nb * sizeof(void*)),
+                         reinterpret_cast<const float* const*>(d + 2 * nb * sizeof(void*)), nb, c->cross_bias, s));
+    if (n_rows) {
+      RAMP_HIP_CHECK(hipStreamSynchronize(s));                // (hipMemcpy below is ordered against the NULL stream only)
+      RAMP_HIP_CHECK(hipMemcpy(c->row_variant, table, (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice));
+    } else {
+      hipLaunchKernelGGL(fill_pattern_kernel, dim3(1024), dim3(256), 0, s, c->row_variant,
+                         reinterpret_cast<const int*>(d + 3 * nb * sizeof(void*)), n_table, c->row_variant_cap);
+      RAMP_HIP_CHECK(hipGetLastError());
+    }
+    RAMP_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  };
+  const int rc = body();
+  (void)hipFree(d);
+  c->rv_rows = n_rows;
+  c->scene_epoch++;
+  c->graph_key.clear();     // scene changed: cross_bias pointer may have moved
+  c->r_key.clear();
+  c->score_calibrated = false; c->r_calibrated = false; c->s_calibrated = false; c->s_pending = false; c->c_cal_valid = false;
+  return rc;
+}
+
 int ramp_set_scene(ramp_ctx* c, const float* latents, int32_t n_variants, const int32_t* row_variant_host,
                    int32_t n_rows_pattern, void* stream) {
   RAMP_REQUIRE(c && c->finalized && latents && n_variants >= 1 && n_variants <= 8, "bad arguments");
   RAMP_REQUIRE(row_variant_host && n_rows_pattern >= 1 && n_rows_pattern <= 64, "bad row-variant pattern");
   for (int i = 0; i < n_rows_pattern; ++i)
     RAMP_REQUIRE(row_variant_host[i] >= 0 && row_variant_host[i] < n_variants, "row variant out of range");
-  hipStream_t s = as_stream(stream);
-  const int nb = c->n_blocks_total;
-  if (n_variants > c->n_variants) { CK(dev_alloc(c, &c->cross_bias, (size_t)n_variants * nb * 256)); c->n_variants = n_variants; }
-  std::vector<const float*> wv(nb), wo(nb), bo(nb);
-  for (auto& st : c->sts) for (int b = 0; b < 2; ++b) {
-    wv[st.blk0 + b] = st.blk[b].wv2; wo[st.blk0 + b] = st.blk[b].wo2; bo[st.blk0 + b] = st.blk[b].bo2;
-  }
-  char* d = nullptr;
-  RAMP_HIP_CHECK(hipMalloc(&d, 3 * nb * sizeof(void*) + n_rows_pattern * sizeof(int)));
-  RAMP_HIP_CHECK(hipMemcpy(d, wv.data(), nb * sizeof(void*), hipMemcpyHostToDevice));
-  RAMP_HIP_CHECK(hipMemcpy(d + nb * sizeof(void*), wo.data(), nb * sizeof(void*), hipMemcpyHostToDevice));
-  RAMP_HIP_CHECK(hipMemcpy(d + 2 * nb * sizeof(void*), bo.data(), nb * sizeof(void*), hipMemcpyHostToDevice));
-  RAMP_HIP_CHECK(hipMemcpy(d + 3 * nb * sizeof(void*), row_variant_host, n_rows_pattern * sizeof(int), hipMemcpyHostToDevice));
-  int rc = launch_cross_bias(latents, n_variants, c->cfg.context_dim, reinterpret_cast<const float* const*>(d),
-                             reinterpret_cast<const float* const*>(d + nb * sizeof(void*)),
-                             reinterpret_cast<const float* const*>(d + 2 * nb * sizeof(void*)), nb, c->cross_bias, s);
-  // row -> variant table for the largest batch this context may see in one ramp_sample call
-  const int want = std::max(c->row_variant_cap, 1 << 20);
-  if (rc == 0 && c->row_variant_cap < want) {
-    float* p; rc = dev_alloc(c, &p, want); c->row_variant = reinterpret_cast<int*>(p); c->row_variant_cap = want;
-  }
-  if (rc == 0) {
-    hipLaunchKernelGGL(fill_pattern_kernel, dim3(1024), dim3(256), 0, s, c->row_variant,
-                       reinterpret_cast<const int*>(d + 3 * nb * sizeof(void*)), n_rows_pattern, c->row_variant_cap);
-  }
-  RAMP_HIP_CHECK(hipStreamSynchronize(s));
-  RAMP_HIP_CHECK(hipFree(d));
-  c->graph_key.clear();     // scene changed: cross_bias pointer may have moved
-  c->r_key.clear();
-  c->score_calibrated = false; c->r_calibrated = false; c->s_calibrated = false; c->s_pending = false; c->c_cal_valid = false;
-  return rc;
+  return set_scene_table(c, latents, n_variants, row_variant_host, n_rows_pattern, 0, as_stream(stream));
+}
+
+int ramp_set_scenes(ramp_ctx* c, const float* latents, int32_t n_variants, const int32_t* row_variant_host, int32_t n_rows,
+                    void* stream) {
+  RAMP_REQUIRE(c && c->finalized && latents && n_variants >= 1 && n_variants <= 65536, "bad arguments (1 .. 65536 latent variants)");
+  RAMP_REQUIRE((long)n_variants * c->n_blocks_total * 256 < (1l << 31), "too many variants for 32-bit offsets into the cross-attention constants");
+  RAMP_REQUIRE(row_variant_host && n_rows >= 1 && n_rows <= (1 << 24), "bad row -> variant table");
+  for (int i = 0; i < n_rows; ++i)
+    RAMP_REQUIRE(row_variant_host[i] >= 0 && row_variant_host[i] < n_variants, "row variant out of range");
+  return set_scene_table(c, latents, n_variants, row_variant_host, n_rows, n_rows, as_stream(stream));
 }
 
 int ramp_encode_scene(ramp_ctx* c, const float* cloud, int32_t n_obstacles, int32_t n_points, int32_t point_dim,
@@ -1633,7 +1664,8 @@ int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, 
   return 0;
 }
 
-static int sample_body(ramp_ctx* c, const ramp_sample_params* p, hipStream_t s, bool chain, bool steady, int cal_eval = -1) {
+// sc != nullptr: a job of many scenes (ramp_sample_scenes) -- the APF of trajectory b runs against the cloud of scene traj_scene[b]
+static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -1647,6 +1679,8 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, hipStream_t s, 
   if (chain) RAMP_HIP_CHECK(hipMemcpyAsync(c->s_chain, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   ApfArgs ap; ap.cloud = c->s_cloud; ap.window = c->s_window; ap.B = B; ap.H = H; ap.S = S; ap.P = p->apf.n_points;
   ap.win = p->apf.window; ap.thr = p->apf.threshold; ap.strength = p->apf.strength;
+  const bool sc_apf = sc && sc->cloud_points;
+  if (sc_apf) { ap.scene = c->s_traj_scene; ap.scene_off = c->s_scene_off; ap.n_scenes = sc->n_scenes; ap.P = 0; }
   if (c->gemm_mode == 2) {
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
     if (!c->force_x6) hipLaunchKernelGGL(zero_words_kernel, dim3((p->n_steps + 255) / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->trip_log), p->n_steps);
@@ -1683,7 +1717,7 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, hipStream_t s, 
     m.w0 = (float)p->w0; m.w1 = (float)p->w1; m.w0p1 = (float)(1.0 + p->w0);
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
     float* chain_j = chain ? c->s_chain + (size_t)(j + 1) * n : nullptr;
-    const bool apf = p->apf.cloud != nullptr && p->apply_apf && p->apply_apf[j];
+    const bool apf = (p->apf.cloud != nullptr || sc_apf) && p->apply_apf && p->apply_apf[j];
     if (!p->ddim) {
       m.coef1 = p->coef1[j]; m.coef2 = p->coef2[j]; m.mean = c->s_mean; m.x0 = nullptr;
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_cfg_mean(m, s));
@@ -1746,8 +1780,8 @@ int ramp_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, vo
   return rc;
 }
 
-int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, float* chain_out, float* x_out,
-                void* stream) {
+static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
+                      void* stream) {
   RAMP_REQUIRE(c && p, "null argument");
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
@@ -1782,6 +1816,29 @@ int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, fl
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_window, p->apf.window_weights_host, (2 * p->apf.window + 1) * 4, hipMemcpyHostToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_cloud, p->apf.cloud, (size_t)p->apf.n_points * 8, hipMemcpyDeviceToDevice, s));
   }
+  const bool sc_apf = sc && sc->cloud_points;
+  int sc_points = 0;
+  if (sc) {
+    RAMP_REQUIRE(!p->apf.cloud, "ramp_sample_scenes: apf.cloud must be NULL (the clouds come with the scene batch)");
+    RAMP_REQUIRE(sc->n_scenes >= 1 && sc->traj_scene, "ramp_sample_scenes: bad scene batch");
+  }
+  if (sc_apf) {
+    RAMP_REQUIRE(sc->cloud_offset_host && sc->cloud_offset_host[0] == 0, "ramp_sample_scenes: cloud offsets must start at 0");
+    for (int i = 0; i < sc->n_scenes; ++i)
+      RAMP_REQUIRE(sc->cloud_offset_host[i + 1] > sc->cloud_offset_host[i], "ramp_sample_scenes: every scene needs at least one cloud point (increasing offsets)");
+    sc_points = sc->cloud_offset_host[sc->n_scenes];
+    RAMP_REQUIRE(p->apf.window >= 0 && p->apf.window <= 64 && p->apf.window_weights_host, "bad APF params");
+    if (!c->s_window) CK(dev_alloc(c, &c->s_window, 256));
+    if ((size_t)sc_points * 2 > c->s_cloud_cap) { CK(dev_alloc(c, &c->s_cloud, (size_t)sc_points * 2)); c->s_cloud_cap = (size_t)sc_points * 2; c->graph_key.clear(); }
+    if ((size_t)B > c->s_traj_scene_cap) { float* q; CK(dev_alloc(c, &q, B)); c->s_traj_scene = reinterpret_cast<int*>(q); c->s_traj_scene_cap = B; c->graph_key.clear(); }
+    if ((size_t)sc->n_scenes + 1 > c->s_scene_off_cap) {
+      float* q; CK(dev_alloc(c, &q, sc->n_scenes + 1)); c->s_scene_off = reinterpret_cast<int*>(q); c->s_scene_off_cap = (size_t)sc->n_scenes + 1; c->graph_key.clear();
+    }
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_window, p->apf.window_weights_host, (2 * p->apf.window + 1) * 4, hipMemcpyHostToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_cloud, sc->cloud_points, (size_t)sc_points * 8, hipMemcpyDeviceToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_scene_off, sc->cloud_offset_host, ((size_t)sc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
+  }
   if (p->n_hard) {
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_val, p->hard_val, hv * 4, hipMemcpyDeviceToDevice, s));
@@ -1811,6 +1868,7 @@ int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, fl
     const int has_apf = p->apf.cloud != nullptr; put(&has_apf, 4);
     put(&p->apf.n_points, 4); put(&p->apf.window, 4); put(&p->apf.threshold, 8); put(&p->apf.strength, 8); put(&p->apf.passes, 4);
     const int ch = chain; put(&ch, 4); put(&c->force_x6, 4); put(&p->noise_mode, 4);
+    if (sc) { const int tag[3] = {0x5343454e /* "SCEN" */, sc_apf ? sc->n_scenes : 0, sc_points}; put(tag, 12); }      // (a single-scene job's key has no such tail)
   }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   steady = h3 && c->cal_reuse;
@@ -1822,6 +1880,7 @@ int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, fl
     auto putc = [&](const void* q, size_t b) { ck.append(static_cast<const char*>(q), b); };
     putc(&p->B, 4); putc(&p->n_rp, 4); putc(p->t, 4); putc(&p->w0, 8); putc(&p->w1, 8);
     const int sp = c->share_prefix; putc(&sp, 4);
+    putc(&c->scene_epoch, 4);                               // the scene table's identity; redundant today: set_scene_table drops every saved table (c_cal_valid)
     if (!c->c_cal_valid) {                                  // (scene / plan / mode changed: every saved table is stale; its buffer is reused)
       for (auto& kv : c->c_cal_saved) c->c_cal_free.push_back(kv.second);
       c->c_cal_saved.clear();
@@ -1848,7 +1907,7 @@ int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, fl
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
   c->last_job_steps = h3 ? p->n_steps : 0;
   if (!p->use_graph) {
-    CK(sample_body(c, p, s, chain, steady, cal_eval));
+    CK(sample_body(c, p, sc, s, chain, steady, cal_eval));
   } else {
     if (key != c->graph_key) {
       for (auto& g : c->graph_exec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
@@ -1868,7 +1927,7 @@ int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, fl
       RAMP_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
       RAMP_HIP_CHECK(hipStreamSynchronize(s));
       RAMP_HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      int rc = sample_body(c, p, cs, chain, steady, cal_eval);
+      int rc = sample_body(c, p, sc, cs, chain, steady, cal_eval);
       hipGraph_t g = nullptr;
       hipError_t e = hipStreamEndCapture(cs, &g);
       if (rc != 0) { if (g) (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs); return rc; }
@@ -1882,6 +1941,17 @@ int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, fl
   if (chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
   if (x_out) RAMP_HIP_CHECK(hipMemcpyAsync(x_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
+}
+
+int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, float* chain_out, float* x_out,
+                void* stream) {
+  return sample_job(c, p, nullptr, noise, chain_out, x_out, stream);
+}
+
+int ramp_sample_scenes(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* scenes, const float* noise, float* chain_out,
+                       float* x_out, void* stream) {
+  RAMP_REQUIRE(scenes, "null scene batch");
+  return sample_job(c, p, scenes, noise, chain_out, x_out, stream);
 }
 
 // ---- receding-horizon replanning --------------------------------------------------------------------

@@ -105,6 +105,35 @@ int ramp_apf(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf_params
   return g_ring.done(s);
 }
 
+int ramp_apf_scenes(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf_params* p, const ramp_scene_batch* sc,
+                    void* stream) {
+  RAMP_REQUIRE(traj && p && sc && p->window_weights_host, "null argument");
+  RAMP_REQUIRE(!p->cloud, "ramp_apf_scenes: apf.cloud must be NULL (the clouds come with the scene batch)");
+  RAMP_REQUIRE(p->window >= 0 && p->window <= 64, "bad window");
+  RAMP_REQUIRE(sc->n_scenes >= 1 && sc->traj_scene && sc->cloud_points && sc->cloud_offset_host && sc->cloud_offset_host[0] == 0,
+               "ramp_apf_scenes: bad scene batch (at least one scene, offsets from 0)");
+  for (int i = 0; i < sc->n_scenes; ++i)
+    RAMP_REQUIRE(sc->cloud_offset_host[i + 1] > sc->cloud_offset_host[i], "ramp_apf_scenes: every scene needs at least one cloud point (increasing offsets)");
+  hipStream_t s = as_stream(stream);
+  // window weights | scene offsets in one block of its own (the offsets of many scenes outgrow a slot of the host-argument ring);
+  // synchronises `stream`
+  const int nw = 2 * p->window + 1;
+  std::vector<int32_t> blk(nw + sc->n_scenes + 1);
+  std::memcpy(blk.data(), p->window_weights_host, nw * 4);
+  std::memcpy(blk.data() + nw, sc->cloud_offset_host, (sc->n_scenes + 1) * 4);
+  int32_t* w = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&w, blk.size() * 4));
+  int rc = 0;
+  if (hipMemcpy(w, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("ramp_apf_scenes: copy of the tables failed"); rc = -1; }
+  ApfArgs a; a.traj = traj; a.cloud = sc->cloud_points; a.window = reinterpret_cast<const float*>(w); a.B = B; a.H = H; a.S = S;
+  a.win = p->window; a.thr = p->threshold; a.strength = p->strength;
+  a.scene = sc->traj_scene; a.scene_off = w + nw; a.n_scenes = sc->n_scenes;
+  for (int q = 0; rc == 0 && q < std::max(1, p->passes); ++q) rc = launch_apf(a, s);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(w);
+  return rc;
+}
+
 int ramp_apf_dynamic(float* traj, int32_t B, int32_t H, int32_t S, const double* points, int32_t n_points,
                      double thr_query, double thr_force, double strength, int32_t window, int32_t affected,
                      const float* goal, const int32_t* enable, void* stream) {

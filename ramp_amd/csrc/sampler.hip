@@ -147,6 +147,10 @@ int launch_hard_cond(float* x, HardConds hc, int B, int H, int S, hipStream_t s)
 constexpr int APF_TILE = 1024;
 constexpr int APF_MAXH = 128;
 
+// SC: the trajectory's own cloud (ApfArgs.scene): block b streams only the points of its scene, indexed from that cloud's first
+// point, so every comparison, tie and sum is the single-cloud kernel's on that cloud.  A scene index outside the table leaves the
+// trajectory as it is.
+template <bool SC>
 __global__ __launch_bounds__(256) void apf_kernel(ApfArgs a) {
   __shared__ double2 cl[APF_TILE];
   __shared__ double best_d2[APF_MAXH];
@@ -157,6 +161,12 @@ __global__ __launch_bounds__(256) void apf_kernel(ApfArgs a) {
   __shared__ int hitf[APF_MAXH];
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* tr = a.traj + (long)b * a.H * a.S;
+  if (SC) {
+    const int sc = a.scene[b];
+    if (sc < 0 || sc >= a.n_scenes) return;                  // (uniform over the block)
+    const int first = a.scene_off[sc];
+    a.cloud += 2l * first; a.P = a.scene_off[sc + 1] - first;
+  }
   for (int h = tid; h < a.H; h += 256) { best_d2[h] = 1.0e300; best_i[h] = -1; }
   for (int p0 = 0; p0 < a.P; p0 += APF_TILE) {
     const int np = min(APF_TILE, a.P - p0);
@@ -214,8 +224,10 @@ __global__ __launch_bounds__(256) void apf_kernel(ApfArgs a) {
   }
 }
 int launch_apf(const ApfArgs& a, hipStream_t s) {
-  RAMP_REQUIRE(a.B > 0 && a.H > 0 && a.H <= APF_MAXH && a.S >= 2 && a.P > 0 && a.win >= 0, "bad APF dims");
-  hipLaunchKernelGGL(apf_kernel, dim3(a.B), dim3(256), 0, s, a);
+  RAMP_REQUIRE(a.B > 0 && a.H > 0 && a.H <= APF_MAXH && a.S >= 2 && (a.P > 0 || a.scene) && a.win >= 0, "bad APF dims");
+  RAMP_REQUIRE(!a.scene || (a.scene_off && a.n_scenes > 0), "APF with per-trajectory scenes needs the scene offset table");
+  if (a.scene) hipLaunchKernelGGL(apf_kernel<true>, dim3(a.B), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(apf_kernel<false>, dim3(a.B), dim3(256), 0, s, a);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }

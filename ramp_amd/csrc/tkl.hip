@@ -36,7 +36,8 @@ constexpr size_t TK_LDS = (size_t)TK_RB + 4 * 256 * 4;
 static_assert(TK_LDS <= 160 * 1024, "LDS budget");
 }  // namespace
 
-// EPI: bit 0 residual, bit 1 row-variant bias.  ABL (diagnostic, ramp_bench_gemm): 1 no LDS-DMA, 2 no stores, 8 no barrier
+// EPI: bit 0 residual, bit 1 row-variant bias, bit 2 (with bit 1) its rows stay in global memory -- more variants than the LDS table
+// holds: a job of many scenes, ramp_set_scenes; each row's constants are requested one epilogue step ahead of their use (step 2; earlier costs spills) and come from the L2.  ABL (diagnostic, ramp_bench_gemm): 1 no LDS-DMA, 2 no stores, 8 no barrier
 template <bool LN, int EPI, int ABL = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void tkl_kernel(TklArgs a, int n_mt) {
@@ -136,7 +137,7 @@ void tkl_kernel(TklArgs a, int n_mt) {
     for (int i = tid; i < a.N; i += 256) bsw[i] = a.bias ? a.bias[i] : 0.f;
     float* lns = reinterpret_cast<float*>(smem + TK_LN);
     if (LN) { lns[tid] = a.ln_g[tid]; lns[256 + tid] = a.ln_b[tid]; }
-    if (EPI & 2) {
+    if ((EPI & 6) == 2) {
       float* rbs = reinterpret_cast<float*>(smem + TK_RB);
       for (int v = 0; v < a.n_var; ++v) rbs[v * 256 + tid] = a.rowbias[(long)v * a.rb_stride + tid];
     }
@@ -204,13 +205,13 @@ void tkl_kernel(TklArgs a, int n_mt) {
     // with the same bits: every lane issues every load and store)
     // (addresses are formed where they are used, from a tile index hipcc cannot see through: as per-tile arrays of row
     // pointers they were spilled and every slab reloaded them from scratch behind an s_waitcnt vmcnt(0))
-    int rbo[4] = {0, 0, 0, 0};                              // LDS offset of each row's variant constants
+    int rbo[4] = {0, 0, 0, 0};                              // LDS offset of each row's variant constants (EPI bit 2: offset into a.rowbias)
     if (EPI & 2) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         long t = (long)mt * 128 + wave * 32 + 8 * j + l8;
         t = t < a.M ? t : a.M - 1;
-        rbo[j] = a.rowvar[a.row0 + (int)(t / a.L)] * 256 + c4;
+        rbo[j] = a.rowvar[a.row0 + (int)(t / a.L)] * ((EPI & 4) ? a.rb_stride : 256) + c4;
       }
     }
     auto row_of = [&](int j) __attribute__((always_inline)) {
@@ -234,9 +235,13 @@ void tkl_kernel(TklArgs a, int n_mt) {
       } else if (st == 2) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) tv[j] = *reinterpret_cast<const f32x4*>(tw_r + 8 * j * TK_TROW);
+        if ((EPI & 6) == 6) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) rbq[j] = *reinterpret_cast<const f32x4*>(a.rowbias + rbo[j] + 32 * pb);
+        }
       } else if (st == 3) {
         bq = *reinterpret_cast<const f32x4*>(bs + 32 * pb);
-        if (EPI & 2) {
+        if ((EPI & 6) == 2) {
 #pragma unroll
           for (int j = 0; j < 4; ++j) rbq[j] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(smem + TK_RB) + rbo[j] + 32 * pb);
         }
@@ -510,7 +515,10 @@ int launch_tkl(const TklArgs& a, hipStream_t s) {
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   RAMP_REQUIRE(a.M > 0 && a.N >= 32 && a.N <= 768 && a.N % 32 == 0 && a.X && a.Y && a.W, "tkl: bad operand");
   RAMP_REQUIRE(al16(a.X) && al16(a.Y) && al16(a.W) && al16(a.resid) && a.ldy % 4 == 0 && a.ldr % 4 == 0, "tkl: operands must be 16-byte aligned");
-  RAMP_REQUIRE(!a.rowbias || (a.rowvar && a.N == 256 && a.n_var >= 1 && a.n_var <= 4 && a.L >= 1 && a.resid), "tkl: row-variant bias needs N = 256, <= 4 variants, a residual");
+  RAMP_REQUIRE(!a.rowbias || (a.rowvar && a.N == 256 && a.n_var >= 1 && a.L >= 1 && a.resid), "tkl: row-variant bias needs N = 256, the row -> variant table, a residual");
+  // more than 4 variants (a job of many scenes): the constants are read from global memory, 16 bytes per lane at 32-bit element offsets
+  RAMP_REQUIRE(!a.rowbias || a.n_var <= 4 || (al16(a.rowbias) && a.rb_stride >= 256 && a.rb_stride % 4 == 0 && (long)a.n_var * a.rb_stride < (1l << 31)),
+               "tkl: row-variant table in global memory needs 16-byte aligned rows and n_var * rb_stride < 2^31");
   RAMP_REQUIRE(!a.ln_g == !a.ln_b, "tkl: LayerNorm needs gamma and beta");
   {   // rows past M are recomputed and rewritten from the inputs (unconditional stores): an in-place residual (Y == resid) would add
       // the last row's update twice when M is not a multiple of 128
@@ -529,7 +537,8 @@ int launch_tkl(const TklArgs& a, hipStream_t s) {
     if (ln && epi == 0) TK_GO(true, 0, 0);
     else if (!ln && epi == 0) TK_GO(false, 0, 0);
     else if (!ln && epi == 1) TK_GO(false, 1, 0);
-    else if (!ln && epi == 3) TK_GO(false, 3, 0);
+    else if (!ln && epi == 3 && a.n_var <= 4) TK_GO(false, 3, 0);
+    else if (!ln && epi == 3) TK_GO(false, 7, 0);
     else RAMP_REQUIRE(false, "tkl: variant not built");
   }
   TK_ABL(1) TK_ABL(2) TK_ABL(8) TK_ABL(3)
@@ -542,7 +551,7 @@ int launch_tkl(const TklArgs& a, hipStream_t s) {
 
 int init_tkl_attributes() {
 #define TK_ATTR(LNV, E, A) RAMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tkl_kernel<LNV, E, A>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TK_LDS))
-  TK_ATTR(true, 0, 0); TK_ATTR(false, 0, 0); TK_ATTR(false, 1, 0); TK_ATTR(false, 3, 0);
+  TK_ATTR(true, 0, 0); TK_ATTR(false, 0, 0); TK_ATTR(false, 1, 0); TK_ATTR(false, 3, 0); TK_ATTR(false, 7, 0);
 #define TK_ATTR3(A) TK_ATTR(true, 0, A); TK_ATTR(false, 1, A); TK_ATTR(false, 0, A)
   TK_ATTR3(1); TK_ATTR3(2); TK_ATTR3(8); TK_ATTR3(3);
 #undef TK_ATTR3

@@ -244,14 +244,16 @@ class _GaussianDiffusionBase(nn.Module):
         return idx, val
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
-                return_chain: bool, ddim_K: Optional[int] = None):
-        """Fill ramp_sample_params from the schedule buffers exactly as the reference's extract() would."""
+                return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None):
+        """Fill ramp_sample_params from the schedule buffers exactly as the reference's extract() would.  ``scene_job``: what
+        ``_prepare_scene_job`` returned -- a job of many scenes (``ramp_sample_scenes``); ``obstacle_pts`` is not read then."""
         m = self.model
         dev = self._device()
         H, S = m.n_support_points, self.state_dim
         n_steps = len(steps)
         m.prepare_time_table(self.n_diffusion_steps)
-        self._prepare_scene(obstacle_pts, B)
+        if scene_job is None:      # (run_inference_scenes: the scene table is already set, set_scenes)
+            self._prepare_scene(obstacle_pts, B)
         buf = {k: getattr(self, k).detach().cpu() for k in
                ('alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod',
                 'posterior_mean_coef1', 'posterior_mean_coef2', 'posterior_log_variance_clipped')}
@@ -300,7 +302,22 @@ class _GaussianDiffusionBase(nn.Module):
         p.hard_idx_host = arr_i(idx) if idx else None
         p.hard_val = _lib.ptr(val) if idx else None
         cloud = None
-        if apf_cfg is not None and any(apply_apf):
+        batch = None
+        if scene_job is not None:
+            batch = _lib.RampSceneBatch()
+            batch.n_scenes = scene_job['n_scenes']
+            batch.traj_scene = _lib.ptr(scene_job['traj_scene'])
+            if apf_cfg is not None and any(apply_apf):
+                w = self._window_weights(apf_cfg['window']).contiguous()
+                keep.append(w)
+                batch.cloud_points = _lib.ptr(scene_job['cloud_points'])
+                batch.cloud_offset_host = scene_job['cloud_offset'].ctypes.data_as(_lib.c_i32p)
+                p.apf.window = int(apf_cfg['window'])
+                p.apf.window_weights_host = C.cast(w.data_ptr(), _lib.c_f32p)
+                p.apf.threshold = float(apf_cfg['threshold'])
+                p.apf.strength = float(apf_cfg['strength'])
+                p.apf.passes = int(apf_cfg.get('passes', 1))
+        elif apf_cfg is not None and any(apply_apf):
             if self.compose:      # first six obstacles of scene A + first four of scene B (static.py:306-310)
                 cloud = torch.cat([obstacle_pts[0], obstacle_pts[1][:4]], dim=0).reshape(-1, 2)
             else:
@@ -331,8 +348,16 @@ class _GaussianDiffusionBase(nn.Module):
             noise = noise.contiguous()
         with torch.cuda.device(dev):
             lib = _lib.load()
-            _lib.check(lib.ramp_sample(m.ctx(), C.byref(p), _lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out),
-                                       _lib.current_stream()), "ramp_sample")
+
+            def job():
+                if batch is not None:
+                    _lib.check(lib.ramp_sample_scenes(m.ctx(), C.byref(p), C.byref(batch), _lib.ptr(noise), _lib.ptr(chain),
+                                                      _lib.ptr(x_out), _lib.current_stream()), "ramp_sample_scenes")
+                else:
+                    _lib.check(lib.ramp_sample(m.ctx(), C.byref(p), _lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out),
+                                               _lib.current_stream()), "ramp_sample")
+
+            job()
             flag = C.c_int32(0)
             _lib.check(lib.ramp_range_status(m.ctx(), C.byref(flag), _lib.current_stream()), "ramp_range_status")
             self.last_job_mode = {0: "fp16x3", 1: "fp32", 2: "bf16x6", 3: "fp16x3"}[m.gemm_mode]      # (0: the library default)
@@ -350,8 +375,7 @@ class _GaussianDiffusionBase(nn.Module):
                 def again(mode):
                     _lib.check(lib.ramp_set_fallback(m.ctx(), mode), "ramp_set_fallback")
                     try:
-                        _lib.check(lib.ramp_sample(m.ctx(), C.byref(p), _lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out),
-                                                   _lib.current_stream()), "ramp_sample")
+                        job()
                         f2 = C.c_int32(0)
                         _lib.check(lib.ramp_range_status(m.ctx(), C.byref(f2), _lib.current_stream()), "ramp_range_status")
                     finally:
@@ -386,12 +410,15 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
-                      noise_std_extra_schedule_fn=None, **sample_kwargs):
+                      noise_std_extra_schedule_fn=None, scene_job=None, **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
         reference's arguments -- on the eager loop below."""
         if not self._is_fused_ddpm_step(sample_fn):
+            if scene_job is not None:
+                raise NotImplementedError("run_inference_scenes runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
+                                          "scene's batch at a time -- use run_inference per scene")
             return self._p_sample_loop_stepwise(shape, hard_conds, context, return_chain, traj_normalized, obstacle_pts, sample_fn,
                                                 n_diffusion_steps_without_noise, noise_std_extra_schedule_fn, sample_kwargs)
         device = self._device()
@@ -415,7 +442,7 @@ class _GaussianDiffusionBase(nn.Module):
                for j in range(len(steps))]
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
-                                    cfg, return_chain)
+                                    cfg, return_chain, scene_job=scene_job)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -456,7 +483,7 @@ class _GaussianDiffusionBase(nn.Module):
 
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
-                           obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1,
+                           obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
                            **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
@@ -466,7 +493,7 @@ class _GaussianDiffusionBase(nn.Module):
         apf = [1 if (self.APF and self._supports_apf and j >= self.apf_ddim['start']) else 0 for j in range(len(steps))]
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
-                                    return_chain)
+                                    return_chain, scene_job=scene_job)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -516,6 +543,62 @@ class _GaussianDiffusionBase(nn.Module):
             return chain
         return chain[-1]
 
+    @torch.no_grad()
+    def _prepare_scene_job(self, scenes, hard_conds, n_samples):
+        """Encode every scene once, hand latents + row table to the context (``set_scenes``) and build what ``_launch`` needs for
+        a multi-scene job: (job dict, concatenated hard conditions, B)."""
+        from .scenes import build_scene_tables
+        if not self._scenes_supported:
+            raise NotImplementedError(f"{type(self).__name__} has no multi-scene job")
+        dev = self._device()
+        m = self.model
+        use_cloud = bool(self.APF and self._supports_apf)
+        sizes = [int(s.numel() // 2) if use_cloud else 1 for s in scenes]
+        tab = build_scene_tables(sizes, n_samples, [list(h.keys()) for h in hard_conds], n_rp=self._n_rp(), compose=self.compose)
+        counts = [int(c) for c in tab['counts']]
+        B = int(sum(counts))
+        hc = {}
+        for k in hard_conds[0].keys():
+            rows = []
+            for h, n in zip(hard_conds, counts):
+                v = h[k].to(dev, torch.float32)
+                v = v.unsqueeze(0).expand(n, -1) if v.dim() == 1 else v
+                if v.shape[0] != n:
+                    raise ValueError(f"hard condition {k}: {v.shape[0]} rows for a scene of {n} samples")
+                rows.append(v)
+            hc[k] = torch.cat(rows).contiguous()
+        m.ctx()
+        lat = torch.cat([m.encode_scene(s.to(dev)) for s in scenes] + [torch.zeros(1, m.context_dim, device=dev)])
+        m.set_scenes(lat, tab['row_variant'])
+        job = {'n_scenes': len(scenes), 'traj_scene': torch.from_numpy(tab['traj_scene']).to(dev), 'cloud_offset': tab['cloud_offset'],
+               'cloud_points': (torch.cat([s.reshape(-1, 2).to(dev, torch.float32) for s in scenes]).contiguous() if use_cloud else None)}
+        return job, hc, B
+
+    @torch.no_grad()
+    def run_inference_scenes(self, scenes, hard_conds, n_samples=1, return_chain=False, **diffusion_kwargs):
+        """Sample MANY scenes in ONE job: the loop over experiment directories of the reference's
+        scripts/inference/inference_static.py (one ``run_inference`` per experiment) as one batch.
+
+        scenes      list of ``obstacle_pts`` tensors (n_obstacles, n_points, dim), shapes may differ per scene
+        hard_conds  list of one dict per scene, the same waypoint indices in every scene; values (S,) or (n_i, S)
+        n_samples   trajectories per scene: an int, or one count per scene
+
+        Every scene is encoded once (``ramp_encode_scene``), the latents (one row per scene plus the shared all-zero
+        unconditional row), the row -> latent table and the per-scene APF clouds go to the context, and ONE job runs.  Returns
+        ``(result, traj_scene)``: what ``run_inference`` returns for the concatenated batch -- (steps + 1, B, H, S) if
+        ``return_chain`` else (B, H, S), a scene's samples adjacent, scenes in order -- and the (B,) int32 scene of each
+        trajectory.  A flagged job is repeated exactly as in ``run_inference``.  As in ``run_inference`` the sampler is the model's
+        own (``sampler='ddpm'`` -> the fused DDPM job, the DDIM default -> ``ddim_p_sample_loop``; ``conditional_sample`` decides by
+        the model's setting, not by its ``ddim`` argument) and ``guide`` / ``n_guide_steps`` / ``t_start_guide`` are accepted and
+        unused.  Not supported: compose, the dynamic planner, a caller-supplied ``sample_fn``."""
+        job, hc, B = self._prepare_scene_job(scenes, hard_conds, n_samples)
+        for k in ('guide', 'n_guide_steps', 't_start_guide'):
+            diffusion_kwargs.pop(k, None)
+        _samples, chain = self.conditional_sample(hc, batch_size=B, ddim=False, return_chain=True, obstacle_pts=None, scene_job=job,
+                                                  **diffusion_kwargs)
+        chain = chain.permute(1, 0, 2, 3)
+        return (chain if return_chain else chain[-1]), job['traj_scene']
+
     # ------------------------------------------------------------------ single-step compat API
     @torch.no_grad()
     def p_mean_variance(self, x, hard_conds, context, t, traj_normalized=None, obstacle_pts=None, forward_t=None,
@@ -559,6 +642,7 @@ class _GaussianDiffusionBase(nn.Module):
         return mean, pv, plv
 
     _supports_apf = True
+    _scenes_supported = True           # run_inference_scenes (the static 2-D and 3-D samplers)
 
     @torch.no_grad()
     def p_mean_variance_compose(self, x, hard_conds, context, t, traj_normalized=None, obstacle_pts=None, forward_t=None,
@@ -649,6 +733,7 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
     _default_cfg_weight = 2.5          # diffusion_model_dynamic.py:157
     _default_ddim = True               # diffusion_model_dynamic.py:46
     _supports_apf = False
+    _scenes_supported = False          # the replanning loop keeps one scene per job
 
     def __init__(self, model=None, variance_schedule='exponential', n_diffusion_steps=100, clip_denoised=True,
                  predict_epsilon=False, loss_type='l2', context_model=None, mask_type=None, traj_len=None,

@@ -1,0 +1,73 @@
+"""Host-side tables of a job that samples MANY scenes at once (``run_inference_scenes`` -> ``ramp_set_scenes`` +
+``ramp_sample_scenes``): the loop over experiment directories of the reference's ``scripts/inference/inference_static.py``
+turned into one batch.  Pure numpy, no device: everything here is testable without a GPU."""
+from __future__ import annotations
+
+from typing import Dict, List, Sequence, Union
+
+import numpy as np
+
+
+def build_scene_tables(cloud_sizes: Sequence[int], n_samples: Union[int, Sequence[int]],
+                       hard_keys: Sequence[Sequence[int]], n_rp: int = 2, compose: bool = False) -> Dict[str, np.ndarray]:
+    """Tables of one multi-scene job.
+
+    cloud_sizes  APF points of each scene's cloud (n_obstacles * n_points), one entry per scene; may differ per scene
+    n_samples    trajectories per scene: one int for all, or one count per scene
+    hard_keys    per scene, the waypoint indices of its hard-condition dict: every scene must condition the same waypoints
+                 in the same order (the job has ONE hard-condition layout, ``hard_val (n_hard, B, S)``)
+    n_rp         network rows per trajectory (2: classifier-free guidance)
+
+    Returns int32 arrays: ``traj_scene`` (B) scene of each trajectory, scenes in order, a scene's samples adjacent;
+    ``row_variant`` (B * n_rp) latent of each network row -- row ``b * n_rp`` reads its scene's latent ``traj_scene[b]``, row
+    ``b * n_rp + 1`` the shared unconditional all-zero latent, index ``n_scenes`` -- ; ``cloud_offset`` (n_scenes + 1) first
+    point of each scene in the concatenated cloud; ``counts`` (n_scenes); ``first`` (n_scenes) first trajectory of each scene.
+    """
+    if compose:
+        raise ValueError("a multi-scene job does not support compose=True (three latent variants per scene): out of scope")
+    if n_rp != 2:
+        raise ValueError("a multi-scene job runs classifier-free guidance rows only (n_rp = 2)")
+    n_scenes = len(cloud_sizes)
+    if n_scenes == 0:
+        raise ValueError("no scenes given")
+    sizes = [int(s) for s in cloud_sizes]
+    for i, s in enumerate(sizes):
+        if s <= 0:
+            raise ValueError(f"scene {i} has an empty cloud")
+    if isinstance(n_samples, (int, np.integer)):
+        counts = [int(n_samples)] * n_scenes
+    else:
+        counts = [int(c) for c in n_samples]
+        if len(counts) != n_scenes:
+            raise ValueError(f"n_samples has {len(counts)} entries for {n_scenes} scenes")
+    for i, c in enumerate(counts):
+        if c <= 0:
+            raise ValueError(f"scene {i} asks for {c} samples; every scene needs at least one")
+    if len(hard_keys) != n_scenes:
+        raise ValueError(f"hard_conds has {len(hard_keys)} entries for {n_scenes} scenes")
+    k0 = [int(k) for k in hard_keys[0]]
+    for i, ks in enumerate(hard_keys):
+        if [int(k) for k in ks] != k0:
+            raise ValueError(f"scene {i} conditions waypoints {list(ks)}, scene 0 {k0}: every scene of a job must condition "
+                             "the same waypoints in the same order")
+    traj_scene = np.repeat(np.arange(n_scenes, dtype=np.int32), counts)
+    row_variant = np.empty(traj_scene.size * 2, dtype=np.int32)
+    row_variant[0::2] = traj_scene
+    row_variant[1::2] = n_scenes
+    cloud_offset = np.zeros(n_scenes + 1, dtype=np.int64)
+    np.cumsum(sizes, out=cloud_offset[1:])
+    if cloud_offset[-1] >= 2 ** 31:
+        raise ValueError("the concatenated cloud does not fit 32-bit offsets")
+    first = np.zeros(n_scenes, dtype=np.int64)
+    first[1:] = np.cumsum(counts)[:-1]
+    return {"traj_scene": traj_scene, "row_variant": row_variant, "cloud_offset": cloud_offset.astype(np.int32),
+            "counts": np.asarray(counts, dtype=np.int32), "first": first.astype(np.int32)}
+
+
+def scene_slices(counts: Sequence[int]) -> List[slice]:
+    """The rows of each scene in the job's batch (what ``build_scene_tables`` laid out)."""
+    out, b = [], 0
+    for c in counts:
+        out.append(slice(b, b + int(c)))
+        b += int(c)
+    return out

@@ -219,6 +219,19 @@ class TemporalUnetInference(nn.Module):
                                                   _lib.current_stream()), "ramp_set_scene")
         self.cached_scene_latents = lat
 
+    def set_scenes(self, latents: torch.Tensor, row_variant):
+        """Many scenes in one batch (``ramp_set_scenes``): latents (n_variants, ctx), unconditional variants all-zero rows;
+        network row r uses variant ``row_variant[r]`` -- an explicit table of B * n_rp entries (sequence or int tensor), not a
+        pattern.  A batch with more rows than the table is refused; ``set_scene`` returns the context to pattern mode."""
+        lat = latents.to(self._device(), torch.float32).contiguous()
+        rv = np.ascontiguousarray(row_variant.cpu().numpy() if torch.is_tensor(row_variant) else row_variant, dtype=np.int32).reshape(-1)
+        self.invalidate_scene()
+        self.cached_batch_size = None
+        with torch.cuda.device(self._device()):
+            _lib.check(_lib.load().ramp_set_scenes(self.ctx(), _lib.ptr(lat), lat.shape[0], rv.ctypes.data_as(_lib.c_i32p), rv.size,
+                                                   _lib.current_stream()), "ramp_set_scenes")
+        self.cached_scene_latents = lat
+
     def cache_scene_encoding(self, obstacle_pts: torch.Tensor, compose: bool = False):
         """Reference semantics (UnetInference.py:146-156): recompute only when the cache is empty or the
         batch size changed; ``obstacle_pts`` (N,No,Np,D) holds one cloud per network row."""
