@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 
@@ -89,6 +90,11 @@ using namespace ramp;
 #define RAMP_DEFAULT_GEMM_MODE 0
 #endif
 
+// the operand-maxima tables of the fp16x3 delayed scaling (ramp_ctx::obs)
+enum { TABLE_EVEN = 0, TABLE_ODD = 1,      // ping-pong by evaluation: evaluation j of a job writes table j & 1 and reads its predecessor's
+       TABLE_CANONICAL = 2,                // what evaluation 0 of a steady sampling job reads: the canonical calibration, written outside any job
+       TABLE_REPLAN_CARRY = 3 };           // written by a replan's last evaluation, read by the next replan's first
+
 struct ramp_ctx {
   ramp_config cfg{};
   int device = 0;
@@ -117,31 +123,30 @@ struct ramp_ctx {
   void* d_ptr_tables = nullptr;
   // sampler state
   float *s_x = nullptr, *s_eps = nullptr, *s_mean = nullptr, *s_x0 = nullptr, *s_noise = nullptr, *s_chain = nullptr;
-  size_t s_cap_B = 0, s_cap_rows = 0, s_noise_cap = 0, s_chain_cap = 0;
+  size_t s_cap_B = 0, s_eps_cap = 0, s_noise_cap = 0, s_chain_cap = 0;      // s_cap_B in trajectories (s_x, s_mean, s_x0), every other capacity in elements
   unsigned long long* s_philox = nullptr;      // device {seed, offset} of a job that draws its own noise (ramp_sample_params.noise_mode 1)
   int* s_hard_idx = nullptr; float* s_hard_val = nullptr; size_t s_hard_val_cap = 0; float* s_window = nullptr;
   float* s_cloud = nullptr; size_t s_cloud_cap = 0;
   int *s_traj_scene = nullptr, *s_scene_off = nullptr; size_t s_traj_scene_cap = 0, s_scene_off_cap = 0;      // per-scene APF of ramp_sample_scenes
-  // graph cache
-  hipGraphExec_t graph_exec[2] = {nullptr, nullptr}; std::string graph_key;   // [0] first evaluation calibrates, [1] it continues
+  // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
+  // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
+  hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
+  bool buffers_moved = false;        // grow() gave a buffer a captured node may hold a new address: staging_done() drops BOTH families' keys
   // Round 6: a job the range guard flagged is repeated IN fp16x3 (ramp_set_fallback(ctx, 2)): the guard's state after every evaluation of a
   // job is logged on the device (trip_log[j]), ramp_range_status finds the first flagged evaluation, and the repeat runs exactly that
   // evaluation as a calibrating one (bf16x6 kernels that record every call site's operand maximum: range-free, and its successor is scaled
   // from maxima that are true) -- a function of the job alone, 1.03 x a steady job instead of the 1.83 x of an all-bf16x6 repeat
-  int* trip_log = nullptr; int trip_log_cap = 0; int last_job_steps = 0; int trip_eval = -1; int trip_site = -1; int rerun = 0;
-  hipGraphExec_t graph_rerun = nullptr; std::string graph_rerun_key;
-  // fp16x3 calibration kept from one ramp_sample to the next of the same job shape (ramp_set_calibration_reuse): the
-  // job's first evaluation then reads the maxima the previous job's first evaluation recorded (table 2).  A job becomes
-  // the next one's calibration only when ramp_range_status has reported it clean.
-  int cal_reuse = 1; bool s_calibrated = false, s_pending = false; std::string s_cal_key, s_pending_key;
+  int* trip_log = nullptr; size_t trip_log_cap = 0; int last_job_steps = 0; int trip_eval = -1; int trip_site = -1; int rerun = 0;
   // Round 5: the calibration a job's first evaluation is scaled from is CANONICAL -- one bf16x6 evaluation, outside the job, on Philox noise of
-  // a fixed seed with the job's hard conditions, at the job's first timestep (table 2) -- instead of whatever the previous job left behind: no
-  // job contains a bf16x6 evaluation, and a job's result does not depend on what ran before it on the context (ramp_set_calibration_reuse)
+  // a fixed seed with NO hard conditions applied, at the job's first timestep (TABLE_CANONICAL) -- instead of whatever the previous job left
+  // behind: no job contains a bf16x6 evaluation, and a job's result does not depend on what ran before it on the context.
+  // ramp_set_calibration_reuse(ctx, 0) turns it off: every job's first evaluation then calibrates itself.
+  int cal_reuse = 1;
   bool c_cal_valid = false; std::string c_cal_key; unsigned long long* c_cal_rec = nullptr;
   std::map<std::string, float*> c_cal_saved;     // canonical tables already computed, by key: switching between job shapes copies 4 KB instead of re-evaluating
   std::vector<float*> c_cal_free;                // their buffers after an invalidation (scene / plan change), for reuse
   // receding-horizon replanning (ramp_replan): fixed device buffers the captured graphs read, the graph of a replan whose
-  // first evaluation calibrates ([0]) and of one that continues from the previous replan's operand maxima ([1])
+  // first evaluation calibrates ([0]) and of one that continues from the previous replan's operand maxima ([1], TABLE_REPLAN_CARRY)
   float *r_noise = nullptr, *r_hist = nullptr, *r_xclean = nullptr, *r_best = nullptr, *r_plen = nullptr, *r_smooth = nullptr,
         *r_cost = nullptr, *r_hard_val = nullptr;
   double *r_static = nullptr, *r_dyn = nullptr;
@@ -159,9 +164,12 @@ struct ramp_ctx {
   int x6_pipe = 1;                   // 1 = fragment-packed weights + pipelined kernel (RAMP_X6_PIPE=0: LDS-staged weights)
   int geglu_group = 64;              // GEGLU weight tiling (32 with the pipelined kernels' wave-private epilogue)
   // fp16x3 (gemm_mode 2): delayed operand scaling.  phase 0 = bf16x6; 1 = bf16x6 that records max|A| per GEMM call site
-  // (the calibration evaluation: the first score evaluation of every ramp_sample); 2 = fp16x3 scaled from the
-  // previous evaluation's maxima, recording its own.  obs[2][MAX_SITES] floats, ping-pong by evaluation.
-  static constexpr int MAX_SITES = 1024, N_OBS_TABLES = 4;      // 0 / 1: ping-pong by evaluation, 2: the canonical calibration of the sampling jobs, 3: carried from replan to replan
+  // (a calibration evaluation: the canonical one outside the sampling jobs, the first evaluation of a job with calibration reuse off, the
+  // flagged evaluation of a repeat, the first replan / single evaluation after a change); 2 = fp16x3 scaled from the
+  // previous evaluation's maxima, recording its own.  obs[N_OBS_TABLES][MAX_SITES] floats; an evaluation reads one table and writes another
+  // (the roles: TABLE_EVEN ... TABLE_REPLAN_CARRY above).
+  static constexpr int MAX_SITES = 1024, N_OBS_TABLES = 4;
+  float* table(int i) const { return obs + (size_t)i * MAX_SITES; }
   int phase = 0, site = 0;
   int ff_fused = 150000;             // fp16x3 evaluations: FF1 -> GEGLU -> FF2 as one launch for M >= this many rows
                                      // (RAMP_FF_FUSED: 0 never, 1 always, n > 1 that threshold)
@@ -1106,20 +1114,37 @@ int encode_scene_3d(ramp_ctx* c, const float* cloud, int No, int Np, float* out,
 }
 
 
+// ---- device buffers of the job layer: typed, grow-only, from the arena (which never frees: an old block stays valid for whatever still holds
+// its address).  A captured graph holds the addresses of the buffers its nodes touch, so every reallocation is noted in the context and
+// staging_done() -- once per job, after its staging and before a graph is chosen -- drops the keys of BOTH graph families: the sampling jobs'
+// and the replans' graphs read the same s_x, s_eps, s_x0 and operand-maxima tables, and one re-capture after a growth is the whole cost.
+template <class T> int renew(ramp_ctx* c, T*& p, size_t n) {      // p = a new block of n T
+  float* q;
+  CK(dev_alloc(c, &q, (n * sizeof(T) + sizeof(float) - 1) / sizeof(float)));
+  // (a first allocation moves nothing -- PROVIDED that a graph captured while the buffer did not exist never meets it: the graph keys carry
+  // whatever decides that a job touches an optional buffer, see where they are built)
+  if (p) c->buffers_moved = true;
+  p = reinterpret_cast<T*>(q);
+  return 0;
+}
+template <class T> int grow(ramp_ctx* c, T*& p, size_t& cap, size_t n) {
+  if (n > cap) { CK(renew(c, p, n)); cap = n; }
+  return 0;
+}
+void staging_done(ramp_ctx* c) {
+  if (c->buffers_moved) { c->graph_key.clear(); c->r_key.clear(); c->buffers_moved = false; }
+}
+
 int ensure_sampler_buffers(ramp_ctx* c, int B, int n_rp, int n_steps, bool chain) {
   const size_t HS = (size_t)c->cfg.horizon * c->cfg.state_dim;
-  bool moved = false;
   if ((size_t)B > c->s_cap_B) {
-    CK(dev_alloc(c, &c->s_x, B * HS)); CK(dev_alloc(c, &c->s_mean, B * HS)); CK(dev_alloc(c, &c->s_x0, B * HS));
-    c->s_cap_B = B; moved = true;
+    CK(renew(c, c->s_x, B * HS)); CK(renew(c, c->s_mean, B * HS)); CK(renew(c, c->s_x0, B * HS));
+    c->s_cap_B = B;
   }
-  if ((size_t)B * n_rp > c->s_cap_rows) {
-    CK(dev_alloc(c, &c->s_eps, (size_t)B * n_rp * HS)); c->s_cap_rows = (size_t)B * n_rp; moved = true;
-  }
+  CK(grow(c, c->s_eps, c->s_eps_cap, (size_t)B * n_rp * HS));
   const size_t nn = (size_t)(n_steps + 1) * B * HS;
-  if (nn > c->s_noise_cap) { CK(dev_alloc(c, &c->s_noise, nn)); c->s_noise_cap = nn; moved = true; }
-  if (chain && nn > c->s_chain_cap) { CK(dev_alloc(c, &c->s_chain, nn)); c->s_chain_cap = nn; moved = true; }
-  if (moved) { c->graph_key.clear(); c->r_key.clear(); }      // captured nodes hold the old pointers
+  CK(grow(c, c->s_noise, c->s_noise_cap, nn));
+  if (chain) CK(grow(c, c->s_chain, c->s_chain_cap, nn));
   return 0;
 }
 
@@ -1148,6 +1173,76 @@ int score_all(ramp_ctx* c, const float* x, int B, int n_rp, int t, float* f_out,
     else if (eps_out) CK(net_backward(c, row0, R, eps_out + (size_t)row0 * H * S, s));
   }
   return 0;
+}
+
+// One score evaluation of a job under the fp16x3 delayed scaling.  phase 1: the bf16x6 kernels, recording every GEMM call site's operand
+// maximum; 2: fp16x3 scaled from the maxima in table t_in; both write their own maxima into table t_out, zeroed first.  phase 0: the context's
+// plain arithmetic (bf16x6 / exact fp32), no tables.  log != nullptr: the range guard's word after the evaluation goes to log[j].
+int guarded_eval(ramp_ctx* c, int phase, int t_in, int t_out, const float* x, int B, int n_rp, int t, float* f_out, float* eps_out,
+                 hipStream_t s, const float* comb = nullptr, int* log = nullptr, int j = 0) {
+  if (phase) {
+    c->obs_in = c->table(t_in); c->obs_out = c->table(t_out);
+    hipLaunchKernelGGL(zero_words_kernel, dim3(ramp_ctx::MAX_SITES / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->obs_out), ramp_ctx::MAX_SITES);
+    RAMP_HIP_CHECK(hipGetLastError());
+  }
+  c->phase = phase;
+  const int rc = score_all(c, x, B, n_rp, t, f_out, eps_out, s, comb);
+  c->phase = 0;
+  CK(rc);
+  if (log) {
+    hipLaunchKernelGGL(log_flag_kernel, dim3(1), dim3(64), 0, s, c->range_flag, log, j);
+    RAMP_HIP_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
+// the weights of the rows' gradients in e_comb (diffusion_model_static.py:164-165, 214; CFG: (1 + w) e_cond - w e_uncond): the network prefix
+// the rows of a trajectory have in common is evaluated once and its input gradient once, on the combined gradient
+std::array<float, 3> comb_weights(int n_rp, double w0, double w1) {
+  if (n_rp == 2) return {(float)(1.0 + w0), -(float)w0, (float)(1.0 - w0 - w1)};
+  return {(float)w0, (float)w1, (float)(1.0 - w0 - w1)};
+}
+
+// ---- captured graphs: *slot empty -> body(capture stream) is captured and instantiated into it; then *slot is launched on s
+template <class Body> int replay(hipGraphExec_t* slot, hipStream_t s, Body&& body) {
+  if (!*slot) {
+    hipStream_t cs;
+    RAMP_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
+    RAMP_HIP_CHECK(hipStreamSynchronize(s));
+    RAMP_HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    int rc = body(cs);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(cs, &g);
+    if (rc != 0) { if (g) (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs); return rc; }
+    if (e != hipSuccess) { (void)hipStreamDestroy(cs); RAMP_HIP_CHECK(e); }
+    e = hipGraphInstantiate(slot, g, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs);
+    RAMP_HIP_CHECK(e);
+  }
+  RAMP_HIP_CHECK(hipGraphLaunch(*slot, s));
+  return 0;
+}
+void drop_graphs(hipGraphExec_t* slots, int n) {
+  for (int i = 0; i < n; ++i) if (slots[i]) { (void)hipGraphExecDestroy(slots[i]); slots[i] = nullptr; }
+}
+
+// the key of a captured graph / a kept calibration: the bytes of everything baked into it
+struct Key {
+  std::string bytes;
+  template <class T> void put(const T& v) {
+    static_assert(!std::is_pointer<T>::value && !std::is_array<T>::value, "an array goes in with its count: put(a, n)");
+    bytes.append(reinterpret_cast<const char*>(&v), sizeof(T));
+  }
+  template <class T> void put(const T* a, size_t count) { bytes.append(reinterpret_cast<const char*>(a), sizeof(T) * count); }
+};
+
+// kept fp16x3 calibrations that a change makes stale: the single evaluations' tables (ramp_score), the replans' carried table, the sampling
+// jobs' canonical table
+enum { CAL_SCORE = 1, CAL_REPLAN = 2, CAL_CANONICAL = 4, CAL_ALL = 7 };
+void invalidate_calibrations(ramp_ctx* c, int what) {
+  if (what & CAL_SCORE) c->score_calibrated = false;
+  if (what & CAL_REPLAN) c->r_calibrated = false;
+  if (what & CAL_CANONICAL) c->c_cal_valid = false;
 }
 
 }  // namespace
@@ -1234,15 +1329,15 @@ int ramp_set_launch_plan(ramp_ctx* c, const ramp_launch_plan* p) {
   c->three_blocks = p->three_blocks != 0; c->x6_pipe = p->x6_pipe != 0; c->mfma16 = p->mfma16 != 0;
   if (changed && c->finalized) {   // other kernels from here on: captured graphs and kept calibrations belong to the old plan
     c->graph_key.clear(); c->r_key.clear();
-    c->score_calibrated = false; c->r_calibrated = false; c->s_calibrated = false; c->s_pending = false; c->c_cal_valid = false;
+    invalidate_calibrations(c, CAL_ALL);
   }
   return 0;
 }
 
 int ramp_destroy(ramp_ctx* c) {
   if (!c) return 0;
-  for (auto& g : c->graph_exec) if (g) (void)hipGraphExecDestroy(g);
-  for (auto& g : c->r_graph) if (g) (void)hipGraphExecDestroy(g);
+  drop_graphs(c->s_graph, 3);
+  drop_graphs(c->r_graph, 2);
   if (c->d_ptr_tables) (void)hipFree(c->d_ptr_tables);
   delete c;
   return 0;
@@ -1585,7 +1680,7 @@ static int set_scene_table(ramp_ctx* c, const float* latents, int n_variants, co
   c->scene_epoch++;
   c->graph_key.clear();     // scene changed: cross_bias pointer may have moved
   c->r_key.clear();
-  c->score_calibrated = false; c->r_calibrated = false; c->s_calibrated = false; c->s_pending = false; c->c_cal_valid = false;
+  invalidate_calibrations(c, CAL_ALL);
   return rc;
 }
 
@@ -1625,40 +1720,26 @@ int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, 
   RAMP_REQUIRE(c && x, "null argument");
   c->launches = 0;
   hipStream_t s = as_stream(stream);
-  c->s_calibrated = false; c->s_pending = false;          // single evaluations overwrite the tables a kept job calibration reads
-  if (c->gemm_mode != 2 || c->force_x6) { c->score_last_mode = c->gemm_mode == 2 ? 1 : c->gemm_mode; return score_all(c, x, B, n_rp, t, f_out, eps_out, s); }
+  if (c->gemm_mode != 2 || c->force_x6) {
+    c->score_last_mode = c->gemm_mode == 2 ? 1 : c->gemm_mode;
+    return guarded_eval(c, 0, 0, 0, x, B, n_rp, t, f_out, eps_out, s);
+  }
   // fp16x3: the same delayed scaling as inside ramp_sample, with the calibration kept across calls.  The first
   // evaluation after context creation / a scene change / a ramp_sample runs the bf16x6 kernels and records every call
   // site's operand maximum; every later one runs fp16x3 scaled from its predecessor's maxima, and is repeated at once
   // with the bf16x6 kernels (recording again) if the range guard fired -- the caller never sees a flagged result.
-  auto tables = [&](int parity) {
-    c->obs_out = c->obs + parity * ramp_ctx::MAX_SITES;
-    c->obs_in = c->obs + (parity ^ 1) * ramp_ctx::MAX_SITES;
-    hipLaunchKernelGGL(zero_words_kernel, dim3(ramp_ctx::MAX_SITES / 256), dim3(256), 0, s,
-                       reinterpret_cast<unsigned*>(c->obs_out), ramp_ctx::MAX_SITES);
-  };
-  int rc = 0;
+  const int t_out = c->score_parity ? TABLE_ODD : TABLE_EVEN, t_in = c->score_parity ? TABLE_EVEN : TABLE_ODD;
   // (a forward-only evaluation leaves the call sites of the input-gradient pass without maxima)
   if (c->score_calibrated && (c->score_calibrated_bwd || eps_out == nullptr)) {
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
-    tables(c->score_parity);
-    RAMP_HIP_CHECK(hipGetLastError());
-    c->phase = 2;
-    rc = score_all(c, x, B, n_rp, t, f_out, eps_out, s);
-    c->phase = 0;
-    CK(rc);
+    CK(guarded_eval(c, 2, t_in, t_out, x, B, n_rp, t, f_out, eps_out, s));
     int flag = 0;
     RAMP_HIP_CHECK(hipMemcpyAsync(&flag, c->range_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     RAMP_HIP_CHECK(hipStreamSynchronize(s));
     c->r_calibrated = false;
     if (!flag) { c->score_parity ^= 1; c->score_last_mode = 2; c->score_calibrated_bwd = eps_out != nullptr; return 0; }
   }
-  tables(c->score_parity);
-  RAMP_HIP_CHECK(hipGetLastError());
-  c->phase = 1;
-  rc = score_all(c, x, B, n_rp, t, f_out, eps_out, s);
-  c->phase = 0;
-  CK(rc);
+  CK(guarded_eval(c, 1, t_in, t_out, x, B, n_rp, t, f_out, eps_out, s));
   c->score_calibrated = true; c->score_calibrated_bwd = eps_out != nullptr; c->score_parity ^= 1; c->score_last_mode = 1;
   c->r_calibrated = false;
   return 0;
@@ -1686,33 +1767,20 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     if (!c->force_x6) hipLaunchKernelGGL(zero_words_kernel, dim3((p->n_steps + 255) / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->trip_log), p->n_steps);
     RAMP_HIP_CHECK(hipGetLastError());
   }
+  const bool h3 = c->gemm_mode == 2 && !c->force_x6;
+  const std::array<float, 3> comb = comb_weights(p->n_rp, p->w0, p->w1);
+  const bool shared = p->n_rp > 1 && c->share_prefix;
   for (int j = 0; j < p->n_steps; ++j) {
-    if (c->gemm_mode == 2 && !c->force_x6) {
-      // evaluation 0 runs fp16x3 scaled from the context's CANONICAL maxima (table 2: canonical_calibration below) -- or, with
-      // ramp_set_calibration_reuse(ctx, 0), calibrates itself (bf16x6 + recorded operand maxima); evaluation j >= 1 runs fp16x3
-      // scaled from j - 1
-      // (j == cal_eval, cal_eval + 1: the evaluation the range guard flagged first in this job's previous run calibrates instead -- see
-      // ramp_ctx::trip_log -- and so does its successor: an excursion that is gone one step later (a spike) would otherwise trip the guard
-      // again from the other side, its successor being scaled from the spike's maxima; 3 % of a job per calibrating evaluation)
-      c->phase = ((j == 0 && !steady) || j == cal_eval || (cal_eval >= 0 && j == cal_eval + 1)) ? 1 : 2;
-      c->obs_out = c->obs + (j & 1) * ramp_ctx::MAX_SITES;
-      c->obs_in = c->obs + (j == 0 ? 2 : ((j & 1) ^ 1)) * ramp_ctx::MAX_SITES;
-      hipLaunchKernelGGL(zero_words_kernel, dim3(ramp_ctx::MAX_SITES / 256), dim3(256), 0, s,
-                         reinterpret_cast<unsigned*>(c->obs_out), ramp_ctx::MAX_SITES);
-      RAMP_HIP_CHECK(hipGetLastError());
-    }
-    // the weights of the rows' gradients in e_comb (diffusion_model_static.py:164-165, 214): the network prefix the rows
-    // of a trajectory have in common is evaluated once and its input gradient once, on the combined gradient
-    const float comb[3] = {p->n_rp == 2 ? (float)(1.0 + p->w0) : (float)p->w0, p->n_rp == 2 ? -(float)p->w0 : (float)p->w1,
-                           (float)(1.0 - p->w0 - p->w1)};
-    const bool shared = p->n_rp > 1 && c->share_prefix;
-    const int rc_score = score_all(c, c->s_x, B, p->n_rp, p->t[j], nullptr, c->s_eps, s, shared ? comb : nullptr);
-    c->phase = 0;
-    CK(rc_score);
-    if (c->gemm_mode == 2 && !c->force_x6) {
-      hipLaunchKernelGGL(log_flag_kernel, dim3(1), dim3(64), 0, s, c->range_flag, c->trip_log, j);
-      RAMP_HIP_CHECK(hipGetLastError());
-    }
+    // fp16x3: evaluation 0 runs scaled from the context's CANONICAL maxima (canonical_calibration below) -- or, with
+    // ramp_set_calibration_reuse(ctx, 0), calibrates itself (bf16x6 + recorded operand maxima); evaluation j >= 1 runs fp16x3
+    // scaled from j - 1
+    // (j == cal_eval, cal_eval + 1: the evaluation the range guard flagged first in this job's previous run calibrates instead -- see
+    // ramp_ctx::trip_log -- and so does its successor: an excursion that is gone one step later (a spike) would otherwise trip the guard
+    // again from the other side, its successor being scaled from the spike's maxima; 3 % of a job per calibrating evaluation)
+    const int phase = !h3 ? 0 : ((j == 0 && !steady) || j == cal_eval || (cal_eval >= 0 && j == cal_eval + 1)) ? 1 : 2;
+    const int t_out = (j & 1) ? TABLE_ODD : TABLE_EVEN, t_in = j == 0 ? TABLE_CANONICAL : (j & 1) ? TABLE_EVEN : TABLE_ODD;
+    CK(guarded_eval(c, phase, t_in, t_out, c->s_x, B, p->n_rp, p->t[j], nullptr, c->s_eps, s, shared ? comb.data() : nullptr,
+                    h3 ? c->trip_log : nullptr, j));
     CfgMeanArgs m; m.x = c->s_x; m.eps = c->s_eps; m.B = B; m.HS = (int)HS; m.n_rp = shared ? 1 : p->n_rp;
     m.w0 = (float)p->w0; m.w1 = (float)p->w1; m.w0p1 = (float)(1.0 + p->w0);
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
@@ -1739,31 +1807,25 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
 }
 
 // The calibration every job's first evaluation is scaled from (fp16x3 mode): ONE score evaluation on the bf16x6 kernels that only records the
-// operand maxima of every GEMM call site (phase 1) into table 2, on a CANONICAL input -- x ~ N(0, I) from Philox4x32-10 with a fixed seed, the
-// at the job's first timestep -- not on anybody's data, not even the job's start / goal values: x_T of every job is a draw of the same distribution, the
+// operand maxima of every GEMM call site (phase 1) into TABLE_CANONICAL, on a CANONICAL input -- x ~ N(0, I) from Philox4x32-10 with a fixed
+// seed, at the job's first timestep, with no hard conditions applied -- not on anybody's data, not even the job's start / goal values (ADVICE
+// r5: with them the table depended on whichever job triggered it): x_T of every job is a draw of the same distribution, the
 // recorded maxima only pick power-of-two scales (the operand may then grow 2^9.9-fold before the range guard fires, elements down to 2^-8 of the
 // maximum keep all 22 bits), and the guard covers a caller whose x_T is something else.  Runs eagerly on the job's stream, outside its graph,
-// once per (batch, first timestep, hard-condition layout, scene).
+// once per (batch, row variants and weights, first timestep, scene).
 static int canonical_calibration(ramp_ctx* c, const ramp_sample_params* p, hipStream_t s) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   if (!c->c_cal_rec) {
-    float* q; CK(dev_alloc(c, &q, 4)); c->c_cal_rec = reinterpret_cast<unsigned long long*>(q);
+    CK(renew(c, c->c_cal_rec, 2));
     const unsigned long long rec[2] = {0x52414d5043414cull /* "RAMPCAL" */, 0ull};
     RAMP_HIP_CHECK(hipMemcpyAsync(c->c_cal_rec, rec, 16, hipMemcpyHostToDevice, s));
     RAMP_HIP_CHECK(hipStreamSynchronize(s));       // (rec is a stack array)
   }
   RAMP_REQUIRE((H * S) % 4 == 0, "H * S must be a multiple of 4");
-  // (round 6, ADVICE r5: NO hard conditions on the canonical input -- with the caller's start / goal applied, table 2 depended on the values of
-  // whichever job triggered it, and a later job with other values inherited scales a fresh context would not have chosen)
   CK(launch_philox_normal(c->s_x, (long)B * H * S, c->c_cal_rec, s));
-  c->phase = 1;
-  c->obs_out = c->obs + 2 * ramp_ctx::MAX_SITES; c->obs_in = c->obs;
-  hipLaunchKernelGGL(zero_words_kernel, dim3(ramp_ctx::MAX_SITES / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->obs_out), ramp_ctx::MAX_SITES);
-  const float comb[3] = {p->n_rp == 2 ? (float)(1.0 + p->w0) : (float)p->w0, p->n_rp == 2 ? -(float)p->w0 : (float)p->w1, (float)(1.0 - p->w0 - p->w1)};
+  const std::array<float, 3> comb = comb_weights(p->n_rp, p->w0, p->w1);
   const bool shared = p->n_rp > 1 && c->share_prefix;
-  const int rc = score_all(c, c->s_x, B, p->n_rp, p->t[0], nullptr, c->s_eps, s, shared ? comb : nullptr);
-  c->phase = 0;
-  return rc;
+  return guarded_eval(c, 1, TABLE_EVEN, TABLE_CANONICAL, c->s_x, B, p->n_rp, p->t[0], nullptr, c->s_eps, s, shared ? comb.data() : nullptr);
 }
 
 int ramp_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, void* stream) {
@@ -1778,6 +1840,16 @@ int ramp_philox_normal(float* out, int64_t n, uint64_t seed, uint64_t offset, vo
   (void)hipStreamSynchronize(s);
   (void)hipFree(rec);
   return rc;
+}
+
+// APF staging of both kinds of job: the window weights (host) and the n_points obstacle points (device, (n_points, 2)) into the context's buffers
+static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, int n_points, hipStream_t s) {
+  RAMP_REQUIRE(n_points > 0 && a.window >= 0 && a.window <= 64 && a.window_weights_host, "bad APF params");
+  if (!c->s_window) CK(renew(c, c->s_window, 256));
+  CK(grow(c, c->s_cloud, c->s_cloud_cap, (size_t)n_points * 2));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->s_window, a.window_weights_host, (2 * a.window + 1) * 4, hipMemcpyHostToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->s_cloud, cloud, (size_t)n_points * 8, hipMemcpyDeviceToDevice, s));
+  return 0;
 }
 
 static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
@@ -1798,24 +1870,13 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const bool chain = chain_out != nullptr;
   const size_t n_noise = (p->ddim ? 1 : (size_t)p->n_steps + 1) * n;
   CK(ensure_sampler_buffers(c, B, p->n_rp, p->n_steps, chain));
-  if (p->n_steps > c->trip_log_cap) {
-    float* q; const int cap = std::max(256, p->n_steps);
-    CK(dev_alloc(c, &q, cap)); c->trip_log = reinterpret_cast<int*>(q); c->trip_log_cap = cap; c->graph_key.clear();
-  }
+  CK(grow(c, c->trip_log, c->trip_log_cap, (size_t)std::max(256, p->n_steps)));
   for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
-  if (!c->s_hard_idx) { float* q; CK(dev_alloc(c, &q, 256)); c->s_hard_idx = reinterpret_cast<int*>(q); }
+  if (!c->s_hard_idx) CK(renew(c, c->s_hard_idx, 256));
   RAMP_REQUIRE(p->n_hard <= 256, "too many hard conditions");
   const size_t hv = (size_t)p->n_hard * B * S;
-  if (hv > c->s_hard_val_cap) { CK(dev_alloc(c, &c->s_hard_val, hv)); c->s_hard_val_cap = hv; c->graph_key.clear(); }
-  if (p->apf.cloud) {
-    RAMP_REQUIRE(p->apf.n_points > 0 && p->apf.window >= 0 && p->apf.window <= 64 && p->apf.window_weights_host, "bad APF params");
-    if (!c->s_window) CK(dev_alloc(c, &c->s_window, 256));
-    if ((size_t)p->apf.n_points * 2 > c->s_cloud_cap) {
-      CK(dev_alloc(c, &c->s_cloud, (size_t)p->apf.n_points * 2)); c->s_cloud_cap = (size_t)p->apf.n_points * 2; c->graph_key.clear();
-    }
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_window, p->apf.window_weights_host, (2 * p->apf.window + 1) * 4, hipMemcpyHostToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_cloud, p->apf.cloud, (size_t)p->apf.n_points * 8, hipMemcpyDeviceToDevice, s));
-  }
+  CK(grow(c, c->s_hard_val, c->s_hard_val_cap, hv));
+  if (p->apf.cloud) CK(stage_apf(c, p->apf, p->apf.cloud, p->apf.n_points, s));
   const bool sc_apf = sc && sc->cloud_points;
   int sc_points = 0;
   if (sc) {
@@ -1827,15 +1888,9 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     for (int i = 0; i < sc->n_scenes; ++i)
       RAMP_REQUIRE(sc->cloud_offset_host[i + 1] > sc->cloud_offset_host[i], "ramp_sample_scenes: every scene needs at least one cloud point (increasing offsets)");
     sc_points = sc->cloud_offset_host[sc->n_scenes];
-    RAMP_REQUIRE(p->apf.window >= 0 && p->apf.window <= 64 && p->apf.window_weights_host, "bad APF params");
-    if (!c->s_window) CK(dev_alloc(c, &c->s_window, 256));
-    if ((size_t)sc_points * 2 > c->s_cloud_cap) { CK(dev_alloc(c, &c->s_cloud, (size_t)sc_points * 2)); c->s_cloud_cap = (size_t)sc_points * 2; c->graph_key.clear(); }
-    if ((size_t)B > c->s_traj_scene_cap) { float* q; CK(dev_alloc(c, &q, B)); c->s_traj_scene = reinterpret_cast<int*>(q); c->s_traj_scene_cap = B; c->graph_key.clear(); }
-    if ((size_t)sc->n_scenes + 1 > c->s_scene_off_cap) {
-      float* q; CK(dev_alloc(c, &q, sc->n_scenes + 1)); c->s_scene_off = reinterpret_cast<int*>(q); c->s_scene_off_cap = (size_t)sc->n_scenes + 1; c->graph_key.clear();
-    }
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_window, p->apf.window_weights_host, (2 * p->apf.window + 1) * 4, hipMemcpyHostToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_cloud, sc->cloud_points, (size_t)sc_points * 8, hipMemcpyDeviceToDevice, s));
+    CK(stage_apf(c, p->apf, sc->cloud_points, sc_points, s));
+    CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));
+    CK(grow(c, c->s_scene_off, c->s_scene_off_cap, (size_t)sc->n_scenes + 1));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_scene_off, sc->cloud_offset_host, ((size_t)sc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
   }
@@ -1844,50 +1899,46 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_val, p->hard_val, hv * 4, hipMemcpyDeviceToDevice, s));
   }
   if (p->noise_mode == 1) {
-    if (!c->s_philox) { float* q; CK(dev_alloc(c, &q, 4)); c->s_philox = reinterpret_cast<unsigned long long*>(q); }
+    if (!c->s_philox) CK(renew(c, c->s_philox, 2));
     const unsigned long long rec[2] = {p->philox_seed, p->philox_offset};
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_philox, rec, 16, hipMemcpyHostToDevice, s));     // (pageable host memory: the copy is staged before the call returns)
   } else {
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_noise, noise, n_noise * 4, hipMemcpyDeviceToDevice, s));
   }
   c->launches = 0;
-  c->score_calibrated = false; c->r_calibrated = false;      // the loop below overwrites the delayed-scaling tables
-  // key: everything baked into the captured nodes (and what a kept calibration belongs to)
-  std::string key;
-  bool steady = false;
-  {
-    auto put = [&](const void* q, size_t b) { key.append(static_cast<const char*>(q), b); };
-    put(&p->B, 4); put(&p->n_rp, 4); put(&p->n_steps, 4); put(&p->ddim, 4); put(&p->w0, 8); put(&p->w1, 8);
-    put(p->t, 4 * p->n_steps); put(p->sqrt_recip, 4 * p->n_steps); put(p->sqrt_recipm1, 4 * p->n_steps);
-    if (p->ddim) { put(p->sqrt_a_t, 4 * p->n_steps); put(p->sqrt_1m_a_t, 4 * p->n_steps); put(p->sqrt_a_prev, 4 * p->n_steps); put(p->dir_coef, 4 * p->n_steps); }
-    else { put(p->coef1, 4 * p->n_steps); put(p->coef2, 4 * p->n_steps); put(p->stdv, 4 * p->n_steps); put(p->use_noise, 4 * p->n_steps); }
-    if (p->apply_apf) put(p->apply_apf, 4 * p->n_steps);
-    if (p->noise_scale) put(p->noise_scale, 4 * p->n_steps);
-    put(&p->clip_denoised, 4); put(&p->predict_x0, 4); put(&p->n_hard, 4);
-    put(&p->philox_sample0, 8); put(&p->philox_total, 8);
-    const int has_apf = p->apf.cloud != nullptr; put(&has_apf, 4);
-    put(&p->apf.n_points, 4); put(&p->apf.window, 4); put(&p->apf.threshold, 8); put(&p->apf.strength, 8); put(&p->apf.passes, 4);
-    const int ch = chain; put(&ch, 4); put(&c->force_x6, 4); put(&p->noise_mode, 4);
-    if (sc) { const int tag[3] = {0x5343454e /* "SCEN" */, sc_apf ? sc->n_scenes : 0, sc_points}; put(tag, 12); }      // (a single-scene job's key has no such tail)
-  }
+  invalidate_calibrations(c, CAL_SCORE | CAL_REPLAN);      // the loop below overwrites the delayed-scaling tables
+  // key: everything baked into the captured nodes.  It also carries whatever decides that the job touches a buffer that may not exist yet
+  // (s_chain: ch; s_cloud / s_window: has_apf and apply_apf; s_hard_val: n_hard; s_philox: noise_mode; the scene tables: the SCEN tag) --
+  // renew() relies on that when it lets a first allocation pass without dropping the graphs: add the field here with any new optional buffer
+  Key key;
+  key.put(p->B); key.put(p->n_rp); key.put(p->n_steps); key.put(p->ddim); key.put(p->w0); key.put(p->w1);
+  key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps); key.put(p->sqrt_recipm1, p->n_steps);
+  if (p->ddim) { key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps); key.put(p->sqrt_a_prev, p->n_steps); key.put(p->dir_coef, p->n_steps); }
+  else { key.put(p->coef1, p->n_steps); key.put(p->coef2, p->n_steps); key.put(p->stdv, p->n_steps); key.put(p->use_noise, p->n_steps); }
+  if (p->apply_apf) key.put(p->apply_apf, p->n_steps);
+  if (p->noise_scale) key.put(p->noise_scale, p->n_steps);
+  key.put(p->clip_denoised); key.put(p->predict_x0); key.put(p->n_hard);
+  key.put(p->philox_sample0); key.put(p->philox_total);
+  const int has_apf = p->apf.cloud != nullptr; key.put(has_apf);
+  key.put(p->apf.n_points); key.put(p->apf.window); key.put(p->apf.threshold); key.put(p->apf.strength); key.put(p->apf.passes);
+  const int ch = chain; key.put(ch); key.put(c->force_x6); key.put(p->noise_mode);
+  if (sc) { const int tag[3] = {0x5343454e /* "SCEN" */, sc_apf ? sc->n_scenes : 0, sc_points}; key.put(tag, 3); }      // (a single-scene job's key has no such tail)
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
-  steady = h3 && c->cal_reuse;
-  c->s_calibrated = false; c->s_pending = false;
+  const bool steady = h3 && c->cal_reuse;
   if (steady) {
     // what the canonical maxima depend on: batch, row variants and their weights, first timestep (the scene and the launch plan invalidate it
     // where they change) -- nothing of the caller's data
-    std::string ck;
-    auto putc = [&](const void* q, size_t b) { ck.append(static_cast<const char*>(q), b); };
-    putc(&p->B, 4); putc(&p->n_rp, 4); putc(p->t, 4); putc(&p->w0, 8); putc(&p->w1, 8);
-    const int sp = c->share_prefix; putc(&sp, 4);
-    putc(&c->scene_epoch, 4);                               // the scene table's identity; redundant today: set_scene_table drops every saved table (c_cal_valid)
+    Key ck;
+    ck.put(p->B); ck.put(p->n_rp); ck.put(p->t[0]); ck.put(p->w0); ck.put(p->w1);
+    const int sp = c->share_prefix; ck.put(sp);
+    ck.put(c->scene_epoch);                                 // the scene table's identity; redundant today: set_scene_table drops every saved table (c_cal_valid)
     if (!c->c_cal_valid) {                                  // (scene / plan / mode changed: every saved table is stale; its buffer is reused)
       for (auto& kv : c->c_cal_saved) c->c_cal_free.push_back(kv.second);
       c->c_cal_saved.clear();
     }
-    if (!c->c_cal_valid || c->c_cal_key != ck) {
-      float* t2 = c->obs + 2 * ramp_ctx::MAX_SITES;
-      auto it = c->c_cal_saved.find(ck);
+    if (!c->c_cal_valid || c->c_cal_key != ck.bytes) {
+      float* t2 = c->table(TABLE_CANONICAL);
+      auto it = c->c_cal_saved.find(ck.bytes);
       if (it != c->c_cal_saved.end()) {                      // a job shape seen before: its table back into place
         RAMP_HIP_CHECK(hipMemcpyAsync(t2, it->second, ramp_ctx::MAX_SITES * sizeof(float), hipMemcpyDeviceToDevice, s));
       } else {
@@ -1895,48 +1946,30 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
         if (c->c_cal_saved.size() < 16) {
           float* keep = nullptr;
           if (!c->c_cal_free.empty()) { keep = c->c_cal_free.back(); c->c_cal_free.pop_back(); }
-          else CK(dev_alloc(c, &keep, ramp_ctx::MAX_SITES));
+          else CK(dev_alloc(c, &keep, ramp_ctx::MAX_SITES));      // (no graph holds it: not a move)
           RAMP_HIP_CHECK(hipMemcpyAsync(keep, t2, ramp_ctx::MAX_SITES * sizeof(float), hipMemcpyDeviceToDevice, s));
-          c->c_cal_saved[ck] = keep;
+          c->c_cal_saved[ck.bytes] = keep;
         }
       }
-      c->c_cal_valid = true; c->c_cal_key = ck;
+      c->c_cal_valid = true; c->c_cal_key = ck.bytes;
       c->launches = 0;
     }
   }
+  staging_done(c);
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
   c->last_job_steps = h3 ? p->n_steps : 0;
   if (!p->use_graph) {
     CK(sample_body(c, p, sc, s, chain, steady, cal_eval));
   } else {
-    if (key != c->graph_key) {
-      for (auto& g : c->graph_exec) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-      if (c->graph_rerun) { (void)hipGraphExecDestroy(c->graph_rerun); c->graph_rerun = nullptr; }
-      c->graph_key = key; c->graph_rerun_key.clear();
-    }
-    const int which = steady ? 1 : 0;
-    hipGraphExec_t* slot = &c->graph_exec[which];
+    if (key.bytes != c->graph_key) { drop_graphs(c->s_graph, 3); c->graph_key = key.bytes; c->graph_rerun_key.clear(); }
+    hipGraphExec_t* slot = &c->s_graph[steady ? 1 : 0];
     if (cal_eval >= 0) {     // the repeat of a flagged job: a graph of its own (kept: a checkpoint that trips at one evaluation does so every job)
-      std::string rk = key; rk.append(reinterpret_cast<const char*>(&cal_eval), 4); rk.append(reinterpret_cast<const char*>(&which), 4);
-      if (rk != c->graph_rerun_key && c->graph_rerun) { (void)hipGraphExecDestroy(c->graph_rerun); c->graph_rerun = nullptr; }
-      c->graph_rerun_key = rk;
-      slot = &c->graph_rerun;
+      Key rk = key; rk.put(cal_eval); rk.put((int)steady);
+      slot = &c->s_graph[2];
+      if (rk.bytes != c->graph_rerun_key) drop_graphs(slot, 1);
+      c->graph_rerun_key = rk.bytes;
     }
-    if (!*slot) {
-      hipStream_t cs;
-      RAMP_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-      RAMP_HIP_CHECK(hipStreamSynchronize(s));
-      RAMP_HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      int rc = sample_body(c, p, sc, cs, chain, steady, cal_eval);
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(cs, &g);
-      if (rc != 0) { if (g) (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs); return rc; }
-      if (e != hipSuccess) { (void)hipStreamDestroy(cs); RAMP_HIP_CHECK(e); }
-      e = hipGraphInstantiate(slot, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs);
-      RAMP_HIP_CHECK(e);
-    }
-    RAMP_HIP_CHECK(hipGraphLaunch(*slot, s));
+    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval); }));
   }
   if (chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
   if (x_out) RAMP_HIP_CHECK(hipMemcpyAsync(x_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
@@ -1970,30 +2003,18 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
     RAMP_HIP_CHECK(hipGetLastError());
   }
+  const std::array<float, 3> comb = comb_weights(p->n_rp, p->w, 0.0);
+  const bool shared = p->n_rp > 1 && c->share_prefix;
   for (int j = 0; j < p->n_steps; ++j) {
     const bool last = p->t[j] == 0;                       // the reference's `i == 0`: smoothing + APF on the final step
     if (last) CK(launch_replan_sm(c->s_x, c->r_state, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
-    if (h3) {
-      // delayed-scaling tables: evaluation j writes table j & 1, the last one table 3, which the first evaluation of the
-      // NEXT replan reads: every steady-state replan sees the same pointers, so its graph is captured once
-      const int t_out = j + 1 == p->n_steps ? 3 : (j & 1);
-      const int t_in = j == 0 ? 3 : ((j - 1) & 1);
-      c->phase = (calibrate && j == 0) ? 1 : 2;
-      c->obs_out = c->obs + t_out * ramp_ctx::MAX_SITES;
-      c->obs_in = c->obs + t_in * ramp_ctx::MAX_SITES;
-      hipLaunchKernelGGL(zero_words_kernel, dim3(ramp_ctx::MAX_SITES / 256), dim3(256), 0, s,
-                         reinterpret_cast<unsigned*>(c->obs_out), ramp_ctx::MAX_SITES);
-      RAMP_HIP_CHECK(hipGetLastError());
-    }
-    const float comb[3] = {(float)(1.0 + p->w), -(float)p->w, 0.f};
-    const bool shared = p->n_rp > 1 && c->share_prefix;
-    const int rc_score = score_all(c, c->s_x, B, p->n_rp, p->t[j], nullptr, c->s_eps, s, shared ? comb : nullptr);
-    c->phase = 0;
-    CK(rc_score);
-    if (c->gemm_mode == 2 && !c->force_x6) {
-      hipLaunchKernelGGL(log_flag_kernel, dim3(1), dim3(64), 0, s, c->range_flag, c->trip_log, j);
-      RAMP_HIP_CHECK(hipGetLastError());
-    }
+    // delayed-scaling tables: evaluation j writes table j & 1, the last one TABLE_REPLAN_CARRY, which the first evaluation of the
+    // NEXT replan reads: every steady-state replan sees the same pointers, so its graph is captured once
+    // (no flag log: a flagged replan is repeated whole by ramp_replan, and the sampling jobs' log stays theirs)
+    const int t_out = j + 1 == p->n_steps ? TABLE_REPLAN_CARRY : (j & 1) ? TABLE_ODD : TABLE_EVEN;
+    const int t_in = j == 0 ? TABLE_REPLAN_CARRY : (j & 1) ? TABLE_EVEN : TABLE_ODD;
+    CK(guarded_eval(c, !h3 ? 0 : (calibrate && j == 0) ? 1 : 2, t_in, t_out, c->s_x, B, p->n_rp, p->t[j], nullptr, c->s_eps, s,
+                    shared ? comb.data() : nullptr));
     CfgMeanArgs m; m.x = c->s_x; m.eps = c->s_eps; m.B = B; m.HS = (int)HS; m.n_rp = shared ? 1 : p->n_rp;
     m.w0 = (float)p->w; m.w1 = 0.f; m.w0p1 = (float)(1.0 + p->w);
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
@@ -2037,34 +2058,20 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   // ---- fixed buffers the graphs read
   CK(ensure_sampler_buffers(c, B, p->n_rp, 0, false));
-  bool moved = false;
   if (!c->r_state) {
-    float* q; CK(dev_alloc(c, &q, 16)); c->r_state = reinterpret_cast<ReplanState*>(q);
-    CK(dev_alloc(c, &q, 8)); c->r_result = reinterpret_cast<int*>(q);
-    CK(dev_alloc(c, &q, 16)); c->r_hard_idx = reinterpret_cast<int*>(q);
-    CK(dev_alloc(c, &c->r_hist, HS)); CK(dev_alloc(c, &c->r_xclean, HS)); CK(dev_alloc(c, &c->r_best, HS));
-    moved = true;
+    CK(renew(c, c->r_state, 1)); CK(renew(c, c->r_result, 8)); CK(renew(c, c->r_hard_idx, 16));
+    CK(renew(c, c->r_hist, HS)); CK(renew(c, c->r_xclean, HS)); CK(renew(c, c->r_best, HS));
   }
   if ((size_t)B > c->r_cap_B) {
-    float* q;
-    CK(dev_alloc(c, &c->r_noise, n)); CK(dev_alloc(c, &c->r_plen, B)); CK(dev_alloc(c, &c->r_smooth, B));
-    CK(dev_alloc(c, &q, B)); c->r_mask = reinterpret_cast<int*>(q);
-    CK(dev_alloc(c, &q, B)); c->r_en = reinterpret_cast<int*>(q);
-    CK(dev_alloc(c, &c->r_hard_val, (size_t)16 * B * S));
-    c->r_cap_B = B; moved = true;
+    CK(renew(c, c->r_noise, n)); CK(renew(c, c->r_plen, B)); CK(renew(c, c->r_smooth, B));
+    CK(renew(c, c->r_mask, B)); CK(renew(c, c->r_en, B));
+    CK(renew(c, c->r_hard_val, (size_t)16 * B * S));
+    c->r_cap_B = B;
   }
-  if ((size_t)p->n_static > c->r_cap_static) {
-    float* q; CK(dev_alloc(c, &q, (size_t)p->n_static * 4)); c->r_static = reinterpret_cast<double*>(q);
-    c->r_cap_static = p->n_static; moved = true;
-  }
-  if ((size_t)p->n_dyn > c->r_cap_dyn) {
-    float* q; CK(dev_alloc(c, &q, (size_t)p->n_dyn * 4)); c->r_dyn = reinterpret_cast<double*>(q);
-    c->r_cap_dyn = p->n_dyn; moved = true;
-  }
-  if ((size_t)(p->n_cost + p->n_extra) > c->r_cap_cost) {
-    CK(dev_alloc(c, &c->r_cost, (size_t)(p->n_cost + p->n_extra) * 2)); c->r_cap_cost = p->n_cost + p->n_extra; moved = true;
-  }
-  if (moved) c->r_key.clear();
+  CK(grow(c, c->r_static, c->r_cap_static, (size_t)p->n_static * 2));
+  CK(grow(c, c->r_dyn, c->r_cap_dyn, (size_t)p->n_dyn * 2));
+  CK(grow(c, c->r_cost, c->r_cap_cost, (size_t)(p->n_cost + p->n_extra) * 2));
+  staging_done(c);
   // ---- this replan's inputs
   RAMP_HIP_CHECK(hipMemcpyAsync(c->r_noise, st->noise, n * 4, hipMemcpyDeviceToDevice, s));
   RAMP_HIP_CHECK(hipMemcpyAsync(c->r_hist, st->history, (size_t)st->n_hist * S * 4, hipMemcpyDeviceToDevice, s));
@@ -2085,42 +2092,22 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   ReplanState hs{}; hs.n_hist = st->n_hist; hs.stepp = st->stepp; hs.pursuer[0] = st->pursuer[0]; hs.pursuer[1] = st->pursuer[1];
   RAMP_HIP_CHECK(hipMemcpyAsync(c->r_state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
   c->launches = 0;
-  c->score_calibrated = false; c->s_calibrated = false; c->s_pending = false;      // (the replans carry their maxima in table 3: the sampling jobs' canonical table 2 survives)
+  invalidate_calibrations(c, CAL_SCORE);      // (the replans carry their maxima in TABLE_REPLAN_CARRY: the sampling jobs' canonical table survives)
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   auto run = [&](bool calibrate) -> int {
     if (!p->use_graph) return replan_body(c, p, s, calibrate);
-    std::string key;
-    auto put = [&](const void* q, size_t b) { key.append(static_cast<const char*>(q), b); };
-    put(&p->B, 4); put(&p->n_steps, 4); put(&p->w, 8); put(p->t, 4 * p->n_steps); put(p->sqrt_recip, 4 * p->n_steps);
-    put(p->sqrt_recipm1, 4 * p->n_steps); put(p->sqrt_a_t, 4 * p->n_steps); put(p->sqrt_1m_a_t, 4 * p->n_steps);
-    put(p->sqrt_a_prev, 4 * p->n_steps); put(p->dir_coef, 4 * p->n_steps); put(&p->q_sqrt_a, 4); put(&p->q_sqrt_1m_a, 4);
-    put(&p->clip_denoised, 4); put(&p->predict_x0, 4); put(&p->n_hard, 4); put(&p->sm_window_last, 4); put(&p->sm_window_final, 4); put(&p->sm_dt, 4);
-    put(&p->sm_max_vel, 4); put(&p->n_static, 4); put(&p->n_dyn, 4); put(&p->thr_static, 8); put(&p->thr_pred, 8);
-    put(&p->strength_static, 8); put(&p->strength_pred, 8); put(&p->window_static, 4); put(&p->n_cost, 4); put(&p->n_extra, 4);
-    put(&p->cost_thr, 4); put(&p->w_smooth, 4); put(&p->w_len, 4); put(&c->force_x6, 4);
-    if (key != c->r_key) {
-      for (auto& g : c->r_graph) if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
-      c->r_key = key;
-    }
-    const int which = (h3 && !calibrate) ? 1 : 0;
-    if (!c->r_graph[which]) {
-      hipStream_t cs;
-      RAMP_HIP_CHECK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-      RAMP_HIP_CHECK(hipStreamSynchronize(s));
-      RAMP_HIP_CHECK(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-      int rc = replan_body(c, p, cs, calibrate);
-      hipGraph_t g = nullptr;
-      hipError_t e = hipStreamEndCapture(cs, &g);
-      if (rc != 0) { if (g) (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs); return rc; }
-      if (e != hipSuccess) { (void)hipStreamDestroy(cs); RAMP_HIP_CHECK(e); }
-      e = hipGraphInstantiate(&c->r_graph[which], g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g); (void)hipStreamDestroy(cs);
-      RAMP_HIP_CHECK(e);
-    }
-    RAMP_HIP_CHECK(hipGraphLaunch(c->r_graph[which], s));
-    return 0;
+    Key key;      // (every r_* buffer exists before the first capture: nothing here is optional in renew()'s sense)
+    key.put(p->B); key.put(p->n_steps); key.put(p->w); key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps);
+    key.put(p->sqrt_recipm1, p->n_steps); key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps);
+    key.put(p->sqrt_a_prev, p->n_steps); key.put(p->dir_coef, p->n_steps); key.put(p->q_sqrt_a); key.put(p->q_sqrt_1m_a);
+    key.put(p->clip_denoised); key.put(p->predict_x0); key.put(p->n_hard); key.put(p->sm_window_last); key.put(p->sm_window_final); key.put(p->sm_dt);
+    key.put(p->sm_max_vel); key.put(p->n_static); key.put(p->n_dyn); key.put(p->thr_static); key.put(p->thr_pred);
+    key.put(p->strength_static); key.put(p->strength_pred); key.put(p->window_static); key.put(p->n_cost); key.put(p->n_extra);
+    key.put(p->cost_thr); key.put(p->w_smooth); key.put(p->w_len); key.put(c->force_x6);
+    if (key.bytes != c->r_key) { drop_graphs(c->r_graph, 2); c->r_key = key.bytes; }
+    return replay(&c->r_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate); });
   };
-  // a one-step replan has no second table to carry its maxima in (its only evaluation reads and clears table 3): it always
+  // a one-step replan has no second table to carry its maxima in (its only evaluation reads and clears TABLE_REPLAN_CARRY): it always
   // calibrates, on the bf16x6 kernels, instead of running fp16x3 from an empty table
   CK(run(h3 && (!c->r_calibrated || p->n_steps == 1)));
   // ---- the one read-back of a replan: {n_free, rank, row} + the range flag
@@ -2246,7 +2233,7 @@ int ramp_set_fallback(ramp_ctx* c, int32_t mode) {
   RAMP_REQUIRE(mode != 2 || c->trip_eval >= 0, "ramp_set_fallback(ctx, 2): no flagged evaluation on record (ramp_range_status of a flagged ramp_sample first)");
   c->force_x6 = mode == 1 ? 1 : 0;
   c->rerun = mode == 2 ? 1 : 0;
-  c->score_calibrated = false; c->r_calibrated = false; c->s_calibrated = false; c->s_pending = false;      // (the canonical table 2 survives: nothing writes it in a bf16x6 job)
+  invalidate_calibrations(c, CAL_SCORE | CAL_REPLAN);      // (the canonical table survives: nothing writes it in a bf16x6 job)
   return 0;
 }
 int ramp_score_mode(ramp_ctx* c, int32_t* mode) {
@@ -2278,7 +2265,7 @@ int ramp_range_trip(ramp_ctx* c, int32_t* eval, int32_t* site) {
 int ramp_set_calibration_reuse(ramp_ctx* c, int32_t on) {
   RAMP_REQUIRE(c, "null argument");
   c->cal_reuse = on ? 1 : 0;
-  c->s_calibrated = false; c->s_pending = false; c->c_cal_valid = false;
+  invalidate_calibrations(c, CAL_CANONICAL);
   return 0;
 }
 int ramp_workspace_bytes(ramp_ctx* c, int64_t* bytes) {

@@ -199,6 +199,85 @@ def test_a_job_does_not_depend_on_what_ran_before_it():
     assert np.array_equal(d, fresh)
 
 
+def test_graphs_survive_buffer_growth():
+    """A small job gives the same bits before and after a larger job has moved the context's buffers, with and without graphs.  On
+    one graph-mode and one eager context: (1) the chain_ddpm_apf job with its chain, (2) the same job with no chain asked for,
+    (3) a job of B = 12 whose cloud is the fixture's cloud twice (the same obstacles, twice the points: s_cloud, the
+    hard-condition values and every per-B buffer move), (4) job 1 again.  Final states of 1, 2 and 4 bitwise equal; chains of 1
+    and 4 bitwise equal on both contexts, to each other and to a fresh context's; chain 4 within the fixture's free-running bar
+    (test_ddpm_apf_chain_teacher_forced: states 0 .. 21 within 1e-4 of the reference).  Every job of this sequence has another
+    graph key than its predecessor (chain, B), so each captures afresh whatever the buffers did: the rule that a MOVED buffer
+    drops the graphs is what test_replan_graphs_survive_buffer_growth probes."""
+    g = np.load(f"{GOLDEN}/chain_ddpm_apf.npz")
+    big = {"noise": synth.make_noise((26, 12, 48, 4), seed=99), "cloud": np.concatenate([g["cloud"], g["cloud"]], axis=1)}
+    assert big["cloud"].shape[0] == g["cloud"].shape[0] and big["cloud"].shape[1] == 2 * g["cloud"].shape[1]
+    hc = {k: torch.from_numpy(v) for k, v in synth.default_hard_conds(4, 48).items()}
+
+    def final_only(dm):
+        with NoiseInjector(list(g["noise"])) as inj:
+            x = dm.conditional_sample(hc, horizon=48, batch_size=4, return_chain=False, obstacle_pts=dev(g["cloud"]),
+                                      noise_std_extra_schedule_fn=lambda x: 0.5)
+            assert inj.used == g["noise"].shape[0]
+        return x.cpu().numpy()
+
+    def sequence(dm):
+        c1, _ = run(dm, g, 4)
+        x2 = final_only(dm)
+        c3, _ = run(dm, big, 12)
+        assert c3.shape == (26, 12, 48, 4) and np.isfinite(c3).all()
+        c4, _ = run(dm, g, 4)
+        assert np.array_equal(c1[-1], x2) and np.array_equal(c1[-1], c4[-1])
+        return c1, c4
+
+    g1, g4 = sequence(make_static(25, use_apf=True, use_graph=True))
+    e1, e4 = sequence(make_static(25, use_apf=True, use_graph=False))
+    fresh, _ = run(make_static(25, use_apf=True, use_graph=True), g, 4)
+    assert np.array_equal(g1, g4) and np.array_equal(e1, e4) and np.array_equal(g1, e1) and np.array_equal(g4, fresh)
+    err = np.abs(g4[:22] - g["chain"][:22]).max()
+    print(f"ddpm apf after a larger job moved the buffers: states 0..21 free-running max {err:.2e}")
+    assert err < 1e-4
+
+
+def test_replan_graphs_survive_buffer_growth():
+    """The one case in which a captured graph's KEY outlives a move of the buffers its nodes point at: the replan graphs (r_key: the
+    replan's own parameters) read s_x, s_eps and s_x0, which a larger SAMPLING job on the same context reallocates.  The reference
+    planner run of replan_chain.npz (B = 6: one ramp_sample + one captured ramp_replan graph per replan), then a B = 12 sampling job
+    on the same context -- same cloud and row pattern, so no scene change drops anything -- then the same planner run again.  Without
+    the rule (engine.hip: renew sets buffers_moved, staging_done clears both keys) the second run replays replan graphs that work in
+    the old blocks while ramp_replan hands out the new s_x.  Every batch handed to a selection, every selected index and every
+    collision mask of the second run equal the first run's (a fresh context's) bit for bit, and the discrete decisions are the
+    reference run's."""
+    from ramp_amd.models import DynamicGaussianDiffusionModel
+    from util import StopReplan, make_fake_pursuit_env
+    g = np.load(f"{GOLDEN}/replan_chain.npz")
+    K = int(g["n_iter"]); B, H, S = g["noise"].shape[1:]
+    u = build_unet(4, 48, False, max_rows=4 * B)
+    dm = DynamicGaussianDiffusionModel(model=u, n_diffusion_steps=100, predict_epsilon=True, use_graph=True).eval().to("cuda")
+
+    def planner_run():
+        dataset, _sphere = make_fake_pursuit_env(stop_at=K)
+        hard = {0: dev(g["hard0"]).repeat(B, 1), H - 1: dev(g["hardN"]).repeat(B, 1)}
+        np.random.seed(23)
+        dm.replan_log = []
+        with NoiseInjector(list(g["noise"])):
+            with pytest.raises(StopReplan):
+                dm.ddim_p_sample_loop((B, H, S), hard, context={'dataset': dataset}, return_chain=True, obstacle_pts=dev(g["cloud"]))
+        return [(e["batch"].cpu().numpy(), e["idx"], e["free"].cpu().numpy()) for e in dm.replan_log]
+
+    first = planner_run()
+    assert len(first) == int(g["n_cost"]) > 2
+    ts = [int(i) for i in dm.ddim_set_timesteps(dm.ddim_num_inference_steps_high)]
+    hard2 = {0: dev(g["hard0"]).repeat(2 * B, 1), H - 1: dev(g["hardN"]).repeat(2 * B, 1)}
+    big, _ = dm._launch(2 * B, dev(synth.make_noise((1, 2 * B, H, S), seed=7)), hard2, dev(g["cloud"]), True, ts, [0] * len(ts), None, None,
+                        False, ddim_K=dm.ddim_num_inference_steps_high)
+    assert big.shape == (2 * B, H, S) and bool(torch.isfinite(big).all())
+    again = planner_run()
+    assert len(again) == len(first)
+    for j, ((b0, i0, f0), (b1, i1, f1)) in enumerate(zip(first, again)):
+        assert i0 == i1 == int(g[f"cost{j}/idx"]) and np.array_equal(f0, f1) and np.array_equal(f0, g[f"cost{j}/free"]), (j, i0, i1)
+        assert np.array_equal(b0, b1), (j, float(np.abs(b0 - b1).max()))
+
+
 def step_teacher_forced(dm, g, ddim, noise_scale=0.5, keep=None):
     """Run every loop iteration from the reference's own previous state (teacher forcing): the APF hook is
     discontinuous and stiff, so free-running chains amplify 1e-5 drift (see tests/test_oracle_vs_golden.py)."""

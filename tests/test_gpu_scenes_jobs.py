@@ -318,6 +318,47 @@ def test_jobs_do_not_depend_on_what_ran_before():
     assert np.array_equal(multi_again, multi_fresh)
 
 
+def test_graphs_survive_buffer_growth():
+    """test_gpu_sampler's test of the same name through ramp_sample_scenes, on one graph-mode and one eager context: (1) the
+    two-scene job [A, B] with its chain, (2) the same job with no chain asked for, (3) the four-scene job [A, B, A, B] -- twice
+    the trajectories, scenes and cloud points: the per-trajectory scene table, the cloud offsets, the cloud and every per-B
+    buffer move -- (4) job 1 again.  Final states of 1, 2 and 4 bitwise equal; chains of 1 and 4 bitwise equal on both contexts,
+    to each other and to a fresh context's; chain 4 within test_2d_mixed_job_meets_both_scenes_bars' free-running bar (states
+    0 .. 21 of either scene within 1e-4 of its reference); no job trips the range guard.  A regression sequence over graph, eager
+    and fresh contexts: every job here resets the scene table and has another graph key than its predecessor, so each captures
+    afresh (test_gpu_sampler.py::test_replan_graphs_survive_buffer_growth is where a key outlives a move)."""
+    ga, gb = np.load(f"{GOLDEN}/chain_ddpm_apf.npz"), np.load(f"{GOLDEN}/chain_c2.npz")
+    fx = [ga, gb]
+    noise = np.concatenate([g["noise"] for g in fx], axis=1)
+
+    def final_only(dm):
+        job, hc, B = dm._prepare_scene_job([dev(g["cloud"]) for g in fx], [_hc(4, 48) for _ in fx], [4, 4])
+        with NoiseInjector(list(noise)) as inj:
+            x = dm.conditional_sample(hc, horizon=48, batch_size=B, return_chain=False, obstacle_pts=None, scene_job=job,
+                                      noise_std_extra_schedule_fn=lambda x: 0.5)
+            assert inj.used == noise.shape[0]
+        return x.cpu().numpy()
+
+    def sequence(dm):
+        c1, _ = _run_scenes(dm, fx)
+        x2 = final_only(dm)
+        c3, ts3 = _run_scenes(dm, fx + fx)
+        assert c3.shape == (26, 16, 48, 4) and ts3.tolist() == [0] * 4 + [1] * 4 + [2] * 4 + [3] * 4
+        c4, _ = _run_scenes(dm, fx)
+        assert _range_flag(dm.model) == 0
+        assert np.array_equal(c1[-1], x2) and np.array_equal(c1[-1], c4[-1])
+        return c1, c4
+
+    g1, g4 = sequence(_static(use_graph=True))
+    e1, e4 = sequence(_static(use_graph=False))
+    fresh, _ = _run_scenes(_static(use_graph=True), fx)
+    assert np.array_equal(g1, g4) and np.array_equal(e1, e4) and np.array_equal(g1, e1) and np.array_equal(g4, fresh)
+    for s, g in enumerate(fx):
+        err = np.abs(g4[:22, 4 * s:4 * s + 4] - g["chain"][:22]).max()
+        print(f"two-scene job after a four-scene job moved the buffers, scene {s}: states 0..21 free-running max {err:.2e}")
+        assert err < 1e-4
+
+
 def test_custom_step_function_is_refused_with_a_message():
     """A caller-supplied sample_fn steps one scene's batch through the eager loop: a many-scene job refuses it by name."""
     ga, gb = np.load(f"{GOLDEN}/chain_ddpm_apf.npz"), np.load(f"{GOLDEN}/chain_c2.npz")
