@@ -158,7 +158,8 @@ struct ramp_ctx {
   // scene-encoder scratch
   float* scene_ws = nullptr; size_t scene_ws_cap = 0;
   // bf16x6 weight planes: fp32 weight base pointer -> (planes, element count)
-  int gemm_mode = 0;                 // 0 = exact fp32 MFMA, 1 = bf16x6 split on the bf16 matrix cores
+  int gemm_mode = 0;                 // 0 = exact fp32 MFMA, 1 = bf16x6 split on the bf16 matrix cores, 2 = fp16x3 split with delayed operand scaling
+                                     // (evaluations in phase 2; its calibration evaluations, phase 1, run the bf16x6 kernels): the default build
   struct X6W { unsigned short* planes; size_t n; int K; unsigned short* packed; unsigned short* packed3; float w_scale_inv; };
   std::map<const float*, X6W> x6;
   int x6_pipe = 1;                   // 1 = fragment-packed weights + pipelined kernel (RAMP_X6_PIPE=0: LDS-staged weights)
@@ -223,15 +224,18 @@ static void prof_post(ramp_ctx* c, hipStream_t s) {
   if (!c->prof_on) return;
   (void)hipEventRecord(c->prof_ev[c->prof_used++], s);
 }
-// run one kernel launch expression with launch counting and optional event bracketing
-#define LAUNCH(ctx_, stream_, cat_, flops_, expr_)                     \
-  do {                                                                 \
-    prof_pre((ctx_), (stream_), (cat_), (double)(flops_));             \
-    int _rc = (expr_);                                                 \
-    prof_post((ctx_), (stream_));                                      \
-    (ctx_)->launches++;                                                \
-    if (_rc != 0) return _rc;                                          \
-  } while (0)
+// One kernel launch with launch counting and optional event bracketing: fn() launches and returns the launch's code.  Whatever else can fail
+// (weight-plane lookup, call-site budget) is done BEFORE this, so that a profile holds whole start / stop pairs whatever happens.
+template <class F> static int bracket(ramp_ctx* c, hipStream_t s, int cat, double flops, std::array<int, 4> shape, F&& fn) {
+  prof_pre(c, s, cat, flops, shape);
+  const int rc = fn();
+  prof_post(c, s);
+  c->launches++;
+  return rc;
+}
+// ... of a launch expression without a shape tag, returning from the caller if it fails
+#define LAUNCH(ctx_, stream_, cat_, flops_, expr_) \
+  CK(bracket((ctx_), (stream_), (cat_), (double)(flops_), {0, 0, 0, 0}, [&] { return (expr_); }))
 
 namespace {
 
@@ -356,243 +360,255 @@ int build_st(ramp_ctx* c, ST& s) {
   return 0;
 }
 
-// ---- op wrappers that count launches -----------------------------------------------------------
+// ---- routing: which kernel serves each product of a score evaluation ---------------------------
+// One GEMM call site of the fp16x3 delayed scaling: where the operand's maximum of the previous evaluation is read and this evaluation's is
+// recorded, the weight's scale, the site's number (what the range guard reports) and the guard's word.  Run::take_site fills it.
+struct Site { const float* in = nullptr; float* out = nullptr; float wsi = 1.f; int id = 0; int* flag = nullptr; };
+template <class A> void attach(A& t, const Site& v) { t.amax_in = v.in; t.amax_out = v.out; t.wsi = v.wsi; t.site = v.id; t.range_flag = v.flag; }
+// the fused feed-forward's two sites, in the order of the launches it replaces (forward: FF1, FF2; backward: d(hg), FF1-dX); one guard word
+void attach(FfxArgs& f, const Site& v1, const Site& v2) {
+  f.amax_in1 = v1.in; f.amax_out1 = v1.out; f.wsi1 = v1.wsi; f.site1 = v1.id;
+  f.amax_in2 = v2.in; f.amax_out2 = v2.out; f.wsi2 = v2.wsi; f.site2 = v2.id;
+  f.range_flag = v1.flag;
+}
+
 struct Run {
   ramp_ctx* c; hipStream_t s; int R; int row0;
-  // attach the split-precision weight planes and the delayed-scaling slots of the next call site; returns 2 when the launch
-  // will run the fp16x3 fragment kernels, 1 for bf16x6 fragments, 0 otherwise (< 0: error)
-  int prep(GemmArgs& b) {
-    if (!(c->gemm_mode >= 1 && (b.N >= 128 || (c->x6_pipe && b.N >= 64)) && b.K % 32 == 0)) return 0;      // (K = 16: the narrow fp32 kernel, no planes)
-    auto it = c->x6.upper_bound(b.W);
-    if (it == c->x6.begin()) return 0;
+  template <class F> int launch(int cat, double flops, std::array<int, 4> shape, F&& fn) { return bracket(c, s, cat, flops, shape, fn); }
+
+  // ---- weight planes and call sites ----
+  // the split-precision planes of the packed weight W points into (ramp_ctx::x6) and W's offset inside it, or nothing
+  struct Planes { const ramp_ctx::X6W* e = nullptr; size_t off = 0; };
+  Planes planes(const float* W) const {
+    auto it = c->x6.upper_bound(W);
+    if (it == c->x6.begin()) return {};
     --it;
-    const auto& e = it->second;
-    if (!(b.W >= it->first && b.W < it->first + e.n)) return 0;
-    const size_t off = b.W - it->first;
-    const bool frag = c->x6_pipe && e.packed && e.K == b.K && off % (32ul * b.K) == 0 && b.N % 32 == 0;
-    if (!frag) { b.Wx = e.planes + off; b.wx_plane = (long)e.n; return 0; }
+    if (!(W >= it->first && W < it->first + it->second.n)) return {};
+    return {&it->second, (size_t)(W - it->first)};
+  }
+  // ... hold W [N][K] in the 32-row fragments the pipelined kernels stream: the bf16 ones, and (h3) the fp16 ones of the fp16x3 evaluations too
+  bool fragments(const Planes& p, int N, int K, bool h3) const {
+    return c->x6_pipe && p.e && p.e->packed && (!h3 || p.e->packed3) && p.e->K == K && p.off % (32ul * K) == 0 && N % 32 == 0;
+  }
+  bool has_h3(const float* W, int N, int K) const { return fragments(planes(W), N, K, true); }
+  // the products that run on weight planes at all: not in exact-fp32 mode, not the narrow outputs, not K = 16 (the narrow exact-fp32 kernel)
+  bool on_planes(int N, int K) const { return c->gemm_mode >= 1 && (N >= 128 || (c->x6_pipe && N >= 64)) && K % 32 == 0; }
+  // The next call site.  The ONLY place a site is numbered: every evaluation of a job must number its sites alike, whichever kernels
+  // serve them, because an evaluation is scaled from the maxima its predecessor recorded under the same numbers.  By phase: 2 reads the
+  // delayed scale and arms the guard (which judges the delayed scale); 1 (calibration: unscaled operands) only records; 0 numbers, nothing else.
+  int take_site(float wsi, Site* v) {
     RAMP_REQUIRE(c->site < ramp_ctx::MAX_SITES, "too many GEMM call sites for the scale table");
-    int kind = 1;
-    if (c->phase == 2 && e.packed3) {
-      b.Wx = e.packed3 + 2 * off; b.wx_packed = 2; b.w_scale_inv = e.w_scale_inv;
-      b.a_absmax_in = c->obs_in + c->site; b.a_absmax_out = c->obs_out + c->site; b.range_flag = c->range_flag;
-      b.site_id = c->site;
-      kind = 2;
-    } else {
-      b.Wx = e.packed + 3 * off; b.wx_packed = 1;
-      if (c->phase >= 1) b.a_absmax_out = c->obs_out + c->site;
-    }
+    const bool scaled = c->phase == 2;
+    *v = Site{scaled ? c->obs_in + c->site : nullptr, c->phase >= 1 ? c->obs_out + c->site : nullptr, wsi, c->site, scaled ? c->range_flag : nullptr};
     c->site++;
-    return kind;
+    return 0;
+  }
+  // ... of a token- or sample-owning launch on the weight W [N][K], with W's fp16 fragment planes: the site, planes and scale prep() attaches
+  // to the tile launch it replaces (same operand, same maxima)
+  int h3_site(const char* who, const float* W, int N, int K, const unsigned short** Wx, Site* v) {
+    const Planes p = planes(W);
+    RAMP_REQUIRE(on_planes(N, K) && fragments(p, N, K, true), std::string(who) + ": weight without fp16 fragment planes (its use_* predicate must have been checked)");
+    if (Wx) *Wx = p.e->packed3 + 2 * p.off;
+    return take_site(p.e->w_scale_inv, v);
+  }
+  // attach the split-precision weight planes and the delayed-scaling slots of the next call site to a tile launch; returns 2 when the launch
+  // will run the fp16x3 fragment kernels, 1 for bf16x6 fragments, 0 otherwise (< 0: error).  Only fragment launches take a site.
+  int prep(GemmArgs& b) {
+    if (!on_planes(b.N, b.K)) return 0;
+    const Planes p = planes(b.W);
+    if (!p.e) return 0;
+    if (!fragments(p, b.N, b.K, false)) { b.Wx = p.e->planes + p.off; b.wx_plane = (long)p.e->n; return 0; }
+    Site v;
+    CK(take_site(p.e->w_scale_inv, &v));
+    if (c->phase == 2 && p.e->packed3) {
+      b.Wx = p.e->packed3 + 2 * p.off; b.wx_packed = 2; b.w_scale_inv = v.wsi;
+      b.a_absmax_in = v.in; b.a_absmax_out = v.out; b.range_flag = v.flag; b.site_id = v.id;
+      return 2;
+    }
+    b.Wx = p.e->packed + 3 * p.off; b.wx_packed = 1; b.a_absmax_out = v.out;      // bf16x6 fragments: unscaled, unguarded; the maximum recorded in phases >= 1
+    return 1;
+  }
+
+  // ---- the fast-path predicates ----
+  // A family serves a product when the evaluation is steady() (tkc: or the calibration one), the launch has at least the family's row
+  // threshold (ramp_launch_plan; 0 = never), the family's shape rule holds and the planes it streams exist (h3 = has_h3 of the weight):
+  //   family       threshold                  shape rule                                                                        phases
+  //   ff_fwd       ff_fused                   FF1 -> GEGLU -> FF2 forward, both weights h3 (gemm.hip)                             2
+  //   ffx / ffx16  ffx_min_rows               a feed-forward pair, forward and backward; STBlock::ffx_f                          2
+  //   tkl / tkl16  tkl_min_rows               K = lda = 256, one tap, N % 32 == 0, N <= 768, no second operand / output; h3       2
+  //   tklb         tkl_min_rows               d(ln1) + LN1 backward: W [256][768] h3; not tklb_off                                2
+  //   ato, atb     atk_min_rows               ato_applicable (atk.hip): L divides 48 or 32; ato: STBlock::ato_w                   2
+  //   abl          atk_min_rows               atb's rule, STBlock::abl_w, wqkv_b h3; abl_on, not tklb_off, tkl_min_rows > 0       2
+  //   tkc          tkc_min_rows               plain k = 5 conv, tkc_applicable (tkc.hip), 32-bit row offsets; ramp_ctx::tkc_w     1, 2
+  //   tkw          tkw_min_rows               plain k = 5 conv + its GroupNorm, tkw_applicable (tkw.hip); h3                      2
+  // No predicate tests force_x6: phase is non-zero only where the caller has established gemm_mode == 2 && !force_x6 first (ramp_score,
+  // sample_body, replan_body, and the steady jobs' canonical_calibration), and ramp_replan raises force_x6 only around a phase-0 repeat --
+  // so the !force_x6 that tkc_planes and use_tkw used to carry was implied by their phase test.
+  bool steady() const { return c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe; }
+  static bool from(int min_rows, int M) { return min_rows > 0 && M >= min_rows; }
+  static bool plain_conv5(const GemmArgs& a) {
+    return a.taps == 5 && !a.Amul && !a.rowbias && a.epi == EPI_LINEAR && a.a_stride == 1 && a.c_rstride == 1 && a.c_roff == 0 &&
+           ((a.shift0 == -2 && a.shift_step == 1) || (a.shift0 == 2 && a.shift_step == -1));
   }
   // a k = 5 convolution with C_in, C_out in {32, 64} on the sample-owning kernel (tkc.hip): in the calibration evaluation too (unscaled
   // operand, maximum recorded), so that the call sites number the same in every fp16x3 evaluation of a job
   const ramp_ctx::TkcW* tkc_planes(const GemmArgs& a) const {
-    if (!(c->tkc_min_rows > 0 && a.M >= c->tkc_min_rows && c->gemm_mode == 2 && (c->phase == 1 || c->phase == 2) && !c->force_x6 && c->x6_pipe)) return nullptr;
-    if (!(a.taps == 5 && !a.A2 && !a.Amul && !a.C2 && !a.rowbias && a.epi == EPI_LINEAR && a.a_stride == 1 && a.c_rstride == 1 && a.c_roff == 0)) return nullptr;
-    if (!((a.shift0 == -2 && a.shift_step == 1) || (a.shift0 == 2 && a.shift_step == -1))) return nullptr;
+    const bool calibrating = c->gemm_mode == 2 && c->phase == 1 && c->x6_pipe;
+    if (!(from(c->tkc_min_rows, a.M) && (steady() || calibrating) && plain_conv5(a) && !a.A2 && !a.C2)) return nullptr;
     if (!tkc_applicable(a.M, a.L, a.N, a.K, nullptr)) return nullptr;
     if (!((long)a.M * a.lda * 4 < (1l << 32))) return nullptr;      // (32-bit row offsets: larger launches keep the tile kernels)
     auto it = c->tkc_w.find(a.W);
     return it == c->tkc_w.end() ? nullptr : &it->second;
   }
-  struct GnPro { const float* c; const float* stats; const float* gamma; const float* beta; };
-  struct GnEpi { float* cst; float* stats; const float* gamma; const float* beta; const float* tbias; float eps; };
-  // ... with the GroupNorm + Mish of its Conv1dBlock fused like tkw below (pro: the input gradient's operand; epi: behind the forward convolution)
+  // ... with the GroupNorm + Mish of its Conv1dBlock fused like tkw below (epi: behind the forward convolution; else the input gradient's operand)
   const ramp_ctx::TkcW* tkc_gn_planes(const GemmArgs& a, bool epi) const {
     if (!(c->tkc_gn & (epi ? 1 : 2)) || (epi && a.resid2)) return nullptr;
     return tkc_planes(a);
   }
-  int tkc(const GemmArgs& a, const ramp_ctx::TkcW& w, const GnPro* pro = nullptr, const GnEpi* epi = nullptr) {
-    RAMP_REQUIRE(c->site < ramp_ctx::MAX_SITES, "too many GEMM call sites for the scale table");
-    prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, -5});
-    TkcArgs t; t.M = a.M; t.L = a.L; t.N = a.N; t.K = a.K; t.dir = a.shift_step; t.X = a.A; t.ldx = a.lda; t.W = w.planes; t.bias = a.bias;
-    t.resid = a.resid; t.ldr = a.ldr; t.resid2 = a.resid2; t.ldr2 = a.ldr2; t.Y = a.C; t.ldy = a.ldc;
-    t.amax_in = c->phase == 2 ? c->obs_in + c->site : nullptr; t.amax_out = c->obs_out + c->site; t.wsi = w.wsi; t.site = c->site;
-    t.range_flag = c->phase == 2 ? c->range_flag : nullptr;      // (the guard judges the DELAYED scale; the calibration evaluation runs unscaled)
-    if (pro) { t.gn_c = pro->c; t.gn_stats = pro->stats; t.gn_gamma = pro->gamma; t.gn_beta = pro->beta; }
-    if (epi) { t.Cst = epi->cst; t.stats = epi->stats; t.gamma = epi->gamma; t.beta = epi->beta; t.tbias = epi->tbias; t.eps = epi->eps; }
-    c->site++;
-    int rc = launch_tkc(t, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
-  }
   // a wide k = 5 convolution (forward: C_out in {128, 256, 512}, C_in up to 1024 from two sources; input gradient: outputs up to 1024)
-  // with its GroupNorm fused (tkw.hip): forward = GroupNorm + Mish behind it (epi),
-  // input gradient = GroupNorm backward folded into the operand (pro); consumes the call site of the tile launch it replaces
+  // with its GroupNorm fused (tkw.hip): forward = GroupNorm + Mish behind it (epi), input gradient = GroupNorm backward folded into the
+  // operand (pro); neither with a second operand / output on the fused side
   bool use_tkw(const GemmArgs& a, bool pro, bool epi) const {
-    return c->tkw_min_rows > 0 && a.M >= c->tkw_min_rows && c->gemm_mode == 2 && c->phase == 2 && !c->force_x6 && c->x6_pipe && a.taps == 5 && !a.Amul &&
-           !a.rowbias && a.epi == EPI_LINEAR && a.a_stride == 1 && a.c_rstride == 1 && a.c_roff == 0 &&
-           ((a.shift0 == -2 && a.shift_step == 1) || (a.shift0 == 2 && a.shift_step == -1)) && tkw_applicable(a.M, a.L, a.N, a.K, pro, epi) &&
+    return from(c->tkw_min_rows, a.M) && steady() && plain_conv5(a) && tkw_applicable(a.M, a.L, a.N, a.K, pro, epi) &&
            (!a.A2 || !pro) && (!a.C2 || !epi) && has_h3(a.W, a.N, a.K);
-  }
-  int tkw(const GemmArgs& a, const GnPro* pro, const GnEpi* epi) {
-    GemmArgs b = a;
-    const int kind = prep(b);
-    if (kind < 0) return kind;
-    RAMP_REQUIRE(kind == 2, "tkw: weight without fp16 fragment planes (use_tkw must have been checked)");
-    prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K * 5, {a.M, a.N, a.K, -7});
-    TkwArgs t; t.M = a.M; t.L = a.L; t.N = a.N; t.K = a.K; t.dir = a.shift_step; t.X = a.A; t.ldx = a.lda; t.X2 = a.A2; t.ldx2 = a.lda2;
-    t.K1 = a.A2 ? a.K1 : a.K; t.W = b.Wx; t.wsi = b.w_scale_inv; t.bias = a.bias; t.resid = a.resid; t.ldr = a.ldr; t.resid2 = a.resid2; t.ldr2 = a.ldr2;
-    t.Y = a.C; t.ldy = a.ldc; t.Y2 = a.C2; t.ldy2 = a.ldc2; t.N1 = a.C2 ? a.N1 : a.N;
-    if (pro) { t.gn_c = pro->c; t.gn_stats = pro->stats; t.gn_gamma = pro->gamma; t.gn_beta = pro->beta; }
-    if (epi) { t.Cst = epi->cst; t.stats = epi->stats; t.gamma = epi->gamma; t.beta = epi->beta; t.tbias = epi->tbias; t.eps = epi->eps; }
-    t.amax_in = b.a_absmax_in; t.amax_out = b.a_absmax_out; t.site = b.site_id; t.range_flag = b.range_flag;
-    int rc = launch_tkw(t, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
-  }
-  int gemm(const GemmArgs& a) {
-    if (a.K % 32 != 0) {      // 16-wide operands (unet_input_dim = 16): exact fp32 narrow kernel, no weight planes, no call site
-      prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, a.taps});
-      int rc = launch_gemm(a, s);
-      prof_post(c, s);
-      c->launches++;
-      return rc;
-    }
-    if (const ramp_ctx::TkcW* w = tkc_planes(a)) return tkc(a, *w);
-    prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, a.taps});
-    GemmArgs b = a;
-    b.three_ok = c->three_blocks;
-    const int kind = prep(b);
-    if (kind < 0) return kind;
-    int rc = launch_gemm(b, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
   }
   // the token-owning fused feed-forward (ffx.hip) serves this feed-forward pair, forward AND backward (the stash layout is
   // private to the two kernels, so both directions of an evaluation must agree: same phase, same M)
-  bool use_ffx(const STBlock& k, int M) const {
-    return k.ffx_f && c->ffx_min_rows > 0 && M >= c->ffx_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe;
+  bool use_ffx(const STBlock& k, int M) const { return k.ffx_f && from(c->ffx_min_rows, M) && steady(); }
+  // a K = 256 linear on the token-owning kernel (tkl.hip); a weight without fp16 fragment planes keeps its launch on the tile kernels
+  bool use_tkl(const GemmArgs& a) const {
+    return from(c->tkl_min_rows, a.M) && steady() && a.K == 256 && a.lda == 256 && a.taps == 1 && a.N % 32 == 0 && a.N <= 768 && !a.A2 &&
+           !a.Amul && !a.resid2 && !a.C2 && a.epi == EPI_LINEAR && has_h3(a.W, a.N, a.K);
   }
-  // consumes the two call sites of the launches it replaces (forward: FF1, FF2; backward: d(hg), FF1-dX), in their order
+  // self-attention + output projection in one launch of sample-owning waves (atk.hip); atb: the attention backward on the same waves
+  bool use_atb(int M, int L) const { return from(c->atk_min_rows, M) && steady() && ato_applicable(M, L, nullptr); }
+  bool use_ato(const STBlock& k, int M, int L) const { return k.ato_w && use_atb(M, L); }
+  // attention backward + d(ln1) + LayerNorm-1 backward in one launch of sample-owning waves (atl.hip), from atk_min_rows tokens on
+  bool use_abl(const STBlock& k, int M, int L) const {
+    return c->abl_on && k.abl_w && use_atb(M, L) && !c->tklb_off && c->tkl_min_rows > 0 && has_h3(k.wqkv_b, 256, 768);
+  }
+  // d(ln1) = d(qkv) Wqkv^T and the LayerNorm-1 backward behind it in one token-owning launch (tkl.hip, tklb_kernel)
+  bool use_tklb(int M, const float* W) const { return !c->tklb_off && from(c->tkl_min_rows, M) && steady() && has_h3(W, 256, 768); }
+
+  // ---- the launch wrappers: take the call site(s) of the tile launch(es) they replace, then launch ----
+  // The GroupNorm around a sample-owning convolution, from the arguments of the launch it absorbs.  pro = the gn_bwd in front of an input
+  // gradient: the operand becomes its dy, normalised against the stash pro->x.  epi = the gn_fwd behind a forward convolution: the
+  // convolution's own output (t.Y so far) is the stash, the activation (+ time bias, + residual) goes to epi->y.
+  template <class T> static void fuse_gn(T& t, const GnBwdArgs* pro, const GnArgs* epi) {
+    if (pro) { t.X = pro->dy; t.ldx = pro->C; t.gn_c = pro->x; t.gn_stats = pro->stats; t.gn_gamma = pro->gamma; t.gn_beta = pro->beta; }
+    if (epi) {
+      t.Cst = t.Y; t.stats = epi->stats; t.gamma = epi->gamma; t.beta = epi->beta; t.tbias = epi->tbias; t.eps = epi->eps;
+      t.Y = epi->y; t.ldy = epi->C;
+      if (epi->resid) { t.resid = epi->resid; t.ldr = epi->C; }
+    }
+  }
+  int tkc(const GemmArgs& a, const ramp_ctx::TkcW& w, const GnBwdArgs* pro = nullptr, const GnArgs* epi = nullptr) {
+    Site v;
+    CK(take_site(w.wsi, &v));
+    TkcArgs t; t.M = a.M; t.L = a.L; t.N = a.N; t.K = a.K; t.dir = a.shift_step; t.X = a.A; t.ldx = a.lda; t.W = w.planes; t.bias = a.bias;
+    t.resid = a.resid; t.ldr = a.ldr; t.resid2 = a.resid2; t.ldr2 = a.ldr2; t.Y = a.C; t.ldy = a.ldc;
+    attach(t, v); fuse_gn(t, pro, epi);
+    return launch(CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, -5}, [&] { return launch_tkc(t, s); });
+  }
+  int tkw(const GemmArgs& a, const GnBwdArgs* pro, const GnArgs* epi) {
+    const unsigned short* Wx; Site v;
+    CK(h3_site("tkw", a.W, a.N, a.K, &Wx, &v));
+    TkwArgs t; t.M = a.M; t.L = a.L; t.N = a.N; t.K = a.K; t.dir = a.shift_step; t.X = a.A; t.ldx = a.lda; t.X2 = a.A2; t.ldx2 = a.lda2;
+    t.K1 = a.A2 ? a.K1 : a.K; t.W = Wx; t.bias = a.bias; t.resid = a.resid; t.ldr = a.ldr; t.resid2 = a.resid2; t.ldr2 = a.ldr2;
+    t.Y = a.C; t.ldy = a.ldc; t.Y2 = a.C2; t.ldy2 = a.ldc2; t.N1 = a.C2 ? a.N1 : a.N;
+    attach(t, v); fuse_gn(t, pro, epi);
+    return launch(CAT_GEMM, 2.0 * a.M * a.N * a.K * 5, {a.M, a.N, a.K, -7}, [&] { return launch_tkw(t, s); });
+  }
+  // any GEMM-class product: the narrow convolutions on tkc where it applies, else the tile kernels
+  int gemm(const GemmArgs& a) {
+    if (const ramp_ctx::TkcW* w = tkc_planes(a)) return tkc(a, *w);
+    GemmArgs b = a;
+    if (a.K % 32 == 0) {      // (else 16-wide operands, unet_input_dim = 16: the exact fp32 narrow kernel, no weight planes, no call site)
+      b.three_ok = c->three_blocks;
+      const int kind = prep(b);
+      if (kind < 0) return kind;
+    }
+    return launch(CAT_GEMM, 2.0 * a.M * a.N * a.K * a.taps, {a.M, a.N, a.K, a.taps}, [&] { return launch_gemm(b, s); });
+  }
+  // A k = 5 convolution and the GroupNorm + Mish of its Conv1dBlock.  a = the convolution, writing the stash g.x; g = the gn_fwd that follows
+  // it.  One launch on tkw, else on tkc, else the pair.  gn_due: the caller has a launch to put between the pair and launches g itself if told to.
+  int conv_gn(const GemmArgs& a, const GnArgs& g, bool* gn_due = nullptr) {
+    RAMP_REQUIRE(a.C == g.x, "conv_gn: the convolution must write the GroupNorm's input");
+    if (gn_due) *gn_due = false;
+    if (use_tkw(a, false, true)) return tkw(a, nullptr, &g);
+    if (const ramp_ctx::TkcW* w = tkc_gn_planes(a, true)) return tkc(a, *w, nullptr, &g);
+    CK(gemm(a));
+    if (gn_due) { *gn_due = true; return 0; }
+    return launch(CAT_ROW, 0, {0, 0, 0, 0}, [&] { return launch_gn_fwd(g, s); });
+  }
+  // The input gradient of that pair.  g = the gn_bwd (into g.dx), a = the transposed convolution reading g.dx.  One launch on tkw or tkc
+  // (the GroupNorm backward is the operand staging of the convolution: g.dx is never written), else the pair.
+  int gn_conv_bwd(const GnBwdArgs& g, const GemmArgs& a) {
+    RAMP_REQUIRE(a.A == g.dx && !g.add, "gn_conv_bwd: the convolution must read the GroupNorm backward's plain result");
+    if (use_tkw(a, true, false)) return tkw(a, &g, nullptr);
+    if (const ramp_ctx::TkcW* w = tkc_gn_planes(a, false)) return tkc(a, *w, &g, nullptr);
+    CK(launch(CAT_ROW, 0, {0, 0, 0, 0}, [&] { return launch_gn_bwd(g, s); }));
+    return gemm(a);
+  }
   int ffx(const STBlock& k, bool bwd, const float* X, const float* z1, float* Y, int M) {
-    RAMP_REQUIRE(c->site + 2 <= ramp_ctx::MAX_SITES, "too many GEMM call sites for the scale table");
-    prof_pre(c, s, CAT_GEMM, 2.0 * M * (2048.0 * 256 + 256.0 * 1024), {M, bwd ? -3 : -2, 256, 2});
+    Site v1, v2;
+    CK(take_site(bwd ? k.ffx_wsi_w2 : k.ffx_wsi_w1, &v1)); CK(take_site(bwd ? k.ffx_wsi_w1 : k.ffx_wsi_w2, &v2));
     FfxArgs f; f.M = M; f.X = X; f.Z1 = z1; f.Y = Y; f.stash = k.a_ag; f.ln_g = k.ln3_g; f.ln_b = k.ln3_b;
     const bool s16 = c->mfma16 && k.ffx16_f;
-    f.Wstream = s16 ? (bwd ? k.ffx16_b : k.ffx16_f) : (bwd ? k.ffx_b : k.ffx_f); f.b1 = k.b1_pk; f.b2 = k.b2; f.range_flag = c->range_flag;
-    f.amax_in1 = c->obs_in + c->site; f.amax_out1 = c->obs_out + c->site; f.site1 = c->site;
-    f.amax_in2 = c->obs_in + c->site + 1; f.amax_out2 = c->obs_out + c->site + 1; f.site2 = c->site + 1;
-    f.wsi1 = bwd ? k.ffx_wsi_w2 : k.ffx_wsi_w1; f.wsi2 = bwd ? k.ffx_wsi_w1 : k.ffx_wsi_w2;
+    f.Wstream = s16 ? (bwd ? k.ffx16_b : k.ffx16_f) : (bwd ? k.ffx_b : k.ffx_f); f.b1 = k.b1_pk; f.b2 = k.b2;
     f.ablate = s16 ? 0 : c->ffx_ablate;
-    c->site += 2;
-    int rc = s16 ? launch_ffx16(f, bwd, s) : launch_ffx(f, bwd, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
+    attach(f, v1, v2);
+    return launch(CAT_GEMM, 2.0 * M * (2048.0 * 256 + 256.0 * 1024), {M, bwd ? -3 : -2, 256, 2}, [&] { return s16 ? launch_ffx16(f, bwd, s) : launch_ffx(f, bwd, s); });
   }
-  // a K = 256 linear on the token-owning kernel (tkl.hip), optionally with LayerNorm folded into its operand; consumes the
-  // call site of the tile-kernel launch it replaces (same operand, same maxima)
-  // the weight W [N][K] carries fragment-packed fp16 planes (what prep() would attach in an fp16x3 evaluation): a weight without
-  // them keeps its launch on the tile kernels instead of failing inside the token-owning wrapper
-  bool has_h3(const float* W, int N, int K) const {
-    auto it = c->x6.upper_bound(W);
-    if (it == c->x6.begin()) return false;
-    --it;
-    const auto& e = it->second;
-    if (!(W >= it->first && W < it->first + e.n)) return false;
-    const size_t off = W - it->first;
-    return c->x6_pipe && e.packed && e.packed3 && e.K == K && off % (32ul * K) == 0 && N % 32 == 0;
-  }
-  bool use_tkl(const GemmArgs& a) const {
-    return c->tkl_min_rows > 0 && a.M >= c->tkl_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe && a.K == 256 && a.lda == 256 &&
-           a.taps == 1 && a.N % 32 == 0 && a.N <= 768 && !a.A2 && !a.Amul && !a.resid2 && !a.C2 && a.epi == EPI_LINEAR && has_h3(a.W, a.N, a.K);
-  }
+  // optionally with LayerNorm folded into the operand
   int tkl(const GemmArgs& a, const float* ln_g, const float* ln_b) {
-    GemmArgs b = a;
-    const int kind = prep(b);
-    if (kind < 0) return kind;
-    RAMP_REQUIRE(kind == 2, "tkl: weight without fp16 fragment planes (use_tkl must have been checked)");
-    prof_pre(c, s, CAT_GEMM, 2.0 * a.M * a.N * a.K, {a.M, a.N, a.K, ln_g ? -11 : -10});
-    TklArgs t; t.M = a.M; t.N = a.N; t.X = a.A; t.Y = a.C; t.ldy = a.ldc; t.W = b.Wx; t.bias = a.bias; t.resid = a.resid; t.ldr = a.ldr;
+    const unsigned short* Wx; Site v;
+    CK(h3_site("tkl", a.W, a.N, a.K, &Wx, &v));
+    TklArgs t; t.M = a.M; t.N = a.N; t.X = a.A; t.Y = a.C; t.ldy = a.ldc; t.W = Wx; t.bias = a.bias; t.resid = a.resid; t.ldr = a.ldr;
     t.rowbias = a.rowbias; t.rowvar = a.rowvar; t.row0 = a.row0; t.rb_stride = a.rb_stride; t.L = a.L; t.n_var = a.rowbias ? c->n_variants : 0;
-    t.ln_g = ln_g; t.ln_b = ln_b; t.amax_in = b.a_absmax_in; t.amax_out = b.a_absmax_out; t.wsi = b.w_scale_inv; t.site = b.site_id;
-    t.range_flag = b.range_flag;
+    t.ln_g = ln_g; t.ln_b = ln_b;
+    attach(t, v);
     auto w16 = c->mfma16 ? c->tk16_w.find(a.W) : c->tk16_w.end();      // the same linear on v_mfma_f32_16x16x32_f16 (tkl16.hip): its own fragment planes, same scale
-    if (w16 != c->tk16_w.end()) t.W = w16->second;
-    int rc = w16 != c->tk16_w.end() ? launch_tkl16(t, s) : launch_tkl(t, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
+    const bool m16 = w16 != c->tk16_w.end();
+    if (m16) t.W = w16->second;
+    return launch(CAT_GEMM, 2.0 * a.M * a.N * a.K, {a.M, a.N, a.K, ln_g ? -11 : -10}, [&] { return m16 ? launch_tkl16(t, s) : launch_tkl(t, s); });
   }
-  // self-attention + output projection (+ bias, + the row variant's cross-attention constant, + residual) in one launch of
-  // sample-owning waves (atk.hip); consumes the call site of the out-projection launch it replaces (same operand o, same maxima)
-  bool use_ato(const STBlock& k, int M, int L) const {
-    return k.ato_w && c->atk_min_rows > 0 && M >= c->atk_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe &&
-           ato_applicable(M, L, nullptr);
-  }
-  bool use_atb(int M, int L) const {
-    return c->atk_min_rows > 0 && M >= c->atk_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe && ato_applicable(M, L, nullptr);
-  }
+  // a plain linear: on tkl where it applies, else the tile kernels
+  int linear(const GemmArgs& a) { return use_tkl(a) ? tkl(a, nullptr, nullptr) : gemm(a); }
+  // (+ bias, + the row variant's cross-attention constant, + residual); the site is the out-projection's (operand o)
   int ato(const STBlock& k, const float* qkv, const float* resid, float* Y, int M, int L, const float* rowbias, int rb_stride) {
-    RAMP_REQUIRE(c->site < ramp_ctx::MAX_SITES, "too many GEMM call sites for the scale table");
-    prof_pre(c, s, CAT_GEMM, 2.0 * M * 256 * 256 + 16.0 * M * L * 64, {M, 256, 256, -4});
+    Site v;
+    CK(take_site(k.ato_wsi, &v));
     AtoArgs t; t.M = M; t.L = L; t.QKV = qkv; t.W = k.ato_w; t.bias = k.bo; t.resid = resid; t.Y = Y;
     t.rowbias = rowbias; t.rowvar = c->row_variant; t.row0 = row0; t.rb_stride = rb_stride; t.n_var = rowbias ? c->n_variants : 0;
-    t.amax_in = c->obs_in + c->site; t.amax_out = c->obs_out + c->site; t.wsi = k.ato_wsi; t.site = c->site; t.range_flag = c->range_flag;
-    c->site++;
-    int rc = launch_ato(t, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
+    attach(t, v);
+    return launch(CAT_GEMM, 2.0 * M * 256 * 256 + 16.0 * M * L * 64, {M, 256, 256, -4}, [&] { return launch_ato(t, s); });
   }
-  // attention backward + d(ln1) + LayerNorm-1 backward in one launch of sample-owning waves (atl.hip): d(qkv) never reaches HBM;
-  // consumes the call site of the d(ln1) GEMM it contains
-  bool use_abl(const STBlock& k, int M, int L) const {
-    return c->abl_on && k.abl_w && use_atb(M, L) && !c->tklb_off && c->tkl_min_rows > 0 && has_h3(k.wqkv_b, 256, 768);      // (from atk_rows tokens on)
-  }
+  // d(qkv) never reaches HBM; the site is the d(ln1) GEMM's (scale: the wqkv_b planes', weights: the block's own stream)
   int abl(const STBlock& k, const float* qkv, const float* dout, const float* z, const float* add, float* out, int M, int L) {
-    GemmArgs b; b.A = c->t_dqkv; b.lda = 768; b.W = k.wqkv_b; b.C = out; b.ldc = 256; b.M = M; b.N = 256; b.K = 768; b.taps = 1; b.L = 1;
-    const int kind = prep(b);                               // (the site's scale slots and the weight's scale; no operand is read through b)
-    if (kind < 0) return kind;
-    RAMP_REQUIRE(kind == 2, "abl: weight without fp16 fragment planes (use_abl must have been checked)");
-    prof_pre(c, s, CAT_GEMM, 2.0 * M * 256 * 768 + 32.0 * M * L * 64, {M, 256, 768, -6});
+    Site v;
+    CK(h3_site("abl", k.wqkv_b, 256, 768, nullptr, &v));
     AblArgs t; t.M = M; t.L = L; t.QKV = qkv; t.dO = dout; t.W = k.abl_w; t.Z = z; t.add = add; t.ln_g = k.ln1_g; t.Y = out;
-    t.amax_in = b.a_absmax_in; t.amax_out = b.a_absmax_out; t.wsi = b.w_scale_inv; t.site = b.site_id; t.range_flag = b.range_flag;
-    int rc = launch_abl(t, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
-  }
-  // d(ln1) = d(qkv) Wqkv^T and the LayerNorm-1 backward behind it in one token-owning launch (tkl.hip, tklb_kernel); consumes
-  // the call site of the d(ln1) GEMM it replaces
-  bool use_tklb(int M, const float* W) const {
-    return !c->tklb_off && c->tkl_min_rows > 0 && M >= c->tkl_min_rows && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe && has_h3(W, 256, 768);
+    attach(t, v);
+    return launch(CAT_GEMM, 2.0 * M * 256 * 768 + 32.0 * M * L * 64, {M, 256, 768, -6}, [&] { return launch_abl(t, s); });
   }
   int tklb(const float* dqkv, const float* W, const float* z, const float* ln_g, const float* add, float* out, int M) {
-    GemmArgs b; b.A = dqkv; b.lda = 768; b.W = W; b.C = out; b.ldc = 256; b.M = M; b.N = 256; b.K = 768; b.taps = 1; b.L = 1;
-    const int kind = prep(b);
-    if (kind < 0) return kind;
-    RAMP_REQUIRE(kind == 2, "tklb: weight without fp16 fragment planes (use_tklb must have been checked)");
-    prof_pre(c, s, CAT_GEMM, 2.0 * M * 256 * 768, {M, 256, 768, -12});
-    TklbArgs t; t.M = M; t.X = dqkv; t.Z = z; t.add = add; t.Y = out; t.W = b.Wx; t.ln_g = ln_g;
-    t.amax_in = b.a_absmax_in; t.amax_out = b.a_absmax_out; t.wsi = b.w_scale_inv; t.site = b.site_id; t.range_flag = b.range_flag;
-    int rc = launch_tklb(t, s);
-    prof_post(c, s);
-    c->launches++;
-    return rc;
+    const unsigned short* Wx; Site v;
+    CK(h3_site("tklb", W, 256, 768, &Wx, &v));
+    TklbArgs t; t.M = M; t.X = dqkv; t.Z = z; t.add = add; t.Y = out; t.W = Wx; t.ln_g = ln_g;
+    attach(t, v);
+    return launch(CAT_GEMM, 2.0 * M * 256 * 768, {M, 256, 768, -12}, [&] { return launch_tklb(t, s); });
   }
   // FF1 -> GEGLU -> FF2 of one transformer block (layers_attention_mini.py:38-45, 147): one fused launch in the fp16x3
   // evaluations (the 1024-wide hidden stays in LDS), two launches otherwise.  Either way the two call sites are
   // numbered in the same order, so calibration and fused evaluations read each other's maxima.
   int ff_forward(const GemmArgs& u, const GemmArgs& f2) {
+    if (!(c->ff_fused && u.M >= c->ff_fused && steady())) { CK(gemm(u)); return gemm(f2); }
     GemmArgs b1 = u, b2 = f2;
-    if (c->ff_fused && u.M >= c->ff_fused && c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe) {
-      prof_pre(c, s, CAT_GEMM, 2.0 * u.M * u.N * u.K + 2.0 * f2.M * f2.N * f2.K, {u.M, -1, u.K, 2});
-      const int k1 = prep(b1); if (k1 < 0) return k1;
-      const int k2 = prep(b2); if (k2 < 0) return k2;
-      RAMP_REQUIRE(k1 == 2 && k2 == 2, "fused feed-forward: weights without fp16 planes");
-      int rc = launch_ff_fwd(b1, b2, s);
-      prof_post(c, s);
-      c->launches++;
-      return rc;
-    }
-    if (int rc = gemm(u)) return rc;
-    return gemm(f2);
+    const int k1 = prep(b1); if (k1 < 0) return k1;
+    const int k2 = prep(b2); if (k2 < 0) return k2;
+    RAMP_REQUIRE(k1 == 2 && k2 == 2, "fused feed-forward: weights without fp16 planes");
+    return launch(CAT_GEMM, 2.0 * u.M * u.N * u.K + 2.0 * f2.M * f2.N * f2.K, {u.M, -1, u.K, 2}, [&] { return launch_ff_fwd(b1, b2, s); });
   }
 };
 
@@ -627,26 +643,19 @@ int rtb_forward(Run& r, RTB& m, const float* xa, int ca, const float* xb, int cb
                 int t) {
   ramp_ctx* c = r.c; const int R = r.R, M = R * m.L;
   const float* tbias = c->time_table + (size_t)t * c->tt_stride + m.tb_off;
+  GnArgs g; g.x = m.a_c1; g.gamma = m.g1; g.beta = m.b1; g.tbias = tbias; g.resid = nullptr; g.y = m.a_h;
+  g.stats = m.a_st1; g.R = R; g.L = m.L; g.C = m.cout; g.eps = 1e-5f; g.mish = 1;
   const float* resid;
-  bool fused1 = false;
+  bool gn_due = true;
   if (m.first) {
     LAUNCH(c, r.s, CAT_SMALLCONV, 0, launch_conv_in_fwd(x_first, m.w5in, m.c1.bias, m.w1in, m.res_bias, m.a_c1, c->t_res, R, n_rp, m.L, m.cin, r.s, m.cout));
     resid = c->t_res;
   } else {
     GemmArgs a = conv5(xa, ca, m.c1.fwd, m.c1.bias, m.a_c1, m.cout, M, m.cout, m.cin, m.L, false);
     if (xb) { a.A2 = xb; a.lda2 = cb; a.K1 = ca; }
-    fused1 = r.use_tkw(a, false, true);
-    if (fused1) {      // conv -> (stash c1, statistics) -> GroupNorm -> Mish -> + time bias = h, one launch (tkw.hip)
-      Run::GnEpi e{m.a_c1, m.a_st1, m.g1, m.b1, tbias, 1e-5f};
-      a.C = m.a_h;
-      CK(r.tkw(a, nullptr, &e));
-    } else if (const ramp_ctx::TkcW* w = r.tkc_gn_planes(a, true)) {      // the same on the narrow levels (tkc.hip)
-      Run::GnEpi e{m.a_c1, m.a_st1, m.g1, m.b1, tbias, 1e-5f};
-      a.C = m.a_h; a.ldc = m.cout;
-      CK(r.tkc(a, *w, nullptr, &e));
-      fused1 = true;
-    } else
-    CK(r.gemm(a));
+    // conv -> (stash c1, statistics) -> GroupNorm -> Mish -> + time bias = h: one launch where tkw / tkc take it; else the GroupNorm follows
+    // the residual product below
+    CK(r.conv_gn(a, g, &gn_due));
     if (m.has_res) {
       GemmArgs b = lin(xa, ca, m.res_f, m.res_bias, c->t_res, m.cout, M, m.cout, m.cin);
       if (xb) { b.A2 = xb; b.lda2 = cb; b.K1 = ca; }
@@ -656,23 +665,11 @@ int rtb_forward(Run& r, RTB& m, const float* xa, int ca, const float* xb, int cb
       resid = xa;
     }
   }
-  GnArgs g; g.x = m.a_c1; g.gamma = m.g1; g.beta = m.b1; g.tbias = tbias; g.resid = nullptr; g.y = m.a_h;
-  g.stats = m.a_st1; g.R = R; g.L = m.L; g.C = m.cout; g.eps = 1e-5f; g.mish = 1;
-  if (!fused1) LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_fwd(g, r.s));
+  if (gn_due) LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_fwd(g, r.s));
+  // conv -> (stash c2, statistics) -> GroupNorm -> Mish -> + residual = the block's output
   GemmArgs c2a = conv5(m.a_h, m.cout, m.c2.fwd, m.c2.bias, m.a_c2, m.cout, M, m.cout, m.cout, m.L, false);
-  if (r.use_tkw(c2a, false, true)) {      // conv -> (stash c2, statistics) -> GroupNorm -> Mish -> + residual = the block's output
-    Run::GnEpi e{m.a_c2, m.a_st2, m.g2, m.b2, nullptr, 1e-5f};
-    c2a.C = m.a_out; c2a.resid = resid; c2a.ldr = m.cout;
-    CK(r.tkw(c2a, nullptr, &e));
-  } else if (const ramp_ctx::TkcW* w = r.tkc_gn_planes(c2a, true)) {
-    Run::GnEpi e{m.a_c2, m.a_st2, m.g2, m.b2, nullptr, 1e-5f};
-    c2a.C = m.a_out; c2a.resid = resid; c2a.ldr = m.cout;
-    CK(r.tkc(c2a, *w, nullptr, &e));
-  } else {
-  CK(r.gemm(c2a));
   g.x = m.a_c2; g.gamma = m.g2; g.beta = m.b2; g.tbias = nullptr; g.resid = resid; g.y = m.a_out; g.stats = m.a_st2;
-  LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_fwd(g, r.s));
-  }
+  CK(r.conv_gn(c2a, g));
   CK(dbg_store(c, "out/" + m.name, m.a_out, (size_t)M * m.cout, r.s));
   return 0;
 }
@@ -684,19 +681,8 @@ int rtb_backward(Run& r, RTB& m, const float* dy, float* dxa, int ca, float* dxb
   CK(dbg_store(c, "gout/" + m.name, dy, (size_t)M * m.cout, r.s));
   GnBwdArgs g; g.dy = dy; g.x = m.a_c2; g.stats = m.a_st2; g.gamma = m.g2; g.beta = m.b2; g.add = nullptr;
   g.dx = c->g_t1; g.R = R; g.L = m.L; g.C = m.cout; g.mish = 1;
-  GemmArgs c2b = conv5(c->g_t1, m.cout, m.c2.bwd, nullptr, c->g_t2, m.cout, M, m.cout, m.cout, m.L, true);
-  if (r.use_tkw(c2b, true, false)) {      // dh = conv2^T(GNbwd(dy mish'; c2)): the GroupNorm backward is the operand staging of the convolution (tkw.hip)
-    Run::GnPro p{m.a_c2, m.a_st2, m.g2, m.b2};
-    c2b.A = dy; c2b.lda = m.cout;
-    CK(r.tkw(c2b, &p, nullptr));
-  } else if (const ramp_ctx::TkcW* w = r.tkc_gn_planes(c2b, false)) {
-    Run::GnPro p{m.a_c2, m.a_st2, m.g2, m.b2};
-    c2b.A = dy; c2b.lda = m.cout;
-    CK(r.tkc(c2b, *w, &p, nullptr));
-  } else {
-  LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_bwd(g, r.s));                                                     // dc2
-  CK(r.gemm(c2b));                                                                                       // dh
-  }
+  // dh = conv2^T(dc2), dc2 = GNbwd(dy mish'; c2)
+  CK(r.gn_conv_bwd(g, conv5(c->g_t1, m.cout, m.c2.bwd, nullptr, c->g_t2, m.cout, M, m.cout, m.cout, m.L, true)));
   g.dy = c->g_t2; g.x = m.a_c1; g.stats = m.a_st1; g.gamma = m.g1; g.beta = m.b1; g.dx = c->g_t1;
   if (m.first) {
     LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_bwd(g, r.s));                                                   // dc1
@@ -710,24 +696,12 @@ int rtb_backward(Run& r, RTB& m, const float* dy, float* dxa, int ca, float* dxb
   } else {
     resid = dy; ldr = m.cout;
   }
+  // dx = conv1^T(dc1) + residual path (+ skip gradient), dc1 = GNbwd(dh mish'; c1)
   GemmArgs a = conv5(c->g_t1, m.cout, m.c1.bwd, nullptr, dxa, ca, M, m.cin, m.cout, m.L, true);
   a.resid = resid; a.ldr = ldr;
   if (dxb) { a.C2 = dxb; a.ldc2 = cb; a.N1 = ca; }
   if (add2) { RAMP_REQUIRE(dxb == nullptr, "add2 with split output"); a.resid2 = add2; a.ldr2 = ca; }
-  if (r.use_tkw(a, true, false)) {        // dx = conv1^T(GNbwd(dh mish'; c1)) + residual path (+ skip gradient), one launch
-    Run::GnPro p{m.a_c1, m.a_st1, m.g1, m.b1};
-    a.A = c->g_t2; a.lda = m.cout;
-    CK(r.tkw(a, &p, nullptr));
-    return 0;
-  }
-  if (const ramp_ctx::TkcW* w = r.tkc_gn_planes(a, false)) {
-    Run::GnPro p{m.a_c1, m.a_st1, m.g1, m.b1};
-    a.A = c->g_t2; a.lda = m.cout;
-    return r.tkc(a, *w, &p, nullptr);
-  }
-  LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_bwd(g, r.s));                                                     // dc1
-  CK(r.gemm(a));
-  return 0;
+  return r.gn_conv_bwd(g, a);
 }
 
 // ---- SpatialTransformer ------------------------------------------------------------------------
@@ -760,11 +734,11 @@ int st_forward(Run& r, ST& m, const float* x, int share = 1) {
     if (r.use_ato(k, Mb, m.L)) {      // softmax(q k^T / 8) v -> out-projection + bias + constant + residual: o never reaches HBM
       CK(r.ato(k, k.a_qkv, zin, pre ? c->t_ln : k.a_z1, Mb, m.L, pre ? nullptr : rowbias, rb_stride));
     } else {
-    LAUNCH(c, r.s, CAT_ATTN, 16.0 * Rb * m.L * m.L * 64, launch_attn_fwd(k.a_qkv, c->t_o, Rb, m.L, r.s));
-    GemmArgs a = lin(c->t_o, D, k.wo_f, k.bo, pre ? c->t_ln : k.a_z1, D, Mb, D, D);
-    a.resid = zin; a.ldr = D; a.L = m.L;
-    if (!pre) { a.rowbias = rowbias; a.rb_stride = rb_stride; a.rowvar = c->row_variant; a.row0 = r.row0; }
-    if (r.use_tkl(a)) CK(r.tkl(a, nullptr, nullptr)); else CK(r.gemm(a));
+      LAUNCH(c, r.s, CAT_ATTN, 16.0 * Rb * m.L * m.L * 64, launch_attn_fwd(k.a_qkv, c->t_o, Rb, m.L, r.s));
+      GemmArgs a = lin(c->t_o, D, k.wo_f, k.bo, pre ? c->t_ln : k.a_z1, D, Mb, D, D);
+      a.resid = zin; a.ldr = D; a.L = m.L;
+      if (!pre) { a.rowbias = rowbias; a.rb_stride = rb_stride; a.rowvar = c->row_variant; a.row0 = r.row0; }
+      CK(r.linear(a));
     }
     if (pre) LAUNCH(c, r.s, CAT_ROW, 0, launch_expand_rows(c->t_ln, k.a_z1, R, share, m.L, D, rowbias, rb_stride, c->row_variant, r.row0, r.s));
     if (r.use_ffx(k, M)) {      // LN3 -> FF1 -> GEGLU -> FF2 -> + z1 in one launch, nothing but the stash and z2 written
@@ -806,20 +780,20 @@ int st_backward(Run& r, ST& m, const float* x, const float* dy, float* dx, int s
     if (r.use_ffx(k, M)) {      // dz1 = dz + LN3bwd(W1^T (d(hg) (.) stash)), d(hg) = W2^T dz: one launch
       CK(r.ffx(k, true, dz, k.a_z1, dz1, M));
     } else {
-    if (c->gemm_mode >= 1 && c->x6_pipe) {
-      // d(hg) only (1024 wide); d(ag) = [d(hg) s1 | d(hg) s2] is formed by the next GEMM's operand loader from the
-      // forward stash: the 2048-wide d(ag) never goes to HBM (saves a 2048-float write and a 2048-float read per token)
-      CK(r.gemm(lin(dz, D, k.w2_b, nullptr, c->t_hg, 1024, M, 1024, D)));
-      GemmArgs v = lin(c->t_hg, 1024, k.w1_b, nullptr, c->t_dln, D, M, D, 2048);         // d(ln3)
-      v.Amul = k.a_ag; v.lda_mul = 2048; v.a_period = 1024;
-      CK(r.gemm(v));
-    } else {
-      GemmArgs w = lin(dz, D, k.w2_b, nullptr, c->t_dag, 2048, M, 1024, D);   // d(hg) -> d(ag) in the epilogue
-      w.epi = EPI_GEGLU_BWD; w.aux_in = k.a_ag; w.ld_aux = 2048;
-      CK(r.gemm(w));
-      CK(r.gemm(lin(c->t_dag, 2048, k.w1_b, nullptr, c->t_dln, D, M, D, 2048)));        // d(ln3)
-    }
-    LAUNCH(c, r.s, CAT_ROW, 0, launch_ln_bwd(c->t_dln, k.a_z1, k.ln3_g, dz, dz1, M, r.s));         // dz1
+      if (c->gemm_mode >= 1 && c->x6_pipe) {
+        // d(hg) only (1024 wide); d(ag) = [d(hg) s1 | d(hg) s2] is formed by the next GEMM's operand loader from the
+        // forward stash: the 2048-wide d(ag) never goes to HBM (saves a 2048-float write and a 2048-float read per token)
+        CK(r.gemm(lin(dz, D, k.w2_b, nullptr, c->t_hg, 1024, M, 1024, D)));
+        GemmArgs v = lin(c->t_hg, 1024, k.w1_b, nullptr, c->t_dln, D, M, D, 2048);         // d(ln3)
+        v.Amul = k.a_ag; v.lda_mul = 2048; v.a_period = 1024;
+        CK(r.gemm(v));
+      } else {
+        GemmArgs w = lin(dz, D, k.w2_b, nullptr, c->t_dag, 2048, M, 1024, D);   // d(hg) -> d(ag) in the epilogue
+        w.epi = EPI_GEGLU_BWD; w.aux_in = k.a_ag; w.ld_aux = 2048;
+        CK(r.gemm(w));
+        CK(r.gemm(lin(c->t_dag, 2048, k.w1_b, nullptr, c->t_dln, D, M, D, 2048)));        // d(ln3)
+      }
+      LAUNCH(c, r.s, CAT_ROW, 0, launch_ln_bwd(c->t_dln, k.a_z1, k.ln3_g, dz, dz1, M, r.s));         // dz1
     }
     const bool pre = share > 1 && b == 0;
     const int Rb = pre ? Rp : R, Mb = Rb * m.L;
@@ -827,24 +801,22 @@ int st_backward(Run& r, ST& m, const float* x, const float* dy, float* dx, int s
       LAUNCH(c, r.s, CAT_ROW, 0, launch_combine_rows(dz1, dz, Rp, share, m.L, D, comb, r.s));
       std::swap(dz, dz1);
     }
-    {
-      GemmArgs o = lin(dz1, D, k.wo_b, nullptr, c->t_o, D, Mb, D, D);                   // d(o)
-      if (r.use_tkl(o)) CK(r.tkl(o, nullptr, nullptr)); else CK(r.gemm(o));
-    }
+    CK(r.linear(lin(dz1, D, k.wo_b, nullptr, c->t_o, D, Mb, D, D)));                    // d(o)
     if (r.use_abl(k, Mb, m.L)) {   // d(q, k, v), d(ln1) and the LayerNorm-1 backward in ONE launch: dz = dz1 + LN1bwd(attention-backward(d(o)) Wqkv^T)
       CK(r.abl(k, k.a_qkv, c->t_o, zin, dz1, dz, Mb, m.L));
     } else {
-    if (r.use_atb(Mb, m.L)) {      // d(q, k, v) on sample-owning waves (atk.hip, atb_kernel): fp16x3 MFMAs, no LDS tile, two waves per SIMD
-      AtbArgs t; t.M = Mb; t.L = m.L; t.QKV = k.a_qkv; t.dO = c->t_o; t.dQKV = c->t_dqkv;
-      LAUNCH(c, r.s, CAT_ATTN, 32.0 * Rb * m.L * m.L * 64, launch_atb(t, r.s));
-    } else
-    LAUNCH(c, r.s, CAT_ATTN, 32.0 * Rb * m.L * m.L * 64, launch_attn_bwd(k.a_qkv, c->t_o, c->t_dqkv, Rb, m.L, r.s));
-    if (r.use_tklb(Mb, k.wqkv_b)) {      // d(ln1) and the LayerNorm-1 backward in one token-owning launch: dz = dz1 + LN1bwd(d(qkv) Wqkv^T)
-      CK(r.tklb(c->t_dqkv, k.wqkv_b, zin, k.ln1_g, dz1, dz, Mb));
-    } else {
-      CK(r.gemm(lin(c->t_dqkv, 768, k.wqkv_b, nullptr, c->t_dln, D, Mb, D, 768)));        // d(ln1)
-      LAUNCH(c, r.s, CAT_ROW, 0, launch_ln_bwd(c->t_dln, zin, k.ln1_g, dz1, dz, Mb, r.s));           // dz (block input)
-    }
+      if (r.use_atb(Mb, m.L)) {      // d(q, k, v) on sample-owning waves (atk.hip, atb_kernel): fp16x3 MFMAs, no LDS tile, two waves per SIMD
+        AtbArgs t; t.M = Mb; t.L = m.L; t.QKV = k.a_qkv; t.dO = c->t_o; t.dQKV = c->t_dqkv;
+        LAUNCH(c, r.s, CAT_ATTN, 32.0 * Rb * m.L * m.L * 64, launch_atb(t, r.s));
+      } else {
+        LAUNCH(c, r.s, CAT_ATTN, 32.0 * Rb * m.L * m.L * 64, launch_attn_bwd(k.a_qkv, c->t_o, c->t_dqkv, Rb, m.L, r.s));
+      }
+      if (r.use_tklb(Mb, k.wqkv_b)) {      // d(ln1) and the LayerNorm-1 backward in one token-owning launch: dz = dz1 + LN1bwd(d(qkv) Wqkv^T)
+        CK(r.tklb(c->t_dqkv, k.wqkv_b, zin, k.ln1_g, dz1, dz, Mb));
+      } else {
+        CK(r.gemm(lin(c->t_dqkv, 768, k.wqkv_b, nullptr, c->t_dln, D, Mb, D, 768)));        // d(ln1)
+        LAUNCH(c, r.s, CAT_ROW, 0, launch_ln_bwd(c->t_dln, zin, k.ln1_g, dz1, dz, Mb, r.s));           // dz (block input)
+      }
     }
   }
   CK(r.gemm(lin(dz, D, m.wpi_b, nullptr, c->t_xn, m.C, Mp, m.C, D)));                   // d(xn)
@@ -908,17 +880,11 @@ int net_forward(ramp_ctx* c, const float* x_chunk, int row0, int R, int n_rp, in
     cur = u.a_y; cc = u.C;
   }
   const int H = c->cfg.horizon, C0 = c->cfg.unet_input_dim, M = R * H;
-  GemmArgs fa = conv5(cur, cc, c->final_conv.fwd, c->final_conv.bias, c->a_fin_c, C0, M, C0, C0, H, false);
-  if (const ramp_ctx::TkcW* w = r.tkc_gn_planes(fa, true)) {
-    Run::GnEpi e{c->a_fin_c, c->a_fin_st, c->fin_g, c->fin_b, nullptr, 1e-5f};
-    fa.C = c->a_fin_a; fa.ldc = C0;
-    CK(r.tkc(fa, *w, nullptr, &e));
-  } else {
-  CK(r.gemm(fa));
+  // the final Conv1dBlock.  (Through the common helper although only tkc ever took it: tkw's rule wants C_out in {128, 256, 512, 1024}
+  // -- tw_geometry, tkw.hip -- and this convolution has unet_input_dim in {16, 32, 64} channels, so use_tkw is false here.)
   GnArgs g; g.x = c->a_fin_c; g.gamma = c->fin_g; g.beta = c->fin_b; g.y = c->a_fin_a; g.stats = c->a_fin_st;
   g.R = R; g.L = H; g.C = C0; g.eps = 1e-5f; g.mish = 1;
-  LAUNCH(c, s, CAT_ROW, 0, launch_gn_fwd(g, s));
-  }
+  CK(r.conv_gn(conv5(cur, cc, c->final_conv.fwd, c->final_conv.bias, c->a_fin_c, C0, M, C0, C0, H, false), g));
   LAUNCH(c, s, CAT_SMALLCONV, 0, launch_conv_out(c->a_fin_a, c->fin_w, c->fin_bias, f_out, want_grad ? c->a_fin_da : nullptr, M, c->cfg.state_dim, s, C0));
   return 0;
 }
@@ -931,15 +897,7 @@ int net_backward(ramp_ctx* c, int row0, int R, float* eps_out, hipStream_t s, in
   GnBwdArgs g; g.dy = c->a_fin_da; g.x = c->a_fin_c; g.stats = c->a_fin_st; g.gamma = c->fin_g; g.beta = c->fin_b;
   g.dx = c->g_t1; g.R = R; g.L = H; g.C = C0; g.mish = 1;
   float* d = c->g_a; float* e = c->g_b;
-  GemmArgs fb = conv5(c->g_t1, C0, c->final_conv.bwd, nullptr, d, C0, M, C0, C0, H, true);
-  if (const ramp_ctx::TkcW* w = r.tkc_gn_planes(fb, false)) {
-    Run::GnPro p{c->a_fin_c, c->a_fin_st, c->fin_g, c->fin_b};
-    fb.A = c->a_fin_da; fb.lda = C0;
-    CK(r.tkc(fb, *w, &p, nullptr));
-  } else {
-  LAUNCH(c, s, CAT_ROW, 0, launch_gn_bwd(g, s));
-  CK(r.gemm(fb));
-  }
+  CK(r.gn_conv_bwd(g, conv5(c->g_t1, C0, c->final_conv.bwd, nullptr, d, C0, M, C0, C0, H, true)));      // (tkc or the pair, as in net_forward)
   for (int k = nl - 2; k >= 0; --k) {
     RTB& a = c->rtbs[2 * nl + 2 + 2 * k]; RTB& b = c->rtbs[2 * nl + 3 + 2 * k]; ST& st = c->sts[nl + 1 + k];
     Resample& u = c->ups[k];

@@ -159,32 +159,96 @@ DISPATCH = {   # H: (ato, abl, tkc, tkw, tklb)
 }
 
 
-@pytest.mark.parametrize("tag,S,H,o3", HORIZON_CASES)
-def test_fused_plan_dispatches_what_the_predicates_admit(tag, S, H, o3):
-    """The bench's launch plan on one eager fp16x3 evaluation (after its calibration): the profiled kernel slots that are
-    non-zero are exactly the ones the predicates admit at this horizon (DISPATCH), so the fixture parity in fp16x3-tkw mode
-    really exercised the sample-owning kernels where they apply, and the fallback path where they do not."""
+# The exact launches of that evaluation per horizon: the nine counts of ramp_profile_read_kernels (slot 8: every other launch of the GEMM
+# class) and ramp_launch_count.  Integers decided on the host by the routing predicates of engine.hip (struct Run), read off the commit before
+# the routing refactor on an MI355X: a change of either is a change of routing, and of the call-site numbering the delayed scaling rests on.
+DISPATCH_COUNTS = {   # H: ((ffx_fwd, ffx_bwd, tkl, tklb, ato, abl, tkc, tkw, other), launch_count)
+    8: ((16, 16, 32, 0, 16, 16, 8, 0, 118), 299),
+    16: ((16, 16, 32, 0, 16, 16, 22, 9, 95), 276),
+    24: ((16, 16, 32, 0, 16, 16, 22, 19, 85), 266),
+    32: ((16, 16, 32, 0, 16, 16, 28, 32, 66), 247),
+    56: ((16, 16, 48, 16, 0, 0, 0, 0, 126), 339),
+    64: ((16, 16, 34, 2, 14, 14, 28, 33, 65), 250),
+}
+
+
+def _profiled_eval(m, x, t, pts):
+    """One eager evaluation under the per-launch profiler: (eps, the nine launch counts of ramp_profile_read_kernels, launch_count())."""
     import ctypes as C
     from ramp_amd import _lib
-    g = np.load(f"{GOLDEN}/unet{tag}.npz")
-    m = build_unet(S, H, o3, max_rows=8, gemm_mode="fp16x3", launch_plan=util.PLANS["tkw"])
-    N = g["x"].shape[0]
-    x = dev(g["x"]); t = torch.from_numpy(g["t"]).cuda()
-    pts = dev(g["cloud"])[None].repeat(N, 1, 1, 1)
-    m(x, t, None, obstacle_pts=pts); m(x, t, None, obstacle_pts=pts)      # forward and input-gradient call sites calibrated
     lib = _lib.load()
     _lib.check(lib.ramp_profile(m.ctx(), 1))
     eps = m(x, t, None, obstacle_pts=pts).cpu().numpy()
     ms = (C.c_double * 9)(); fl = (C.c_double * 9)(); cnt = (C.c_int64 * 9)()
     _lib.check(lib.ramp_profile_read_kernels(m.ctx(), 9, ms, fl, cnt))
     _lib.check(lib.ramp_profile(m.ctx(), 0))
+    return eps, tuple(cnt), m.launch_count()
+
+
+@pytest.mark.parametrize("tag,S,H,o3", HORIZON_CASES)
+def test_fused_plan_dispatches_what_the_predicates_admit(tag, S, H, o3):
+    """The bench's launch plan on one eager fp16x3 evaluation (after its calibration): the profiled kernel slots that are
+    non-zero are exactly the ones the predicates admit at this horizon (DISPATCH), so the fixture parity in fp16x3-tkw mode
+    really exercised the sample-owning kernels where they apply, and the fallback path where they do not; and the launches
+    are exactly the recorded ones (DISPATCH_COUNTS)."""
+    g = np.load(f"{GOLDEN}/unet{tag}.npz")
+    m = build_unet(S, H, o3, max_rows=8, gemm_mode="fp16x3", launch_plan=util.PLANS["tkw"])
+    N = g["x"].shape[0]
+    x = dev(g["x"]); t = torch.from_numpy(g["t"]).cuda()
+    pts = dev(g["cloud"])[None].repeat(N, 1, 1, 1)
+    m(x, t, None, obstacle_pts=pts); m(x, t, None, obstacle_pts=pts)      # forward and input-gradient call sites calibrated
+    eps, counts, launches = _profiled_eval(m, x, t, pts)
     assert m.score_mode() == "fp16x3"
-    counts = list(cnt)
-    print(f"{tag}: kernel launches ffx_fwd ffx_bwd tkl tklb ato abl tkc tkw other = {counts}")
+    print(f"{tag}: kernel launches ffx_fwd ffx_bwd tkl tklb ato abl tkc tkw other = {counts}, launch_count {launches}")
     assert counts[0] > 0 and counts[1] > 0 and counts[2] > 0, counts
     want = dict(zip(("ato", "abl", "tkc", "tkw", "tklb"), DISPATCH[H]))
     got = dict(ato=counts[4] > 0, abl=counts[5] > 0, tkc=counts[6] > 0, tkw=counts[7] > 0, tklb=counts[3] > 0)
     assert got == want, (H, counts)
+    assert (counts, launches) == DISPATCH_COUNTS[H], (H, counts, launches)
+    assert rel(eps, g["eps"]) < 5e-5
+
+
+# The same pair for every launch plan of util.PLANS, bf16x6 and fp32 on the 2d_h48 fixture: of the third evaluation (fp16x3 modes: the
+# steady one) and, in the fp16x3 modes, of the first -- the calibration evaluation, on the bf16x6 kernels except for the narrow k = 5
+# convolutions, which tkc.hip takes there too so that the call sites number alike.  Recorded like DISPATCH_COUNTS.
+ROUTING_MODES = [f"fp16x3-{k}" if k else "fp16x3" for k in util.PLANS] + ["bf16x6", "fp32"]
+ROUTING_COUNTS = {   # mode: (third evaluation, first evaluation or None), each ((nine counts), launch_count)
+    "fp16x3": (((0, 0, 0, 0, 0, 0, 0, 0, 254), 435), ((0, 0, 0, 0, 0, 0, 0, 0, 254), 435)),
+    "fp16x3-fusedff": (((0, 0, 0, 0, 0, 0, 0, 0, 238), 419), ((0, 0, 0, 0, 0, 0, 0, 0, 254), 435)),
+    "fp16x3-ffx": (((16, 16, 0, 0, 0, 0, 0, 0, 190), 371), ((0, 0, 0, 0, 0, 0, 0, 0, 254), 435)),
+    "fp16x3-tok": (((16, 16, 48, 16, 0, 0, 0, 0, 126), 339), ((0, 0, 0, 0, 0, 0, 0, 0, 254), 435)),
+    "fp16x3-atk": (((16, 16, 32, 0, 16, 16, 0, 0, 126), 307), ((0, 0, 0, 0, 0, 0, 0, 0, 254), 435)),
+    "fp16x3-tkc": (((16, 16, 32, 0, 16, 16, 28, 0, 98), 279), ((0, 0, 0, 0, 0, 0, 28, 0, 226), 407)),
+    "fp16x3-tkw": (((16, 16, 32, 0, 16, 16, 28, 33, 65), 246), ((0, 0, 0, 0, 0, 0, 28, 0, 226), 407)),
+    "fp16x3-m32": (((16, 16, 32, 0, 16, 16, 28, 33, 65), 246), ((0, 0, 0, 0, 0, 0, 28, 0, 226), 407)),
+    "bf16x6": (((0, 0, 0, 0, 0, 0, 0, 0, 254), 435), None),
+    "fp32": (((0, 0, 0, 0, 0, 0, 0, 0, 254), 435), None),
+}
+
+
+@pytest.mark.parametrize("mode", ROUTING_MODES)
+def test_routing_of_every_launch_plan_and_phase(mode):
+    """Which kernel serves each product of a score evaluation -- and with it the order in which GEMM call sites are taken -- is pinned
+    for every launch plan in every phase it reaches: the launches of the calibration evaluation (fp16x3 modes) and of the third one
+    equal the recorded ones (ROUTING_COUNTS)."""
+    g = np.load(f"{GOLDEN}/unet2d_h48.npz")
+    base, _, plan = mode.partition("-")
+    m = build_unet(4, 48, False, max_rows=8, gemm_mode=base, launch_plan=util.PLANS[plan] if base == "fp16x3" else None)
+    N = g["x"].shape[0]
+    x = dev(g["x"]); t = torch.from_numpy(g["t"]).cuda()
+    pts = dev(g["cloud"])[None].repeat(N, 1, 1, 1)
+    m.prepare_time_table(int(g["t"][0]) + 1); m.cache_scene_encoding(pts)      # (the scene encoder's launches stay out of the first profile)
+    first = None
+    if base == "fp16x3":
+        first = _profiled_eval(m, x, t, pts)[1:]
+        assert m.score_mode() == "bf16x6"                      # calibration evaluation
+    else:
+        m(x, t, None, obstacle_pts=pts)
+    m(x, t, None, obstacle_pts=pts)
+    eps, counts, launches = _profiled_eval(m, x, t, pts)
+    assert m.score_mode() == base
+    print(f"{mode}: third evaluation {counts} launch_count {launches}; first {first}")
+    assert ((counts, launches), first) == ROUTING_COUNTS[mode], (mode, counts, launches, first)
     assert rel(eps, g["eps"]) < 5e-5
 
 
