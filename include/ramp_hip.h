@@ -335,6 +335,44 @@ int ramp_traj_metrics(const float* traj, int32_t B, int32_t H, int32_t S, const 
 /* Metrics.compute_variance_waypoints (metrics.py:8-19): sum over waypoints of the unbiased variance of all B*B entries
  * of triu(cdist(p, p), 1).  scratch: device, 2 * H * ceil(B/256) doubles; out: device, 1 double. */
 int ramp_waypoint_variance(const float* traj, int32_t B, int32_t H, int32_t S, double* scratch, double* out, void* stream);
+
+/* ---- evaluation and selection of a many-scene batch (what ramp_sample_scenes returns), per scene, in a fixed number of launches ----
+ * Layout: a scene's trajectories are adjacent, scenes in order.  Every table is a DEVICE int32 array of n_scenes + 1 entries:
+ * traj_first ([0] = 0, [n_scenes] = B, strictly increasing) the first row of each scene; box_offset / cloud_offset the first box /
+ * point of each scene in the boxes / cost clouds concatenated over the scenes (box_offset may repeat a value: a scene without
+ * boxes has intensity 0; cloud_offset is strictly increasing).  n_boxes_total / n_points_total: entries of the concatenated arrays;
+ * a span is clamped to them.  Nothing here copies or synchronises: asynchronous on `stream`, capturable.  No float atomics, every
+ * sum in an order fixed by the scene's own rows: a scene's results do not depend on the rest of the batch. */
+/* ramp_traj_metrics with each trajectory testing the boxes of its own scene (the loop over experiments around
+ * Metrics.compute_collision_intensity, scripts/inference/inference_static.py:113-190 + core/metrics.py:21-81): a scene's rows are bit
+ * for bit what ramp_traj_metrics gives for that slice and that scene's boxes. */
+int ramp_traj_metrics_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                             const float* box_centers, const float* box_sizes, const int32_t* box_offset, int32_t n_boxes_total,
+                             float* intensity, float* path_len, float* smooth, void* stream);
+/* Metrics.trajectory_success_and_metrics (core/metrics.py:83-126) per scene, free = intensity <= threshold, without compacting the
+ * free rows: summary device (n_scenes, 6) doubles = {n_traj, n_free, mean intensity over all rows, mean path length over the free
+ * rows, their unbiased std, waypoint variance (compute_variance_waypoints, metrics.py:8-19) of the free rows}; n_free == 0: the last
+ * three are NaN; n_free == 1: std NaN, variance 0.  free_mask: device (B) int32.  intensity / path_len: device (B), e.g. from
+ * ramp_traj_metrics_scenes.  H <= 65535.
+ * scratch: device, 2 * H * W + n_scenes + 1 doubles with W = ceil(B / 256) + n_scenes (pair sums of every 256-row tile of every
+ * scene per waypoint, then the scenes' tile table). */
+int ramp_scene_summary(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                       const float* intensity, const float* path_len, float threshold, double* scratch, double* summary,
+                       int32_t* free_mask, void* stream);
+/* ramp_traj_costs with each trajectory reading its own scene's span of the concatenated cost cloud (cost.py:3-54 inside the loop
+ * over experiments): bit for bit ramp_traj_costs with that scene's cloud.  H within the cost kernel's limit (128). */
+int ramp_traj_costs_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                           const float* cloud, const int32_t* cloud_offset, int32_t n_points_total, float threshold, int32_t* mask,
+                           float* path_len, float* smooth, void* stream);
+/* ramp_select_best per scene (compute_trajectory_costs, cost.py:56-88, once per experiment): min-max normalisation over the scene's
+ * collision-free rows, w_smooth * smooth + w_len * length, first minimum.  result_dev device (n_scenes, 4) int32 = {n_free, rank of
+ * the winner among the scene's free rows, its row in the whole batch, 0}; best_out device (n_scenes, H, S): the winner, unmodified
+ * (the x[0, 2:] = 0 of the dynamic planner is not part of the static flow).  A scene without a free row: {0, -1, -1, 0} and a NaN
+ * block. */
+int ramp_select_best_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                            const float* cloud, const int32_t* cloud_offset, int32_t n_points_total, float threshold, float w_smooth,
+                            float w_len, int32_t* mask, float* path_len, float* smooth, float* best_out, int32_t* result_dev,
+                            void* stream);
 /* one p_mean_variance evaluation given eps (diffusion_model_static.py:161-172); predict_x0 != 0: predict_epsilon=False,
  * x0 = the combined network output (diffusion_model_static.py:109-118) */
 int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, double w0, double w1,

@@ -4,7 +4,10 @@ from __future__ import annotations
 
 import torch
 
+import numpy as np
+
 from . import _lib
+from .scenes import build_eval_tables, scene_counts
 
 
 def _costs(trajs, obstacle_points, thr):
@@ -52,3 +55,42 @@ def compute_trajectory_costs(trajs, obstacle_points, smoothness_weight=.1, path_
     total = smoothness_weight * sm + path_length_weight * pl
     best = torch.argmin(total)
     return trajs[free][best], total[best], total, free, best
+
+
+def compute_trajectory_costs_scenes(trajs, counts_or_traj_scene, clouds, smoothness_weight=.1, path_length_weight=.9,
+                                    collision_threshold=0.0):
+    """``compute_trajectory_costs`` (cost.py:56-88, normalize=True) for every scene of a many-scene batch at once
+    (ramp_select_best_scenes: two launches whatever the number of scenes): scene i's trajectories are scored against
+    ``clouds[i]`` alone ((..., 2) points, 2-D like cost.py).
+
+    Returns device tensors, without a host sync: ``best`` (n_scenes, H, S) the winner of each scene (NaN where no trajectory is
+    collision-free), ``n_free`` (n_scenes) int32, ``best_index`` (n_scenes) the winner's index among the scene's collision-free
+    trajectories (what the reference's argmin returns; -1 for none), ``best_row`` (n_scenes) its row in the batch (-1 for none) and
+    the (B) bool ``collision_free_mask``."""
+    if trajs.device.type != "cuda":
+        raise _lib.RampHipError("trajectory costs: tensors must live on a HIP device (no CPU path)")
+    t = trajs.detach().to(torch.float32).contiguous()
+    B, H, S = t.shape
+    n_scenes = len(clouds)
+    pts = []
+    for i, c in enumerate(clouds):
+        c = torch.as_tensor(c)
+        if c.dim() < 1 or c.shape[-1] != 2:
+            raise ValueError(f"scene {i}: cost clouds are 2-D point sets (..., 2); got shape {tuple(c.shape)}")
+        pts.append(c.detach().reshape(-1, 2).to(torch.float32))
+    counts = scene_counts(counts_or_traj_scene, n_scenes, B)
+    tab = build_eval_tables(counts, cloud_sizes=[p.shape[0] for p in pts])
+    dev = t.device
+    cloud = torch.cat([p.to(dev) for p in pts]).contiguous()
+    tables = torch.from_numpy(np.concatenate([tab["traj_first"], tab["cloud_offset"]])).to(dev)
+    mask = torch.empty(B, dtype=torch.int32, device=dev)
+    plen = torch.empty(B, device=dev)
+    smooth = torch.empty(B, device=dev)
+    best = torch.empty(n_scenes, H, S, device=dev)
+    res = torch.empty(n_scenes, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_select_best_scenes(
+            _lib.ptr(t), B, H, S, tables.data_ptr(), n_scenes, _lib.ptr(cloud), tables[n_scenes + 1:].data_ptr(), cloud.shape[0],
+            float(collision_threshold), float(smoothness_weight), float(path_length_weight), _lib.ptr(mask), _lib.ptr(plen),
+            _lib.ptr(smooth), _lib.ptr(best), _lib.ptr(res), _lib.current_stream()), "ramp_select_best_scenes")
+    return best, res[:, 0], res[:, 1], res[:, 2], ~mask.bool()

@@ -67,11 +67,26 @@ int launch_replan_near(const float* x, const ReplanState* st, float thr, int* en
 int launch_replan_goal(float* x0, const float* x, int B, int H, int S, hipStream_t s);
 int launch_replan_select(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                          float* best, int* result, int B, int H, int S, hipStream_t s);
+// one block per scene of a many-scene batch (rows [traj_first[s], traj_first[s + 1])): result (n_scenes, 4) with the row in the whole
+// batch, best (n_scenes, H, S) the winner unmodified; a scene without a free row gets {0, -1, -1, 0} and a NaN block
+int launch_select_scenes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
+                         const int* traj_first, int n_scenes, float* best, int* result, int B, int H, int S, hipStream_t s);
 // mask[b] = any_{h,p} ||xy - p|| < thr ; plen[b], smooth[b]
 int launch_traj_costs(const float* traj, const float* cloud, int B, int H, int S, int P, float thr,
                       int* mask, float* plen, float* smooth, hipStream_t s);
+// the same with row b reading only the points [cloud_off[s], cloud_off[s + 1]) of its scene s (traj_first[s] <= b < traj_first[s + 1])
+int launch_traj_costs_scenes(const float* traj, const float* cloud, const int* traj_first, const int* cloud_off, int n_scenes,
+                             int P_total, int B, int H, int S, float thr, int* mask, float* plen, float* smooth, hipStream_t s);
 int launch_traj_metrics(const float* traj, int B, int H, int S, const float* centers, const float* sizes, int n_boxes,
                         float* intensity, float* path_len, float* smooth, hipStream_t s);
 // scratch: 2 * H * ceil(B / 256) doubles; out: 1 double
 int launch_waypoint_variance(const float* traj, int B, int H, int S, double* scratch, double* out, hipStream_t s);
+// many-scene batch: row b tests the boxes [box_off[s], box_off[s + 1]) of its scene only
+int launch_traj_metrics_scenes(const float* traj, int B, int H, int S, const int* traj_first, int n_scenes, const float* centers,
+                               const float* sizes, const int* box_off, int n_boxes_total, float* intensity, float* path_len,
+                               float* smooth, hipStream_t s);
+// per-scene records of 6 doubles {n_traj, n_free, mean intensity, mean and unbiased std of the free path lengths, waypoint variance
+// of the free rows} and the (B) free mask.  scratch: 2 * H * W + n_scenes + 1 doubles, W = ceil(B / 256) + n_scenes
+int launch_scene_summary(const float* traj, int B, int H, int S, const int* traj_first, int n_scenes, const float* intensity,
+                         const float* path_len, float thr, double* scratch, double* summary, int* free_mask, hipStream_t s);
 }  // namespace ramp

@@ -173,6 +173,52 @@ int ramp_waypoint_variance(const float* traj, int32_t B, int32_t H, int32_t S, d
   return launch_waypoint_variance(traj, B, H, S, scratch, out, as_stream(stream));
 }
 
+
+// ---- a many-scene batch (ramp_sample_scenes' layout: a scene's rows adjacent, scenes in order), every table on the device ----
+#define RAMP_REQUIRE_SCENES(B, S, n_scenes) \
+  do { RAMP_REQUIRE((n_scenes) > 0, "n_scenes must be positive"); RAMP_REQUIRE((B) > 0, "empty batch (B <= 0)"); \
+       RAMP_REQUIRE((S) >= 2, "trajectories need xy states (S >= 2)"); } while (0)
+int ramp_traj_metrics_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                             const float* box_centers, const float* box_sizes, const int32_t* box_offset, int32_t n_boxes_total,
+                             float* intensity, float* path_len, float* smooth, void* stream) {
+  RAMP_REQUIRE(traj && intensity && path_len && smooth, "null argument");
+  RAMP_REQUIRE(traj_first && box_offset, "null scene table");
+  RAMP_REQUIRE(n_boxes_total == 0 || (box_centers && box_sizes), "null boxes");
+  RAMP_REQUIRE_SCENES(B, S, n_scenes);
+  return launch_traj_metrics_scenes(traj, B, H, S, traj_first, n_scenes, box_centers, box_sizes, box_offset, n_boxes_total, intensity,
+                                    path_len, smooth, as_stream(stream));
+}
+int ramp_scene_summary(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                       const float* intensity, const float* path_len, float threshold, double* scratch, double* summary,
+                       int32_t* free_mask, void* stream) {
+  RAMP_REQUIRE(traj && intensity && path_len && scratch && summary && free_mask, "null argument");
+  RAMP_REQUIRE(traj_first, "null scene table");
+  RAMP_REQUIRE_SCENES(B, S, n_scenes);
+  return launch_scene_summary(traj, B, H, S, traj_first, n_scenes, intensity, path_len, threshold, scratch, summary, free_mask,
+                              as_stream(stream));
+}
+int ramp_traj_costs_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                           const float* cloud, const int32_t* cloud_offset, int32_t n_points_total, float threshold, int32_t* mask,
+                           float* path_len, float* smooth, void* stream) {
+  RAMP_REQUIRE(traj && cloud && mask && path_len && smooth, "null argument");
+  RAMP_REQUIRE(traj_first && cloud_offset, "null scene table");
+  RAMP_REQUIRE_SCENES(B, S, n_scenes);
+  return launch_traj_costs_scenes(traj, cloud, traj_first, cloud_offset, n_scenes, n_points_total, B, H, S, threshold, mask, path_len,
+                                  smooth, as_stream(stream));
+}
+int ramp_select_best_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                            const float* cloud, const int32_t* cloud_offset, int32_t n_points_total, float threshold, float w_smooth,
+                            float w_len, int32_t* mask, float* path_len, float* smooth, float* best_out, int32_t* result_dev,
+                            void* stream) {
+  RAMP_REQUIRE(traj && cloud && mask && path_len && smooth && best_out && result_dev, "null argument");
+  RAMP_REQUIRE(traj_first && cloud_offset, "null scene table");
+  RAMP_REQUIRE_SCENES(B, S, n_scenes);
+  hipStream_t s = as_stream(stream);
+  CK(launch_traj_costs_scenes(traj, cloud, traj_first, cloud_offset, n_scenes, n_points_total, B, H, S, threshold, mask, path_len,
+                              smooth, s));
+  return launch_select_scenes(traj, mask, path_len, smooth, w_smooth, w_len, traj_first, n_scenes, best_out, result_dev, B, H, S, s);
+}
+
 int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, double w0, double w1,
                   float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, int32_t clip, int32_t predict_x0, float* x0_out,
                   float* mean_out, float* ecomb_out, void* stream) {

@@ -311,11 +311,14 @@ __global__ __launch_bounds__(256) void replan_goal_kernel(float* __restrict__ x0
 }
 // compute_trajectory_costs (cost.py:56-88) over the B per-trajectory scalars: min-max normalisation over the
 // collision-free ones, total = w_s * smooth + w_l * length, first minimum; the winner is gathered with x[0, 2:] = 0
-// (diffusion_model_dynamic.py:607).  One block.  result: {n_free, rank of the winner among the free ones, its row, 0}
-__global__ __launch_bounds__(1024) void replan_select_kernel(const float* __restrict__ traj, const int* __restrict__ mask,
-                                                              const float* __restrict__ plen, const float* __restrict__ smooth,
-                                                              float w_s, float w_l, float* __restrict__ best,
-                                                              int* __restrict__ result, int B, int H, int S) {
+// (diffusion_model_dynamic.py:607).  One block of 1024 threads over rows [0, B) of the arrays it is given.
+// result: {n_free, rank of the winner among the free ones, its row + row0, 0}.  SCENES: the static flow of a many-scene batch --
+// the winner is copied unmodified, a block with no free row gets a NaN `best` and {0, -1, -1, 0}.
+template <bool SCENES>
+__device__ __forceinline__ void select_block(const float* __restrict__ traj, const int* __restrict__ mask,
+                                             const float* __restrict__ plen, const float* __restrict__ smooth,
+                                             float w_s, float w_l, float* __restrict__ best,
+                                             int* __restrict__ result, int B, int H, int S, int row0) {
   __shared__ float r_min[2][16], r_max[2][16];
   __shared__ float r_tot[16]; __shared__ int r_idx[16], r_cnt[16];
   __shared__ float s_lo[2], s_hi[2]; __shared__ int s_best, s_free;
@@ -367,20 +370,41 @@ __global__ __launch_bounds__(1024) void replan_select_kernel(const float* __rest
   }
   __syncthreads();
   const int bb = s_best;
-  if (bb == 0x7fffffff) { if (tid == 0) { result[0] = 0; result[1] = -1; result[2] = -1; } return; }
+  if (bb == 0x7fffffff) {
+    if (tid == 0) { result[0] = 0; result[1] = -1; result[2] = -1; if (SCENES) result[3] = 0; }
+    if (SCENES) for (int e = tid; e < H * S; e += 1024) best[e] = __int_as_float(0x7fc00000);
+    return;
+  }
   int rank = 0;
   for (int b = tid; b < bb; b += 1024) rank += !mask[b];
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) rank += __shfl_xor(rank, m);
   if (lane == 0) r_cnt[wave] = rank;
   __syncthreads();
-  if (tid == 0) { int r = 0; for (int w = 0; w < 16; ++w) r += r_cnt[w]; result[0] = s_free; result[1] = r; result[2] = bb; }
+  if (tid == 0) { int r = 0; for (int w = 0; w < 16; ++w) r += r_cnt[w]; result[0] = s_free; result[1] = r; result[2] = bb + row0; if (SCENES) result[3] = 0; }
   if (traj == nullptr) return;                            // selection from gathered costs only (multi-GPU merge): the winner's owner holds the row
   for (int e = tid; e < H * S; e += 1024) {
     float v = traj[(long)bb * H * S + e];
-    if (e < S && e >= 2) v = 0.f;
+    if (!SCENES && e < S && e >= 2) v = 0.f;
     best[e] = v;
   }
+}
+
+__global__ __launch_bounds__(1024) void replan_select_kernel(const float* __restrict__ traj, const int* __restrict__ mask,
+                                                              const float* __restrict__ plen, const float* __restrict__ smooth,
+                                                              float w_s, float w_l, float* __restrict__ best,
+                                                              int* __restrict__ result, int B, int H, int S) {
+  select_block<false>(traj, mask, plen, smooth, w_s, w_l, best, result, B, H, S, 0);
+}
+// the same rule, one block per scene over the scene's rows [traj_first[s], traj_first[s + 1]) of a many-scene batch
+__global__ __launch_bounds__(1024) void select_scenes_kernel(const float* __restrict__ traj, const int* __restrict__ mask,
+                                                              const float* __restrict__ plen, const float* __restrict__ smooth,
+                                                              float w_s, float w_l, const int* __restrict__ traj_first,
+                                                              float* __restrict__ best, int* __restrict__ result, int B, int H, int S) {
+  const int s = blockIdx.x;
+  const int first = min(max(traj_first[s], 0), B), end = min(max(traj_first[s + 1], first), B);
+  select_block<true>(traj + (long)first * H * S, mask + first, plen + first, smooth + first, w_s, w_l, best + (long)s * H * S,
+                     result + 4 * s, end - first, H, S, first);
 }
 
 int launch_replan_init(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
@@ -414,6 +438,14 @@ int launch_replan_goal(float* x0, const float* x, int B, int H, int S, hipStream
 int launch_replan_select(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                          float* best, int* result, int B, int H, int S, hipStream_t s) {
   hipLaunchKernelGGL(replan_select_kernel, dim3(1), dim3(1024), 0, s, traj, mask, plen, smooth, w_s, w_l, best, result, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_select_scenes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
+                         const int* traj_first, int n_scenes, float* best, int* result, int B, int H, int S, hipStream_t s) {
+  RAMP_REQUIRE(B > 0 && H > 0 && S >= 2 && n_scenes > 0 && n_scenes <= B, "bad selection dims");
+  hipLaunchKernelGGL(select_scenes_kernel, dim3(n_scenes), dim3(1024), 0, s, traj, mask, plen, smooth, w_s, w_l, traj_first, best,
+                     result, B, H, S);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -498,15 +530,15 @@ int launch_apf_dynamic(const ApfDynArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 // trajectory costs: collision mask against the cloud, path length, smoothness (cost.py:3-54)
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void traj_costs_kernel(const float* __restrict__ traj, const float* __restrict__ cloud,
-                                                          int H, int S, int P, float thr, int* __restrict__ mask,
-                                                          float* __restrict__ plen, float* __restrict__ smooth) {
+// one block of 256 threads per trajectory `tr` against the P points of `cloud`; shared by the one-cloud and the per-scene kernel
+__device__ __forceinline__ void traj_costs_block(const float* __restrict__ tr, const float* __restrict__ cloud,
+                                                 int H, int S, int P, float thr, int* __restrict__ mask,
+                                                 float* __restrict__ plen, float* __restrict__ smooth) {
   __shared__ float2 cl[APF_TILE];
   __shared__ float xy[APF_MAXH * 2];
   __shared__ int any_hit;
   __shared__ float segl[APF_MAXH], segs[APF_MAXH];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const float* tr = traj + (long)b * H * S;
+  const int tid = threadIdx.x;
   if (tid == 0) any_hit = 0;
   for (int h = tid; h < H; h += 256) { xy[2 * h] = tr[h * S]; xy[2 * h + 1] = tr[h * S + 1]; }
   for (int p0 = 0; p0 < P; p0 += APF_TILE) {
@@ -534,13 +566,42 @@ __global__ __launch_bounds__(256) void traj_costs_kernel(const float* __restrict
   if (tid == 0) {
     float pl = 0.f, sm = 0.f;
     for (int h = 0; h < H - 1; ++h) { pl = add(pl, segl[h]); sm = add(sm, segs[h]); }
-    mask[b] = any_hit; plen[b] = pl; smooth[b] = sm;
+    *mask = any_hit; *plen = pl; *smooth = sm;
   }
+}
+__global__ __launch_bounds__(256) void traj_costs_kernel(const float* __restrict__ traj, const float* __restrict__ cloud,
+                                                          int H, int S, int P, float thr, int* __restrict__ mask,
+                                                          float* __restrict__ plen, float* __restrict__ smooth) {
+  const int b = blockIdx.x;
+  traj_costs_block(traj + (long)b * H * S, cloud, H, S, P, thr, mask + b, plen + b, smooth + b);
+}
+// traj_costs_kernel for a batch of many scenes: row b reads the points [cloud_off[s], cloud_off[s + 1]) of its own scene s,
+// found by bisection of traj_first (n_scenes + 1, increasing).  Spans are clamped to [0, P_total]: a wrong table reads wrong
+// points, never outside the cloud.
+__global__ __launch_bounds__(256) void traj_costs_scenes_kernel(const float* __restrict__ traj, const float* __restrict__ cloud,
+                                                                 const int* __restrict__ traj_first, const int* __restrict__ cloud_off,
+                                                                 int n_scenes, int P_total, int H, int S, float thr,
+                                                                 int* __restrict__ mask, float* __restrict__ plen,
+                                                                 float* __restrict__ smooth) {
+  const int b = blockIdx.x;
+  int lo = 0, hi = n_scenes - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (traj_first[mid] <= b) lo = mid; else hi = mid - 1; }
+  const int p0 = min(max(cloud_off[lo], 0), P_total), p1 = min(max(cloud_off[lo + 1], p0), P_total);
+  traj_costs_block(traj + (long)b * H * S, cloud + 2 * (long)p0, H, S, p1 - p0, thr, mask + b, plen + b, smooth + b);
 }
 int launch_traj_costs(const float* traj, const float* cloud, int B, int H, int S, int P, float thr, int* mask,
                       float* plen, float* smooth, hipStream_t s) {
   RAMP_REQUIRE(B > 0 && H > 1 && H <= APF_MAXH && S >= 2 && P > 0, "bad cost dims");
   hipLaunchKernelGGL(traj_costs_kernel, dim3(B), dim3(256), 0, s, traj, cloud, H, S, P, thr, mask, plen, smooth);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_traj_costs_scenes(const float* traj, const float* cloud, const int* traj_first, const int* cloud_off, int n_scenes,
+                             int P_total, int B, int H, int S, float thr, int* mask, float* plen, float* smooth, hipStream_t s) {
+  RAMP_REQUIRE(B > 0 && S >= 2 && n_scenes > 0 && n_scenes <= B && P_total > 0, "bad cost dims");
+  RAMP_REQUIRE(H > 1 && H <= APF_MAXH, "horizon beyond the cost kernel's limit");
+  hipLaunchKernelGGL(traj_costs_scenes_kernel, dim3(B), dim3(256), 0, s, traj, cloud, traj_first, cloud_off, n_scenes, P_total, H, S,
+                     thr, mask, plen, smooth);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }

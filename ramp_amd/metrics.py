@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .scenes import build_eval_tables, scene_counts
 
 
 def _dev_traj(trajs: torch.Tensor) -> torch.Tensor:
@@ -28,6 +29,22 @@ def _per_traj(trajs, centers=None, sizes=None):
                                                  out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
                                                  _lib.current_stream()), "ramp_traj_metrics")
     return out
+
+
+class SceneMetrics(dict):
+    """One scene's dict of ``Metrics.evaluate_scenes``: the keys of ``trajectory_success_and_metrics``.  ``free_trajectories`` is
+    gathered from the batch's free mask (a boolean-mask gather, i.e. a host sync) only when it is first read, so that
+    evaluating many scenes costs no per-scene sync; ``rows`` is the scene's slice of the batch."""
+
+    def __init__(self, values, trajs, free_mask, rows):
+        super().__init__(values)
+        self._trajs, self._free_mask, self.rows = trajs, free_mask, rows
+
+    def __missing__(self, key):
+        if key != 'free_trajectories':
+            raise KeyError(key)
+        self[key] = self._trajs[self.rows][self._free_mask[self.rows]]
+        return self[key]
 
 
 class Metrics:
@@ -88,6 +105,73 @@ class Metrics:
                 v = float(self.compute_variance_waypoints(free))
                 m['waypoint_variance'] = v if not np.isnan(v) else None
         return m
+
+
+    @staticmethod
+    def evaluate_scenes(trajs: torch.Tensor, counts_or_traj_scene, box_centers_list, box_sizes_list, threshold: float = 0.01):
+        """``compute_collision_intensity`` + ``trajectory_success_and_metrics`` for every scene of a many-scene batch
+        (``run_inference_scenes``: a scene's trajectories adjacent, scenes in order) in one pass: the loop over experiments of
+        scripts/inference/inference_static.py around metrics.py:21-126.
+
+        counts_or_traj_scene  trajectories per scene, or the (B) ``traj_scene`` array (a device one costs a copy: pass counts)
+        box_centers_list / box_sizes_list  per scene, what ``compute_collision_intensity`` takes ((n, 2) centres, (n, 2) or (n) sizes;
+                                           a scene may have no box)
+
+        Returns ``(per_scene, free_mask)``: one dict per scene with the keys and value conventions of
+        ``trajectory_success_and_metrics`` (None where the reference gives None, collision intensity in percent), and the (B) bool
+        device mask ``intensity <= threshold``.  ``free_trajectories`` is gathered lazily, when a caller reads it (SceneMetrics);
+        ``.rows`` of each dict is the scene's slice of the batch.
+        All uploads happen first (boxes, one int32 table); then ramp_traj_metrics_scenes + ramp_scene_summary, four kernels
+        whatever the number of scenes; the call ends in its only device-to-host copy, the (n_scenes, 6) records."""
+        t = _dev_traj(trajs)
+        B, H, S = t.shape
+        n_scenes = len(box_centers_list)
+        if len(box_sizes_list) != n_scenes:
+            raise ValueError(f"{n_scenes} box-centre entries but {len(box_sizes_list)} box-size entries")
+        counts = scene_counts(counts_or_traj_scene, n_scenes, B)
+        cs, ss = [], []
+        for c, z in zip(box_centers_list, box_sizes_list):
+            c = torch.as_tensor(c, dtype=torch.float32).detach().cpu().reshape(-1, 2)
+            z = torch.as_tensor(z, dtype=torch.float32).detach().cpu()
+            if z.dim() == 1:
+                z = z.unsqueeze(-1).repeat(1, 2)
+            z = z.reshape(-1, 2)
+            if z.shape[0] != c.shape[0]:
+                raise ValueError(f"scene {len(cs)}: {c.shape[0]} box centres but {z.shape[0]} box sizes")
+            cs.append(c); ss.append(z)
+        tab = build_eval_tables(counts, box_counts=[c.shape[0] for c in cs])
+        n_boxes = int(tab["box_offset"][-1])
+        dev = t.device
+        boxes = torch.cat([torch.cat(cs), torch.cat(ss)]).contiguous().to(dev)         # (2 n_boxes, 2): centres then sizes
+        tables = torch.from_numpy(np.concatenate([tab["traj_first"], tab["box_offset"]])).to(dev)
+        per = torch.empty(3, B, device=dev)
+        W = (B + 255) // 256 + n_scenes
+        scratch = torch.empty(2 * H * W + n_scenes + 1, dtype=torch.float64, device=dev)
+        summary = torch.empty(n_scenes, 6, dtype=torch.float64, device=dev)
+        mask = torch.empty(B, dtype=torch.int32, device=dev)
+        first, box_off = tables[:n_scenes + 1], tables[n_scenes + 1:]
+        with torch.cuda.device(dev):
+            lib = _lib.load()
+            _lib.check(lib.ramp_traj_metrics_scenes(_lib.ptr(t), B, H, S, first.data_ptr(), n_scenes,
+                                                    boxes.data_ptr() if n_boxes else None,
+                                                    boxes[n_boxes:].data_ptr() if n_boxes else None, box_off.data_ptr(), n_boxes,
+                                                    per[0].data_ptr(), per[1].data_ptr(), per[2].data_ptr(),
+                                                    _lib.current_stream()), "ramp_traj_metrics_scenes")
+            _lib.check(lib.ramp_scene_summary(_lib.ptr(t), B, H, S, first.data_ptr(), n_scenes, per[0].data_ptr(),
+                                              per[1].data_ptr(), float(threshold), _lib.ptr(scratch), _lib.ptr(summary),
+                                              _lib.ptr(mask), _lib.current_stream()), "ramp_scene_summary")
+        free_mask = mask.bool()
+        rec = summary.cpu().numpy()                                                     # the one device-to-host copy
+        out, b = [], 0
+        for i in range(n_scenes):
+            n_traj, n_free, ci, pl, sd, var = rec[i]
+            out.append(SceneMetrics({'success': 1 if n_free > 0 else 0, 'collision_intensity': float(ci) * 100,
+                                     'path_length': None if np.isnan(pl) else float(pl),
+                                     'path_length_std': None if np.isnan(sd) else float(sd),
+                                     'waypoint_variance': None if np.isnan(var) else float(var),
+                                     'n_free_trajectories': int(n_free)}, trajs, free_mask, slice(b, b + counts[i])))
+            b += counts[i]
+        return out, free_mask
 
 
 class DynamicMetrics(Metrics):

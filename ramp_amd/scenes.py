@@ -3,7 +3,7 @@
 turned into one batch.  Pure numpy, no device: everything here is testable without a GPU."""
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
@@ -71,3 +71,59 @@ def scene_slices(counts: Sequence[int]) -> List[slice]:
         out.append(slice(b, b + int(c)))
         b += int(c)
     return out
+
+
+def _offsets(what: str, sizes: Sequence[int], n_scenes: int, allow_empty: bool) -> np.ndarray:
+    vals = [int(v) for v in sizes]
+    if len(vals) != n_scenes:
+        raise ValueError(f"{what} has {len(vals)} entries for {n_scenes} scenes")
+    for i, v in enumerate(vals):
+        if v < 0 or (v == 0 and not allow_empty):
+            raise ValueError(f"scene {i}: {what} is {v}" + ("" if allow_empty else "; every scene needs at least one"))
+    off = np.zeros(n_scenes + 1, dtype=np.int64)
+    np.cumsum(vals, out=off[1:])
+    if off[-1] >= 2 ** 31:
+        raise ValueError(f"the concatenated {what} do not fit 32-bit offsets")
+    return off.astype(np.int32)
+
+
+def build_eval_tables(counts: Sequence[int], box_counts: Optional[Sequence[int]] = None,
+                      cloud_sizes: Optional[Sequence[int]] = None) -> Dict[str, np.ndarray]:
+    """Tables of the per-scene evaluation of a many-scene batch (``ramp_traj_metrics_scenes``, ``ramp_scene_summary``,
+    ``ramp_traj_costs_scenes``, ``ramp_select_best_scenes``), for the layout ``build_scene_tables`` produces: a scene's
+    trajectories adjacent, scenes in order.
+
+    counts       trajectories of each scene, at least one each
+    box_counts   boxes of each scene (0 allowed: such a scene has collision intensity 0), or None
+    cloud_sizes  points of each scene's cost cloud, at least one each, or None
+
+    Returns int32 arrays of ``n_scenes + 1`` entries: ``traj_first`` (strictly increasing, ``[-1] = B``) and, for what was given,
+    ``box_offset`` (may repeat a value) and ``cloud_offset`` (strictly increasing) into the boxes / clouds concatenated over scenes.
+    """
+    n_scenes = len(counts)
+    if n_scenes == 0:
+        raise ValueError("no scenes given")
+    out = {"traj_first": _offsets("trajectory counts", counts, n_scenes, allow_empty=False)}
+    if box_counts is not None:
+        out["box_offset"] = _offsets("box counts", box_counts, n_scenes, allow_empty=True)
+    if cloud_sizes is not None:
+        out["cloud_offset"] = _offsets("cost cloud sizes", cloud_sizes, n_scenes, allow_empty=False)
+    return out
+
+
+def scene_counts(counts_or_traj_scene, n_scenes: int, B: int) -> List[int]:
+    """Per-scene trajectory counts from either the counts themselves (``n_scenes`` positive entries summing to ``B``) or the
+    ``traj_scene`` (B) array of ``build_scene_tables`` (scenes in order, a scene's rows adjacent).  A device ``traj_scene`` is copied
+    to the host: pass counts where that copy matters."""
+    v = counts_or_traj_scene
+    if hasattr(v, "detach"):
+        v = v.detach().cpu().numpy()
+    v = np.asarray(v).astype(np.int64).reshape(-1)
+    if v.size == n_scenes and int(v.sum()) == B and bool((v > 0).all()):
+        return [int(c) for c in v]
+    if v.size != B:
+        raise ValueError(f"expected {n_scenes} per-scene counts summing to {B}, or the scene of each of the {B} trajectories; "
+                         f"got {v.size} entries")
+    if v.size and (v.min() < 0 or v.max() >= n_scenes or bool((np.diff(v) < 0).any())):
+        raise ValueError("traj_scene must hold scene indices in [0, n_scenes) in ascending order (a scene's trajectories adjacent)")
+    return [int(c) for c in np.bincount(v, minlength=n_scenes)]
