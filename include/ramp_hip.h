@@ -125,14 +125,25 @@ int ramp_encode_scene(ramp_ctx* ctx, const float* cloud, int32_t n_obstacles, in
 /* TemporalUnetInference.forward / forward_no_energy (UnetInference.py:157-224).
  * x (B,H,S); each trajectory is evaluated n_rp times (rows b*n_rp + v).  f_out (B*n_rp,H,S)
  * receives forward_no_energy's output, eps_out (B*n_rp,H,S) the energy gradient; either may be
- * NULL.  t is the (batch-uniform) diffusion timestep, 0 <= t < T of the prepared table.
+ * NULL.  t is the diffusion timestep of EVERY row, 0 <= t < T of the prepared table (what the samplers pass: make_timesteps'
+ * batch-uniform vector); one timestep per row is ramp_score_rows below.
  * fp16x3 mode: the first call after ramp_create / ramp_set_scene / ramp_sample / ramp_set_fallback runs the bf16x6
  * kernels and records every GEMM call site's operand maximum; later calls run the fp16x3 kernels scaled from their
  * predecessor's maxima.  If the range guard fires the evaluation is repeated at once with the bf16x6 kernels (one
  * 4-byte read-back per call decides), so a flagged result is never returned. */
 int ramp_score(ramp_ctx* ctx, const float* x, int32_t B, int32_t n_rp, int32_t t,
                float* f_out, float* eps_out, void* stream);
-/* arithmetic the last ramp_score call's result was computed in: 0 exact fp32, 1 bf16x6, 2 fp16x3 */
+/* ramp_score with one diffusion timestep per network row (UnetInference.py:198 embeds `time` per row; the reference's own
+ * loss / p_losses draws t = randint(0, T, (B,)), diffusion_model_static.py:478-511).  t_rows_host: HOST int32 array of B * n_rp
+ * entries, entry r the timestep of row r (the row_variant_host convention); every entry is checked against the prepared table
+ * (0 <= t < T) before anything is launched, then the table is copied to a device buffer of the context (sliced per chunk when
+ * B * n_rp exceeds max_rows).  The time-conditioning arithmetic is the same precomputed table; only the row -> table-line choice is
+ * per row, so a row's result has the bits ramp_score gives it at that row's t.  Arithmetic modes, the fp16x3 calibration kept from
+ * call to call (shared with ramp_score), the range guard and its bf16x6 repeat, debug taps and ramp_set_scenes tables: ramp_score's.
+ * The samplers (ramp_sample*, ramp_replan) keep the uniform path. */
+int ramp_score_rows(ramp_ctx* ctx, const float* x, int32_t B, int32_t n_rp, const int32_t* t_rows_host,
+                    float* f_out, float* eps_out, void* stream);
+/* arithmetic the last ramp_score / ramp_score_rows call's result was computed in: 0 exact fp32, 1 bf16x6, 2 fp16x3 */
 int ramp_score_mode(ramp_ctx* ctx, int32_t* mode);
 
 /* ---- sampler loops: run_inference -> conditional_sample -> p_sample_loop / ddim_p_sample_loop
@@ -335,6 +346,16 @@ int ramp_traj_metrics(const float* traj, int32_t B, int32_t H, int32_t S, const 
 /* Metrics.compute_variance_waypoints (metrics.py:8-19): sum over waypoints of the unbiased variance of all B*B entries
  * of triu(cdist(p, p), 1).  scratch: device, 2 * H * ceil(B/256) doubles; out: device, 1 double. */
 int ramp_waypoint_variance(const float* traj, int32_t B, int32_t H, int32_t S, double* scratch, double* out, void* stream);
+/* The two elementwise ends of the denoising loss (p_losses, diffusion_model_static.py:467-505), one launch / one two-stage reduction:
+ * ramp_q_sample_rows: x_noisy[b] = sqrt_ac[t_rows[b]] x_start[b] + sqrt_1m_ac[t_rows[b]] noise[b]; pin_endpoints != 0: waypoints 0 and
+ *   H - 1 overwritten by x_start's.  Everything on the device: schedules (T), t_rows int32 (B); a row whose t is outside [0, T) comes back NaN.
+ * ramp_denoise_loss: overwrites waypoints 0 and H - 1 of x_recon with x_start's IN PLACE, then out[0] = mean of (x_recon - target)^2
+ *   (l1 = 0: WeightedL2, helpers.py:97-100) or |x_recon - target| (l1 = 1: WeightedL1, :91-94), no weights; fp32 terms, fp64 sums in
+ *   a fixed order (bit-reproducible).  scratch: device, 1024 doubles; out: device, 1 double. */
+int ramp_q_sample_rows(const float* x_start, const float* noise, const float* sqrt_ac, const float* sqrt_1m_ac, const int32_t* t_rows,
+                       int32_t T, float* x_noisy, int32_t B, int32_t H, int32_t S, int32_t pin_endpoints, void* stream);
+int ramp_denoise_loss(float* x_recon, const float* x_start, const float* target, int32_t B, int32_t H, int32_t S, int32_t l1,
+                      double* scratch, double* out, void* stream);
 
 /* ---- evaluation and selection of a many-scene batch (what ramp_sample_scenes returns), per scene, in a fixed number of launches ----
  * Layout: a scene's trajectories are adjacent, scenes in order.  Every table is a DEVICE int32 array of n_scenes + 1 entries:
@@ -451,6 +472,13 @@ int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, con
                 const float* gn_c, const float* gn_stats, const float* gn_gamma, const float* gn_beta, const float* gamma, const float* beta,
                 const float* tbias, int32_t M, int32_t L, int32_t N, int32_t K, int32_t dir, int32_t N1, float absmax_prev, float* Y, float* Y2,
                 float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream);
+/* The forward form of ramp_op_tkw (one operand, one output, GroupNorm epilogue) with one timestep per sample: sample r (L tokens) adds
+ * time_table[t_rows[r] * tt_stride + n] behind the Mish instead of tbias[n].  time_table device (T, tt_stride) at this layer's column offset,
+ * t_rows device int32 (M / L), every entry in [0, T) -- the caller's duty here, ramp_score_rows checks it on the host.  Samples that carry
+ * timestep t equal, bit for bit, ramp_op_tkw with tbias = time_table + t * tt_stride. */
+int ramp_op_tkw_rows(const float* X, const float* W, const float* bias, const float* resid, const float* gamma, const float* beta,
+                     const float* time_table, int32_t tt_stride, const int32_t* t_rows, int32_t M, int32_t L, int32_t N, int32_t K, float absmax_prev,
+                     float* Y, float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream);
 /* d(ln1) = d(qkv) Wqkv^T with the LayerNorm-1 backward in its epilogue (tkl.hip, tklb_kernel; the product path's replacement of
  * the d(ln1) GEMM + ln_bwd pair, reference layers_attention_mini.py:132 differentiated): out = add + LNbwd(dqkv W^T; z, ln_g).
  * dqkv (M, 768), W (256, 768) = [Wq | Wk | Wv]^T rows, z / add / out (M, 256), device fp32.  Scaling arguments as ramp_op_tkl. */
@@ -468,6 +496,10 @@ int ramp_op_abl(const float* qkv, const float* dout, const float* W, const float
 int ramp_op_groupnorm(const float* x, const float* gamma, const float* beta, const float* tbias,
                       const float* resid, float* y, float* stats, int32_t R, int32_t L, int32_t C,
                       float eps, int32_t mish, void* stream);
+/* ramp_op_groupnorm with one timestep per row: row r adds time_table[t_rows[r] * tt_stride + c]; t_rows device int32 (R), entries in [0, T) */
+int ramp_op_groupnorm_rows(const float* x, const float* gamma, const float* beta, const float* time_table, int32_t tt_stride,
+                           const int32_t* t_rows, const float* resid, float* y, float* stats, int32_t R, int32_t L, int32_t C,
+                           float eps, int32_t mish, void* stream);
 int ramp_op_groupnorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma,
                           const float* beta, const float* add, float* dx, int32_t R, int32_t L, int32_t C,
                           int32_t mish, void* stream);

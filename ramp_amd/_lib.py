@@ -105,6 +105,8 @@ PROTOTYPES = {
     "ramp_encode_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "ramp_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
+    "ramp_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, c_i32p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     "ramp_score_mode": (C.c_int, [C.c_void_p, c_i32p]),
     "ramp_sample": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
@@ -128,6 +130,8 @@ PROTOTYPES = {
     "ramp_traj_metrics": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_waypoint_variance": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_q_sample_rows": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ramp_denoise_loss": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 3),
     "ramp_traj_costs": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_traj_metrics_scenes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
@@ -154,8 +158,10 @@ PROTOTYPES = {
     "ramp_op_atb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "ramp_op_abl": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_float, C.c_void_p, c_f32p, c_i32p, C.c_void_p]),
     "ramp_op_tkw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 11 + [C.c_int32] * 6 + [C.c_float] + [C.c_void_p] * 4 + [c_f32p, c_i32p, C.c_void_p]),
+    "ramp_op_tkw_rows": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_void_p] + [C.c_int32] * 4 + [C.c_float] + [C.c_void_p] * 3 + [c_f32p, c_i32p, C.c_void_p]),
     "ramp_op_tklb": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_float, C.c_void_p, c_f32p, c_i32p, C.c_void_p]),
     "ramp_op_groupnorm": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_void_p]),
+    "ramp_op_groupnorm_rows": (C.c_int, [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_int32, C.c_void_p]),
     "ramp_op_groupnorm_bwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 4 + [C.c_void_p]),
     "ramp_op_layernorm": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "ramp_op_layernorm_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_void_p]),

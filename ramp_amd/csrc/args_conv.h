@@ -23,6 +23,8 @@ struct TkcArgs {
   // to `stats`, Y = mish(GN(Cst) gamma + beta) + tbias + resid
   const float* gn_c = nullptr; const float* gn_stats = nullptr; const float* gn_gamma = nullptr; const float* gn_beta = nullptr;
   float* Cst = nullptr; float* stats = nullptr; const float* gamma = nullptr; const float* beta = nullptr; const float* tbias = nullptr; float eps = 1e-5f;
+  // EPI with per-row timesteps: t_rows (M / L) given -> sample r adds tbias[t_rows[r] * tt_stride + n] (tbias = line 0 of the time table at this layer's offset)
+  const int* t_rows = nullptr; int tt_stride = 0;
 };
 bool tkc_applicable(int M, int L, int N, int K, int* ng);
 int launch_tkc(const TkcArgs& a, hipStream_t s);
@@ -50,6 +52,7 @@ struct TkwArgs {
   float* Y2 = nullptr; int ldy2 = 0; int N1 = 0;            // N1 == N when Y2 unused
   float* Cst = nullptr; float* stats = nullptr;             // EPI 1: (M, N) stash, (M / L, 8, 2) mean / rstd
   const float* gamma = nullptr; const float* beta = nullptr; const float* tbias = nullptr; float eps = 1e-5f;
+  const int* t_rows = nullptr; int tt_stride = 0;           // EPI 1 / 2 with per-row timesteps, as TkcArgs: the time bias of a token is read in the epilogue from its sample's table line
   const float* amax_in = nullptr; float* amax_out = nullptr; int site = 0;
   int* range_flag = nullptr;
   int ablate = 0;                      // diagnostic (ramp_bench_gemm only; wrong results): 1 no MFMA loop, 2 no operand loads, 4 no epilogue stores

@@ -10,6 +10,8 @@ struct GnArgs {
   const float* x = nullptr;       // (R, L, C) conv output
   const float* gamma = nullptr; const float* beta = nullptr;
   const float* tbias = nullptr;   // (C) added after the activation, or null
+  // per-row timesteps: t_rows (R) given -> row r adds tbias[t_rows[r] * tt_stride + c] (tbias = line 0 of the time table at this layer's offset)
+  const int* t_rows = nullptr; int tt_stride = 0;
   const float* resid = nullptr;   // (R, L, C) added after the activation, or null
   float* y = nullptr;             // (R, L, C)
   float* stats = nullptr;         // (R, 8, 2) mean, rstd (written)

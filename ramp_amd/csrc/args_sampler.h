@@ -25,6 +25,11 @@ int launch_ddpm_finish(const float* mean, const float* noise, float stdv, float 
 int launch_ddim_finish(const float* x_in, const float* x0, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
                        float dir_coef, HardConds hc, float* x, float* chain_out, int B, int H, int S, hipStream_t s);
 int launch_hard_cond(float* x, HardConds hc, int B, int H, int S, hipStream_t s);
+// q_sample with one timestep per row (diffusion_model_static.py:467-476) and, with pin, both endpoints overwritten by x_start (:483-484):
+// x_noisy[b] = sqrt_ac[t[b]] x_start[b] + sqrt_1m_ac[t[b]] noise[b]; pin: waypoints 0 and H - 1 = x_start's.  t device (B), schedules device (T);
+// a row whose t is outside [0, T) is written as NaN, never read with it
+int launch_q_sample_rows(const float* x_start, const float* noise, const float* sqrt_ac, const float* sqrt_1m_ac, const int* t_rows, int T,
+                         float* x_noisy, int B, int H, int S, int pin, hipStream_t s);
 // out[0..n) ~ N(0, 1): Philox4x32-10 + Box-Muller, rec = device {seed, offset in groups of four elements} (sampler.hip)
 int launch_philox_normal(float* out, long n, const unsigned long long* rec, hipStream_t s);
 // the same stream addressed by GLOBAL sample index: out is this shard's (n_blocks, B, HS) noise block of a job whose whole
@@ -81,6 +86,12 @@ int launch_traj_metrics(const float* traj, int B, int H, int S, const float* cen
                         float* intensity, float* path_len, float* smooth, hipStream_t s);
 // scratch: 2 * H * ceil(B / 256) doubles; out: 1 double
 int launch_waypoint_variance(const float* traj, int B, int H, int S, double* scratch, double* out, hipStream_t s);
+// denoising loss (diffusion_model_static.py:497-505, helpers.py:71-100): waypoints 0 and H - 1 of x_recon are overwritten with x_start's (in
+// place), then out[0] = mean over all elements of (x_recon - target)^2 (l1 = 0) or |x_recon - target| (l1 = 1): fp32 terms, fp64 sums in a fixed
+// order (two stages).  scratch: DENOISE_LOSS_BLOCKS doubles; out: 1 double
+constexpr int DENOISE_LOSS_BLOCKS = 1024;
+int launch_denoise_loss(float* x_recon, const float* x_start, const float* target, int B, int H, int S, int l1, double* scratch, double* out,
+                        hipStream_t s);
 // many-scene batch: row b tests the boxes [box_off[s], box_off[s + 1]) of its scene only
 int launch_traj_metrics_scenes(const float* traj, int B, int H, int S, const int* traj_first, int n_scenes, const float* centers,
                                const float* sizes, const int* box_off, int n_boxes_total, float* intensity, float* path_len,

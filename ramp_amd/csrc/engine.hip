@@ -196,6 +196,9 @@ struct ramp_ctx {
   int force_x6 = 0;                  // ramp_set_fallback: run ramp_sample entirely in bf16x6 although the mode is fp16x3
   // single evaluations (ramp_score): the tables of the last evaluation stay valid as the next one's calibration
   bool score_calibrated = false; bool score_calibrated_bwd = false; int score_parity = 0; int score_last_mode = 0;
+  // ramp_score_rows: the row -> timestep table of the call (device, its entries range-checked on the host); t_rows_cur is non-null only
+  // while that call's evaluations are being launched -- rtb_forward hands it, offset by the chunk's first row, to the time-bias consumers
+  int* t_rows_dev = nullptr; size_t t_rows_cap = 0; const int* t_rows_cur = nullptr;
   float* obs = nullptr; float *obs_in = nullptr, *obs_out = nullptr;
   int* range_flag = nullptr;
   // debug
@@ -497,7 +500,7 @@ struct Run {
   template <class T> static void fuse_gn(T& t, const GnBwdArgs* pro, const GnArgs* epi) {
     if (pro) { t.X = pro->dy; t.ldx = pro->C; t.gn_c = pro->x; t.gn_stats = pro->stats; t.gn_gamma = pro->gamma; t.gn_beta = pro->beta; }
     if (epi) {
-      t.Cst = t.Y; t.stats = epi->stats; t.gamma = epi->gamma; t.beta = epi->beta; t.tbias = epi->tbias; t.eps = epi->eps;
+      t.Cst = t.Y; t.stats = epi->stats; t.gamma = epi->gamma; t.beta = epi->beta; t.tbias = epi->tbias; t.t_rows = epi->t_rows; t.tt_stride = epi->tt_stride; t.eps = epi->eps;
       t.Y = epi->y; t.ldy = epi->C;
       if (epi->resid) { t.resid = epi->resid; t.ldr = epi->C; }
     }
@@ -644,6 +647,8 @@ int rtb_forward(Run& r, RTB& m, const float* xa, int ca, const float* xb, int cb
   ramp_ctx* c = r.c; const int R = r.R, M = R * m.L;
   const float* tbias = c->time_table + (size_t)t * c->tt_stride + m.tb_off;
   GnArgs g; g.x = m.a_c1; g.gamma = m.g1; g.beta = m.b1; g.tbias = tbias; g.resid = nullptr; g.y = m.a_h;
+  // ramp_score_rows: every row picks its own table line (t == 0 here: tbias is line 0 at this block's offset)
+  if (c->t_rows_cur) { g.t_rows = c->t_rows_cur + r.row0; g.tt_stride = c->tt_stride; }
   g.stats = m.a_st1; g.R = R; g.L = m.L; g.C = m.cout; g.eps = 1e-5f; g.mish = 1;
   const float* resid;
   bool gn_due = true;
@@ -668,7 +673,7 @@ int rtb_forward(Run& r, RTB& m, const float* xa, int ca, const float* xb, int cb
   if (gn_due) LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_fwd(g, r.s));
   // conv -> (stash c2, statistics) -> GroupNorm -> Mish -> + residual = the block's output
   GemmArgs c2a = conv5(m.a_h, m.cout, m.c2.fwd, m.c2.bias, m.a_c2, m.cout, M, m.cout, m.cout, m.L, false);
-  g.x = m.a_c2; g.gamma = m.g2; g.beta = m.b2; g.tbias = nullptr; g.resid = resid; g.y = m.a_out; g.stats = m.a_st2;
+  g.x = m.a_c2; g.gamma = m.g2; g.beta = m.b2; g.tbias = nullptr; g.t_rows = nullptr; g.resid = resid; g.y = m.a_out; g.stats = m.a_st2;
   CK(r.conv_gn(c2a, g));
   CK(dbg_store(c, "out/" + m.name, m.a_out, (size_t)M * m.cout, r.s));
   return 0;
@@ -1701,6 +1706,28 @@ int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, 
   c->score_calibrated = true; c->score_calibrated_bwd = eps_out != nullptr; c->score_parity ^= 1; c->score_last_mode = 1;
   c->r_calibrated = false;
   return 0;
+}
+
+int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const int32_t* t_rows_host, float* f_out, float* eps_out,
+                    void* stream) {
+  RAMP_REQUIRE(c && x && t_rows_host, "null argument");
+  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= 3 && (long)B * n_rp <= (1l << 24), "bad batch");
+  RAMP_REQUIRE(c->time_table != nullptr && c->tt_T > 0, "time table not prepared (ramp_prepare_time_table)");
+  const size_t n = (size_t)B * n_rp;
+  for (size_t i = 0; i < n; ++i)
+    RAMP_REQUIRE(t_rows_host[i] >= 0 && t_rows_host[i] < c->tt_T, "a row's timestep is outside the prepared time table");
+  hipStream_t s = as_stream(stream);
+  if (c->t_rows_cap < n) {
+    float* p; CK(dev_alloc(c, &p, n)); c->t_rows_dev = reinterpret_cast<int*>(p); c->t_rows_cap = n;
+  }
+  RAMP_HIP_CHECK(hipStreamSynchronize(s));                  // (an earlier call's kernels may still read the table; hipMemcpy is ordered against the NULL stream only)
+  RAMP_HIP_CHECK(hipMemcpy(c->t_rows_dev, t_rows_host, n * sizeof(int), hipMemcpyHostToDevice));
+  // everything else -- arithmetic modes, the kept fp16x3 calibration and its range guard, taps, chunking -- is ramp_score's, run with t = 0:
+  // the consumers then see line 0 of the table as their base and add the row's line offset
+  c->t_rows_cur = c->t_rows_dev;
+  const int rc = ramp_score(c, x, B, n_rp, 0, f_out, eps_out, stream);
+  c->t_rows_cur = nullptr;
+  return rc;
 }
 
 // sc != nullptr: a job of many scenes (ramp_sample_scenes) -- the APF of trajectory b runs against the cloud of scene traj_scene[b]

@@ -4,6 +4,8 @@
 // triangular pairwise distance matrix, per waypoint, summed over waypoints).
 #include "args_sampler.h"
 
+#include <algorithm>
+
 namespace ramp {
 
 // one wave per trajectory; lane = waypoint (strided when H > 64).  The arithmetic of one row, shared by the one-scene and
@@ -121,6 +123,47 @@ int launch_waypoint_variance(const float* traj, int B, int H, int S, double* scr
   const int nblk = (B + 255) / 256;
   hipLaunchKernelGGL(waypoint_pairs_kernel, dim3(nblk, H), dim3(256), 0, s, traj, B, H, S, scratch);
   hipLaunchKernelGGL(waypoint_var_kernel, dim3(1), dim3(64), 0, s, scratch, nblk, H, B, out);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---- denoising loss: stage 1 -- block k owns the contiguous elements [k per, (k + 1) per), pins the endpoints of x_recon in place and
+// sums its fp32 terms in fp64 (thread-strided, then a fixed shuffle / LDS tree); stage 2 -- one thread adds the block sums in order.
+// Nothing depends on the launch's timing: the same inputs give the same bits.
+__global__ __launch_bounds__(256)
+void denoise_loss_kernel(float* __restrict__ x_recon, const float* __restrict__ x_start, const float* __restrict__ target, long n, long per,
+                         int H, int S, int l1, double* __restrict__ partial) {
+  __shared__ double red[4];
+  const long lo = (long)blockIdx.x * per, hi = min(lo + per, n);
+  double acc = 0.0;
+  for (long i = lo + threadIdx.x; i < hi; i += 256) {
+    const int h = (int)((i / S) % H);
+    float r = x_recon[i];
+    if (h == 0 || h == H - 1) { r = x_start[i]; x_recon[i] = r; }
+    const float d = r - target[i];
+    const float term = l1 ? fabsf(d) : d * d;
+    acc += (double)term;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+__global__ void denoise_loss_finish_kernel(const double* __restrict__ partial, int nblk, long n, double* __restrict__ out) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  double total = 0.0;
+  for (int k = 0; k < nblk; ++k) total += partial[k];
+  out[0] = total / (double)n;
+}
+int launch_denoise_loss(float* x_recon, const float* x_start, const float* target, int B, int H, int S, int l1, double* scratch, double* out,
+                        hipStream_t s) {
+  RAMP_REQUIRE(B > 0 && H > 1 && S > 0, "bad loss dims");
+  const long n = (long)B * H * S;
+  const int nblk = (int)std::min<long>((n + 255) / 256, DENOISE_LOSS_BLOCKS);
+  const long per = (n + nblk - 1) / nblk;
+  hipLaunchKernelGGL(denoise_loss_kernel, dim3(nblk), dim3(256), 0, s, x_recon, x_start, target, n, per, H, S, l1, scratch);
+  hipLaunchKernelGGL(denoise_loss_finish_kernel, dim3(1), dim3(64), 0, s, scratch, nblk, n, out);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }

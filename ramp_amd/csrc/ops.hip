@@ -172,6 +172,16 @@ int ramp_waypoint_variance(const float* traj, int32_t B, int32_t H, int32_t S, d
   RAMP_REQUIRE(traj && scratch && out, "null argument");
   return launch_waypoint_variance(traj, B, H, S, scratch, out, as_stream(stream));
 }
+int ramp_q_sample_rows(const float* x_start, const float* noise, const float* sqrt_ac, const float* sqrt_1m_ac, const int32_t* t_rows, int32_t T,
+                       float* x_noisy, int32_t B, int32_t H, int32_t S, int32_t pin_endpoints, void* stream) {
+  RAMP_REQUIRE(x_start && noise && sqrt_ac && sqrt_1m_ac && t_rows && x_noisy, "null argument");
+  return launch_q_sample_rows(x_start, noise, sqrt_ac, sqrt_1m_ac, t_rows, T, x_noisy, B, H, S, pin_endpoints != 0, as_stream(stream));
+}
+int ramp_denoise_loss(float* x_recon, const float* x_start, const float* target, int32_t B, int32_t H, int32_t S, int32_t l1, double* scratch,
+                      double* out, void* stream) {
+  RAMP_REQUIRE(x_recon && x_start && target && scratch && out && (l1 == 0 || l1 == 1), "null argument or bad loss type");
+  return launch_denoise_loss(x_recon, x_start, target, B, H, S, l1, scratch, out, as_stream(stream));
+}
 
 
 // ---- a many-scene batch (ramp_sample_scenes' layout: a scene's rows adjacent, scenes in order), every table on the device ----
@@ -451,10 +461,12 @@ int ramp_op_abl(const float* qkv, const float* dout, const float* W, const float
   return rc;
 }
 
-int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, const float* bias, const float* resid, const float* resid2,
-                const float* gn_c, const float* gn_stats, const float* gn_gamma, const float* gn_beta, const float* gamma, const float* beta,
-                const float* tbias, int32_t M, int32_t L, int32_t N, int32_t K, int32_t dir, int32_t N1, float absmax_prev, float* Y, float* Y2,
-                float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
+}  // extern "C"
+// ramp_op_tkw and ramp_op_tkw_rows: t_rows == nullptr -> tbias is the (N) time bias; else tbias is the time table (line stride tt_stride) and sample r adds line t_rows[r]
+static int op_tkw(const float* X, const float* X2, int32_t K1, const float* W, const float* bias, const float* resid, const float* resid2,
+                  const float* gn_c, const float* gn_stats, const float* gn_gamma, const float* gn_beta, const float* gamma, const float* beta,
+                  const float* tbias, const int32_t* t_rows, int32_t tt_stride, int32_t M, int32_t L, int32_t N, int32_t K, int32_t dir, int32_t N1,
+                  float absmax_prev, float* Y, float* Y2, float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
   RAMP_REQUIRE(X && W && Y && M > 0 && L > 0 && N % 32 == 0 && K % 16 == 0, "bad arguments");
   hipStream_t s = as_stream(stream);
   DevArena ar;
@@ -477,7 +489,7 @@ int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, con
     t.resid2 = resid2; t.ldr2 = N; t.Y = Y; t.ldy = N; t.amax_in = absmax_prev > 0.f ? sl : nullptr; t.amax_out = sl + 1; t.wsi = 1.f / sc;
     t.range_flag = reinterpret_cast<int*>(sl + 2);
     t.gn_c = gn_c; t.gn_stats = gn_stats; t.gn_gamma = gn_gamma; t.gn_beta = gn_beta;
-    t.Cst = Cst; t.stats = stats; t.gamma = gamma; t.beta = beta; t.tbias = tbias; t.eps = 1e-5f;
+    t.Cst = Cst; t.stats = stats; t.gamma = gamma; t.beta = beta; t.tbias = tbias; t.t_rows = t_rows; t.tt_stride = tt_stride; t.eps = 1e-5f;
     int rc5 = launch_tkc(t, s);
     hipError_t e5 = hipStreamSynchronize(s);
     float back[4] = {0, 0, 0, 0};
@@ -505,7 +517,7 @@ int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, con
   TkwArgs a; a.M = M; a.L = L; a.N = N; a.K = K; a.dir = dir; a.X = X; a.ldx = X2 ? K1 : K; a.X2 = X2; a.ldx2 = X2 ? K - K1 : 0; a.K1 = X2 ? K1 : K;
   a.gn_c = gn_c; a.gn_stats = gn_stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.W = planes; a.wsi = 1.f / sc; a.bias = bias;
   a.resid = resid; a.ldr = N; a.resid2 = resid2; a.ldr2 = N; a.Y = Y; a.ldy = Y2 ? N1 : N; a.Y2 = Y2; a.ldy2 = Y2 ? N - N1 : 0; a.N1 = Y2 ? N1 : N;
-  a.Cst = Cst; a.stats = stats; a.gamma = gamma; a.beta = beta; a.tbias = tbias; a.eps = 1e-5f;
+  a.Cst = Cst; a.stats = stats; a.gamma = gamma; a.beta = beta; a.tbias = tbias; a.t_rows = t_rows; a.tt_stride = tt_stride; a.eps = 1e-5f;
   a.amax_in = absmax_prev > 0.f ? slots : nullptr; a.amax_out = slots + 1; a.site = 0; a.range_flag = reinterpret_cast<int*>(slots + 2);
   int rc = launch_tkw(a, s);
   hipError_t e = hipStreamSynchronize(s);
@@ -517,6 +529,22 @@ int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, con
   }
   RAMP_HIP_CHECK(e);
   return rc;
+}
+
+extern "C" {
+int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, const float* bias, const float* resid, const float* resid2,
+                const float* gn_c, const float* gn_stats, const float* gn_gamma, const float* gn_beta, const float* gamma, const float* beta,
+                const float* tbias, int32_t M, int32_t L, int32_t N, int32_t K, int32_t dir, int32_t N1, float absmax_prev, float* Y, float* Y2,
+                float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
+  return op_tkw(X, X2, K1, W, bias, resid, resid2, gn_c, gn_stats, gn_gamma, gn_beta, gamma, beta, tbias, nullptr, 0, M, L, N, K, dir, N1, absmax_prev,
+                Y, Y2, Cst, stats, absmax_out_host, range_flag_out_host, stream);
+}
+int ramp_op_tkw_rows(const float* X, const float* W, const float* bias, const float* resid, const float* gamma, const float* beta,
+                     const float* time_table, int32_t tt_stride, const int32_t* t_rows, int32_t M, int32_t L, int32_t N, int32_t K, float absmax_prev,
+                     float* Y, float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
+  RAMP_REQUIRE(time_table && t_rows && Cst && stats && gamma && beta && tt_stride >= N, "bad arguments (the forward convolution with its GroupNorm epilogue, a time table and a row -> timestep table)");
+  return op_tkw(X, nullptr, K, W, bias, resid, nullptr, nullptr, nullptr, nullptr, nullptr, gamma, beta, time_table, t_rows, tt_stride, M, L, N, K, 1, N,
+                absmax_prev, Y, nullptr, Cst, stats, absmax_out_host, range_flag_out_host, stream);
 }
 
 int ramp_op_tklb(const float* dqkv, const float* W, const float* z, const float* ln_g, const float* add, int32_t M,
@@ -556,6 +584,14 @@ int ramp_op_groupnorm(const float* x, const float* gamma, const float* beta, con
   RAMP_REQUIRE(x && gamma && beta && y, "null argument");
   GnArgs g; g.x = x; g.gamma = gamma; g.beta = beta; g.tbias = tbias; g.resid = resid; g.y = y; g.stats = stats;
   g.R = R; g.L = L; g.C = C; g.eps = eps; g.mish = mish;
+  return launch_gn_fwd(g, as_stream(stream));
+}
+int ramp_op_groupnorm_rows(const float* x, const float* gamma, const float* beta, const float* time_table, int32_t tt_stride,
+                           const int32_t* t_rows, const float* resid, float* y, float* stats, int32_t R, int32_t L, int32_t C, float eps,
+                           int32_t mish, void* stream) {
+  RAMP_REQUIRE(x && gamma && beta && y && time_table && t_rows && tt_stride >= C, "null argument");
+  GnArgs g; g.x = x; g.gamma = gamma; g.beta = beta; g.tbias = time_table; g.t_rows = t_rows; g.tt_stride = tt_stride; g.resid = resid; g.y = y;
+  g.stats = stats; g.R = R; g.L = L; g.C = C; g.eps = eps; g.mish = mish;
   return launch_gn_fwd(g, as_stream(stream));
 }
 int ramp_op_groupnorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, const float* beta,

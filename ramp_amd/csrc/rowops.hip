@@ -97,7 +97,7 @@ __global__ __launch_bounds__(256) void gn_fwd_kernel(GnArgs a) {
   const f32x4 gam = reinterpret_cast<const f32x4*>(a.gamma)[c4];
   const f32x4 bet = reinterpret_cast<const f32x4*>(a.beta)[c4];
   f32x4 tb = {0, 0, 0, 0};
-  if (a.tbias) tb = reinterpret_cast<const f32x4*>(a.tbias)[c4];
+  if (a.tbias) tb = reinterpret_cast<const f32x4*>(a.t_rows ? a.tbias + (size_t)a.t_rows[row] * a.tt_stride : a.tbias)[c4];   // (per-row timesteps: this row's table line)
   f32x4* yr = reinterpret_cast<f32x4*>(a.y + (long)row * a.L * a.C);
   const f32x4* rr = a.resid ? reinterpret_cast<const f32x4*>(a.resid + (long)row * a.L * a.C) : nullptr;
 #pragma unroll
@@ -216,7 +216,7 @@ __global__ __launch_bounds__(256) void gn_fwd_c16_kernel(GnArgs a) {
   const f32x4 gam = reinterpret_cast<const f32x4*>(a.gamma)[c4];
   const f32x4 bet = reinterpret_cast<const f32x4*>(a.beta)[c4];
   f32x4 tb = {0, 0, 0, 0};
-  if (a.tbias) tb = reinterpret_cast<const f32x4*>(a.tbias)[c4];
+  if (a.tbias) tb = reinterpret_cast<const f32x4*>(a.t_rows ? a.tbias + (size_t)a.t_rows[row] * a.tt_stride : a.tbias)[c4];   // (per-row timesteps: this row's table line)
   f32x4* yr = reinterpret_cast<f32x4*>(a.y + (long)row * a.L * 16);
   const f32x4* rr = a.resid ? reinterpret_cast<const f32x4*>(a.resid + (long)row * a.L * 16) : nullptr;
 #pragma unroll
@@ -297,6 +297,7 @@ static int gn_check(int R, int L, int C) {
 }
 int launch_gn_fwd(const GnArgs& a, hipStream_t s) {
   if (int e = gn_check(a.R, a.L, a.C)) return e;
+  RAMP_REQUIRE(!a.t_rows || (a.tbias && a.tt_stride > 0 && a.tt_stride % 4 == 0), "GroupNorm: a row -> timestep table needs the time table and its stride (a multiple of 4 floats)");
   if (a.C == 16) hipLaunchKernelGGL(gn_fwd_c16_kernel, dim3(a.R), dim3(256), 0, s, a);
   else if (a.C == 512) hipLaunchKernelGGL(gn_fwd_kernel<true>, dim3(a.R), dim3(256), 0, s, a);
   else hipLaunchKernelGGL(gn_fwd_kernel<false>, dim3(a.R), dim3(256), 0, s, a);

@@ -129,6 +129,34 @@ int launch_ddim_finish(const float* x_in, const float* x0, float sqrt_a_t, float
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
+// q_sample per row + endpoint pinning (the training-side forward process, diffusion_model_static.py:467-486): the reference's
+// extract(a, t) * x_start + extract(b, t) * noise, two products and one sum in fp32 (this file is built without FMA contraction)
+__global__ __launch_bounds__(256)
+void q_sample_rows_kernel(const float* __restrict__ x_start, const float* __restrict__ noise, const float* __restrict__ sqrt_ac,
+                          const float* __restrict__ sqrt_1m_ac, const int* __restrict__ t_rows, int T, float* __restrict__ x_noisy,
+                          int B, int H, int S, int pin) {
+  const long n = (long)B * H * S, HS = (long)H * S;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const int b = (int)(i / HS), h = (int)((i - (long)b * HS) / S);
+    const int t = t_rows[b];
+    const float x = x_start[i];
+    float v;
+    if (pin && (h == 0 || h == H - 1)) v = x;
+    else if (t < 0 || t >= T) v = __builtin_nanf("");
+    else v = sqrt_ac[t] * x + sqrt_1m_ac[t] * noise[i];
+    x_noisy[i] = v;
+  }
+}
+int launch_q_sample_rows(const float* x_start, const float* noise, const float* sqrt_ac, const float* sqrt_1m_ac, const int* t_rows, int T,
+                         float* x_noisy, int B, int H, int S, int pin, hipStream_t s) {
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0 && T > 0, "bad q_sample dims");
+  const long n = (long)B * H * S;
+  const int nblk = (int)std::min<long>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(q_sample_rows_kernel, dim3(nblk), dim3(256), 0, s, x_start, noise, sqrt_ac, sqrt_1m_ac, t_rows, T, x_noisy, B, H, S, pin);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_hard_cond(float* x, HardConds hc, int B, int H, int S, hipStream_t s) {
   if (hc.n == 0) return 0;
   hipLaunchKernelGGL(hard_cond_kernel, dim3(ew_grid((long)hc.n * B * S)), dim3(256), 0, s, x, hc, B, H, S);

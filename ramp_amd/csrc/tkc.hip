@@ -77,7 +77,9 @@ size_t tkc_packed_halves(int N, int K) { return (size_t)5 * (N / 16) * (K / 32) 
 // tkw.hip -- EPI: Cst = conv + bias (the stash), its statistics, Y = mish(GN(Cst)) + time bias + residual; PRO: the operand is the GroupNorm + Mish input
 // gradient GNbwd(X (.) mish'(gamma x^ + beta) gamma) of the forward layer's stash gn_c.  A wave owns whole samples and ALL channels, so both reductions
 // (over a sample's tokens x a group's C / 8 channels) stay inside the wave: in-lane over the four channels of a register quad, one shuffle for the second
-// quad of an 8-channel group, the tokens through 2 KB of wave-private scratch.
+// quad of an 8-channel group, the tokens through 2 KB of wave-private scratch.  EPI 2 = EPI 1 with per-row timesteps (TkcArgs::t_rows): the time-bias
+// quad is read per (channel block, token) from the table line of the token's sample instead of once per channel block; an instantiation of its own, so
+// that a launch without a row table runs exactly the EPI 1 code.
 template <int NG, int NB, int KS, int PRO, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2)))
 void tkc_kernel(TkcArgs a, int n_tiles) {
@@ -291,6 +293,13 @@ void tkc_kernel(TkcArgs a, int n_tiles) {
       unsigned trow[NG];
 #pragma unroll
       for (int t = 0; t < NG; ++t) trow[t] = (unsigned)min(tok0 + 16 * t + c, m_last);
+      // EPI 2: the time-table line of each token's sample (tok0 is a multiple of T, L | T: sample = tok0 / L + smp; samples past M read the last one's)
+      const float* tline[EPI == 2 ? NG : 1];
+      if constexpr (EPI == 2) {
+        const int s0 = tok0 / a.L, s_last = a.M / a.L - 1;
+#pragma unroll
+        for (int t = 0; t < NG; ++t) tline[t] = a.tbias + (size_t)a.t_rows[min(s0 + smp[t], s_last)] * (size_t)a.tt_stride + 4 * g;
+      }
       float mean[4][NG], var[4][NG];
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
@@ -316,9 +325,10 @@ void tkc_kernel(TkcArgs a, int n_tiles) {
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
         const f32x4 gam = *reinterpret_cast<const f32x4*>(a.gamma + 16 * nb + 4 * g), bet = *reinterpret_cast<const f32x4*>(a.beta + 16 * nb + 4 * g);
-        const f32x4 tb = a.tbias ? *reinterpret_cast<const f32x4*>(a.tbias + 16 * nb + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 tb = (EPI == 1 && a.tbias) ? *reinterpret_cast<const f32x4*>(a.tbias + 16 * nb + 4 * g) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int t = 0; t < NG; ++t) {
+          if constexpr (EPI == 2) tb = *reinterpret_cast<const f32x4*>(tline[t] + 16 * nb);
           const float rstd = 1.f / sqrtf(var[nb][t] + a.eps);
           const bool live = full || tok0 + 16 * t + c < a.M;
           // one writer per (sample, group): the sample's first token, the group's first register quad
@@ -418,7 +428,8 @@ int launch_tkc(const TkcArgs& a, hipStream_t s) {
   RAMP_REQUIRE((long)a.M * a.ldx * 4 < (1l << 32), "tkc: 32-bit row offsets");
   RAMP_REQUIRE(!ranges_overlap(a.Y, ((size_t)(a.M - 1) * a.ldy + a.N) * 4, a.X, ((size_t)(a.M - 1) * a.ldx + a.K) * 4), "tkc: the output must not overlap the operand");
   const int T = 16 * ng, n_tiles = (a.M + 4 * T - 1) / (4 * T);
-  const int pro = a.gn_c ? 1 : 0, epi = a.Cst ? 1 : 0;
+  const int pro = a.gn_c ? 1 : 0, epi = a.Cst ? (a.t_rows ? 2 : 1) : 0;
+  RAMP_REQUIRE(!a.t_rows || (a.Cst && a.tbias && a.tt_stride > 0 && a.tt_stride % 4 == 0), "tkc: a row -> timestep table needs the GroupNorm epilogue, the time table and its stride (a multiple of 4 floats)");
   RAMP_REQUIRE(!(pro && epi), "tkc: the GroupNorm backward operand and the GroupNorm epilogue do not occur together");
   if (pro) RAMP_REQUIRE(a.gn_stats && a.gn_gamma && a.gn_beta && al16(a.gn_c) && al16(a.gn_gamma) && al16(a.gn_beta) && a.ldx >= a.K, "tkc: GroupNorm-backward operand incomplete");
   if (epi) RAMP_REQUIRE(a.stats && a.gamma && a.beta && a.bias && !a.resid2 && al16(a.Cst) && al16(a.gamma) && al16(a.beta) && al16(a.tbias), "tkc: GroupNorm epilogue incomplete");
@@ -430,6 +441,7 @@ int launch_tkc(const TkcArgs& a, hipStream_t s) {
 #define TC_CASE(NGV) \
   if (ng == NGV) { \
     if (pro) { TC_SHAPE(NGV, 1, 0) } \
+    if (epi == 2) { TC_SHAPE(NGV, 0, 2) } \
     if (epi) { TC_SHAPE(NGV, 0, 1) } \
     TC_SHAPE(NGV, 0, 0) \
   }
@@ -447,7 +459,7 @@ int launch_tkc(const TkcArgs& a, hipStream_t s) {
 
 int init_tkc_attributes() {
 #define TC_ATTR1(NGV, NBV, KSV, PROV, EPIV) RAMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tkc_kernel<NGV, NBV, KSV, PROV, EPIV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tkc_lds<NGV, NBV, KSV>()))
-#define TC_ATTR(NGV, NBV, KSV) TC_ATTR1(NGV, NBV, KSV, 0, 0); TC_ATTR1(NGV, NBV, KSV, 1, 0); TC_ATTR1(NGV, NBV, KSV, 0, 1)
+#define TC_ATTR(NGV, NBV, KSV) TC_ATTR1(NGV, NBV, KSV, 0, 0); TC_ATTR1(NGV, NBV, KSV, 1, 0); TC_ATTR1(NGV, NBV, KSV, 0, 1); TC_ATTR1(NGV, NBV, KSV, 0, 2)
   TC_ATTR(3, 4, 2); TC_ATTR(3, 4, 1); TC_ATTR(3, 2, 2); TC_ATTR(3, 2, 1);
   TC_ATTR(2, 4, 2); TC_ATTR(2, 4, 1); TC_ATTR(2, 2, 2); TC_ATTR(2, 2, 1);
   TC_ATTR(4, 4, 1); TC_ATTR(4, 2, 2); TC_ATTR(4, 2, 1);

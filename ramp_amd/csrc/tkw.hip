@@ -60,8 +60,12 @@ struct TwGeom { int KC, n_chunks, rows, xrow, n_pass; size_t lds; };
 
 // MB: 32-channel blocks of a wave per pass (1: N = 128, 2: N = 256 / 512 / 1024); PRO > 0: GroupNorm backward folded into the operand, PRO = the
 // wave instructions of RP rows of one staging pass (3, 4, 6, 8: whole samples); EPI 1: GroupNorm + Mish behind the convolution (N <= 256: a group
-// is one 32-channel block or half of one); EPI 2: the same at N = 512 (two passes of 256; a group = the wave's 64 channels of the pass)
-template <int MB, int PRO, int EPI>
+// is one 32-channel block or half of one); EPI 2: the same at N = 512 (two passes of 256; a group = the wave's 64 channels of the pass);
+// RT (EPI 1 / 2 with per-row timesteps, TkwArgs::t_rows): a tile holds up to 32 samples, each with a time-table line of its own, so the time bias
+// is not staged in prm but read in the epilogue -- one 16-byte load per (token, channel quad) from the L2-resident table, where the residual is
+// read the same way; no LDS beyond today's 80 KB, three more address registers.  Instantiations of their own: without a row table the kernels are
+// the ones they were.
+template <int MB, int PRO, int EPI, bool RT>
 __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -420,6 +424,8 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
         for (int tg = 0; tg < TW_NT; ++tg) {
           const int t = tok0 + 32 * tg + tok;
           const int tk = min(t, m_last);
+          const float* tline = nullptr;                      // RT: the table line of this token's sample (tokens past M read the last sample's)
+          if constexpr (RT) tline = a.tbias + (size_t)a.t_rows[min(tok0 / a.L + divL(32 * tg + tok), m_last / a.L)] * (size_t)a.tt_stride;
 #pragma unroll
           for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -430,7 +436,8 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
               f32x4 v;
 #pragma unroll
               for (int j = 0; j < 4; ++j) v[j] = tw_mish((acc[mb][tg][4 * q + j] - mean_t[gi][tg]) * rstd_t[gi][tg] * gam[j] + bet[j]);
-              v += *reinterpret_cast<const f32x4*>(prm + 768 + n - poff);
+              if constexpr (RT) v += *reinterpret_cast<const f32x4*>(tline + n);
+              else v += *reinterpret_cast<const f32x4*>(prm + 768 + n - poff);
               if (a.resid) v += *reinterpret_cast<const f32x4*>(a.resid + (size_t)tk * a.ldr + n);
               if (t < a.M && !(a.ablate & 4)) *reinterpret_cast<f32x4*>(a.Y + (size_t)tk * a.ldy + n) = v;
             }
@@ -447,10 +454,14 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
 // 256 registers per lane everywhere: two blocks share a CU (tw_geometry)
 template <int PRO, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void tkw_kernel1(TkwArgs a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) { tkw_body<1, PRO, EPI>(a, n_tiles, kc32, n_chunks, n_rows, n_pass, mulL); }
+void tkw_kernel1(TkwArgs a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) { tkw_body<1, PRO, EPI, false>(a, n_tiles, kc32, n_chunks, n_rows, n_pass, mulL); }
 template <int PRO, int EPI>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
-void tkw_kernel2(TkwArgs a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) { tkw_body<2, PRO, EPI>(a, n_tiles, kc32, n_chunks, n_rows, n_pass, mulL); }
+void tkw_kernel2(TkwArgs a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) { tkw_body<2, PRO, EPI, false>(a, n_tiles, kc32, n_chunks, n_rows, n_pass, mulL); }
+// the forward kernels with per-row timesteps (RT): kernels of their own names, so the ones above stay the instantiations they were
+template <int MB, int EPI>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void tkw_rows_kernel(TkwArgs a, int n_tiles, int kc32, int n_chunks, int n_rows, int n_pass, int mulL) { tkw_body<MB, 0, EPI, true>(a, n_tiles, kc32, n_chunks, n_rows, n_pass, mulL); }
 
 namespace {
 
@@ -489,11 +500,12 @@ int tw_pro_variant(int L, int N, int K) {
   return 0;
 }
 
-template <int MB, int PRO, int EPI> int tkw_go(const TkwArgs& a, const TwGeom& g, hipStream_t s) {
+template <int MB, int PRO, int EPI, bool RT = false> int tkw_go(const TkwArgs& a, const TwGeom& g, hipStream_t s) {
   const int n_tiles = (a.M + TW_TB - 1) / TW_TB;
   const int per_cu = g.lds * 2 <= 160 * 1024 ? 2 : 1;        // (all variants compile to <= 256 registers: two waves per SIMD)
   const int nb = std::min(n_tiles, per_cu * device_cu_count());
-  if (MB == 1) hipLaunchKernelGGL((tkw_kernel1<PRO, EPI>), dim3(nb), dim3(256), g.lds, s, a, n_tiles, g.KC >> 5, g.n_chunks, g.rows, g.n_pass, (65536 + a.L - 1) / a.L);
+  if constexpr (RT) hipLaunchKernelGGL((tkw_rows_kernel<MB, EPI ? EPI : 1>), dim3(nb), dim3(256), g.lds, s, a, n_tiles, g.KC >> 5, g.n_chunks, g.rows, g.n_pass, (65536 + a.L - 1) / a.L);
+  else if (MB == 1) hipLaunchKernelGGL((tkw_kernel1<PRO, EPI>), dim3(nb), dim3(256), g.lds, s, a, n_tiles, g.KC >> 5, g.n_chunks, g.rows, g.n_pass, (65536 + a.L - 1) / a.L);
   else hipLaunchKernelGGL((tkw_kernel2<PRO, EPI>), dim3(nb), dim3(256), g.lds, s, a, n_tiles, g.KC >> 5, g.n_chunks, g.rows, g.n_pass, (65536 + a.L - 1) / a.L);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
@@ -528,12 +540,17 @@ int launch_tkw(const TkwArgs& a, hipStream_t s) {
                a.ldy % 4 == 0 && a.ldy2 % 4 == 0 && a.ldr % 4 == 0 && a.ldr2 % 4 == 0, "tkw: operands must be 16-byte aligned");
   if (pro) RAMP_REQUIRE(a.gn_stats && a.gn_gamma && a.gn_beta && a.ldx >= a.K, "tkw: GroupNorm-backward operand incomplete");
   if (epi) RAMP_REQUIRE(a.stats && a.gamma && a.beta && a.bias && !a.resid2 && a.ldy >= a.N, "tkw: GroupNorm epilogue incomplete");
+  RAMP_REQUIRE(!a.t_rows || (epi && a.tbias && a.tt_stride > 0 && a.tt_stride % 4 == 0), "tkw: a row -> timestep table needs the GroupNorm epilogue, the time table and its stride (a multiple of 4 floats)");
   const size_t ybytes = ((size_t)(a.M - 1) * a.ldy + a.N1) * 4, xbytes = ((size_t)(a.M - 1) * a.ldx + a.K1) * 4;
   RAMP_REQUIRE(!ranges_overlap(a.Y, ybytes, a.X, xbytes), "tkw: the output must not overlap the operand");
   RAMP_REQUIRE(!epi || !ranges_overlap(a.Cst, (size_t)a.M * a.N * 4, a.X, xbytes), "tkw: the stash must not overlap the operand");
   const int mbv = a.N == 128 ? 1 : 2;
   const int prov = pro ? tw_pro_variant(a.L, a.N, a.K) : 0;
   const int epv = epi ? (a.N == 512 ? 2 : 1) : 0;
+  if (a.t_rows) {
+    if (mbv == 1) return tkw_go<1, 0, 1, true>(a, g, s);
+    return epv == 2 ? tkw_go<2, 0, 2, true>(a, g, s) : tkw_go<2, 0, 1, true>(a, g, s);
+  }
 #define TW_CASE(MBV, PROV, EPIV) if (mbv == MBV && prov == PROV && epv == EPIV) return tkw_go<MBV, PROV, EPIV>(a, g, s);
   TW_CASE(1, 0, 0) TW_CASE(1, 0, 1) TW_CASE(1, 3, 0) TW_CASE(1, 4, 0) TW_CASE(1, 6, 0) TW_CASE(1, 8, 0)
   TW_CASE(2, 0, 0) TW_CASE(2, 0, 1) TW_CASE(2, 0, 2) TW_CASE(2, 3, 0) TW_CASE(2, 4, 0) TW_CASE(2, 6, 0) TW_CASE(2, 8, 0)
@@ -546,6 +563,9 @@ int init_tkw_attributes() {
   TW_ATTR(tkw_kernel1, 0, 0); TW_ATTR(tkw_kernel1, 0, 1); TW_ATTR(tkw_kernel1, 3, 0); TW_ATTR(tkw_kernel1, 4, 0); TW_ATTR(tkw_kernel1, 6, 0); TW_ATTR(tkw_kernel1, 8, 0);
   TW_ATTR(tkw_kernel2, 0, 0); TW_ATTR(tkw_kernel2, 0, 1); TW_ATTR(tkw_kernel2, 0, 2); TW_ATTR(tkw_kernel2, 3, 0); TW_ATTR(tkw_kernel2, 4, 0); TW_ATTR(tkw_kernel2, 6, 0); TW_ATTR(tkw_kernel2, 8, 0);
 #undef TW_ATTR
+#define TW_ATTR_RT(MBV, EPIV) RAMP_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tkw_rows_kernel<MBV, EPIV>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024))
+  TW_ATTR_RT(1, 1); TW_ATTR_RT(2, 1); TW_ATTR_RT(2, 2);
+#undef TW_ATTR_RT
   return 0;
 }
 

@@ -114,6 +114,9 @@ class _GaussianDiffusionBase(nn.Module):
         alphas_cumprod_prev = torch.cat([torch.ones(1), alphas_cumprod[:-1]])
         self.clip_denoised = clip_denoised
         self.predict_epsilon = predict_epsilon
+        # the denoising loss (loss / p_losses): 'l2' (the reference default) and 'l1' are served, helpers.py:71-100; anything else is
+        # refused when a loss is asked for, not here -- the sampling configs pass whatever their training run used
+        self.loss_type = loss_type
         self.register_buffer('betas', betas)
         self.register_buffer('alphas_cumprod', alphas_cumprod)
         self.register_buffer('alphas_cumprod_prev', alphas_cumprod_prev)
@@ -703,6 +706,68 @@ class StaticGaussianDiffusionModel(_GaussianDiffusionBase):
     _default_cfg_weight = 2.0          # diffusion_model_static.py:163
     _default_compose = (2.0, 2.0)      # diffusion_model_static.py:205
     _default_ddim = True               # diffusion_model_static.py:41
+
+    # ------------------------------------------------------------------ the denoising loss (evaluation only)
+    def _rows_t(self, t, B: int) -> torch.Tensor:
+        """t (B,) -> device int32, every entry checked against the schedule on the host (no kernel indexes with an unchecked value)."""
+        tv = t.detach().reshape(-1).to("cpu", torch.int64)
+        if tv.numel() != B:
+            raise ValueError(f"`t` must hold one timestep per row ({B}); got {tv.numel()}")
+        if int(tv.min()) < 0 or int(tv.max()) >= self.n_diffusion_steps:
+            raise ValueError(f"timesteps must lie in [0, {self.n_diffusion_steps}); got [{int(tv.min())}, {int(tv.max())}]")
+        return tv.to(self._device(), torch.int32)
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None, pin_endpoints: bool = False):
+        """diffusion_model_static.py:467-476: sqrt(acp[t]) x_start + sqrt(1 - acp[t]) noise with one t per row, in one launch
+        (ramp_q_sample_rows).  ``pin_endpoints`` also overwrites waypoints 0 and H - 1 with x_start's in that launch (p_losses, :483-484)."""
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        dev = self._device()
+        xs = x_start.detach().to(dev, torch.float32).contiguous()
+        nz = noise.detach().to(dev, torch.float32).contiguous()
+        B, H, S = xs.shape
+        tr = self._rows_t(t, B)
+        out = torch.empty_like(xs)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ramp_q_sample_rows(_lib.ptr(xs), _lib.ptr(nz), _lib.ptr(self.sqrt_alphas_cumprod),
+                                                      _lib.ptr(self.sqrt_one_minus_alphas_cumprod), _lib.ptr(tr), self.n_diffusion_steps,
+                                                      _lib.ptr(out), B, H, S, int(bool(pin_endpoints)), _lib.current_stream()),
+                       "ramp_q_sample_rows")
+        return out
+
+    @torch.no_grad()
+    def p_losses(self, x_start, context, t, hard_conds, obstacle_pts, noise=None):
+        """diffusion_model_static.py:478-505 in eval mode: the denoising loss of the loaded network on x_start at one timestep per
+        row.  Returns (loss, info) like the reference, loss a 0-d float32 tensor, info = {'x_noisy', 'x_recon'} (the reference's is
+        empty).  ``noise=`` supplies the draw (the reference draws torch.randn_like itself)."""
+        if self.training:
+            raise NotImplementedError("p_losses in training mode: parameter gradients are out of scope here; call .eval() first")
+        if self.loss_type not in ("l2", "l1"):
+            raise NotImplementedError(f"loss_type {self.loss_type!r}: only 'l2' and 'l1' are served (helpers.py:91-100)")
+        if noise is None:
+            noise = torch.randn_like(x_start)
+        dev = self._device()
+        xs = x_start.detach().to(dev, torch.float32).contiguous()
+        nz = noise.detach().to(dev, torch.float32).contiguous()
+        B, H, S = xs.shape
+        x_noisy = self.q_sample(xs, t, nz, pin_endpoints=True)
+        if context is not None:
+            context = self.context_model(context)
+        x_recon = self.model(x_noisy, t, context, obstacle_pts=obstacle_pts).contiguous()
+        target = nz if self.predict_epsilon else xs
+        scratch = torch.empty(1024, device=dev, dtype=torch.float64)
+        out = torch.empty(1, device=dev, dtype=torch.float64)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ramp_denoise_loss(_lib.ptr(x_recon), _lib.ptr(xs), _lib.ptr(target), B, H, S,
+                                                     int(self.loss_type == "l1"), _lib.ptr(scratch), _lib.ptr(out),
+                                                     _lib.current_stream()), "ramp_denoise_loss")
+        return out[0].to(torch.float32), {"x_noisy": x_noisy, "x_recon": x_recon, "loss64": out[0]}
+
+    def loss(self, x, context, *args, **kwargs):
+        """diffusion_model_static.py:507-511: t = randint(0, T, (B,)) per row, then p_losses(x, context, t, hard_conds, obstacle_pts)."""
+        t = torch.randint(0, self.n_diffusion_steps, (x.shape[0],), device=x.device).long()
+        return self.p_losses(x, context, t, *args, **kwargs)
 
 
 class GaussianDiffusionModel3d(_GaussianDiffusionBase):

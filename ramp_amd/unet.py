@@ -275,23 +275,22 @@ class TemporalUnetInference(nn.Module):
         if obstacle_pts is None:
             raise ValueError("obstacle_pts is required (the reference dereferences it unconditionally)")
         x = x.detach().to(self._device(), torch.float32).contiguous()
-        if torch.is_tensor(time):
-            tv = time.reshape(-1)
-            # the time-conditioning tables are per step, not per row: the samplers always pass make_timesteps'
-            # batch-uniform vector (diffusion_model_static.py:16-18); per-row timesteps are refused, not ignored
-            if tv.numel() > 1 and not bool((tv == tv[0]).all()):
-                raise ValueError("per-row timesteps are not supported: `time` must be uniform over the batch")
-            t = int(tv[0])
-        else:
-            t = int(time)
-        self.prepare_time_table(max(t + 1, self._T_table, 1))
-        self.cache_scene_encoding(obstacle_pts, compose)
         n = x.shape[0]
+        # the samplers pass make_timesteps' batch-uniform vector (diffusion_model_static.py:16-18): one table line for the whole
+        # launch (ramp_score).  One timestep per row (UnetInference.py:198; p_losses' randint draw) picks the line per row
+        # (ramp_score_rows); the table arithmetic is the same
+        t, rows = _split_time(time, n)
+        self.prepare_time_table(max((t if rows is None else int(rows.max())) + 1, self._T_table, 1))
+        self.cache_scene_encoding(obstacle_pts, compose)
         f = torch.empty_like(x) if want_f else None
         eps = torch.empty_like(x) if want_eps else None
         with torch.cuda.device(self._device()):
-            _lib.check(_lib.load().ramp_score(self.ctx(), _lib.ptr(x), n, 1, t, _lib.ptr(f), _lib.ptr(eps),
-                                              _lib.current_stream()), "ramp_score")
+            if rows is None:
+                _lib.check(_lib.load().ramp_score(self.ctx(), _lib.ptr(x), n, 1, t, _lib.ptr(f), _lib.ptr(eps),
+                                                  _lib.current_stream()), "ramp_score")
+            else:
+                _lib.check(_lib.load().ramp_score_rows(self.ctx(), _lib.ptr(x), n, 1, rows.ctypes.data_as(_lib.c_i32p), _lib.ptr(f),
+                                                       _lib.ptr(eps), _lib.current_stream()), "ramp_score_rows")
         return f, eps
 
     def forward(self, x, time, context, x_start=None, obstacle_pts=None, forward_t=None, compose=False):
@@ -334,6 +333,27 @@ class TemporalUnetInference(nn.Module):
         n = C.c_int64()
         _lib.check(_lib.load().ramp_launch_count(self.ctx(), C.byref(n)))
         return n.value
+
+
+def _split_time(time, n_rows: int):
+    """`time` of a forward call -> (t, None) when one timestep serves every row (an int, a one-element or a uniform tensor), else
+    (None, rows) with rows the host int32 array of one timestep per row.  A tensor whose length is neither 1 nor the row count,
+    or a negative timestep, is refused here; the upper bound is the prepared table's and is checked by the library."""
+    if not torch.is_tensor(time) and not isinstance(time, np.ndarray):
+        t = int(time)
+        if t < 0:
+            raise ValueError(f"timestep must be non-negative; got {t}")
+        return t, None
+    tv = np.ascontiguousarray(time.detach().cpu().numpy() if torch.is_tensor(time) else time).reshape(-1)
+    if tv.size not in (1, n_rows):
+        raise ValueError(f"`time` must hold one timestep or one per row ({n_rows}); got {tv.size}")
+    if tv.dtype.kind not in "iu":
+        tv = tv.astype(np.int64)              # (a float `time` is truncated like int(time) always was)
+    if int(tv.min()) < 0:
+        raise ValueError(f"timesteps must be non-negative; got {int(tv.min())}")
+    if bool((tv == tv[0]).all()):
+        return int(tv[0]), None
+    return None, tv.astype(np.int32)
 
 
 def load_numpy_state_dict(model: nn.Module, sd: Dict[str, np.ndarray], prefix: str = ""):
