@@ -1429,13 +1429,7 @@ int ramp_finalize_weights(ramp_ctx* c) {
       }
       float* q3 = nullptr; float wsi = 1.f;
       if (q && c->gemm_mode == 2) {
-        // static power-of-two weight scale: max |w| -> [2^10, 2^11)
-        std::vector<float> hw(n);
-        RAMP_HIP_CHECK(hipMemcpy(hw.data(), w, n * sizeof(float), hipMemcpyDeviceToHost));
-        float mx = 0.f;
-        for (float v : hw) mx = std::max(mx, std::fabs(v));
-        float sc = 1.f;
-        if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }   // mx in [2^(e-1), 2^e)
+        float sc = 1.f; CK(device_weight_scale(w, n, &sc));          // static power-of-two weight scale: max |w| -> [2^10, 2^11)
         CK(dev_alloc(c, &q3, n + 4));
         CK(launch_pack_h3(w, reinterpret_cast<unsigned short*>(q3), (long)(n / K), K, sc, 0));
         wsi = 1.f / sc;
@@ -1525,12 +1519,7 @@ int ramp_finalize_weights(ramp_ctx* c) {
       auto reg_tkc = [&](const float* w, int N, int K) -> int {
         if (!w || c->tkc_w.count(w) || !((N == 32 || N == 64) && (K == 32 || K == 64))) return 0;
         const size_t n = 5ul * N * K;
-        std::vector<float> hw(n);
-        RAMP_HIP_CHECK(hipMemcpy(hw.data(), w, n * sizeof(float), hipMemcpyDeviceToHost));
-        float mx = 0.f;
-        for (float v : hw) mx = std::max(mx, std::fabs(v));
-        float sc = 1.f;
-        if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
+        float sc = 1.f; CK(device_weight_scale(w, n, &sc));
         float* q; CK(dev_alloc(c, &q, tkc_packed_halves(N, K) / 2 + 4));
         CK(tkc_pack(w, N, K, sc, reinterpret_cast<unsigned short*>(q), 0));
         c->tkc_w[w] = {reinterpret_cast<unsigned short*>(q), 1.f / sc};
@@ -1866,12 +1855,9 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   int sc_points = 0;
   if (sc) {
     RAMP_REQUIRE(!p->apf.cloud, "ramp_sample_scenes: apf.cloud must be NULL (the clouds come with the scene batch)");
-    RAMP_REQUIRE(sc->n_scenes >= 1 && sc->traj_scene, "ramp_sample_scenes: bad scene batch");
+    CK(check_scene_batch(sc, sc_apf, "ramp_sample_scenes"));
   }
   if (sc_apf) {
-    RAMP_REQUIRE(sc->cloud_offset_host && sc->cloud_offset_host[0] == 0, "ramp_sample_scenes: cloud offsets must start at 0");
-    for (int i = 0; i < sc->n_scenes; ++i)
-      RAMP_REQUIRE(sc->cloud_offset_host[i + 1] > sc->cloud_offset_host[i], "ramp_sample_scenes: every scene needs at least one cloud point (increasing offsets)");
     sc_points = sc->cloud_offset_host[sc->n_scenes];
     CK(stage_apf(c, p->apf, sc->cloud_points, sc_points, s));
     CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));

@@ -1,9 +1,10 @@
 // Helpers shared by the three host translation units behind the C ABI -- engine.hip (context, weight packing, the network schedule, sampler
 // loops, graph capture), ops.hip (the context-free kernel-level entry points ramp_apf ... ramp_op_*) and bench.hip (the micro-benchmark /
 // stress harness, linked into the tools library only) -- as internal-linkage definitions: small device kernels, the device arena, the
-// weight packing of the fused feed-forward on raw fp32 weights.
+// fp16x3 weight scale of a device weight, the check of a scene batch, the weight packing of the fused feed-forward on raw fp32 weights.
 #pragma once
 #include "common.h"
+#include "weight_scale.h"
 #include "../../include/ramp_hip.h"
 
 #include <algorithm>
@@ -84,13 +85,35 @@ struct DevArena {
   }
 };
 
+// the static fp16x3 scale (fp16_weight_scale, weight_scale.h) of a device weight of n floats: one download and a host max |w|
+int device_weight_scale(const float* w_dev, size_t n, float* scale) {
+  std::vector<float> hw(n);
+  RAMP_HIP_CHECK(hipMemcpy(hw.data(), w_dev, n * sizeof(float), hipMemcpyDeviceToHost));
+  float mx = 0.f;
+  for (float v : hw) mx = std::max(mx, std::fabs(v));
+  *scale = fp16_weight_scale(mx);
+  return 0;
+}
+
+// what ramp_sample_scenes and ramp_apf_scenes (`who`) require of a scene batch: at least one scene and the trajectory -> scene table;
+// where the per-scene clouds are used (need_cloud), the points and host offsets that start at 0 and give every scene a point
+int check_scene_batch(const ramp_scene_batch* sc, bool need_cloud, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(sc && sc->n_scenes >= 1 && sc->traj_scene, w + "bad scene batch (at least one scene, a trajectory -> scene table)");
+  if (!need_cloud) return 0;
+  RAMP_REQUIRE(sc->cloud_points && sc->cloud_offset_host && sc->cloud_offset_host[0] == 0, w + "bad scene batch (cloud points, offsets from 0)");
+  for (int i = 0; i < sc->n_scenes; ++i)
+    RAMP_REQUIRE(sc->cloud_offset_host[i + 1] > sc->cloud_offset_host[i], w + "every scene needs at least one cloud point (increasing offsets)");
+  return 0;
+}
+
 
 }  // namespace
 }  // namespace ramp
 
 using namespace ramp;
 
-// ---- the token-owning fused feed-forward (ffx.hip) on raw fp32 weights: packs exactly as ramp_finalize_weights does --------
+// ---- the token-owning fused feed-forward (ffx.hip) on raw fp32 weights: packs as ramp_finalize_weights does, with its scale function ---
 namespace {
 struct FfxPack {
   unsigned short *stream_f = nullptr, *stream_b = nullptr;   // 96 x 32 KB each
@@ -98,16 +121,8 @@ struct FfxPack {
 };
 // W1 [2048][256] (rows: 1024 a then 1024 g), W2 [256][1024]; everything allocated from `ar`
 int ffx_pack_all(DevArena& ar, const float* W1, const float* b1, const float* W2, FfxPack* out, hipStream_t s, bool s16 = false) {
-  auto maxabs = [&](const float* d, size_t n, float* sc) -> int {
-    std::vector<float> hw(n);
-    RAMP_HIP_CHECK(hipMemcpy(hw.data(), d, n * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f; for (float v : hw) mx = std::max(mx, std::fabs(v));
-    *sc = 1.f;
-    if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); *sc = std::ldexp(1.f, 11 - e); }
-    return 0;
-  };
   float sc1 = 1.f, sc2 = 1.f;
-  CK(maxabs(W1, 2048 * 256, &sc1)); CK(maxabs(W2, 256 * 1024, &sc2));
+  CK(device_weight_scale(W1, 2048 * 256, &sc1)); CK(device_weight_scale(W2, 256 * 1024, &sc2));
   float* w1_pk = ar.alloc(2048 * 256); out->b1_pk = ar.alloc(2048);
   float* w1t = ar.alloc(2048 * 256); float* w2t = ar.alloc(1024 * 256); float* tmp = ar.alloc(2048 * 256);
   auto planes = [&](size_t n) { return reinterpret_cast<unsigned short*>(ar.alloc(n + 4)); };   // 2 n halves

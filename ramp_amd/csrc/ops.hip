@@ -1,57 +1,77 @@
 // The context-free kernel-level entry points of the C ABI (include/ramp_hip.h): ramp_apf ... ramp_ddim_finish (what the Python mirror of the
 // reference's helper functions calls one kernel at a time) and the ramp_op_* unit entry points the parity tests drive every kernel family through
-// (each packs its weights from raw fp32 exactly as ramp_finalize_weights does).  Split from engine.hip in round 6: an edit of a kernel family's
-// argument struct rebuilds this file and its own, not the sampler.
+// (each packs its weights from raw fp32 with the scale function ramp_finalize_weights uses, device_weight_scale -> fp16_weight_scale, and
+// the same pack routine).  Split from engine.hip in round 6: an edit of a kernel family's argument struct rebuilds this file and its own,
+// not the sampler.
 #include "engine_util.h"
+
+namespace {
+// What every ramp_op_* entry point with a scaled operand does around its own pack call and argument struct.  Device memory lives as long
+// as the call (a DevArena).  begin(), called behind the pack: the slots of `n` operand sites -- previous maxima [0, n), recorded maxima
+// [n, 2n), range flag [2n] -- uploaded on the stream.  finish(): one synchronisation, the slots read back into the caller's outputs
+// (zeros where begin() never ran); a failed call leaves the outputs untouched.
+struct ScaledOp {
+  hipStream_t s; const int n;
+  DevArena ar;
+  float* slots = nullptr;
+  float host[12] = {0};
+  ScaledOp(hipStream_t st, int n_sites = 1) : s(st), n(n_sites) {}
+  size_t n_slots() const { return (size_t)(2 * n + 1 + 3) / 4 * 4; }
+  unsigned short* planes(size_t n_floats) { return reinterpret_cast<unsigned short*>(ar.alloc(n_floats)); }     // 2 n_floats halves
+  int begin(const float* absmax_prev) {      // n previous maxima (null: none given)
+    slots = ar.alloc(n_slots());
+    RAMP_REQUIRE(slots, "hipMalloc failed");
+    for (int i = 0; i < n; ++i) host[i] = absmax_prev ? absmax_prev[i] : 0.f;
+    RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, n_slots() * sizeof(float), hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  const float* amax_in(int i = 0) const { return host[i] > 0.f ? slots + i : nullptr; }      // null: no maximum given, the operand runs unscaled
+  float* amax_out(int i = 0) const { return slots + n + i; }
+  int* range_flag() const { return reinterpret_cast<int*>(slots + 2 * n); }
+  // the four fields every single-site argument struct has
+  template <class Args> void attach(Args& a, float w_scale) const {
+    a.amax_in = amax_in(); a.amax_out = amax_out(); a.wsi = 1.f / w_scale; a.range_flag = range_flag();
+  }
+  int finish(int rc, float* absmax_out_host, int32_t* range_flag_out_host) {
+    hipError_t e = hipStreamSynchronize(s);
+    if (rc == 0 && e == hipSuccess) {
+      if (slots) e = hipMemcpy(host, slots, n_slots() * sizeof(float), hipMemcpyDeviceToHost);
+      if (absmax_out_host) for (int i = 0; i < n; ++i) absmax_out_host[i] = host[n + i];
+      if (range_flag_out_host) std::memcpy(range_flag_out_host, &host[2 * n], 4);
+    }
+    RAMP_HIP_CHECK(e);
+    return rc;
+  }
+};
+}  // namespace
 
 namespace ramp {
 int op_gemm_packed(GemmArgs a, int mode, float a_absmax_prev, float* a_absmax_out_host, int32_t* range_flag_out_host, hipStream_t s) {
   RAMP_REQUIRE(mode >= 0 && mode <= 3, "mode: 0 fp32, 1 bf16x6, 2 bf16x6 (LDS-staged weights), 3 fp16x3");
   const int N = a.N, K = a.K;
-  const long n = (long)a.taps * N * K;
+  const size_t n = (size_t)a.taps * N * K;
   const bool frag_ok = N >= 64 && N % 32 == 0 && K % 16 == 0;
-  unsigned short* planes = nullptr; float* slots = nullptr;
-  int rc = 0;
+  ScaledOp h(s);
   if (mode == 3 && frag_ok) {
-    // the product's static weight scale: max |w| -> [2^10, 2^11)  (ramp_finalize_weights)
-    std::vector<float> hw(n);
-    RAMP_HIP_CHECK(hipMemcpy(hw.data(), a.W, n * sizeof(float), hipMemcpyDeviceToHost));
-    float mx = 0.f; for (float v : hw) mx = std::max(mx, std::fabs(v));
-    float sc = 1.f;
-    if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-    RAMP_HIP_CHECK(hipMalloc(&planes, 2 * n * sizeof(unsigned short)));
-    RAMP_HIP_CHECK(hipMalloc(&slots, 16));
-    const float v[4] = {a_absmax_prev, 0.f, 0.f, 0.f};
-    RAMP_HIP_CHECK(hipMemcpyAsync(slots, v, 16, hipMemcpyHostToDevice, s));
-    rc = launch_pack_h3(a.W, planes, (long)a.taps * N, K, sc, s);
+    float sc = 1.f; CK(device_weight_scale(a.W, n, &sc));
+    unsigned short* planes = h.planes(n + 4);
+    RAMP_REQUIRE(planes, "hipMalloc failed");
+    CK(launch_pack_h3(a.W, planes, (long)a.taps * N, K, sc, s));
+    CK(h.begin(&a_absmax_prev));
     a.Wx = planes; a.wx_packed = 2; a.w_scale_inv = 1.f / sc;
-    a.a_absmax_in = a_absmax_prev > 0.f ? slots : nullptr; a.a_absmax_out = slots + 1;
-    a.range_flag = reinterpret_cast<int*>(slots + 2);
+    a.a_absmax_in = h.amax_in(); a.a_absmax_out = h.amax_out(); a.range_flag = h.range_flag();
   } else if (mode == 1 && frag_ok) {
-    RAMP_HIP_CHECK(hipMalloc(&planes, 3 * n * sizeof(unsigned short)));
-    rc = launch_pack_x6(a.W, planes, (long)a.taps * N, K, s);
+    unsigned short* planes = h.planes((3 * n + 1) / 2 + 4);
+    RAMP_REQUIRE(planes, "hipMalloc failed");
+    CK(launch_pack_x6(a.W, planes, (long)a.taps * N, K, s));
     a.Wx = planes; a.wx_packed = 1;
   } else if ((mode == 1 || mode == 2) && N >= 128) {
-    RAMP_HIP_CHECK(hipMalloc(&planes, 3 * n * sizeof(unsigned short)));
-    rc = launch_split3(a.W, planes, n, s);
-    a.Wx = planes; a.wx_plane = n;
+    unsigned short* planes = h.planes((3 * n + 1) / 2 + 4);
+    RAMP_REQUIRE(planes, "hipMalloc failed");
+    CK(launch_split3(a.W, planes, (long)n, s));
+    a.Wx = planes; a.wx_plane = (long)n;
   }
-  if (rc == 0) rc = launch_gemm(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  if (rc == 0 && e == hipSuccess && slots) {
-    float back[4] = {0, 0, 0, 0};
-    e = hipMemcpy(back, slots, 16, hipMemcpyDeviceToHost);
-    if (a_absmax_out_host) *a_absmax_out_host = back[1];
-    int fl; std::memcpy(&fl, &back[2], 4);
-    if (range_flag_out_host) *range_flag_out_host = fl;
-  } else {
-    if (a_absmax_out_host) *a_absmax_out_host = 0.f;
-    if (range_flag_out_host) *range_flag_out_host = 0;
-  }
-  if (planes) (void)hipFree(planes);
-  if (slots) (void)hipFree(slots);
-  RAMP_HIP_CHECK(e);
-  return rc;
+  return h.finish(launch_gemm(a, s), a_absmax_out_host, range_flag_out_host);     // (no slots outside fp16x3: reports 0 / 0)
 }
 }  // namespace ramp
 
@@ -110,10 +130,7 @@ int ramp_apf_scenes(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf
   RAMP_REQUIRE(traj && p && sc && p->window_weights_host, "null argument");
   RAMP_REQUIRE(!p->cloud, "ramp_apf_scenes: apf.cloud must be NULL (the clouds come with the scene batch)");
   RAMP_REQUIRE(p->window >= 0 && p->window <= 64, "bad window");
-  RAMP_REQUIRE(sc->n_scenes >= 1 && sc->traj_scene && sc->cloud_points && sc->cloud_offset_host && sc->cloud_offset_host[0] == 0,
-               "ramp_apf_scenes: bad scene batch (at least one scene, offsets from 0)");
-  for (int i = 0; i < sc->n_scenes; ++i)
-    RAMP_REQUIRE(sc->cloud_offset_host[i + 1] > sc->cloud_offset_host[i], "ramp_apf_scenes: every scene needs at least one cloud point (increasing offsets)");
+  CK(check_scene_batch(sc, true, "ramp_apf_scenes"));
   hipStream_t s = as_stream(stream);
   // window weights | scene offsets in one block of its own (the offsets of many scenes outgrow a slot of the host-argument ring);
   // synchronises `stream`
@@ -247,6 +264,20 @@ int ramp_ddim_finish(const float* x, const float* x0, float sqrt_a_t, float sqrt
                             as_stream(stream));
 }
 
+// the sample-owning k = 5 convolution (tkc.hip) on the raw weight W [5][N][K]: mode 5 of ramp_op_gemm_mode and the narrow layers of
+// ramp_op_tkw; `t` carries the caller's operands
+static int op_tkc(TkcArgs t, const float* W, float absmax_prev, float* absmax_out_host, int32_t* range_flag_out_host, hipStream_t s) {
+  ScaledOp h(s);
+  float sc = 1.f; CK(device_weight_scale(W, (size_t)5 * t.N * t.K, &sc));
+  unsigned short* pl = h.planes(tkc_packed_halves(t.N, t.K) / 2 + 4);
+  RAMP_REQUIRE(pl, "hipMalloc failed");
+  CK(init_tkc_attributes());
+  CK(tkc_pack(W, t.N, t.K, sc, pl, s));
+  CK(h.begin(&absmax_prev));
+  t.W = pl; h.attach(t, sc);
+  return h.finish(launch_tkc(t, s), absmax_out_host, range_flag_out_host);
+}
+
 int ramp_op_gemm(const float* A, const float* W, const float* bias, const float* resid, float* C, int32_t M, int32_t N,
                  int32_t K, int32_t taps, int32_t shift0, int32_t shift_step, int32_t L, void* stream) {
   return ramp_op_gemm_mode(A, W, bias, resid, C, M, N, K, taps, shift0, shift_step, L, 0, 0.f, nullptr, nullptr, stream);
@@ -262,31 +293,9 @@ int ramp_op_gemm_mode(const float* A, const float* W, const float* bias, const f
   if (mode == 5) {
     RAMP_REQUIRE(taps == 5 && ((shift0 == -2 && shift_step == 1) || (shift0 == 2 && shift_step == -1)) && tkc_applicable(M, L, N, K, nullptr),
                  "mode 5: a k = 5 convolution (or its input gradient) with C_in, C_out in {32, 64}, L >= 8 dividing 48 or 32");
-    DevArena ar;
-    std::vector<float> hw((size_t)5 * N * K);
-    RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, hw.size() * 4, hipMemcpyDeviceToHost));
-    float mx = 0.f; for (float v : hw) mx = std::max(mx, std::fabs(v));
-    float sc = 1.f;
-    if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-    unsigned short* pl = reinterpret_cast<unsigned short*>(ar.alloc(tkc_packed_halves(N, K) / 2 + 4));
-    float* sl = ar.alloc(4);
-    RAMP_REQUIRE(pl && sl, "hipMalloc failed");
-    CK(init_tkc_attributes());
-    CK(tkc_pack(W, N, K, sc, pl, s));
-    const float v[4] = {a_absmax_prev, 0.f, 0.f, 0.f};
-    RAMP_HIP_CHECK(hipMemcpyAsync(sl, v, 16, hipMemcpyHostToDevice, s));
-    TkcArgs t; t.M = M; t.L = L; t.N = N; t.K = K; t.dir = shift_step; t.X = A; t.ldx = K; t.W = pl; t.bias = bias; t.resid = resid; t.ldr = N;
-    t.Y = C; t.ldy = N; t.amax_in = a_absmax_prev > 0.f ? sl : nullptr; t.amax_out = sl + 1; t.wsi = 1.f / sc; t.range_flag = reinterpret_cast<int*>(sl + 2);
-    int rc5 = launch_tkc(t, s);
-    hipError_t e5 = hipStreamSynchronize(s);
-    float back[4] = {0, 0, 0, 0};
-    if (rc5 == 0 && e5 == hipSuccess) {
-      e5 = hipMemcpy(back, sl, sizeof(back), hipMemcpyDeviceToHost);
-      if (a_absmax_out_host) *a_absmax_out_host = back[1];
-      if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-    }
-    RAMP_HIP_CHECK(e5);
-    return rc5;
+    TkcArgs t; t.M = M; t.L = L; t.N = N; t.K = K; t.dir = shift_step; t.X = A; t.ldx = K; t.bias = bias; t.resid = resid; t.ldr = N;
+    t.Y = C; t.ldy = N;
+    return op_tkc(t, W, a_absmax_prev, a_absmax_out_host, range_flag_out_host, s);
   }
   GemmArgs a; a.A = A; a.lda = K; a.W = W; a.bias = bias; a.resid = resid; a.ldr = N; a.C = C; a.ldc = N;
   a.M = M; a.N = N; a.K = K; a.taps = taps; a.shift0 = shift0; a.shift_step = shift_step; a.L = L;
@@ -297,36 +306,27 @@ static int op_ffx_impl(const float* z1, const float* dz, const float* W1, const 
                        float* absmax_out_host, int32_t* range_flag_out_host, void* stream, bool s16) {
   RAMP_REQUIRE(z1 && W1 && b1 && W2 && b2 && ln_g && ln_b && z2 && M > 0, "null argument");
   hipStream_t s = as_stream(stream);
-  DevArena ar;
+  ScaledOp h(s, 4);        // sites: forward LN(z1), forward a gelu(g), backward dz, backward second product
   FfxPack pk;
-  CK(ffx_pack_all(ar, W1, b1, W2, &pk, s, s16));
+  CK(ffx_pack_all(h.ar, W1, b1, W2, &pk, s, s16));
   auto launch_ffx = [s16](const FfxArgs& a, bool bwd, hipStream_t st) { return s16 ? ramp::launch_ffx16(a, bwd, st) : ramp::launch_ffx(a, bwd, st); };
   const size_t mt = ((size_t)M + 127) / 128;
-  float* stash = ar.alloc(mt * 128 * 2048); float* slots = ar.alloc(12);
-  RAMP_REQUIRE(stash && slots, "hipMalloc failed");
-  float host[12] = {0};
-  for (int i = 0; i < 4; ++i) host[i] = absmax_prev_host ? absmax_prev_host[i] : 0.f;
-  RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, sizeof(host), hipMemcpyHostToDevice, s));
+  float* stash = h.ar.alloc(mt * 128 * 2048);
+  RAMP_REQUIRE(stash, "hipMalloc failed");
+  CK(h.begin(absmax_prev_host));
   FfxArgs f; f.M = M; f.X = z1; f.Z1 = z1; f.Y = z2; f.stash = stash; f.ln_g = ln_g; f.ln_b = ln_b; f.Wstream = pk.stream_f;
-  f.b1 = pk.b1_pk; f.b2 = b2; f.range_flag = reinterpret_cast<int*>(slots + 8);
-  f.amax_in1 = host[0] > 0.f ? slots + 0 : nullptr; f.amax_out1 = slots + 4; f.wsi1 = pk.wsi_w1; f.site1 = 0;
-  f.amax_in2 = host[1] > 0.f ? slots + 1 : nullptr; f.amax_out2 = slots + 5; f.wsi2 = pk.wsi_w2; f.site2 = 1;
+  f.b1 = pk.b1_pk; f.b2 = b2; f.range_flag = h.range_flag();
+  f.amax_in1 = h.amax_in(0); f.amax_out1 = h.amax_out(0); f.wsi1 = pk.wsi_w1; f.site1 = 0;
+  f.amax_in2 = h.amax_in(1); f.amax_out2 = h.amax_out(1); f.wsi2 = pk.wsi_w2; f.site2 = 1;
   int rc = launch_ffx(f, false, s);
   if (rc == 0 && dz && dz1) {
     FfxArgs g; g.M = M; g.X = dz; g.Z1 = z1; g.Y = dz1; g.stash = stash; g.ln_g = ln_g; g.ln_b = ln_b; g.Wstream = pk.stream_b;
-    g.range_flag = reinterpret_cast<int*>(slots + 8);
-    g.amax_in1 = host[2] > 0.f ? slots + 2 : nullptr; g.amax_out1 = slots + 6; g.wsi1 = pk.wsi_w2; g.site1 = 2;
-    g.amax_in2 = host[3] > 0.f ? slots + 3 : nullptr; g.amax_out2 = slots + 7; g.wsi2 = pk.wsi_w1; g.site2 = 3;
+    g.range_flag = h.range_flag();
+    g.amax_in1 = h.amax_in(2); g.amax_out1 = h.amax_out(2); g.wsi1 = pk.wsi_w2; g.site1 = 2;
+    g.amax_in2 = h.amax_in(3); g.amax_out2 = h.amax_out(3); g.wsi2 = pk.wsi_w1; g.site2 = 3;
     rc = launch_ffx(g, true, s);
   }
-  hipError_t e = hipStreamSynchronize(s);
-  if (rc == 0 && e == hipSuccess) {
-    e = hipMemcpy(host, slots, sizeof(host), hipMemcpyDeviceToHost);
-    if (absmax_out_host) for (int i = 0; i < 4; ++i) absmax_out_host[i] = host[4 + i];
-    if (range_flag_out_host) std::memcpy(range_flag_out_host, &host[8], 4);
-  }
-  RAMP_HIP_CHECK(e);
-  return rc;
+  return h.finish(rc, absmax_out_host, range_flag_out_host);
 }
 int ramp_op_ffx(const float* z1, const float* dz, const float* W1, const float* b1, const float* W2, const float* b2,
                 const float* ln_g, const float* ln_b, int32_t M, const float* absmax_prev_host, float* z2, float* dz1,
@@ -344,37 +344,20 @@ static int op_tkl_impl(const float* X, const float* W, const float* bias, const 
                        float absmax_prev, float* Y, float* absmax_out_host, int32_t* range_flag_out_host, void* stream, bool s16) {
   RAMP_REQUIRE(X && W && Y && M > 0 && N >= 32 && N % 32 == 0 && N <= 768, "bad arguments");
   hipStream_t s = as_stream(stream);
-  DevArena ar;
-  std::vector<float> hw((size_t)N * 256);
-  RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, hw.size() * 4, hipMemcpyDeviceToHost));
-  float mx = 0.f;
-  for (float v : hw) mx = std::max(mx, std::fabs(v));
-  float sc = 1.f;
-  if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-  unsigned short* planes = reinterpret_cast<unsigned short*>(ar.alloc((size_t)N * 256 + 4));
-  float* slots = ar.alloc(4);
-  RAMP_REQUIRE(planes && slots, "hipMalloc failed");
+  ScaledOp h(s);
+  float sc = 1.f; CK(device_weight_scale(W, (size_t)N * 256, &sc));
+  unsigned short* planes = h.planes((size_t)N * 256 + 4);
+  RAMP_REQUIRE(planes, "hipMalloc failed");
   if (s16) {      // 16 x 32 fragments (tkl16.hip)
-    float* tmp = ar.alloc((size_t)N * 256);
+    float* tmp = h.ar.alloc((size_t)N * 256);
     RAMP_REQUIRE(tmp, "hipMalloc failed");
     CK(ffx16_pack(W, N, 256, 0, sc, tmp, planes, s));
   } else CK(launch_pack_h3(W, planes, N, 256, sc, s));
-  const float host[4] = {absmax_prev, 0.f, 0.f, 0.f};
-  RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, sizeof(host), hipMemcpyHostToDevice, s));
+  CK(h.begin(&absmax_prev));
   TklArgs a; a.M = M; a.N = N; a.X = X; a.Y = Y; a.ldy = N; a.W = planes; a.bias = bias; a.resid = resid; a.ldr = N;
   a.rowbias = rowbias; a.rowvar = rowvar; a.row0 = 0; a.rb_stride = N; a.L = L > 0 ? L : 1; a.n_var = n_var;
-  a.ln_g = ln_g; a.ln_b = ln_b; a.amax_in = absmax_prev > 0.f ? slots : nullptr; a.amax_out = slots + 1; a.wsi = 1.f / sc; a.site = 0;
-  a.range_flag = reinterpret_cast<int*>(slots + 2);
-  int rc = s16 ? launch_tkl16(a, s) : launch_tkl(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  float back[4] = {0, 0, 0, 0};
-  if (rc == 0 && e == hipSuccess) {
-    e = hipMemcpy(back, slots, sizeof(back), hipMemcpyDeviceToHost);
-    if (absmax_out_host) *absmax_out_host = back[1];
-    if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-  }
-  RAMP_HIP_CHECK(e);
-  return rc;
+  a.ln_g = ln_g; a.ln_b = ln_b; h.attach(a, sc);
+  return h.finish(s16 ? launch_tkl16(a, s) : launch_tkl(a, s), absmax_out_host, range_flag_out_host);
 }
 
 int ramp_op_tkl(const float* X, const float* W, const float* bias, const float* resid, const float* rowbias,
@@ -392,34 +375,17 @@ int ramp_op_ato(const float* qkv, const float* Wo, const float* bias, const floa
                 int32_t n_var, int32_t L, int32_t M, float absmax_prev, float* Y, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
   RAMP_REQUIRE(qkv && Wo && resid && Y && M > 0 && L > 0, "bad arguments");
   hipStream_t s = as_stream(stream);
-  DevArena ar;
-  std::vector<float> hw((size_t)256 * 256);
-  RAMP_HIP_CHECK(hipMemcpy(hw.data(), Wo, hw.size() * 4, hipMemcpyDeviceToHost));
-  float mx = 0.f;
-  for (float v : hw) mx = std::max(mx, std::fabs(v));
-  float sc = 1.f;
-  if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-  unsigned short* stream_w = reinterpret_cast<unsigned short*>(ar.alloc(8 * 8192 + 4));
-  float* slots = ar.alloc(4);
-  RAMP_REQUIRE(stream_w && slots, "hipMalloc failed");
+  ScaledOp h(s);
+  float sc = 1.f; CK(device_weight_scale(Wo, (size_t)256 * 256, &sc));
+  unsigned short* stream_w = h.planes(8 * 8192 + 4);
+  RAMP_REQUIRE(stream_w, "hipMalloc failed");
   CK(init_atk_attributes());
   CK(ato_pack(Wo, sc, stream_w, s));
-  const float host[4] = {absmax_prev, 0.f, 0.f, 0.f};
-  RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, sizeof(host), hipMemcpyHostToDevice, s));
+  CK(h.begin(&absmax_prev));
   AtoArgs a; a.M = M; a.L = L; a.QKV = qkv; a.W = stream_w; a.bias = bias; a.resid = resid; a.Y = Y;
   a.rowbias = rowbias; a.rowvar = rowvar; a.row0 = 0; a.rb_stride = 256; a.n_var = rowbias ? n_var : 0;
-  a.amax_in = absmax_prev > 0.f ? slots : nullptr; a.amax_out = slots + 1; a.wsi = 1.f / sc; a.site = 0;
-  a.range_flag = reinterpret_cast<int*>(slots + 2);
-  int rc = launch_ato(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  float back[4] = {0, 0, 0, 0};
-  if (rc == 0 && e == hipSuccess) {
-    e = hipMemcpy(back, slots, sizeof(back), hipMemcpyDeviceToHost);
-    if (absmax_out_host) *absmax_out_host = back[1];
-    if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-  }
-  RAMP_HIP_CHECK(e);
-  return rc;
+  h.attach(a, sc);
+  return h.finish(launch_ato(a, s), absmax_out_host, range_flag_out_host);
 }
 
 int ramp_op_atb(const float* qkv, const float* dout, float* dqkv, int32_t M, int32_t L, void* stream) {
@@ -432,36 +398,18 @@ int ramp_op_abl(const float* qkv, const float* dout, const float* W, const float
                 float absmax_prev, float* out, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
   RAMP_REQUIRE(qkv && dout && W && z && ln_g && add && out && M > 0 && L > 0, "bad arguments");
   hipStream_t s = as_stream(stream);
-  DevArena ar;
-  std::vector<float> hw((size_t)256 * 768);
-  RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, hw.size() * 4, hipMemcpyDeviceToHost));
-  float mx = 0.f;
-  for (float v : hw) mx = std::max(mx, std::fabs(v));
-  float sc = 1.f;
-  if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-  unsigned short* stream_w = reinterpret_cast<unsigned short*>(ar.alloc((size_t)256 * 768 + 4));
-  float* slots = ar.alloc(4);
-  RAMP_REQUIRE(stream_w && slots, "hipMalloc failed");
+  ScaledOp h(s);
+  float sc = 1.f; CK(device_weight_scale(W, (size_t)256 * 768, &sc));
+  unsigned short* stream_w = h.planes((size_t)256 * 768 + 4);
+  RAMP_REQUIRE(stream_w, "hipMalloc failed");
   CK(init_atl_attributes());
   CK(abl_pack(W, sc, stream_w, s));
-  const float host[4] = {absmax_prev, 0.f, 0.f, 0.f};
-  RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, sizeof(host), hipMemcpyHostToDevice, s));
+  CK(h.begin(&absmax_prev));
   AblArgs a; a.M = M; a.L = L; a.QKV = qkv; a.dO = dout; a.W = stream_w; a.Z = z; a.add = add; a.ln_g = ln_g; a.Y = out;
-  a.amax_in = absmax_prev > 0.f ? slots : nullptr; a.amax_out = slots + 1; a.wsi = 1.f / sc; a.site = 0;
-  a.range_flag = reinterpret_cast<int*>(slots + 2);
-  int rc = launch_abl(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  float back[4] = {0, 0, 0, 0};
-  if (rc == 0 && e == hipSuccess) {
-    e = hipMemcpy(back, slots, sizeof(back), hipMemcpyDeviceToHost);
-    if (absmax_out_host) *absmax_out_host = back[1];
-    if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-  }
-  RAMP_HIP_CHECK(e);
-  return rc;
+  h.attach(a, sc);
+  return h.finish(launch_abl(a, s), absmax_out_host, range_flag_out_host);
 }
 
-}  // extern "C"
 // ramp_op_tkw and ramp_op_tkw_rows: t_rows == nullptr -> tbias is the (N) time bias; else tbias is the time table (line stride tt_stride) and sample r adds line t_rows[r]
 static int op_tkw(const float* X, const float* X2, int32_t K1, const float* W, const float* bias, const float* resid, const float* resid2,
                   const float* gn_c, const float* gn_stats, const float* gn_gamma, const float* gn_beta, const float* gamma, const float* beta,
@@ -469,69 +417,31 @@ static int op_tkw(const float* X, const float* X2, int32_t K1, const float* W, c
                   float absmax_prev, float* Y, float* Y2, float* Cst, float* stats, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
   RAMP_REQUIRE(X && W && Y && M > 0 && L > 0 && N % 32 == 0 && K % 16 == 0, "bad arguments");
   hipStream_t s = as_stream(stream);
-  DevArena ar;
-  const size_t n = (size_t)5 * N * K;
   if (N <= 64 && K <= 64) {      // the narrow layers: the same fusion on sample-owning WAVES (tkc.hip)
     RAMP_REQUIRE(!X2 && !Y2 && tkc_applicable(M, L, N, K, nullptr), "narrow fused convolution: C_in, C_out in {32, 64}, L >= 8 dividing 48 or 32, one operand, one output");
-    std::vector<float> hw(n);
-    RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, n * 4, hipMemcpyDeviceToHost));
-    float mx = 0.f; for (float v : hw) mx = std::max(mx, std::fabs(v));
-    float sc = 1.f;
-    if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-    unsigned short* pl = reinterpret_cast<unsigned short*>(ar.alloc(tkc_packed_halves(N, K) / 2 + 4));
-    float* sl = ar.alloc(4);
-    RAMP_REQUIRE(pl && sl, "hipMalloc failed");
-    CK(init_tkc_attributes());
-    CK(tkc_pack(W, N, K, sc, pl, s));
-    const float v[4] = {absmax_prev, 0.f, 0.f, 0.f};
-    RAMP_HIP_CHECK(hipMemcpyAsync(sl, v, 16, hipMemcpyHostToDevice, s));
-    TkcArgs t; t.M = M; t.L = L; t.N = N; t.K = K; t.dir = dir; t.X = X; t.ldx = K; t.W = pl; t.bias = bias; t.resid = resid; t.ldr = N;
-    t.resid2 = resid2; t.ldr2 = N; t.Y = Y; t.ldy = N; t.amax_in = absmax_prev > 0.f ? sl : nullptr; t.amax_out = sl + 1; t.wsi = 1.f / sc;
-    t.range_flag = reinterpret_cast<int*>(sl + 2);
+    TkcArgs t; t.M = M; t.L = L; t.N = N; t.K = K; t.dir = dir; t.X = X; t.ldx = K; t.bias = bias; t.resid = resid; t.ldr = N;
+    t.resid2 = resid2; t.ldr2 = N; t.Y = Y; t.ldy = N;
     t.gn_c = gn_c; t.gn_stats = gn_stats; t.gn_gamma = gn_gamma; t.gn_beta = gn_beta;
     t.Cst = Cst; t.stats = stats; t.gamma = gamma; t.beta = beta; t.tbias = tbias; t.t_rows = t_rows; t.tt_stride = tt_stride; t.eps = 1e-5f;
-    int rc5 = launch_tkc(t, s);
-    hipError_t e5 = hipStreamSynchronize(s);
-    float back[4] = {0, 0, 0, 0};
-    if (rc5 == 0 && e5 == hipSuccess) {
-      e5 = hipMemcpy(back, sl, sizeof(back), hipMemcpyDeviceToHost);
-      if (absmax_out_host) *absmax_out_host = back[1];
-      if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-    }
-    RAMP_HIP_CHECK(e5);
-    return rc5;
+    return op_tkc(t, W, absmax_prev, absmax_out_host, range_flag_out_host, s);
   }
-  std::vector<float> hw(n);
-  RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, n * 4, hipMemcpyDeviceToHost));
-  float mx = 0.f;
-  for (float v : hw) mx = std::max(mx, std::fabs(v));
-  float sc = 1.f;
-  if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-  unsigned short* planes = reinterpret_cast<unsigned short*>(ar.alloc(n + 4));
-  float* slots = ar.alloc(4);
-  RAMP_REQUIRE(planes && slots, "hipMalloc failed");
+  ScaledOp h(s);
+  const size_t n = (size_t)5 * N * K;
+  float sc = 1.f; CK(device_weight_scale(W, n, &sc));
+  unsigned short* planes = h.planes(n + 4);
+  RAMP_REQUIRE(planes, "hipMalloc failed");
   CK(init_tkw_attributes());
   CK(launch_pack_h3(W, planes, (long)5 * N, K, sc, s));
-  const float host[4] = {absmax_prev, 0.f, 0.f, 0.f};
-  RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, sizeof(host), hipMemcpyHostToDevice, s));
+  CK(h.begin(&absmax_prev));
   TkwArgs a; a.M = M; a.L = L; a.N = N; a.K = K; a.dir = dir; a.X = X; a.ldx = X2 ? K1 : K; a.X2 = X2; a.ldx2 = X2 ? K - K1 : 0; a.K1 = X2 ? K1 : K;
-  a.gn_c = gn_c; a.gn_stats = gn_stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.W = planes; a.wsi = 1.f / sc; a.bias = bias;
+  a.gn_c = gn_c; a.gn_stats = gn_stats; a.gn_gamma = gn_gamma; a.gn_beta = gn_beta; a.W = planes; a.bias = bias;
   a.resid = resid; a.ldr = N; a.resid2 = resid2; a.ldr2 = N; a.Y = Y; a.ldy = Y2 ? N1 : N; a.Y2 = Y2; a.ldy2 = Y2 ? N - N1 : 0; a.N1 = Y2 ? N1 : N;
   a.Cst = Cst; a.stats = stats; a.gamma = gamma; a.beta = beta; a.tbias = tbias; a.t_rows = t_rows; a.tt_stride = tt_stride; a.eps = 1e-5f;
-  a.amax_in = absmax_prev > 0.f ? slots : nullptr; a.amax_out = slots + 1; a.site = 0; a.range_flag = reinterpret_cast<int*>(slots + 2);
-  int rc = launch_tkw(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  float back[4] = {0, 0, 0, 0};
-  if (rc == 0 && e == hipSuccess) {
-    e = hipMemcpy(back, slots, sizeof(back), hipMemcpyDeviceToHost);
-    if (absmax_out_host) *absmax_out_host = back[1];
-    if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-  }
-  RAMP_HIP_CHECK(e);
-  return rc;
+  h.attach(a, sc);
+  return h.finish(launch_tkw(a, s), absmax_out_host, range_flag_out_host);
 }
 
-extern "C" {
+
 int ramp_op_tkw(const float* X, const float* X2, int32_t K1, const float* W, const float* bias, const float* resid, const float* resid2,
                 const float* gn_c, const float* gn_stats, const float* gn_gamma, const float* gn_beta, const float* gamma, const float* beta,
                 const float* tbias, int32_t M, int32_t L, int32_t N, int32_t K, int32_t dir, int32_t N1, float absmax_prev, float* Y, float* Y2,
@@ -551,32 +461,15 @@ int ramp_op_tklb(const float* dqkv, const float* W, const float* z, const float*
                  float absmax_prev, float* out, float* absmax_out_host, int32_t* range_flag_out_host, void* stream) {
   RAMP_REQUIRE(dqkv && W && z && ln_g && add && out && M > 0, "bad arguments");
   hipStream_t s = as_stream(stream);
-  DevArena ar;
-  std::vector<float> hw((size_t)256 * 768);
-  RAMP_HIP_CHECK(hipMemcpy(hw.data(), W, hw.size() * 4, hipMemcpyDeviceToHost));
-  float mx = 0.f;
-  for (float v : hw) mx = std::max(mx, std::fabs(v));
-  float sc = 1.f;
-  if (mx > 0.f && std::isfinite(mx)) { int e; std::frexp(mx, &e); sc = std::ldexp(1.f, 11 - e); }
-  unsigned short* planes = reinterpret_cast<unsigned short*>(ar.alloc((size_t)256 * 768 + 4));
-  float* slots = ar.alloc(4);
-  RAMP_REQUIRE(planes && slots, "hipMalloc failed");
+  ScaledOp h(s);
+  float sc = 1.f; CK(device_weight_scale(W, (size_t)256 * 768, &sc));
+  unsigned short* planes = h.planes((size_t)256 * 768 + 4);
+  RAMP_REQUIRE(planes, "hipMalloc failed");
   CK(launch_pack_h3(W, planes, 256, 768, sc, s));
-  const float host[4] = {absmax_prev, 0.f, 0.f, 0.f};
-  RAMP_HIP_CHECK(hipMemcpyAsync(slots, host, sizeof(host), hipMemcpyHostToDevice, s));
+  CK(h.begin(&absmax_prev));
   TklbArgs a; a.M = M; a.X = dqkv; a.Z = z; a.add = add; a.Y = out; a.W = planes; a.ln_g = ln_g;
-  a.amax_in = absmax_prev > 0.f ? slots : nullptr; a.amax_out = slots + 1; a.wsi = 1.f / sc; a.site = 0;
-  a.range_flag = reinterpret_cast<int*>(slots + 2);
-  int rc = launch_tklb(a, s);
-  hipError_t e = hipStreamSynchronize(s);
-  float back[4] = {0, 0, 0, 0};
-  if (rc == 0 && e == hipSuccess) {
-    e = hipMemcpy(back, slots, sizeof(back), hipMemcpyDeviceToHost);
-    if (absmax_out_host) *absmax_out_host = back[1];
-    if (range_flag_out_host) std::memcpy(range_flag_out_host, &back[2], 4);
-  }
-  RAMP_HIP_CHECK(e);
-  return rc;
+  h.attach(a, sc);
+  return h.finish(launch_tklb(a, s), absmax_out_host, range_flag_out_host);
 }
 
 int ramp_op_groupnorm(const float* x, const float* gamma, const float* beta, const float* tbias, const float* resid,

@@ -412,3 +412,48 @@ def test_attention_lengths_cover_every_accepted_horizon():
     eng = open(os.path.join(ROOT, "ramp_amd", "csrc", "engine.hip")).read()
     assert "cfg->horizon >= 8 && cfg->horizon <= 64 && cfg->horizon % 8 == 0" in eng      # the accepted horizons this test assumes
     assert built == sorted({H >> k for H in range(8, 65, 8) for k in range(4)}), built
+
+
+def test_fp16_weight_scale_rule():
+    """fp16_weight_scale (csrc/weight_scale.h), the one statement of the fp16x3 static weight scale "max |w| -> [2^10, 2^11)", through
+    a stand-alone host program built with the compiler of ramp_amd.build: 0, inf and NaN give 1; for every finite positive maximum the
+    scale is a finite power of two, and max_abs * scale lies in [2^10, 2^11) wherever that product neither overflows nor underflows.
+    Which inputs those are follows from the float format: max_abs in [2^(e-1), 2^e) needs the scale 2^(11-e); e <= 128, so the scale is
+    never below 2^-117 and the product never overflows; the scale is a float only up to 2^127, i.e. for max_abs >= 2^-117 -- there the
+    product is exact and is asserted.  Below 2^-117 (the denormals included) no float scale reaches the interval: the scaling
+    underflows it, and the scale must be the largest power of two, 2^127."""
+    import math
+    import subprocess
+    import tempfile
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc")
+    f32 = np.float32
+    top = np.finfo(f32).max
+    cases = [0.0, 2.0 ** -149, 2.0 ** -127, float(np.nextafter(f32(2.0 ** -117), f32(0))), 2.0 ** -117, 1.0, float(top), math.inf, math.nan]
+    cases += [2.0 ** k for k in (-116, -24, -10, -1, 5, 10, 11, 12, 127)]                    # exact powers of two -> 2^10
+    cases += [float(np.nextafter(f32(2.0), f32(0))), 1.3 / 16, 0.3, 0.7, 3.14159, 1000.0, 2047.9, 65504.0, 1.0e-30, 3.0e38]
+    x = np.array(cases, dtype=f32)
+    with tempfile.TemporaryDirectory() as d:
+        exe = os.path.join(d, "weight_scale_check")
+        subprocess.check_call([hipcc, "-x", "c++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "ramp_amd", "csrc"),
+                               os.path.join(ROOT, "tests", "weight_scale_check.cpp"), "-o", exe])
+        out = subprocess.check_output([exe] + [f"{int(v):08x}" for v in x.view(np.uint32)], text=True).split()
+    s = np.array([int(v, 16) for v in out], dtype=np.uint32).view(f32)
+    assert len(s) == len(x)
+    n_range = 0
+    for xi, si in zip(x, s):
+        if not (np.isfinite(xi) and xi > 0):
+            assert si == 1.0, (xi, si)
+            continue
+        assert np.isfinite(si) and math.frexp(float(si))[0] == 0.5, (xi, si)                 # a finite power of two
+        with np.errstate(over="raise"):
+            p = xi * si
+        if xi >= f32(2.0 ** -117):
+            assert f32(1024.0) <= p < f32(2048.0), (xi, si, p)
+            n_range += 1
+        else:
+            assert si == f32(2.0 ** 127) and p < f32(1024.0), (xi, si, p)
+    assert n_range == len(cases) - 6                                                         # all but 0, inf, NaN and the three maxima below 2^-117
+    for k in (-116, -24, -10, -1, 5, 10, 11, 12, 127):
+        assert s[cases.index(2.0 ** k)] == f32(2.0 ** (10 - k)), k                           # 2^k -> exactly 2^10
