@@ -54,13 +54,24 @@ def make_timesteps(batch_size, i, device):
     return torch.full((batch_size,), i, device=device, dtype=torch.long)
 
 
-def _f32(values) -> "C.Array":
-    arr = (C.c_float * len(values))(*[float(v) for v in values])
-    return arr
+class _HostArrays:
+    """Owns what a params struct points at for the length of a job: the ctypes arrays it hands out, any tensor given to ``keep``."""
+
+    def __init__(self):
+        self._keep = []
+
+    def keep(self, obj):
+        self._keep.append(obj)
+        return obj
+
+    def f32(self, values):
+        return C.cast(self.keep((C.c_float * len(values))(*[float(v) for v in values])), _lib.c_f32p)
+
+    def i32(self, values):
+        return C.cast(self.keep((C.c_int32 * len(values))(*[int(v) for v in values])), _lib.c_i32p)
 
 
-def _i32(values) -> "C.Array":
-    return (C.c_int32 * len(values))(*[int(v) for v in values])
+DDIM_FIELDS = ('sqrt_recip', 'sqrt_recipm1', 'sqrt_a_t', 'sqrt_1m_a_t', 'sqrt_a_prev', 'dir_coef')
 
 
 class _GaussianDiffusionBase(nn.Module):
@@ -191,41 +202,26 @@ class _GaussianDiffusionBase(nn.Module):
         self.model.invalidate_scene()
 
     def _prepare_scene(self, obstacle_pts: torch.Tensor, B=None):
-        """Encode the distinct scene(s) once and hand the variants to the context.  Cache contract: a cloud is re-encoded when
-        its content differs from the last one's (``torch.equal`` against a kept clone); the comparison is skipped only for the
-        same tensor OBJECT with the same ``_version`` -- writes that bypass the version counter need ``invalidate_scene()``."""
+        """Encode the distinct scene(s) once and hand the variants to the context.  A cloud is re-encoded when its content differs
+        from the last one's (``unet.SceneCache``); writes that bypass the tensor's version counter need ``invalidate_scene()``."""
         m = self.model
-        dev = self._device()
-        zero = torch.zeros(1, m.context_dim, device=dev)
+        zero = torch.zeros(1, m.context_dim, device=self._device())
         if self.compose:
             assert obstacle_pts.dim() == 4 and obstacle_pts.shape[0] == 2, \
                 "compose expects obstacle_pts of shape (2, n_obstacles, n_points, dim)"
-            lat = torch.cat([m.encode_scene(obstacle_pts), zero])
-            pattern = [0, 1, 2]
+            m.set_scene(torch.cat([m.encode_scene(obstacle_pts), zero]), [0, 1, 2])
         else:
             pattern = self._row_pattern(B)
             # the step-at-a-time callers (p_mean_variance, the replanning loop) pass the same cloud every step
-            m.ctx()                          # (re)creates the context and clears the key after a weight reload
-            # keyed on CONTENT: the cloud is a few KB, and a (data_ptr, _version) key of a temporary device copy is
-            # recycled by the caching allocator for the next same-shaped cloud
-            key = (tuple(obstacle_pts.shape), tuple(pattern))
-            ref = getattr(m, '_scene_ref', None)
+            m.ctx()                          # (re)creates the context and clears the cache after a weight reload
             if obstacle_pts.device != self._device():        # a CPU-resident cloud is compared (and encoded) on the device
                 obstacle_pts = obstacle_pts.to(self._device())
-            if getattr(m, '_scene_key', None) == key and ref is not None and ref.dtype == obstacle_pts.dtype:
-                # fast path: the very tensor seen last time, unmodified since (no device reduction, no host sync)
-                ident = (obstacle_pts.data_ptr(), obstacle_pts._version, id(obstacle_pts))
-                if getattr(m, '_scene_ident', None) == ident and getattr(m, '_scene_src', None) is obstacle_pts:
-                    return
-                if torch.equal(ref, obstacle_pts):
-                    m._scene_ident, m._scene_src = ident, obstacle_pts
-                    return
-            lat = torch.cat([m.encode_scene(obstacle_pts), zero])
-        m.set_scene(lat, pattern)
-        m._scene_key = None if self.compose else key
-        m._scene_ref = None if self.compose else obstacle_pts.detach().clone()
-        m._scene_ident = None if self.compose else (obstacle_pts.data_ptr(), obstacle_pts._version, id(obstacle_pts))
-        m._scene_src = None if self.compose else obstacle_pts       # (kept alive: its id / data_ptr cannot be recycled)
+            # keyed on CONTENT: the cloud is a few KB, and a (data_ptr, _version) key of a temporary device copy is
+            # recycled by the caching allocator for the next same-shaped cloud
+            if m.scene_cache.holds(obstacle_pts, pattern):
+                return
+            m.set_scene(torch.cat([m.encode_scene(obstacle_pts), zero]), pattern)
+            m.scene_cache.remember(obstacle_pts, pattern)
         m.cached_batch_size = None          # the compat forward() cache is keyed differently
 
     @staticmethod
@@ -233,23 +229,140 @@ class _GaussianDiffusionBase(nn.Module):
         # APFhelper.py:42-44, same torch expression
         return torch.exp(-0.5 * torch.square(torch.arange(-window, window + 1)) / (window / 2) ** 2).float()
 
-    def _hard_arrays(self, hard_conds: Dict[int, torch.Tensor], B: int):
-        keys = list(hard_conds.keys())
+    def _fill_hard(self, p, arrays: _HostArrays, hard_conds: Dict[int, torch.Tensor], B: int):
+        """n_hard / hard_idx_host / hard_val of ramp_sample_params and ramp_replan_params."""
         H = self.model.n_support_points
-        idx = [k if k >= 0 else H + k for k in keys]
-        vals = []
-        for k in keys:
-            v = hard_conds[k].to(self._device(), torch.float32)
-            if v.dim() == 1:
-                v = v.unsqueeze(0).expand(B, -1)
-            vals.append(v)
-        val = torch.stack(vals).contiguous() if vals else torch.zeros(0, B, self.state_dim, device=self._device())
-        return idx, val
+        idx = [k if k >= 0 else H + k for k in hard_conds]
+        p.n_hard = len(idx)
+        if idx:
+            vals = [hard_conds[k].to(self._device(), torch.float32) for k in hard_conds]
+            val = torch.stack([v.unsqueeze(0).expand(B, -1) if v.dim() == 1 else v for v in vals]).contiguous()
+            p.hard_idx_host, p.hard_val = arrays.i32(idx), _lib.ptr(arrays.keep(val))
+
+    # ------------------------------------------------------------------ what goes into ramp_sample_params
+    def _ddim_coefficients(self, steps, K) -> Dict[str, list]:
+        """THE DDIM rule (diffusion_model_static.py:265-331 with eta = 0, use_clipped_model_output): per step t of ``steps``, with
+        prev = t - T // K and alpha_prev = final_alpha_cumprod when prev < 0, the scalars of ``DDIM_FIELDS`` -- x0 from eps
+        (sqrt_recip, sqrt_recipm1), eps' = (x - sqrt_a_t x0) / sqrt_1m_a_t, x <- sqrt_a_prev x0 + dir_coef eps'.  ``dir_coef`` keeps
+        the reference's variance term; at eta = 0 it equals (1 - alpha_prev) ** 0.5 on every step in use (test_sampler_host.py)."""
+        ac, sr, srm = (b.detach().cpu() for b in (self.alphas_cumprod, self.sqrt_recip_alphas_cumprod, self.sqrt_recipm1_alphas_cumprod))
+        out = {k: [] for k in DDIM_FIELDS}
+        for t in steps:
+            prev = t - self.n_diffusion_steps // K
+            a_t = ac[t]
+            a_prev = ac[prev] if prev >= 0 else self.final_alpha_cumprod[0]
+            variance = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
+            std_dev_t = 0.0 * variance ** 0.5                                   # eta = 0
+            out['sqrt_recip'].append(sr[t]); out['sqrt_recipm1'].append(srm[t])
+            out['sqrt_a_t'].append(a_t ** 0.5); out['sqrt_1m_a_t'].append((1 - a_t) ** 0.5)
+            out['sqrt_a_prev'].append(a_prev ** 0.5)
+            out['dir_coef'].append((1 - a_prev - std_dev_t ** 2) ** 0.5)
+        return out
+
+    def _ddpm_steps(self, n_diffusion_steps_without_noise=0):
+        """The DDPM loop's counter i = T - 1 .. -n_without_noise and the timestep it evaluates, max(i, 0) (sample_functions.py:25-27)."""
+        raw = list(reversed(range(-n_diffusion_steps_without_noise, self.n_diffusion_steps)))
+        return [max(i, 0) for i in raw], raw
+
+    def _fill_schedule(self, p, arrays: _HostArrays, ddim: bool, steps, noise_scale=None, ddim_K: Optional[int] = None):
+        """The per-step schedule tables of ramp_sample_params, from the schedule buffers exactly as the reference's extract() would
+        (host data only: no device, no context).  DDPM fills coef1 / coef2 / stdv / use_noise / noise_scale, DDIM the DDIM rule's."""
+        p.n_steps, p.ddim = len(steps), int(ddim)
+        p.t = arrays.i32(steps)
+        if ddim:
+            for k, v in self._ddim_coefficients(steps, ddim_K or self.ddim_num_inference_steps).items():
+                setattr(p, k, arrays.f32(v))
+            return
+        for field, buf in (('sqrt_recip', self.sqrt_recip_alphas_cumprod), ('sqrt_recipm1', self.sqrt_recipm1_alphas_cumprod),
+                           ('coef1', self.posterior_mean_coef1), ('coef2', self.posterior_mean_coef2)):
+            buf = buf.detach().cpu()
+            setattr(p, field, arrays.f32([buf[t] for t in steps]))
+        # model_std = exp(0.5 * posterior_log_variance_clipped[t])   (sample_functions.py:35-36)
+        plv = self.posterior_log_variance_clipped.detach().cpu()
+        p.stdv = arrays.f32([torch.exp(0.5 * plv[t]) for t in steps])
+        p.use_noise = arrays.i32([0 if t == 0 else 1 for t in steps])
+        p.noise_scale = arrays.f32(noise_scale)
+
+    @staticmethod
+    def _compose_apf_cloud(obstacle_pts):
+        """compose: the APF field is the first six obstacles of scene A + the first four of scene B (static.py:306-310)."""
+        return torch.cat([obstacle_pts[0], obstacle_pts[1][:4]], dim=0).reshape(-1, 2)
+
+    def _fill_apf(self, p, arrays: _HostArrays, apf_cfg, obstacle_pts=None, batch=None, scene_job=None):
+        """ramp_apf_params of the job; the points are one cloud (``obstacle_pts``) or, for a scene batch, its per-scene tables."""
+        w = arrays.keep(self._window_weights(apf_cfg['window']).contiguous())
+        p.apf.window = int(apf_cfg['window'])
+        p.apf.window_weights_host = C.cast(w.data_ptr(), _lib.c_f32p)
+        p.apf.threshold = float(apf_cfg['threshold'])
+        p.apf.strength = float(apf_cfg['strength'])
+        p.apf.passes = int(apf_cfg.get('passes', 1))
+        if batch is not None:
+            batch.cloud_points = _lib.ptr(scene_job['cloud_points'])
+            batch.cloud_offset_host = scene_job['cloud_offset'].ctypes.data_as(_lib.c_i32p)
+            return
+        cloud = self._compose_apf_cloud(obstacle_pts) if self.compose else obstacle_pts.reshape(-1, 2)
+        cloud = arrays.keep(cloud.to(self._device(), torch.float32).contiguous())
+        p.apf.cloud = _lib.ptr(cloud)
+        p.apf.n_points = cloud.shape[0]
+
+    def _philox_block(self, B: int, n_steps: int, ddim: bool):
+        """A job that draws its own noise takes the next (n_steps + 1 | 1) * total * H * S elements of the Philox stream: returns
+        (seed, offset, sample0, total) for the params and advances the offset by the WHOLE job's block (every shard advances alike)."""
+        s0, tot = self._philox_shard if self._philox_shard is not None else (0, B)
+        if not (0 <= s0 and s0 + B <= tot):
+            raise ValueError(f"set_noise_shard: samples [{s0}, {s0 + B}) lie outside the job's {tot}")
+        n_el = (1 if ddim else n_steps + 1) * tot * self.model.n_support_points * self.state_dim
+        offset = self._philox_offset
+        self.last_philox = (self.noise_seed, offset, n_el)
+        self._philox_offset += (n_el + 3) // 4
+        return self.noise_seed, offset, s0, tot
+
+    def _run_guarded(self, job):
+        """Run ``job`` under the fp16x3 range-guard policy: a flagged result is discarded and the same job (same noise) repeated, never
+        a silently degraded answer.  First IN fp16x3 with the evaluation that raised the guard run as a calibrating one (range-free,
+        its successor scaled from true maxima: ramp_set_fallback(ctx, 2)); if that repeat is flagged as well, all in bf16x6."""
+        m, lib = self.model, _lib.load()
+
+        def flagged():
+            flag = C.c_int32(0)
+            _lib.check(lib.ramp_range_status(m.ctx(), C.byref(flag), _lib.current_stream()), "ramp_range_status")
+            return flag.value
+
+        def again(mode):
+            _lib.check(lib.ramp_set_fallback(m.ctx(), mode), "ramp_set_fallback")
+            try:
+                job()
+                return flagged()
+            finally:
+                _lib.check(lib.ramp_set_fallback(m.ctx(), 0), "ramp_set_fallback")
+
+        job()
+        flag = flagged()
+        self.last_job_mode = {0: "fp16x3", 1: "fp32", 2: "bf16x6", 3: "fp16x3"}[m.gemm_mode]      # (0: the library default)
+        if not flag:
+            return
+        if not self.fp16_fallback:
+            raise _lib.RampHipError("fp16x3 GEMM: an operand left the fp16 range between two score evaluations "
+                                    f"(call site {flag - 1}); use gemm_mode='bf16x6'")
+        ev, site = C.c_int32(-1), C.c_int32(-1)
+        _lib.check(lib.ramp_range_trip(m.ctx(), C.byref(ev), C.byref(site)), "ramp_range_trip")
+        again_flag = 1
+        if ev.value >= 0 and self.fp16_rerun:
+            warnings.warn(f"fp16x3 range guard tripped in evaluation {ev.value} (GEMM call site {site.value}): repeating the job "
+                          "in fp16x3 with that evaluation calibrating")
+            self.range_reruns += 1
+            again_flag = again(2)
+            self.last_job_mode = "fp16x3-rerun"
+        if again_flag:
+            warnings.warn(f"fp16x3 range guard tripped at GEMM call site {flag - 1}: repeating the job in bf16x6")
+            self.range_fallbacks += 1
+            again(1)
+            self.last_job_mode = "bf16x6"
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
                 return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None):
-        """Fill ramp_sample_params from the schedule buffers exactly as the reference's extract() would.  ``scene_job``: what
-        ``_prepare_scene_job`` returned -- a job of many scenes (``ramp_sample_scenes``); ``obstacle_pts`` is not read then."""
+        """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
+        (``ramp_sample_scenes``); ``obstacle_pts`` is not read then."""
         m = self.model
         dev = self._device()
         H, S = m.n_support_points, self.state_dim
@@ -257,96 +370,27 @@ class _GaussianDiffusionBase(nn.Module):
         m.prepare_time_table(self.n_diffusion_steps)
         if scene_job is None:      # (run_inference_scenes: the scene table is already set, set_scenes)
             self._prepare_scene(obstacle_pts, B)
-        buf = {k: getattr(self, k).detach().cpu() for k in
-               ('alphas_cumprod', 'sqrt_recip_alphas_cumprod', 'sqrt_recipm1_alphas_cumprod',
-                'posterior_mean_coef1', 'posterior_mean_coef2', 'posterior_log_variance_clipped')}
-        p = _lib.RampSampleParams()
-        keep = []          # keep ctypes arrays alive
-
-        def arr_f(vals):
-            a = _f32(vals); keep.append(a); return C.cast(a, _lib.c_f32p)
-
-        def arr_i(vals):
-            a = _i32(vals); keep.append(a); return C.cast(a, _lib.c_i32p)
-
-        p.B, p.n_rp, p.n_steps, p.ddim = B, self._n_rp(), n_steps, int(ddim)
-        if self.compose:
-            p.w0, p.w1 = float(self.compose_weights[0]), float(self.compose_weights[1])
-        else:
-            p.w0, p.w1 = float(self.cfg_weight), 0.0
-        p.t = arr_i(steps)
-        p.sqrt_recip = arr_f([buf['sqrt_recip_alphas_cumprod'][t] for t in steps])
-        p.sqrt_recipm1 = arr_f([buf['sqrt_recipm1_alphas_cumprod'][t] for t in steps])
-        if not ddim:
-            p.coef1 = arr_f([buf['posterior_mean_coef1'][t] for t in steps])
-            p.coef2 = arr_f([buf['posterior_mean_coef2'][t] for t in steps])
-            # model_std = exp(0.5 * posterior_log_variance_clipped[t])   (sample_functions.py:35-36)
-            p.stdv = arr_f([torch.exp(0.5 * buf['posterior_log_variance_clipped'][t]) for t in steps])
-            p.use_noise = arr_i([0 if t == 0 else 1 for t in steps])
-            p.noise_scale = arr_f(noise_scale)
-        else:
-            ac = buf['alphas_cumprod']
-            K = ddim_K or self.ddim_num_inference_steps
-            sa, s1, sp, dc = [], [], [], []
-            for t in steps:
-                prev = t - self.n_diffusion_steps // K
-                a_t = ac[t]
-                a_prev = ac[prev] if prev >= 0 else self.final_alpha_cumprod[0]
-                variance = (1 - a_prev) / (1 - a_t) * (1 - a_t / a_prev)
-                std_dev_t = 0.0 * variance ** 0.5                                   # eta = 0
-                sa.append(a_t ** 0.5); s1.append((1 - a_t) ** 0.5); sp.append(a_prev ** 0.5)
-                dc.append((1 - a_prev - std_dev_t ** 2) ** 0.5)
-            p.sqrt_a_t, p.sqrt_1m_a_t, p.sqrt_a_prev, p.dir_coef = arr_f(sa), arr_f(s1), arr_f(sp), arr_f(dc)
-        p.apply_apf = arr_i(apply_apf)
+        p, arrays = _lib.RampSampleParams(), _HostArrays()
+        p.B, p.n_rp = B, self._n_rp()
+        p.w0, p.w1 = (float(w) for w in (self.compose_weights if self.compose else (self.cfg_weight, 0.0)))
+        self._fill_schedule(p, arrays, ddim, steps, noise_scale, ddim_K)
+        p.apply_apf = arrays.i32(apply_apf)
         p.clip_denoised = int(bool(self.clip_denoised))
         p.predict_x0 = int(not self.predict_epsilon)
-        idx, val = self._hard_arrays(hard_conds, B)
-        p.n_hard = len(idx)
-        p.hard_idx_host = arr_i(idx) if idx else None
-        p.hard_val = _lib.ptr(val) if idx else None
-        cloud = None
+        self._fill_hard(p, arrays, hard_conds, B)
         batch = None
         if scene_job is not None:
             batch = _lib.RampSceneBatch()
             batch.n_scenes = scene_job['n_scenes']
             batch.traj_scene = _lib.ptr(scene_job['traj_scene'])
-            if apf_cfg is not None and any(apply_apf):
-                w = self._window_weights(apf_cfg['window']).contiguous()
-                keep.append(w)
-                batch.cloud_points = _lib.ptr(scene_job['cloud_points'])
-                batch.cloud_offset_host = scene_job['cloud_offset'].ctypes.data_as(_lib.c_i32p)
-                p.apf.window = int(apf_cfg['window'])
-                p.apf.window_weights_host = C.cast(w.data_ptr(), _lib.c_f32p)
-                p.apf.threshold = float(apf_cfg['threshold'])
-                p.apf.strength = float(apf_cfg['strength'])
-                p.apf.passes = int(apf_cfg.get('passes', 1))
-        elif apf_cfg is not None and any(apply_apf):
-            if self.compose:      # first six obstacles of scene A + first four of scene B (static.py:306-310)
-                cloud = torch.cat([obstacle_pts[0], obstacle_pts[1][:4]], dim=0).reshape(-1, 2)
-            else:
-                cloud = obstacle_pts.reshape(-1, 2)
-            cloud = cloud.to(dev, torch.float32).contiguous()
-            w = self._window_weights(apf_cfg['window']).contiguous()
-            keep.append(w)
-            p.apf.cloud = _lib.ptr(cloud)
-            p.apf.n_points = cloud.shape[0]
-            p.apf.window = int(apf_cfg['window'])
-            p.apf.window_weights_host = C.cast(w.data_ptr(), _lib.c_f32p)
-            p.apf.threshold = float(apf_cfg['threshold'])
-            p.apf.strength = float(apf_cfg['strength'])
-            p.apf.passes = int(apf_cfg.get('passes', 1))
+        if apf_cfg is not None and any(apply_apf):
+            self._fill_apf(p, arrays, apf_cfg, obstacle_pts, batch, scene_job)
         p.use_graph = int(self.use_graph)
         chain = torch.empty((n_steps + 1, B, H, S), device=dev, dtype=torch.float32) if return_chain else None
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
-        if noise is None:          # the job draws its own: the next (n_steps + 1 | 1) * B * H * S elements of the Philox stream
-            s0, tot = self._philox_shard if self._philox_shard is not None else (0, B)
-            if not (0 <= s0 and s0 + B <= tot):
-                raise ValueError(f"set_noise_shard: samples [{s0}, {s0 + B}) lie outside the job's {tot}")
-            n_el = (1 if ddim else n_steps + 1) * tot * H * S                     # the WHOLE job's block: every shard advances alike
-            p.noise_mode, p.philox_seed, p.philox_offset = 1, self.noise_seed, self._philox_offset
-            p.philox_sample0, p.philox_total = s0, tot
-            self.last_philox = (self.noise_seed, self._philox_offset, n_el)
-            self._philox_offset += (n_el + 3) // 4
+        if noise is None:          # the job draws its own
+            p.noise_mode = 1
+            p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim)
         else:
             noise = noise.contiguous()
         with torch.cuda.device(dev):
@@ -360,43 +404,7 @@ class _GaussianDiffusionBase(nn.Module):
                     _lib.check(lib.ramp_sample(m.ctx(), C.byref(p), _lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out),
                                                _lib.current_stream()), "ramp_sample")
 
-            job()
-            flag = C.c_int32(0)
-            _lib.check(lib.ramp_range_status(m.ctx(), C.byref(flag), _lib.current_stream()), "ramp_range_status")
-            self.last_job_mode = {0: "fp16x3", 1: "fp32", 2: "bf16x6", 3: "fp16x3"}[m.gemm_mode]      # (0: the library default)
-            if flag.value:
-                # an operand left the range the delayed fp16 scaling assumed: the result is discarded and the same job (same noise) is
-                # repeated -- never a silently degraded answer.  First IN fp16x3 with the evaluation that raised the guard run as a
-                # calibrating one (range-free, and its successor is scaled from true maxima: ramp_set_fallback(ctx, 2)); only if that
-                # repeat is flagged as well, with every evaluation on the bf16x6 kernels.
-                if not self.fp16_fallback:
-                    raise _lib.RampHipError("fp16x3 GEMM: an operand left the fp16 range between two score evaluations "
-                                            f"(call site {flag.value - 1}); use gemm_mode='bf16x6'")
-                ev, site = C.c_int32(-1), C.c_int32(-1)
-                _lib.check(lib.ramp_range_trip(m.ctx(), C.byref(ev), C.byref(site)), "ramp_range_trip")
-
-                def again(mode):
-                    _lib.check(lib.ramp_set_fallback(m.ctx(), mode), "ramp_set_fallback")
-                    try:
-                        job()
-                        f2 = C.c_int32(0)
-                        _lib.check(lib.ramp_range_status(m.ctx(), C.byref(f2), _lib.current_stream()), "ramp_range_status")
-                    finally:
-                        _lib.check(lib.ramp_set_fallback(m.ctx(), 0), "ramp_set_fallback")
-                    return f2.value
-
-                again_flag = 1
-                if ev.value >= 0 and self.fp16_rerun:
-                    warnings.warn(f"fp16x3 range guard tripped in evaluation {ev.value} (GEMM call site {site.value}): repeating the job "
-                                  "in fp16x3 with that evaluation calibrating")
-                    self.range_reruns += 1
-                    again_flag = again(2)
-                    self.last_job_mode = "fp16x3-rerun"
-                if again_flag:
-                    warnings.warn(f"fp16x3 range guard tripped at GEMM call site {flag.value - 1}: repeating the job in bf16x6")
-                    self.range_fallbacks += 1
-                    again(1)
-                    self.last_job_mode = "bf16x6"
+            self._run_guarded(job)
         return x_out, chain
 
     # ------------------------------------------------------------------ loops (reference signatures)
@@ -428,13 +436,8 @@ class _GaussianDiffusionBase(nn.Module):
         B = shape[0]
         philox = self.noise_source == "philox"
         x = None if philox else torch.randn(shape, device=device)
-        noises = [x]
-        steps, raw = [], []
-        for i in reversed(range(-n_diffusion_steps_without_noise, self.n_diffusion_steps)):
-            steps.append(max(i, 0))                                 # sample_functions.py:25-27
-            raw.append(i)
-            if not philox:
-                noises.append(torch.randn_like(x))                  # drawn every step, zeroed at t == 0
+        steps, raw = self._ddpm_steps(n_diffusion_steps_without_noise)
+        noises = [x] + ([] if philox else [torch.randn_like(x) for _ in steps])       # drawn every step, zeroed at t == 0
         if noise_std_extra_schedule_fn is None:
             scales = [1.0] * len(steps)
         else:       # the reference hands the schedule function t[0], a 0-d long tensor on the device (sample_functions.py:24, 41-44)
@@ -603,11 +606,8 @@ class _GaussianDiffusionBase(nn.Module):
         return (chain if return_chain else chain[-1]), job['traj_scene']
 
     # ------------------------------------------------------------------ single-step compat API
-    @torch.no_grad()
-    def p_mean_variance(self, x, hard_conds, context, t, traj_normalized=None, obstacle_pts=None, forward_t=None,
-                        compose=False):
-        """One p_mean_variance on the HIP kernels (diffusion_model_static.py:149-186); obstacle_pts is the
-        un-batched cloud as passed by the loops.  Returns what the reference returns for the current mode."""
+    def _x0_mean_eps(self, x, t, obstacle_pts):
+        """``ramp_score`` + ``ramp_cfg_mean`` at timestep t: (x0, posterior mean, guidance-combined eps)."""
         dev = self._device()
         B = x.shape[0]
         ti = int(t.reshape(-1)[0])
@@ -632,6 +632,14 @@ class _GaussianDiffusionBase(nn.Module):
                                          int(bool(self.clip_denoised)), int(not self.predict_epsilon),
                                          _lib.ptr(x0), _lib.ptr(mean), _lib.ptr(ec),
                                          _lib.current_stream()), "ramp_cfg_mean")
+        return x0, mean, ec
+
+    @torch.no_grad()
+    def p_mean_variance(self, x, hard_conds, context, t, traj_normalized=None, obstacle_pts=None, forward_t=None,
+                        compose=False):
+        """One p_mean_variance on the HIP kernels (diffusion_model_static.py:149-186); obstacle_pts is the
+        un-batched cloud as passed by the loops.  Returns what the reference returns for the current mode."""
+        x0, mean, ec = self._x0_mean_eps(x, t, obstacle_pts)
         pv = extract(self.posterior_variance, t, x.shape)
         plv = extract(self.posterior_log_variance_clipped, t, x.shape)
         if self.ddim:
@@ -639,6 +647,7 @@ class _GaussianDiffusionBase(nn.Module):
         if (self.APF and self._supports_apf and not self.compose and forward_t is not None
                 and forward_t > self.apf_ddpm['after']):
             from .apf import ObstacleField, avoidance
+            pts = obstacle_pts[0] if obstacle_pts.dim() == 4 else obstacle_pts      # one copy of the cloud is the field
             field = ObstacleField(pts.reshape(-1, 2), distance_threshold=self.apf_ddpm['threshold'])
             mean = avoidance(mean, field, avoidance_window=self.apf_ddpm['window'],
                              avoidance_strength=self.apf_ddpm['strength'])
@@ -658,6 +667,17 @@ class _GaussianDiffusionBase(nn.Module):
         return self.p_mean_variance(x, hard_conds, context, t, traj_normalized=traj_normalized, obstacle_pts=obstacle_pts,
                                     forward_t=None, compose=True)
 
+    def _ddim_finish(self, xx, x0, ti, K):
+        """The deterministic DDIM update of one step from (x_t, x0), through the kernel-level entry point."""
+        k = self._ddim_coefficients([ti], K)
+        out = torch.empty_like(xx)
+        B, H, S = xx.shape
+        with torch.cuda.device(self._device()):
+            _lib.check(_lib.load().ramp_ddim_finish(_lib.ptr(xx), _lib.ptr(x0), float(k['sqrt_a_t'][0]), float(k['sqrt_1m_a_t'][0]),
+                                                    float(k['sqrt_a_prev'][0]), float(k['dir_coef'][0]), _lib.ptr(out), B, H, S,
+                                                    _lib.current_stream()), "ramp_ddim_finish")
+        return out
+
     @torch.no_grad()
     def ddim_p_sample(self, x, hard_conds, context, t, obstacle_pts, traj_normalized=None, forward_t=None, eta=0.0,
                       use_clipped_model_output=False):
@@ -666,39 +686,21 @@ class _GaussianDiffusionBase(nn.Module):
         ``forward_t >= 2``, then the deterministic update -- the step ``ramp_sample`` runs inside its captured loop, here one
         at a time through the kernel-level entry points."""
         assert use_clipped_model_output and eta == 0.0
-        dev = self._device()
-        B, H, S = x.shape
         ti = int(t.reshape(-1)[0])
-        prev = ti - self.n_diffusion_steps // self.ddim_num_inference_steps
-        ac = self.alphas_cumprod.detach().cpu()
-        a_t = ac[ti]
-        a_prev = ac[prev] if prev >= 0 else self.final_alpha_cumprod[0]
-        was = self.ddim
-        self.ddim = True
-        try:
-            _, _, _, x0, _ = self.p_mean_variance(x, hard_conds, context, t, traj_normalized=traj_normalized,
-                                                  obstacle_pts=obstacle_pts, compose=self.compose)
-        finally:
-            self.ddim = was
-        xx = x.detach().to(dev, torch.float32).contiguous()
+        x0 = self._x0_mean_eps(x, t, obstacle_pts)[0]
+        xx = x.detach().to(self._device(), torch.float32).contiguous()
         c = self.apf_ddim
         if self.APF and self._supports_apf and forward_t is not None and forward_t >= c['start']:
             from .apf import ObstacleField, avoidance
-            if self.compose:      # first six obstacles of scene A + first four of scene B (static.py:306-310)
-                cloud = torch.cat([obstacle_pts[0], obstacle_pts[1][:4]], dim=0).reshape(-1, 2)
+            if self.compose:
+                cloud = self._compose_apf_cloud(obstacle_pts)
             else:       # the loop hands over obstacle_pts.unsqueeze(0) (static.py:366); one copy of the cloud is the field
                 cloud = (obstacle_pts[0] if obstacle_pts.dim() == 4 else obstacle_pts).reshape(-1, 2)
             field = ObstacleField(cloud, distance_threshold=c['threshold'])
             for _ in range(c['passes']):
                 x0 = avoidance(x0, field, avoidance_window=c['window'], avoidance_strength=c['strength'])
                 x0 = apply_hard_conditioning(x0, hard_conds)
-        out = torch.empty_like(xx)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().ramp_ddim_finish(_lib.ptr(xx), _lib.ptr(x0.contiguous()), float(a_t ** 0.5),
-                                                    float((1 - a_t) ** 0.5), float(a_prev ** 0.5),
-                                                    float((1 - a_prev) ** 0.5), _lib.ptr(out), B, H, S,
-                                                    _lib.current_stream()), "ramp_ddim_finish")
-        return out
+        return self._ddim_finish(xx, x0.contiguous(), ti, self.ddim_num_inference_steps)
 
 
 class StaticGaussianDiffusionModel(_GaussianDiffusionBase):
@@ -783,472 +785,9 @@ class GaussianDiffusionModel3d(_GaussianDiffusionBase):
         return rep(x), t.repeat((n_rp,)), rep(traj_normalized), rep(obstacle_pts)
 
 
-class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
-    """Pursuit-evasion wrapper (diffusion_model_dynamic.py:24-680): the pieces on the sampler hot path — CFG
-    (w = 2.5) + x0 + clamp + posterior (``p_mean_variance``), one DDIM step with the per-trajectory static /
-    pursuer APF (``ddim_p_sample``), velocity smoothing ``sm`` and ``q_sample`` re-noising, and the receding-horizon
-    replanning state machine around them (``ddim_p_sample_loop`` / ``ddim_replan_scratch`` / ``run_inference``,
-    :461-667; SURVEY.md §8(f) "next" row 1), which reaches the environment through the same attribute path as the
-    reference (``context['dataset'].env.obj_fixed_list / obj_extra_list``).
-
-    ``cfg_mode='reference_compat'`` reproduces the reference's row pairing exactly: it
-    lays rows out blocked [x_0..x_{B-1}, x_0..x_{B-1}] while the net zeroes the latent of every odd GLOBAL row, so
-    for even B even samples get pure eps_cond and odd samples pure eps_uncond, and for odd B odd samples get the
-    inverted combination.  ``cfg_mode='intended'`` is true classifier-free guidance."""
-    _default_cfg_weight = 2.5          # diffusion_model_dynamic.py:157
-    _default_ddim = True               # diffusion_model_dynamic.py:46
-    _supports_apf = False
-    _scenes_supported = False          # the replanning loop keeps one scene per job
-
-    def __init__(self, model=None, variance_schedule='exponential', n_diffusion_steps=100, clip_denoised=True,
-                 predict_epsilon=False, loss_type='l2', context_model=None, mask_type=None, traj_len=None,
-                 cfg_mode: str = 'reference_compat', **kwargs):
-        super().__init__(model=model, variance_schedule=variance_schedule, n_diffusion_steps=n_diffusion_steps,
-                         clip_denoised=clip_denoised, predict_epsilon=predict_epsilon, loss_type=loss_type,
-                         context_model=context_model, **kwargs)
-        self.mask_type = mask_type
-        self.traj_len = traj_len
-        self.ddim_num_inference_steps_high = 10
-        self.ddim_num_inference_steps_low = 5
-        assert cfg_mode in ('reference_compat', 'intended')
-        self.cfg_mode = cfg_mode
-
-    # dynamic APF constants hard-coded in the reference (diffusion_model_dynamic.py:380-389)
-    apf_dynamic = dict(obs_radius=0.1, points_per_obstacle=64, threshold_static=0.2, threshold_pred=0.5,
-                       strength_static=0.15, strength_pred=0.15, window_static=8, window_pred=5)
-
-    def deep_repeat_tensor(self, x, t, traj_normalized, obstacle_pts, n_rp):
-        """diffusion_model_dynamic.py:129-147: blocked ``repeat`` (the layout behind quirk Q1, see ``cfg_mode``)."""
-        rep = lambda v: v.repeat((n_rp,) + (1,) * (v.dim() - 1))
-        return rep(x), t.repeat((n_rp,)), rep(traj_normalized), rep(obstacle_pts)
-
-    def _row_pattern(self, B):
-        if self.cfg_mode == 'intended' or B is None:
-            return [0, 1]
-        # rows here are [b*2 + v]; v = 0 plays global row b, v = 1 plays global row B + b of the reference
-        return [0, 0, 1, 1] if B % 2 == 0 else [0, 1, 1, 0]
-
-    @torch.no_grad()
-    def ddim_p_sample(self, x, hard_conds, context, t, obstacle_pts, traj_normalized=None, forward_t=None, eta=0.0,
-                      use_apf=False, use_clipped_model_output=False, obstacle_field=None, pursuer_pos=None):
-        """One DDIM step of the high-level plan (diffusion_model_dynamic.py:338-447).  With ``use_apf`` the
-        caller supplies ``obstacle_field`` (ramp_amd.apf_dynamic.ObstacleField, dynamic cloud already updated) and
-        the pursuer position; every trajectory gets the static pass, those whose current waypoint is within
-        ``threshold_pred`` of the pursuer also the pursuer pass, then the goal waypoint is restored."""
-        assert use_clipped_model_output and eta == 0.0
-        from .apf_dynamic import avoidance
-        dev = self._device()
-        B, H, S = x.shape
-        ti = int(t.reshape(-1)[0])
-        prev = ti - self.n_diffusion_steps // self.ddim_num_inference_steps_high
-        ac = self.alphas_cumprod.detach().cpu()
-        a_t = ac[ti]
-        a_prev = ac[prev] if prev >= 0 else self.final_alpha_cumprod[0]
-        was = self.ddim
-        self.ddim = True
-        _, _, _, x0, _ = self.p_mean_variance(x, hard_conds, context, t, traj_normalized=traj_normalized,
-                                              obstacle_pts=obstacle_pts)
-        self.ddim = was
-        xx = x.detach().to(dev, torch.float32).contiguous()
-        if use_apf:
-            if obstacle_field is None or pursuer_pos is None:
-                raise ValueError("use_apf=True needs obstacle_field and pursuer_pos (the reference pulls them from "
-                                 "context['dataset'].env, which is outside the sampler hot path)")
-            c = self.apf_dynamic
-            x_start = xx[:, forward_t].clone()
-            x_goal = xx[:, -1].clone()
-            avoidance(x0, obstacle_field, is_dynamic=False, avoidance_window=c['window_static'],
-                      avoidance_strength=c['strength_static'], avoidance_strength_pred=c['strength_pred'])
-            near = (torch.norm(x_start[:, :2] - pursuer_pos.to(dev, torch.float32)[None, :2], dim=1)
-                    < c['threshold_pred']).to(torch.int32)
-            avoidance(x0, obstacle_field, is_dynamic=True, avoidance_window=c['window_pred'],
-                      avoidance_strength=c['strength_static'], avoidance_strength_pred=c['strength_pred'],
-                      affected_states=H, goal_state=x_goal[0], enable=near)
-            x0[:, -1] = x_goal
-        out = torch.empty_like(xx)
-        idx = (C.c_int32 * 1)(0)
-        with torch.cuda.device(dev):
-            p = _lib.RampSampleParams()      # reuse the DDIM finish through the kernel-level path: no hard conds here
-            _lib.check(_lib.load().ramp_ddim_finish(_lib.ptr(xx), _lib.ptr(x0), float(a_t ** 0.5),
-                                                    float((1 - a_t) ** 0.5), float(a_prev ** 0.5),
-                                                    float((1 - a_prev) ** 0.5), _lib.ptr(out), B, H, S,
-                                                    _lib.current_stream()), "ramp_ddim_finish")
-        return out
-
-    def sm(self, s1, s2, dt=0.1, num_steps=3, max_vel=.8):
-        """Velocity-limited straight-line states between s1 and s2 (diffusion_model_dynamic.py:192-214)."""
-        delta_pos = s2[:, :2] - s1[:, :2]
-        dist = torch.norm(delta_pos, dim=1, keepdim=True)
-        direc = torch.where(dist > 1e-6, delta_pos / dist, torch.zeros_like(delta_pos))
-        desired_v = delta_pos / (num_steps * dt)
-        base_v = torch.where(torch.norm(desired_v, dim=1, keepdim=True) > max_vel, direc * max_vel, desired_v)
-        tt = torch.arange(1, num_steps + 1, device=s1.device).float().view(1, num_steps, 1) * dt
-        pos = s1[:, None, :2] + tt * base_v[:, None, :]
-        return torch.cat([pos, base_v.unsqueeze(1).expand(-1, num_steps, -1)], dim=-1)
-
-    def q_sample(self, x_start, t, noise=None):
-        """diffusion_model_dynamic.py:671-680."""
-        if noise is None:
-            noise = torch.randn_like(x_start)
-        return (extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
-                + extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
-
-    # ------------------------------------------------------------------ receding-horizon planner
-    def _obstacle_field(self, context):
-        """Lazily build the APF clouds exactly where the reference does (diffusion_model_dynamic.py:391-411): static
-        boxes from context['static_obstacle_centers'/'sizes'], pursuer from the env's moving sphere field."""
-        from .apf_dynamic import ObstacleField
-        if 'obstacle_field' not in context:
-            sphere = context['dataset'].env.obj_extra_list[0].fields[0]
-            c = self.apf_dynamic
-
-            def dynamic_obstacle_fn(t, start_pos, replan_guide=True, best_idx=None):
-                if replan_guide and best_idx is not None:
-                    start_pos = start_pos[best_idx].unsqueeze(0)
-                sphere.update_centers(t, start_pos)
-                return sphere.centers[0].cpu().numpy(), c['obs_radius']
-
-            context['obstacle_field'] = ObstacleField(context['static_obstacle_centers'], context['static_obstacle_sizes'],
-                                                      dynamic_obstacle_fn, c['points_per_obstacle'],
-                                                      distance_threshold=c['threshold_static'],
-                                                      distance_threshold_pred=c['threshold_pred'], device=self._device())
-        return context['obstacle_field']
-
-    def _step(self, x, hard_conds, context, i, obstacle_pts, traj_normalized, forward_t, use_apf):
-        """ddim_p_sample as the loops call it: with use_apf the pursuer cloud is advanced to ``forward_t`` first."""
-        B = x.shape[0]
-        t = torch.full((B,), int(i), device=self._device(), dtype=torch.long)
-        field, pursuer = None, None
-        if use_apf:
-            field = self._obstacle_field(context)
-            field.update_dynamic(forward_t, x[:, forward_t, :2].clone(), replan_guide=True)
-            pursuer = torch.as_tensor(np.asarray(field.dynamic_center), dtype=torch.float32)
-        return self.ddim_p_sample(x, hard_conds, context, t, obstacle_pts, traj_normalized=traj_normalized,
-                                  forward_t=forward_t, eta=0.0, use_apf=use_apf, use_clipped_model_output=True,
-                                  obstacle_field=field, pursuer_pos=pursuer)
-
-    @torch.no_grad()
-    def ddim_replan_scratch(self, shape, hard_conds, context=None, traj_normalized=None, forward_t=None,
-                            obstacle_pts=None, use_apf=False, executed_history=None):
-        """diffusion_model_dynamic.py:461-493."""
-        x = torch.randn(shape, device=self._device())
-        x = apply_hard_conditioning(x, hard_conds)
-        for h, st in enumerate(executed_history):
-            x[:, h] = st
-        for i in self.ddim_set_timesteps(self.ddim_num_inference_steps_high):
-            if i == 0:
-                use_apf = True
-            x = self._step(x, hard_conds, context, i, obstacle_pts, traj_normalized, forward_t, use_apf)
-            x = apply_hard_conditioning(x, hard_conds)
-            for h, st in enumerate(executed_history):
-                x[:, h] = st
-        return x
-
-    # ------------------------------------------------------------------ receding-horizon planner, one graph per replan
-    def _ddim_arrays(self, steps, K):
-        ac = self.alphas_cumprod.detach().cpu()
-        sr, srm, sa, s1, sp, dc = [], [], [], [], [], []
-        for t in steps:
-            prev = t - self.n_diffusion_steps // K
-            a_t = ac[t]
-            a_prev = ac[prev] if prev >= 0 else self.final_alpha_cumprod[0]
-            sr.append(self.sqrt_recip_alphas_cumprod[t]); srm.append(self.sqrt_recipm1_alphas_cumprod[t])
-            sa.append(a_t ** 0.5); s1.append((1 - a_t) ** 0.5); sp.append(a_prev ** 0.5); dc.append((1 - a_prev) ** 0.5)
-        return sr, srm, sa, s1, sp, dc
-
-    @torch.no_grad()
-    def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
-                           obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1,
-                           max_iteration=60, **sample_kwargs):
-        """Pursuit-evasion receding-horizon planner (diffusion_model_dynamic.py:495-624), MI355X-shaped: the 10-step
-        high-level plan is ONE ``ramp_sample`` job and every replan ONE ``ramp_replan`` graph replay (q_sample of the
-        current plan, 5 DDIM steps with the executed history / goal pinned, smoothing, static + pursuer APF on the last
-        step, collision mask, costs, selection -- all on the device), with a 16-byte result record and the winning
-        trajectory as the only read-backs.  Host work per replan is what the reference leaves to the environment: the
-        pursuer's dynamics callback (fed x[:, stepp, :2], i.e. the pinned executed state, known before the replan starts),
-        its re-sampled sphere cloud (numpy RNG, same call order as the reference) and the termination test.
-        ``self.replan_log`` (a list, optional) receives every batch handed to a selection, for the parity tests."""
-        from .apf_dynamic import generate_sphere_points
-        from . import dist as rdist
-        import torch.distributed as tdist
-        device = self._device()
-        B, H, S = shape
-        lib = _lib.load()
-        m = self.model
-        log = getattr(self, 'replan_log', None)
-        # several GPUs: `shape[0]` is THIS rank's share of the candidates; every selection merges the ranks' candidates
-        # (12 bytes per candidate all-gathered, the winner's owner broadcasts its trajectory: ramp_amd.dist.select_best_sharded),
-        # so all ranks execute the same plan and feed the same environment (SURVEY 8(e))
-        sharded = tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1
-        env = context['dataset'].env
-        fixed = env.obj_fixed_list[0].fields[0]
-        context['static_obstacle_centers'] = fixed.centers.cpu().numpy()[:4]
-        context['static_obstacle_sizes'] = fixed.sizes.cpu().numpy()[:4]
-        sphere = env.obj_extra_list[0].fields[0]
-        cloud = obstacle_pts.to(device).contiguous()
-        cost_cloud = cloud.reshape(-1, 2).to(torch.float32).contiguous()
-        chain_obs = []
-        chain_start = [hard_conds[0][0].unsqueeze(0)]
-        safe_threshold, distance_threshold_pred = 0.2, 0.4
-        thr_high, thr_low = 0.02, 0.05
-        chain = [] if return_chain else None
-        # STAGE I: high-level plan (10 DDIM steps, hard conditioning after each: one captured job), then the selection
-        x = torch.randn(shape, device=device)
-        ts = [int(i) for i in self.ddim_set_timesteps(self.ddim_num_inference_steps_high)]
-        xb, _ = self._launch(B, x.unsqueeze(0), hard_conds, cloud, True, ts, [0] * len(ts), None, None, False,
-                             ddim_K=self.ddim_num_inference_steps_high)
-        mask = torch.empty(B, dtype=torch.int32, device=device)
-        plen = torch.empty(B, device=device); smooth = torch.empty(B, device=device)
-        best = torch.empty((H, S), device=device)
-        res_dev = torch.zeros(4, dtype=torch.int32, device=device)
-        with torch.cuda.device(device):
-            _lib.check(lib.ramp_select_best(_lib.ptr(xb), B, H, S, _lib.ptr(cost_cloud), cost_cloud.shape[0], thr_high, 0.1, 0.9,
-                                            _lib.ptr(mask), _lib.ptr(plen), _lib.ptr(smooth), _lib.ptr(best), _lib.ptr(res_dev),
-                                            _lib.current_stream()), "ramp_select_best")
-        n_free, rank, _row, _ = (int(v) for v in res_dev.cpu())
-        if log is not None:
-            log.append(dict(batch=xb.clone(), npts=cost_cloud.shape[0], idx=rank if n_free else -1, free=(mask == 0).clone()))
-        if sharded:
-            x_plan, n_free, _row = rdist.select_best_sharded(xb, mask, plen, smooth, 0.1, 0.9, zero_start=False)
-        if n_free == 0:
-            raise RuntimeError("no collision-free high-level plan (the reference dereferences None here)")
-        if not sharded:
-            x_plan = xb[_row].clone()   # (the selection kernel zeroes x[0, 2:] as the replans need; the high-level winner stays as is)
-        high_plan = x_plan.clone()
-        hist_dev = torch.zeros((H, S), device=device)
-        hist_dev[0] = x_plan[0]
-        executed_history = [x_plan[0].clone().unsqueeze(0)]
-        best_host = x_plan.cpu().numpy()
-        # STAGE II
-        low = ts[-self.ddim_num_inference_steps_low:]
-        sr, srm, sa, s1, sp, dc = self._ddim_arrays(low, self.ddim_num_inference_steps_high)
-        keep = []
-
-        def arr_f(vals):
-            a = _f32(vals); keep.append(a); return C.cast(a, _lib.c_f32p)
-
-        def arr_i(vals):
-            a = _i32(vals); keep.append(a); return C.cast(a, _lib.c_i32p)
-
-        c = self.apf_dynamic
-        p = _lib.RampReplanParams()
-        p.B, p.n_rp, p.n_steps, p.clip_denoised, p.w = B, 2, len(low), int(bool(self.clip_denoised)), float(self.cfg_weight)
-        p.predict_x0 = int(not self.predict_epsilon)
-        p.t = arr_i(low)
-        p.sqrt_recip, p.sqrt_recipm1 = arr_f(sr), arr_f(srm)
-        p.sqrt_a_t, p.sqrt_1m_a_t, p.sqrt_a_prev, p.dir_coef = arr_f(sa), arr_f(s1), arr_f(sp), arr_f(dc)
-        p.q_sqrt_a = float(self.sqrt_alphas_cumprod[low[0]]); p.q_sqrt_1m_a = float(self.sqrt_one_minus_alphas_cumprod[low[0]])
-        idx, hval = self._hard_arrays(hard_conds, B)
-        p.n_hard = len(idx); p.hard_idx_host = arr_i(idx) if idx else None; p.hard_val = _lib.ptr(hval) if idx else None
-        p.sm_window_last, p.sm_window_final, p.sm_dt, p.sm_max_vel = 3, 2, 0.1, 0.8
-        p.thr_static, p.thr_pred = float(c['threshold_static']), float(c['threshold_pred'])
-        p.strength_static, p.strength_pred, p.window_static = float(c['strength_static']), float(c['strength_pred']), int(c['window_static'])
-        p.n_dyn = int(c['points_per_obstacle'])
-        p.cost_cloud, p.n_cost, p.n_extra = _lib.ptr(cost_cloud), cost_cloud.shape[0], 64
-        p.cost_thr, p.w_smooth, p.w_len = thr_low, 0.1, 0.9
-        p.use_graph = int(self.use_graph)
-        x_clean = x_plan.contiguous()
-        stepp = 0
-        batch = torch.empty((B, H, S), device=device) if (log is not None or sharded) else None
-        for k in range(max_iteration):
-            noise = torch.randn_like(xb)                           # q_sample's randn_like(x_start)
-            field = self._obstacle_field(context)
-            p.static_pts, p.n_static = _lib.ptr(field._static_dev), field._static_dev.shape[0]
-            # the environment step of the reference's last DDIM step (diffusion_model_dynamic.py:396-411): the pursuer sees
-            # x[:, stepp, :2], which is the pinned executed state of every candidate
-            field.update_dynamic(k, executed_history[-1][:, :2].expand(B, 2).clone(), replan_guide=True)
-            centre = np.asarray(field.dynamic_center, np.float64)
-            dyn = np.ascontiguousarray(field.dynamic_points, np.float64)
-            assert dyn.shape == (p.n_dyn, 2)
-            near = bool(np.linalg.norm(best_host[stepp, :2] - sphere.centers[0].cpu().numpy()) < distance_threshold_pred)
-            extra = None
-            if near:
-                extra = np.ascontiguousarray(generate_sphere_points(sphere.centers[0].cpu().numpy(),
-                                                                    sphere.radii[0].cpu().numpy(), 64), np.float32)
-            st = _lib.RampReplanState()
-            st.noise, st.x_clean, st.history = _lib.ptr(noise), _lib.ptr(x_clean), _lib.ptr(hist_dev)
-            st.n_hist, st.stepp = len(executed_history), stepp
-            st.dyn_pts_host = dyn.ctypes.data
-            st.pursuer[0], st.pursuer[1] = float(np.float32(centre[0])), float(np.float32(centre[1]))
-            st.near = int(near)
-            st.extra_pts_host = extra.ctypes.data if near else None
-            res = _lib.RampReplanResult()
-            with torch.cuda.device(device):
-                _lib.check(lib.ramp_replan(m.ctx(), C.byref(p), C.byref(st), _lib.ptr(best), _lib.ptr(batch),
-                                           _lib.ptr(mask) if (log is not None or sharded) else None, C.byref(res), _lib.current_stream()),
-                           "ramp_replan")
-            if res.fell_back:
-                self.range_fallbacks += 1
-                warnings.warn(f"fp16x3 range guard tripped at GEMM call site {res.fell_back - 1}: replan repeated in bf16x6")
-            if log is not None:
-                log.append(dict(batch=batch.clone(), npts=cost_cloud.shape[0] + (64 if near else 0),
-                                idx=res.best_rank if res.n_free else -1, free=(mask == 0).clone()))
-            n_free_all = res.n_free
-            if sharded:                                            # the local winner is only a candidate: merge over the ranks
-                with torch.cuda.device(device):
-                    _lib.check(lib.ramp_replan_costs(m.ctx(), B, _lib.ptr(mask), _lib.ptr(plen), _lib.ptr(smooth),
-                                                     _lib.current_stream()), "ramp_replan_costs")
-                merged, n_free_all, _ = rdist.select_best_sharded(batch, mask, plen, smooth, 0.1, 0.9)
-                if merged is not None:
-                    best.copy_(merged)
-            if n_free_all == 0:
-                # no candidate survived: the reference re-plans from scratch until one does (:591-605), eager path
-                from .cost import compute_trajectory_costs
-                # Sharded: the ranks re-plan round by round in LOCK-STEP (every rank draws the same number of torch / numpy random
-                # numbers, so their pursuer clouds stay identical afterwards, and nobody waits in a collective while another rank
-                # is still looping); after each round the lowest rank that found a collision-free plan broadcasts it.
-                nb = min(30, rdist.min_over_ranks(B, device) if sharded else B)      # the SAME count on every rank: equal RNG consumption
-                while True:
-                    new_hc = {kk: v[:nb].clone() for kk, v in hard_conds.items()}
-                    xs = self.ddim_replan_scratch((nb, H, S), new_hc, context, traj_normalized, forward_t=k,
-                                                  obstacle_pts=cloud, use_apf=False, executed_history=executed_history)
-                    xs[:, stepp + 1:stepp + 3] = self.sm(xs[:, stepp], xs[:, stepp + 2], num_steps=2)
-                    xs, _, _, _, _ = compute_trajectory_costs(xs, cost_cloud, collision_threshold=thr_low)
-                    if xs is not None:
-                        xs = xs.clone(); xs[0, 2:] = 0.0
-                        best.copy_(xs)
-                    if not sharded:
-                        if xs is not None:
-                            break
-                        continue
-                    src = rdist.lowest_rank_with(xs is not None, device)
-                    if src >= 0:
-                        tdist.broadcast(best, src=src)
-                        break
-            x_cur = best.clone()
-            best_host = x_cur.cpu().numpy()
-            x_clean = x_cur
-            executed_history.append(x_cur[stepp + 1].clone().unsqueeze(0))
-            hist_dev[stepp + 1] = x_cur[stepp + 1]
-            updated_start_state = x_cur[stepp].clone()
-            stepp += 1
-            if return_chain:
-                if stepp == 1:
-                    chain.append(high_plan.unsqueeze(0).clone())
-                chain.append(x_cur.unsqueeze(0).clone())
-            chain_obs.append(sphere.centers.clone())
-            chain_start.append(updated_start_state.unsqueeze(0).clone())
-            if float(np.linalg.norm(best_host[stepp - 1, :2] - best_host[-1, :2])) < safe_threshold:
-                break
-        if return_chain:
-            chain = torch.stack(chain, dim=1)
-        return x_cur, chain, chain_obs, chain_start
-
-    @torch.no_grad()
-    def ddim_p_sample_loop_eager(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
-                                 obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1,
-                                 max_iteration=60, **sample_kwargs):
-        """The same planner as a host loop over the step-at-a-time entry points (one launch sequence and several syncs
-        per DDIM step): kept as the readable restatement the graph path is tested against."""
-        from .apf_dynamic import generate_sphere_points
-        from .cost import compute_trajectory_costs
-        device = self._device()
-        B = shape[0]
-        x = torch.randn(shape, device=device)
-        x = apply_hard_conditioning(x, hard_conds)
-        env = context['dataset'].env
-        fixed = env.obj_fixed_list[0].fields[0]
-        context['static_obstacle_centers'] = fixed.centers.cpu().numpy()[:4]
-        context['static_obstacle_sizes'] = fixed.sizes.cpu().numpy()[:4]
-        sphere = env.obj_extra_list[0].fields[0]
-        cloud = obstacle_pts.to(device).contiguous()          # (n_obstacles, n_points, 2); the reference replicates it per row
-        cost_cloud = cloud.reshape(-1, 2)
-        chain_obs = []
-        chain_start = [hard_conds[0][0].unsqueeze(0)]
-        safe_threshold, distance_threshold_pred = 0.2, 0.4
-        thr_high, thr_low = 0.02, 0.05
-        replan_scratch_shape = (min(30, B), shape[1], shape[2])   # the reference hard-codes (30, 48, 4)
-        chain = [] if return_chain else None
-        stepp = 0
-        # STAGE I: high-level plan
-        for i in self.ddim_set_timesteps(self.ddim_num_inference_steps_high):
-            x = self._step(x, hard_conds, context, i, cloud, traj_normalized, None, False)
-            x = apply_hard_conditioning(x, hard_conds)
-        best_traj, _, _, _, _ = compute_trajectory_costs(x, cost_cloud, collision_threshold=thr_high)
-        if best_traj is None:
-            raise RuntimeError("no collision-free high-level plan (the reference dereferences None here)")
-        high_plan = best_traj.clone()
-        x = best_traj.clone()
-        executed_history = [x[0].clone().unsqueeze(0)]
-        # STAGE II: receding-horizon replanning
-        ts = self.ddim_set_timesteps(self.ddim_num_inference_steps_high)
-        low = ts[-self.ddim_num_inference_steps_low:]
-        for k in range(max_iteration):
-            x_clean = x.clone()
-            x = x.unsqueeze(0).repeat(B, 1, 1).contiguous()
-            noise_t = torch.tensor([int(low[0])], device=device)
-            x = self.q_sample(x, noise_t).contiguous()
-            x[:, 0, 2:] = 0
-            for h, st in enumerate(executed_history):
-                x[:, h] = st
-            x[:, -1] = x_clean[-1]
-            for i in low:
-                use_apf = False
-                if i == 0:
-                    use_apf = True
-                    window = 3
-                    x[:, stepp + 1:stepp + 1 + window] = self.sm(x[:, stepp], x[:, stepp + window], num_steps=window)
-                x = self._step(x, hard_conds, context, i, cloud, traj_normalized, k, use_apf)
-                x = apply_hard_conditioning(x, hard_conds)
-                for h, st in enumerate(executed_history):
-                    x[:, h] = st
-                x[:, -1] = x_clean[-1]
-                x[:, 0, 2:] = 0.0
-            window = 2
-            x[:, stepp + 1:stepp + 1 + window] = self.sm(x[:, stepp], x[:, stepp + window], num_steps=window)
-            near = np.linalg.norm(x[0, stepp, :2].cpu().numpy() - sphere.centers[0].cpu().numpy()) < distance_threshold_pred
-            if near:
-                pts = generate_sphere_points(sphere.centers[0].cpu().numpy(), sphere.radii[0].cpu().numpy(), 64)
-                allpts = torch.cat([cost_cloud, torch.from_numpy(pts).to(device, cloud.dtype)])
-                x, _, _, _, _ = compute_trajectory_costs(x, allpts, collision_threshold=thr_low)
-            else:
-                x, _, _, _, _ = compute_trajectory_costs(x, cost_cloud, collision_threshold=thr_low)
-            while x is None:
-                new_hc = {kk: v[:replan_scratch_shape[0]].clone() for kk, v in hard_conds.items()}
-                x = self.ddim_replan_scratch(replan_scratch_shape, new_hc, context, traj_normalized, forward_t=k,
-                                             obstacle_pts=cloud, use_apf=False, executed_history=executed_history)
-                window = 2
-                x[:, stepp + 1:stepp + 1 + window] = self.sm(x[:, stepp], x[:, stepp + window], num_steps=window)
-                x, _, _, _, _ = compute_trajectory_costs(x, cost_cloud, collision_threshold=thr_low)
-            x = x.clone()
-            x[0, 2:] = 0.0
-            executed_history.append(x[stepp + 1].clone().unsqueeze(0))
-            updated_start_state = x[stepp].clone()
-            stepp += 1
-            if return_chain:
-                if stepp == 1:
-                    chain.append(high_plan.unsqueeze(0).clone())
-                chain.append(x.unsqueeze(0).clone())
-            chain_obs.append(sphere.centers.clone())
-            chain_start.append(updated_start_state.unsqueeze(0).clone())
-            if torch.norm(x[stepp - 1, :2] - x[-1, :2]) < safe_threshold:
-                break
-        if return_chain:
-            chain = torch.stack(chain, dim=1)
-        return x, chain, chain_obs, chain_start
-
-    @torch.no_grad()
-    def conditional_sample(self, hard_conds, horizon=None, batch_size=1, ddim=False, traj_normalized=None,
-                           obstacle_pts=None, **sample_kwargs):
-        horizon = horizon or self.model.n_support_points
-        shape = (batch_size, horizon, self.state_dim)
-        for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
-            sample_kwargs.pop(k, None)
-        return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized, obstacle_pts=obstacle_pts,
-                                       **sample_kwargs)
-
-    @torch.no_grad()
-    def run_inference(self, context=None, hard_conds=None, n_samples=1, return_chain=False, traj_normalized=None,
-                      obstacle_pts=None, **diffusion_kwargs):
-        """diffusion_model_dynamic.py:649-667: (chain (iters, 1, H, S), chain_obs, chain_start) if return_chain."""
-        hard_conds = copy(hard_conds)
-        context = copy(context)
-        for k, v in hard_conds.items():
-            hard_conds[k] = v.to(self._device()).unsqueeze(0).expand(n_samples, -1).contiguous() if v.dim() == 1 else v
-        samples, chain, chain_obs, chain_start = self.conditional_sample(
-            hard_conds, context=context, batch_size=n_samples, return_chain=True, traj_normalized=traj_normalized,
-            obstacle_pts=obstacle_pts, **diffusion_kwargs)
-        chain = chain.permute(1, 0, 2, 3)
-        if return_chain:
-            return chain, chain_obs, chain_start
-        return chain[-1]
+def __getattr__(name):
+    # the pursuit-evasion planner lives in diffusion_dynamic.py (which imports this module); re-exported from here on first use
+    if name == 'DynamicGaussianDiffusionModel':
+        from .diffusion_dynamic import DynamicGaussianDiffusionModel
+        return DynamicGaussianDiffusionModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

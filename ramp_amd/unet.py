@@ -21,6 +21,41 @@ from .scene_encoder import ObstacleEncoder, ObstacleEncoderSet
 from .spec import UNET_DIM_MULTS, make_unet_spec, unet_param_shapes  # noqa: F401  (re-export)
 
 
+class SceneCache:
+    """Which cloud the context's scene was encoded from (the samplers' ``_prepare_scene``).  A cloud is the remembered one when
+    shape, row pattern and dtype match and its content equals a kept clone; the comparison is skipped only for the same tensor
+    OBJECT with the same ``_version``.  Whatever else changes the context's scene calls ``clear()``."""
+
+    def __init__(self):
+        self.clear()
+
+    def clear(self):
+        self.key = self.ref = None          # (cloud shape, row pattern); clone of the cloud encoded last
+        self.ident = self.src = None        # (data_ptr, _version, id) of the tensor object seen last; that object (kept alive: no recycling)
+
+    @staticmethod
+    def _ident(cloud):
+        return (cloud.data_ptr(), cloud._version, id(cloud))
+
+    def holds(self, cloud: torch.Tensor, pattern) -> bool:
+        """Is ``cloud`` under ``pattern`` what was remembered last?"""
+        if self.ref is None or self.key != (tuple(cloud.shape), tuple(pattern)) or self.ref.dtype != cloud.dtype:
+            return False
+        # fast path: the very tensor seen last time, unmodified since (no device reduction, no host sync)
+        ident = self._ident(cloud)
+        if self.ident == ident and self.src is cloud:
+            return True
+        if torch.equal(self.ref, cloud):
+            self.ident, self.src = ident, cloud
+            return True
+        return False
+
+    def remember(self, cloud: torch.Tensor, pattern):
+        self.key = (tuple(cloud.shape), tuple(pattern))
+        self.ref = cloud.detach().clone()
+        self.ident, self.src = self._ident(cloud), cloud
+
+
 class TemporalUnetInference(nn.Module):
     """Energy-gradient temporal U-Net: ``forward`` returns eps = d/dx 0.5*||f(x, t, scene)||^2."""
 
@@ -63,8 +98,7 @@ class TemporalUnetInference(nn.Module):
         self._weights: "OrderedDict[str, torch.Tensor]" = OrderedDict()   # host fp32 copies (checkpoint truth)
         self._ctx: Optional[C.c_void_p] = None
         self._T_table = 0
-        self._scene_key = None
-        self._scene_ref = None
+        self.scene_cache = SceneCache()
         self.cached_scene_latents = None
         self.cached_batch_size = None
 
@@ -103,8 +137,7 @@ class TemporalUnetInference(nn.Module):
             _lib.load().ramp_destroy(self._ctx)
             self._ctx = None
             self._T_table = 0
-            self._scene_key = None
-            self._scene_ref = None
+            self.scene_cache.clear()
 
     def __del__(self):
         try:
@@ -211,8 +244,7 @@ class TemporalUnetInference(nn.Module):
         """latents (n_variants, ctx) with all-zero rows for unconditional variants; row r of the network
         uses variant row_pattern[r % len(row_pattern)]."""
         lat = latents.to(self._device(), torch.float32).contiguous()
-        self._scene_key = None
-        self._scene_ref = None
+        self.scene_cache.clear()
         pat = (C.c_int32 * len(row_pattern))(*row_pattern)
         with torch.cuda.device(self._device()):
             _lib.check(_lib.load().ramp_set_scene(self.ctx(), _lib.ptr(lat), lat.shape[0], pat, len(row_pattern),
@@ -225,7 +257,7 @@ class TemporalUnetInference(nn.Module):
         pattern.  A batch with more rows than the table is refused; ``set_scene`` returns the context to pattern mode."""
         lat = latents.to(self._device(), torch.float32).contiguous()
         rv = np.ascontiguousarray(row_variant.cpu().numpy() if torch.is_tensor(row_variant) else row_variant, dtype=np.int32).reshape(-1)
-        self.invalidate_scene()
+        self.scene_cache.clear()
         self.cached_batch_size = None
         with torch.cuda.device(self._device()):
             _lib.check(_lib.load().ramp_set_scenes(self.ctx(), _lib.ptr(lat), lat.shape[0], rv.ctypes.data_as(_lib.c_i32p), rv.size,
@@ -258,17 +290,14 @@ class TemporalUnetInference(nn.Module):
     def reset_cache(self):
         self.cached_scene_latents = None
         self.cached_batch_size = None
-        self.invalidate_scene()             # the samplers' content-keyed cache too: forces a re-encode
+        self.scene_cache.clear()            # the samplers' content-keyed cache too: forces a re-encode
 
     def invalidate_scene(self):
         """Forget the scene the samplers encoded last.  The samplers skip the comparison of the cloud's CONTENT when they are
         handed the very tensor object they saw last time with an unchanged autograd version counter; a write that does not
         bump that counter (``x.data.copy_()``, a raw-pointer kernel, a DLPack / externally shared buffer) must be followed by
         this call (or ``reset_cache()``), otherwise the previous scene encoding stays in use."""
-        self._scene_key = None
-        self._scene_ref = None
-        self._scene_ident = None
-        self._scene_src = None
+        self.scene_cache.clear()
 
     # ------------------------------------------------------------------ forward
     def _run(self, x, time, obstacle_pts, compose, want_f, want_eps):

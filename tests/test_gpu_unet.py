@@ -109,7 +109,7 @@ def test_scene_cache_is_keyed_on_content():
                      noise_std_extra_schedule_fn=lambda x: 0.5)                  # same content: no re-encode
     assert torch.equal(u.cached_scene_latents[0], lats[0])
     u.reset_cache()
-    assert u._scene_key is None
+    assert u.scene_cache.key is None
 
 
 @pytest.mark.parametrize("S,H,o3", [(4, 48, False), (6, 64, True)])
