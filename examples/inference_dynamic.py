@@ -18,6 +18,10 @@ replays.  ``--make-synthetic DIR`` writes an experiment tree in the reference's 
 checkpoint).  Rendering is left out.
 
     python examples/inference_dynamic.py --make-synthetic /tmp/ramp_dyn --n-samples 64 --max-replans 6
+
+``--one-job 0,0,0`` runs the listed contexts (a context may repeat: the reference's run_multiple_experiments runs every context several
+times, :277-330) as ONE many-episode job -- ``run_inference_episodes``: every replan iteration of all episodes is one captured hipGraph
+(ramp_replan_episodes) -- and prints one line per episode.  Without it the script runs one context, as before.
 """
 from __future__ import annotations
 
@@ -105,11 +109,10 @@ class DynamicInference:
         self.context_manager = compat.ContextManager()
         self.model = None
 
-    def run_single_experiment(self, context_idx: int, env_index: int = 0, dataset=None, obstacle_pts=None):
-        """``dataset`` / ``obstacle_pts``: tests inject the reference fixture's environment and cloud; by default they come
-        from the experiment directory like the reference's TrajectoryDataset item."""
+    def _experiment_inputs(self, context_idx: int, env_index: int = 0, dataset=None, obstacle_pts=None):
+        """What one experiment hands to the planner, read from the experiment directory like the reference's TrajectoryDataset item
+        (inference_dynamic.py:111-154, 190-194): (context, hard_conds, obstacle_pts, box_centers, box_size)."""
         cfg = self.config
-        torch.cuda.set_device(0)
         env_dir = os.path.join(cfg.dataset_path, cfg.dataset_subdir, str(env_index))
         data = compat.load_environment_dir(env_dir)
         box_centers, box_size = data['box_centers'], data['box_sizes']
@@ -118,23 +121,60 @@ class DynamicInference:
         if obstacle_pts is None:
             obstacle_pts = data['obstacle_points']
             obstacle_pts = torch.cat([obstacle_pts[:4], obstacle_pts[torch.randint(0, 4, (2,))]], dim=0)   # 4 obstacles + 2 repeats (:142)
-        n_support_points = cfg.n_support_points
-        traj_normalized = torch.zeros(n_support_points, cfg.state_dim)
         start_state_pos, goal_state_pos = self.context_manager.load_context(
             os.path.join(cfg.dataset_path, cfg.dataset_subdir, 'contexts', 'contexts'), context_idx, self.device)
+        hard_conds = compat.StateGenerator.get_hard_cond_custom(torch.vstack((start_state_pos, goal_state_pos)), horizon=cfg.n_support_points,
+                                                                include_velocity=cfg.include_velocity)
+        return {'dataset': dataset}, hard_conds, obstacle_pts, box_centers, box_size
+
+    def _load_model(self, max_rows: int):
+        cfg = self.config
         diffusion_configs = dict(variance_schedule=cfg.variance_schedule, n_diffusion_steps=cfg.n_diffusion_steps, predict_epsilon=cfg.predict_epsilon)
-        unet_configs = dict(state_dim=cfg.state_dim, n_support_points=n_support_points, unet_input_dim=cfg.unet_input_dim,
+        unet_configs = dict(state_dim=cfg.state_dim, n_support_points=cfg.n_support_points, unet_input_dim=cfg.unet_input_dim,
                             dim_mults=UNET_DIM_MULTS[cfg.unet_dim_mults_option])
-        self.model = get_model(model_class=cfg.diffusion_model_class, model=TemporalUnetInference(max_rows=2 * cfg.n_samples, **unet_configs),
+        self.model = get_model(model_class=cfg.diffusion_model_class, model=TemporalUnetInference(max_rows=max_rows, **unet_configs),
                                tensor_args=self.tensor_args, **diffusion_configs, **unet_configs)
         compat.load_checkpoint(self.model, cfg.trained_models_dir, cfg.model_id, use_ema=cfg.use_ema, device="cpu")
         self.model.eval()
         for p in self.model.parameters():
             p.requires_grad_(False)
-        hard_conds = compat.StateGenerator.get_hard_cond_custom(torch.vstack((start_state_pos, goal_state_pos)), horizon=n_support_points,
-                                                                include_velocity=cfg.include_velocity)
-        context = {'dataset': dataset}
-        start_state_pos = hard_conds[0][:2]; goal_state_pos = hard_conds[n_support_points - 1][:2]
+
+    def _experiment_metrics(self, hard_conds, chain_obs, chain_start, box_centers, box_size, elapsed):
+        """The executed path and its collision intensity (inference_dynamic.py:224-252)."""
+        chain_obs = list(chain_obs)
+        chain_obs.pop()
+        chain_obs = [t.cpu().detach().numpy() for t in chain_obs]
+        chain_start = [np.around(t[:, :2].cpu().detach().numpy(), decimals=4) for t in chain_start]
+        trajs = torch.tensor(np.stack([s.squeeze() for s in chain_start])).unsqueeze(0)           # the executed path (1, n, 2)
+        ci = self.metrics_calculator.compute_collision_intensity(trajs.to(self.device), box_centers[:4].to(self.device), box_size[:4].to(self.device))
+        return {'chain_start': chain_start, 'chain_obs': chain_obs, 'start_state_pos': hard_conds[0][:2],
+                'goal_state_pos': hard_conds[self.config.n_support_points - 1][:2], 'computation_time': elapsed,
+                'collision_intensity': bool(ci.any().item()), 'n_replans': len(chain_obs)}
+
+    def run_experiments_as_one_job(self, context_indices, env_index: int = 0):
+        """The listed contexts (repeats allowed) as ONE many-episode job: each episode its own environment, pursuer and numpy stream,
+        all advancing one replan per ``ramp_replan_episodes`` call.  Returns one metrics dict per episode (``computation_time``: the
+        whole job's)."""
+        cfg = self.config
+        torch.cuda.set_device(0)
+        inputs = [self._experiment_inputs(i, env_index) for i in context_indices]
+        self._load_model(2 * cfg.n_samples * len(inputs))
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        results = self.model.run_inference_episodes([x[0] for x in inputs], [x[1] for x in inputs], [x[2] for x in inputs],
+                                                    n_samples=cfg.n_samples, rngs=[np.random.RandomState(e) for e in range(len(inputs))],
+                                                    return_chain=True, max_iteration=cfg.max_replans)
+        torch.cuda.synchronize(); elapsed = time.perf_counter() - t0
+        return [self._experiment_metrics(x[1], obs, start, x[3], x[4], elapsed) for x, (_chain, obs, start) in zip(inputs, results)]
+
+    def run_single_experiment(self, context_idx: int, env_index: int = 0, dataset=None, obstacle_pts=None):
+        """``dataset`` / ``obstacle_pts``: tests inject the reference fixture's environment and cloud; by default they come
+        from the experiment directory like the reference's TrajectoryDataset item."""
+        cfg = self.config
+        torch.cuda.set_device(0)
+        context, hard_conds, obstacle_pts, box_centers, box_size = self._experiment_inputs(context_idx, env_index, dataset, obstacle_pts)
+        n_support_points = cfg.n_support_points
+        traj_normalized = torch.zeros(n_support_points, cfg.state_dim)
+        self._load_model(2 * cfg.n_samples)
         t_start_guide = ceil(cfg.start_guide_steps_fraction * self.model.n_diffusion_steps)
         sample_fn_kwargs = dict(guide=None, n_guide_steps=cfg.n_guide_steps, t_start_guide=t_start_guide, noise_std_extra_schedule_fn=lambda x: 0.5)
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -143,14 +183,8 @@ class DynamicInference:
             obstacle_pts=obstacle_pts, sample_fn=ddpm_sample_fn, **sample_fn_kwargs,
             n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise, max_iteration=cfg.max_replans)
         torch.cuda.synchronize(); elapsed = time.perf_counter() - t0
-        chain_obs.pop()
-        chain_obs = [t.cpu().detach().numpy() for t in chain_obs]
-        chain_start = [np.around(t[:, :2].cpu().detach().numpy(), decimals=4) for t in chain_start]
-        trajs = torch.tensor(np.stack([s.squeeze() for s in chain_start])).unsqueeze(0)           # the executed path (1, n, 2)
-        ci = self.metrics_calculator.compute_collision_intensity(trajs.to(self.device), box_centers[:4].to(self.device), box_size[:4].to(self.device))
         self.last_chain = trajs_normalized_iters
-        return {'chain_start': chain_start, 'chain_obs': chain_obs, 'start_state_pos': start_state_pos, 'goal_state_pos': goal_state_pos,
-                'computation_time': elapsed, 'collision_intensity': bool(ci.any().item()), 'n_replans': len(chain_obs)}
+        return self._experiment_metrics(hard_conds, chain_obs, chain_start, box_centers, box_size, elapsed)
 
 
 def main(argv=None):
@@ -160,6 +194,7 @@ def main(argv=None):
     ap.add_argument("--n-samples", type=int, default=DynamicConfig.n_samples); ap.add_argument("--max-replans", type=int, default=DynamicConfig.max_replans)
     ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=DynamicConfig.unet_input_dim)
     ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=DynamicConfig.unet_dim_mults_option)
+    ap.add_argument("--one-job", metavar="CONTEXTS", help="comma-separated context indices (repeats allowed) to run as ONE many-episode job")
     args = ap.parse_args(argv)
     cfg = DynamicConfig(); cfg.n_samples, cfg.model_id, cfg.max_replans = args.n_samples, args.model_id, args.max_replans
     cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
@@ -171,6 +206,12 @@ def main(argv=None):
             ap.error("--dataset-path and --trained-models-dir (or --make-synthetic DIR) are required")
         cfg.dataset_path, cfg.trained_models_dir = args.dataset_path, args.trained_models_dir
     runner = DynamicInference(cfg)
+    if args.one_job:
+        many = runner.run_experiments_as_one_job([int(v) for v in args.one_job.split(",")])
+        for m in many:
+            print(json.dumps({"n_replans": m["n_replans"], "computation_time": m["computation_time"],
+                              "collision_intensity": m["collision_intensity"], "executed_states": len(m["chain_start"])}))
+        return many, runner
     metrics = runner.run_single_experiment(args.context)
     print(json.dumps({"n_replans": metrics["n_replans"], "computation_time": metrics["computation_time"],
                       "collision_intensity": metrics["collision_intensity"], "executed_states": len(metrics["chain_start"])}))

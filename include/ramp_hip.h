@@ -300,6 +300,48 @@ typedef struct ramp_replan_result {
  * (B) int32 or NULL (1 = in collision).  Synchronises `stream` (the result record is in host memory on return). */
 int ramp_replan(ramp_ctx* ctx, const ramp_replan_params* p, const ramp_replan_state* st, float* best_out, float* batch_out,
                 int32_t* mask_out, ramp_replan_result* result_host, void* stream);
+/* ---- many episodes replanned in lock-step: the evaluation campaign of scripts/inference/inference_dynamic.py (run_multiple_experiments:
+ *      contexts x experiments, each one ddim_p_sample_loop of up to 60 replans with 35 candidates) as ONE job per replan iteration ----
+ * One call = one replan iteration of E independent episodes, in one captured hipGraph of its own: the B = sum of the episodes' candidate
+ * counts rows run ramp_replan's body, every row against the record, executed history, clean plan, static cloud, pursuer cloud, goal and cost
+ * cloud of ITS episode; per row the arithmetic is ramp_replan's.  The row -> latent table is the one given to ramp_set_scenes (B * 2
+ * rows).  `p` carries what the episodes share (schedule, CFG weight, hard-condition layout (n_hard, B, S), smoothing, thresholds, strengths,
+ * n_dyn, n_extra, cost threshold and weights); its B is the whole batch and its static_pts / n_static / cost_cloud / n_cost are not read.
+ * An episode with active = 0 has ended: its rows stay in the batch (initialised from its clean plan, so everything stays finite) and its
+ * selection is skipped.  Removing ended episodes from the batch, or refilling their slots, is not provided. */
+typedef struct ramp_episode_state {
+  int32_t n_hist;                  /* executed states of this episode, pinned at waypoints 0 .. n_hist-1 (1 .. H)         */
+  int32_t stepp;                   /* its current waypoint                                                            */
+  int32_t active;                  /* 0: the episode has ended                                                        */
+  int32_t reserved;
+  float pursuer[2];                /* its pursuer's centre                                                            */
+  float reserved2[2];
+} ramp_episode_state;
+
+typedef struct ramp_episode_batch {
+  int32_t n_episodes;              /* E                                                                               */
+  int32_t reserved;
+  const int32_t* traj_first_host;  /* host (E + 1): first row of each episode, [0] = 0, [E] = p->B, strictly increasing  */
+  const float* noise;              /* device (B, H, S)                                                                */
+  const float* x_clean;            /* device (E, H, S) current plans, or NULL = the previous call's winners           */
+  const float* history;            /* device (E, H, S): rows [0, n_hist) of an episode's block are read               */
+  const ramp_episode_state* state_host;   /* host (E)                                                                 */
+  const double* static_pts;        /* device (sum n_static, 2) float64: the episodes' static APF clouds, concatenated */
+  const int32_t* static_offset_host;      /* host (E + 1): first point of each, [0] = 0, strictly increasing          */
+  const double* dyn_pts_host;      /* host (E, n_dyn, 2) float64: every pursuer's sphere cloud after its update        */
+  const float* cost_cloud;         /* device (sum n_cost, 2): the episodes' static cost clouds, concatenated          */
+  const int32_t* cost_offset_host; /* host (E + 1), [0] = 0, strictly increasing                                      */
+  const int32_t* near_host;        /* host (E): 1 = this episode's extra points join its cost cloud                    */
+  const float* extra_pts_host;     /* host (E, n_extra, 2): read for the near episodes only; NULL if n_extra == 0 or none is near */
+} ramp_episode_batch;
+
+/* best_out device (E,H,S) or NULL; batch_out device (B,H,S) or NULL; mask_out device (B) int32 or NULL; results_host host int32 (E,4) =
+ * per episode {n_free, rank of the winner among the episode's free rows, its row in the whole batch, 0}, {0, -1, -1, 0} when no candidate
+ * is free, {-1, -1, -1, 0} for an ended episode -- in both cases the episode's block of best_out is its previous plan.  result_host:
+ * n_free = free candidates over all active episodes, best_rank = best_row = -1, fell_back as in ramp_replan (the call is repeated whole).
+ * One synchronisation of `stream`: E x 16 bytes of results and the range flag. */
+int ramp_replan_episodes(ramp_ctx* ctx, const ramp_replan_params* p, const ramp_episode_batch* ep, float* best_out, float* batch_out,
+                         int32_t* mask_out, int32_t* results_host, ramp_replan_result* result_host, void* stream);
 /* the selection alone (compute_trajectory_costs + winner with x[0, 2:] = 0) for a finished batch, e.g. the high-level plan
  * (diffusion_model_dynamic.py:524-530): mask / path_len / smooth device (B), best_out device (H,S), result_dev device
  * int32[4] = {n_free, best_rank, best_row, 0}.  Asynchronous. */

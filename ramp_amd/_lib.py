@@ -73,6 +73,20 @@ class RampReplanState(C.Structure):
                 ("reserved", C.c_int32), ("extra_pts_host", C.c_void_p)]
 
 
+class RampEpisodeState(C.Structure):
+    """ramp_episode_state: what differs between the episodes of a many-episode replan (32 bytes, the device record's layout)."""
+    _fields_ = [("n_hist", C.c_int32), ("stepp", C.c_int32), ("active", C.c_int32), ("reserved", C.c_int32),
+                ("pursuer", C.c_float * 2), ("reserved2", C.c_float * 2)]
+
+
+class RampEpisodeBatch(C.Structure):
+    """ramp_episode_batch: the per-episode inputs of ramp_replan_episodes."""
+    _fields_ = [("n_episodes", C.c_int32), ("reserved", C.c_int32), ("traj_first_host", c_i32p), ("noise", C.c_void_p),
+                ("x_clean", C.c_void_p), ("history", C.c_void_p), ("state_host", C.POINTER(RampEpisodeState)),
+                ("static_pts", C.c_void_p), ("static_offset_host", c_i32p), ("dyn_pts_host", C.c_void_p),
+                ("cost_cloud", C.c_void_p), ("cost_offset_host", c_i32p), ("near_host", c_i32p), ("extra_pts_host", C.c_void_p)]
+
+
 class RampProbeGemmArgs(C.Structure):
     """ramp_probe_gemm_args (include/ramp_hip_tools.h): the operand fields of the engine's GEMM launch arguments."""
     _fields_ = [("A", C.c_void_p), ("lda", C.c_int32), ("A2", C.c_void_p), ("lda2", C.c_int32), ("K1", C.c_int32),
@@ -115,6 +129,8 @@ PROTOTYPES = {
     "ramp_philox_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "ramp_replan": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampReplanState), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.POINTER(RampReplanResult), C.c_void_p]),
+    "ramp_replan_episodes": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampEpisodeBatch), C.c_void_p, C.c_void_p,
+                                       C.c_void_p, c_i32p, C.POINTER(RampReplanResult), C.c_void_p]),
     "ramp_select_best": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_replan_costs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -16,36 +16,38 @@ import torch
 from . import _lib
 
 
-def generate_sphere_points(center, radius, num_points, surface_ratio=0.9):
+def generate_sphere_points(center, radius, num_points, surface_ratio=0.9, rng=np.random):
     """Golden-angle ring of ``surface_ratio * num_points`` points plus uniform interior points
-    (APFhelper_dynamic.py:18-39)."""
+    (APFhelper_dynamic.py:18-39).  ``rng``: where the draws come from -- the ``numpy.random`` module (the reference's global
+    stream) or a ``numpy.random.RandomState``, which gives an episode of a many-episode job a stream of its own."""
     n_surf = int(num_points * surface_ratio)
     n_in = num_points - n_surf
     ang = np.pi * (3 - np.sqrt(5)) * np.arange(n_surf)
     xs, ys = radius * np.cos(ang) + center[0], radius * np.sin(ang) + center[1]
     if n_in > 0:
-        r = radius * np.sqrt(np.random.uniform(0, 1, n_in))
-        th = np.random.uniform(0, 2 * np.pi, n_in)
+        r = radius * np.sqrt(rng.uniform(0, 1, n_in))
+        th = rng.uniform(0, 2 * np.pi, n_in)
         xs = np.concatenate((xs, r * np.cos(th) + center[0]))
         ys = np.concatenate((ys, r * np.sin(th) + center[1]))
     return np.column_stack((xs, ys))
 
 
-def generate_box_points(center, size, num_points):
-    """2/3..all of the points uniform on the box perimeter, the rest uniform inside (APFhelper_dynamic.py:41-68)."""
+def generate_box_points(center, size, num_points, rng=np.random):
+    """2/3..all of the points uniform on the box perimeter, the rest uniform inside (APFhelper_dynamic.py:41-68); ``rng`` as in
+    ``generate_sphere_points``."""
     (cx, cy), (w, h) = center, size
     left, right, top, bottom = cx - w / 2, cx + w / 2, cy + h / 2, cy - h / 2
-    n_b = np.random.randint(2 * num_points // 3, num_points + 1)
+    n_b = rng.randint(2 * num_points // 3, num_points + 1)
     n_i = num_points - n_b
     corners = np.array([[left, top], [right, top], [right, bottom], [left, bottom]])
     lens = np.array([w, h, w, h]).repeat(2)
-    pos = np.random.rand(n_b) * lens.sum()
+    pos = rng.rand(n_b) * lens.sum()
     cum = np.cumsum(lens)
     e = np.searchsorted(cum, pos)
     t = (pos - np.concatenate(([0], cum[:-1]))[e]) / lens[e]
     a, b = corners[e % 4], corners[(e + 1) % 4]
     boundary = a + t[:, None] * (b - a)
-    inside = np.random.rand(n_i, 2)
+    inside = rng.rand(n_i, 2)
     inside[:, 0] = inside[:, 0] * w + left
     inside[:, 1] = inside[:, 1] * h + bottom
     return np.concatenate([boundary, inside], axis=0)
@@ -54,14 +56,15 @@ def generate_box_points(center, size, num_points):
 class ObstacleField:
     def __init__(self, static_obstacle_centers=None, static_obstacle_sizes=None,
                  dynamic_obstacle_fn: Optional[Callable] = None, points_per_obstacle=32, distance_threshold=0.1,
-                 distance_threshold_pred=0.2, static_points=None, device="cuda"):
+                 distance_threshold_pred=0.2, static_points=None, device="cuda", rng=np.random):
         self.dynamic_obstacle_fn = dynamic_obstacle_fn
+        self.rng = rng                          # the stream every cloud of this field is drawn from (see generate_sphere_points)
         self.points_per_obstacle = points_per_obstacle
         self.distance_threshold = float(distance_threshold)
         self.distance_threshold_pred = float(distance_threshold_pred)
         self.device = torch.device(device)
         if static_points is None:
-            static_points = np.vstack([generate_box_points(c, s, points_per_obstacle)
+            static_points = np.vstack([generate_box_points(c, s, points_per_obstacle, rng=rng)
                                        for c, s in zip(static_obstacle_centers, static_obstacle_sizes)])
         self.static_obstacle_points = np.asarray(static_points, np.float64)
         self._static_dev = torch.from_numpy(self.static_obstacle_points).to(self.device).contiguous()
@@ -78,7 +81,7 @@ class ObstacleField:
         if self.last_update_time != t:
             center, radius = self.dynamic_obstacle_fn(t, start_pos, replan_guide, best_idx)
             self.dynamic_center = center
-            self.set_dynamic_points(generate_sphere_points(center, radius, self.points_per_obstacle))
+            self.set_dynamic_points(generate_sphere_points(center, radius, self.points_per_obstacle, rng=self.rng))
             self.last_update_time = t
 
 

@@ -59,6 +59,12 @@ struct ApfDynArgs {
   int window = -1;                // >= 0: static pass around the closest waypoint; < 0: waypoints [0, affected)
   int affected = 0;
   double thr_query = 0, thr_force = 0, strength = 0;
+  // one cloud per episode (a job of many episodes, ramp_replan_episodes): trajectory b reads the points of episode episode[b] --
+  // [ep_off[e], ep_off[e + 1]) of `points` (the episodes' clouds concatenated, P = their total, spans clamped to it), or, without
+  // ep_off, the e-th block of P points -- and `goal` is row 0's goal state inside a (B,H,S) batch: row b blends towards its own
+  const int* episode = nullptr;   // (B) episode of each trajectory, or null = one cloud of P points and one goal for all
+  const int* ep_off = nullptr;    // (n_episodes + 1) first point of each episode's cloud, or null = P points each
+  int n_episodes = 0;
 };
 int launch_apf_dynamic(const ApfDynArgs& a, hipStream_t s);
 // receding-horizon replanning (sampler.hip): what changes from replan to replan, resident on the device
@@ -70,6 +76,27 @@ int launch_replan_pin(float* x, HardConds hc, const float* hist, const float* x_
 int launch_replan_sm(float* x, const ReplanState* st, int window, float dt, float max_vel, int B, int H, int S, hipStream_t s);
 int launch_replan_near(const float* x, const ReplanState* st, float thr, int* en, int B, int H, int S, hipStream_t s);
 int launch_replan_goal(float* x0, const float* x, int B, int H, int S, hipStream_t s);
+// The same four kernels for a batch of many episodes advancing in lock-step (ramp_replan_episodes): row b belongs to episode
+// row_ep[b] and reads that episode's record, history (E,H,S) and clean plan (E,H,S); per row the arithmetic is the single-episode
+// kernels' own.  `active` = 0 marks an episode that has ended: its rows still run (from its last plan), its selection is skipped.
+struct EpisodeState { int n_hist; int stepp; int active; int pad0; float pursuer[2]; float pad1[2]; };
+struct EpisodeTable { const EpisodeState* st = nullptr; const int* row_ep = nullptr; int n_episodes = 0; };
+int launch_replan_init_episodes(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
+                                EpisodeTable ep, int B, int H, int S, hipStream_t s);
+int launch_replan_pin_episodes(float* x, HardConds hc, const float* hist, const float* x_clean, EpisodeTable ep, int B, int H, int S,
+                               hipStream_t s);
+int launch_replan_sm_episodes(float* x, EpisodeTable ep, int window, float dt, float max_vel, int B, int H, int S, hipStream_t s);
+int launch_replan_near_episodes(const float* x, EpisodeTable ep, float thr, int* en, int B, int H, int S, hipStream_t s);
+// dst segment e = [seg_off[e], seg_off[e + 1]) (device table, E + 1 entries, seg_off[e] = first static cost point of episode e + e * n_extra):
+// the episode's points of `cloud` (the episodes' static cost clouds, concatenated) followed by its n_extra points of `extra` (E, n_extra, 2).
+// Writes stay inside the P_total points of dst; a wrong table copies wrong points
+int launch_episode_cost_segments(float* dst, const float* cloud, const float* extra, const int* seg_off, int n_episodes, int n_extra,
+                                 int P_total, hipStream_t s);
+// one block per episode over its rows [traj_first[e], traj_first[e + 1]): the replan's selection (winner with x[0, 2:] = 0) into
+// best (E,H,S) and result (E,4) = {n_free, rank, row in the whole batch, 0}; no free row: {0, -1, -1, 0}, inactive: {-1, -1, -1, 0},
+// and in both cases the episode's `best` block stays as it is
+int launch_select_episodes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
+                           const int* traj_first, EpisodeTable ep, float* best, int* result, int B, int H, int S, hipStream_t s);
 int launch_replan_select(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                          float* best, int* result, int B, int H, int S, hipStream_t s);
 // one block per scene of a many-scene batch (rows [traj_first[s], traj_first[s + 1])): result (n_scenes, 4) with the row in the whole

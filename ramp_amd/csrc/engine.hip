@@ -155,6 +155,18 @@ struct ramp_ctx {
   size_t r_cap_B = 0, r_cap_static = 0, r_cap_dyn = 0, r_cap_cost = 0;
   hipGraphExec_t r_graph[2] = {nullptr, nullptr}; std::string r_key;
   bool r_calibrated = false;
+  // many episodes in lock-step (ramp_replan_episodes): the same roles per episode, in buffers, graphs and a key of their own.  e_cap_B
+  // rows, e_cap_E episodes, the clouds in points; e_best_E: the episode count e_best holds winners (or plans) for.  The carried
+  // operand maxima share TABLE_REPLAN_CARRY with ramp_replan: each of the two invalidates the other's calibration
+  float *e_noise = nullptr, *e_hist = nullptr, *e_xclean = nullptr, *e_best = nullptr, *e_plen = nullptr, *e_smooth = nullptr,
+        *e_cost = nullptr, *e_extra = nullptr, *e_hard_val = nullptr;
+  double *e_static = nullptr, *e_dyn = nullptr;
+  int *e_mask = nullptr, *e_en = nullptr, *e_result = nullptr, *e_hard_idx = nullptr, *e_row_ep = nullptr, *e_first = nullptr,
+      *e_static_off = nullptr, *e_cost_off = nullptr;
+  EpisodeState* e_state = nullptr;
+  size_t e_cap_B = 0, e_cap_E = 0, e_cap_static = 0, e_cap_dyn = 0, e_cap_cost = 0, e_cap_extra = 0; int e_best_E = 0;
+  hipGraphExec_t e_graph[2] = {nullptr, nullptr}; std::string e_key;
+  bool e_calibrated = false;
   // scene-encoder scratch
   float* scene_ws = nullptr; size_t scene_ws_cap = 0;
   // bf16x6 weight planes: fp32 weight base pointer -> (planes, element count)
@@ -1095,7 +1107,7 @@ template <class T> int grow(ramp_ctx* c, T*& p, size_t& cap, size_t n) {
   return 0;
 }
 void staging_done(ramp_ctx* c) {
-  if (c->buffers_moved) { c->graph_key.clear(); c->r_key.clear(); c->buffers_moved = false; }
+  if (c->buffers_moved) { c->graph_key.clear(); c->r_key.clear(); c->e_key.clear(); c->buffers_moved = false; }
 }
 
 int ensure_sampler_buffers(ramp_ctx* c, int B, int n_rp, int n_steps, bool chain) {
@@ -1204,7 +1216,7 @@ struct Key {
 enum { CAL_SCORE = 1, CAL_REPLAN = 2, CAL_CANONICAL = 4, CAL_ALL = 7 };
 void invalidate_calibrations(ramp_ctx* c, int what) {
   if (what & CAL_SCORE) c->score_calibrated = false;
-  if (what & CAL_REPLAN) c->r_calibrated = false;
+  if (what & CAL_REPLAN) c->r_calibrated = c->e_calibrated = false;
   if (what & CAL_CANONICAL) c->c_cal_valid = false;
 }
 
@@ -1632,6 +1644,7 @@ static int set_scene_table(ramp_ctx* c, const float* latents, int n_variants, co
   c->scene_epoch++;
   c->graph_key.clear();     // scene changed: cross_bias pointer may have moved
   c->r_key.clear();
+  c->e_key.clear();
   invalidate_calibrations(c, CAL_ALL);
   return rc;
 }
@@ -1963,12 +1976,17 @@ int ramp_sample_scenes(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
 // graph: q_sample of the current plan -> n_steps x [score, CFG + x0, (last step: static + pursuer APF), DDIM update,
 // pinned waypoints] -> smoothing -> collision mask / costs -> selection.  The pursuer's new position is computed by the
 // caller BEFORE the replan: the reference hands the environment x[:, stepp, :2], which is the pinned executed state.
-static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, bool calibrate) {
+// ej != nullptr: the replan of many episodes (ramp_replan_episodes) -- the same sequence on the episode forms of the kernels and the e_*
+// buffers: row b reads the record, history, clean plan, clouds and goal of its own episode
+struct EpisodeJob { int E, P_static, P_cost; };      // episodes; points of the concatenated static APF clouds / of the cost segments
+static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, bool calibrate, const EpisodeJob* ej = nullptr) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S;
-  HardConds hc; hc.idx = c->r_hard_idx; hc.val = c->r_hard_val; hc.n = p->n_hard;
+  HardConds hc; hc.idx = ej ? c->e_hard_idx : c->r_hard_idx; hc.val = ej ? c->e_hard_val : c->r_hard_val; hc.n = p->n_hard;
   HardConds none;
-  CK(launch_replan_init(c->s_x, c->r_xclean, c->r_noise, p->q_sqrt_a, p->q_sqrt_1m_a, c->r_hist, c->r_state, B, H, S, s));
+  EpisodeTable et; if (ej) { et.st = c->e_state; et.row_ep = c->e_row_ep; et.n_episodes = ej->E; }
+  if (ej) CK(launch_replan_init_episodes(c->s_x, c->e_xclean, c->e_noise, p->q_sqrt_a, p->q_sqrt_1m_a, c->e_hist, et, B, H, S, s));
+  else CK(launch_replan_init(c->s_x, c->r_xclean, c->r_noise, p->q_sqrt_a, p->q_sqrt_1m_a, c->r_hist, c->r_state, B, H, S, s));
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   if (h3) {
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
@@ -1978,7 +1996,8 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
   const bool shared = p->n_rp > 1 && c->share_prefix;
   for (int j = 0; j < p->n_steps; ++j) {
     const bool last = p->t[j] == 0;                       // the reference's `i == 0`: smoothing + APF on the final step
-    if (last) CK(launch_replan_sm(c->s_x, c->r_state, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
+    if (last && ej) CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
+    else if (last) CK(launch_replan_sm(c->s_x, c->r_state, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
     // delayed-scaling tables: evaluation j writes table j & 1, the last one TABLE_REPLAN_CARRY, which the first evaluation of the
     // NEXT replan reads: every steady-state replan sees the same pointers, so its graph is captured once
     // (no flag log: a flagged replan is repeated whole by ramp_replan, and the sampling jobs' log stays theirs)
@@ -1992,19 +2011,31 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
     m.mean = nullptr; m.x0 = c->s_x0;
     CK(launch_cfg_mean(m, s));
     if (last) {
-      CK(launch_replan_near(c->s_x, c->r_state, (float)p->thr_pred, c->r_en, B, H, S, s));
+      if (ej) CK(launch_replan_near_episodes(c->s_x, et, (float)p->thr_pred, c->e_en, B, H, S, s));
+      else CK(launch_replan_near(c->s_x, c->r_state, (float)p->thr_pred, c->r_en, B, H, S, s));
       ApfDynArgs a; a.traj = c->s_x0; a.B = B; a.H = H; a.S = S;
       a.points = c->r_static; a.P = p->n_static; a.window = p->window_static; a.affected = H;
       a.thr_query = p->thr_static; a.thr_force = p->thr_static; a.strength = p->strength_static;
+      if (ej) { a.points = c->e_static; a.P = ej->P_static; a.episode = c->e_row_ep; a.ep_off = c->e_static_off; a.n_episodes = ej->E; }
       CK(launch_apf_dynamic(a, s));
       a.points = c->r_dyn; a.P = p->n_dyn; a.window = -1; a.affected = H; a.thr_query = p->thr_pred;
       a.strength = p->strength_pred; a.goal = c->s_x + (size_t)(H - 1) * S; a.enable = c->r_en;
+      if (ej) { a.points = c->e_dyn; a.ep_off = nullptr; a.enable = c->e_en; }      // (n_dyn points per episode; every row its own goal)
       CK(launch_apf_dynamic(a, s));
       CK(launch_replan_goal(c->s_x0, c->s_x, B, H, S, s));
     }
     CK(launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], none,
                           c->s_x, nullptr, B, H, S, s));
-    CK(launch_replan_pin(c->s_x, hc, c->r_hist, c->r_xclean, c->r_state, B, H, S, s));
+    if (ej) CK(launch_replan_pin_episodes(c->s_x, hc, c->e_hist, c->e_xclean, et, B, H, S, s));
+    else CK(launch_replan_pin(c->s_x, hc, c->r_hist, c->r_xclean, c->r_state, B, H, S, s));
+  }
+  if (ej) {
+    CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_final, p->sm_dt, p->sm_max_vel, B, H, S, s));
+    CK(launch_traj_costs_scenes(c->s_x, c->e_cost, c->e_first, c->e_cost_off, ej->E, ej->P_cost, B, H, S, p->cost_thr, c->e_mask, c->e_plen,
+                                c->e_smooth, s));
+    CK(launch_select_episodes(c->s_x, c->e_mask, c->e_plen, c->e_smooth, p->w_smooth, p->w_len, c->e_first, et, c->e_best, c->e_result, B,
+                              H, S, s));
+    return 0;
   }
   CK(launch_replan_sm(c->s_x, c->r_state, p->sm_window_final, p->sm_dt, p->sm_max_vel, B, H, S, s));
   CK(launch_traj_costs(c->s_x, c->r_cost, B, H, S, p->n_cost + p->n_extra, p->cost_thr, c->r_mask, c->r_plen, c->r_smooth, s));
@@ -2064,6 +2095,7 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   RAMP_HIP_CHECK(hipMemcpyAsync(c->r_state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
   c->launches = 0;
   invalidate_calibrations(c, CAL_SCORE);      // (the replans carry their maxima in TABLE_REPLAN_CARRY: the sampling jobs' canonical table survives)
+  c->e_calibrated = false;                    // (a many-episode replan that follows finds this batch's maxima in the carried table, not its own)
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   auto run = [&](bool calibrate) -> int {
     if (!p->use_graph) return replan_body(c, p, s, calibrate);
@@ -2105,6 +2137,152 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   if (best_out) RAMP_HIP_CHECK(hipMemcpyAsync(best_out, c->r_best, HS * 4, hipMemcpyDeviceToDevice, s));
   if (batch_out) RAMP_HIP_CHECK(hipMemcpyAsync(batch_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   if (mask_out) RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->r_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+
+static_assert(sizeof(ramp_episode_state) == sizeof(EpisodeState) && sizeof(EpisodeState) == 32, "the host record is copied as the device record");
+static_assert(offsetof(ramp_episode_state, active) == offsetof(EpisodeState, active) && offsetof(ramp_episode_state, pursuer) == offsetof(EpisodeState, pursuer), "the host record is copied as the device record");
+
+// (E + 1) first-entry table of host memory: [0] = 0, strictly increasing; returns the total through *total
+static int check_offsets(const int32_t* off, int E, const char* what, int* total) {
+  RAMP_REQUIRE(off && off[0] == 0, std::string(what) + ": the offset table must start at 0");
+  for (int e = 0; e < E; ++e) RAMP_REQUIRE(off[e + 1] > off[e], std::string(what) + ": the offset table must be strictly increasing");
+  *total = off[E];
+  return 0;
+}
+
+int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, float* best_out, float* batch_out,
+                         int32_t* mask_out, int32_t* results_host, ramp_replan_result* result_host, void* stream) {
+  RAMP_REQUIRE(c && p && ep && results_host && result_host, "null argument");
+  RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
+  const int B = p->B, E = ep->n_episodes, H = c->cfg.horizon, S = c->cfg.state_dim;
+  RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
+  RAMP_REQUIRE(E >= 1 && E <= B && E <= 65536, "bad episode count (1 .. min(B, 65536))");
+  RAMP_REQUIRE(c->rv_rows >= B * p->n_rp, "the row -> latent table of a many-episode replan comes from ramp_set_scenes (B * n_rp rows)");
+  RAMP_REQUIRE(p->t && p->sqrt_recip && p->sqrt_recipm1 && p->sqrt_a_t && p->sqrt_1m_a_t && p->sqrt_a_prev && p->dir_coef, "missing schedule arrays");
+  RAMP_REQUIRE(p->n_hard >= 0 && p->n_hard <= 16 && (p->n_hard == 0 || (p->hard_idx_host && p->hard_val)), "bad hard conditions");
+  RAMP_REQUIRE(p->n_dyn > 0 && p->n_extra >= 0 && p->n_dyn <= (1 << 20) && p->n_extra <= (1 << 20), "bad clouds");
+  RAMP_REQUIRE(ep->noise && ep->history && ep->state_host && ep->static_pts && ep->dyn_pts_host && ep->cost_cloud && ep->near_host, "missing episode inputs");
+  int n_rows = 0, P_static = 0, n_cost = 0;
+  CK(check_offsets(ep->traj_first_host, E, "traj_first", &n_rows));
+  RAMP_REQUIRE(n_rows == B, "traj_first must end at the batch size");
+  CK(check_offsets(ep->static_offset_host, E, "static clouds", &P_static));
+  CK(check_offsets(ep->cost_offset_host, E, "cost clouds", &n_cost));
+  RAMP_REQUIRE((long)n_cost + (long)E * p->n_extra < (1l << 31) && (long)E * p->n_dyn < (1l << 30), "the concatenated clouds do not fit 32-bit offsets");
+  bool any_near = false;
+  for (int e = 0; e < E; ++e) {
+    const ramp_episode_state& st = ep->state_host[e];
+    RAMP_REQUIRE(st.n_hist >= 1 && st.n_hist <= H && st.stepp >= 0 && st.stepp < H, "bad episode state");
+    any_near |= ep->near_host[e] != 0;
+  }
+  RAMP_REQUIRE(!any_near || p->n_extra == 0 || ep->extra_pts_host, "missing pursuer points");
+  RAMP_REQUIRE(ep->x_clean || (c->e_best && c->e_best_E == E), "no current plans: pass x_clean on the first call");
+  for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
+  hipStream_t s = as_stream(stream);
+  const size_t HS = (size_t)H * S, n = (size_t)B * HS, nE = (size_t)E * HS;
+  const int P_cost = n_cost + E * p->n_extra;
+  // ---- fixed buffers the graphs read
+  CK(ensure_sampler_buffers(c, B, p->n_rp, 0, false));
+  if (!c->e_hard_idx) CK(renew(c, c->e_hard_idx, 16));
+  if ((size_t)B > c->e_cap_B) {
+    CK(renew(c, c->e_noise, n)); CK(renew(c, c->e_plen, B)); CK(renew(c, c->e_smooth, B));
+    CK(renew(c, c->e_mask, B)); CK(renew(c, c->e_en, B)); CK(renew(c, c->e_row_ep, B));
+    CK(renew(c, c->e_hard_val, (size_t)16 * B * S));
+    c->e_cap_B = B;
+  }
+  if ((size_t)E > c->e_cap_E) {
+    CK(renew(c, c->e_hist, nE)); CK(renew(c, c->e_xclean, nE)); CK(renew(c, c->e_best, nE)); CK(renew(c, c->e_state, E));
+    CK(renew(c, c->e_result, (size_t)4 * E)); CK(renew(c, c->e_first, (size_t)E + 1)); CK(renew(c, c->e_static_off, (size_t)E + 1));
+    CK(renew(c, c->e_cost_off, (size_t)E + 1));
+    c->e_cap_E = E;
+  }
+  CK(grow(c, c->e_static, c->e_cap_static, (size_t)P_static * 2));
+  CK(grow(c, c->e_dyn, c->e_cap_dyn, (size_t)E * p->n_dyn * 2));
+  CK(grow(c, c->e_cost, c->e_cap_cost, (size_t)P_cost * 2));
+  CK(grow(c, c->e_extra, c->e_cap_extra, std::max<size_t>((size_t)E * p->n_extra * 2, 2)));      // (staging only: no graph reads it)
+  staging_done(c);
+  // ---- this call's inputs.  Host staging lives until the synchronisation below.
+  std::vector<int> row_ep(B), cost_off(E + 1);
+  std::vector<float> extra((size_t)E * p->n_extra * 2, 1.0e9f);      // far-away fillers, as in ramp_replan, where the pursuer is not near
+  for (int e = 0; e < E; ++e) {
+    for (int b = ep->traj_first_host[e]; b < ep->traj_first_host[e + 1]; ++b) row_ep[b] = e;
+    cost_off[e] = ep->cost_offset_host[e] + e * p->n_extra;
+    if (ep->near_host[e] && p->n_extra)
+      std::copy(ep->extra_pts_host + (size_t)e * p->n_extra * 2, ep->extra_pts_host + (size_t)(e + 1) * p->n_extra * 2, extra.begin() + (size_t)e * p->n_extra * 2);
+  }
+  cost_off[E] = P_cost;
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_noise, ep->noise, n * 4, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hist, ep->history, nE * 4, hipMemcpyDeviceToDevice, s));
+  if (ep->x_clean) {      // (also what `best` holds for an episode that selects nothing in this call)
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->e_xclean, ep->x_clean, nE * 4, hipMemcpyDeviceToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->e_best, ep->x_clean, nE * 4, hipMemcpyDeviceToDevice, s));
+  } else {
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->e_xclean, c->e_best, nE * 4, hipMemcpyDeviceToDevice, s));
+  }
+  c->e_best_E = E;
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_row_ep, row_ep.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_first, ep->traj_first_host, ((size_t)E + 1) * 4, hipMemcpyHostToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_state, ep->state_host, (size_t)E * sizeof(EpisodeState), hipMemcpyHostToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_static, ep->static_pts, (size_t)P_static * 16, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_static_off, ep->static_offset_host, ((size_t)E + 1) * 4, hipMemcpyHostToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_dyn, ep->dyn_pts_host, (size_t)E * p->n_dyn * 16, hipMemcpyHostToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_cost_off, cost_off.data(), ((size_t)E + 1) * 4, hipMemcpyHostToDevice, s));
+  // the cost segments (an episode's static cloud, then its n_extra slots) in one copy and one launch, whatever the number of episodes
+  if (p->n_extra) RAMP_HIP_CHECK(hipMemcpyAsync(c->e_extra, extra.data(), extra.size() * 4, hipMemcpyHostToDevice, s));
+  CK(launch_episode_cost_segments(c->e_cost, ep->cost_cloud, c->e_extra, c->e_cost_off, E, p->n_extra, P_cost, s));
+  if (p->n_hard) {
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hard_val, p->hard_val, (size_t)p->n_hard * B * S * 4, hipMemcpyDeviceToDevice, s));
+  }
+  c->launches = 0;
+  invalidate_calibrations(c, CAL_SCORE);
+  c->r_calibrated = false;                    // (the carried table now holds this batch's maxima)
+  const bool h3 = c->gemm_mode == 2 && !c->force_x6;
+  const EpisodeJob ej{E, P_static, P_cost};
+  auto run = [&](bool calibrate) -> int {
+    if (!p->use_graph) return replan_body(c, p, s, calibrate, &ej);
+    Key key;      // everything baked into the nodes: ramp_replan's fields, the episode count, the row table and the clouds' totals
+    key.put(p->B); key.put(p->n_steps); key.put(p->w); key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps);
+    key.put(p->sqrt_recipm1, p->n_steps); key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps);
+    key.put(p->sqrt_a_prev, p->n_steps); key.put(p->dir_coef, p->n_steps); key.put(p->q_sqrt_a); key.put(p->q_sqrt_1m_a);
+    key.put(p->clip_denoised); key.put(p->predict_x0); key.put(p->n_hard); key.put(p->sm_window_last); key.put(p->sm_window_final); key.put(p->sm_dt);
+    key.put(p->sm_max_vel); key.put(p->n_dyn); key.put(p->thr_static); key.put(p->thr_pred);
+    key.put(p->strength_static); key.put(p->strength_pred); key.put(p->window_static); key.put(p->n_extra);
+    key.put(p->cost_thr); key.put(p->w_smooth); key.put(p->w_len); key.put(c->force_x6);
+    key.put(E); key.put(ep->traj_first_host, (size_t)E + 1); key.put(P_static); key.put(P_cost);
+    if (key.bytes != c->e_key) { drop_graphs(c->e_graph, 2); c->e_key = key.bytes; }
+    return replay(&c->e_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, &ej); });
+  };
+  CK(run(h3 && (!c->e_calibrated || p->n_steps == 1)));
+  // ---- the one read-back: E result records + the range flag
+  std::vector<int> back((size_t)4 * E + 1, 0);
+  RAMP_HIP_CHECK(hipMemcpyAsync(back.data(), c->e_result, (size_t)E * 16, hipMemcpyDeviceToHost, s));
+  if (h3) RAMP_HIP_CHECK(hipMemcpyAsync(back.data() + 4 * E, c->range_flag, 4, hipMemcpyDeviceToHost, s));
+  RAMP_HIP_CHECK(hipStreamSynchronize(s));
+  result_host->fell_back = 0;
+  if (h3 && back[4 * E]) {
+    // as in ramp_replan: the whole call again (same inputs) on the bf16x6 kernels, and the next one calibrates.  The flagged run left
+    // winners in e_best: back to the plans it started from first, which is what an episode that selects nothing keeps
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->e_best, c->e_xclean, nE * 4, hipMemcpyDeviceToDevice, s));
+    c->force_x6 = 1;
+    int rc = replan_body(c, p, s, false, &ej);
+    c->force_x6 = 0;
+    CK(rc);
+    const int flag = back[4 * E];
+    RAMP_HIP_CHECK(hipMemcpyAsync(back.data(), c->e_result, (size_t)E * 16, hipMemcpyDeviceToHost, s));
+    RAMP_HIP_CHECK(hipStreamSynchronize(s));
+    c->e_calibrated = false;
+    result_host->fell_back = flag;
+  } else if (h3) {
+    c->e_calibrated = true;
+  }
+  int n_free = 0;
+  for (int e = 0; e < E; ++e) if (back[4 * e] > 0) n_free += back[4 * e];
+  std::copy(back.begin(), back.begin() + (size_t)4 * E, results_host);
+  result_host->n_free = n_free; result_host->best_rank = -1; result_host->best_row = -1;
+  if (best_out) RAMP_HIP_CHECK(hipMemcpyAsync(best_out, c->e_best, nE * 4, hipMemcpyDeviceToDevice, s));
+  if (batch_out) RAMP_HIP_CHECK(hipMemcpyAsync(batch_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
+  if (mask_out) RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->e_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

@@ -266,7 +266,18 @@ int launch_apf(const ApfArgs& a, hipStream_t s) {
 // waypoint, the pursuer's position) lives in a small device record, so the captured graph of one replan never changes.
 // ------------------------------------------------------------------------------------------
 // x = q_sample(repeat(x_clean), t) = sqrt_ac[t] * x_clean + sqrt_1m_ac[t] * noise (diffusion_model_dynamic.py:671-680),
-// then x[:, 0, 2:] = 0, the executed history, and the goal waypoint of the clean plan (:540-546)
+// then x[:, 0, 2:] = 0, the executed history, and the goal waypoint of the clean plan (:540-546).
+// Each of the four steps below is ONE per-row rule (replan_*_row) behind two kernels: the single-episode one, whose rows all read
+// the same record / history / clean plan, and the many-episode one (ramp_replan_episodes), whose row b reads those of episode
+// row_ep[b].  x_clean, hist: the (H,S) blocks of the row's own episode.
+__device__ __forceinline__ float replan_init_value(const float* __restrict__ x_clean, const float* __restrict__ hist, float nz,
+                                                   float sa, float s1a, int n_hist, int h, int si, int H, int S) {
+  float v = add(mul(sa, x_clean[h * S + si]), mul(s1a, nz));
+  if (h == 0 && si >= 2) v = 0.f;
+  if (h < n_hist) v = hist[h * S + si];
+  if (h == H - 1) v = x_clean[h * S + si];
+  return v;
+}
 __global__ __launch_bounds__(256) void replan_init_kernel(float* __restrict__ x, const float* __restrict__ x_clean,
                                                            const float* __restrict__ noise, float sa, float s1a,
                                                            const float* __restrict__ hist, const ReplanState* __restrict__ st,
@@ -275,15 +286,28 @@ __global__ __launch_bounds__(256) void replan_init_kernel(float* __restrict__ x,
   const long n = (long)B * H * S;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
     const int si = (int)(idx % S); const int h = (int)((idx / S) % H);
-    float v = add(mul(sa, x_clean[h * S + si]), mul(s1a, noise[idx]));
-    if (h == 0 && si >= 2) v = 0.f;
-    if (h < n_hist) v = hist[h * S + si];
-    if (h == H - 1) v = x_clean[h * S + si];
-    x[idx] = v;
+    x[idx] = replan_init_value(x_clean, hist, noise[idx], sa, s1a, n_hist, h, si, H, S);
+  }
+}
+__global__ __launch_bounds__(256) void replan_init_episodes_kernel(float* __restrict__ x, const float* __restrict__ x_clean,
+                                                                    const float* __restrict__ noise, float sa, float s1a,
+                                                                    const float* __restrict__ hist, EpisodeTable ep, int B, int H, int S) {
+  const long n = (long)B * H * S, HS = (long)H * S;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
+    const int si = (int)(idx % S); const int h = (int)((idx / S) % H);
+    const int e = ep.row_ep[idx / HS];
+    x[idx] = replan_init_value(x_clean + e * HS, hist + e * HS, noise[idx], sa, s1a, ep.st[e].n_hist, h, si, H, S);
   }
 }
 // after every DDIM step: apply_hard_conditioning, then the executed history, the goal of the clean plan, x[:, 0, 2:] = 0
 // (diffusion_model_dynamic.py:563-568); one thread per (trajectory, state component), the pinned waypoints in order
+__device__ __forceinline__ void replan_pin_row(float* __restrict__ xb, const HardConds& hc, const float* __restrict__ hist,
+                                               const float* __restrict__ x_clean, int n_hist, int b, int si, int B, int H, int S) {
+  for (int k = 0; k < hc.n; ++k) xb[hc.idx[k] * S + si] = hc.val[((long)k * B + b) * S + si];
+  for (int h = 0; h < n_hist; ++h) xb[h * S + si] = hist[h * S + si];
+  xb[(H - 1) * S + si] = x_clean[(H - 1) * S + si];
+  if (si >= 2) xb[si] = 0.f;
+}
 __global__ __launch_bounds__(256) void replan_pin_kernel(float* __restrict__ x, HardConds hc, const float* __restrict__ hist,
                                                           const float* __restrict__ x_clean, const ReplanState* __restrict__ st,
                                                           int B, int H, int S) {
@@ -291,21 +315,21 @@ __global__ __launch_bounds__(256) void replan_pin_kernel(float* __restrict__ x, 
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= B * S) return;
   const int b = idx / S, si = idx - b * S;
-  float* xb = x + (long)b * H * S;
-  for (int k = 0; k < hc.n; ++k) xb[hc.idx[k] * S + si] = hc.val[((long)k * B + b) * S + si];
-  for (int h = 0; h < n_hist; ++h) xb[h * S + si] = hist[h * S + si];
-  xb[(H - 1) * S + si] = x_clean[(H - 1) * S + si];
-  if (si >= 2) xb[si] = 0.f;
+  replan_pin_row(x + (long)b * H * S, hc, hist, x_clean, n_hist, b, si, B, H, S);
+}
+__global__ __launch_bounds__(256) void replan_pin_episodes_kernel(float* __restrict__ x, HardConds hc, const float* __restrict__ hist,
+                                                                   const float* __restrict__ x_clean, EpisodeTable ep, int B, int H, int S) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= B * S) return;
+  const int b = idx / S, si = idx - b * S;
+  const int e = ep.row_ep[b];
+  const long HS = (long)H * S;
+  replan_pin_row(x + b * HS, hc, hist + e * HS, x_clean + e * HS, ep.st[e].n_hist, b, si, B, H, S);
 }
 // sm(): velocity-limited straight-line states between waypoints stepp and stepp + window, written to
 // stepp + 1 .. stepp + window (diffusion_model_dynamic.py:192-214), torch's fp32 evaluation order
-__global__ __launch_bounds__(256) void replan_sm_kernel(float* __restrict__ x, const ReplanState* __restrict__ st, int window,
-                                                         float dt, float max_vel, int B, int H, int S) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  const int stepp = st->stepp;
+__device__ __forceinline__ void replan_sm_row(float* __restrict__ xb, int stepp, int window, float dt, float max_vel, int H, int S) {
   if (stepp + window >= H) return;                        // the reference would index past the horizon here
-  float* xb = x + (long)b * H * S;
   const float* s1 = xb + stepp * S; const float* s2 = xb + (stepp + window) * S;
   const float dx = sub(s2[0], s1[0]), dy = sub(s2[1], s1[1]);
   const float dist = sqrtf(add(mul(dx, dx), mul(dy, dy)));
@@ -321,15 +345,36 @@ __global__ __launch_bounds__(256) void replan_sm_kernel(float* __restrict__ x, c
     o[2] = vx; o[3] = vy;
   }
 }
+__global__ __launch_bounds__(256) void replan_sm_kernel(float* __restrict__ x, const ReplanState* __restrict__ st, int window,
+                                                         float dt, float max_vel, int B, int H, int S) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  replan_sm_row(x + (long)b * H * S, st->stepp, window, dt, max_vel, H, S);
+}
+__global__ __launch_bounds__(256) void replan_sm_episodes_kernel(float* __restrict__ x, EpisodeTable ep, int window, float dt,
+                                                                  float max_vel, int B, int H, int S) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  replan_sm_row(x + (long)b * H * S, ep.st[ep.row_ep[b]].stepp, window, dt, max_vel, H, S);
+}
 // en[b] = || x[b, stepp, :2] - pursuer || < thr   (diffusion_model_dynamic.py:414-420: which trajectories get the
 // pursuer pass); x0[:, -1] = x[:, -1] afterwards is replan_goal_kernel
+__device__ __forceinline__ int replan_near_row(const float* __restrict__ q, const float* __restrict__ pursuer, float thr) {
+  const float dx = sub(q[0], pursuer[0]), dy = sub(q[1], pursuer[1]);
+  return sqrtf(add(mul(dx, dx), mul(dy, dy))) < thr;
+}
 __global__ __launch_bounds__(256) void replan_near_kernel(const float* __restrict__ x, const ReplanState* __restrict__ st,
                                                            float thr, int* __restrict__ en, int B, int H, int S) {
   const int b = blockIdx.x * 256 + threadIdx.x;
   if (b >= B) return;
-  const float* q = x + ((long)b * H + st->stepp) * S;
-  const float dx = sub(q[0], st->pursuer[0]), dy = sub(q[1], st->pursuer[1]);
-  en[b] = sqrtf(add(mul(dx, dx), mul(dy, dy))) < thr;
+  en[b] = replan_near_row(x + ((long)b * H + st->stepp) * S, st->pursuer, thr);
+}
+__global__ __launch_bounds__(256) void replan_near_episodes_kernel(const float* __restrict__ x, EpisodeTable ep, float thr,
+                                                                    int* __restrict__ en, int B, int H, int S) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const EpisodeState* st = ep.st + ep.row_ep[b];
+  en[b] = replan_near_row(x + ((long)b * H + st->stepp) * S, st->pursuer, thr);
 }
 __global__ __launch_bounds__(256) void replan_goal_kernel(float* __restrict__ x0, const float* __restrict__ x, int B, int H, int S) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -341,8 +386,9 @@ __global__ __launch_bounds__(256) void replan_goal_kernel(float* __restrict__ x0
 // collision-free ones, total = w_s * smooth + w_l * length, first minimum; the winner is gathered with x[0, 2:] = 0
 // (diffusion_model_dynamic.py:607).  One block of 1024 threads over rows [0, B) of the arrays it is given.
 // result: {n_free, rank of the winner among the free ones, its row + row0, 0}.  SCENES: the static flow of a many-scene batch --
-// the winner is copied unmodified, a block with no free row gets a NaN `best` and {0, -1, -1, 0}.
-template <bool SCENES>
+// the winner is copied unmodified, a block with no free row gets a NaN `best` and {0, -1, -1, 0}.  EPISODE: one episode of a many-episode
+// replan -- the replan's rule on the winner (x[0, 2:] = 0), result[3] = 0 written, and without a free row `best` stays as it is.
+template <bool SCENES, bool EPISODE = false>
 __device__ __forceinline__ void select_block(const float* __restrict__ traj, const int* __restrict__ mask,
                                              const float* __restrict__ plen, const float* __restrict__ smooth,
                                              float w_s, float w_l, float* __restrict__ best,
@@ -399,7 +445,7 @@ __device__ __forceinline__ void select_block(const float* __restrict__ traj, con
   __syncthreads();
   const int bb = s_best;
   if (bb == 0x7fffffff) {
-    if (tid == 0) { result[0] = 0; result[1] = -1; result[2] = -1; if (SCENES) result[3] = 0; }
+    if (tid == 0) { result[0] = 0; result[1] = -1; result[2] = -1; if (SCENES || EPISODE) result[3] = 0; }
     if (SCENES) for (int e = tid; e < H * S; e += 1024) best[e] = __int_as_float(0x7fc00000);
     return;
   }
@@ -409,7 +455,7 @@ __device__ __forceinline__ void select_block(const float* __restrict__ traj, con
   for (int m = 32; m >= 1; m >>= 1) rank += __shfl_xor(rank, m);
   if (lane == 0) r_cnt[wave] = rank;
   __syncthreads();
-  if (tid == 0) { int r = 0; for (int w = 0; w < 16; ++w) r += r_cnt[w]; result[0] = s_free; result[1] = r; result[2] = bb + row0; if (SCENES) result[3] = 0; }
+  if (tid == 0) { int r = 0; for (int w = 0; w < 16; ++w) r += r_cnt[w]; result[0] = s_free; result[1] = r; result[2] = bb + row0; if (SCENES || EPISODE) result[3] = 0; }
   if (traj == nullptr) return;                            // selection from gathered costs only (multi-GPU merge): the winner's owner holds the row
   for (int e = tid; e < H * S; e += 1024) {
     float v = traj[(long)bb * H * S + e];
@@ -434,6 +480,20 @@ __global__ __launch_bounds__(1024) void select_scenes_kernel(const float* __rest
   select_block<true>(traj + (long)first * H * S, mask + first, plen + first, smooth + first, w_s, w_l, best + (long)s * H * S,
                      result + 4 * s, end - first, H, S, first);
 }
+// the replan's rule, one block per episode of a many-episode replan over the episode's rows; an episode that has ended is skipped
+__global__ __launch_bounds__(1024) void select_episodes_kernel(const float* __restrict__ traj, const int* __restrict__ mask,
+                                                                const float* __restrict__ plen, const float* __restrict__ smooth,
+                                                                float w_s, float w_l, const int* __restrict__ traj_first, EpisodeTable ep,
+                                                                float* __restrict__ best, int* __restrict__ result, int B, int H, int S) {
+  const int e = blockIdx.x;
+  if (!ep.st[e].active) {                                   // (uniform over the block)
+    if (threadIdx.x < 4) result[4 * e + threadIdx.x] = threadIdx.x < 3 ? -1 : 0;
+    return;
+  }
+  const int first = min(max(traj_first[e], 0), B), end = min(max(traj_first[e + 1], first), B);
+  select_block<false, true>(traj + (long)first * H * S, mask + first, plen + first, smooth + first, w_s, w_l, best + (long)e * H * S,
+                            result + 4 * e, end - first, H, S, first);
+}
 
 int launch_replan_init(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
                        const ReplanState* st, int B, int H, int S, hipStream_t s) {
@@ -455,6 +515,46 @@ int launch_replan_sm(float* x, const ReplanState* st, int window, float dt, floa
 }
 int launch_replan_near(const float* x, const ReplanState* st, float thr, int* en, int B, int H, int S, hipStream_t s) {
   hipLaunchKernelGGL(replan_near_kernel, dim3((B + 255) / 256), dim3(256), 0, s, x, st, thr, en, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+static int check_episode_table(const EpisodeTable& ep, int B) {
+  RAMP_REQUIRE(ep.st && ep.row_ep && ep.n_episodes > 0 && ep.n_episodes <= B, "bad episode table");
+  return 0;
+}
+int launch_replan_init_episodes(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
+                                EpisodeTable ep, int B, int H, int S, hipStream_t s) {
+  if (int rc = check_episode_table(ep, B)) return rc;
+  hipLaunchKernelGGL(replan_init_episodes_kernel, dim3(ew_grid((long)B * H * S)), dim3(256), 0, s, x, x_clean, noise, sa, s1a, hist, ep, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_replan_pin_episodes(float* x, HardConds hc, const float* hist, const float* x_clean, EpisodeTable ep, int B, int H, int S,
+                               hipStream_t s) {
+  if (int rc = check_episode_table(ep, B)) return rc;
+  hipLaunchKernelGGL(replan_pin_episodes_kernel, dim3((B * S + 255) / 256), dim3(256), 0, s, x, hc, hist, x_clean, ep, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_replan_sm_episodes(float* x, EpisodeTable ep, int window, float dt, float max_vel, int B, int H, int S, hipStream_t s) {
+  RAMP_REQUIRE(S >= 4 && window >= 1, "sm needs (x, y, vx, vy) states");
+  if (int rc = check_episode_table(ep, B)) return rc;
+  hipLaunchKernelGGL(replan_sm_episodes_kernel, dim3((B + 255) / 256), dim3(256), 0, s, x, ep, window, dt, max_vel, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_replan_near_episodes(const float* x, EpisodeTable ep, float thr, int* en, int B, int H, int S, hipStream_t s) {
+  if (int rc = check_episode_table(ep, B)) return rc;
+  hipLaunchKernelGGL(replan_near_episodes_kernel, dim3((B + 255) / 256), dim3(256), 0, s, x, ep, thr, en, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_select_episodes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
+                           const int* traj_first, EpisodeTable ep, float* best, int* result, int B, int H, int S, hipStream_t s) {
+  RAMP_REQUIRE(B > 0 && H > 0 && S >= 2 && traj && best && result && traj_first, "bad selection dims");
+  if (int rc = check_episode_table(ep, B)) return rc;
+  hipLaunchKernelGGL(select_episodes_kernel, dim3(ep.n_episodes), dim3(1024), 0, s, traj, mask, plen, smooth, w_s, w_l, traj_first, ep,
+                     best, result, B, H, S);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -484,6 +584,10 @@ int launch_select_scenes(const float* traj, const int* mask, const float* plen, 
 // waypoint ci nearest to the cloud; window < 0: pursuer pass over waypoints [0, affected) with the 0.9 / 0.1
 // avoid / goal blend.  Each waypoint update is independent (no accumulation across waypoints).
 // ------------------------------------------------------------------------------------------
+// EP: the trajectory's own episode (ApfDynArgs.episode): block b streams only its episode's points, indexed from that cloud's first
+// point, and blends towards its own goal, so every comparison, tie and sum is the one-cloud kernel's on that cloud.  An episode
+// index outside the table leaves the trajectory as it is.
+template <bool EP>
 __global__ __launch_bounds__(256) void apf_dyn_kernel(ApfDynArgs a) {
   __shared__ double2 cl[APF_TILE];
   __shared__ double best_d2[APF_MAXH];
@@ -491,6 +595,17 @@ __global__ __launch_bounds__(256) void apf_dyn_kernel(ApfDynArgs a) {
   __shared__ int s_lo, s_hi;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (a.enable && !a.enable[b]) return;
+  if (EP) {
+    const int e = a.episode[b];
+    if (e < 0 || e >= a.n_episodes) return;                  // (uniform over the block)
+    if (a.ep_off) {
+      const int p0 = min(max(a.ep_off[e], 0), a.P), p1 = min(max(a.ep_off[e + 1], p0), a.P);
+      a.points += 2l * p0; a.P = p1 - p0;
+    } else {
+      a.points += 2l * e * a.P;
+    }
+    if (a.goal) a.goal += (long)b * a.H * a.S;
+  }
   float* tr = a.traj + (long)b * a.H * a.S;
   const int nq = a.window >= 0 ? a.H : min(a.affected, a.H);
   for (int h = tid; h < a.H; h += 256) { best_d2[h] = 1.0e300; best_i[h] = -1; }
@@ -550,7 +665,9 @@ __global__ __launch_bounds__(256) void apf_dyn_kernel(ApfDynArgs a) {
 }
 int launch_apf_dynamic(const ApfDynArgs& a, hipStream_t s) {
   RAMP_REQUIRE(a.B > 0 && a.H > 0 && a.H <= APF_MAXH && a.S >= 2 && a.P > 0 && a.traj && a.points, "bad dynamic-APF dims");
-  hipLaunchKernelGGL(apf_dyn_kernel, dim3(a.B), dim3(256), 0, s, a);
+  RAMP_REQUIRE(!a.episode || a.n_episodes > 0, "dynamic APF with per-trajectory episodes needs their count");
+  if (a.episode) hipLaunchKernelGGL(apf_dyn_kernel<true>, dim3(a.B), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(apf_dyn_kernel<false>, dim3(a.B), dim3(256), 0, s, a);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
@@ -616,6 +733,27 @@ __global__ __launch_bounds__(256) void traj_costs_scenes_kernel(const float* __r
   while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (traj_first[mid] <= b) lo = mid; else hi = mid - 1; }
   const int p0 = min(max(cloud_off[lo], 0), P_total), p1 = min(max(cloud_off[lo + 1], p0), P_total);
   traj_costs_block(traj + (long)b * H * S, cloud + 2 * (long)p0, H, S, p1 - p0, thr, mask + b, plen + b, smooth + b);
+}
+// the cost segments of a many-episode replan: block e copies episode e's static cost points, then its n_extra extra points
+__global__ __launch_bounds__(256) void episode_cost_segments_kernel(float2* __restrict__ dst, const float2* __restrict__ cloud,
+                                                                     const float2* __restrict__ extra, const int* __restrict__ seg_off,
+                                                                     int n_extra, int P_total) {
+  const int e = blockIdx.x;
+  const int d0 = min(max(seg_off[e], 0), P_total), d1 = min(max(seg_off[e + 1], d0), P_total);
+  const int nc = max(d1 - d0 - n_extra, 0);                 // static points of this episode
+  const long s0 = (long)d0 - (long)e * n_extra;              // its first point in `cloud`
+  if (s0 < 0) return;
+  for (int i = threadIdx.x; i < d1 - d0; i += 256)
+    dst[d0 + i] = i < nc ? cloud[s0 + i] : extra[(long)e * n_extra + (i - nc)];
+}
+int launch_episode_cost_segments(float* dst, const float* cloud, const float* extra, const int* seg_off, int n_episodes, int n_extra,
+                                 int P_total, hipStream_t s) {
+  RAMP_REQUIRE(dst && cloud && seg_off && n_episodes > 0 && n_extra >= 0 && P_total > 0 && (extra || n_extra == 0), "bad cost segments");
+  RAMP_REQUIRE(((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(cloud) | reinterpret_cast<uintptr_t>(extra)) & 7) == 0, "cost points must be 8-byte aligned");
+  hipLaunchKernelGGL(episode_cost_segments_kernel, dim3(n_episodes), dim3(256), 0, s, reinterpret_cast<float2*>(dst),
+                     reinterpret_cast<const float2*>(cloud), reinterpret_cast<const float2*>(extra), seg_off, n_extra, P_total);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 int launch_traj_costs(const float* traj, const float* cloud, int B, int H, int S, int P, float thr, int* mask,
                       float* plen, float* smooth, hipStream_t s) {

@@ -1,6 +1,8 @@
 """DynamicGaussianDiffusionModel (mpd/models/diffusion_models/diffusion_model_dynamic.py:24-680), re-exported by ``ramp_amd.diffusion``.
 Its planner exists twice -- ``ddim_p_sample_loop`` on ``ramp_sample`` / ``ramp_replan`` and ``ddim_p_sample_loop_eager``, the host
-restatement it is tested against -- and the two share only what is literally the same: ``_Episode``, ``_replan_from_scratch``."""
+restatement it is tested against -- and the two share only what is literally the same: ``_Episode``, ``_replan_from_scratch``.
+``run_inference_episodes`` advances MANY episodes in lock-step on ``ramp_sample_scenes`` / ``ramp_replan_episodes``; it shares the
+per-episode environment step (``_environment_step``) and book-keeping (``_Episode``) with the one-episode planner."""
 import warnings
 
 import ctypes as C
@@ -153,9 +155,10 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
                 + extract(self.sqrt_one_minus_alphas_cumprod, t, x_start.shape) * noise)
 
     # ------------------------------------------------------------------ receding-horizon planner
-    def _obstacle_field(self, context):
+    def _obstacle_field(self, context, rng=np.random):
         """Lazily build the APF clouds exactly where the reference does (diffusion_model_dynamic.py:391-411): static
-        boxes from context['static_obstacle_centers'/'sizes'], pursuer from the env's moving sphere field."""
+        boxes from context['static_obstacle_centers'/'sizes'], pursuer from the env's moving sphere field.  ``rng``: the stream the
+        field draws its clouds from when it is built here (an episode of a many-episode job has its own)."""
         from .apf_dynamic import ObstacleField
         if 'obstacle_field' not in context:
             sphere = context['dataset'].env.obj_extra_list[0].fields[0]
@@ -170,7 +173,7 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
             context['obstacle_field'] = ObstacleField(context['static_obstacle_centers'], context['static_obstacle_sizes'],
                                                       dynamic_obstacle_fn, c['points_per_obstacle'],
                                                       distance_threshold=c['threshold_static'],
-                                                      distance_threshold_pred=c['threshold_pred'], device=self._device())
+                                                      distance_threshold_pred=c['threshold_pred'], device=self._device(), rng=rng)
         return context['obstacle_field']
 
     def _step(self, x, hard_conds, context, i, obstacle_pts, traj_normalized, forward_t, use_apf):
@@ -249,22 +252,30 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         p.use_graph = int(self.use_graph)
         return p
 
-    def _replan_state(self, p, k, context, ep: _Episode, B, best_host, noise, x_clean, hist_dev):
-        """The environment step of the reference's last DDIM step (diffusion_model_dynamic.py:396-411) as a ramp_replan_state: the
-        pursuer sees x[:, stepp, :2], which is the pinned executed state of every candidate.  Returns (state, near, its host arrays)."""
+    def _environment_step(self, k, context, ep: _Episode, B, best_host, rng=np.random):
+        """One episode's environment step before replan ``k`` (diffusion_model_dynamic.py:396-411), in the reference's order of host
+        random draws: the pursuer's dynamics see x[:, stepp, :2] -- the pinned executed state of all B candidates -- and its sphere
+        cloud is re-sampled (``update_dynamic``), then the near-check draws the sphere points that join the cost cloud.
+        Returns (field, pursuer centre float64 (2), pursuer cloud float64 (n_dyn, 2), near, extra cost points float32 (64, 2) or None)."""
         from .apf_dynamic import generate_sphere_points
-        field = self._obstacle_field(context)
-        p.static_pts, p.n_static = _lib.ptr(field._static_dev), field._static_dev.shape[0]
+        field = self._obstacle_field(context, rng)
         field.update_dynamic(k, ep.executed_history[-1][:, :2].expand(B, 2).clone(), replan_guide=True)
         centre = np.asarray(field.dynamic_center, np.float64)
         dyn = np.ascontiguousarray(field.dynamic_points, np.float64)
-        assert dyn.shape == (p.n_dyn, 2)
         sphere = ep.sphere
         near = bool(np.linalg.norm(best_host[ep.stepp, :2] - sphere.centers[0].cpu().numpy()) < ep.distance_threshold_pred)
         extra = None
         if near:
             extra = np.ascontiguousarray(generate_sphere_points(sphere.centers[0].cpu().numpy(),
-                                                                sphere.radii[0].cpu().numpy(), 64), np.float32)
+                                                                sphere.radii[0].cpu().numpy(), 64, rng=rng), np.float32)
+        return field, centre, dyn, near, extra
+
+    def _replan_state(self, p, k, context, ep: _Episode, B, best_host, noise, x_clean, hist_dev):
+        """The environment step of the reference's last DDIM step (diffusion_model_dynamic.py:396-411) as a ramp_replan_state: the
+        pursuer sees x[:, stepp, :2], which is the pinned executed state of every candidate.  Returns (state, near, its host arrays)."""
+        field, centre, dyn, near, extra = self._environment_step(k, context, ep, B, best_host)
+        p.static_pts, p.n_static = _lib.ptr(field._static_dev), field._static_dev.shape[0]
+        assert dyn.shape == (p.n_dyn, 2)
         st = _lib.RampReplanState()
         st.noise, st.x_clean, st.history = _lib.ptr(noise), _lib.ptr(x_clean), _lib.ptr(hist_dev)
         st.n_hist, st.stepp = len(ep.executed_history), ep.stepp
@@ -452,6 +463,198 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
             if ep.reached(torch.norm(x[ep.stepp - 1, :2] - x[-1, :2])):
                 break
         return ep.result(x)
+
+
+    # ------------------------------------------------------------------ many episodes in lock-step, one graph per replan iteration
+    def _check_episode_lists(self, contexts, hard_conds, obstacle_pts, n_samples, rngs):
+        """The refusals of ``run_inference_episodes`` that need no device work: returns the per-episode candidate counts."""
+        import torch.distributed as tdist
+        if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+            raise NotImplementedError("run_inference_episodes under a multi-rank process group: sharding a many-episode job is out of scope")
+        E = len(contexts)
+        if E == 0:
+            raise ValueError("no episodes given")
+        counts = [int(n_samples)] * E if isinstance(n_samples, (int, np.integer)) else [int(n) for n in n_samples]
+        for name, v in (('hard_conds', hard_conds), ('obstacle_pts', obstacle_pts), ('n_samples', counts), ('rngs', rngs)):
+            if v is not None and len(v) != E:
+                raise ValueError(f"{name} has {len(v)} entries for {E} episodes")
+        if min(counts) <= 0:
+            raise ValueError("every episode needs at least one candidate")
+        k0 = list(hard_conds[0].keys())
+        for e, h in enumerate(hard_conds):
+            if list(h.keys()) != k0:
+                raise ValueError(f"episode {e} conditions waypoints {list(h.keys())}, episode 0 {k0}: every episode of a job must "
+                                 "condition the same waypoints in the same order")
+        if 2 * sum(counts) > self.model.max_rows:
+            raise ValueError(f"{sum(counts)} candidates are {2 * sum(counts)} network rows, beyond the network's max_rows = {self.model.max_rows}")
+        return counts
+
+    @torch.no_grad()
+    def run_inference_episodes(self, contexts, hard_conds, obstacle_pts, n_samples=35, rngs=None, return_chain=False,
+                               max_iteration=60, traj_normalized=None):
+        """MANY pursuit-evasion episodes in ONE job per replan iteration: the loop over contexts and experiments of the reference's
+        scripts/inference/inference_dynamic.py (``run_multiple_experiments``: one ``run_inference`` per episode, each up to 60 replans of
+        35 candidates) advanced in lock-step, so that a replan is E x n rows wide instead of n.
+
+        contexts      list of per-episode contexts (``{'dataset': ...}``: each episode its own environment)
+        hard_conds    list of one dict per episode, the same waypoint indices in every episode; values (S,) or (n_e, S)
+        obstacle_pts  list of per-episode clouds (n_obstacles, n_points, 2); shapes may differ
+        n_samples     candidates per episode: an int, or one count per episode
+        rngs          list of ``numpy.random.RandomState`` (or None = the global ``numpy.random`` for all): the stream episode e's
+                      APF clouds, pursuer clouds and cost points are drawn from, in the one-episode planner's order
+
+        STAGE I is one many-scene DDIM job (``ramp_sample_scenes``) and one per-episode selection (``ramp_select_best_scenes``);
+        STAGE II loops while any episode is active: per active episode the environment step, then ONE ``ramp_replan_episodes`` call
+        for all, then the per-episode book-keeping.  An episode that has reached its goal or ``max_iteration`` keeps its rows in the
+        batch (the job's shape, buffers and graph never change) and its results are ignored.  An episode without a collision-free
+        candidate falls back to the eager from-scratch re-plan of the one-episode planner, alone; that path installs a single scene,
+        so the job's scene table is installed again afterwards and the next call calibrates.
+        ``self.replan_log`` (a list, optional) receives one entry per selection and episode: ``episode``, ``active``, ``record`` (the
+        episode's result record of that call) and, for an active episode, ``batch``, ``npts``, ``idx``, ``free``.
+
+        Returns a list with, per episode, what ``run_inference`` returns: ``(chain (iters, 1, H, S), chain_obs, chain_start)`` if
+        ``return_chain`` else the final plan (1, H, S).  Raises ``NotImplementedError`` under a multi-rank process group and
+        ``ValueError`` for lists of different lengths, differing hard-condition keys or more than ``max_rows`` network rows."""
+        from .scenes import build_episode_tables
+        counts = self._check_episode_lists(contexts, hard_conds, obstacle_pts, n_samples, rngs)
+        device, m, lib = self._device(), self.model, _lib.load()
+        E, B, H, S = len(contexts), sum(counts), m.n_support_points, self.state_dim
+        rngs = [np.random] * E if rngs is None else list(rngs)
+        log = getattr(self, 'replan_log', None)
+        tab = build_episode_tables(counts, [self._row_pattern(n) for n in counts])
+        first = [int(v) for v in tab['traj_first']]
+        rows = [slice(first[e], first[e + 1]) for e in range(E)]
+        # 1. set-up: per-episode contexts, hard conditions of the whole batch, cost clouds, the job's scene table
+        contexts = [copy(c) for c in contexts]
+        hcs = []                                               # per episode, expanded to its rows: what the eager fallback takes
+        for h, n in zip(hard_conds, counts):
+            hc = {}
+            for kk, v in h.items():
+                v = v.to(device, torch.float32)
+                hc[kk] = (v.unsqueeze(0).expand(n, -1) if v.dim() == 1 else v).contiguous()
+                if hc[kk].shape[0] != n:
+                    raise ValueError(f"hard condition {kk}: {hc[kk].shape[0]} rows for an episode of {n} candidates")
+            hcs.append(hc)
+        hard = {kk: torch.cat([hc[kk] for hc in hcs]).contiguous() for kk in hcs[0]}
+        eps = [_Episode(c, hc, pts, device, True) for c, hc, pts in zip(contexts, hcs, obstacle_pts)]
+        clouds = [ep.cloud.reshape(-1, 2).to(torch.float32).contiguous() for ep in eps]
+        cost_cloud = torch.cat(clouds).contiguous()
+        cost_off = np.concatenate([[0], np.cumsum([c.shape[0] for c in clouds])]).astype(np.int32)
+        m.ctx()
+        latents = torch.cat([m.encode_scene(ep.cloud) for ep in eps] + [torch.zeros(1, m.context_dim, device=device)])
+        m.set_scenes(latents, tab['row_variant'])
+        first_dev = torch.from_numpy(tab['traj_first']).to(device)
+        mask, plen, smooth = torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, device=device), torch.empty(B, device=device)
+        best = torch.empty((E, H, S), device=device)
+        # 2. STAGE I: one many-scene DDIM job, one selection per episode (the winner unmodified, as the high-level plan wants)
+        ts = [int(i) for i in self.ddim_set_timesteps(self.ddim_num_inference_steps_high)]
+        x = torch.randn((B, H, S), device=device)
+        job = {'n_scenes': E, 'traj_scene': torch.from_numpy(tab['row_episode']).to(device), 'cloud_offset': None, 'cloud_points': None}
+        xb, _ = self._launch(B, x.unsqueeze(0), hard, None, True, ts, [0] * len(ts), None, None, False,
+                             ddim_K=self.ddim_num_inference_steps_high, scene_job=job)
+        res_dev = torch.zeros((E, 4), dtype=torch.int32, device=device)
+        cost_off_dev = torch.from_numpy(cost_off).to(device)
+        with torch.cuda.device(device):
+            _lib.check(lib.ramp_select_best_scenes(_lib.ptr(xb), B, H, S, _lib.ptr(first_dev), E, _lib.ptr(cost_cloud),
+                                                   _lib.ptr(cost_off_dev), cost_cloud.shape[0], eps[0].thr_high,
+                                                   0.1, 0.9, _lib.ptr(mask), _lib.ptr(plen), _lib.ptr(smooth), _lib.ptr(best),
+                                                   _lib.ptr(res_dev), _lib.current_stream()), "ramp_select_best_scenes")
+        res = res_dev.cpu().numpy()
+        for e, ep in enumerate(eps):
+            n_free, rank, row = (int(v) for v in res[e, :3])
+            if log is not None:
+                log.append(dict(episode=e, active=True, record=[int(v) for v in res[e]], batch=xb[rows[e]].clone(), npts=clouds[e].shape[0],
+                                idx=rank if n_free else -1, free=(mask[rows[e]] == 0).clone()))
+            if n_free == 0:
+                raise RuntimeError(f"episode {e}: no collision-free high-level plan (the reference dereferences None here)")
+            ep.start(xb[row].clone())
+        cur = best.clone()                                    # (E, H, S) current plans, and their host copy
+        best_host = cur.cpu().numpy()
+        hist = torch.zeros((E, H, S), device=device)
+        hist[:, 0] = best[:, 0]
+        # 3. STAGE II: what the episodes share, and the per-episode tables of the call
+        arrays = _HostArrays()
+        p = self._replan_params(B, ts[-self.ddim_num_inference_steps_low:], hard, cost_cloud, eps[0].thr_low, arrays)
+        p.cost_cloud, p.n_cost = None, 0                      # (the clouds come per episode)
+        n_dyn, n_extra = p.n_dyn, p.n_extra
+        state = (_lib.RampEpisodeState * E)()
+        dyn = np.zeros((E, n_dyn, 2), np.float64)
+        near = np.zeros(E, np.int32)
+        extra = np.zeros((E, n_extra, 2), np.float32)
+        eb = _lib.RampEpisodeBatch()
+        eb.n_episodes = E
+        eb.traj_first_host = tab['traj_first'].ctypes.data_as(_lib.c_i32p)
+        eb.state_host = state
+        eb.dyn_pts_host, eb.near_host, eb.extra_pts_host = dyn.ctypes.data, near.ctypes.data_as(_lib.c_i32p), extra.ctypes.data
+        eb.cost_cloud, eb.cost_offset_host = _lib.ptr(cost_cloud), cost_off.ctypes.data_as(_lib.c_i32p)
+        active = [True] * E
+        x_clean = best.clone()                                # explicit on the first call and after a fallback; else the previous winners
+        static_pts = static_off = None
+        want_batch = log is not None
+        batch = torch.empty((B, H, S), device=device) if want_batch else None
+        results = np.zeros((E, 4), np.int32)
+        for k in range(max_iteration):
+            if not any(active):
+                break
+            # 4. the environment step of every active episode
+            noise = torch.randn_like(xb)                           # q_sample's randn_like(x_start), all episodes' rows
+            fields = []
+            for e, ep in enumerate(eps):
+                state[e].active = int(active[e])
+                if not active[e]:
+                    continue
+                field, centre, dyn[e], near_e, extra_e = self._environment_step(k, contexts[e], ep, counts[e], best_host[e], rngs[e])
+                fields.append(field)
+                near[e] = int(near_e)
+                if near_e:
+                    extra[e] = extra_e
+                state[e].n_hist, state[e].stepp = len(ep.executed_history), ep.stepp
+                state[e].pursuer[0], state[e].pursuer[1] = float(np.float32(centre[0])), float(np.float32(centre[1]))
+            if static_pts is None:                                 # (every field exists after the first step: all episodes start active)
+                static_pts = torch.cat([f._static_dev for f in fields]).contiguous()
+                static_off = np.concatenate([[0], np.cumsum([f._static_dev.shape[0] for f in fields])]).astype(np.int32)
+                eb.static_pts, eb.static_offset_host = _lib.ptr(static_pts), static_off.ctypes.data_as(_lib.c_i32p)
+            eb.noise, eb.history, eb.x_clean = _lib.ptr(noise), _lib.ptr(hist), _lib.ptr(x_clean)
+            # 5. the replan of all episodes: one graph replay
+            rr = _lib.RampReplanResult()
+            with torch.cuda.device(device):
+                _lib.check(lib.ramp_replan_episodes(m.ctx(), C.byref(p), C.byref(eb), _lib.ptr(best), _lib.ptr(batch),
+                                                    _lib.ptr(mask) if want_batch else None, results.ctypes.data_as(_lib.c_i32p),
+                                                    C.byref(rr), _lib.current_stream()), "ramp_replan_episodes")
+            if rr.fell_back:
+                self.range_fallbacks += 1
+                warnings.warn(f"fp16x3 range guard tripped at GEMM call site {rr.fell_back - 1}: replan repeated in bf16x6")
+            x_clean = None
+            # 6. from-scratch fallback (one episode alone, eager), then the book-keeping of every active episode
+            for e, ep in enumerate(eps):
+                if log is not None and not active[e]:
+                    log.append(dict(episode=e, active=False, record=results[e].tolist()))
+                elif log is not None:
+                    log.append(dict(episode=e, active=True, record=results[e].tolist(), batch=batch[rows[e]].clone(),
+                                    npts=clouds[e].shape[0] + (n_extra if near[e] else 0),
+                                    idx=int(results[e, 1]) if results[e, 0] else -1, free=(mask[rows[e]] == 0).clone()))
+                if active[e] and results[e, 0] == 0:
+                    self._replan_until_free(ep, (counts[e], H, S), hcs[e], contexts[e], traj_normalized, k, clouds[e], best[e], False)
+                    x_clean = best                                 # the next call takes its plans from here, not from its own winners
+            if x_clean is not None:
+                m.set_scenes(latents, tab['row_variant'])          # (the eager path installed one episode's scene)
+            cur = best.clone()
+            best_host = cur.cpu().numpy()
+            moved = [e for e in range(E) if active[e]]
+            at = torch.tensor([eps[e].stepp + 1 for e in moved], device=device)
+            sel = torch.tensor(moved, device=device)
+            hist[sel, at] = cur[sel, at]
+            for e in moved:
+                ep = eps[e]
+                ep.record(cur[e])
+                if ep.reached(float(np.linalg.norm(best_host[e][ep.stepp - 1, :2] - best_host[e][-1, :2]))):
+                    active[e] = False
+        out = []
+        for e, ep in enumerate(eps):
+            _x, chain, chain_obs, chain_start = ep.result(cur[e])
+            chain = chain.permute(1, 0, 2, 3)
+            out.append((chain, chain_obs, chain_start) if return_chain else chain[-1])
+        return out
 
     @torch.no_grad()
     def conditional_sample(self, hard_conds, horizon=None, batch_size=1, ddim=False, traj_normalized=None,

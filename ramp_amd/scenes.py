@@ -111,6 +111,38 @@ def build_eval_tables(counts: Sequence[int], box_counts: Optional[Sequence[int]]
     return out
 
 
+def build_episode_tables(counts: Sequence[int], row_patterns: Sequence[Sequence[int]]) -> Dict[str, np.ndarray]:
+    """Tables of one many-episode replanning job (``run_inference_episodes`` -> ``ramp_set_scenes`` + ``ramp_replan_episodes``): the
+    loop over contexts and experiments of the reference's ``scripts/inference/inference_dynamic.py`` turned into one batch.
+
+    counts        candidate trajectories of each episode, at least one each; an episode's rows are adjacent, episodes in order
+    row_patterns  per episode, the network-row -> variant pattern (0 = the episode's own latent, 1 = unconditional) its
+                  single-episode job would hand to ``set_scene``, applied cyclically FROM THE EPISODE'S FIRST ROW: ``[0, 1]`` for true
+                  classifier-free guidance, and for the reference's row pairing ``[0, 0, 1, 1]`` (even count) or ``[0, 1, 1, 0]`` (odd
+                  count) by the parity of the episode's OWN count -- so an episode's rows read what they read in a job of their own
+
+    Returns int32 arrays: ``traj_first`` (E + 1) first row of each episode, ``[-1] = B``; ``row_episode`` (B) episode of each
+    trajectory; ``row_variant`` (2 B) latent of each network row, episode e's own latent at index e and the shared all-zero one
+    at index E."""
+    E = len(counts)
+    if E == 0:
+        raise ValueError("no episodes given")
+    if len(row_patterns) != E:
+        raise ValueError(f"row_patterns has {len(row_patterns)} entries for {E} episodes")
+    traj_first = _offsets("candidate counts", counts, E, allow_empty=False)
+    if 2 * int(traj_first[-1]) >= 2 ** 31:
+        raise ValueError("the job's network rows do not fit 32-bit offsets")
+    row_episode = np.repeat(np.arange(E, dtype=np.int32), np.diff(traj_first))
+    row_variant = np.empty(2 * row_episode.size, dtype=np.int32)
+    for e, pat in enumerate(row_patterns):
+        pat = np.asarray([int(v) for v in pat], dtype=np.int64)
+        if pat.size == 0 or bool(((pat != 0) & (pat != 1)).any()):
+            raise ValueError(f"episode {e}: a row pattern is a non-empty sequence of 0 (conditional) and 1 (unconditional), got {pat.tolist()}")
+        r0, r1 = 2 * int(traj_first[e]), 2 * int(traj_first[e + 1])
+        row_variant[r0:r1] = np.where(np.resize(pat, r1 - r0) == 0, e, E)
+    return {"traj_first": traj_first, "row_episode": row_episode, "row_variant": row_variant}
+
+
 def scene_counts(counts_or_traj_scene, n_scenes: int, B: int) -> List[int]:
     """Per-scene trajectory counts from either the counts themselves (``n_scenes`` positive entries summing to ``B``) or the
     ``traj_scene`` (B) array of ``build_scene_tables`` (scenes in order, a scene's rows adjacent).  A device ``traj_scene`` is copied
