@@ -122,6 +122,24 @@ int ramp_set_scenes(ramp_ctx* ctx, const float* latents, int32_t n_variants, con
 int ramp_encode_scene(ramp_ctx* ctx, const float* cloud, int32_t n_obstacles, int32_t n_points, int32_t point_dim,
                       float* latent_out, void* stream);
 
+/* scene_encoder for MANY scenes in one call, with a launch count per pass that does not depend on the number of scenes: the
+ * per-scene loop that run_inference_scenes / run_inference_episodes would otherwise make over ramp_encode_scene.
+ * points: device (sum P, point_dim), the scenes' clouds concatenated.  Two HOST int32 CSR tables (copied before the call returns):
+ * scene_first_host[n_scenes + 1], the first obstacle of each scene, and obstacle_first_host[n_obstacles + 1], the first point of each
+ * obstacle.  Scenes may differ in obstacle count and in points per obstacle; inside one scene every obstacle has the same point
+ * count (the reference's (No, Np, D) tensor).  latents_out: device (n_scenes, context_dim), 16-byte aligned; row i holds, BIT FOR
+ * BIT, what ramp_encode_scene writes for scene i alone, whatever else is in the batch and whatever the budget.
+ * Scenes are encoded in passes of consecutive scenes: a pass holds as many whole scenes as fit in max_points points (0 = the default
+ * below) and always at least one, so a scene larger than the budget gets a pass of its own; the scratch buffer is sized to the
+ * largest pass (the 2-D encoder keeps 960 floats per point: about 126 MB at the default).  n_passes_out (host, may be NULL)
+ * receives the number of passes.  Everything is checked on the host before the first launch; refused (non-zero, the entry's name in
+ * ramp_last_error): n_scenes < 1, tables that do not start at 0 or are not strictly increasing (an empty scene or obstacle), a
+ * scene whose obstacles differ in point count, a point_dim other than the model's, totals beyond 32-bit offsets. */
+#define RAMP_ENCODE_DEFAULT_MAX_POINTS 32768
+int ramp_encode_scenes(ramp_ctx* ctx, const float* points, const int32_t* obstacle_first_host, const int32_t* scene_first_host,
+                       int32_t n_scenes, int32_t point_dim, int32_t max_points, float* latents_out, int32_t* n_passes_out,
+                       void* stream);
+
 /* TemporalUnetInference.forward / forward_no_energy (UnetInference.py:157-224).
  * x (B,H,S); each trajectory is evaluated n_rp times (rows b*n_rp + v).  f_out (B*n_rp,H,S)
  * receives forward_no_energy's output, eps_out (B*n_rp,H,S) the energy gradient; either may be

@@ -117,6 +117,8 @@ PROTOTYPES = {
     "ramp_set_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, C.c_int32, C.c_void_p]),
     "ramp_set_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, c_i32p, C.c_int32, C.c_void_p]),
     "ramp_encode_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ramp_encode_scenes": (C.c_int, [C.c_void_p, C.c_void_p, c_i32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, c_i32p,
+                                     C.c_void_p]),
     "ramp_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                              C.c_void_p]),
     "ramp_score_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, c_i32p, C.c_void_p, C.c_void_p,

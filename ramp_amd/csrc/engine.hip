@@ -7,6 +7,7 @@
 // autograd.grad is replaced by the explicit dX chain below (all parameters are frozen, so no
 // dW / db products exist anywhere).
 #include "engine_util.h"
+#include "encode_plan.h"
 
 #include <algorithm>
 #include <array>
@@ -169,6 +170,7 @@ struct ramp_ctx {
   bool e_calibrated = false;
   // scene-encoder scratch
   float* scene_ws = nullptr; size_t scene_ws_cap = 0;
+  int* enc_tab = nullptr; size_t enc_tab_cap = 0;      // ramp_encode_scenes: the pass-local CSR and tile tables of every pass of the call
   // bf16x6 weight planes: fp32 weight base pointer -> (planes, element count)
   int gemm_mode = 0;                 // 0 = exact fp32 MFMA, 1 = bf16x6 split on the bf16 matrix cores, 2 = fp16x3 split with delayed operand scaling
                                      // (evaluations in phase 2; its calibration evaluations, phase 1, run the bf16x6 kernels): the default build
@@ -1089,6 +1091,133 @@ int encode_scene_3d(ramp_ctx* c, const float* cloud, int No, int Np, float* out,
 }
 
 
+// ---- many scenes in one pass (ramp_encode_scenes) -------------------------------------------------
+// The schedules of encode_scene_2d / encode_scene_3d over the concatenated tokens of a pass: every per-token stage and every GEMM is
+// the single-scene launch with M = the pass's rows (launch_gemm picks its tile from N and K, a row's result does not depend on M);
+// only the stages that look across tokens take the tables.  The device tables of one pass, rebased to the pass's first obstacle / point:
+struct EncodeTables {
+  const int* obstacle_first;   // [n_obstacles + 1] first point of each obstacle
+  const int* scene_first;      // [n_scenes + 1] first TOKEN of each scene (2-D: point, 3-D: obstacle)
+  const int* tiles;            // [n_tiles][3] attention tiles over the scenes' tokens
+  int n_scenes, n_obstacles, n_points, n_tiles;
+};
+size_t encode_scratch_2d(size_t T, size_t No, size_t Ns) { return T * (192 + 64 * 4 + 192 + 256) + 3 * ((No + 3) & ~(size_t)3) + Ns * (64 + 256) + 4096; }
+size_t encode_scratch_3d(size_t T, size_t No, size_t Ns) { return T * (64 + 256) + No * (256 * 4 + 768 + 512) + 512 + Ns * 512 + 4096; }
+
+// cloud: the pass's points (T, 2); out: the pass's first latent row (n_scenes, 320)
+int encode_scenes_2d(ramp_ctx* c, const float* cloud, const EncodeTables& tb, float* out, hipStream_t s) {
+  const int T = tb.n_points, No = tb.n_obstacles, Ns = tb.n_scenes, CTX = 320;
+  float* p = c->scene_ws;
+  float* F = p; p += (size_t)T * 192;
+  float* COMB = p; p += (size_t)T * 64;
+  float* X = p; p += (size_t)T * 64;
+  float* X2 = p; p += (size_t)T * 64;
+  float* LNb = p; p += (size_t)T * 64;
+  float* QKV = p; p += (size_t)T * 192;
+  float* Hb = p; p += (size_t)T * 256;
+  float* centers = p; p += 2 * ((No + 3) & ~3);
+  float* maxd = p; p += (No + 3) & ~3;
+  float* P0 = p; p += (size_t)Ns * 64; float* P1 = p; p += (size_t)Ns * 256;
+  float *w, *b, *g, *be, *div;
+  CK(sw(c, "pos_encoder.div_term", &div));
+  CK(sw(c, "point_embedding.0.weight", &w)); CK(sw(c, "point_embedding.0.bias", &b));
+  CK(sw(c, "point_embedding.1.weight", &g)); CK(sw(c, "point_embedding.1.bias", &be));
+  CK(scene_enc2d_prep_seg(cloud, tb.obstacle_first, No, centers, maxd, s));
+  CK(scene_enc2d_feat_seg(cloud, tb.obstacle_first, No, centers, maxd, div, w, b, g, be, F, T, s));
+  CK(sw(c, "combined_encoder.0.weight", &w)); CK(sw(c, "combined_encoder.0.bias", &b));
+  CK(launch_gemm(slin(F, 192, w, b, X2, T, 64), s));
+  CK(sw(c, "combined_encoder.1.weight", &g)); CK(sw(c, "combined_encoder.1.bias", &be));
+  CK(scene_ln64(X2, g, be, COMB, T, 1, s));
+  const int dims[3] = {64, 96, 160};
+  int off = 0;
+  for (int i = 0; i < 3; ++i) {
+    const float* xin = COMB;
+    for (int j = 0; j < 3; ++j) {
+      const std::string t = "set_transformers." + std::to_string(i) + "." + std::to_string(j);
+      CK(sw(c, t + ".norm1.weight", &g)); CK(sw(c, t + ".norm1.bias", &be));
+      CK(scene_ln64(xin, g, be, LNb, T, 0, s));
+      CK(sw(c, t + ".attn.qkv.weight", &w));
+      CK(launch_gemm(slin(LNb, 64, w, nullptr, QKV, T, 192), s));
+      CK(scene_attention_seg(QKV, LNb, tb.tiles, tb.n_tiles, 4, 16, 0.25f, s));
+      CK(sw(c, t + ".attn.proj.weight", &w)); CK(sw(c, t + ".attn.proj.bias", &b));
+      CK(launch_gemm(slin(LNb, 64, w, b, X2, T, 64, xin), s));
+      CK(sw(c, t + ".norm2.weight", &g)); CK(sw(c, t + ".norm2.bias", &be));
+      CK(scene_ln64(X2, g, be, LNb, T, 0, s));
+      CK(sw(c, t + ".mlp.0.weight", &w)); CK(sw(c, t + ".mlp.0.bias", &b));
+      CK(launch_gemm(slin(LNb, 64, w, b, Hb, T, 256), s));
+      CK(scene_affine_act(Hb, nullptr, nullptr, nullptr, Hb, (long)T * 256, 256, 1, s));
+      CK(sw(c, t + ".mlp.3.weight", &w)); CK(sw(c, t + ".mlp.3.bias", &b));
+      CK(launch_gemm(slin(Hb, 256, w, b, X, T, 64, X2), s));
+      xin = X;
+    }
+    const int d = dims[i];
+    const std::string q = "poolings." + std::to_string(i);
+    CK(scene_colreduce_seg(X, P0, tb.scene_first, Ns, 64, 64, 0, s));           // mean over each scene's own tokens
+    CK(sw(c, q + ".0.weight", &w)); CK(sw(c, q + ".0.bias", &b));
+    CK(launch_gemm(slin(P0, 64, w, b, P1, Ns, d), s));
+    CK(scene_affine_act(P1, nullptr, nullptr, nullptr, P1, (long)Ns * d, d, 1, s));
+    CK(sw(c, q + ".2.weight", &w)); CK(sw(c, q + ".2.bias", &b));
+    GemmArgs last = slin(P1, d, w, b, out + off, Ns, d);
+    last.ldc = CTX;                                                            // a scene's three pooled parts side by side in its latent row
+    CK(launch_gemm(last, s));
+    off += d;
+  }
+  return 0;
+}
+
+// cloud: the pass's points (T, 3); out: the pass's first latent row (n_scenes, 256)
+int encode_scenes_3d(ramp_ctx* c, const float* cloud, const EncodeTables& tb, float* out, hipStream_t s) {
+  const int T = tb.n_points, No = tb.n_obstacles, Ns = tb.n_scenes, E = 256;
+  float* p = c->scene_ws;
+  float* H1 = p; p += (size_t)T * 64;
+  float* H2 = p; p += (size_t)T * E;
+  float* X = p; p += (size_t)No * E; float* X2 = p; p += (size_t)No * E;
+  float* LNb = p; p += (size_t)No * E; float* O = p; p += (size_t)No * E;
+  float* QKV = p; p += (size_t)No * 768; float* Hb = p; p += (size_t)No * 512;
+  float* sc = p; p += 256; float* sh = p; p += 256; float* S0 = p; p += (size_t)Ns * E; float* S1 = p; p += (size_t)Ns * E;
+  float *w, *b, *g, *be, *rm, *rv;
+  CK(sw(c, "point_processor.conv1.weight", &w)); CK(sw(c, "point_processor.conv1.bias", &b));
+  CK(scene_linear_small(cloud, w, b, H1, T, 64, 3, s));
+  CK(sw(c, "point_processor.bn1.weight", &g)); CK(sw(c, "point_processor.bn1.bias", &be));
+  CK(sw(c, "point_processor.bn1.running_mean", &rm)); CK(sw(c, "point_processor.bn1.running_var", &rv));
+  CK(scene_bn_fold(g, be, rm, rv, sc, sh, 64, s));
+  CK(scene_affine_act(H1, sc, sh, nullptr, H1, (long)T * 64, 64, 2, s));
+  CK(sw(c, "point_processor.conv2.weight", &w)); CK(sw(c, "point_processor.conv2.bias", &b));
+  CK(launch_gemm(slin(H1, 64, w, b, H2, T, E), s));
+  CK(sw(c, "point_processor.bn2.weight", &g)); CK(sw(c, "point_processor.bn2.bias", &be));
+  CK(sw(c, "point_processor.bn2.running_mean", &rm)); CK(sw(c, "point_processor.bn2.running_var", &rv));
+  CK(scene_bn_fold(g, be, rm, rv, sc, sh, E, s));
+  CK(scene_affine_act(H2, sc, sh, nullptr, H2, (long)T * E, E, 2, s));
+  CK(scene_colreduce_seg(H2, X, tb.obstacle_first, No, E, E, 1, s));            // max over the points of each obstacle
+  for (int i = 0; i < 2; ++i) {
+    const std::string t = "set_transformer_blocks." + std::to_string(i);
+    CK(sw(c, t + ".norm1.weight", &g)); CK(sw(c, t + ".norm1.bias", &be));
+    CK(launch_ln_fwd(X, g, be, LNb, No, s));
+    CK(sw(c, t + ".mha.in_proj_weight", &w)); CK(sw(c, t + ".mha.in_proj_bias", &b));
+    CK(launch_gemm(slin(LNb, E, w, b, QKV, No, 768), s));
+    CK(scene_attention_seg(QKV, O, tb.tiles, tb.n_tiles, 4, 64, 0.125f, s));
+    CK(sw(c, t + ".mha.out_proj.weight", &w)); CK(sw(c, t + ".mha.out_proj.bias", &b));
+    CK(launch_gemm(slin(O, E, w, b, X2, No, E, X), s));
+    CK(sw(c, t + ".norm2.weight", &g)); CK(sw(c, t + ".norm2.bias", &be));
+    CK(launch_ln_fwd(X2, g, be, LNb, No, s));
+    CK(sw(c, t + ".ffn.0.weight", &w)); CK(sw(c, t + ".ffn.0.bias", &b));
+    CK(launch_gemm(slin(LNb, E, w, b, Hb, No, 512), s));
+    CK(scene_affine_act(Hb, nullptr, nullptr, nullptr, Hb, (long)No * 512, 512, 2, s));
+    CK(sw(c, t + ".ffn.3.weight", &w)); CK(sw(c, t + ".ffn.3.bias", &b));
+    CK(launch_gemm(slin(Hb, 512, w, b, X, No, E, X2), s));
+  }
+  CK(sw(c, "output_proj.weight", &w)); CK(sw(c, "output_proj.bias", &b));
+  CK(launch_gemm(slin(X, E, w, b, O, No, E), s));
+  CK(scene_colreduce_seg(O, S0, tb.scene_first, Ns, E, E, 1, s));               // max over the obstacles of each scene
+  CK(sw(c, "global_pooling.0.weight", &w)); CK(sw(c, "global_pooling.0.bias", &b));
+  CK(launch_gemm(slin(S0, E, w, b, S1, Ns, E), s));
+  CK(scene_affine_act(S1, nullptr, nullptr, nullptr, S1, (long)Ns * E, E, 2, s));
+  CK(sw(c, "global_pooling.2.weight", &w)); CK(sw(c, "global_pooling.2.bias", &b));
+  CK(launch_gemm(slin(S1, E, w, b, out, Ns, E), s));
+  return 0;
+}
+
+
 // ---- device buffers of the job layer: typed, grow-only, from the arena (which never frees: an old block stays valid for whatever still holds
 // its address).  A captured graph holds the addresses of the buffers its nodes touch, so every reallocation is noted in the context and
 // staging_done() -- once per job, after its staging and before a graph is chosen -- drops the keys of BOTH graph families: the sampling jobs'
@@ -1678,6 +1807,63 @@ int ramp_encode_scene(ramp_ctx* c, const float* cloud, int32_t n_obstacles, int3
   }
   RAMP_REQUIRE(point_dim == 3 && c->cfg.context_dim == 256, "3-D scene encoder takes (No,Np,3) and produces 256-d");
   return encode_scene_3d(c, cloud, n_obstacles, n_points, latent_out, as_stream(stream));
+}
+
+int ramp_encode_scenes(ramp_ctx* c, const float* points, const int32_t* obstacle_first_host, const int32_t* scene_first_host,
+                       int32_t n_scenes, int32_t point_dim, int32_t max_points, float* latents_out, int32_t* n_passes_out, void* stream) {
+  static_assert(ENCODE_DEFAULT_MAX_POINTS == RAMP_ENCODE_DEFAULT_MAX_POINTS, "the planner's default budget is the header's");
+  const std::string who = "ramp_encode_scenes: ";
+  // everything is checked on the host before the first launch
+  RAMP_REQUIRE(c && c->finalized && points && latents_out, who + "bad arguments (context with finalized weights, points, latents_out)");
+  RAMP_REQUIRE((reinterpret_cast<uintptr_t>(latents_out) & 15) == 0, who + "latents_out must be 16-byte aligned");
+  RAMP_REQUIRE(point_dim == (c->cfg.context_dim == 320 ? 2 : 3) && (c->cfg.context_dim == 320 || c->cfg.context_dim == 256),
+               who + "point_dim is not the model's (the 2-D encoder takes (.., 2) points and produces 320-d latents, the 3-D one (.., 3) and 256-d)");
+  std::vector<EncodePass> passes;
+  const std::string refusal = plan_encode_passes(scene_first_host, obstacle_first_host, n_scenes, max_points, &passes);
+  RAMP_REQUIRE(refusal.empty(), who + refusal);
+  const bool two_d = point_dim == 2;
+  const long n_points = obstacle_first_host[scene_first_host[n_scenes]];
+  RAMP_REQUIRE(n_points * point_dim < (1l << 31) && (long)n_scenes * c->cfg.context_dim < (1l << 31), who + "the batch does not fit 32-bit offsets");
+  // the tables of every pass, rebased to the pass, in ONE host array and one upload: [obstacle_first | scene's first token | tiles] per pass
+  std::vector<int32_t> tab;
+  std::vector<size_t> at(passes.size());
+  size_t scratch = 0;
+  for (size_t k = 0; k < passes.size(); ++k) {
+    const EncodePass& ps = passes[k];
+    at[k] = tab.size();
+    for (int o = ps.obstacle0; o <= ps.obstacle1; ++o) tab.push_back(obstacle_first_host[o] - ps.point0);
+    for (int sc = ps.scene0; sc <= ps.scene1; ++sc)
+      tab.push_back(two_d ? obstacle_first_host[scene_first_host[sc]] - ps.point0 : scene_first_host[sc] - ps.obstacle0);
+    for (int sc = ps.scene0; sc < ps.scene1; ++sc) {
+      const int base = two_d ? obstacle_first_host[scene_first_host[sc]] - ps.point0 : scene_first_host[sc] - ps.obstacle0;
+      const int Ts = two_d ? obstacle_first_host[scene_first_host[sc + 1]] - obstacle_first_host[scene_first_host[sc]]
+                           : scene_first_host[sc + 1] - scene_first_host[sc];
+      for (int q0 = 0; q0 < Ts; q0 += ENCODE_TILE) { tab.push_back(base); tab.push_back(Ts); tab.push_back(q0); }
+    }
+    const size_t T = ps.point1 - ps.point0, No = ps.obstacle1 - ps.obstacle0, Ns = ps.scene1 - ps.scene0;
+    scratch = std::max(scratch, two_d ? encode_scratch_2d(T, No, Ns) : encode_scratch_3d(T, No, Ns));
+  }
+  hipStream_t s = as_stream(stream);
+  CK(scene_scratch(c, scratch));
+  if (tab.size() > c->enc_tab_cap) {
+    float* q; CK(dev_alloc(c, &q, tab.size())); c->enc_tab = reinterpret_cast<int*>(q); c->enc_tab_cap = tab.size();
+  }
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->enc_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));   // (pageable host memory: staged before the call returns)
+  for (size_t k = 0; k < passes.size(); ++k) {
+    const EncodePass& ps = passes[k];
+    EncodeTables tb;
+    tb.n_scenes = ps.scene1 - ps.scene0; tb.n_obstacles = ps.obstacle1 - ps.obstacle0; tb.n_points = ps.point1 - ps.point0;
+    tb.n_tiles = two_d ? ps.point_tiles : ps.obstacle_tiles;
+    tb.obstacle_first = c->enc_tab + at[k];
+    tb.scene_first = tb.obstacle_first + tb.n_obstacles + 1;
+    tb.tiles = tb.scene_first + tb.n_scenes + 1;
+    const float* cloud = points + (size_t)ps.point0 * point_dim;
+    float* out = latents_out + (size_t)ps.scene0 * c->cfg.context_dim;
+    if (two_d) CK(encode_scenes_2d(c, cloud, tb, out, s));
+    else CK(encode_scenes_3d(c, cloud, tb, out, s));
+  }
+  if (n_passes_out) *n_passes_out = (int32_t)passes.size();
+  return 0;
 }
 
 int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, float* f_out, float* eps_out,

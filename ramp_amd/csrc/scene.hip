@@ -160,7 +160,144 @@ __global__ __launch_bounds__(64) void attn_generic_kernel(const float* __restric
   }
 }
 
+// ================================================================================================================================
+// Many scenes in one pass (ramp_encode_scenes): the kernels above that look across tokens, in segmented form.  A batch is the
+// concatenated point array plus CSR tables; every kernel below keeps the arithmetic AND the per-element order of its single-scene
+// counterpart, so that a scene's latent has the same bits alone and inside any batch.
+// ================================================================================================================================
+
+// enc2d_prep_kernel with each obstacle's own point run: obstacle o owns points [obstacle_first[o], obstacle_first[o + 1])
+__global__ __launch_bounds__(64) void enc2d_prep_seg_kernel(const float* __restrict__ cloud, const int* __restrict__ obstacle_first,
+                                                            float* __restrict__ centers, float* __restrict__ maxd) {
+  const int o = blockIdx.x, lane = threadIdx.x;
+  const int first = obstacle_first[o], Np = obstacle_first[o + 1] - first;
+  const float* p = cloud + (long)first * 2;
+  float sx = 0.f, sy = 0.f;
+  for (int i = lane; i < Np; i += 64) { sx += p[2 * i]; sy += p[2 * i + 1]; }
+  const float cx = wsum(sx) / (float)Np, cy = wsum(sy) / (float)Np;
+  float m = 0.f;
+  for (int i = lane; i < Np; i += 64) m = fmaxf(m, fmaxf(fabsf(p[2 * i] - cx), fabsf(p[2 * i + 1] - cy)));
+  m = wmax(m);
+  if (lane == 0) { centers[2 * o] = cx; centers[2 * o + 1] = cy; maxd[o] = m; }
+}
+
+// enc2d_feat_kernel with the token's obstacle looked up in the table (the last o with obstacle_first[o] <= t) instead of t / Np
+__global__ __launch_bounds__(256) void enc2d_feat_seg_kernel(const float* __restrict__ cloud, const int* __restrict__ obstacle_first,
+                                                             int n_obstacles, const float* __restrict__ centers,
+                                                             const float* __restrict__ maxd, const float* __restrict__ div,
+                                                             const float* __restrict__ w0, const float* __restrict__ b0,
+                                                             const float* __restrict__ g0, const float* __restrict__ be0,
+                                                             float* __restrict__ feat, int T) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  int lo = 0, hi = n_obstacles - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (obstacle_first[mid] <= t) lo = mid; else hi = mid - 1;
+  }
+  const int o = lo;
+  const float x = cloud[2 * t], y = cloud[2 * t + 1];
+  const float cx = centers[2 * o], cy = centers[2 * o + 1];
+  float e = w0[2 * lane] * x + w0[2 * lane + 1] * y + b0[lane];
+  const float mean = wsum(e) * (1.f / 64.f);
+  const float d = e - mean;
+  const float rstd = 1.f / sqrtf(wsum(d * d) * (1.f / 64.f) + 1e-5f);
+  e = gelu_s(d * rstd * g0[lane] + be0[lane]);
+  const float dv = div[lane >> 1];
+  const float den = maxd[o] + 1e-8f;
+  const float rx = (x - cx) / den, ry = (y - cy) / den;
+  float po, pr;
+  if (lane & 1) { po = cosf(cx * dv) + cosf(cy * dv); pr = cosf(rx * dv) + cosf(ry * dv); }
+  else { po = sinf(cx * dv) + sinf(cy * dv); pr = sinf(rx * dv) + sinf(ry * dv); }
+  float* f = feat + (long)t * 192;
+  f[lane] = e; f[64 + lane] = po; f[128 + lane] = pr;
+}
+
+// colreduce_kernel over a variable-length run of rows per segment: out[s][c] = mean / max over the rows [first[s], first[s + 1]) of
+// x, in row order; the mean divides by the segment's own length
+__global__ __launch_bounds__(256) void colreduce_seg_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                            const int* __restrict__ first, int C, int ldo, int mode) {
+  const int s = blockIdx.x;
+  const int r0 = first[s], seglen = first[s + 1] - r0;
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const float* p = x + (long)r0 * C + c;
+    float acc = mode ? -3.0e38f : 0.f;
+    for (int t = 0; t < seglen; ++t) { const float v = p[(long)t * C]; acc = mode ? fmaxf(acc, v) : acc + v; }
+    out[(long)s * ldo + c] = mode ? acc : acc / (float)seglen;
+  }
+}
+
+// attn_generic_kernel per scene: block (tile, head) owns the 64 queries from tiles[tile] = {scene's first token, scene's token count
+// T_s, first query inside the scene} and walks ONLY that scene's keys, in 64-key LDS tiles counted from the scene's first token --
+// the running maximum, the expf correction and the accumulation in key order are the single-scene kernel's, query for query
+template <int DH>
+__global__ __launch_bounds__(64) void attn_seg_kernel(const float* __restrict__ qkv, float* __restrict__ o, const int* __restrict__ tiles,
+                                                      int E, float scale) {
+  __shared__ float ks[64][DH + 1], vs[64][DH + 1];
+  const int h = blockIdx.y, lane = threadIdx.x;
+  const int base = tiles[3 * blockIdx.x], T = tiles[3 * blockIdx.x + 1];
+  const int i = tiles[3 * blockIdx.x + 2] + lane;          // query, counted inside the scene
+  const bool live = i < T;
+  const float* sq = qkv + (long)base * 3 * E;               // the scene's rows
+  float q[DH], acc[DH];
+#pragma unroll
+  for (int d = 0; d < DH; ++d) { q[d] = live ? sq[(long)i * 3 * E + h * DH + d] : 0.f; acc[d] = 0.f; }
+  float m = -3.0e38f, l = 0.f;
+  for (int j0 = 0; j0 < T; j0 += 64) {
+    const int nj = min(64, T - j0);
+    __syncthreads();
+    for (int e = lane; e < nj * DH; e += 64) {
+      const int j = e / DH, d = e - j * DH;
+      ks[j][d] = sq[(long)(j0 + j) * 3 * E + E + h * DH + d];
+      vs[j][d] = sq[(long)(j0 + j) * 3 * E + 2 * E + h * DH + d];
+    }
+    __syncthreads();
+    for (int j = 0; j < nj; ++j) {
+      float s = 0.f;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) s += q[d] * ks[j][d];
+      s *= scale;
+      const float mn = fmaxf(m, s);
+      const float corr = expf(m - mn), p = expf(s - mn);
+      l = l * corr + p;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) acc[d] = acc[d] * corr + p * vs[j][d];
+      m = mn;
+    }
+  }
+  if (live) {
+    const float inv = 1.f / l;
+#pragma unroll
+    for (int d = 0; d < DH; ++d) o[((long)base + i) * E + h * DH + d] = acc[d] * inv;
+  }
+}
+
 static inline int g256(long n) { long g = (n + 255) / 256; return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g)); }
+
+int scene_enc2d_prep_seg(const float* cloud, const int* obstacle_first, int n_obstacles, float* centers, float* maxd, hipStream_t s) {
+  hipLaunchKernelGGL(enc2d_prep_seg_kernel, dim3(n_obstacles), dim3(64), 0, s, cloud, obstacle_first, centers, maxd);
+  RAMP_HIP_CHECK(hipGetLastError()); return 0;
+}
+int scene_enc2d_feat_seg(const float* cloud, const int* obstacle_first, int n_obstacles, const float* centers, const float* maxd,
+                         const float* div, const float* w0, const float* b0, const float* g0, const float* be0, float* feat, int T,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(enc2d_feat_seg_kernel, dim3((T + 3) / 4), dim3(256), 0, s, cloud, obstacle_first, n_obstacles, centers, maxd, div,
+                     w0, b0, g0, be0, feat, T);
+  RAMP_HIP_CHECK(hipGetLastError()); return 0;
+}
+int scene_colreduce_seg(const float* x, float* out, const int* first, int n_seg, int C, int ldo, int mode, hipStream_t s) {
+  hipLaunchKernelGGL(colreduce_seg_kernel, dim3(n_seg), dim3(256), 0, s, x, out, first, C, ldo, mode);
+  RAMP_HIP_CHECK(hipGetLastError()); return 0;
+}
+int scene_attention_seg(const float* qkv, float* o, const int* tiles, int n_tiles, int heads, int dh, float scale, hipStream_t s) {
+  RAMP_REQUIRE(dh == 16 || dh == 64, "segmented attention is instantiated for head dims 16 and 64");
+  RAMP_REQUIRE(n_tiles >= 1, "segmented attention without a tile");
+  const dim3 grid(n_tiles, heads);
+  if (dh == 16) hipLaunchKernelGGL(attn_seg_kernel<16>, grid, dim3(64), 0, s, qkv, o, tiles, heads * dh, scale);
+  else hipLaunchKernelGGL(attn_seg_kernel<64>, grid, dim3(64), 0, s, qkv, o, tiles, heads * dh, scale);
+  RAMP_HIP_CHECK(hipGetLastError()); return 0;
+}
 
 int scene_enc2d_prep(const float* cloud, int No, int Np, float* centers, float* maxd, hipStream_t s) {
   hipLaunchKernelGGL(enc2d_prep_kernel, dim3(No), dim3(64), 0, s, cloud, Np, centers, maxd);

@@ -551,7 +551,7 @@ class _GaussianDiffusionBase(nn.Module):
 
     @torch.no_grad()
     def _prepare_scene_job(self, scenes, hard_conds, n_samples):
-        """Encode every scene once, hand latents + row table to the context (``set_scenes``) and build what ``_launch`` needs for
+        """Encode all scenes in one call (``encode_scenes``), hand latents + row table to the context (``set_scenes``) and build what ``_launch`` needs for
         a multi-scene job: (job dict, concatenated hard conditions, B)."""
         from .scenes import build_scene_tables
         if not self._scenes_supported:
@@ -574,7 +574,7 @@ class _GaussianDiffusionBase(nn.Module):
                 rows.append(v)
             hc[k] = torch.cat(rows).contiguous()
         m.ctx()
-        lat = torch.cat([m.encode_scene(s.to(dev)) for s in scenes] + [torch.zeros(1, m.context_dim, device=dev)])
+        lat = torch.cat([m.encode_scenes([s.to(dev) for s in scenes]), torch.zeros(1, m.context_dim, device=dev)])
         m.set_scenes(lat, tab['row_variant'])
         job = {'n_scenes': len(scenes), 'traj_scene': torch.from_numpy(tab['traj_scene']).to(dev), 'cloud_offset': tab['cloud_offset'],
                'cloud_points': (torch.cat([s.reshape(-1, 2).to(dev, torch.float32) for s in scenes]).contiguous() if use_cloud else None)}
@@ -589,7 +589,7 @@ class _GaussianDiffusionBase(nn.Module):
         hard_conds  list of one dict per scene, the same waypoint indices in every scene; values (S,) or (n_i, S)
         n_samples   trajectories per scene: an int, or one count per scene
 
-        Every scene is encoded once (``ramp_encode_scene``), the latents (one row per scene plus the shared all-zero
+        All scenes are encoded in one call (``ramp_encode_scenes``), the latents (one row per scene plus the shared all-zero
         unconditional row), the row -> latent table and the per-scene APF clouds go to the context, and ONE job runs.  Returns
         ``(result, traj_scene)``: what ``run_inference`` returns for the concatenated batch -- (steps + 1, B, H, S) if
         ``return_chain`` else (B, H, S), a scene's samples adjacent, scenes in order -- and the (B,) int32 scene of each

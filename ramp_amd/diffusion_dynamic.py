@@ -541,7 +541,7 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         cost_cloud = torch.cat(clouds).contiguous()
         cost_off = np.concatenate([[0], np.cumsum([c.shape[0] for c in clouds])]).astype(np.int32)
         m.ctx()
-        latents = torch.cat([m.encode_scene(ep.cloud) for ep in eps] + [torch.zeros(1, m.context_dim, device=device)])
+        latents = torch.cat([m.encode_scenes([ep.cloud for ep in eps]), torch.zeros(1, m.context_dim, device=device)])
         m.set_scenes(latents, tab['row_variant'])
         first_dev = torch.from_numpy(tab['traj_first']).to(device)
         mask, plen, smooth = torch.empty(B, dtype=torch.int32, device=device), torch.empty(B, device=device), torch.empty(B, device=device)

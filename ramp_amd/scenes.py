@@ -111,6 +111,40 @@ def build_eval_tables(counts: Sequence[int], box_counts: Optional[Sequence[int]]
     return out
 
 
+def build_encode_tables(shapes: Sequence[Sequence[int]]) -> Dict[str, np.ndarray]:
+    """CSR tables of a ragged batch of scenes for the scene encoder (``TemporalUnetInference.encode_scenes`` ->
+    ``ramp_encode_scenes``), the clouds concatenated point by point in scene order.
+
+    shapes   per scene ``(n_obstacles, n_points)``: the leading dimensions of its ``(No, Np, D)`` cloud; scenes may differ in both,
+             inside one scene every obstacle has ``n_points`` points
+
+    Returns int32 arrays: ``scene_first`` (n_scenes + 1) first obstacle of each scene and ``obstacle_first`` (n_obstacles + 1) first
+    point of each obstacle, both from 0 and strictly increasing.  Refused, as the C ABI refuses them: no scene, a scene without an
+    obstacle or with empty obstacles, totals beyond 32-bit offsets."""
+    n_scenes = len(shapes)
+    if n_scenes == 0:
+        raise ValueError("no scenes given")
+    counts, sizes, total = [], [], 0
+    for i, sh in enumerate(shapes):
+        if len(sh) != 2:
+            raise ValueError(f"scene {i}: expected (n_obstacles, n_points), got {tuple(sh)}")
+        no, npts = int(sh[0]), int(sh[1])
+        if no <= 0:
+            raise ValueError(f"scene {i} has no obstacle (n_obstacles = {no})")
+        if npts <= 0:
+            raise ValueError(f"scene {i} has empty obstacles (n_points = {npts})")
+        total += no * npts
+        if total >= 2 ** 31:
+            raise ValueError(f"scene {i}: the concatenated clouds do not fit 32-bit offsets")
+        counts.append(no)
+        sizes.append(npts)
+    scene_first = np.zeros(n_scenes + 1, dtype=np.int64)
+    np.cumsum(counts, out=scene_first[1:])
+    obstacle_first = np.zeros(int(scene_first[-1]) + 1, dtype=np.int64)
+    np.cumsum(np.repeat(np.asarray(sizes, dtype=np.int64), counts), out=obstacle_first[1:])
+    return {"scene_first": scene_first.astype(np.int32), "obstacle_first": obstacle_first.astype(np.int32)}
+
+
 def build_episode_tables(counts: Sequence[int], row_patterns: Sequence[Sequence[int]]) -> Dict[str, np.ndarray]:
     """Tables of one many-episode replanning job (``run_inference_episodes`` -> ``ramp_set_scenes`` + ``ramp_replan_episodes``): the
     loop over contexts and experiments of the reference's ``scripts/inference/inference_dynamic.py`` turned into one batch.

@@ -101,6 +101,7 @@ class TemporalUnetInference(nn.Module):
         self.scene_cache = SceneCache()
         self.cached_scene_latents = None
         self.cached_batch_size = None
+        self.last_encode_passes = None      # passes of the last encode_scenes call (ramp_encode_scenes' n_passes_out)
 
     # ------------------------------------------------------------------ state dict
     def state_dict(self, *args, destination=None, prefix='', keep_vars=False):
@@ -227,17 +228,44 @@ class TemporalUnetInference(nn.Module):
     # ------------------------------------------------------------------ scene
     @torch.no_grad()
     def encode_scene(self, cloud: torch.Tensor) -> torch.Tensor:
-        """cloud (No,Np,D) or (n_scenes,No,Np,D) -> latents (n_scenes, context_dim), on the HIP kernels
-        (ramp_encode_scene).  ``self.scene_encoder`` (torch) only holds the parameters / state_dict."""
-        if cloud.dim() == 3:
-            cloud = cloud.unsqueeze(0)
+        """cloud (No,Np,D) or (n_scenes,No,Np,D) -> latents (n_scenes, context_dim), on the HIP kernels.  One cloud is one
+        ``ramp_encode_scene`` call; the 4-D form is ``encode_scenes`` over its scenes (the same bits, one pass).
+        ``self.scene_encoder`` (torch) only holds the parameters / state_dict."""
+        if cloud.dim() == 4:
+            return self.encode_scenes(list(cloud))
         cloud = cloud.to(self._device(), torch.float32).contiguous()
-        out = torch.empty((cloud.shape[0], self.context_dim), device=self._device(), dtype=torch.float32)
+        out = torch.empty((1, self.context_dim), device=self._device(), dtype=torch.float32)
         with torch.cuda.device(self._device()):
-            for i in range(cloud.shape[0]):
-                _lib.check(_lib.load().ramp_encode_scene(self.ctx(), _lib.ptr(cloud[i]), cloud.shape[1], cloud.shape[2],
-                                                         cloud.shape[3], out[i].data_ptr(), _lib.current_stream()),
-                           "ramp_encode_scene")
+            _lib.check(_lib.load().ramp_encode_scene(self.ctx(), _lib.ptr(cloud), cloud.shape[0], cloud.shape[1],
+                                                     cloud.shape[2], out.data_ptr(), _lib.current_stream()),
+                       "ramp_encode_scene")
+        return out
+
+    @torch.no_grad()
+    def encode_scenes(self, clouds, max_points: Optional[int] = None) -> torch.Tensor:
+        """Many scenes in one call (``ramp_encode_scenes``): ``clouds`` is a list of (No_i, Np_i, D) tensors whose obstacle and point
+        counts may differ; returns the latents (n_scenes, context_dim), row i bit for bit what ``encode_scene(clouds[i])`` gives.
+        The scenes run in passes of at most ``max_points`` points (None: the library's default; a larger scene gets a pass of its
+        own) and the number of launches per pass does not depend on the number of scenes; ``last_encode_passes`` holds the pass count."""
+        from .scenes import build_encode_tables
+        clouds = list(clouds)
+        for i, c in enumerate(clouds):
+            if c.dim() != 3:
+                raise ValueError(f"scene {i}: a cloud is (n_obstacles, n_points, D), got {tuple(c.shape)}")
+            if c.shape[2] != clouds[0].shape[2]:
+                raise ValueError(f"scene {i}: point dimension {c.shape[2]}, scene 0 has {clouds[0].shape[2]}")
+        tab = build_encode_tables([(c.shape[0], c.shape[1]) for c in clouds])
+        dev = self._device()
+        D = int(clouds[0].shape[2])
+        pts = torch.cat([c.to(dev, torch.float32).reshape(-1, D) for c in clouds]).contiguous()
+        out = torch.empty((len(clouds), self.context_dim), device=dev, dtype=torch.float32)
+        n_passes = C.c_int32(0)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ramp_encode_scenes(self.ctx(), _lib.ptr(pts), tab["obstacle_first"].ctypes.data_as(_lib.c_i32p),
+                                                      tab["scene_first"].ctypes.data_as(_lib.c_i32p), len(clouds), D,
+                                                      int(max_points or 0), _lib.ptr(out), C.byref(n_passes), _lib.current_stream()),
+                       "ramp_encode_scenes")
+        self.last_encode_passes = int(n_passes.value)
         return out
 
     def set_scene(self, latents: torch.Tensor, row_pattern: List[int]):
