@@ -26,6 +26,10 @@ extern "C" {
 
 typedef struct ramp_ctx ramp_ctx;
 
+/* most network rows one trajectory may have: ramp_score / ramp_score_rows accept n_rp up to it, ramp_sample_composed composes up to
+ * RAMP_MAX_ROWS_PER_TRAJ - 1 obstacle sets (the last row is the unconditional one) */
+#define RAMP_MAX_ROWS_PER_TRAJ 8
+
 /* Architecture of TemporalUnetInference.__init__ (UnetInference.py:42-56, 93-145). */
 typedef struct ramp_config {
   int32_t state_dim;       /* S: 4 (Maze2D) or 6 (Maze3D)                              */
@@ -141,7 +145,7 @@ int ramp_encode_scenes(ramp_ctx* ctx, const float* points, const int32_t* obstac
                        void* stream);
 
 /* TemporalUnetInference.forward / forward_no_energy (UnetInference.py:157-224).
- * x (B,H,S); each trajectory is evaluated n_rp times (rows b*n_rp + v).  f_out (B*n_rp,H,S)
+ * x (B,H,S); each trajectory is evaluated n_rp times (rows b*n_rp + v, 1 <= n_rp <= RAMP_MAX_ROWS_PER_TRAJ).  f_out (B*n_rp,H,S)
  * receives forward_no_energy's output, eps_out (B*n_rp,H,S) the energy gradient; either may be
  * NULL.  t is the diffusion timestep of EVERY row, 0 <= t < T of the prepared table (what the samplers pass: make_timesteps'
  * batch-uniform vector); one timestep per row is ramp_score_rows below.
@@ -179,7 +183,7 @@ typedef struct ramp_apf_params {
 
 typedef struct ramp_sample_params {
   int32_t B;               /* trajectories                                                */
-  int32_t n_rp;            /* 2 = CFG, 3 = compose                                        */
+  int32_t n_rp;            /* 2 = CFG, 3 = compose; ramp_sample_composed: 2 .. 8          */
   int32_t n_steps;         /* loop iterations                                             */
   int32_t ddim;            /* 0 = DDPM (ddpm_sample_fn), 1 = DDIM eta=0                   */
   double w0, w1;           /* guidance weights (w for CFG; w1,w2 for compose)             */
@@ -244,6 +248,25 @@ typedef struct ramp_scene_batch {
 } ramp_scene_batch;
 int ramp_sample_scenes(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_scene_batch* scenes, const float* noise,
                        float* chain_out, float* x_out, void* stream);
+/* Composition over ANY number of obstacle sets, many scenes per job: p_mean_variance_compose samples with
+ * e = u + sum_k w_k (c_k - u) over obstacle sets (diffusion_model_static.py:188-229, diffusion_model_3d.py:163-182; the 3-D file carries the
+ * three-set form as commented-out code, "for 2 compose (more than two obstacle sets)", :165-174).  Here a trajectory's rows and their weights
+ * are data: n_rp = (most sets of any scene) + 1 rows per trajectory, row b * n_rp + j reads the latent the ramp_set_scenes table gives it
+ * and its gradient enters e_comb[b] = sum_j row_weight[b][j] eps[b * n_rp + j] (j ascending) -- set k of the scene with w_k, the
+ * unconditional row with 1 - sum_k w_k, a padding row (a scene with fewer sets) with 0.  p->w0 and p->w1 are ignored.  The table is
+ * copied into a buffer of the context before the launch and the captured graph reads that buffer: the graph is keyed on n_rp and
+ * "composed", not on the weights, so a second job of the same shape with other weights replays the same graph and gets its own
+ * weights.  `scenes` gives every trajectory its own APF cloud exactly as in ramp_sample_scenes (NULL = no APF clouds).  Graph capture,
+ * Philox noise, the range guard, the fp16x3 repeat and calibration reuse are ramp_sample's.  Refused on the host before any launch
+ * (non-zero, the entry's name in ramp_last_error): g == NULL, row_weight == NULL, n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ,
+ * n_rp != p->n_rp, no ramp_set_scenes table in place, a table shorter than B * n_rp rows. */
+typedef struct ramp_guidance_rows {
+  int32_t n_rp;               /* rows per trajectory, 2 .. RAMP_MAX_ROWS_PER_TRAJ; must equal p->n_rp */
+  int32_t reserved;
+  const float* row_weight;    /* device (B, n_rp): weight of each row's gradient in e_comb */
+} ramp_guidance_rows;
+int ramp_sample_composed(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_guidance_rows* g, const ramp_scene_batch* scenes,
+                         const float* noise, float* chain_out, float* x_out, void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from
@@ -459,6 +482,13 @@ int ramp_select_best_scenes(const float* traj, int32_t B, int32_t H, int32_t S, 
 int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, double w0, double w1,
                   float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, int32_t clip, int32_t predict_x0,
                   float* x0_out, float* mean_out, float* ecomb_out, void* stream);
+/* ramp_cfg_mean with one weight per network row (the guidance step of ramp_sample_composed when the prefix is not shared;
+ * diffusion_model_static.py:188-229, diffusion_model_3d.py:165-174): e_comb[b] = sum_j row_weight[b * n_rp + j] eps[b * n_rp + j], j = 0 .. n_rp - 1
+ * in that order, then x0, clamp and posterior mean exactly as ramp_cfg_mean.  row_weight device (B, n_rp), 2 <= n_rp <=
+ * RAMP_MAX_ROWS_PER_TRAJ; HS a multiple of 4 and every tensor 16-byte aligned (four elements per access). */
+int ramp_cfg_mean_rows(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, const float* row_weight,
+                       float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, int32_t clip, int32_t predict_x0,
+                       float* x0_out, float* mean_out, float* ecomb_out, void* stream);
 /* the DDIM update of ddim_p_sample given x0 (diffusion_model_static.py:321-333 / _dynamic.py:436-447), eta = 0:
  * x_out = sqrt_a_prev * x0 + dir_coef * (x - sqrt_a_t * x0) / sqrt_1m_a_t */
 int ramp_ddim_finish(const float* x, const float* x0, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,

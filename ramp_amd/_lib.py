@@ -41,6 +41,14 @@ class RampSceneBatch(C.Structure):
                 ("cloud_offset_host", c_i32p)]
 
 
+class RampGuidanceRows(C.Structure):
+    """ramp_guidance_rows: the per-trajectory guidance weights of a composed job (ramp_sample_composed)."""
+    _fields_ = [("n_rp", C.c_int32), ("reserved", C.c_int32), ("row_weight", C.c_void_p)]
+
+
+MAX_ROWS_PER_TRAJ = 8       # RAMP_MAX_ROWS_PER_TRAJ
+
+
 class RampSampleParams(C.Structure):
     _fields_ = [("B", C.c_int32), ("n_rp", C.c_int32), ("n_steps", C.c_int32), ("ddim", C.c_int32),
                 ("w0", C.c_double), ("w1", C.c_double),
@@ -128,6 +136,8 @@ PROTOTYPES = {
                               C.c_void_p]),
     "ramp_sample_scenes": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampSceneBatch), C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
+    "ramp_sample_composed": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch),
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_philox_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "ramp_replan": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampReplanState), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.POINTER(RampReplanResult), C.c_void_p]),
@@ -164,6 +174,9 @@ PROTOTYPES = {
     "ramp_cfg_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),
+    "ramp_cfg_mean_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
     "ramp_ddim_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p,
                                    C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "ramp_op_gemm": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 7 + [C.c_void_p]),

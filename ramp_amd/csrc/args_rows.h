@@ -38,6 +38,8 @@ int launch_ln_bwd(const float* dy, const float* x, const float* gamma, const flo
 int launch_expand_rows(const float* in, float* out, int R, int n_rp, int L, int C, const float* rowbias, int rb_stride,
                        const int* rowvar, int row0, hipStream_t s);
 int launch_combine_rows(const float* in, float* out, int B, int n_rp, int L, int C, const float* w, hipStream_t s);
+// the same sum with the weights as DEVICE data, one line of n_rp per trajectory (2 <= n_rp <= 8): out[b] = sum_j row_weight[b n_rp + j] in[b n_rp + j]
+int launch_combine_rows_weighted(const float* in, float* out, int B, int n_rp, int L, int C, const float* row_weight, hipStream_t s);
 
 // GEGLU on ag (n_tok, 2*F): hg = a * gelu(g); backward writes dag (n_tok, 2*F)
 int launch_geglu_fwd(const float* ag, float* hg, int n_tok, int F, hipStream_t s);

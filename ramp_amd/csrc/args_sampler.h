@@ -16,6 +16,9 @@ struct CfgMeanArgs {
   int predict_x0 = 0;           // predict_epsilon=False (the reference constructor's default): the combined network output IS x0
 };
 int launch_cfg_mean(const CfgMeanArgs& a, hipStream_t s);
+// the same step with e_comb[b] = sum_j row_weight[b n_rp + j] eps[b n_rp + j] (j = 0 .. n_rp - 1 in that order; row_weight device (B, n_rp),
+// 2 <= n_rp <= 8, HS a multiple of 4); w0 / w1 / w0p1 are not read
+int launch_cfg_mean_rows(const CfgMeanArgs& a, const float* row_weight, hipStream_t s);
 
 struct HardConds { const int* idx = nullptr; const float* val = nullptr; int n = 0; };  // val (n,B,S)
 

@@ -129,6 +129,10 @@ struct ramp_ctx {
   int* s_hard_idx = nullptr; float* s_hard_val = nullptr; size_t s_hard_val_cap = 0; float* s_window = nullptr;
   float* s_cloud = nullptr; size_t s_cloud_cap = 0;
   int *s_traj_scene = nullptr, *s_scene_off = nullptr; size_t s_traj_scene_cap = 0, s_scene_off_cap = 0;      // per-scene APF of ramp_sample_scenes
+  // ramp_sample_composed: the job's (B, n_rp) guidance weights, copied here before the launch (the captured graph reads this buffer, so the
+  // weights are data of a replay); g_weight_cur is non-null only while that job's evaluations are being launched or captured -- the
+  // shared-prefix backward and the guidance step then take a trajectory's weights from its line instead of the host scalars
+  float* g_weight = nullptr; size_t g_weight_cap = 0; const float* g_weight_cur = nullptr;
   // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
   // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
   hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
@@ -787,6 +791,14 @@ int st_forward(Run& r, ST& m, const float* x, int share = 1) {
 
 // share > 1: see st_forward; comb = the weights of the rows' gradients in what the sampler uses.  dy, and everything down
 // to d(z1) of the first block, have r.R rows; from there on (and dx) one COMBINED row per trajectory.
+// out[b] = sum_j w_j in[b share + j] where the rows of a trajectory meet again: the job's host scalars, or (a composed job) the chunk's lines of
+// the device weight table -- r.row0 = b0 * share is the chunk's first row, hence its first trajectory's first weight
+int combine_prefix(Run& r, const float* in, float* out, int Rp, int share, int L, int C, const float* comb) {
+  ramp_ctx* c = r.c;
+  if (c->g_weight_cur) LAUNCH(c, r.s, CAT_ROW, 0, launch_combine_rows_weighted(in, out, Rp, share, L, C, c->g_weight_cur + r.row0, r.s));
+  else LAUNCH(c, r.s, CAT_ROW, 0, launch_combine_rows(in, out, Rp, share, L, C, comb, r.s));
+  return 0;
+}
 int st_backward(Run& r, ST& m, const float* x, const float* dy, float* dx, int share = 1, const float* comb = nullptr) {
   ramp_ctx* c = r.c; const int R = r.R, M = R * m.L, D = 256;
   const int Rp = R / share, Mp = Rp * m.L;
@@ -817,7 +829,7 @@ int st_backward(Run& r, ST& m, const float* x, const float* dy, float* dx, int s
     const bool pre = share > 1 && b == 0;
     const int Rb = pre ? Rp : R, Mb = Rb * m.L;
     if (pre) {      // the rows of a trajectory meet again: dz (free now) <- sum_j comb_j dz1[row j]
-      LAUNCH(c, r.s, CAT_ROW, 0, launch_combine_rows(dz1, dz, Rp, share, m.L, D, comb, r.s));
+      CK(combine_prefix(r, dz1, dz, Rp, share, m.L, D, comb));
       std::swap(dz, dz1);
     }
     CK(r.linear(lin(dz1, D, k.wo_b, nullptr, c->t_o, D, Mb, D, D)));                    // d(o)
@@ -842,7 +854,7 @@ int st_backward(Run& r, ST& m, const float* x, const float* dy, float* dx, int s
   GnBwdArgs g; g.dy = c->t_xn; g.x = x; g.stats = m.a_gst; g.gamma = m.gn_g; g.beta = m.gn_b; g.add = dy; g.dx = dx;
   g.R = Rp; g.L = m.L; g.C = m.C; g.mish = 0;
   if (share > 1) {   // the gradient through the outer residual, combined (t_o is free after the attention backward)
-    LAUNCH(c, r.s, CAT_ROW, 0, launch_combine_rows(dy, c->t_o, Rp, share, m.L, m.C, comb, r.s));
+    CK(combine_prefix(r, dy, c->t_o, Rp, share, m.L, m.C, comb));
     g.add = c->t_o;
   }
   LAUNCH(c, r.s, CAT_ROW, 0, launch_gn_bwd(g, r.s));
@@ -1254,14 +1266,16 @@ int ensure_sampler_buffers(ramp_ctx* c, int B, int n_rp, int n_steps, bool chain
 
 // one score evaluation over all rows of a batch, chunked to the context capacity
 // comb != nullptr (n_rp host floats; sampling jobs): the rows of a trajectory share the network prefix they have in
-// common and eps_out receives (B, H, S) = sum_j comb[j] * eps of row j instead of the (B n_rp, H, S) row gradients
+// common and eps_out receives (B, H, S) = sum_j comb[j] * eps of row j instead of the (B n_rp, H, S) row gradients.
+// In a composed job (c->g_weight_cur set) comb is ONLY that non-null flag: the weights are the lines of the device table and combine_prefix
+// never reads comb, which holds three floats whatever n_rp is
 int score_all(ramp_ctx* c, const float* x, int B, int n_rp, int t, float* f_out, float* eps_out, hipStream_t s,
               const float* comb = nullptr) {
   const int H = c->cfg.horizon, S = c->cfg.state_dim;
   RAMP_REQUIRE(c->finalized, "weights not finalized");
   RAMP_REQUIRE(c->time_table != nullptr && t >= 0 && t < c->tt_T, "timestep outside the prepared time table");
   RAMP_REQUIRE(c->cross_bias != nullptr, "ramp_set_scene has not been called");
-  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= 3, "bad batch");
+  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= RAMP_MAX_ROWS_PER_TRAJ, "bad batch");
   RAMP_REQUIRE(c->row_variant_cap >= B * n_rp, "row-variant table shorter than the batch (call ramp_set_scene after sizing)");
   RAMP_REQUIRE(c->rv_rows == 0 || B * n_rp <= c->rv_rows, "the batch has more rows (B * n_rp) than the row -> variant table given to ramp_set_scenes");
   const int cap_traj = c->cfg.max_rows / n_rp;
@@ -1899,7 +1913,7 @@ int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, 
 int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const int32_t* t_rows_host, float* f_out, float* eps_out,
                     void* stream) {
   RAMP_REQUIRE(c && x && t_rows_host, "null argument");
-  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= 3 && (long)B * n_rp <= (1l << 24), "bad batch");
+  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= RAMP_MAX_ROWS_PER_TRAJ && (long)B * n_rp <= (1l << 24), "bad batch");
   RAMP_REQUIRE(c->time_table != nullptr && c->tt_T > 0, "time table not prepared (ramp_prepare_time_table)");
   const size_t n = (size_t)B * n_rp;
   for (size_t i = 0; i < n; ++i)
@@ -1919,6 +1933,7 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 }
 
 // sc != nullptr: a job of many scenes (ramp_sample_scenes) -- the APF of trajectory b runs against the cloud of scene traj_scene[b]
+// c->g_weight_cur != nullptr: a composed job (ramp_sample_composed) -- the rows' weights in e_comb come from that device table
 static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
@@ -1941,7 +1956,8 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     RAMP_HIP_CHECK(hipGetLastError());
   }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
-  const std::array<float, 3> comb = comb_weights(p->n_rp, p->w0, p->w1);
+  // (a composed job: comb below only says "combined evaluation", see score_all; its weights are c->g_weight_cur's)
+  const std::array<float, 3> comb = c->g_weight_cur ? std::array<float, 3>{0.f, 0.f, 0.f} : comb_weights(p->n_rp, p->w0, p->w1);
   const bool shared = p->n_rp > 1 && c->share_prefix;
   for (int j = 0; j < p->n_steps; ++j) {
     // fp16x3: evaluation 0 runs scaled from the context's CANONICAL maxima (canonical_calibration below) -- or, with
@@ -1959,15 +1975,17 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
     float* chain_j = chain ? c->s_chain + (size_t)(j + 1) * n : nullptr;
     const bool apf = (p->apf.cloud != nullptr || sc_apf) && p->apply_apf && p->apply_apf[j];
+    // the guidance step: the shared prefix has combined the rows already (one row left); otherwise by the job's scalars or its weight table
+    const bool by_table = c->g_weight_cur && !shared;
     if (!p->ddim) {
       m.coef1 = p->coef1[j]; m.coef2 = p->coef2[j]; m.mean = c->s_mean; m.x0 = nullptr;
-      LAUNCH(c, s, CAT_SAMPLER, 0, launch_cfg_mean(m, s));
+      LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
       if (apf) { ap.traj = c->s_mean; for (int q = 0; q < std::max(1, p->apf.passes); ++q) LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); }
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddpm_finish(c->s_mean, c->s_noise + (size_t)(j + 1) * n, p->stdv[j], p->noise_scale ? p->noise_scale[j] : 1.f, p->use_noise[j],
                             hc, c->s_x, chain_j, B, H, S, s));
     } else {
       m.mean = nullptr; m.x0 = c->s_x0;
-      LAUNCH(c, s, CAT_SAMPLER, 0, launch_cfg_mean(m, s));
+      LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
       if (apf) {
         ap.traj = c->s_x0;
         for (int q = 0; q < std::max(1, p->apf.passes); ++q) { LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x0, hc, B, H, S, s)); }
@@ -1996,7 +2014,7 @@ static int canonical_calibration(ramp_ctx* c, const ramp_sample_params* p, hipSt
   }
   RAMP_REQUIRE((H * S) % 4 == 0, "H * S must be a multiple of 4");
   CK(launch_philox_normal(c->s_x, (long)B * H * S, c->c_cal_rec, s));
-  const std::array<float, 3> comb = comb_weights(p->n_rp, p->w0, p->w1);
+  const std::array<float, 3> comb = c->g_weight_cur ? std::array<float, 3>{0.f, 0.f, 0.f} : comb_weights(p->n_rp, p->w0, p->w1);      // (composed: a flag only, as in sample_body)
   const bool shared = p->n_rp > 1 && c->share_prefix;
   return guarded_eval(c, 1, TABLE_EVEN, TABLE_CANONICAL, c->s_x, B, p->n_rp, p->t[0], nullptr, c->s_eps, s, shared ? comb.data() : nullptr);
 }
@@ -2025,14 +2043,15 @@ static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, 
   return 0;
 }
 
+// g != nullptr: a composed job (ramp_sample_composed; its arguments are checked there) -- n_rp up to RAMP_MAX_ROWS_PER_TRAJ, p->w0 / p->w1 not read
 static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
-                      void* stream) {
+                      void* stream, const ramp_guidance_rows* g = nullptr) {
   RAMP_REQUIRE(c && p, "null argument");
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
   RAMP_REQUIRE(p->noise_mode == 0 || (c->cfg.horizon * c->cfg.state_dim) % 4 == 0, "noise_mode 1 needs H * S to be a multiple of 4");
   RAMP_REQUIRE(noise || p->noise_mode == 1, "null noise (only a job that draws its own, noise_mode 1, may omit it)");
-  RAMP_REQUIRE(p->B > 0 && p->n_steps > 0 && p->n_rp >= 1 && p->n_rp <= 3, "bad sample dims");
+  RAMP_REQUIRE(p->B > 0 && p->n_steps > 0 && p->n_rp >= 1 && p->n_rp <= (g ? RAMP_MAX_ROWS_PER_TRAJ : 3), "bad sample dims");
   RAMP_REQUIRE(p->t && p->sqrt_recip && p->sqrt_recipm1, "missing schedule arrays");
   if (p->ddim) RAMP_REQUIRE(p->sqrt_a_t && p->sqrt_1m_a_t && p->sqrt_a_prev && p->dir_coef, "missing DDIM arrays");
   else RAMP_REQUIRE(p->coef1 && p->coef2 && p->stdv && p->use_noise, "missing DDPM arrays");
@@ -2064,6 +2083,18 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_scene_off, sc->cloud_offset_host, ((size_t)sc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
   }
+  std::vector<float> g_host;      // the weights on the host: part of the canonical calibration's key below
+  if (g) {
+    const size_t nw = (size_t)B * p->n_rp;
+    CK(grow(c, c->g_weight, c->g_weight_cap, nw));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->g_weight, g->row_weight, nw * 4, hipMemcpyDeviceToDevice, s));
+    if (c->gemm_mode == 2 && !c->force_x6 && c->cal_reuse) {
+      g_host.resize(nw);
+      RAMP_HIP_CHECK(hipMemcpyAsync(g_host.data(), c->g_weight, nw * 4, hipMemcpyDeviceToHost, s));
+      RAMP_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    c->g_weight_cur = c->g_weight;      // (the entry point clears it when this function returns)
+  }
   if (p->n_hard) {
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_val, p->hard_val, hv * 4, hipMemcpyDeviceToDevice, s));
@@ -2078,10 +2109,11 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   c->launches = 0;
   invalidate_calibrations(c, CAL_SCORE | CAL_REPLAN);      // the loop below overwrites the delayed-scaling tables
   // key: everything baked into the captured nodes.  It also carries whatever decides that the job touches a buffer that may not exist yet
-  // (s_chain: ch; s_cloud / s_window: has_apf and apply_apf; s_hard_val: n_hard; s_philox: noise_mode; the scene tables: the SCEN tag) --
+  // (s_chain: ch; s_cloud / s_window: has_apf and apply_apf; s_hard_val: n_hard; s_philox: noise_mode; the scene tables: the SCEN tag; g_weight: the COMP tag) --
   // renew() relies on that when it lets a first allocation pass without dropping the graphs: add the field here with any new optional buffer
   Key key;
-  key.put(p->B); key.put(p->n_rp); key.put(p->n_steps); key.put(p->ddim); key.put(p->w0); key.put(p->w1);
+  const double kw0 = g ? 0.0 : p->w0, kw1 = g ? 0.0 : p->w1;      // (a composed job's weights are data of the graph, not part of its shape)
+  key.put(p->B); key.put(p->n_rp); key.put(p->n_steps); key.put(p->ddim); key.put(kw0); key.put(kw1);
   key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps); key.put(p->sqrt_recipm1, p->n_steps);
   if (p->ddim) { key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps); key.put(p->sqrt_a_prev, p->n_steps); key.put(p->dir_coef, p->n_steps); }
   else { key.put(p->coef1, p->n_steps); key.put(p->coef2, p->n_steps); key.put(p->stdv, p->n_steps); key.put(p->use_noise, p->n_steps); }
@@ -2093,14 +2125,16 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   key.put(p->apf.n_points); key.put(p->apf.window); key.put(p->apf.threshold); key.put(p->apf.strength); key.put(p->apf.passes);
   const int ch = chain; key.put(ch); key.put(c->force_x6); key.put(p->noise_mode);
   if (sc) { const int tag[3] = {0x5343454e /* "SCEN" */, sc_apf ? sc->n_scenes : 0, sc_points}; key.put(tag, 3); }      // (a single-scene job's key has no such tail)
+  if (g) { const int tag = 0x434f4d50 /* "COMP" */; key.put(tag); }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
     // what the canonical maxima depend on: batch, row variants and their weights, first timestep (the scene and the launch plan invalidate it
     // where they change) -- nothing of the caller's data
     Key ck;
-    ck.put(p->B); ck.put(p->n_rp); ck.put(p->t[0]); ck.put(p->w0); ck.put(p->w1);
+    ck.put(p->B); ck.put(p->n_rp); ck.put(p->t[0]); ck.put(kw0); ck.put(kw1);
     const int sp = c->share_prefix; ck.put(sp);
+    if (g) { const int tag = 0x434f4d50; ck.put(tag); ck.put(g_host.data(), (int)g_host.size()); }      // (the operand maxima of the prefix backward follow the weights)
     ck.put(c->scene_epoch);                                 // the scene table's identity; redundant today: set_scene_table drops every saved table (c_cal_valid)
     if (!c->c_cal_valid) {                                  // (scene / plan / mode changed: every saved table is stale; its buffer is reused)
       for (auto& kv : c->c_cal_saved) c->c_cal_free.push_back(kv.second);
@@ -2155,6 +2189,24 @@ int ramp_sample_scenes(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
                        float* x_out, void* stream) {
   RAMP_REQUIRE(scenes, "null scene batch");
   return sample_job(c, p, scenes, noise, chain_out, x_out, stream);
+}
+
+// Composition over any number of obstacle sets (diffusion_model_static.py:188-229; diffusion_model_3d.py:163-182, three sets at :165-174) and many
+// scenes per job: rows and weights are data.  Every refusal is a host check made before anything is staged or launched.
+int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                         float* chain_out, float* x_out, void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_composed: null argument");
+  RAMP_REQUIRE(g, "ramp_sample_composed: null guidance table");
+  RAMP_REQUIRE(g->row_weight, "ramp_sample_composed: null row_weight");
+  RAMP_REQUIRE(g->n_rp >= 2 && g->n_rp <= RAMP_MAX_ROWS_PER_TRAJ, "ramp_sample_composed: n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ");
+  RAMP_REQUIRE(g->n_rp == p->n_rp, "ramp_sample_composed: the guidance table's n_rp differs from the job's");
+  RAMP_REQUIRE(p->B > 0 && (long)p->B * p->n_rp <= (1l << 24), "ramp_sample_composed: bad batch");
+  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, "ramp_sample_composed: H * S must be a multiple of 4 (the guidance step moves four elements per access)");
+  RAMP_REQUIRE(c->rv_rows > 0, "ramp_sample_composed: the row -> latent table comes from ramp_set_scenes (none is in place)");
+  RAMP_REQUIRE(c->rv_rows >= p->B * p->n_rp, "ramp_sample_composed: the ramp_set_scenes table is shorter than B * n_rp rows");
+  const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g);
+  c->g_weight_cur = nullptr;
+  return rc;
 }
 
 // ---- receding-horizon replanning --------------------------------------------------------------------

@@ -256,6 +256,20 @@ int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32
   return launch_cfg_mean(m, as_stream(stream));
 }
 
+int ramp_cfg_mean_rows(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, const float* row_weight,
+                       float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, int32_t clip, int32_t predict_x0, float* x0_out,
+                       float* mean_out, float* ecomb_out, void* stream) {
+  RAMP_REQUIRE(x && eps && row_weight, "ramp_cfg_mean_rows: null argument");
+  RAMP_REQUIRE(n_rp >= 2 && n_rp <= RAMP_MAX_ROWS_PER_TRAJ, "ramp_cfg_mean_rows: n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ");
+  RAMP_REQUIRE(B > 0 && HS > 0 && HS % 4 == 0, "ramp_cfg_mean_rows: B > 0 and H * S a positive multiple of 4");
+  for (const void* q : {(const void*)x, (const void*)eps, (const void*)x0_out, (const void*)mean_out, (const void*)ecomb_out})
+    RAMP_REQUIRE(((uintptr_t)q & 15) == 0, "ramp_cfg_mean_rows: tensors must be 16-byte aligned");
+  CfgMeanArgs m; m.x = x; m.eps = eps; m.B = B; m.HS = HS; m.n_rp = n_rp;
+  m.sqrt_recip = sqrt_recip; m.sqrt_recipm1 = sqrt_recipm1; m.coef1 = coef1; m.coef2 = coef2;
+  m.clip = clip; m.predict_x0 = predict_x0 != 0; m.x0 = x0_out; m.mean = mean_out; m.ecomb = ecomb_out;
+  return launch_cfg_mean_rows(m, row_weight, as_stream(stream));
+}
+
 int ramp_ddim_finish(const float* x, const float* x0, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,
                      float dir_coef, float* x_out, int32_t B, int32_t H, int32_t S, void* stream) {
   RAMP_REQUIRE(x && x0 && x_out, "null argument");

@@ -436,6 +436,28 @@ int launch_combine_rows(const float* in, float* out, int B, int n_rp, int L, int
   return 0;
 }
 
+// combine with the weights as per-trajectory DEVICE data (a composed job, ramp_sample_composed): out[b] = sum_j rw[b n_rp + j] in[b n_rp + j],
+// j = 0 .. n_rp - 1 in that order; rw points at the weights of the chunk's first trajectory
+__global__ __launch_bounds__(256) void combine_rows_weighted_kernel(const float* __restrict__ in, float* __restrict__ out, long n4,
+                                                                     int row4, int n_rp, const float* __restrict__ rw) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const long b = i / row4; const int w = (int)(i - b * row4);
+    const f32x4* src = reinterpret_cast<const f32x4*>(in) + (b * n_rp) * row4 + w;
+    const float* wb = rw + b * n_rp;
+    f32x4 v = src[0] * wb[0];
+    for (int j = 1; j < n_rp; ++j) v += src[j * (long)row4] * wb[j];
+    reinterpret_cast<f32x4*>(out)[i] = v;
+  }
+}
+int launch_combine_rows_weighted(const float* in, float* out, int B, int n_rp, int L, int C, const float* row_weight, hipStream_t s) {
+  RAMP_REQUIRE(B > 0 && n_rp >= 2 && n_rp <= 8 && C % 4 == 0 && row_weight, "bad combine_rows_weighted arguments");
+  const long n4 = (long)B * L * C / 4;
+  long g = (n4 + 255) / 256; if (g > 16384) g = 16384;
+  hipLaunchKernelGGL(combine_rows_weighted_kernel, dim3((int)g), dim3(256), 0, s, in, out, n4, L * C / 4, n_rp, row_weight);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // ------------------------------------------------------------------------------------------
 // GEGLU
 // ------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@
 
 namespace ramp {
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ float mul(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float add(float a, float b) { return __fadd_rn(a, b); }
 __device__ __forceinline__ float sub(float a, float b) { return __fsub_rn(a, b); }
@@ -51,6 +53,45 @@ int launch_cfg_mean(const CfgMeanArgs& a, hipStream_t s) {
   const long n = (long)a.B * a.HS;
   long g = (n + 255) / 256; if (g > 8192) g = 8192;
   hipLaunchKernelGGL(cfg_mean_kernel, dim3((int)g), dim3(256), 0, s, a);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Composition over any number of obstacle sets, e = u + sum_k w_k (c_k - u) (diffusion_model_static.py:188-229; diffusion_model_3d.py:163-182,
+// the three-set form at :165-174) written as one weight per row, e_comb[b] = sum_j rw[b][j] eps[b n_rp + j]: the unconditional row carries
+// 1 - sum_k w_k.  Four elements per thread (HS % 4 == 0 keeps them inside one trajectory); x0, clamp and posterior mean as in cfg_mean_kernel.
+__global__ __launch_bounds__(256) void cfg_mean_rows_kernel(CfgMeanArgs a, const float* __restrict__ rw) {
+  const int hs4 = a.HS / 4;
+  const long n4 = (long)a.B * hs4;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+    const long b = i / hs4; const int e4 = (int)(i - b * hs4);
+    const f32x4* ep = reinterpret_cast<const f32x4*>(a.eps) + (b * a.n_rp) * hs4 + e4;
+    const float* wb = rw + b * a.n_rp;
+    const f32x4 e0 = ep[0]; const float w0 = wb[0];
+    f32x4 ec = f32x4{mul(w0, e0[0]), mul(w0, e0[1]), mul(w0, e0[2]), mul(w0, e0[3])};
+    for (int j = 1; j < a.n_rp; ++j) {
+      const f32x4 ej = ep[j * (long)hs4]; const float wj = wb[j];
+      ec = f32x4{add(ec[0], mul(wj, ej[0])), add(ec[1], mul(wj, ej[1])), add(ec[2], mul(wj, ej[2])), add(ec[3], mul(wj, ej[3]))};
+    }
+    const f32x4 xv = reinterpret_cast<const f32x4*>(a.x)[i];
+    f32x4 x0, mean;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      float v = a.predict_x0 ? ec[q] : sub(mul(a.sqrt_recip, xv[q]), mul(a.sqrt_recipm1, ec[q]));
+      if (a.clip) v = fminf(fmaxf(v, -1.f), 1.f);
+      x0[q] = v;
+      mean[q] = add(mul(a.coef1, v), mul(a.coef2, xv[q]));
+    }
+    if (a.ecomb) reinterpret_cast<f32x4*>(a.ecomb)[i] = ec;
+    if (a.x0) reinterpret_cast<f32x4*>(a.x0)[i] = x0;
+    if (a.mean) reinterpret_cast<f32x4*>(a.mean)[i] = mean;
+  }
+}
+int launch_cfg_mean_rows(const CfgMeanArgs& a, const float* row_weight, hipStream_t s) {
+  RAMP_REQUIRE(a.B > 0 && a.HS > 0 && a.HS % 4 == 0 && a.n_rp >= 2 && a.n_rp <= 8 && row_weight, "bad cfg_mean_rows dims");
+  const long n4 = (long)a.B * (a.HS / 4);
+  long g = (n4 + 255) / 256; if (g > 8192) g = 8192;
+  hipLaunchKernelGGL(cfg_mean_rows_kernel, dim3((int)g), dim3(256), 0, s, a, row_weight);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }

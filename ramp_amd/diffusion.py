@@ -360,9 +360,10 @@ class _GaussianDiffusionBase(nn.Module):
             self.last_job_mode = "bf16x6"
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
-                return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None):
+                return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None):
         """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
-        (``ramp_sample_scenes``); ``obstacle_pts`` is not read then."""
+        (``ramp_sample_scenes``); ``obstacle_pts`` is not read then.  ``guidance`` (with a ``scene_job``): a composed job
+        (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``."""
         m = self.model
         dev = self._device()
         H, S = m.n_support_points, self.state_dim
@@ -373,6 +374,13 @@ class _GaussianDiffusionBase(nn.Module):
         p, arrays = _lib.RampSampleParams(), _HostArrays()
         p.B, p.n_rp = B, self._n_rp()
         p.w0, p.w1 = (float(w) for w in (self.compose_weights if self.compose else (self.cfg_weight, 0.0)))
+        rows = None
+        if guidance is not None:      # the weights are the table's; w0 / w1 are not read
+            if scene_job is None:
+                raise ValueError("a composed job needs its scene job (the row -> latent table comes from set_scenes)")
+            p.n_rp, p.w0, p.w1 = int(guidance['n_rp']), 0.0, 0.0
+            rows = _lib.RampGuidanceRows()
+            rows.n_rp, rows.row_weight = p.n_rp, _lib.ptr(arrays.keep(guidance['row_weight']))
         self._fill_schedule(p, arrays, ddim, steps, noise_scale, ddim_K)
         p.apply_apf = arrays.i32(apply_apf)
         p.clip_denoised = int(bool(self.clip_denoised))
@@ -397,7 +405,10 @@ class _GaussianDiffusionBase(nn.Module):
             lib = _lib.load()
 
             def job():
-                if batch is not None:
+                if rows is not None:
+                    _lib.check(lib.ramp_sample_composed(m.ctx(), C.byref(p), C.byref(rows), C.byref(batch), _lib.ptr(noise), _lib.ptr(chain),
+                                                        _lib.ptr(x_out), _lib.current_stream()), "ramp_sample_composed")
+                elif batch is not None:
                     _lib.check(lib.ramp_sample_scenes(m.ctx(), C.byref(p), C.byref(batch), _lib.ptr(noise), _lib.ptr(chain),
                                                       _lib.ptr(x_out), _lib.current_stream()), "ramp_sample_scenes")
                 else:
@@ -421,7 +432,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
-                      noise_std_extra_schedule_fn=None, scene_job=None, **sample_kwargs):
+                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
@@ -444,11 +455,11 @@ class _GaussianDiffusionBase(nn.Module):
             ts = torch.tensor(raw, device=device, dtype=torch.long)
             scales = [float(noise_std_extra_schedule_fn(ts[j])) for j in range(len(raw))]
         # compose: ddpm_sample_fn calls p_mean_variance_compose, which has no APF hook (static.py:188-229)
-        apf = [1 if (self.APF and self._supports_apf and not self.compose and j > self.apf_ddpm['after']) else 0
+        apf = [1 if (self.APF and self._supports_apf and not self.compose and guidance is None and j > self.apf_ddpm['after']) else 0
                for j in range(len(steps))]
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
-                                    cfg, return_chain, scene_job=scene_job)
+                                    cfg, return_chain, scene_job=scene_job, guidance=guidance)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -490,7 +501,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
-                           **sample_kwargs):
+                           guidance=None, **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
         B = shape[0]
@@ -499,7 +510,7 @@ class _GaussianDiffusionBase(nn.Module):
         apf = [1 if (self.APF and self._supports_apf and j >= self.apf_ddim['start']) else 0 for j in range(len(steps))]
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
-                                    return_chain, scene_job=scene_job)
+                                    return_chain, scene_job=scene_job, guidance=guidance)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -549,6 +560,21 @@ class _GaussianDiffusionBase(nn.Module):
             return chain
         return chain[-1]
 
+    def _concat_hard_conds(self, hard_conds, counts):
+        """The scenes' hard-condition dicts as the job's one dict: per waypoint, (B, S) values, a scene's samples adjacent."""
+        dev = self._device()
+        hc = {}
+        for k in hard_conds[0].keys():
+            rows = []
+            for h, n in zip(hard_conds, counts):
+                v = h[k].to(dev, torch.float32)
+                v = v.unsqueeze(0).expand(n, -1) if v.dim() == 1 else v
+                if v.shape[0] != n:
+                    raise ValueError(f"hard condition {k}: {v.shape[0]} rows for a scene of {n} samples")
+                rows.append(v)
+            hc[k] = torch.cat(rows).contiguous()
+        return hc
+
     @torch.no_grad()
     def _prepare_scene_job(self, scenes, hard_conds, n_samples):
         """Encode all scenes in one call (``encode_scenes``), hand latents + row table to the context (``set_scenes``) and build what ``_launch`` needs for
@@ -563,16 +589,7 @@ class _GaussianDiffusionBase(nn.Module):
         tab = build_scene_tables(sizes, n_samples, [list(h.keys()) for h in hard_conds], n_rp=self._n_rp(), compose=self.compose)
         counts = [int(c) for c in tab['counts']]
         B = int(sum(counts))
-        hc = {}
-        for k in hard_conds[0].keys():
-            rows = []
-            for h, n in zip(hard_conds, counts):
-                v = h[k].to(dev, torch.float32)
-                v = v.unsqueeze(0).expand(n, -1) if v.dim() == 1 else v
-                if v.shape[0] != n:
-                    raise ValueError(f"hard condition {k}: {v.shape[0]} rows for a scene of {n} samples")
-                rows.append(v)
-            hc[k] = torch.cat(rows).contiguous()
+        hc = self._concat_hard_conds(hard_conds, counts)
         m.ctx()
         lat = torch.cat([m.encode_scenes([s.to(dev) for s in scenes]), torch.zeros(1, m.context_dim, device=dev)])
         m.set_scenes(lat, tab['row_variant'])
@@ -596,12 +613,92 @@ class _GaussianDiffusionBase(nn.Module):
         trajectory.  A flagged job is repeated exactly as in ``run_inference``.  As in ``run_inference`` the sampler is the model's
         own (``sampler='ddpm'`` -> the fused DDPM job, the DDIM default -> ``ddim_p_sample_loop``; ``conditional_sample`` decides by
         the model's setting, not by its ``ddim`` argument) and ``guide`` / ``n_guide_steps`` / ``t_start_guide`` are accepted and
-        unused.  Not supported: compose, the dynamic planner, a caller-supplied ``sample_fn``."""
+        unused.  Not supported: compose (``run_inference_composed`` is the composed many-scene job), the dynamic planner,
+        a caller-supplied ``sample_fn``."""
         job, hc, B = self._prepare_scene_job(scenes, hard_conds, n_samples)
         for k in ('guide', 'n_guide_steps', 't_start_guide'):
             diffusion_kwargs.pop(k, None)
         _samples, chain = self.conditional_sample(hc, batch_size=B, ddim=False, return_chain=True, obstacle_pts=None, scene_job=job,
                                                   **diffusion_kwargs)
+        chain = chain.permute(1, 0, 2, 3)
+        return (chain if return_chain else chain[-1]), job['traj_scene']
+
+    @torch.no_grad()
+    def _prepare_composed_job(self, scenes, hard_conds, n_samples, weights=None, apf_clouds=None):
+        """Encode all obstacle sets of all scenes in one call (``encode_scenes``), hand latents + row table to the context (``set_scenes``)
+        and build what ``_launch`` needs for a composed job: (scene job dict, guidance dict, concatenated hard conditions, B)."""
+        from .scenes import build_compose_tables
+        dev = self._device()
+        m = self.model
+        sets = []
+        for i, s in enumerate(scenes):
+            one = list(s) if (torch.is_tensor(s) and s.dim() == 4) else ([s] if torch.is_tensor(s) else list(s))
+            for c in one:
+                if not torch.is_tensor(c) or c.dim() != 3:
+                    raise ValueError(f"scene {i}: expected a (K, No, Np, D) tensor or a list of (No, Np, D) tensors")
+            sets.append(one)
+        if weights is None:
+            weights = float(self._default_compose[0])
+        tab = build_compose_tables([len(s) for s in sets], n_samples, [list(h.keys()) for h in hard_conds], weights)
+        counts = [int(c) for c in tab['counts']]
+        B = int(sum(counts))
+        hc = self._concat_hard_conds(hard_conds, counts)
+        use_cloud = bool(self.APF and self._supports_apf)
+        cloud_points, cloud_offset = None, np.arange(len(sets) + 1, dtype=np.int32)
+        if use_cloud:
+            if apf_clouds is not None and len(apf_clouds) != len(sets):
+                raise ValueError(f"apf_clouds has {len(apf_clouds)} entries for {len(sets)} scenes")
+            # the field of scene i: the caller's cloud, or every point of every set of the scene
+            per = [(apf_clouds[i].reshape(-1, 2) if apf_clouds is not None else torch.cat([c.reshape(-1, 2) for c in one]))
+                   .to(dev, torch.float32) for i, one in enumerate(sets)]
+            from .scenes import build_eval_tables
+            cloud_offset = build_eval_tables(counts, cloud_sizes=[int(c.shape[0]) for c in per])['cloud_offset']
+            cloud_points = torch.cat(per).contiguous()
+        m.ctx()
+        lat = torch.cat([m.encode_scenes([c.to(dev) for one in sets for c in one]), torch.zeros(1, m.context_dim, device=dev)])
+        m.set_scenes(lat, tab['row_variant'])
+        job = {'n_scenes': len(sets), 'traj_scene': torch.from_numpy(tab['traj_scene']).to(dev), 'cloud_offset': cloud_offset,
+               'cloud_points': cloud_points}
+        guidance = {'n_rp': int(tab['n_rp']), 'row_weight': torch.from_numpy(tab['row_weight']).to(dev).contiguous()}
+        return job, guidance, hc, B
+
+    @torch.no_grad()
+    def run_inference_composed(self, scenes, hard_conds, n_samples=1, weights=None, apf_clouds=None, return_chain=False,
+                               **diffusion_kwargs):
+        """Compose ANY number of obstacle sets per trajectory, many scenes in ONE job: the reference's p_mean_variance_compose,
+        e = u + sum_k w_k (c_k - u) (diffusion_model_static.py:188-229; diffusion_model_3d.py:163-182, whose three-set form is
+        commented-out code at :165-174), with rows and weights as data.
+
+        scenes      per scene a (K_i, No, Np, D) tensor or a list of K_i (No_k, Np_k, D) tensors: its obstacle sets, 1 <= K_i <= 7
+        hard_conds  one dict per scene, the same waypoint indices in every scene; values (S,) or (n_i, S)
+        n_samples   trajectories per scene: an int, or one count per scene
+        weights     None (every set weighs ``_default_compose[0]``: 2 for the 2-D sampler, 5 for the 3-D one), one number, one list
+                    of max K_i numbers, or one list per scene (``scenes.build_compose_tables``)
+        apf_clouds  per scene the (.., 2) points of its APF field; None: every point of every set of the scene.  The reference's
+                    "six obstacles of A plus four of B" rule is ``_compose_apf_cloud``: a caller who wants it passes it
+
+        Every trajectory gets ``max K_i + 1`` network rows; a scene with fewer sets is padded with zero-weight rows that read the
+        all-zero latent, and pays their compute.  All sets of all scenes are encoded in one ``encode_scenes`` call, one
+        ``set_scenes`` call follows and ONE job (``ramp_sample_composed``) runs.  The sampler is the model's own, as in
+        ``run_inference_scenes``: on the fused DDPM job no APF hook fires (the reference's compose path has none); the DDIM loop
+        (``ddim_num_inference_steps`` as the constructor set it) applies the three-pass APF to x0 from ``apf_ddim['start']`` against
+        each trajectory's own scene cloud when the wrapper was built with ``use_apf``.  The wrapper's ``compose`` flag plays no part.
+        Returns ``(result, traj_scene)`` like ``run_inference_scenes``.  Refused with a message: a caller-supplied ``sample_fn``, the
+        dynamic planner, a multi-rank process group."""
+        import torch.distributed as tdist
+        if not self._scenes_supported:
+            raise NotImplementedError(f"run_inference_composed: {type(self).__name__} has no composed job (composition in the dynamic "
+                                      "planner is out of scope)")
+        if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+            raise NotImplementedError("run_inference_composed under a multi-rank process group: sharding a composed job is out of scope")
+        if not self._is_fused_ddpm_step(diffusion_kwargs.get('sample_fn')):
+            raise NotImplementedError("run_inference_composed runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
+                                      "scene's batch at a time")
+        job, guidance, hc, B = self._prepare_composed_job(scenes, hard_conds, n_samples, weights, apf_clouds)
+        for k in ('guide', 'n_guide_steps', 't_start_guide'):
+            diffusion_kwargs.pop(k, None)
+        _samples, chain = self.conditional_sample(hc, batch_size=B, ddim=False, return_chain=True, obstacle_pts=None, scene_job=job,
+                                                  guidance=guidance, **diffusion_kwargs)
         chain = chain.permute(1, 0, 2, 3)
         return (chain if return_chain else chain[-1]), job['traj_scene']
 

@@ -7,6 +7,8 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 
+from ._lib import MAX_ROWS_PER_TRAJ      # RAMP_MAX_ROWS_PER_TRAJ (include/ramp_hip.h); the binding module imports no device code until load()
+
 
 def build_scene_tables(cloud_sizes: Sequence[int], n_samples: Union[int, Sequence[int]],
                        hard_keys: Sequence[Sequence[int]], n_rp: int = 2, compose: bool = False) -> Dict[str, np.ndarray]:
@@ -62,6 +64,114 @@ def build_scene_tables(cloud_sizes: Sequence[int], n_samples: Union[int, Sequenc
     first[1:] = np.cumsum(counts)[:-1]
     return {"traj_scene": traj_scene, "row_variant": row_variant, "cloud_offset": cloud_offset.astype(np.int32),
             "counts": np.asarray(counts, dtype=np.int32), "first": first.astype(np.int32)}
+
+
+
+
+def _set_weights(weights, set_counts: Sequence[int]) -> List[List[float]]:
+    """The per-scene, per-set guidance weights of ``build_compose_tables`` as doubles."""
+    n_scenes, k_max = len(set_counts), max(set_counts)
+    if weights is None:
+        return [[1.0] * k for k in set_counts]
+    if isinstance(weights, (int, float, np.integer, np.floating)):
+        return [[float(weights)] * k for k in set_counts]
+    ws = list(weights)
+    if ws and all(isinstance(w, (int, float, np.integer, np.floating)) for w in ws):
+        if len(ws) != k_max:
+            raise ValueError(f"weights has {len(ws)} entries; a flat list holds one weight per set, {k_max} (the largest set count) -- "
+                             "or give one list per scene")
+        return [[float(w) for w in ws[:k]] for k in set_counts]
+    if len(ws) != n_scenes:
+        raise ValueError(f"weights has {len(ws)} lists for {n_scenes} scenes")
+    out = []
+    for i, (w, k) in enumerate(zip(ws, set_counts)):
+        w = [float(v) for v in np.asarray(w, dtype=np.float64).reshape(-1)]
+        if len(w) != k:
+            raise ValueError(f"scene {i}: {len(w)} weights for {k} obstacle sets")
+        out.append(w)
+    return out
+
+
+def build_compose_tables(set_counts: Sequence[int], n_samples: Union[int, Sequence[int]], hard_keys: Sequence[Sequence[int]],
+                         weights=None) -> Dict[str, np.ndarray]:
+    """Tables of one COMPOSED job (``run_inference_composed`` -> ``ramp_set_scenes`` + ``ramp_sample_composed``): every scene is a
+    composition of ``K_i`` obstacle sets, e = u + sum_k w_k (c_k - u) (the reference's p_mean_variance_compose,
+    diffusion_model_static.py:188-229 and diffusion_model_3d.py:163-182, for any number of sets), and many scenes share the job.
+
+    set_counts   obstacle sets of each scene, ``K_i >= 1``; every trajectory gets ``n_rp = max K_i + 1 <= 8`` network rows
+    n_samples    trajectories per scene: one int for all, or one count per scene
+    hard_keys    per scene, the waypoint indices of its hard-condition dict: the same in every scene, in the same order
+    weights      None (every set weighs 1), one number for every set, one list of ``max K_i`` numbers (set k of every scene gets
+                 entry k) or one list per scene of ``K_i`` numbers
+
+    The latents are expected in job order -- all sets of scene 0, all sets of scene 1, ... -- followed by ONE all-zero row at index
+    ``sum K_i``.  Row ``b * n_rp + k`` of trajectory b (scene i) reads set k of its scene for ``k < K_i``; row ``b * n_rp + n_rp - 1``
+    is the unconditional row; the rows in between are PADDING: they read the zero latent and weigh 0.  Padding is how scenes with
+    different set counts share a job, and its cost is those rows' compute: a scene with K sets in a job of n_rp rows per trajectory
+    pays for ``n_rp - 1 - K`` rows whose result is discarded.
+    Weight of set k: ``float32(w_k)``; of the unconditional row: ``float32(1 - w_0 - w_1 - ...)`` with the difference taken in double,
+    left to right -- the rule of the engine's two-set job, so two sets with (w1, w2) get exactly that job's weights, and one set with
+    ``1 + w`` the weights of classifier-free guidance at w.
+
+    Returns ``traj_scene`` (B) int32, ``row_variant`` (B * n_rp) int32, ``row_weight`` (B, n_rp) float32, ``counts`` (n_scenes) int32,
+    ``first`` (n_scenes) int32 first trajectory of each scene, ``set_first`` (n_scenes + 1) int32 first latent of each scene, and
+    ``n_rp`` (int)."""
+    n_scenes = len(set_counts)
+    if n_scenes == 0:
+        raise ValueError("no scenes given")
+    ks = [int(k) for k in set_counts]
+    for i, k in enumerate(ks):
+        if k < 1:
+            raise ValueError(f"scene {i} has {k} obstacle sets; every scene needs at least one")
+    n_rp = max(ks) + 1
+    if n_rp > MAX_ROWS_PER_TRAJ:
+        raise ValueError(f"a scene has {max(ks)} obstacle sets: {n_rp} network rows per trajectory, the engine takes at most {MAX_ROWS_PER_TRAJ} "
+                         f"({MAX_ROWS_PER_TRAJ - 1} sets)")
+    if isinstance(n_samples, (int, np.integer)):
+        counts = [int(n_samples)] * n_scenes
+    else:
+        counts = [int(c) for c in n_samples]
+        if len(counts) != n_scenes:
+            raise ValueError(f"n_samples has {len(counts)} entries for {n_scenes} scenes")
+    for i, c in enumerate(counts):
+        if c <= 0:
+            raise ValueError(f"scene {i} asks for {c} samples; every scene needs at least one")
+    if len(hard_keys) != n_scenes:
+        raise ValueError(f"hard_conds has {len(hard_keys)} entries for {n_scenes} scenes")
+    k0 = [int(k) for k in hard_keys[0]]
+    for i, hk in enumerate(hard_keys):
+        if [int(k) for k in hk] != k0:
+            raise ValueError(f"scene {i} conditions waypoints {list(hk)}, scene 0 {k0}: every scene of a job must condition "
+                             "the same waypoints in the same order")
+    ws = _set_weights(weights, ks)
+    for i, w in enumerate(ws):
+        with np.errstate(over="ignore"):
+            finite = np.isfinite(np.asarray(w, dtype=np.float64)).all() and np.isfinite(np.asarray(w, dtype=np.float64).astype(np.float32)).all()
+        if not finite:
+            raise ValueError(f"scene {i}: weights must be finite, got {w}")
+    B = int(sum(counts))
+    if B * n_rp >= 2 ** 24:
+        raise ValueError("the job's network rows exceed the engine's row table (2^24)")
+    set_first = np.zeros(n_scenes + 1, dtype=np.int64)
+    np.cumsum(ks, out=set_first[1:])
+    zero = int(set_first[-1])
+    traj_scene = np.repeat(np.arange(n_scenes, dtype=np.int32), counts)
+    variant = np.full((n_scenes, n_rp), zero, dtype=np.int32)
+    weight = np.zeros((n_scenes, n_rp), dtype=np.float32)
+    for i, (k, w) in enumerate(zip(ks, ws)):
+        variant[i, :k] = set_first[i] + np.arange(k)
+        weight[i, :k] = np.asarray(w, dtype=np.float64).astype(np.float32)      # (finite: checked above)
+        u = 1.0
+        for v in w:
+            u -= v
+        weight[i, n_rp - 1] = np.float32(u)
+    if not np.isfinite(weight).all():
+        raise ValueError("weights must be finite: the unconditional row's weight 1 - sum_k w_k leaves the float32 range")
+    first = np.zeros(n_scenes, dtype=np.int64)
+    first[1:] = np.cumsum(counts)[:-1]
+    return {"traj_scene": traj_scene, "row_variant": np.ascontiguousarray(variant[traj_scene].reshape(-1)),
+            "row_weight": np.ascontiguousarray(weight[traj_scene]), "counts": np.asarray(counts, dtype=np.int32),
+            "first": first.astype(np.int32), "set_first": set_first.astype(np.int32), "n_rp": n_rp}
 
 
 def scene_slices(counts: Sequence[int]) -> List[slice]:
