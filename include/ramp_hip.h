@@ -165,6 +165,14 @@ int ramp_score(ramp_ctx* ctx, const float* x, int32_t B, int32_t n_rp, int32_t t
  * The samplers (ramp_sample*, ramp_replan) keep the uniform path. */
 int ramp_score_rows(ramp_ctx* ctx, const float* x, int32_t B, int32_t n_rp, const int32_t* t_rows_host,
                     float* f_out, float* eps_out, void* stream);
+/* ramp_score plus the energies of the evaluation: the score is an energy gradient, eps = grad_x 1/2 ||f(x, t, scene)||^2 (EnergyGradFunction
+ * returns that energy as its second value, UnetInference.py:26-32), and energy_out[r] = 1/2 sum_{h,s} f[r,h,s]^2 for every network row r --
+ * device double (B * n_rp).  fp32 squares, fp64 sum in a fixed order (one wave per row: lane l takes elements l, l + 64, ..., then a fixed
+ * butterfly), so an energy has the same bits from run to run and however max_rows chunks the batch.  f_out and eps_out (either may be
+ * NULL) have the bits ramp_score gives them; everything else -- arithmetic modes, kept calibration, range guard and its repeat -- is
+ * ramp_score's. */
+int ramp_score_energy(ramp_ctx* ctx, const float* x, int32_t B, int32_t n_rp, int32_t t, float* f_out, float* eps_out,
+                      double* energy_out, void* stream);
 /* arithmetic the last ramp_score / ramp_score_rows call's result was computed in: 0 exact fp32, 1 bf16x6, 2 fp16x3 */
 int ramp_score_mode(ramp_ctx* ctx, int32_t* mode);
 
@@ -267,6 +275,48 @@ typedef struct ramp_guidance_rows {
 } ramp_guidance_rows;
 int ramp_sample_composed(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_guidance_rows* g, const ramp_scene_batch* scenes,
                          const float* noise, float* chain_out, float* x_out, void* stream);
+/* ---- Langevin refinement inside the sampling job (ULA / MALA) ----
+ * Composed reverse diffusion with summed scores is biased; a few MCMC steps per noise level, Metropolis-corrected where the model exposes
+ * an energy, remove the bias (Du et al., "Reduce, Reuse, Recycle", ICML 2023).  With sigma_t = sqrt(1 - alphas_cumprod[t]), step size eta,
+ * a = eta / sigma_t, c = sqrt(2 eta), eps the guidance-combined gradient and E the guidance-combined energy (sum_j w_j E_row_j with the
+ * weights that form eps, fp64), iteration j of the job evaluates eps(x, t_j) (and E, MALA) as ever, then runs n_inner[j] inner steps:
+ *   propose   x' = x - a eps(x) + c z on free waypoints, x' = x on the waypoints the hard conditions pin           (fp32)
+ *   evaluate  eps' = eps(x', t_j), E' = E(x', t_j): ONE evaluation, a link of the job's calibration chain like any other
+ *   accept    ULA: always.  MALA: log alpha = -(E' - E) / sigma_t - (||x - x' + a eps'||^2 - ||x' - x + a eps||^2) / (4 eta), fp64 over the
+ *             free elements, a the proposal's own fp32 value; accepted when log u < log alpha and E', log alpha are finite.  An accepted
+ *             trajectory's x, cached eps and cached E become the proposal's.
+ * The reverse step (guidance step, APF hook, DDPM / DDIM update, hard conditioning) then uses the CACHED eps of the state the inner steps
+ * ended on: a job runs n_steps + sum n_inner evaluations.  ULA requests no energies.  The range guard logs every evaluation (ramp_range_trip
+ * counts inner ones too) and a flagged job is repeated as ever.
+ *
+ * kind: 0 off (the call IS ramp_sample / ramp_sample_scenes / ramp_sample_composed, bit for bit), 1 ULA, 2 MALA.  n_inner, step_size, sigma:
+ * HOST arrays of n_steps entries; sigma[j] = sqrt_one_minus_alphas_cumprod[t[j]] (ramp_sample_params carries no such table for the DDPM loop,
+ * and the library never derives schedule values itself: the caller hands them over like every other per-iteration array).  g (NULL = p's CFG / compose scalars) and scenes (NULL = one
+ * scene) as in ramp_sample_composed / ramp_sample_scenes.
+ * noise_mode 0: mcmc_noise device (sum n_inner, B, H, S) normals and mcmc_u device (sum n_inner, B) uniforms in (0, 1), inner steps in job
+ * order; ULA ignores mcmc_u.  noise_mode 1: both come from the job's Philox stream (seed, offset), BEHIND the main block: with K = sum
+ * n_inner, T = philox_total (or B), g = sample0 + b the global sample and blocks of T * H * S elements,
+ *   main block      blocks 0 .. n_steps (DDIM draws block 0 only, as ever)
+ *   normal of (inner step k, sample g, element e)   = element ((n_steps + 1 + k) T + g) H S + e of the stream
+ *   uniform of (inner step k, sample g)             = ((r >> 9) + 0.5) 2^-23, r = output 0 of group (n_steps + 1 + K) T H S / 4 + k T + g
+ * (groups of four elements, counted from philox_offset), so a shard draws what the whole job draws for its samples.
+ * accept_out: device int32 (sum n_inner, B), 1 = accepted, or NULL.  The captured graph is keyed on the job's shape, kind, n_inner and the
+ * step sizes (kernel arguments): a job with other step sizes is captured anew, never replayed from a stale graph; composed weights stay data.
+ * Refused on the host before any launch (non-zero, "ramp_sample_mcmc" in ramp_last_error): kind outside 0 .. 2; with kind != 0,
+ * p->predict_x0 != 0 (the combined output is then no score: no density to correct), n_inner outside 0 .. RAMP_MCMC_MAX_INNER, a non-positive or
+ * non-finite step_size / sigma where n_inner > 0, NULL mcmc_noise / mcmc_u where noise_mode 0 needs them; g->n_rp != p->n_rp and the other
+ * guidance-table checks of ramp_sample_composed. */
+#define RAMP_MCMC_MAX_INNER 16
+typedef struct ramp_mcmc_params {
+  int32_t kind;               /* 0 off, 1 ULA, 2 MALA                                        */
+  int32_t reserved;
+  const int32_t* n_inner;     /* host (n_steps): inner steps after iteration j's evaluation  */
+  const float* step_size;     /* host (n_steps): eta, > 0 wherever n_inner > 0               */
+  const float* sigma;         /* host (n_steps): sqrt(1 - alphas_cumprod[t[j]])              */
+} ramp_mcmc_params;
+int ramp_sample_mcmc(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_mcmc_params* m, const ramp_guidance_rows* g,
+                     const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise, const float* mcmc_u,
+                     float* chain_out, float* x_out, int32_t* accept_out, void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from
@@ -489,6 +539,23 @@ int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32
 int ramp_cfg_mean_rows(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, const float* row_weight,
                        float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, int32_t clip, int32_t predict_x0,
                        float* x0_out, float* mean_out, float* ecomb_out, void* stream);
+/* the kernels of ramp_score_energy / ramp_sample_mcmc one at a time (all pointers device unless said otherwise):
+ * ramp_row_energy: energy_out[r] = 1/2 sum_e f[r, e]^2, f (R, HS).
+ * ramp_combine_energy: energy_out[b] = sum_j w_j energy_rows[b n_rp + j] in fp64, j ascending; w = weights_host (HOST, n_rp <= 3 floats) or
+ * line b of row_weight (device (B, n_rp)) -- exactly one of the two.
+ * ramp_mcmc_propose: x_prop = (x - a eps) + c z (fp32: two products, a difference, a sum) on free waypoints, x on the n_pinned waypoints
+ * pinned_idx (device int32) lists.
+ * ramp_mcmc_accept: kind 1 accepts always; kind 2 forms log alpha as documented at ramp_sample_mcmc from (x, x_prop, eps, eps_prop, energy,
+ * energy_prop, a, sigma, eta), writes it to log_alpha_out (optional) and accepts where log u < log alpha and energy_prop, log alpha are
+ * finite.  Accepted trajectories: x <- x_prop, eps <- eps_prop, energy <- energy_prop.  accept_out int32 (B). */
+int ramp_row_energy(const float* f, int32_t R, int32_t HS, double* energy_out, void* stream);
+int ramp_combine_energy(const double* energy_rows, int32_t B, int32_t n_rp, const float* weights_host, const float* row_weight,
+                        double* energy_out, void* stream);
+int ramp_mcmc_propose(const float* x, const float* eps, const float* z, float a, float c, const int32_t* pinned_idx, int32_t n_pinned,
+                      float* x_prop, int32_t B, int32_t H, int32_t S, void* stream);
+int ramp_mcmc_accept(float* x, const float* x_prop, float* eps, const float* eps_prop, double* energy, const double* energy_prop,
+                     const float* u, int32_t kind, float a, double sigma, double eta, const int32_t* pinned_idx, int32_t n_pinned,
+                     int32_t* accept_out, double* log_alpha_out, int32_t B, int32_t H, int32_t S, void* stream);
 /* the DDIM update of ddim_p_sample given x0 (diffusion_model_static.py:321-333 / _dynamic.py:436-447), eta = 0:
  * x_out = sqrt_a_prev * x0 + dir_coef * (x - sqrt_a_t * x0) / sqrt_1m_a_t */
 int ramp_ddim_finish(const float* x, const float* x0, float sqrt_a_t, float sqrt_1m_a_t, float sqrt_a_prev,

@@ -47,6 +47,13 @@ class RampGuidanceRows(C.Structure):
 
 
 MAX_ROWS_PER_TRAJ = 8       # RAMP_MAX_ROWS_PER_TRAJ
+MCMC_MAX_INNER = 16         # RAMP_MCMC_MAX_INNER
+MCMC_KINDS = {'ula': 1, 'mala': 2}
+
+
+class RampMcmcParams(C.Structure):
+    """ramp_mcmc_params: the Langevin refinement of a sampling job (ramp_sample_mcmc)."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("n_inner", c_i32p), ("step_size", c_f32p), ("sigma", c_f32p)]
 
 
 class RampSampleParams(C.Structure):
@@ -138,6 +145,14 @@ PROTOTYPES = {
                                      C.c_void_p, C.c_void_p]),
     "ramp_sample_composed": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch),
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_sample_mcmc": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampMcmcParams), C.POINTER(RampGuidanceRows),
+                                   C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
+    "ramp_score_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "ramp_row_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ramp_combine_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_mcmc_propose": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p]),
+    "ramp_mcmc_accept": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_int32, C.c_void_p,
+                                                       C.c_void_p] + [C.c_int32] * 3 + [C.c_void_p]),
     "ramp_philox_normal": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p]),
     "ramp_replan": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampReplanState), C.c_void_p, C.c_void_p,
                               C.c_void_p, C.POINTER(RampReplanResult), C.c_void_p]),

@@ -38,7 +38,38 @@ int launch_philox_normal(float* out, long n, const unsigned long long* rec, hipS
 // the same stream addressed by GLOBAL sample index: out is this shard's (n_blocks, B, HS) noise block of a job whose whole
 // noise block is (n_blocks, B_total, HS); local sample b is global sample sample0 + b, i.e. out[(j B + b) HS + e] = element
 // (j B_total + sample0 + b) HS + e of the stream (HS % 4 == 0).  B_total == B, sample0 == 0 is launch_philox_normal.
-int launch_philox_normal_sharded(float* out, int n_blocks, int B, int HS, long sample0, long B_total, const unsigned long long* rec, hipStream_t s);
+// block0 > 0: the launch's block j is block block0 + j of the job's stream (the MCMC draws behind a job's main block)
+int launch_philox_normal_sharded(float* out, int n_blocks, int B, int HS, long sample0, long B_total, const unsigned long long* rec, hipStream_t s,
+                                 long block0 = 0);
+// out (n_blocks, B) uniforms in (0, 1): out[k B + b] = ((r >> 9) + 0.5) 2^-23 with r = output 0 of the stream's group
+// group0 + k B_total + sample0 + b (one group of four per uniform)
+int launch_philox_uniform_sharded(float* out, int n_blocks, int B, long group0, long sample0, long B_total, const unsigned long long* rec,
+                                  hipStream_t s);
+
+// ---- energies and Langevin refinement (sampler.hip) ------------------------------------------------
+// E[r] = 1/2 sum_e f[r, e]^2 for the R rows of f (R, HS): fp32 squares, fp64 sum in a fixed order, one wave per row
+int launch_row_energy(const float* f, double* E, int R, int HS, hipStream_t s);
+// the weights of the rows' energies in a trajectory's combined energy: the job's host scalars (comb_weights; n_rp <= 3) or, rw != nullptr,
+// the lines of the device (B, n_rp) table of a composed job
+struct EnergyWeights { float w[3] = {0.f, 0.f, 0.f}; const float* rw = nullptr; };
+// E_comb[b] = sum_j w_j E_rows[b n_rp + j] (fp64, j ascending)
+int launch_combine_energy(const double* E_rows, const EnergyWeights& w, double* E_comb, int B, int n_rp, hipStream_t s);
+// x' = x - a eps + cz z on free waypoints, x' = x on the waypoints hc lists (only hc.idx / hc.n are read)
+int launch_mcmc_propose(const float* x, const float* eps, const float* z, float a, float cz, HardConds hc, float* xp, int B, int H, int S,
+                        hipStream_t s);
+struct McmcAcceptArgs {
+  float* x = nullptr; const float* xp = nullptr;       // (B,H,S) state (overwritten where accepted) and proposal
+  float* eps = nullptr; const float* eps_p = nullptr;  // (B,H,S) cached combined gradient at x (overwritten where accepted) / at x'
+  double* E = nullptr; const double* E_p = nullptr;    // (B) cached combined energy at x (overwritten where accepted) / at x'; MALA only
+  const float* u = nullptr;                            // (B) uniforms in (0, 1); MALA only
+  int* flag = nullptr;                                 // (B) 1 = accepted
+  double* log_alpha = nullptr;                         // optional (B): MALA's log acceptance ratio
+  HardConds hc;                                        // pinned waypoints (idx / n)
+  int B = 0, H = 0, S = 0, mala = 0;
+  float a = 0;                                         // eta / sigma_t, the proposal's own fp32 value
+  double inv_sigma = 0, inv_4eta = 0;                  // 1 / sigma_t, 1 / (4 eta)
+};
+int launch_mcmc_accept(const McmcAcceptArgs& a, hipStream_t s);
 
 struct ApfArgs {
   float* traj = nullptr;        // (B,H,S) modified in place (xy channels only)

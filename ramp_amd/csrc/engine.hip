@@ -133,6 +133,18 @@ struct ramp_ctx {
   // weights are data of a replay); g_weight_cur is non-null only while that job's evaluations are being launched or captured -- the
   // shared-prefix backward and the guidance step then take a trajectory's weights from its line instead of the host scalars
   float* g_weight = nullptr; size_t g_weight_cap = 0; const float* g_weight_cur = nullptr;
+  // energies E = 1/2 ||f||^2 of an evaluation (ramp_score_energy, the MALA steps of ramp_sample_mcmc): e_rows_cur is non-null only while such
+  // an evaluation is being launched or captured -- score_all then adds the energy of every row of a chunk to e_rows_cur[row] (the chunk's f
+  // goes to the caller's f_out, or to m_f).  Nothing of this is allocated or launched by a job that asks for no energy.
+  double* e_rows_cur = nullptr;
+  float* m_f = nullptr; size_t m_f_cap = 0;                  // f of all rows (rows, H, S) where the caller gives no f_out
+  double* m_Erows = nullptr; size_t m_Erows_cap = 0;         // per-row energies (rows)
+  // Langevin refinement inside a sampling job (ramp_sample_mcmc): proposal, cached combined gradient at the state and at the proposal, their
+  // combined energies (MALA), the inner steps' normals (sum K, B, H, S), uniforms (sum K, B) and accept flags (sum K, B).  The step sizes
+  // are kernel arguments, hence part of the graph key: a job with other step sizes is captured anew
+  float *m_xp = nullptr, *m_eps = nullptr, *m_eps_p = nullptr; size_t m_cap_B = 0;
+  double *m_E = nullptr, *m_Ep = nullptr; size_t m_E_cap = 0;
+  float *m_noise = nullptr, *m_u = nullptr; int* m_flag = nullptr; size_t m_noise_cap = 0, m_u_cap = 0;
   // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
   // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
   hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
@@ -1285,8 +1297,11 @@ int score_all(ramp_ctx* c, const float* x, int B, int n_rp, int t, float* f_out,
     float* fo = f_out ? f_out + (size_t)row0 * H * S : nullptr;
     c->site = 0;                                       // every chunk walks the same GEMM call sites
     const int share = (comb && n_rp > 1 && c->share_prefix) ? n_rp : 1;
-    RAMP_REQUIRE(!comb || (eps_out && !f_out), "combined evaluation: gradient only");
+    // (a combined evaluation hands out f only as the scratch its rows' energies are taken from)
+    RAMP_REQUIRE(!comb || (eps_out && (!f_out || c->e_rows_cur)), "combined evaluation: gradient (and energies) only");
+    RAMP_REQUIRE(!c->e_rows_cur || f_out, "energies need f of every row");
     CK(net_forward(c, x + (size_t)b0 * H * S, row0, R, n_rp, t, fo, eps_out != nullptr, s, share));
+    if (c->e_rows_cur) LAUNCH(c, s, CAT_SAMPLER, 0, launch_row_energy(fo, c->e_rows_cur + row0, R, H * S, s));
     if (eps_out && share > 1) CK(net_backward(c, row0, R, eps_out + (size_t)b0 * H * S, s, share, comb));
     else if (eps_out) CK(net_backward(c, row0, R, eps_out + (size_t)row0 * H * S, s));
   }
@@ -1910,6 +1925,24 @@ int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, 
   return 0;
 }
 
+// ramp_score plus the rows' energies: the same evaluation (arithmetic modes, kept calibration, range guard and its repeat, chunking -- a
+// repeated evaluation overwrites its energies too), with score_all taking each chunk's energies from the chunk's f
+int ramp_score_energy(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, float* f_out, float* eps_out, double* energy_out,
+                      void* stream) {
+  RAMP_REQUIRE(c && x && energy_out, "ramp_score_energy: null argument");
+  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= RAMP_MAX_ROWS_PER_TRAJ && (long)B * n_rp <= (1l << 24), "ramp_score_energy: bad batch");
+  float* f = f_out;
+  if (!f) {
+    CK(grow(c, c->m_f, c->m_f_cap, (size_t)B * n_rp * c->cfg.horizon * c->cfg.state_dim));
+    staging_done(c);
+    f = c->m_f;
+  }
+  c->e_rows_cur = energy_out;
+  const int rc = ramp_score(c, x, B, n_rp, t, f, eps_out, stream);
+  c->e_rows_cur = nullptr;
+  return rc;
+}
+
 int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const int32_t* t_rows_host, float* f_out, float* eps_out,
                     void* stream) {
   RAMP_REQUIRE(c && x && t_rows_host, "null argument");
@@ -1934,7 +1967,13 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 
 // sc != nullptr: a job of many scenes (ramp_sample_scenes) -- the APF of trajectory b runs against the cloud of scene traj_scene[b]
 // c->g_weight_cur != nullptr: a composed job (ramp_sample_composed) -- the rows' weights in e_comb come from that device table
-static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1) {
+// The Langevin refinement of a job (ramp_sample_mcmc), checked by the entry: kind 1 ULA / 2 MALA, total = sum of n_inner > 0
+struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
+
+// mj != nullptr: K_j = mj->n_inner[j] inner steps (propose -> one evaluation at x' -> accept) follow the evaluation of iteration j, and the reverse
+// step uses the cached combined gradient of the state they ended on; every evaluation, inner ones included, is one link of the calibration chain
+static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1,
+                       const McmcJob* mj = nullptr) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -1942,6 +1981,16 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   if (p->noise_mode == 1)
     LAUNCH(c, s, CAT_SAMPLER, 0, launch_philox_normal_sharded(c->s_noise, p->ddim ? 1 : p->n_steps + 1, B, (int)HS, (long)p->philox_sample0,
                                                               p->philox_total > 0 ? (long)p->philox_total : (long)B, c->s_philox, s));
+  const int n_evals = p->n_steps + (mj ? mj->total : 0);
+  const bool mala = mj && mj->kind == 2;
+  if (mj && p->noise_mode == 1) {      // the inner steps' draws: behind the main block, see ramp_sample_mcmc in ramp_hip.h
+    const long total = p->philox_total > 0 ? (long)p->philox_total : (long)B;
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_philox_normal_sharded(c->m_noise, mj->total, B, (int)HS, (long)p->philox_sample0, total, c->s_philox, s,
+                                                              (long)p->n_steps + 1));
+    if (mala)
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_philox_uniform_sharded(c->m_u, mj->total, B, ((long)p->n_steps + 1 + mj->total) * total * (long)(HS / 4),
+                                                                 (long)p->philox_sample0, total, c->s_philox, s));
+  }
   // x_T = noise[0]; apply_hard_conditioning; chain[0]
   RAMP_HIP_CHECK(hipMemcpyAsync(c->s_x, c->s_noise, n * 4, hipMemcpyDeviceToDevice, s));
   LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x, hc, B, H, S, s));
@@ -1952,31 +2001,72 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   if (sc_apf) { ap.scene = c->s_traj_scene; ap.scene_off = c->s_scene_off; ap.n_scenes = sc->n_scenes; ap.P = 0; }
   if (c->gemm_mode == 2) {
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
-    if (!c->force_x6) hipLaunchKernelGGL(zero_words_kernel, dim3((p->n_steps + 255) / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->trip_log), p->n_steps);
+    if (!c->force_x6) hipLaunchKernelGGL(zero_words_kernel, dim3((n_evals + 255) / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->trip_log), n_evals);
     RAMP_HIP_CHECK(hipGetLastError());
   }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   // (a composed job: comb below only says "combined evaluation", see score_all; its weights are c->g_weight_cur's)
   const std::array<float, 3> comb = c->g_weight_cur ? std::array<float, 3>{0.f, 0.f, 0.f} : comb_weights(p->n_rp, p->w0, p->w1);
   const bool shared = p->n_rp > 1 && c->share_prefix;
+  int ev = 0, kk = 0;      // evaluations / inner steps so far
+  // One evaluation of the job, link `ev` of its calibration chain (a plain job: ev == j).
+  // fp16x3: evaluation 0 runs scaled from the context's CANONICAL maxima (canonical_calibration below) -- or, with
+  // ramp_set_calibration_reuse(ctx, 0), calibrates itself (bf16x6 + recorded operand maxima); evaluation e >= 1 runs fp16x3
+  // scaled from e - 1
+  // (e == cal_eval, cal_eval + 1: the evaluation the range guard flagged first in this job's previous run calibrates instead -- see
+  // ramp_ctx::trip_log -- and so does its successor: an excursion that is gone one step later (a spike) would otherwise trip the guard
+  // again from the other side, its successor being scaled from the spike's maxima; 3 % of a job per calibrating evaluation)
+  auto eval_at = [&](const float* x, int t, float* f_out, float* eps_out) -> int {
+    const int e = ev++;
+    const int phase = !h3 ? 0 : ((e == 0 && !steady) || e == cal_eval || (cal_eval >= 0 && e == cal_eval + 1)) ? 1 : 2;
+    const int t_out = (e & 1) ? TABLE_ODD : TABLE_EVEN, t_in = e == 0 ? TABLE_CANONICAL : (e & 1) ? TABLE_EVEN : TABLE_ODD;
+    return guarded_eval(c, phase, t_in, t_out, x, B, p->n_rp, t, f_out, eps_out, s, shared ? comb.data() : nullptr, h3 ? c->trip_log : nullptr, e);
+  };
+  // The evaluation of a job with inner steps: the combined gradient of x into eps_comb (B, H, S) and, E != nullptr, the combined energy into E (B)
+  auto eval_comb = [&](const float* x, int t, float* eps_comb, double* E) -> int {
+    c->e_rows_cur = E ? c->m_Erows : nullptr;
+    const int rc = eval_at(x, t, E ? c->m_f : nullptr, shared ? eps_comb : c->s_eps);
+    c->e_rows_cur = nullptr;
+    CK(rc);
+    if (!shared) {      // the rows' gradients are still apart: the guidance step's own combination, nothing else of it
+      CfgMeanArgs m; m.x = x; m.eps = c->s_eps; m.B = B; m.HS = (int)HS; m.n_rp = p->n_rp; m.ecomb = eps_comb;
+      m.w0 = (float)p->w0; m.w1 = (float)p->w1; m.w0p1 = (float)(1.0 + p->w0);
+      LAUNCH(c, s, CAT_SAMPLER, 0, c->g_weight_cur ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
+    }
+    if (E) {
+      EnergyWeights w; w.rw = c->g_weight_cur;
+      if (p->n_rp == 1) w.w[0] = 1.f; else for (int q = 0; q < 3; ++q) w.w[q] = comb[q];
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_combine_energy(c->m_Erows, w, E, B, p->n_rp, s));
+    }
+    return 0;
+  };
   for (int j = 0; j < p->n_steps; ++j) {
-    // fp16x3: evaluation 0 runs scaled from the context's CANONICAL maxima (canonical_calibration below) -- or, with
-    // ramp_set_calibration_reuse(ctx, 0), calibrates itself (bf16x6 + recorded operand maxima); evaluation j >= 1 runs fp16x3
-    // scaled from j - 1
-    // (j == cal_eval, cal_eval + 1: the evaluation the range guard flagged first in this job's previous run calibrates instead -- see
-    // ramp_ctx::trip_log -- and so does its successor: an excursion that is gone one step later (a spike) would otherwise trip the guard
-    // again from the other side, its successor being scaled from the spike's maxima; 3 % of a job per calibrating evaluation)
-    const int phase = !h3 ? 0 : ((j == 0 && !steady) || j == cal_eval || (cal_eval >= 0 && j == cal_eval + 1)) ? 1 : 2;
-    const int t_out = (j & 1) ? TABLE_ODD : TABLE_EVEN, t_in = j == 0 ? TABLE_CANONICAL : (j & 1) ? TABLE_EVEN : TABLE_ODD;
-    CK(guarded_eval(c, phase, t_in, t_out, c->s_x, B, p->n_rp, p->t[j], nullptr, c->s_eps, s, shared ? comb.data() : nullptr,
-                    h3 ? c->trip_log : nullptr, j));
-    CfgMeanArgs m; m.x = c->s_x; m.eps = c->s_eps; m.B = B; m.HS = (int)HS; m.n_rp = shared ? 1 : p->n_rp;
+    if (!mj) {
+      CK(eval_at(c->s_x, p->t[j], nullptr, c->s_eps));
+    } else {
+      const int K = mj->n_inner[j];
+      const bool wantE = mala && K > 0;
+      CK(eval_comb(c->s_x, p->t[j], c->m_eps, wantE ? c->m_E : nullptr));
+      const double eta = (double)mj->step_size[j], sig = (double)mj->sigma[j];
+      const float a = (float)(eta / sig), cz = (float)std::sqrt(2.0 * eta);
+      for (int k = 0; k < K; ++k, ++kk) {
+        LAUNCH(c, s, CAT_SAMPLER, 0, launch_mcmc_propose(c->s_x, c->m_eps, c->m_noise + (size_t)kk * n, a, cz, hc, c->m_xp, B, H, S, s));
+        CK(eval_comb(c->m_xp, p->t[j], c->m_eps_p, wantE ? c->m_Ep : nullptr));
+        McmcAcceptArgs ac; ac.x = c->s_x; ac.xp = c->m_xp; ac.eps = c->m_eps; ac.eps_p = c->m_eps_p; ac.E = c->m_E; ac.E_p = c->m_Ep;
+        ac.u = c->m_u + (size_t)kk * B; ac.flag = c->m_flag + (size_t)kk * B; ac.hc = hc; ac.B = B; ac.H = H; ac.S = S; ac.mala = mala; ac.a = a;
+        ac.inv_sigma = 1.0 / sig; ac.inv_4eta = 1.0 / (4.0 * eta);
+        LAUNCH(c, s, CAT_SAMPLER, 0, launch_mcmc_accept(ac, s));
+      }
+    }
+    // (with inner steps the gradient is the cached COMBINED one of the state they ended on: one row per trajectory, as after the shared prefix)
+    const bool combined = shared || mj != nullptr;
+    CfgMeanArgs m; m.x = c->s_x; m.eps = mj ? c->m_eps : c->s_eps; m.B = B; m.HS = (int)HS; m.n_rp = combined ? 1 : p->n_rp;
     m.w0 = (float)p->w0; m.w1 = (float)p->w1; m.w0p1 = (float)(1.0 + p->w0);
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
     float* chain_j = chain ? c->s_chain + (size_t)(j + 1) * n : nullptr;
     const bool apf = (p->apf.cloud != nullptr || sc_apf) && p->apply_apf && p->apply_apf[j];
     // the guidance step: the shared prefix has combined the rows already (one row left); otherwise by the job's scalars or its weight table
-    const bool by_table = c->g_weight_cur && !shared;
+    const bool by_table = c->g_weight_cur && !combined;
     if (!p->ddim) {
       m.coef1 = p->coef1[j]; m.coef2 = p->coef2[j]; m.mean = c->s_mean; m.x0 = nullptr;
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
@@ -2044,8 +2134,11 @@ static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, 
 }
 
 // g != nullptr: a composed job (ramp_sample_composed; its arguments are checked there) -- n_rp up to RAMP_MAX_ROWS_PER_TRAJ, p->w0 / p->w1 not read
+// mj != nullptr: Langevin refinement (ramp_sample_mcmc; its arguments are checked there) -- mcmc_noise / mcmc_u the injected draws (noise_mode 0),
+// accept_out (sum K, B) the accept flags
 static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
-                      void* stream, const ramp_guidance_rows* g = nullptr) {
+                      void* stream, const ramp_guidance_rows* g = nullptr, const McmcJob* mj = nullptr, const float* mcmc_noise = nullptr,
+                      const float* mcmc_u = nullptr, int32_t* accept_out = nullptr) {
   RAMP_REQUIRE(c && p, "null argument");
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
@@ -2062,7 +2155,19 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const bool chain = chain_out != nullptr;
   const size_t n_noise = (p->ddim ? 1 : (size_t)p->n_steps + 1) * n;
   CK(ensure_sampler_buffers(c, B, p->n_rp, p->n_steps, chain));
-  CK(grow(c, c->trip_log, c->trip_log_cap, (size_t)std::max(256, p->n_steps)));
+  const int n_evals = p->n_steps + (mj ? mj->total : 0);
+  CK(grow(c, c->trip_log, c->trip_log_cap, (size_t)std::max(256, n_evals)));
+  if (mj) {
+    const size_t nk = (size_t)mj->total, rows = (size_t)B * p->n_rp;
+    if ((size_t)B > c->m_cap_B) { CK(renew(c, c->m_xp, n)); CK(renew(c, c->m_eps, n)); CK(renew(c, c->m_eps_p, n)); c->m_cap_B = B; }
+    CK(grow(c, c->m_noise, c->m_noise_cap, nk * n));
+    if (nk * B > c->m_u_cap) { CK(renew(c, c->m_u, nk * B)); CK(renew(c, c->m_flag, nk * B)); c->m_u_cap = nk * B; }
+    if (mj->kind == 2) {      // MALA alone asks for energies: f of every row, the rows' energies, the combined energy of state and proposal
+      CK(grow(c, c->m_f, c->m_f_cap, rows * H * S));
+      CK(grow(c, c->m_Erows, c->m_Erows_cap, rows));
+      if ((size_t)B > c->m_E_cap) { CK(renew(c, c->m_E, (size_t)B)); CK(renew(c, c->m_Ep, (size_t)B)); c->m_E_cap = B; }
+    }
+  }
   for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
   if (!c->s_hard_idx) CK(renew(c, c->s_hard_idx, 256));
   RAMP_REQUIRE(p->n_hard <= 256, "too many hard conditions");
@@ -2105,6 +2210,8 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_philox, rec, 16, hipMemcpyHostToDevice, s));     // (pageable host memory: the copy is staged before the call returns)
   } else {
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_noise, noise, n_noise * 4, hipMemcpyDeviceToDevice, s));
+    if (mj) RAMP_HIP_CHECK(hipMemcpyAsync(c->m_noise, mcmc_noise, (size_t)mj->total * n * 4, hipMemcpyDeviceToDevice, s));
+    if (mj && mj->kind == 2) RAMP_HIP_CHECK(hipMemcpyAsync(c->m_u, mcmc_u, (size_t)mj->total * B * 4, hipMemcpyDeviceToDevice, s));
   }
   c->launches = 0;
   invalidate_calibrations(c, CAL_SCORE | CAL_REPLAN);      // the loop below overwrites the delayed-scaling tables
@@ -2126,6 +2233,10 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const int ch = chain; key.put(ch); key.put(c->force_x6); key.put(p->noise_mode);
   if (sc) { const int tag[3] = {0x5343454e /* "SCEN" */, sc_apf ? sc->n_scenes : 0, sc_points}; key.put(tag, 3); }      // (a single-scene job's key has no such tail)
   if (g) { const int tag = 0x434f4d50 /* "COMP" */; key.put(tag); }
+  if (mj) {      // (the m_* buffers exist only for such a job; the step sizes are kernel arguments of the captured nodes)
+    const int tag[2] = {0x4d434d43 /* "MCMC" */, mj->kind}; key.put(tag, 2);
+    key.put(mj->n_inner, p->n_steps); key.put(mj->step_size, p->n_steps); key.put(mj->sigma, p->n_steps);
+  }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
@@ -2161,9 +2272,9 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   }
   staging_done(c);
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
-  c->last_job_steps = h3 ? p->n_steps : 0;
+  c->last_job_steps = h3 ? n_evals : 0;
   if (!p->use_graph) {
-    CK(sample_body(c, p, sc, s, chain, steady, cal_eval));
+    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj));
   } else {
     if (key.bytes != c->graph_key) { drop_graphs(c->s_graph, 3); c->graph_key = key.bytes; c->graph_rerun_key.clear(); }
     hipGraphExec_t* slot = &c->s_graph[steady ? 1 : 0];
@@ -2173,8 +2284,9 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       if (rk.bytes != c->graph_rerun_key) drop_graphs(slot, 1);
       c->graph_rerun_key = rk.bytes;
     }
-    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval); }));
+    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj); }));
   }
+  if (mj && accept_out) RAMP_HIP_CHECK(hipMemcpyAsync(accept_out, c->m_flag, (size_t)mj->total * B * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
   if (x_out) RAMP_HIP_CHECK(hipMemcpyAsync(x_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
@@ -2191,20 +2303,57 @@ int ramp_sample_scenes(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   return sample_job(c, p, scenes, noise, chain_out, x_out, stream);
 }
 
+// what a guidance table must satisfy, for both entries that take one (`who` names the entry in the message)
+static int check_guidance(ramp_ctx* c, const ramp_sample_params* p, const ramp_guidance_rows* g, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(g->row_weight, w + "null row_weight");
+  RAMP_REQUIRE(g->n_rp >= 2 && g->n_rp <= RAMP_MAX_ROWS_PER_TRAJ, w + "n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ");
+  RAMP_REQUIRE(g->n_rp == p->n_rp, w + "the guidance table's n_rp differs from the job's");
+  RAMP_REQUIRE(p->B > 0 && (long)p->B * p->n_rp <= (1l << 24), w + "bad batch");
+  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the guidance step moves four elements per access)");
+  RAMP_REQUIRE(c->rv_rows > 0, w + "the row -> latent table comes from ramp_set_scenes (none is in place)");
+  RAMP_REQUIRE(c->rv_rows >= p->B * p->n_rp, w + "the ramp_set_scenes table is shorter than B * n_rp rows");
+  return 0;
+}
+
 // Composition over any number of obstacle sets (diffusion_model_static.py:188-229; diffusion_model_3d.py:163-182, three sets at :165-174) and many
 // scenes per job: rows and weights are data.  Every refusal is a host check made before anything is staged or launched.
 int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
                          float* chain_out, float* x_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_composed: null argument");
   RAMP_REQUIRE(g, "ramp_sample_composed: null guidance table");
-  RAMP_REQUIRE(g->row_weight, "ramp_sample_composed: null row_weight");
-  RAMP_REQUIRE(g->n_rp >= 2 && g->n_rp <= RAMP_MAX_ROWS_PER_TRAJ, "ramp_sample_composed: n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ");
-  RAMP_REQUIRE(g->n_rp == p->n_rp, "ramp_sample_composed: the guidance table's n_rp differs from the job's");
-  RAMP_REQUIRE(p->B > 0 && (long)p->B * p->n_rp <= (1l << 24), "ramp_sample_composed: bad batch");
-  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, "ramp_sample_composed: H * S must be a multiple of 4 (the guidance step moves four elements per access)");
-  RAMP_REQUIRE(c->rv_rows > 0, "ramp_sample_composed: the row -> latent table comes from ramp_set_scenes (none is in place)");
-  RAMP_REQUIRE(c->rv_rows >= p->B * p->n_rp, "ramp_sample_composed: the ramp_set_scenes table is shorter than B * n_rp rows");
+  CK(check_guidance(c, p, g, "ramp_sample_composed"));
   const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g);
+  c->g_weight_cur = nullptr;
+  return rc;
+}
+
+// Langevin refinement inside the job: one entry for plain (g, scenes NULL), many-scene (scenes) and composed (g) jobs.  kind 0 is the
+// matching plain entry, bit for bit.  Every refusal is a host check made before anything is staged or launched.
+int ramp_sample_mcmc(ramp_ctx* c, const ramp_sample_params* p, const ramp_mcmc_params* m, const ramp_guidance_rows* g,
+                     const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise, const float* mcmc_u, float* chain_out,
+                     float* x_out, int32_t* accept_out, void* stream) {
+  RAMP_REQUIRE(c && p && m, "ramp_sample_mcmc: null argument");
+  RAMP_REQUIRE(m->kind >= 0 && m->kind <= 2, "ramp_sample_mcmc: kind must be 0 (off), 1 (ULA) or 2 (MALA)");
+  if (g) CK(check_guidance(c, p, g, "ramp_sample_mcmc"));
+  McmcJob mj{m->kind, m->n_inner, m->step_size, m->sigma, 0};
+  if (m->kind != 0) {
+    RAMP_REQUIRE(p->predict_x0 == 0, "ramp_sample_mcmc: predict_x0 != 0 -- the combined network output is then x0, not a score: there is no density to correct");
+    RAMP_REQUIRE(p->n_steps > 0 && m->n_inner && m->step_size && m->sigma, "ramp_sample_mcmc: missing n_inner / step_size / sigma arrays");
+    for (int j = 0; j < p->n_steps; ++j) {
+      RAMP_REQUIRE(m->n_inner[j] >= 0 && m->n_inner[j] <= RAMP_MCMC_MAX_INNER, "ramp_sample_mcmc: n_inner outside 0 .. 16");
+      if (m->n_inner[j] == 0) continue;
+      RAMP_REQUIRE(std::isfinite(m->step_size[j]) && m->step_size[j] > 0.f, "ramp_sample_mcmc: step_size must be positive and finite where n_inner > 0");
+      RAMP_REQUIRE(std::isfinite(m->sigma[j]) && m->sigma[j] > 0.f, "ramp_sample_mcmc: sigma must be positive and finite where n_inner > 0");
+      mj.total += m->n_inner[j];
+    }
+    if (mj.total > 0 && p->noise_mode == 0) {
+      RAMP_REQUIRE(mcmc_noise, "ramp_sample_mcmc: null mcmc_noise (noise_mode 0 injects the inner steps' normals)");
+      RAMP_REQUIRE(m->kind != 2 || mcmc_u, "ramp_sample_mcmc: null mcmc_u (noise_mode 0 injects MALA's uniforms)");
+    }
+  }
+  // (kind 0, or no inner step anywhere: the plain job)
+  const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g, mj.total > 0 ? &mj : nullptr, mcmc_noise, mcmc_u, accept_out);
   c->g_weight_cur = nullptr;
   return rc;
 }

@@ -278,6 +278,45 @@ int ramp_ddim_finish(const float* x, const float* x0, float sqrt_a_t, float sqrt
                             as_stream(stream));
 }
 
+int ramp_row_energy(const float* f, int32_t R, int32_t HS, double* energy_out, void* stream) {
+  RAMP_REQUIRE(f && energy_out, "ramp_row_energy: null argument");
+  RAMP_REQUIRE(R > 0 && HS > 0, "ramp_row_energy: R > 0 and H * S > 0");
+  return launch_row_energy(f, energy_out, R, HS, as_stream(stream));
+}
+
+int ramp_combine_energy(const double* energy_rows, int32_t B, int32_t n_rp, const float* weights_host, const float* row_weight,
+                        double* energy_out, void* stream) {
+  RAMP_REQUIRE(energy_rows && energy_out, "ramp_combine_energy: null argument");
+  RAMP_REQUIRE((weights_host != nullptr) != (row_weight != nullptr), "ramp_combine_energy: exactly one of weights_host and row_weight");
+  RAMP_REQUIRE(B > 0 && n_rp >= 1 && n_rp <= (row_weight ? RAMP_MAX_ROWS_PER_TRAJ : 3), "ramp_combine_energy: n_rp outside 1 .. 3 (host weights) / 1 .. RAMP_MAX_ROWS_PER_TRAJ (table)");
+  EnergyWeights w; w.rw = row_weight;
+  if (weights_host) for (int j = 0; j < n_rp; ++j) w.w[j] = weights_host[j];
+  return launch_combine_energy(energy_rows, w, energy_out, B, n_rp, as_stream(stream));
+}
+
+int ramp_mcmc_propose(const float* x, const float* eps, const float* z, float a, float c, const int32_t* pinned_idx, int32_t n_pinned,
+                      float* x_prop, int32_t B, int32_t H, int32_t S, void* stream) {
+  RAMP_REQUIRE(x && eps && z && x_prop, "ramp_mcmc_propose: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0 && n_pinned >= 0 && (n_pinned == 0 || pinned_idx), "ramp_mcmc_propose: bad dims");
+  HardConds hc; hc.idx = pinned_idx; hc.n = n_pinned;
+  return launch_mcmc_propose(x, eps, z, a, c, hc, x_prop, B, H, S, as_stream(stream));
+}
+
+int ramp_mcmc_accept(float* x, const float* x_prop, float* eps, const float* eps_prop, double* energy, const double* energy_prop,
+                     const float* u, int32_t kind, float a, double sigma, double eta, const int32_t* pinned_idx, int32_t n_pinned,
+                     int32_t* accept_out, double* log_alpha_out, int32_t B, int32_t H, int32_t S, void* stream) {
+  RAMP_REQUIRE(x && x_prop && eps && eps_prop && accept_out, "ramp_mcmc_accept: null argument");
+  RAMP_REQUIRE(kind == 1 || kind == 2, "ramp_mcmc_accept: kind must be 1 (ULA) or 2 (MALA)");
+  RAMP_REQUIRE(kind == 1 || (energy && energy_prop && u), "ramp_mcmc_accept: MALA needs energy, energy_prop and u");
+  RAMP_REQUIRE(kind == 1 || (sigma > 0 && eta > 0), "ramp_mcmc_accept: sigma and eta must be positive");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0 && n_pinned >= 0 && (n_pinned == 0 || pinned_idx), "ramp_mcmc_accept: bad dims");
+  McmcAcceptArgs m; m.x = x; m.xp = x_prop; m.eps = eps; m.eps_p = eps_prop; m.E = energy; m.E_p = energy_prop; m.u = u;
+  m.flag = accept_out; m.log_alpha = log_alpha_out; m.hc.idx = pinned_idx; m.hc.n = n_pinned; m.B = B; m.H = H; m.S = S;
+  m.mala = kind == 2; m.a = a;
+  if (m.mala) { m.inv_sigma = 1.0 / sigma; m.inv_4eta = 1.0 / (4.0 * eta); }
+  return launch_mcmc_accept(m, as_stream(stream));
+}
+
 // the sample-owning k = 5 convolution (tkc.hip) on the raw weight W [5][N][K]: mode 5 of ramp_op_gemm_mode and the narrow layers of
 // ramp_op_tkw; `t` carries the caller's operands
 static int op_tkc(TkcArgs t, const float* W, float absmax_prev, float* absmax_out_host, int32_t* range_flag_out_host, hipStream_t s) {

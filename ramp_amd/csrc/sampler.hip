@@ -868,13 +868,143 @@ int launch_philox_normal(float* out, long n, const unsigned long long* rec, hipS
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
-int launch_philox_normal_sharded(float* out, int n_blocks, int B, int HS, long sample0, long B_total, const unsigned long long* rec, hipStream_t s) {
+int launch_philox_normal_sharded(float* out, int n_blocks, int B, int HS, long sample0, long B_total, const unsigned long long* rec, hipStream_t s,
+                                 long block0) {
   RAMP_REQUIRE(out && rec && n_blocks > 0 && B > 0 && HS > 0 && HS % 4 == 0, "philox: bad shard dims (H S must be a multiple of 4)");
-  RAMP_REQUIRE(sample0 >= 0 && B_total >= sample0 + B, "philox: the shard [sample0, sample0 + B) must lie inside the job's B_total samples");
+  RAMP_REQUIRE(sample0 >= 0 && B_total >= sample0 + B && block0 >= 0, "philox: the shard [sample0, sample0 + B) must lie inside the job's B_total samples");
   RAMP_REQUIRE((reinterpret_cast<uintptr_t>(out) & 15) == 0, "philox: output must be 16-byte aligned");
   const long n = (long)n_blocks * B * HS, n_grp = n >> 2;
+  // (block j of this launch is block block0 + j of the stream: (block0 + j) B_total + sample0 + b = j B_total + (block0 B_total + sample0) + b)
   hipLaunchKernelGGL(philox_normal_kernel, dim3((unsigned)std::min<long>((n_grp + 255) / 256, 8192)), dim3(256), 0, s, out, n, rec,
-                     (long)(HS / 4), (long)B, sample0, B_total);
+                     (long)(HS / 4), (long)B, block0 * B_total + sample0, B_total);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// out[k B + b] = the uniform of (inner step k, global sample sample0 + b): u = ((r >> 9) + 0.5) 2^-23 in (0, 1), r = output 0 of the stream's group
+// group0 + k B_total + sample0 + b (one group per uniform, its other three words unused)
+__global__ __launch_bounds__(256) void philox_uniform_kernel(float* __restrict__ out, long n, const unsigned long long* __restrict__ rec,
+                                                              long group0, long B, long sample0, long B_total) {
+  const unsigned long long seed = rec[0], offset = rec[1];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const long k = i / B, b = i - k * B;
+    const unsigned long long ctr = (unsigned long long)(group0 + k * B_total + sample0 + b) + offset;
+    unsigned c[4] = {(unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0u};
+    philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+    out[i] = ((float)(c[0] >> 9) + 0.5f) * 1.1920928955078125e-7f;
+  }
+}
+int launch_philox_uniform_sharded(float* out, int n_blocks, int B, long group0, long sample0, long B_total, const unsigned long long* rec,
+                                  hipStream_t s) {
+  RAMP_REQUIRE(out && rec && n_blocks > 0 && B > 0 && group0 >= 0, "philox uniform: bad dims");
+  RAMP_REQUIRE(sample0 >= 0 && B_total >= sample0 + B, "philox uniform: the shard [sample0, sample0 + B) must lie inside the job's B_total samples");
+  const long n = (long)n_blocks * B;
+  hipLaunchKernelGGL(philox_uniform_kernel, dim3((unsigned)std::min<long>((n + 255) / 256, 8192)), dim3(256), 0, s, out, n, rec, group0, (long)B,
+                     sample0, B_total);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---- energies and Langevin refinement (ULA / MALA) ---------------------------------------------------------------------------
+// The score is an energy gradient, eps = grad_x 1/2 ||f(x, t, scene)||^2 (UnetInference.py:26-32 returns the energy next to it), so two
+// states can be compared: E[r] = 1/2 sum_{h,s} f[r,h,s]^2.  One wave per row: lane l adds the fp32 squares of elements l, l + 64, ... in
+// fp64 in that order, then the 64 partial sums meet in a fixed butterfly -- no atomics, the same bits whatever the launch's row count is.
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void row_energy_kernel(const float* __restrict__ f, double* __restrict__ E, int R, int HS) {
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (r >= R) return;                                  // (a whole wave leaves together)
+  const float* fr = f + (size_t)r * HS;
+  double acc = 0.0;
+  for (int e = lane; e < HS; e += 64) { const float v = fr[e]; acc += (double)mul(v, v); }
+  acc = wave_sum(acc);
+  if (lane == 0) E[r] = 0.5 * acc;
+}
+int launch_row_energy(const float* f, double* E, int R, int HS, hipStream_t s) {
+  RAMP_REQUIRE(f && E && R > 0 && HS > 0, "row_energy: bad operands");
+  hipLaunchKernelGGL(row_energy_kernel, dim3((R + 3) / 4), dim3(256), 0, s, f, E, R, HS);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+// E_comb[b] = sum_j w_j E[b n_rp + j] in fp64, j ascending: w the job's three host scalars (w.rw == nullptr) or line b of the device table
+__global__ __launch_bounds__(256) void combine_energy_kernel(const double* __restrict__ E, EnergyWeights w, double* __restrict__ out, int B, int n_rp) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  double acc = 0.0;
+  for (int j = 0; j < n_rp; ++j) {
+    const float wj = w.rw ? w.rw[(size_t)b * n_rp + j] : w.w[j];
+    acc += (double)wj * E[(size_t)b * n_rp + j];
+  }
+  out[b] = acc;
+}
+int launch_combine_energy(const double* E_rows, const EnergyWeights& w, double* E_comb, int B, int n_rp, hipStream_t s) {
+  RAMP_REQUIRE(E_rows && E_comb && B > 0 && n_rp >= 1 && n_rp <= 8 && (w.rw || n_rp <= 3), "combine_energy: bad operands");
+  hipLaunchKernelGGL(combine_energy_kernel, dim3((B + 255) / 256), dim3(256), 0, s, E_rows, w, E_comb, B, n_rp);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+__device__ __forceinline__ bool pinned(const HardConds& hc, int h) {
+  bool hit = false;
+  for (int k = 0; k < hc.n; ++k) hit |= (hc.idx[k] == h);
+  return hit;
+}
+// Langevin proposal: x' = (x - a eps) + c z on free waypoints (two products, a difference and a sum in fp32, no contraction), x' = x on the
+// waypoints the hard conditions pin
+__global__ __launch_bounds__(256) void mcmc_propose_kernel(const float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ z,
+                                                            float a, float cz, HardConds hc, float* __restrict__ xp, int B, int H, int S) {
+  const long n = (long)B * H * S;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
+    const int h = (int)((idx / S) % H);
+    const float xv = x[idx];
+    xp[idx] = pinned(hc, h) ? xv : add(sub(xv, mul(a, eps[idx])), mul(cz, z[idx]));
+  }
+}
+int launch_mcmc_propose(const float* x, const float* eps, const float* z, float a, float cz, HardConds hc, float* xp, int B, int H, int S,
+                        hipStream_t s) {
+  RAMP_REQUIRE(x && eps && z && xp && B > 0 && H > 0 && S > 0, "mcmc_propose: bad operands");
+  hipLaunchKernelGGL(mcmc_propose_kernel, dim3(ew_grid((long)B * H * S)), dim3(256), 0, s, x, eps, z, a, cz, hc, xp, B, H, S);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
+}
+// Accept / reject, one wave per trajectory.  mala: log alpha = -(E' - E) / sigma - (||x - x' + a eps'||^2 - ||x' - x + a eps||^2) / (4 eta), every
+// term and both sums in fp64 over the free elements (lane l adds elements l, l + 64, ... in order, then the butterfly); accepted when
+// log u < log alpha with E' and log alpha finite.  !mala (ULA): always.  An accepted trajectory's x, eps (and E) become the proposal's.
+__global__ __launch_bounds__(256) void mcmc_accept_kernel(McmcAcceptArgs a) {
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (b >= a.B) return;
+  const int HS = a.H * a.S;
+  const size_t o = (size_t)b * HS;
+  bool acc = true;
+  double la = 0.0;
+  if (a.mala) {
+    double fwd = 0.0, rev = 0.0;
+    for (int e = lane; e < HS; e += 64) {
+      if (pinned(a.hc, e / a.S)) continue;
+      const double xv = a.x[o + e], xq = a.xp[o + e];
+      const double dr = xv - xq + (double)a.a * (double)a.eps_p[o + e];      // x - mean(x')
+      const double df = xq - xv + (double)a.a * (double)a.eps[o + e];        // x' - mean(x)
+      rev += dr * dr; fwd += df * df;
+    }
+    rev = wave_sum(rev); fwd = wave_sum(fwd);
+    const double Ep = a.E_p[b];
+    la = -(Ep - a.E[b]) * a.inv_sigma - (rev - fwd) * a.inv_4eta;
+    acc = isfinite(Ep) && isfinite(la) && log((double)a.u[b]) < la;
+    if (lane == 0 && a.log_alpha) a.log_alpha[b] = la;
+  }
+  if (acc) {
+    for (int e = lane; e < HS; e += 64) { a.x[o + e] = a.xp[o + e]; a.eps[o + e] = a.eps_p[o + e]; }
+    if (lane == 0 && a.mala) a.E[b] = a.E_p[b];
+  }
+  if (lane == 0) a.flag[b] = acc ? 1 : 0;
+}
+int launch_mcmc_accept(const McmcAcceptArgs& a, hipStream_t s) {
+  RAMP_REQUIRE(a.x && a.xp && a.eps && a.eps_p && a.flag && a.B > 0 && a.H > 0 && a.S > 0, "mcmc_accept: bad operands");
+  RAMP_REQUIRE(!a.mala || (a.E && a.E_p && a.u), "mcmc_accept: MALA needs the energies and the uniforms");
+  hipLaunchKernelGGL(mcmc_accept_kernel, dim3((a.B + 3) / 4), dim3(256), 0, s, a);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -74,6 +74,52 @@ class _HostArrays:
 DDIM_FIELDS = ('sqrt_recip', 'sqrt_recipm1', 'sqrt_a_t', 'sqrt_1m_a_t', 'sqrt_a_prev', 'dir_coef')
 
 
+def mcmc_tables(mcmc: dict, steps, alphas_cumprod) -> dict:
+    """The per-iteration tables of a Langevin refinement (``mcmc=`` of run_inference*; ramp_mcmc_params) for the job whose
+    iterations evaluate the network timesteps ``steps`` (the DDPM or the DDIM list), host data only.
+
+      kind        'ula' | 'mala'
+      steps       K inner steps on every iteration, or one count per iteration (0 .. 16)
+      step_scale  c: eta_t = c (1 - alphas_cumprod[t]), so a = eta / sigma_t = c sigma_t and the noise scale is sigma_t sqrt(2 c)
+      step_size   None, or one eta per iteration (overrides step_scale)
+      t_range     (lo, hi): only iterations with lo <= t <= hi refine (K_j = 0 outside)
+      noise, u    optional injected draws, (sum K, B, H, S) normals and (sum K, B) uniforms in (0, 1), for a job whose loop noise is
+                  injected too (``noise_source='torch'``); None: ``torch.randn`` / ``torch.rand`` behind the loop's own draws
+
+    Returns ``{'kind': 1 | 2, 'n_inner': [...], 'step_size': [...], 'sigma': [...], 'total': sum K}``; sigma_t = sqrt(1 - alphas_cumprod[t])."""
+    if not isinstance(mcmc, dict):
+        raise TypeError("mcmc= takes a dict(kind=, steps=, step_scale= | step_size=, t_range=)")
+    unknown = set(mcmc) - {'kind', 'steps', 'step_scale', 'step_size', 't_range', 'noise', 'u'}
+    if unknown:
+        raise ValueError(f"mcmc=: unknown keys {sorted(unknown)}")
+    kind = mcmc.get('kind', 'mala')
+    if kind not in _lib.MCMC_KINDS:
+        raise ValueError(f"mcmc kind must be 'ula' or 'mala'; got {kind!r}")
+    n = len(steps)
+    ac = np.asarray(alphas_cumprod.detach().cpu().numpy() if torch.is_tensor(alphas_cumprod) else alphas_cumprod, dtype=np.float64)
+    K = mcmc.get('steps', 1)
+    K = [int(K)] * n if np.isscalar(K) else [int(k) for k in K]
+    if len(K) != n:
+        raise ValueError(f"mcmc steps: {len(K)} entries for {n} iterations")
+    if 't_range' in mcmc and mcmc['t_range'] is not None:
+        lo, hi = mcmc['t_range']
+        K = [k if lo <= t <= hi else 0 for k, t in zip(K, steps)]
+    if any(k < 0 or k > _lib.MCMC_MAX_INNER for k in K):
+        raise ValueError(f"mcmc steps must lie in 0 .. {_lib.MCMC_MAX_INNER} per iteration")
+    sigma = [float(np.sqrt(1.0 - ac[t])) for t in steps]
+    if mcmc.get('step_size') is not None:
+        eta = [float(e) for e in mcmc['step_size']]
+        if len(eta) != n:
+            raise ValueError(f"mcmc step_size: {len(eta)} entries for {n} iterations")
+    else:
+        c = float(mcmc.get('step_scale', 0.1))
+        eta = [c * float(1.0 - ac[t]) for t in steps]
+    for k, e in zip(K, eta):
+        if k > 0 and not (np.isfinite(e) and e > 0):
+            raise ValueError("mcmc step sizes must be positive and finite wherever inner steps run")
+    return {'kind': _lib.MCMC_KINDS[kind], 'n_inner': K, 'step_size': eta, 'sigma': sigma, 'total': int(sum(K))}
+
+
 class _GaussianDiffusionBase(nn.Module):
     _default_cfg_weight = 2.0
 
@@ -100,6 +146,7 @@ class _GaussianDiffusionBase(nn.Module):
         # several GPUs: this wrapper's batch is samples [sample0, sample0 + B) of a job of `total` trajectories; a philox job then
         # draws exactly the elements the unsharded job draws for those samples (set_noise_shard; ramp_sample_params.philox_sample0)
         self._philox_shard = None
+        self.last_mcmc = None                   # after a job with mcmc=: {'accept': (sum K, B) int32, 'rate': per iteration, 'n_inner': per iteration}
         self.context_model = context_model
         self.n_diffusion_steps = n_diffusion_steps
         self.ddim_num_inference_steps = 8 if (compose and use_apf) else 5      # diffusion_model_static.py:40
@@ -305,17 +352,38 @@ class _GaussianDiffusionBase(nn.Module):
         p.apf.cloud = _lib.ptr(cloud)
         p.apf.n_points = cloud.shape[0]
 
-    def _philox_block(self, B: int, n_steps: int, ddim: bool):
+    def _philox_block(self, B: int, n_steps: int, ddim: bool, n_inner: int = 0):
         """A job that draws its own noise takes the next (n_steps + 1 | 1) * total * H * S elements of the Philox stream: returns
-        (seed, offset, sample0, total) for the params and advances the offset by the WHOLE job's block (every shard advances alike)."""
+        (seed, offset, sample0, total) for the params and advances the offset by the WHOLE job's block (every shard advances alike).
+        ``n_inner`` > 0 (a job with Langevin steps): its draws sit behind the full (n_steps + 1)-block main block -- n_inner blocks of
+        normals, then one group per uniform (ramp_sample_mcmc in ramp_hip.h) -- and the offset advances past them."""
         s0, tot = self._philox_shard if self._philox_shard is not None else (0, B)
         if not (0 <= s0 and s0 + B <= tot):
             raise ValueError(f"set_noise_shard: samples [{s0}, {s0 + B}) lie outside the job's {tot}")
-        n_el = (1 if ddim else n_steps + 1) * tot * self.model.n_support_points * self.state_dim
+        hs = self.model.n_support_points * self.state_dim
+        n_el = (1 if ddim else n_steps + 1) * tot * hs
         offset = self._philox_offset
         self.last_philox = (self.noise_seed, offset, n_el)
-        self._philox_offset += (n_el + 3) // 4
+        if n_inner:
+            self._philox_offset += (n_steps + 1 + n_inner) * tot * hs // 4 + n_inner * tot
+        else:
+            self._philox_offset += (n_el + 3) // 4
         return self.noise_seed, offset, s0, tot
+
+    def _mcmc_tables(self, mcmc: dict, steps) -> dict:
+        """The host tables of the job's Langevin refinement (``mcmc_tables``), or the refusal -- before anything touches the device."""
+        if not self.predict_epsilon:
+            raise NotImplementedError("mcmc=: predict_epsilon=False makes the combined network output x0, not a score -- there is no "
+                                      "density for the Langevin steps to correct")
+        return mcmc_tables(mcmc, steps, self.alphas_cumprod)
+
+    @staticmethod
+    def _fill_mcmc(arrays: _HostArrays, tab: dict):
+        """ramp_mcmc_params from the tables of ``mcmc_tables``."""
+        mp = _lib.RampMcmcParams()
+        mp.kind = tab['kind']
+        mp.n_inner, mp.step_size, mp.sigma = arrays.i32(tab['n_inner']), arrays.f32(tab['step_size']), arrays.f32(tab['sigma'])
+        return mp
 
     def _run_guarded(self, job):
         """Run ``job`` under the fp16x3 range-guard policy: a flagged result is discarded and the same job (same noise) repeated, never
@@ -360,11 +428,15 @@ class _GaussianDiffusionBase(nn.Module):
             self.last_job_mode = "bf16x6"
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
-                return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None):
+                return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None,
+                mcmc: Optional[dict] = None):
         """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
         (``ramp_sample_scenes``); ``obstacle_pts`` is not read then.  ``guidance`` (with a ``scene_job``): a composed job
-        (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``."""
+        (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``.
+        ``mcmc``: Langevin refinement inside the job (``ramp_sample_mcmc``, the one entry for all three kinds of job; ``mcmc_tables``);
+        the accept flags land in ``self.last_mcmc``."""
         m = self.model
+        tab = self._mcmc_tables(mcmc, steps) if mcmc is not None else None
         dev = self._device()
         H, S = m.n_support_points, self.state_dim
         n_steps = len(steps)
@@ -396,16 +468,36 @@ class _GaussianDiffusionBase(nn.Module):
         p.use_graph = int(self.use_graph)
         chain = torch.empty((n_steps + 1, B, H, S), device=dev, dtype=torch.float32) if return_chain else None
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
+        mp = z_in = u_in = accept = None
+        if tab is not None:
+            mp = self._fill_mcmc(arrays, tab)
+            accept = torch.zeros((tab['total'], B), device=dev, dtype=torch.int32)
         if noise is None:          # the job draws its own
+            if mcmc is not None and (mcmc.get('noise') is not None or mcmc.get('u') is not None):
+                raise ValueError("mcmc['noise'] / mcmc['u'] inject the inner steps' draws next to an injected loop noise; with "
+                                 "noise_source='philox' the job draws both itself -- leave them out")
             p.noise_mode = 1
-            p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim)
+            p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim, tab['total'] if tab else 0)
         else:
             noise = noise.contiguous()
+            if tab and tab['total']:      # the inner steps' draws, behind the loop's own in call order
+                z_in, u_in = mcmc.get('noise'), mcmc.get('u')
+                z_in = torch.randn((tab['total'], B, H, S), device=dev) if z_in is None else z_in.to(dev, torch.float32).contiguous()
+                if u_in is None:
+                    u_in = torch.rand((tab['total'], B), device=dev).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
+                u_in = u_in.to(dev, torch.float32).contiguous()
+                if tuple(z_in.shape) != (tab['total'], B, H, S) or tuple(u_in.shape) != (tab['total'], B):
+                    raise ValueError(f"mcmc noise / u must be ({tab['total']}, {B}, {H}, {S}) / ({tab['total']}, {B})")
         with torch.cuda.device(dev):
             lib = _lib.load()
 
             def job():
-                if rows is not None:
+                if mp is not None:
+                    _lib.check(lib.ramp_sample_mcmc(m.ctx(), C.byref(p), C.byref(mp), C.byref(rows) if rows is not None else None,
+                                                    C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
+                                                    _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
+                                                    _lib.current_stream()), "ramp_sample_mcmc")
+                elif rows is not None:
                     _lib.check(lib.ramp_sample_composed(m.ctx(), C.byref(p), C.byref(rows), C.byref(batch), _lib.ptr(noise), _lib.ptr(chain),
                                                         _lib.ptr(x_out), _lib.current_stream()), "ramp_sample_composed")
                 elif batch is not None:
@@ -416,6 +508,13 @@ class _GaussianDiffusionBase(nn.Module):
                                                _lib.current_stream()), "ramp_sample")
 
             self._run_guarded(job)
+        if tab is not None:      # one copy back
+            acc = accept.cpu()
+            rate, k0 = [], 0
+            for K in tab['n_inner']:
+                rate.append(float(acc[k0:k0 + K].float().mean()) if K else float('nan'))
+                k0 += K
+            self.last_mcmc = {'accept': acc, 'rate': rate, 'n_inner': list(tab['n_inner']), 'kind': tab['kind']}
         return x_out, chain
 
     # ------------------------------------------------------------------ loops (reference signatures)
@@ -432,12 +531,14 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
-                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, **sample_kwargs):
+                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
         reference's arguments -- on the eager loop below."""
         if not self._is_fused_ddpm_step(sample_fn):
+            if mcmc is not None:
+                raise NotImplementedError("mcmc= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if scene_job is not None:
                 raise NotImplementedError("run_inference_scenes runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
                                           "scene's batch at a time -- use run_inference per scene")
@@ -459,7 +560,7 @@ class _GaussianDiffusionBase(nn.Module):
                for j in range(len(steps))]
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
-                                    cfg, return_chain, scene_job=scene_job, guidance=guidance)
+                                    cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -501,7 +602,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
-                           guidance=None, **sample_kwargs):
+                           guidance=None, mcmc=None, **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
         B = shape[0]
@@ -510,7 +611,7 @@ class _GaussianDiffusionBase(nn.Module):
         apf = [1 if (self.APF and self._supports_apf and j >= self.apf_ddim['start']) else 0 for j in range(len(steps))]
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
-                                    return_chain, scene_job=scene_job, guidance=guidance)
+                                    return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -521,6 +622,8 @@ class _GaussianDiffusionBase(nn.Module):
         horizon = horizon or self.model.n_support_points
         shape = (batch_size, horizon, self.state_dim)
         if self.ddim:
+            if sample_kwargs.get('mcmc') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
+                raise NotImplementedError("mcmc= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
             for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
                 sample_kwargs.pop(k, None)      # silently ignored by the reference's DDIM loop
             return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized,
@@ -703,6 +806,42 @@ class _GaussianDiffusionBase(nn.Module):
         return (chain if return_chain else chain[-1]), job['traj_scene']
 
     # ------------------------------------------------------------------ single-step compat API
+    def _comb_weights(self):
+        """The weights of the rows' gradients (and energies) in the guidance-combined ones, as the library forms them (fp32)."""
+        n_rp = self._n_rp()
+        w0, w1 = (self.compose_weights if self.compose else (self.cfg_weight, 0.0))
+        if n_rp == 1:
+            return [1.0]
+        if n_rp == 2:
+            return [float(np.float32(1.0 + w0)), -float(np.float32(w0))]
+        return [float(np.float32(w0)), float(np.float32(w1)), float(np.float32(1.0 - w0 - w1))]
+
+    @torch.no_grad()
+    def energy(self, x, t, obstacle_pts) -> torch.Tensor:
+        """The guidance-combined energy of each trajectory at timestep t, E[b] = sum_j w_j 1/2 ||f(row j of b)||^2 with the weights that
+        form the combined gradient (CFG: (1 + w) E_cond - w E_uncond): the scalar whose gradient ``_x0_mean_eps`` combines.  (B,) float64
+        (``ramp_score_energy`` + ``ramp_combine_energy``)."""
+        dev = self._device()
+        B = x.shape[0]
+        ti = int(t.reshape(-1)[0]) if torch.is_tensor(t) else int(t)
+        self.model.prepare_time_table(self.n_diffusion_steps)
+        pts = obstacle_pts
+        if not self.compose and pts.dim() == 4:
+            pts = pts[0]
+        self._prepare_scene(pts.to(dev), B)
+        xx = x.detach().to(dev, torch.float32).contiguous()
+        n_rp = self._n_rp()
+        e_rows = torch.empty((B * n_rp,), device=dev, dtype=torch.float64)
+        out = torch.empty((B,), device=dev, dtype=torch.float64)
+        w = self._comb_weights()
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            _lib.check(lib.ramp_score_energy(self.model.ctx(), _lib.ptr(xx), B, n_rp, ti, None, None, _lib.ptr(e_rows),
+                                             _lib.current_stream()), "ramp_score_energy")
+            _lib.check(lib.ramp_combine_energy(_lib.ptr(e_rows), B, n_rp, (C.c_float * n_rp)(*w), None, _lib.ptr(out),
+                                               _lib.current_stream()), "ramp_combine_energy")
+        return out
+
     def _x0_mean_eps(self, x, t, obstacle_pts):
         """``ramp_score`` + ``ramp_cfg_mean`` at timestep t: (x0, posterior mean, guidance-combined eps)."""
         dev = self._device()

@@ -360,6 +360,26 @@ class TemporalUnetInference(nn.Module):
     def forward_no_energy(self, x, time, x_start=None, obstacle_pts=None, forward_t=None, compose=False):
         return self._run(x, time, obstacle_pts, compose, True, False)[0]
 
+    @torch.no_grad()
+    def energy(self, x, time, obstacle_pts=None, compose=False) -> torch.Tensor:
+        """E[r] = 1/2 sum_{h,s} f[r,h,s]^2 of every row of ``x`` (rows, H, S): the scalar whose input gradient ``forward`` returns
+        (the reference's EnergyGradFunction hands it out as its second value).  (rows,) float64, from ``ramp_score_energy``; ``time``
+        is one timestep for all rows."""
+        if obstacle_pts is None:
+            raise ValueError("obstacle_pts is required (the reference dereferences it unconditionally)")
+        n = x.shape[0]
+        t, rows = _split_time(time, n)
+        if rows is not None:
+            raise ValueError("energy(): one timestep for all rows (ramp_score_energy has no per-row form)")
+        x = x.detach().to(self._device(), torch.float32).contiguous()
+        self.prepare_time_table(max(t + 1, self._T_table, 1))
+        self.cache_scene_encoding(obstacle_pts, compose)
+        out = torch.empty((n,), device=self._device(), dtype=torch.float64)
+        with torch.cuda.device(self._device()):
+            _lib.check(_lib.load().ramp_score_energy(self.ctx(), _lib.ptr(x), n, 1, t, None, None, _lib.ptr(out), _lib.current_stream()),
+                       "ramp_score_energy")
+        return out
+
     # ------------------------------------------------------------------ debug taps
     def debug_read(self, kind: str, module: str, shape) -> torch.Tensor:
         out = torch.empty(shape, device=self._device(), dtype=torch.float32)
