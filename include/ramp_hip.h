@@ -317,6 +317,60 @@ typedef struct ramp_mcmc_params {
 int ramp_sample_mcmc(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_mcmc_params* m, const ramp_guidance_rows* g,
                      const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise, const float* mcmc_u,
                      float* chain_out, float* x_out, int32_t* accept_out, void* stream);
+/* ---- cost-gradient guidance steps inside the sampling job, 2-D and 3-D ----
+ * The reference samplers accept guide / n_guide_steps / t_start_guide and ignore them (guide_gradient_steps is a stub that returns x,
+ * sample_functionsdynamic.py:280-292); this is what those names mean in cost-guided trajectory diffusion: a few gradient steps on a
+ * differentiable trajectory cost inside the reverse step.  For one trajectory x (H, S), d = point_dim, p_h = x[h, 0:d] and its scene's cloud
+ * c (P, d):
+ *   C_obs    = sum_h sum_j 1/2 max(0, r - |p_h - c_j|)^2          every cloud point inside radius r (C1, no argmin)
+ *   C_smooth = sum_{h=0}^{H-2} 1/2 |p_{h+1} - p_h|^2
+ *   C_acc    = sum_{h=1}^{H-2} 1/2 |p_{h+1} - 2 p_h + p_{h-1}|^2
+ *   C        = w_obs C_obs + w_smooth C_smooth + w_acc C_acc
+ * A pair at distance 0 contributes no gradient; an empty cloud makes C_obs = 0.  One guide iteration: (1) the waypoints the job's hard
+ * conditions pin take their conditioned values in the working copy, (2) g = dC/dp, (3) g = 0 on the pinned waypoints, (4) n = |g|_2 over the
+ * trajectory, (5) s = min(1, max_norm / n), s = 1 if max_norm <= 0 or n = 0, (6) p <- p - (step s) g on the free waypoints.  Pinned
+ * waypoints and the channels >= d of the array in memory keep their bits.  All arithmetic is fp32 (the five scalars are rounded to fp32
+ * once), every product and sum rounded as written; |g|^2 is summed in fp64.  The fp32 sums over points run in an order fixed by (P, the
+ * kernel's tile of 1024 points): same inputs, same bits, whatever the batch.  H <= 128.
+ * Place in the reverse step of iteration j with n_guide[j] > 0: after the guidance-combined posterior mean (DDPM) resp. x0 (DDIM) and after
+ * the APF hook where that fires, before the noise / DDIM update and its hard conditioning; ONE launch runs the n_guide[j] iterations for all
+ * trajectories and scenes.  With inner MCMC steps the guide belongs to the reverse step, not to the inner steps.  It draws no random
+ * numbers: the Philox layout of a job, and what a shard needs, are unchanged.
+ * The clouds are the guide's own table (scenes->cloud_points stays the 2-D APF table and may be NULL): points and offsets are copied into
+ * buffers of the context before the launch and the captured graph reads those, so other cloud CONTENTS of the same sizes replay the same
+ * graph and are honoured.  n_guide, step and the five scalars are kernel arguments and part of the graph key: a job with other values is
+ * captured anew. */
+#define RAMP_GUIDE_MAX_STEPS 16
+typedef struct ramp_cost_guide {
+  int32_t point_dim;                 /* 2 or 3, <= state_dim */
+  int32_t n_scenes;                  /* clouds in the table; 1 for a single-scene job */
+  const float* cloud_points;         /* device (sum P, point_dim), scenes concatenated */
+  const int32_t* cloud_offset_host;  /* host (n_scenes + 1), [0] = 0, non-decreasing (an empty cloud is allowed) */
+  double radius, w_obs, w_smooth, w_acc, max_norm;
+  const int32_t* n_guide;            /* host (n_steps): guide iterations on loop iteration j, 0 .. RAMP_GUIDE_MAX_STEPS */
+  const float* step;                 /* host (n_steps): step size on iteration j (the caller folds any schedule factor in) */
+} ramp_cost_guide;
+/* ramp_sample_mcmc plus the guide: one entry for plain, many-scene, composed and MCMC jobs (m == NULL = no inner steps).  cg == NULL, or
+ * n_guide zero on every iteration, IS ramp_sample_mcmc, bit for bit.  On DDPM the guide acts on the posterior mean, on DDIM on x0.
+ * scenes->traj_scene maps trajectories to cg's clouds: cg->n_scenes must equal scenes->n_scenes, or be 1 with scenes == NULL.
+ * Refused on the host before any launch (non-zero, "ramp_sample_guided" in ramp_last_error): point_dim outside {2, 3} or > state_dim,
+ * n_guide[j] outside 0 .. RAMP_GUIDE_MAX_STEPS, non-finite scalars or step, radius <= 0 with w_obs != 0, offsets that are not
+ * non-decreasing from 0, a scene-count mismatch, cloud_points == NULL with a non-empty table, H > 128; and what ramp_sample_mcmc refuses.
+ * ramp_replan / ramp_replan_episodes take no guide. */
+int ramp_sample_guided(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
+                       const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
+                       const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream);
+/* the kernel alone on (B, H, S) trajectories in place, the counterpart of ramp_apf / ramp_apf_scenes: n_iter (0 .. RAMP_GUIDE_MAX_STEPS)
+ * iterations with step size `step` in one launch; cg->n_guide and cg->step are not read.  traj_scene device int32 (B) or NULL = scene 0;
+ * a trajectory whose scene index is outside [0, n_scenes) is left unchanged.  hard_idx_host host (n_hard) waypoint indices (later entries
+ * win), hard_val device (n_hard, B, S) as in ramp_sample_params.  Refusals as above, with "ramp_guide_step".  Synchronises `stream`. */
+int ramp_guide_step(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene, int32_t n_iter,
+                    float step, int32_t n_hard, const int32_t* hard_idx_host, const float* hard_val, void* stream);
+/* the three unweighted terms per trajectory, terms_out device (B, 3) doubles = {C_obs, C_smooth, C_acc}: fp64 sums over fp32 pair values in
+ * a fixed order, for ranking and diagnostics (no hard conditions: the trajectory as it is; NaN for a scene index outside the table).
+ * Synchronises `stream`. */
+int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene,
+                    double* terms_out, void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from

@@ -56,6 +56,16 @@ class RampMcmcParams(C.Structure):
     _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("n_inner", c_i32p), ("step_size", c_f32p), ("sigma", c_f32p)]
 
 
+GUIDE_MAX_STEPS = 16        # RAMP_GUIDE_MAX_STEPS
+
+
+class RampCostGuide(C.Structure):
+    """ramp_cost_guide: the cost-gradient guidance of a sampling job (ramp_sample_guided) and of the kernel-level ramp_guide_step / ramp_guide_cost."""
+    _fields_ = [("point_dim", C.c_int32), ("n_scenes", C.c_int32), ("cloud_points", C.c_void_p), ("cloud_offset_host", c_i32p),
+                ("radius", C.c_double), ("w_obs", C.c_double), ("w_smooth", C.c_double), ("w_acc", C.c_double), ("max_norm", C.c_double),
+                ("n_guide", c_i32p), ("step", c_f32p)]
+
+
 class RampSampleParams(C.Structure):
     _fields_ = [("B", C.c_int32), ("n_rp", C.c_int32), ("n_steps", C.c_int32), ("ddim", C.c_int32),
                 ("w0", C.c_double), ("w1", C.c_double),
@@ -147,6 +157,11 @@ PROTOTYPES = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_sample_mcmc": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampMcmcParams), C.POINTER(RampGuidanceRows),
                                    C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
+    "ramp_sample_guided": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampCostGuide), C.POINTER(RampMcmcParams),
+                                     C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
+    "ramp_guide_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_int32, C.c_float,
+                                  C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
+    "ramp_guide_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_score_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "ramp_row_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "ramp_combine_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p]),

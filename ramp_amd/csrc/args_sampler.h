@@ -84,6 +84,22 @@ struct ApfArgs {
   int n_scenes = 0;
 };
 int launch_apf(const ApfArgs& a, hipStream_t s);
+// ---- cost-gradient guidance (guide.hip; ramp_cost_guide in ramp_hip.h) -----------------------------
+struct GuideArgs {
+  float* traj = nullptr;            // (B,H,S): channels [0, D) of the free waypoints are updated in place (the cost kernel only reads)
+  int B = 0, H = 0, S = 0, D = 2;   // D = point_dim, 2 or 3, <= S; H <= 128
+  const float* cloud = nullptr;     // (P_total, D): the scenes' clouds, concatenated
+  const int* cloud_off = nullptr;   // device (n_scenes + 1): first point of each scene's cloud (an empty span is allowed; spans are clamped to P_total)
+  const int* scene = nullptr;       // (B) scene of each trajectory, or null = scene 0 for all; an index outside the table leaves the trajectory alone
+  int n_scenes = 1, P_total = 0;
+  float radius = 0, w_obs = 0, w_smooth = 0, w_acc = 0, max_norm = 0;
+  float step = 0; int n_iter = 0;   // (the cost kernel reads neither, nor hc)
+  HardConds hc;                     // pinned waypoints: their conditioned values enter the cost, their gradient is zero, their memory is not written
+};
+// n_iter guide iterations in ONE launch, one block per trajectory; n_iter == 0 launches nothing
+int launch_guide_step(const GuideArgs& a, hipStream_t s);
+// terms (B, 3) doubles = {C_obs, C_smooth, C_acc} unweighted (NaN for a trajectory whose scene index is outside the table)
+int launch_guide_cost(const GuideArgs& a, double* terms, hipStream_t s);
 struct ApfDynArgs {
   float* traj = nullptr;          // (B,H,S) in place (xy only)
   const double* points = nullptr; // (P,2) float64

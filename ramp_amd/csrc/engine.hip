@@ -145,6 +145,10 @@ struct ramp_ctx {
   float *m_xp = nullptr, *m_eps = nullptr, *m_eps_p = nullptr; size_t m_cap_B = 0;
   double *m_E = nullptr, *m_Ep = nullptr; size_t m_E_cap = 0;
   float *m_noise = nullptr, *m_u = nullptr; int* m_flag = nullptr; size_t m_noise_cap = 0, m_u_cap = 0;
+  // cost-gradient guidance inside a sampling job (ramp_sample_guided): the guide's own clouds (sum P, point_dim) and their offsets (n_scenes + 1),
+  // copied here before the launch -- the captured graph reads these buffers, so the clouds' contents are data of a replay.  The iteration
+  // counts, step sizes and the five scalars are kernel arguments, hence part of the graph key
+  float* cg_cloud = nullptr; size_t cg_cloud_cap = 0; int* cg_off = nullptr; size_t cg_off_cap = 0;
   // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
   // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
   hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
@@ -1969,11 +1973,14 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 // c->g_weight_cur != nullptr: a composed job (ramp_sample_composed) -- the rows' weights in e_comb come from that device table
 // The Langevin refinement of a job (ramp_sample_mcmc), checked by the entry: kind 1 ULA / 2 MALA, total = sum of n_inner > 0
 struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
+// The cost guide of a job (ramp_sample_guided), checked by the entry; only a guide with n_guide > 0 somewhere becomes one
+struct GuideJob { const ramp_cost_guide* cg; };
 
 // mj != nullptr: K_j = mj->n_inner[j] inner steps (propose -> one evaluation at x' -> accept) follow the evaluation of iteration j, and the reverse
 // step uses the cached combined gradient of the state they ended on; every evaluation, inner ones included, is one link of the calibration chain
+// gj != nullptr: on iteration j with n_guide[j] > 0 ONE launch runs that many guide iterations on the posterior mean (DDPM) / x0 (DDIM), behind the APF hook
 static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1,
-                       const McmcJob* mj = nullptr) {
+                       const McmcJob* mj = nullptr, const GuideJob* gj = nullptr) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -1999,6 +2006,18 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   ap.win = p->apf.window; ap.thr = p->apf.threshold; ap.strength = p->apf.strength;
   const bool sc_apf = sc && sc->cloud_points;
   if (sc_apf) { ap.scene = c->s_traj_scene; ap.scene_off = c->s_scene_off; ap.n_scenes = sc->n_scenes; ap.P = 0; }
+  GuideArgs ga;
+  if (gj) {
+    ga = guide_args(gj->cg, nullptr, B, H, S);
+    ga.cloud = c->cg_cloud; ga.cloud_off = c->cg_off; ga.scene = sc ? c->s_traj_scene : nullptr; ga.hc = hc;
+  }
+  // the guide's launch of iteration j on `target`, if it has one
+  auto guide_at = [&](int j, float* target) -> int {
+    if (!gj || gj->cg->n_guide[j] <= 0) return 0;
+    ga.traj = target; ga.n_iter = gj->cg->n_guide[j]; ga.step = gj->cg->step[j];
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_step(ga, s));
+    return 0;
+  };
   if (c->gemm_mode == 2) {
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
     if (!c->force_x6) hipLaunchKernelGGL(zero_words_kernel, dim3((n_evals + 255) / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->trip_log), n_evals);
@@ -2071,6 +2090,7 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
       m.coef1 = p->coef1[j]; m.coef2 = p->coef2[j]; m.mean = c->s_mean; m.x0 = nullptr;
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
       if (apf) { ap.traj = c->s_mean; for (int q = 0; q < std::max(1, p->apf.passes); ++q) LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); }
+      CK(guide_at(j, c->s_mean));
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddpm_finish(c->s_mean, c->s_noise + (size_t)(j + 1) * n, p->stdv[j], p->noise_scale ? p->noise_scale[j] : 1.f, p->use_noise[j],
                             hc, c->s_x, chain_j, B, H, S, s));
     } else {
@@ -2080,6 +2100,7 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
         ap.traj = c->s_x0;
         for (int q = 0; q < std::max(1, p->apf.passes); ++q) { LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x0, hc, B, H, S, s)); }
       }
+      CK(guide_at(j, c->s_x0));      // (the hard conditioning that follows is ddim_finish's own)
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], hc,
                             c->s_x, chain_j, B, H, S, s));
     }
@@ -2136,9 +2157,10 @@ static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, 
 // g != nullptr: a composed job (ramp_sample_composed; its arguments are checked there) -- n_rp up to RAMP_MAX_ROWS_PER_TRAJ, p->w0 / p->w1 not read
 // mj != nullptr: Langevin refinement (ramp_sample_mcmc; its arguments are checked there) -- mcmc_noise / mcmc_u the injected draws (noise_mode 0),
 // accept_out (sum K, B) the accept flags
+// gj != nullptr: cost-gradient guidance (ramp_sample_guided; its arguments are checked there)
 static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
                       void* stream, const ramp_guidance_rows* g = nullptr, const McmcJob* mj = nullptr, const float* mcmc_noise = nullptr,
-                      const float* mcmc_u = nullptr, int32_t* accept_out = nullptr) {
+                      const float* mcmc_u = nullptr, int32_t* accept_out = nullptr, const GuideJob* gj = nullptr) {
   RAMP_REQUIRE(c && p, "null argument");
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
@@ -2187,6 +2209,19 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     CK(grow(c, c->s_scene_off, c->s_scene_off_cap, (size_t)sc->n_scenes + 1));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_scene_off, sc->cloud_offset_host, ((size_t)sc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
+  }
+  int gj_points = 0;
+  if (gj) {      // the guide's own cloud table; the trajectory -> scene table is the scene batch's
+    const ramp_cost_guide* cg = gj->cg;
+    gj_points = cg->cloud_offset_host[cg->n_scenes];
+    CK(grow(c, c->cg_cloud, c->cg_cloud_cap, std::max<size_t>(4, (size_t)gj_points * cg->point_dim)));
+    CK(grow(c, c->cg_off, c->cg_off_cap, (size_t)cg->n_scenes + 1));
+    if (gj_points) RAMP_HIP_CHECK(hipMemcpyAsync(c->cg_cloud, cg->cloud_points, (size_t)gj_points * cg->point_dim * 4, hipMemcpyDeviceToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->cg_off, cg->cloud_offset_host, ((size_t)cg->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
+    if (sc && !sc_apf) {
+      CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));
+      RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    }
   }
   std::vector<float> g_host;      // the weights on the host: part of the canonical calibration's key below
   if (g) {
@@ -2237,6 +2272,12 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     const int tag[2] = {0x4d434d43 /* "MCMC" */, mj->kind}; key.put(tag, 2);
     key.put(mj->n_inner, p->n_steps); key.put(mj->step_size, p->n_steps); key.put(mj->sigma, p->n_steps);
   }
+  if (gj) {      // (cg_cloud / cg_off exist only for such a job; counts, step sizes and scalars are kernel arguments of the captured nodes)
+    const ramp_cost_guide* cg = gj->cg;
+    const int tag[5] = {0x47554944 /* "GUID" */, cg->point_dim, cg->n_scenes, gj_points, sc ? 1 : 0}; key.put(tag, 5);
+    const double sc5[5] = {cg->radius, cg->w_obs, cg->w_smooth, cg->w_acc, cg->max_norm}; key.put(sc5, 5);
+    key.put(cg->n_guide, p->n_steps); key.put(cg->step, p->n_steps);
+  }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
@@ -2274,7 +2315,7 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
   c->last_job_steps = h3 ? n_evals : 0;
   if (!p->use_graph) {
-    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj));
+    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj, gj));
   } else {
     if (key.bytes != c->graph_key) { drop_graphs(c->s_graph, 3); c->graph_key = key.bytes; c->graph_rerun_key.clear(); }
     hipGraphExec_t* slot = &c->s_graph[steady ? 1 : 0];
@@ -2284,7 +2325,7 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       if (rk.bytes != c->graph_rerun_key) drop_graphs(slot, 1);
       c->graph_rerun_key = rk.bytes;
     }
-    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj); }));
+    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj, gj); }));
   }
   if (mj && accept_out) RAMP_HIP_CHECK(hipMemcpyAsync(accept_out, c->m_flag, (size_t)mj->total * B * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
@@ -2328,34 +2369,65 @@ int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_gu
   return rc;
 }
 
-// Langevin refinement inside the job: one entry for plain (g, scenes NULL), many-scene (scenes) and composed (g) jobs.  kind 0 is the
-// matching plain entry, bit for bit.  Every refusal is a host check made before anything is staged or launched.
+// Langevin refinement and cost-gradient guidance inside the job: one body behind ramp_sample_mcmc (cg == nullptr) and ramp_sample_guided, for
+// plain (g, scenes NULL), many-scene (scenes) and composed (g) jobs.  kind 0 / no guide iteration anywhere is the matching plain entry, bit for
+// bit.  Every refusal is a host check made before anything is staged or launched; `who` names the entry in the message.
+static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
+                          const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
+                          const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  const int kind = m ? m->kind : 0;
+  RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");
+  if (g) CK(check_guidance(c, p, g, who));
+  McmcJob mj{kind, m ? m->n_inner : nullptr, m ? m->step_size : nullptr, m ? m->sigma : nullptr, 0};
+  if (kind != 0) {
+    RAMP_REQUIRE(p->predict_x0 == 0, w + "predict_x0 != 0 -- the combined network output is then x0, not a score: there is no density to correct");
+    RAMP_REQUIRE(p->n_steps > 0 && m->n_inner && m->step_size && m->sigma, w + "missing n_inner / step_size / sigma arrays");
+    for (int j = 0; j < p->n_steps; ++j) {
+      RAMP_REQUIRE(m->n_inner[j] >= 0 && m->n_inner[j] <= RAMP_MCMC_MAX_INNER, w + "n_inner outside 0 .. 16");
+      if (m->n_inner[j] == 0) continue;
+      RAMP_REQUIRE(std::isfinite(m->step_size[j]) && m->step_size[j] > 0.f, w + "step_size must be positive and finite where n_inner > 0");
+      RAMP_REQUIRE(std::isfinite(m->sigma[j]) && m->sigma[j] > 0.f, w + "sigma must be positive and finite where n_inner > 0");
+      mj.total += m->n_inner[j];
+    }
+    if (mj.total > 0 && p->noise_mode == 0) {
+      RAMP_REQUIRE(mcmc_noise, w + "null mcmc_noise (noise_mode 0 injects the inner steps' normals)");
+      RAMP_REQUIRE(kind != 2 || mcmc_u, w + "null mcmc_u (noise_mode 0 injects MALA's uniforms)");
+    }
+  }
+  GuideJob gj{cg};
+  int guide_total = 0;
+  if (cg) {
+    CK(check_cost_guide(cg, c->cfg.state_dim, who));
+    RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the guide kernel serves horizons up to 128");
+    RAMP_REQUIRE(scenes ? cg->n_scenes == scenes->n_scenes : cg->n_scenes == 1,
+                 w + "the guide's n_scenes must equal the scene batch's (1 without a scene batch)");
+    RAMP_REQUIRE(p->n_steps > 0 && cg->n_guide && cg->step, w + "missing n_guide / step arrays");
+    for (int j = 0; j < p->n_steps; ++j) {
+      RAMP_REQUIRE(cg->n_guide[j] >= 0 && cg->n_guide[j] <= RAMP_GUIDE_MAX_STEPS, w + "n_guide outside 0 .. RAMP_GUIDE_MAX_STEPS");
+      RAMP_REQUIRE(std::isfinite(cg->step[j]), w + "step must be finite");
+      guide_total += cg->n_guide[j];
+    }
+  }
+  // (kind 0, or no inner step anywhere: the plain job; no guide iteration anywhere: the unguided job)
+  const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g, mj.total > 0 ? &mj : nullptr, mcmc_noise, mcmc_u, accept_out,
+                            guide_total > 0 ? &gj : nullptr);
+  c->g_weight_cur = nullptr;
+  return rc;
+}
+
 int ramp_sample_mcmc(ramp_ctx* c, const ramp_sample_params* p, const ramp_mcmc_params* m, const ramp_guidance_rows* g,
                      const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise, const float* mcmc_u, float* chain_out,
                      float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p && m, "ramp_sample_mcmc: null argument");
-  RAMP_REQUIRE(m->kind >= 0 && m->kind <= 2, "ramp_sample_mcmc: kind must be 0 (off), 1 (ULA) or 2 (MALA)");
-  if (g) CK(check_guidance(c, p, g, "ramp_sample_mcmc"));
-  McmcJob mj{m->kind, m->n_inner, m->step_size, m->sigma, 0};
-  if (m->kind != 0) {
-    RAMP_REQUIRE(p->predict_x0 == 0, "ramp_sample_mcmc: predict_x0 != 0 -- the combined network output is then x0, not a score: there is no density to correct");
-    RAMP_REQUIRE(p->n_steps > 0 && m->n_inner && m->step_size && m->sigma, "ramp_sample_mcmc: missing n_inner / step_size / sigma arrays");
-    for (int j = 0; j < p->n_steps; ++j) {
-      RAMP_REQUIRE(m->n_inner[j] >= 0 && m->n_inner[j] <= RAMP_MCMC_MAX_INNER, "ramp_sample_mcmc: n_inner outside 0 .. 16");
-      if (m->n_inner[j] == 0) continue;
-      RAMP_REQUIRE(std::isfinite(m->step_size[j]) && m->step_size[j] > 0.f, "ramp_sample_mcmc: step_size must be positive and finite where n_inner > 0");
-      RAMP_REQUIRE(std::isfinite(m->sigma[j]) && m->sigma[j] > 0.f, "ramp_sample_mcmc: sigma must be positive and finite where n_inner > 0");
-      mj.total += m->n_inner[j];
-    }
-    if (mj.total > 0 && p->noise_mode == 0) {
-      RAMP_REQUIRE(mcmc_noise, "ramp_sample_mcmc: null mcmc_noise (noise_mode 0 injects the inner steps' normals)");
-      RAMP_REQUIRE(m->kind != 2 || mcmc_u, "ramp_sample_mcmc: null mcmc_u (noise_mode 0 injects MALA's uniforms)");
-    }
-  }
-  // (kind 0, or no inner step anywhere: the plain job)
-  const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g, mj.total > 0 ? &mj : nullptr, mcmc_noise, mcmc_u, accept_out);
-  c->g_weight_cur = nullptr;
-  return rc;
+  return sample_refined(c, p, nullptr, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_mcmc");
+}
+
+int ramp_sample_guided(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
+                       const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
+                       const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_guided: null argument");
+  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
 }
 
 // ---- receding-horizon replanning --------------------------------------------------------------------

@@ -107,6 +107,29 @@ int check_scene_batch(const ramp_scene_batch* sc, bool need_cloud, const char* w
   return 0;
 }
 
+// what ramp_sample_guided, ramp_guide_step and ramp_guide_cost (`who`) require of a cost guide on S-wide states, n_guide / step aside: host
+// checks only, made before anything is staged or launched
+int check_cost_guide(const ramp_cost_guide* cg, int S, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(cg, w + "null cost guide");
+  RAMP_REQUIRE((cg->point_dim == 2 || cg->point_dim == 3) && cg->point_dim <= S, w + "point_dim must be 2 or 3 and at most state_dim");
+  RAMP_REQUIRE(std::isfinite(cg->radius) && std::isfinite(cg->w_obs) && std::isfinite(cg->w_smooth) && std::isfinite(cg->w_acc) &&
+               std::isfinite(cg->max_norm), w + "radius, w_obs, w_smooth, w_acc and max_norm must be finite");
+  RAMP_REQUIRE(cg->w_obs == 0.0 || cg->radius > 0.0, w + "radius must be positive where w_obs != 0");
+  RAMP_REQUIRE(cg->n_scenes >= 1 && cg->cloud_offset_host && cg->cloud_offset_host[0] == 0, w + "bad cloud table (at least one scene, offsets from 0)");
+  for (int i = 0; i < cg->n_scenes; ++i)
+    RAMP_REQUIRE(cg->cloud_offset_host[i + 1] >= cg->cloud_offset_host[i], w + "cloud offsets must be non-decreasing");
+  RAMP_REQUIRE(cg->cloud_offset_host[cg->n_scenes] == 0 || cg->cloud_points, w + "null cloud_points with a non-empty table");
+  return 0;
+}
+// the kernel's arguments from a checked guide; the table pointers (cloud, cloud_off, scene) and the hard conditions are the caller's to fill
+GuideArgs guide_args(const ramp_cost_guide* cg, float* traj, int B, int H, int S) {
+  GuideArgs a; a.traj = traj; a.B = B; a.H = H; a.S = S; a.D = cg->point_dim; a.n_scenes = cg->n_scenes;
+  a.P_total = cg->cloud_offset_host[cg->n_scenes];
+  a.radius = (float)cg->radius; a.w_obs = (float)cg->w_obs; a.w_smooth = (float)cg->w_smooth; a.w_acc = (float)cg->w_acc;
+  a.max_norm = (float)cg->max_norm;
+  return a;
+}
 
 }  // namespace
 }  // namespace ramp

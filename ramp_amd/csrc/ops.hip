@@ -151,6 +151,46 @@ int ramp_apf_scenes(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf
   return rc;
 }
 
+// the guide's kernels on the caller's arrays: offsets | hard-condition indices go to the device in one block of their own (synchronises `stream`)
+static int guide_op(GuideArgs a, const ramp_cost_guide* cg, const int32_t* traj_scene, int32_t n_hard, const int32_t* hard_idx_host,
+                    const float* hard_val, double* terms_out, hipStream_t s) {
+  std::vector<int32_t> blk(cg->cloud_offset_host, cg->cloud_offset_host + cg->n_scenes + 1);
+  blk.insert(blk.end(), hard_idx_host, hard_idx_host + n_hard);
+  int32_t* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, blk.size() * 4));
+  int rc = 0;
+  if (hipMemcpy(d, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("guide: copy of the tables failed"); rc = -1; }
+  a.cloud = cg->cloud_points; a.cloud_off = d; a.scene = traj_scene;
+  a.hc.idx = d + cg->n_scenes + 1; a.hc.val = hard_val; a.hc.n = n_hard;
+  if (rc == 0) rc = terms_out ? launch_guide_cost(a, terms_out, s) : launch_guide_step(a, s);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(d);
+  return rc;
+}
+
+int ramp_guide_step(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene, int32_t n_iter,
+                    float step, int32_t n_hard, const int32_t* hard_idx_host, const float* hard_val, void* stream) {
+  RAMP_REQUIRE(traj && cg, "ramp_guide_step: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_step: bad dims (H up to 128)");
+  CK(check_cost_guide(cg, S, "ramp_guide_step"));
+  RAMP_REQUIRE(n_iter >= 0 && n_iter <= RAMP_GUIDE_MAX_STEPS, "ramp_guide_step: n_iter outside 0 .. RAMP_GUIDE_MAX_STEPS");
+  RAMP_REQUIRE(std::isfinite(step), "ramp_guide_step: step must be finite");
+  RAMP_REQUIRE(n_hard >= 0 && n_hard <= 256 && (n_hard == 0 || (hard_idx_host && hard_val)), "ramp_guide_step: bad hard conditions");
+  for (int j = 0; j < n_hard; ++j) RAMP_REQUIRE(hard_idx_host[j] >= 0 && hard_idx_host[j] < H, "ramp_guide_step: hard index out of range");
+  if (n_iter == 0) return 0;
+  GuideArgs a = guide_args(cg, traj, B, H, S);
+  a.n_iter = n_iter; a.step = step;
+  return guide_op(a, cg, traj_scene, n_hard, hard_idx_host, hard_val, nullptr, as_stream(stream));
+}
+
+int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene,
+                    double* terms_out, void* stream) {
+  RAMP_REQUIRE(traj && cg && terms_out, "ramp_guide_cost: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_cost: bad dims (H up to 128)");
+  CK(check_cost_guide(cg, S, "ramp_guide_cost"));
+  return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
+}
+
 int ramp_apf_dynamic(float* traj, int32_t B, int32_t H, int32_t S, const double* points, int32_t n_points,
                      double thr_query, double thr_force, double strength, int32_t window, int32_t affected,
                      const float* goal, const int32_t* enable, void* stream) {

@@ -120,6 +120,64 @@ def mcmc_tables(mcmc: dict, steps, alphas_cumprod) -> dict:
     return {'kind': _lib.MCMC_KINDS[kind], 'n_inner': K, 'step_size': eta, 'sigma': sigma, 'total': int(sum(K))}
 
 
+GUIDE_KEYS = {'cloud', 'clouds', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'step', 'n_steps', 't_start', 'max_norm', 'scale_by_variance'}
+
+
+def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
+    """The host tables of a job's cost-gradient guidance (``cost_guide=`` of run_inference*; ramp_cost_guide) for the job whose iterations
+    evaluate the network timesteps ``steps`` (the DDPM or the DDIM list), host data only -- the clouds are not looked at here.
+
+      cloud | clouds     the guide's obstacle points, (P, d) or (No, Np, d), d = 2 or 3; ``clouds``: one per scene of a scene / composed job
+      radius             r of the obstacle term (required, > 0, unless w_obs = 0)
+      w_obs, w_smooth, w_acc   weights of the three terms (default 1, 0, 0)
+      step               step size (required), or one per iteration
+      n_steps            guide iterations per loop iteration (default 1), or one count per iteration (0 .. 16)
+      t_start            only iterations with t < t_start are guided (default inf: all)
+      max_norm           clip of the trajectory's gradient norm, 0 = off (default)
+      scale_by_variance  multiply the step of iteration j by posterior_variance[t_j] (default False)
+
+    Returns ``{'n_guide': [...], 'step': [...], 'radius', 'w_obs', 'w_smooth', 'w_acc', 'max_norm', 'total': sum n_guide}``."""
+    if not isinstance(cost_guide, dict):
+        raise TypeError("cost_guide= takes a dict(cloud= | clouds=, radius=, step=, w_obs=, w_smooth=, w_acc=, n_steps=, t_start=, max_norm=, "
+                        "scale_by_variance=)")
+    unknown = set(cost_guide) - GUIDE_KEYS
+    if unknown:
+        raise ValueError(f"cost_guide=: unknown keys {sorted(unknown)}")
+    if ('cloud' in cost_guide) == ('clouds' in cost_guide):
+        raise ValueError("cost_guide=: exactly one of cloud= and clouds=")
+    n = len(steps)
+    out = {'radius': float(cost_guide.get('radius', 0.0)), 'w_obs': float(cost_guide.get('w_obs', 1.0)),
+           'w_smooth': float(cost_guide.get('w_smooth', 0.0)), 'w_acc': float(cost_guide.get('w_acc', 0.0)),
+           'max_norm': float(cost_guide.get('max_norm', 0.0))}
+    if not all(np.isfinite(v) for v in out.values()):
+        raise ValueError("cost_guide=: radius, w_obs, w_smooth, w_acc and max_norm must be finite")
+    if out['w_obs'] != 0.0 and not out['radius'] > 0.0:
+        raise ValueError("cost_guide=: radius must be positive where w_obs != 0")
+    if 'step' not in cost_guide:
+        raise ValueError("cost_guide=: step= is required")
+    K = cost_guide.get('n_steps', 1)
+    K = [int(K)] * n if np.isscalar(K) else [int(k) for k in K]
+    if len(K) != n:
+        raise ValueError(f"cost_guide n_steps: {len(K)} entries for {n} iterations")
+    if any(k < 0 or k > _lib.GUIDE_MAX_STEPS for k in K):
+        raise ValueError(f"cost_guide n_steps must lie in 0 .. {_lib.GUIDE_MAX_STEPS} per iteration")
+    t_start = float(cost_guide.get('t_start', float('inf')))
+    if np.isnan(t_start):
+        raise ValueError("cost_guide=: t_start is NaN")
+    K = [k if t < t_start else 0 for k, t in zip(K, steps)]
+    st = cost_guide['step']
+    st = [float(st)] * n if np.isscalar(st) else [float(v) for v in st]
+    if len(st) != n:
+        raise ValueError(f"cost_guide step: {len(st)} entries for {n} iterations")
+    if cost_guide.get('scale_by_variance', False):
+        pv = np.asarray(posterior_variance.detach().cpu().numpy() if torch.is_tensor(posterior_variance) else posterior_variance, dtype=np.float64)
+        st = [v * float(pv[t]) for v, t in zip(st, steps)]
+    if not all(np.isfinite(v) for v in st):
+        raise ValueError("cost_guide=: step sizes must be finite")
+    out.update(n_guide=K, step=st, total=int(sum(K)))
+    return out
+
+
 class _GaussianDiffusionBase(nn.Module):
     _default_cfg_weight = 2.0
 
@@ -385,6 +443,21 @@ class _GaussianDiffusionBase(nn.Module):
         mp.n_inner, mp.step_size, mp.sigma = arrays.i32(tab['n_inner']), arrays.f32(tab['step_size']), arrays.f32(tab['sigma'])
         return mp
 
+    def _fill_guide(self, arrays: _HostArrays, tab: dict, cost_guide: dict, scene_job: Optional[dict]):
+        """ramp_cost_guide from the tables of ``guide_tables`` and the guide's clouds: one for a plain job, one per scene for a scene /
+        composed job (a single ``cloud`` then serves every scene)."""
+        from .guide import cloud_table, fill_cost_guide
+        n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
+        clouds = [cost_guide['cloud']] * n_scenes if 'cloud' in cost_guide else list(cost_guide['clouds'])
+        if len(clouds) != n_scenes:
+            raise ValueError(f"cost_guide clouds: {len(clouds)} entries for {n_scenes} scene(s)")
+        points, off, d = cloud_table(clouds, self._device())
+        if d > self.state_dim:
+            raise ValueError(f"cost_guide: {d}-D points on {self.state_dim}-wide states")
+        cg = fill_cost_guide(arrays.keep(points), arrays.keep(off), d, tab)
+        cg.n_guide, cg.step = arrays.i32(tab['n_guide']), arrays.f32(tab['step'])
+        return cg
+
     def _run_guarded(self, job):
         """Run ``job`` under the fp16x3 range-guard policy: a flagged result is discarded and the same job (same noise) repeated, never
         a silently degraded answer.  First IN fp16x3 with the evaluation that raised the guard run as a calibrating one (range-free,
@@ -429,14 +502,16 @@ class _GaussianDiffusionBase(nn.Module):
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
                 return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None,
-                mcmc: Optional[dict] = None):
+                mcmc: Optional[dict] = None, cost_guide: Optional[dict] = None):
         """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
         (``ramp_sample_scenes``); ``obstacle_pts`` is not read then.  ``guidance`` (with a ``scene_job``): a composed job
         (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``.
         ``mcmc``: Langevin refinement inside the job (``ramp_sample_mcmc``, the one entry for all three kinds of job; ``mcmc_tables``);
-        the accept flags land in ``self.last_mcmc``."""
+        the accept flags land in ``self.last_mcmc``.  ``cost_guide``: cost-gradient guidance inside the job (``ramp_sample_guided``, the
+        same one entry with the guide added; ``guide_tables``)."""
         m = self.model
         tab = self._mcmc_tables(mcmc, steps) if mcmc is not None else None
+        gtab = guide_tables(cost_guide, steps, self.posterior_variance) if cost_guide is not None else None
         dev = self._device()
         H, S = m.n_support_points, self.state_dim
         n_steps = len(steps)
@@ -469,6 +544,7 @@ class _GaussianDiffusionBase(nn.Module):
         chain = torch.empty((n_steps + 1, B, H, S), device=dev, dtype=torch.float32) if return_chain else None
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
         mp = z_in = u_in = accept = None
+        cg = self._fill_guide(arrays, gtab, cost_guide, scene_job) if gtab is not None else None
         if tab is not None:
             mp = self._fill_mcmc(arrays, tab)
             accept = torch.zeros((tab['total'], B), device=dev, dtype=torch.int32)
@@ -492,7 +568,13 @@ class _GaussianDiffusionBase(nn.Module):
             lib = _lib.load()
 
             def job():
-                if mp is not None:
+                if cg is not None:
+                    _lib.check(lib.ramp_sample_guided(m.ctx(), C.byref(p), C.byref(cg), C.byref(mp) if mp is not None else None,
+                                                      C.byref(rows) if rows is not None else None,
+                                                      C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
+                                                      _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
+                                                      _lib.current_stream()), "ramp_sample_guided")
+                elif mp is not None:
                     _lib.check(lib.ramp_sample_mcmc(m.ctx(), C.byref(p), C.byref(mp), C.byref(rows) if rows is not None else None,
                                                     C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
                                                     _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
@@ -531,7 +613,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
-                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, **sample_kwargs):
+                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, cost_guide=None, **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
@@ -539,6 +621,8 @@ class _GaussianDiffusionBase(nn.Module):
         if not self._is_fused_ddpm_step(sample_fn):
             if mcmc is not None:
                 raise NotImplementedError("mcmc= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
+            if cost_guide is not None:
+                raise NotImplementedError("cost_guide= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if scene_job is not None:
                 raise NotImplementedError("run_inference_scenes runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
                                           "scene's batch at a time -- use run_inference per scene")
@@ -560,7 +644,7 @@ class _GaussianDiffusionBase(nn.Module):
                for j in range(len(steps))]
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
-                                    cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc)
+                                    cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -602,7 +686,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
-                           guidance=None, mcmc=None, **sample_kwargs):
+                           guidance=None, mcmc=None, cost_guide=None, **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
         B = shape[0]
@@ -611,7 +695,7 @@ class _GaussianDiffusionBase(nn.Module):
         apf = [1 if (self.APF and self._supports_apf and j >= self.apf_ddim['start']) else 0 for j in range(len(steps))]
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
-                                    return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc)
+                                    return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -624,6 +708,8 @@ class _GaussianDiffusionBase(nn.Module):
         if self.ddim:
             if sample_kwargs.get('mcmc') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
                 raise NotImplementedError("mcmc= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
+            if sample_kwargs.get('cost_guide') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
+                raise NotImplementedError("cost_guide= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
             for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
                 sample_kwargs.pop(k, None)      # silently ignored by the reference's DDIM loop
             return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized,
