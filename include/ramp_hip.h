@@ -371,6 +371,66 @@ int ramp_guide_step(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cos
  * Synchronises `stream`. */
 int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene,
                     double* terms_out, void* stream);
+/* ---- resampling trajectories by cost inside the sampling job (SMC steering) ----
+ * A job draws B candidates per scene and ranks them when it has finished; sequential Monte Carlo steering (Feynman-Kac steering, twisted SMC
+ * for diffusion) weights every candidate at chosen noise levels by a potential on the job's current clean estimate and resamples within the
+ * scene, so that the remaining evaluations go to candidates that are still promising.
+ * Groups: the B trajectories are partitioned into n_groups contiguous groups by the host table group_first_host (n_groups + 1): [0] = 0,
+ * strictly increasing, [n_groups] = B.  A plain job has one group of B, a many-scene or composed job one group per scene.  Resampling never
+ * crosses a group.  Per trajectory the job keeps logw and c_prev (fp64, both 0 at the start of the job).
+ * Event: on iteration j with resample[j] != 0,
+ *   1. c_b = w_obs C_obs + w_smooth C_smooth + w_acc C_acc, the three terms exactly what ramp_guide_cost returns on the array the cost guide
+ *      works on (the posterior mean on DDPM, x0 on DDIM) as it stands after the APF hook and the guide, no hard conditions applied, before
+ *      the noise / DDIM update; the products and the two sums in fp64, left to right.  Clouds and scalars come from rs->cost (a ramp_cost_guide
+ *      of the event's own, whose n_guide, step and max_norm are not read; it may be the job's guide table).
+ *   2. logw_b += -lambda[j] (c_b - c_prev_b), then c_prev_b = c_b: the difference potential -- with constant lambda the product of an
+ *      unresampled lineage telescopes to exp(-lambda c).  A non-finite logw_b counts as -inf (weight 0).
+ *   3. after the iteration's update and hard conditioning, per group of size n: W_i = exp(logw_i - max logw) / sum, ESS = 1 / sum W_i^2.
+ *      Every weight 0: ESS = 0, identity, nothing changes.
+ *   4. ESS < ess_frac n (ess_frac in [0, 2]: 0 never, above 1 always): systematic resampling with ONE uniform u per (event, group).  cum =
+ *      the inclusive fp64 prefix sums of W with cum_{n-1} taken as 1; a_i = min(n - 1, #{k : cum_k <= (i + u) / n}); then x[i] <- x[a_i] for
+ *      the whole (H, S) row, c_prev[i] <- c[a_i], logw <- 0 in that group.  Otherwise the ancestors are the identity and x, logw stay.
+ *   5. with chain_out, block j + 1 is the state after the event.
+ * The order of the fp64 sums (max, sum, prefix sums, ESS) is the implementation's; nothing else is free.
+ * Outputs per event k (events in job order), any of them NULL: ancestor_out device int32 (n_events, B), indices within the batch; ess_out
+ * device double (n_events, n_groups); cost_out device double (n_events, B), the c_b of that event; logw_out device double (B) at the end of
+ * the job.
+ * Randomness.  noise_mode 0: resample_u is a device (n_events, n_groups) float array in (0, 1).  noise_mode 1: u comes from the job's Philox
+ * stream behind everything a job draws today; in the notation of ramp_sample_mcmc above, with G = groups_total (0 means n_groups) and
+ * g = group0 + the local group index,
+ *   uniform of (event k, global group g) = ((r >> 9) + 0.5) 2^-23, r = output 0 of group (n_steps + 1 + K) T H S / 4 + K T + k G + g
+ * (the K T groups of MALA's uniforms are reserved whether or not the job is MALA).  A repeat of a flagged job replays the same uniforms.
+ * Group boundaries and u are data in buffers of the context that the captured graph reads: other boundaries with equal n_groups replay the same
+ * graph and are honoured.  n_groups, the resample[] flags, lambda[], ess_frac and the potential's scalars are part of the graph key. */
+#define RAMP_RESAMPLE_MAX_EVENTS 64
+typedef struct ramp_resample_params {
+  int32_t n_groups;
+  int32_t group0;                     /* Philox: global index of this call's first group (0 for a whole job)       */
+  int32_t groups_total;               /* Philox: groups of the whole job; 0 = n_groups                              */
+  int32_t reserved;
+  const int32_t* group_first_host;    /* host (n_groups + 1): [0] = 0, strictly increasing, [n_groups] = B          */
+  const int32_t* resample;            /* host (n_steps): != 0 = an event on iteration j; at most 64 events          */
+  const double* lambda;               /* host (n_steps): the potential's inverse temperature on iteration j         */
+  double ess_frac;                    /* in [0, 2]                                                                  */
+  const ramp_cost_guide* cost;        /* clouds and scalars of the cost; n_guide, step and max_norm are not read    */
+} ramp_resample_params;
+/* ramp_sample_guided plus the resampling events: the one entry for plain, many-scene, composed, MCMC and guided jobs.  rs == NULL, or no
+ * flag set, IS ramp_sample_guided, bit for bit.  rs->cost->n_scenes must equal scenes->n_scenes, or be 1 with scenes == NULL.
+ * Refused on the host before any launch (non-zero, "ramp_sample_steered" in ramp_last_error): a malformed group table; ess_frac outside
+ * [0, 2] or non-finite; a missing or non-finite lambda; more than RAMP_RESAMPLE_MAX_EVENTS events; p->ddim != 0 without MCMC inner steps
+ * (m->kind != 0 and sum n_inner > 0: eta = 0 DDIM never separates duplicates); p->predict_x0 != 0; what the cost table's own checks refuse
+ * (see ramp_sample_guided), H > 128; group0 / groups_total that do not hold the call's groups; NULL resample_u in noise_mode 0; and what
+ * ramp_sample_guided refuses.  ramp_replan / ramp_replan_episodes take no resampling. */
+int ramp_sample_steered(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_resample_params* rs, const ramp_cost_guide* cg,
+                        const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                        const float* mcmc_noise, const float* mcmc_u, const float* resample_u, float* chain_out, float* x_out,
+                        int32_t* accept_out, int32_t* ancestor_out, double* ess_out, double* cost_out, double* logw_out, void* stream);
+/* steps 3 and 4 alone on (B, H, S) trajectories in place (H S a multiple of 4): logw device double (B), c_prev device double (B) or NULL, u
+ * device float (n_groups), ancestor_out device int32 (B) or NULL, ess_out device double (n_groups) or NULL.  Refused with
+ * "ramp_resample_groups": a malformed group table, ess_frac outside [0, 2] or non-finite, null x / logw / u, H S no multiple of 4.
+ * Synchronises `stream`. */
+int ramp_resample_groups(float* x, int32_t B, int32_t H, int32_t S, double* logw, double* c_prev, const int32_t* group_first_host,
+                         int32_t n_groups, const float* u, double ess_frac, int32_t* ancestor_out, double* ess_out, void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from

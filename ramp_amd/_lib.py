@@ -66,6 +66,17 @@ class RampCostGuide(C.Structure):
                 ("n_guide", c_i32p), ("step", c_f32p)]
 
 
+RESAMPLE_MAX_EVENTS = 64   # RAMP_RESAMPLE_MAX_EVENTS
+c_f64p = C.POINTER(C.c_double)
+
+
+class RampResampleParams(C.Structure):
+    """ramp_resample_params: the resampling events of a sampling job (ramp_sample_steered)."""
+    _fields_ = [("n_groups", C.c_int32), ("group0", C.c_int32), ("groups_total", C.c_int32), ("reserved", C.c_int32),
+                ("group_first_host", c_i32p), ("resample", c_i32p), ("lambda_", c_f64p), ("ess_frac", C.c_double),
+                ("cost", C.POINTER(RampCostGuide))]
+
+
 class RampSampleParams(C.Structure):
     _fields_ = [("B", C.c_int32), ("n_rp", C.c_int32), ("n_steps", C.c_int32), ("ddim", C.c_int32),
                 ("w0", C.c_double), ("w1", C.c_double),
@@ -159,6 +170,10 @@ PROTOTYPES = {
                                    C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
     "ramp_sample_guided": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampCostGuide), C.POINTER(RampMcmcParams),
                                      C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
+    "ramp_sample_steered": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampResampleParams), C.POINTER(RampCostGuide),
+                                      C.POINTER(RampMcmcParams), C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch)] + [C.c_void_p] * 12),
+    "ramp_resample_groups": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, c_i32p, C.c_int32, C.c_void_p,
+                                       C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_guide_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_int32, C.c_float,
                                   C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
     "ramp_guide_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_void_p, C.c_void_p]),

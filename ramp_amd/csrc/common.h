@@ -9,4 +9,5 @@
 #include "args_conv.h"
 #include "args_rows.h"
 #include "args_sampler.h"
+#include "args_resample.h"
 #include "args_scene.h"

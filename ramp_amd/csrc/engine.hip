@@ -149,6 +149,14 @@ struct ramp_ctx {
   // copied here before the launch -- the captured graph reads these buffers, so the clouds' contents are data of a replay.  The iteration
   // counts, step sizes and the five scalars are kernel arguments, hence part of the graph key
   float* cg_cloud = nullptr; size_t cg_cloud_cap = 0; int* cg_off = nullptr; size_t cg_off_cap = 0;
+  // resampling inside a sampling job (ramp_sample_steered): per trajectory {logw | c_prev | cum | tmp} (4 B doubles) and the cost terms (3 B), the
+  // gather's second buffer, and per event the ancestors, ESS, costs and uniforms; the group table, the uniforms (noise_mode 0) and the potential's
+  // clouds are copied here before the launch -- data of a replay.  Flags, lambda, ess_frac and the potential's scalars are in the graph key
+  double* rs_state = nullptr; size_t rs_state_cap = 0; double* rs_terms = nullptr; size_t rs_terms_cap = 0;
+  float* rs_xtmp = nullptr; size_t rs_xtmp_cap = 0;
+  int* rs_anc = nullptr; size_t rs_anc_cap = 0; double* rs_ess = nullptr; size_t rs_ess_cap = 0; double* rs_cost = nullptr; size_t rs_cost_cap = 0;
+  float* rs_u = nullptr; size_t rs_u_cap = 0; int* rs_gf = nullptr; size_t rs_gf_cap = 0;
+  float* rs_cloud = nullptr; size_t rs_cloud_cap = 0; int* rs_off = nullptr; size_t rs_off_cap = 0;
   // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
   // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
   hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
@@ -1975,12 +1983,20 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
 // The cost guide of a job (ramp_sample_guided), checked by the entry; only a guide with n_guide > 0 somewhere becomes one
 struct GuideJob { const ramp_cost_guide* cg; };
+// The resampling events of a job (ramp_sample_steered), checked by the entry; only a table with a flag set somewhere becomes one.  The injected
+// uniforms (noise_mode 0) and the four outputs travel with it
+struct ResampleJob {
+  const ramp_resample_params* rs; int n_events;
+  const float* u; int32_t* ancestor_out; double* ess_out; double* cost_out; double* logw_out;
+};
 
 // mj != nullptr: K_j = mj->n_inner[j] inner steps (propose -> one evaluation at x' -> accept) follow the evaluation of iteration j, and the reverse
 // step uses the cached combined gradient of the state they ended on; every evaluation, inner ones included, is one link of the calibration chain
 // gj != nullptr: on iteration j with n_guide[j] > 0 ONE launch runs that many guide iterations on the posterior mean (DDPM) / x0 (DDIM), behind the APF hook
+// rj != nullptr: on iteration j with resample[j] != 0 the cost of that array (behind the guide) updates the log-weights, and at the end of the
+// iteration every group is resampled: three launches and the copy back, unconditional (identity where nothing resampled), so the graph has no branch
 static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1,
-                       const McmcJob* mj = nullptr, const GuideJob* gj = nullptr) {
+                       const McmcJob* mj = nullptr, const GuideJob* gj = nullptr, const ResampleJob* rj = nullptr) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -2016,6 +2032,43 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     if (!gj || gj->cg->n_guide[j] <= 0) return 0;
     ga.traj = target; ga.n_iter = gj->cg->n_guide[j]; ga.step = gj->cg->step[j];
     LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_step(ga, s));
+    return 0;
+  };
+  GuideArgs ra;
+  int ke = 0;      // events so far
+  if (rj) {
+    const ramp_resample_params* rs = rj->rs;
+    ra = guide_args(rs->cost, nullptr, B, H, S);
+    ra.cloud = c->rs_cloud; ra.cloud_off = c->rs_off; ra.scene = sc ? c->s_traj_scene : nullptr;
+    hipLaunchKernelGGL(zero_words_kernel, dim3((4 * B + 255) / 256), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->rs_state), 4 * B);      // logw = c_prev = 0
+    RAMP_HIP_CHECK(hipGetLastError());
+    if (p->noise_mode == 1) {      // one uniform per (event, group): behind the inner steps' draws, see ramp_resample_params in ramp_hip.h
+      const long T = p->philox_total > 0 ? (long)p->philox_total : (long)B, K = mj ? mj->total : 0;
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_philox_uniform_sharded(c->rs_u, rj->n_events, rs->n_groups, ((long)p->n_steps + 1 + K) * T * (long)(HS / 4) + K * T,
+                                                                 (long)rs->group0, rs->groups_total > 0 ? (long)rs->groups_total : (long)rs->n_groups, c->s_philox, s));
+    }
+  }
+  // steps 1 and 2 of the event of iteration j, if it has one: the cost of `target` and the weight update
+  auto weigh_at = [&](int j, float* target) -> int {
+    if (!rj || !rj->rs->resample[j]) return 0;
+    ra.traj = target;
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_cost(ra, c->rs_terms, s));
+    ResampleWeightArgs w; w.terms = c->rs_terms; w.logw = c->rs_state; w.c_prev = c->rs_state + B; w.cost_out = c->rs_cost + (size_t)ke * B; w.B = B;
+    w.w_obs = rj->rs->cost->w_obs; w.w_smooth = rj->rs->cost->w_smooth; w.w_acc = rj->rs->cost->w_acc; w.lambda = rj->rs->lambda[j];
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_resample_weights(w, s));
+    return 0;
+  };
+  // steps 3 to 5, on the state the iteration ended on
+  auto resample_at = [&](int j, float* chain_j) -> int {
+    if (!rj || !rj->rs->resample[j]) return 0;
+    ResampleGroupsArgs g; g.logw = c->rs_state; g.c_prev = c->rs_state + B; g.cum = c->rs_state + 2 * (size_t)B; g.tmp = c->rs_state + 3 * (size_t)B;
+    g.group_first = c->rs_gf; g.u = c->rs_u + (size_t)ke * rj->rs->n_groups; g.ess_frac = rj->rs->ess_frac;
+    g.ancestor = c->rs_anc + (size_t)ke * B; g.ess_out = c->rs_ess + (size_t)ke * rj->rs->n_groups; g.B = B; g.n_groups = rj->rs->n_groups;
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_resample_groups(g, s));
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_resample_gather(c->s_x, g.ancestor, c->rs_xtmp, B, (int)HS, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_x, c->rs_xtmp, n * 4, hipMemcpyDeviceToDevice, s));
+    if (chain_j) RAMP_HIP_CHECK(hipMemcpyAsync(chain_j, c->rs_xtmp, n * 4, hipMemcpyDeviceToDevice, s));
+    ++ke;
     return 0;
   };
   if (c->gemm_mode == 2) {
@@ -2091,6 +2144,7 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
       if (apf) { ap.traj = c->s_mean; for (int q = 0; q < std::max(1, p->apf.passes); ++q) LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); }
       CK(guide_at(j, c->s_mean));
+      CK(weigh_at(j, c->s_mean));
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddpm_finish(c->s_mean, c->s_noise + (size_t)(j + 1) * n, p->stdv[j], p->noise_scale ? p->noise_scale[j] : 1.f, p->use_noise[j],
                             hc, c->s_x, chain_j, B, H, S, s));
     } else {
@@ -2101,9 +2155,11 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
         for (int q = 0; q < std::max(1, p->apf.passes); ++q) { LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x0, hc, B, H, S, s)); }
       }
       CK(guide_at(j, c->s_x0));      // (the hard conditioning that follows is ddim_finish's own)
+      CK(weigh_at(j, c->s_x0));
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], hc,
                             c->s_x, chain_j, B, H, S, s));
     }
+    CK(resample_at(j, chain_j));
   }
   return 0;
 }
@@ -2158,9 +2214,11 @@ static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, 
 // mj != nullptr: Langevin refinement (ramp_sample_mcmc; its arguments are checked there) -- mcmc_noise / mcmc_u the injected draws (noise_mode 0),
 // accept_out (sum K, B) the accept flags
 // gj != nullptr: cost-gradient guidance (ramp_sample_guided; its arguments are checked there)
+// rj != nullptr: resampling events (ramp_sample_steered; its arguments are checked there)
 static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
                       void* stream, const ramp_guidance_rows* g = nullptr, const McmcJob* mj = nullptr, const float* mcmc_noise = nullptr,
-                      const float* mcmc_u = nullptr, int32_t* accept_out = nullptr, const GuideJob* gj = nullptr) {
+                      const float* mcmc_u = nullptr, int32_t* accept_out = nullptr, const GuideJob* gj = nullptr,
+                      const ResampleJob* rj = nullptr) {
   RAMP_REQUIRE(c && p, "null argument");
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
@@ -2223,6 +2281,27 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     }
   }
+  int rj_points = 0;
+  if (rj) {      // the potential's own cloud table, the group table and (noise_mode 0) the uniforms
+    const ramp_resample_params* rs = rj->rs;
+    const ramp_cost_guide* rc = rs->cost;
+    const size_t ne = (size_t)rj->n_events, ng = (size_t)rs->n_groups;
+    rj_points = rc->cloud_offset_host[rc->n_scenes];
+    CK(grow(c, c->rs_state, c->rs_state_cap, 4 * (size_t)B)); CK(grow(c, c->rs_terms, c->rs_terms_cap, 3 * (size_t)B));
+    CK(grow(c, c->rs_xtmp, c->rs_xtmp_cap, n));
+    CK(grow(c, c->rs_anc, c->rs_anc_cap, ne * B)); CK(grow(c, c->rs_ess, c->rs_ess_cap, ne * ng)); CK(grow(c, c->rs_cost, c->rs_cost_cap, ne * B));
+    CK(grow(c, c->rs_u, c->rs_u_cap, ne * ng)); CK(grow(c, c->rs_gf, c->rs_gf_cap, ng + 1));
+    CK(grow(c, c->rs_cloud, c->rs_cloud_cap, std::max<size_t>(4, (size_t)rj_points * rc->point_dim)));
+    CK(grow(c, c->rs_off, c->rs_off_cap, (size_t)rc->n_scenes + 1));
+    if (rj_points) RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_cloud, rc->cloud_points, (size_t)rj_points * rc->point_dim * 4, hipMemcpyDeviceToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_off, rc->cloud_offset_host, ((size_t)rc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_gf, rs->group_first_host, (ng + 1) * 4, hipMemcpyHostToDevice, s));
+    if (p->noise_mode == 0) RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_u, rj->u, ne * ng * 4, hipMemcpyDeviceToDevice, s));
+    if (sc && !sc_apf && !gj) {
+      CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));
+      RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+    }
+  }
   std::vector<float> g_host;      // the weights on the host: part of the canonical calibration's key below
   if (g) {
     const size_t nw = (size_t)B * p->n_rp;
@@ -2278,6 +2357,14 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     const double sc5[5] = {cg->radius, cg->w_obs, cg->w_smooth, cg->w_acc, cg->max_norm}; key.put(sc5, 5);
     key.put(cg->n_guide, p->n_steps); key.put(cg->step, p->n_steps);
   }
+  if (rj) {      // (the rs_* buffers exist only for such a job; flags, lambda, ess_frac, the scalars and the Philox group fields are kernel arguments)
+    const ramp_resample_params* rs = rj->rs;
+    const ramp_cost_guide* rc = rs->cost;
+    const int tag[9] = {0x52534d50 /* "RSMP" */, rs->n_groups, rj->n_events, rs->group0, rs->groups_total, rc->point_dim, rc->n_scenes, rj_points, sc ? 1 : 0};
+    key.put(tag, 9);
+    const double sc5[5] = {rs->ess_frac, rc->radius, rc->w_obs, rc->w_smooth, rc->w_acc}; key.put(sc5, 5);
+    key.put(rs->resample, p->n_steps); key.put(rs->lambda, p->n_steps);
+  }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
@@ -2315,7 +2402,7 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
   c->last_job_steps = h3 ? n_evals : 0;
   if (!p->use_graph) {
-    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj, gj));
+    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj, gj, rj));
   } else {
     if (key.bytes != c->graph_key) { drop_graphs(c->s_graph, 3); c->graph_key = key.bytes; c->graph_rerun_key.clear(); }
     hipGraphExec_t* slot = &c->s_graph[steady ? 1 : 0];
@@ -2325,9 +2412,16 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       if (rk.bytes != c->graph_rerun_key) drop_graphs(slot, 1);
       c->graph_rerun_key = rk.bytes;
     }
-    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj, gj); }));
+    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj, gj, rj); }));
   }
   if (mj && accept_out) RAMP_HIP_CHECK(hipMemcpyAsync(accept_out, c->m_flag, (size_t)mj->total * B * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (rj) {
+    const size_t ne = (size_t)rj->n_events, ng = (size_t)rj->rs->n_groups;
+    if (rj->ancestor_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->ancestor_out, c->rs_anc, ne * B * sizeof(int), hipMemcpyDeviceToDevice, s));
+    if (rj->ess_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->ess_out, c->rs_ess, ne * ng * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (rj->cost_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->cost_out, c->rs_cost, ne * B * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (rj->logw_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->logw_out, c->rs_state, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s));
+  }
   if (chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
   if (x_out) RAMP_HIP_CHECK(hipMemcpyAsync(x_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
@@ -2374,7 +2468,8 @@ int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_gu
 // bit.  Every refusal is a host check made before anything is staged or launched; `who` names the entry in the message.
 static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
                           const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
-                          const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who) {
+                          const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who,
+                          ResampleJob* rj = nullptr) {
   const std::string w = std::string(who) + ": ";
   const int kind = m ? m->kind : 0;
   RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");
@@ -2409,9 +2504,28 @@ static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_c
       guide_total += cg->n_guide[j];
     }
   }
+  if (rj) {      // (the entry hands over only a table with a flag set)
+    const ramp_resample_params* rs = rj->rs;
+    RAMP_REQUIRE(resample_group_table_fault(rs->group_first_host, rs->n_groups, p->B) == 0,
+                 w + "malformed group table (n_groups >= 1, [0] = 0, strictly increasing, [n_groups] = B)");
+    RAMP_REQUIRE(resample_ess_frac_ok(rs->ess_frac), w + "ess_frac must be finite and lie in [0, 2]");
+    RAMP_REQUIRE(rs->lambda, w + "missing lambda array");
+    for (int j = 0; j < p->n_steps; ++j) RAMP_REQUIRE(std::isfinite(rs->lambda[j]), w + "lambda must be finite");
+    RAMP_REQUIRE(rj->n_events <= RAMP_RESAMPLE_MAX_EVENTS, w + "more than RAMP_RESAMPLE_MAX_EVENTS events");
+    RAMP_REQUIRE(!p->ddim || mj.total > 0, w + "DDIM (eta = 0) never separates duplicates: resampling needs MCMC inner steps there");
+    RAMP_REQUIRE(p->predict_x0 == 0, w + "predict_x0 != 0 is not served with resampling");
+    CK(check_cost_guide(rs->cost, c->cfg.state_dim, who));
+    RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the cost kernel serves horizons up to 128");
+    RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the gather moves four elements per access)");
+    RAMP_REQUIRE(scenes ? rs->cost->n_scenes == scenes->n_scenes : rs->cost->n_scenes == 1,
+                 w + "the potential's n_scenes must equal the scene batch's (1 without a scene batch)");
+    RAMP_REQUIRE(rs->group0 >= 0 && rs->groups_total >= 0 && (rs->groups_total == 0 ? rs->group0 == 0 : rs->group0 + rs->n_groups <= rs->groups_total),
+                 w + "group0 + n_groups must lie inside groups_total");
+    RAMP_REQUIRE(p->noise_mode != 0 || rj->u, w + "null resample_u (noise_mode 0 injects the events' uniforms)");
+  }
   // (kind 0, or no inner step anywhere: the plain job; no guide iteration anywhere: the unguided job)
   const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g, mj.total > 0 ? &mj : nullptr, mcmc_noise, mcmc_u, accept_out,
-                            guide_total > 0 ? &gj : nullptr);
+                            guide_total > 0 ? &gj : nullptr, rj);
   c->g_weight_cur = nullptr;
   return rc;
 }
@@ -2428,6 +2542,20 @@ int ramp_sample_guided(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost
                        const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_guided: null argument");
   return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
+}
+
+// The one entry for every kind of job: ramp_sample_guided plus the resampling events.  rs == NULL or no flag set is that entry itself
+int ramp_sample_steered(ramp_ctx* c, const ramp_sample_params* p, const ramp_resample_params* rs, const ramp_cost_guide* cg,
+                        const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                        const float* mcmc_noise, const float* mcmc_u, const float* resample_u, float* chain_out, float* x_out,
+                        int32_t* accept_out, int32_t* ancestor_out, double* ess_out, double* cost_out, double* logw_out, void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_steered: null argument");
+  ResampleJob rj{rs, 0, resample_u, ancestor_out, ess_out, cost_out, logw_out};
+  if (rs && rs->resample) for (int j = 0; j < p->n_steps; ++j) rj.n_events += rs->resample[j] != 0;
+  if (rj.n_events == 0)
+    return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
+  RAMP_REQUIRE(rs->cost, "ramp_sample_steered: null cost table");
+  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_steered", &rj);
 }
 
 // ---- receding-horizon replanning --------------------------------------------------------------------

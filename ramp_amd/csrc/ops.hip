@@ -191,6 +191,37 @@ int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ra
   return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
 }
 
+// steps 3 and 4 of a resampling event on the caller's arrays, in place: one block of scratch {cum | tmp | x's second buffer | group table |
+// ancestors} of its own (synchronises `stream`)
+int ramp_resample_groups(float* x, int32_t B, int32_t H, int32_t S, double* logw, double* c_prev, const int32_t* group_first_host,
+                         int32_t n_groups, const float* u, double ess_frac, int32_t* ancestor_out, double* ess_out, void* stream) {
+  RAMP_REQUIRE(x && logw && u, "ramp_resample_groups: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0 && ((long)H * S) % 4 == 0, "ramp_resample_groups: bad dims (H * S must be a multiple of 4)");
+  RAMP_REQUIRE(resample_group_table_fault(group_first_host, n_groups, B) == 0,
+               "ramp_resample_groups: malformed group table (n_groups >= 1, [0] = 0, strictly increasing, [n_groups] = B)");
+  RAMP_REQUIRE(resample_ess_frac_ok(ess_frac), "ramp_resample_groups: ess_frac must be finite and lie in [0, 2]");
+  hipStream_t s = as_stream(stream);
+  const size_t n = (size_t)B * H * S;
+  const size_t bytes = 2 * (size_t)B * 8 + n * 4 + ((size_t)n_groups + 1 + B) * 4;      // (every part a multiple of 16 bytes or the last ones)
+  char* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, bytes));
+  ResampleGroupsArgs a; a.logw = logw; a.c_prev = c_prev; a.u = u; a.ess_frac = ess_frac; a.ess_out = ess_out; a.B = B; a.n_groups = n_groups;
+  float* xtmp = reinterpret_cast<float*>(d);                                   // hipMalloc's alignment serves the 16-byte vectors
+  a.cum = reinterpret_cast<double*>(d + n * 4); a.tmp = a.cum + B;
+  int* gf = reinterpret_cast<int*>(d + n * 4 + 2 * (size_t)B * 8);
+  int* anc = gf + n_groups + 1;
+  a.group_first = gf; a.ancestor = anc;
+  int rc = 0;
+  if (hipMemcpyAsync(gf, group_first_host, ((size_t)n_groups + 1) * 4, hipMemcpyHostToDevice, s) != hipSuccess) { set_last_error("ramp_resample_groups: copy of the group table failed"); rc = -1; }
+  if (rc == 0) rc = launch_resample_groups(a, s);
+  if (rc == 0) rc = launch_resample_gather(x, anc, xtmp, B, H * S, s);
+  if (rc == 0 && hipMemcpyAsync(x, xtmp, n * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { set_last_error("ramp_resample_groups: copy back failed"); rc = -1; }
+  if (rc == 0 && ancestor_out && hipMemcpyAsync(ancestor_out, anc, (size_t)B * 4, hipMemcpyDeviceToDevice, s) != hipSuccess) { set_last_error("ramp_resample_groups: copy of the ancestors failed"); rc = -1; }
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(d);
+  return rc;
+}
+
 int ramp_apf_dynamic(float* traj, int32_t B, int32_t H, int32_t S, const double* points, int32_t n_points,
                      double thr_query, double thr_force, double strength, int32_t window, int32_t affected,
                      const float* goal, const int32_t* enable, void* stream) {

@@ -178,6 +178,70 @@ def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
     return out
 
 
+RESAMPLE_KEYS = {'every', 'flags', 't_start', 'lambda_', 'ess_frac', 'cloud', 'clouds', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'u'}
+
+
+def resample_tables(resample: dict, steps) -> dict:
+    """The host tables of a job's resampling events (``resample=`` of run_inference*; ramp_resample_params) for the job whose iterations
+    evaluate the network timesteps ``steps``, host data only -- clouds and uniforms are not looked at here.
+
+      every | flags      an event on every ``every``-th iteration (j + 1 a multiple of it), or one 0 / 1 flag per iteration
+      t_start            only iterations with t < t_start hold an event (default inf: all)
+      lambda_            the potential's inverse temperature (required), or one per iteration
+      ess_frac           a group resamples when ESS < ess_frac * size, in [0, 2] (default 0.5; 0 never, above 1 always)
+      cloud | clouds     the cost's obstacle points as in ``cost_guide=``; ``clouds``: one per scene of a scene / composed job
+      radius, w_obs, w_smooth, w_acc   the cost c = w_obs C_obs + w_smooth C_smooth + w_acc C_acc (defaults 0, 1, 0, 0)
+      u                  optional (n_events, n_groups) uniforms in (0, 1) of a job whose noise is injected
+
+    Returns ``{'resample': [...], 'lambda': [...], 'ess_frac', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'events': [j, ...]}``."""
+    if not isinstance(resample, dict):
+        raise TypeError("resample= takes a dict(every= | flags=, t_start=, lambda_=, ess_frac=, cloud= | clouds=, radius=, w_obs=, w_smooth=, "
+                        "w_acc=, u=)")
+    unknown = set(resample) - RESAMPLE_KEYS
+    if unknown:
+        raise ValueError(f"resample=: unknown keys {sorted(unknown)}")
+    if ('cloud' in resample) == ('clouds' in resample):
+        raise ValueError("resample=: exactly one of cloud= and clouds=")
+    if ('every' in resample) == ('flags' in resample):
+        raise ValueError("resample=: exactly one of every= and flags=")
+    n = len(steps)
+    out = {'radius': float(resample.get('radius', 0.0)), 'w_obs': float(resample.get('w_obs', 1.0)),
+           'w_smooth': float(resample.get('w_smooth', 0.0)), 'w_acc': float(resample.get('w_acc', 0.0))}
+    if not all(np.isfinite(v) for v in out.values()):
+        raise ValueError("resample=: radius, w_obs, w_smooth and w_acc must be finite")
+    if out['w_obs'] != 0.0 and not out['radius'] > 0.0:
+        raise ValueError("resample=: radius must be positive where w_obs != 0")
+    if 'every' in resample:
+        every = int(resample['every'])
+        if every < 1:
+            raise ValueError("resample=: every must be at least 1")
+        flags = [1 if (j + 1) % every == 0 else 0 for j in range(n)]
+    else:
+        flags = [1 if int(f) else 0 for f in resample['flags']]
+        if len(flags) != n:
+            raise ValueError(f"resample flags: {len(flags)} entries for {n} iterations")
+    t_start = float(resample.get('t_start', float('inf')))
+    if np.isnan(t_start):
+        raise ValueError("resample=: t_start is NaN")
+    flags = [f if t < t_start else 0 for f, t in zip(flags, steps)]
+    if sum(flags) > _lib.RESAMPLE_MAX_EVENTS:
+        raise ValueError(f"resample=: {sum(flags)} events, at most {_lib.RESAMPLE_MAX_EVENTS}")
+    if 'lambda_' not in resample:
+        raise ValueError("resample=: lambda_= is required")
+    lam = resample['lambda_']
+    lam = [float(lam)] * n if np.isscalar(lam) else [float(v) for v in lam]
+    if len(lam) != n:
+        raise ValueError(f"resample lambda_: {len(lam)} entries for {n} iterations")
+    if not all(np.isfinite(v) for v in lam):
+        raise ValueError("resample=: lambda_ must be finite")
+    ess_frac = float(resample.get('ess_frac', 0.5))
+    if not (np.isfinite(ess_frac) and 0.0 <= ess_frac <= 2.0):
+        raise ValueError("resample=: ess_frac must lie in [0, 2]")
+    out.update(resample=flags, ess_frac=ess_frac, events=[j for j, f in enumerate(flags) if f])
+    out['lambda'] = lam
+    return out
+
+
 class _GaussianDiffusionBase(nn.Module):
     _default_cfg_weight = 2.0
 
@@ -204,6 +268,7 @@ class _GaussianDiffusionBase(nn.Module):
         # several GPUs: this wrapper's batch is samples [sample0, sample0 + B) of a job of `total` trajectories; a philox job then
         # draws exactly the elements the unsharded job draws for those samples (set_noise_shard; ramp_sample_params.philox_sample0)
         self._philox_shard = None
+        self.last_resample = None               # after a job with resample=: {'ancestors': (n_events, B) int32, 'ess': (n_events, n_groups), 'cost': (n_events, B), 'logw': (B,), 'group_first', 'events'}
         self.last_mcmc = None                   # after a job with mcmc=: {'accept': (sum K, B) int32, 'rate': per iteration, 'n_inner': per iteration}
         self.context_model = context_model
         self.n_diffusion_steps = n_diffusion_steps
@@ -410,11 +475,12 @@ class _GaussianDiffusionBase(nn.Module):
         p.apf.cloud = _lib.ptr(cloud)
         p.apf.n_points = cloud.shape[0]
 
-    def _philox_block(self, B: int, n_steps: int, ddim: bool, n_inner: int = 0):
+    def _philox_block(self, B: int, n_steps: int, ddim: bool, n_inner: int = 0, n_resample: int = 0):
         """A job that draws its own noise takes the next (n_steps + 1 | 1) * total * H * S elements of the Philox stream: returns
         (seed, offset, sample0, total) for the params and advances the offset by the WHOLE job's block (every shard advances alike).
         ``n_inner`` > 0 (a job with Langevin steps): its draws sit behind the full (n_steps + 1)-block main block -- n_inner blocks of
-        normals, then one group per uniform (ramp_sample_mcmc in ramp_hip.h) -- and the offset advances past them."""
+        normals, then one group per uniform (ramp_sample_mcmc in ramp_hip.h) -- and the offset advances past them.  ``n_resample`` > 0 (a
+        job with resampling events): that many groups more, one per (event, group), behind the inner steps' (ramp_resample_params)."""
         s0, tot = self._philox_shard if self._philox_shard is not None else (0, B)
         if not (0 <= s0 and s0 + B <= tot):
             raise ValueError(f"set_noise_shard: samples [{s0}, {s0 + B}) lie outside the job's {tot}")
@@ -422,8 +488,8 @@ class _GaussianDiffusionBase(nn.Module):
         n_el = (1 if ddim else n_steps + 1) * tot * hs
         offset = self._philox_offset
         self.last_philox = (self.noise_seed, offset, n_el)
-        if n_inner:
-            self._philox_offset += (n_steps + 1 + n_inner) * tot * hs // 4 + n_inner * tot
+        if n_inner or n_resample:
+            self._philox_offset += (n_steps + 1 + n_inner) * tot * hs // 4 + n_inner * tot + n_resample
         else:
             self._philox_offset += (n_el + 3) // 4
         return self.noise_seed, offset, s0, tot
@@ -457,6 +523,45 @@ class _GaussianDiffusionBase(nn.Module):
         cg = fill_cost_guide(arrays.keep(points), arrays.keep(off), d, tab)
         cg.n_guide, cg.step = arrays.i32(tab['n_guide']), arrays.f32(tab['step'])
         return cg
+
+    def _fill_resample(self, arrays: _HostArrays, tab: dict, resample: dict, scene_job: Optional[dict], hard_conds, B: int):
+        """ramp_resample_params from the tables of ``resample_tables``: one group for a plain job, one per scene for a scene / composed job,
+        the cost's clouds like the guide's.  Returns (params, its cost table, the host group table)."""
+        from .guide import cloud_table, fill_cost_guide
+        n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
+        if scene_job is None:
+            gf = np.array([0, B], dtype=np.int32)
+        else:
+            ts = scene_job['traj_scene'].cpu().numpy()
+            if np.any(np.diff(ts) < 0):
+                raise ValueError("resample=: a scene's trajectories must be adjacent, scenes in order")
+            gf = np.concatenate([[0], np.cumsum(np.bincount(ts, minlength=n_scenes))]).astype(np.int32)
+            if np.any(np.diff(gf) <= 0):
+                raise ValueError("resample=: every scene needs at least one trajectory")
+        for k, v in hard_conds.items():      # a resampled row keeps its place's pinned values: they must agree inside a group
+            v = v.detach().cpu()
+            if v.dim() == 2:
+                for a, b in zip(gf[:-1], gf[1:]):
+                    if not bool((v[a:b] == v[a:a + 1]).all()):
+                        raise ValueError(f"resample=: the values of hard condition {k} differ inside a group (trajectories {a} .. {b - 1}): "
+                                         "resampling moves whole rows between them")
+        clouds = [resample['cloud']] * n_scenes if 'cloud' in resample else list(resample['clouds'])
+        if len(clouds) != n_scenes:
+            raise ValueError(f"resample clouds: {len(clouds)} entries for {n_scenes} scene(s)")
+        points, off, d = cloud_table(clouds, self._device())
+        if d > self.state_dim:
+            raise ValueError(f"resample: {d}-D points on {self.state_dim}-wide states")
+        cost = arrays.keep(fill_cost_guide(arrays.keep(points), arrays.keep(off), d, tab))
+        rs = _lib.RampResampleParams()
+        rs.n_groups, rs.group0, rs.groups_total = len(gf) - 1, 0, 0
+        gf = arrays.keep(gf)
+        rs.group_first_host = gf.ctypes.data_as(_lib.c_i32p)
+        rs.resample = arrays.i32(tab['resample'])
+        lam = arrays.keep(np.asarray(tab['lambda'], dtype=np.float64))
+        rs.lambda_ = lam.ctypes.data_as(_lib.c_f64p)
+        rs.ess_frac = tab['ess_frac']
+        rs.cost = C.pointer(cost)
+        return rs, cost, gf
 
     def _run_guarded(self, job):
         """Run ``job`` under the fp16x3 range-guard policy: a flagged result is discarded and the same job (same noise) repeated, never
@@ -502,14 +607,25 @@ class _GaussianDiffusionBase(nn.Module):
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
                 return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None,
-                mcmc: Optional[dict] = None, cost_guide: Optional[dict] = None):
+                mcmc: Optional[dict] = None, cost_guide: Optional[dict] = None, resample: Optional[dict] = None):
         """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
         (``ramp_sample_scenes``); ``obstacle_pts`` is not read then.  ``guidance`` (with a ``scene_job``): a composed job
         (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``.
         ``mcmc``: Langevin refinement inside the job (``ramp_sample_mcmc``, the one entry for all three kinds of job; ``mcmc_tables``);
         the accept flags land in ``self.last_mcmc``.  ``cost_guide``: cost-gradient guidance inside the job (``ramp_sample_guided``, the
-        same one entry with the guide added; ``guide_tables``)."""
+        same one entry with the guide added; ``guide_tables``).  ``resample``: resampling events inside the job (``ramp_sample_steered``;
+        ``resample_tables``); ancestors, ESS, costs and final log-weights land in ``self.last_resample``."""
         m = self.model
+        rtab = resample_tables(resample, steps) if resample is not None else None
+        if rtab is not None:
+            if self._philox_shard is not None:
+                raise NotImplementedError("resample=: a sharded job (set_noise_shard) cannot resample -- a group's trajectories would sit on "
+                                          "several devices")
+            if not self.predict_epsilon:
+                raise NotImplementedError("resample=: predict_epsilon=False is not served")
+            if ddim and not (mcmc is not None and mcmc_tables(mcmc, steps, self.alphas_cumprod)['total'] > 0):
+                raise NotImplementedError("resample=: the DDIM loop (eta = 0) never separates duplicates -- add mcmc= inner steps or sample "
+                                          "with sampler='ddpm'")
         tab = self._mcmc_tables(mcmc, steps) if mcmc is not None else None
         gtab = guide_tables(cost_guide, steps, self.posterior_variance) if cost_guide is not None else None
         dev = self._device()
@@ -545,6 +661,26 @@ class _GaussianDiffusionBase(nn.Module):
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
         mp = z_in = u_in = accept = None
         cg = self._fill_guide(arrays, gtab, cost_guide, scene_job) if gtab is not None else None
+        rs = ru = r_anc = r_ess = r_cost = r_logw = None
+        n_ev = len(rtab['events']) if rtab is not None else 0
+        if n_ev:
+            rs, _cost, r_gf = self._fill_resample(arrays, rtab, resample, scene_job, hard_conds, B)
+            G = rs.n_groups
+            r_anc = torch.empty((n_ev, B), device=dev, dtype=torch.int32)
+            r_ess = torch.empty((n_ev, G), device=dev, dtype=torch.float64)
+            r_cost = torch.empty((n_ev, B), device=dev, dtype=torch.float64)
+            r_logw = torch.empty((B,), device=dev, dtype=torch.float64)
+            if noise is None:
+                if resample.get('u') is not None:
+                    raise ValueError("resample['u'] injects the events' uniforms next to an injected loop noise; with noise_source='philox' "
+                                     "the job draws them itself -- leave it out")
+            else:
+                ru = resample.get('u')
+                if ru is None:
+                    ru = torch.rand((n_ev, G), device=dev).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
+                ru = torch.as_tensor(ru).to(dev, torch.float32).contiguous()
+                if tuple(ru.shape) != (n_ev, G):
+                    raise ValueError(f"resample u must be ({n_ev}, {G}); got {tuple(ru.shape)}")
         if tab is not None:
             mp = self._fill_mcmc(arrays, tab)
             accept = torch.zeros((tab['total'], B), device=dev, dtype=torch.int32)
@@ -553,7 +689,8 @@ class _GaussianDiffusionBase(nn.Module):
                 raise ValueError("mcmc['noise'] / mcmc['u'] inject the inner steps' draws next to an injected loop noise; with "
                                  "noise_source='philox' the job draws both itself -- leave them out")
             p.noise_mode = 1
-            p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim, tab['total'] if tab else 0)
+            p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim, tab['total'] if tab else 0,
+                                                                                                     n_ev * rs.n_groups if n_ev else 0)
         else:
             noise = noise.contiguous()
             if tab and tab['total']:      # the inner steps' draws, behind the loop's own in call order
@@ -568,7 +705,14 @@ class _GaussianDiffusionBase(nn.Module):
             lib = _lib.load()
 
             def job():
-                if cg is not None:
+                if rs is not None:
+                    _lib.check(lib.ramp_sample_steered(m.ctx(), C.byref(p), C.byref(rs), C.byref(cg) if cg is not None else None,
+                                                       C.byref(mp) if mp is not None else None, C.byref(rows) if rows is not None else None,
+                                                       C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
+                                                       _lib.ptr(u_in), _lib.ptr(ru), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
+                                                       _lib.ptr(r_anc), _lib.ptr(r_ess), _lib.ptr(r_cost), _lib.ptr(r_logw),
+                                                       _lib.current_stream()), "ramp_sample_steered")
+                elif cg is not None:
                     _lib.check(lib.ramp_sample_guided(m.ctx(), C.byref(p), C.byref(cg), C.byref(mp) if mp is not None else None,
                                                       C.byref(rows) if rows is not None else None,
                                                       C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
@@ -597,6 +741,11 @@ class _GaussianDiffusionBase(nn.Module):
                 rate.append(float(acc[k0:k0 + K].float().mean()) if K else float('nan'))
                 k0 += K
             self.last_mcmc = {'accept': acc, 'rate': rate, 'n_inner': list(tab['n_inner']), 'kind': tab['kind']}
+        if rtab is not None:
+            self.last_resample = {'ancestors': r_anc.cpu() if n_ev else torch.empty((0, B), dtype=torch.int32),
+                                  'ess': r_ess.cpu() if n_ev else None, 'cost': r_cost.cpu() if n_ev else None,
+                                  'logw': r_logw.cpu() if n_ev else torch.zeros((B,), dtype=torch.float64),
+                                  'group_first': r_gf.copy() if n_ev else None, 'events': list(rtab['events'])}
         return x_out, chain
 
     # ------------------------------------------------------------------ loops (reference signatures)
@@ -613,7 +762,8 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
-                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, cost_guide=None, **sample_kwargs):
+                      noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, cost_guide=None, resample=None,
+                      **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
@@ -623,6 +773,8 @@ class _GaussianDiffusionBase(nn.Module):
                 raise NotImplementedError("mcmc= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if cost_guide is not None:
                 raise NotImplementedError("cost_guide= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
+            if resample is not None:
+                raise NotImplementedError("resample= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if scene_job is not None:
                 raise NotImplementedError("run_inference_scenes runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
                                           "scene's batch at a time -- use run_inference per scene")
@@ -644,7 +796,8 @@ class _GaussianDiffusionBase(nn.Module):
                for j in range(len(steps))]
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
-                                    cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide)
+                                    cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide,
+                                    resample=resample)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -686,7 +839,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
-                           guidance=None, mcmc=None, cost_guide=None, **sample_kwargs):
+                           guidance=None, mcmc=None, cost_guide=None, resample=None, **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
         B = shape[0]
@@ -695,7 +848,8 @@ class _GaussianDiffusionBase(nn.Module):
         apf = [1 if (self.APF and self._supports_apf and j >= self.apf_ddim['start']) else 0 for j in range(len(steps))]
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
-                                    return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide)
+                                    return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide,
+                                    resample=resample)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -710,6 +864,8 @@ class _GaussianDiffusionBase(nn.Module):
                 raise NotImplementedError("mcmc= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
             if sample_kwargs.get('cost_guide') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
                 raise NotImplementedError("cost_guide= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
+            if sample_kwargs.get('resample') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
+                raise NotImplementedError("resample= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
             for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
                 sample_kwargs.pop(k, None)      # silently ignored by the reference's DDIM loop
             return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized,

@@ -665,6 +665,8 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
             raise NotImplementedError("mcmc=: DynamicGaussianDiffusionModel has no Langevin refinement (the replanning jobs are out of scope)")
         if sample_kwargs.get('cost_guide') is not None:
             raise NotImplementedError("cost_guide=: DynamicGaussianDiffusionModel has no cost guide (the replanning jobs are out of scope)")
+        if sample_kwargs.get('resample') is not None:
+            raise NotImplementedError("resample=: DynamicGaussianDiffusionModel has no resampling (the replanning jobs are out of scope)")
         for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
             sample_kwargs.pop(k, None)
         return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized, obstacle_pts=obstacle_pts,
