@@ -356,7 +356,7 @@ typedef struct ramp_cost_guide {
  * Refused on the host before any launch (non-zero, "ramp_sample_guided" in ramp_last_error): point_dim outside {2, 3} or > state_dim,
  * n_guide[j] outside 0 .. RAMP_GUIDE_MAX_STEPS, non-finite scalars or step, radius <= 0 with w_obs != 0, offsets that are not
  * non-decreasing from 0, a scene-count mismatch, cloud_points == NULL with a non-empty table, H > 128; and what ramp_sample_mcmc refuses.
- * ramp_replan / ramp_replan_episodes take no guide. */
+ * ramp_replan / ramp_replan_episodes take a guide of their own, with a moving-cloud term and per-episode pins: ramp_replan_guide below. */
 int ramp_sample_guided(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
                        const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
                        const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream);
@@ -420,7 +420,7 @@ typedef struct ramp_resample_params {
  * [0, 2] or non-finite; a missing or non-finite lambda; more than RAMP_RESAMPLE_MAX_EVENTS events; p->ddim != 0 without MCMC inner steps
  * (m->kind != 0 and sum n_inner > 0: eta = 0 DDIM never separates duplicates); p->predict_x0 != 0; what the cost table's own checks refuse
  * (see ramp_sample_guided), H > 128; group0 / groups_total that do not hold the call's groups; NULL resample_u in noise_mode 0; and what
- * ramp_sample_guided refuses.  ramp_replan / ramp_replan_episodes take no resampling. */
+ * ramp_sample_guided refuses.  ramp_replan / ramp_replan_episodes take no resampling (their guide is ramp_replan_guide). */
 int ramp_sample_steered(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_resample_params* rs, const ramp_cost_guide* cg,
                         const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
                         const float* mcmc_noise, const float* mcmc_u, const float* resample_u, float* chain_out, float* x_out,
@@ -547,6 +547,66 @@ typedef struct ramp_episode_batch {
  * One synchronisation of `stream`: E x 16 bytes of results and the range flag. */
 int ramp_replan_episodes(ramp_ctx* ctx, const ramp_replan_params* p, const ramp_episode_batch* ep, float* best_out, float* batch_out,
                          int32_t* mask_out, int32_t* results_host, ramp_replan_result* result_host, void* stream);
+/* ---- cost guidance inside the replanning jobs, with a moving-pursuer term ----
+ * ramp_cost_guide's gradient steps for ramp_replan / ramp_replan_episodes.  What a replan needs and that guide cannot give: pins that differ
+ * from row to row (the executed history of the row's own episode and the goal of its clean plan), a static cloud AND a pursuer per row, and
+ * an obstacle that is where it WILL be at waypoint h, not where it is now.  For one candidate x (H, S) of episode e (the planner is 2-D):
+ * p_h = x[h, 0:2], c (P, 2) the episode's static cloud, m (M, 2) its moving cloud now (the pursuer's sphere points), delta (H, 2) its track --
+ * the displacement of that cloud at waypoint h, predicted by the caller:
+ *   C_obs    = sum_h sum_j 1/2 max(0, r     - |p_h - c_j|)^2
+ *   C_mov    = sum_h sum_j 1/2 max(0, r_mov - |(p_h - delta_h) - m_j|)^2
+ *   C_smooth, C_acc as in ramp_cost_guide
+ *   C        = w_obs C_obs + w_mov C_mov + w_smooth C_smooth + w_acc C_acc
+ * fp32, every product and sum rounded once, as written; the moving pair's difference is sub(sub(p, delta), m) per component; a pair at
+ * distance 0 contributes no gradient; an empty static cloud or M = 0 drops its term; g = w_obs g_obs + (w_mov g_mov + (w_smooth g_smooth +
+ * w_acc g_acc)); |g|^2 is summed in fp64.  The fp32 sums over points follow ramp_cost_guide's rule (a lane's points in order, a butterfly
+ * over the lanes, the tiles of 1024 points in order), the static tiles first, then the moving tile: the bits do not depend on the batch.
+ * M <= 1024 (one tile), H <= 128.
+ * One iteration is ramp_cost_guide's six steps with the pinned waypoints of row b of episode e: every waypoint < n_hist[e], waypoint H - 1
+ * and every waypoint of the hard-condition table.  Their values in the working copy are what the replan's pinning writes there, in its
+ * order: the hard-condition values in table order, then the rows of the history, then x_clean[e][H - 1].  Only channels 0:2 are touched;
+ * pinned waypoints and channels >= 2 keep their bits in memory; a row whose episode has active == 0 is left unchanged.
+ * Place in the replan, on DDIM step j with n_guide[j] > 0: on x0, after the CFG combination and, on the last step, after both APF passes and
+ * the goal copy, before the DDIM update.  ONE launch per guided step, whatever E and the iteration count.  No random numbers.
+ * Static clouds, moving points, tracks and offsets are copied into buffers of the context before the launch and the captured graph reads
+ * those: other CONTENTS of equal sizes replay the same graph and are honoured.  The seven scalars, n_guide[], step[], n_mov, the clouds'
+ * total and whether tap_out is set are part of the graph key.  The bf16x6 repeat of a flagged replan runs the same guide. */
+typedef struct ramp_replan_guide {
+  int32_t n_scenes;                  /* 1 for ramp_replan, E for ramp_replan_episodes */
+  int32_t n_mov;                     /* points of each episode's moving cloud, 0 .. 1024 */
+  const float*   cloud_points;       /* device (sum P, 2): static guide clouds, concatenated (an empty one allowed) */
+  const int32_t* cloud_offset_host;  /* host (n_scenes + 1): [0] = 0, non-decreasing */
+  const float*   mov_points_host;    /* host (n_scenes, n_mov, 2) */
+  const float*   mov_track_host;     /* host (n_scenes, H, 2) */
+  double radius, radius_mov, w_obs, w_mov, w_smooth, w_acc, max_norm;
+  const int32_t* n_guide;            /* host (p->n_steps), 0 .. RAMP_GUIDE_MAX_STEPS */
+  const float*   step;               /* host (p->n_steps) */
+  float* tap_out;                    /* device (2, B, H, S) or NULL: x0 just before / just after the LAST guided launch of the call */
+} ramp_replan_guide;
+/* ramp_replan / ramp_replan_episodes with the guide: rg == NULL, or n_guide zero on every step, IS the unguided call, bit for bit (and
+ * ramp_replan / ramp_replan_episodes are these entries with rg == NULL).  Refused on the host before any launch (non-zero, the entry's
+ * name in ramp_last_error): n_mov outside 0 .. 1024; n_scenes != 1 (ramp_replan_guided) resp. != E; offsets that are not non-decreasing
+ * from 0; non-finite scalars or step; radius <= 0 with w_obs != 0; radius_mov <= 0 with w_mov != 0 and n_mov > 0; n_guide[j] outside
+ * 0 .. RAMP_GUIDE_MAX_STEPS; a NULL table where one is needed (offsets, n_guide, step, cloud_points with a non-empty table, moving points
+ * and track with n_mov > 0); H > 128; state_dim < 2. */
+int ramp_replan_guided(ramp_ctx* ctx, const ramp_replan_params* p, const ramp_replan_state* st, const ramp_replan_guide* rg, float* best_out,
+                       float* batch_out, int32_t* mask_out, ramp_replan_result* result_host, void* stream);
+int ramp_replan_episodes_guided(ramp_ctx* ctx, const ramp_replan_params* p, const ramp_episode_batch* ep, const ramp_replan_guide* rg,
+                                float* best_out, float* batch_out, int32_t* mask_out, int32_t* results_host,
+                                ramp_replan_result* result_host, void* stream);
+/* the kernel alone on (B, H, S) rows in place: n_iter (0 .. RAMP_GUIDE_MAX_STEPS) iterations of size `step` in one launch; rg->n_guide,
+ * rg->step and rg->tap_out are not read, rg->n_scenes >= 1.  traj_scene device int32 (B) or NULL = scene 0; a row whose index is outside
+ * the table is left unchanged.  pin_first device int32 (B) or NULL (= 0): waypoints < pin_first[b] and waypoint H - 1 are pinned, together
+ * with the hard_idx_host (n_hard) waypoints; a pinned waypoint's value in the working copy is hard_val's (device (n_hard, B, S), later
+ * entries win) where the table names it and the array's own otherwise -- so a replan's launch is this call with its history rows and its
+ * goal appended to the table.  Refusals as above, with "ramp_guide_step_moving".  Synchronises `stream`. */
+int ramp_guide_step_moving(float* traj, int32_t B, int32_t H, int32_t S, const ramp_replan_guide* rg, const int32_t* traj_scene,
+                           const int32_t* pin_first, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
+                           const float* hard_val, void* stream);
+/* terms_out device (B, 4) doubles = {C_obs, C_mov, C_smooth, C_acc}, unweighted, of the rows as they are: fp64 sums over fp32 pair values
+ * in a fixed order (NaN for a scene index outside the table; with n_mov == 0 columns 0, 2, 3 are ramp_guide_cost's).  Synchronises `stream`. */
+int ramp_guide_cost_moving(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_replan_guide* rg, const int32_t* traj_scene,
+                           double* terms_out, void* stream);
 /* the selection alone (compute_trajectory_costs + winner with x[0, 2:] = 0) for a finished batch, e.g. the high-level plan
  * (diffusion_model_dynamic.py:524-530): mask / path_len / smooth device (B), best_out device (H,S), result_dev device
  * int32[4] = {n_free, best_rank, best_row, 0}.  Asynchronous. */

@@ -66,6 +66,15 @@ class RampCostGuide(C.Structure):
                 ("n_guide", c_i32p), ("step", c_f32p)]
 
 
+class RampReplanGuide(C.Structure):
+    """ramp_replan_guide: the cost guide of the replanning jobs (ramp_replan_guided, ramp_replan_episodes_guided) and of the kernel-level
+    ramp_guide_step_moving / ramp_guide_cost_moving."""
+    _fields_ = [("n_scenes", C.c_int32), ("n_mov", C.c_int32), ("cloud_points", C.c_void_p), ("cloud_offset_host", c_i32p),
+                ("mov_points_host", c_f32p), ("mov_track_host", c_f32p),
+                ("radius", C.c_double), ("radius_mov", C.c_double), ("w_obs", C.c_double), ("w_mov", C.c_double), ("w_smooth", C.c_double),
+                ("w_acc", C.c_double), ("max_norm", C.c_double), ("n_guide", c_i32p), ("step", c_f32p), ("tap_out", C.c_void_p)]
+
+
 RESAMPLE_MAX_EVENTS = 64   # RAMP_RESAMPLE_MAX_EVENTS
 c_f64p = C.POINTER(C.c_double)
 
@@ -188,6 +197,14 @@ PROTOTYPES = {
                               C.c_void_p, C.POINTER(RampReplanResult), C.c_void_p]),
     "ramp_replan_episodes": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampEpisodeBatch), C.c_void_p, C.c_void_p,
                                        C.c_void_p, c_i32p, C.POINTER(RampReplanResult), C.c_void_p]),
+    "ramp_replan_guided": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampReplanState), C.POINTER(RampReplanGuide), C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(RampReplanResult), C.c_void_p]),
+    "ramp_replan_episodes_guided": (C.c_int, [C.c_void_p, C.POINTER(RampReplanParams), C.POINTER(RampEpisodeBatch), C.POINTER(RampReplanGuide),
+                                              C.c_void_p, C.c_void_p, C.c_void_p, c_i32p, C.POINTER(RampReplanResult), C.c_void_p]),
+    "ramp_guide_step_moving": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampReplanGuide), C.c_void_p, C.c_void_p,
+                                         C.c_int32, C.c_float, C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
+    "ramp_guide_cost_moving": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampReplanGuide), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "ramp_select_best": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_float, C.c_float,
                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_replan_costs": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -147,6 +147,33 @@ int launch_episode_cost_segments(float* dst, const float* cloud, const float* ex
 // and in both cases the episode's `best` block stays as it is
 int launch_select_episodes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                            const int* traj_first, EpisodeTable ep, float* best, int* result, int B, int H, int S, hipStream_t s);
+// ---- the cost guide of the replanning jobs (guide_replan.hip; ramp_replan_guide in ramp_hip.h) -------------------
+// The static term of GuideArgs (2-D) plus a moving cloud of n_mov <= 1024 points per scene displaced by a per-waypoint track, and pins that
+// differ from row to row: waypoints < n_first(b), waypoint H - 1 and the hard-conditioned ones.  n_first(b) = pin_first[b], or the n_hist of
+// the row's episode record (est, with its `active` switch: a row of an ended episode is left alone) or of the single replan's record (rst).
+// The working copy's pinned values: the hard condition's (later entries win), then -- only with hist / x_clean, the replans' buffers
+// (n_scenes, H, S) -- the history rows and the clean plan's goal, replan_pin_row's order; a pinned waypoint nothing names keeps the array's own
+struct MovingGuideArgs {
+  float* traj = nullptr;            // (B,H,S): channels 0:2 of the free waypoints are updated in place (the cost kernel only reads)
+  int B = 0, H = 0, S = 0;          // H <= 128, S >= 2
+  const float* cloud = nullptr;     // (P_total, 2): the scenes' static clouds, concatenated
+  const int* cloud_off = nullptr;   // device (n_scenes + 1); an empty span is allowed, spans are clamped to P_total
+  const float* mov = nullptr;       // device (n_scenes, n_mov, 2): every scene's moving cloud now
+  const float* track = nullptr;     // device (n_scenes, H, 2): its displacement at waypoint h
+  const int* scene = nullptr;       // (B) scene (episode) of each row, or null = 0 for all; an index outside the table leaves the row alone
+  int n_scenes = 1, P_total = 0, n_mov = 0;
+  const int* pin_first = nullptr; const EpisodeState* est = nullptr; const ReplanState* rst = nullptr;   // where n_first(b) comes from (all null: 0)
+  const float* hist = nullptr; const float* x_clean = nullptr;
+  float radius = 0, radius_mov = 0, w_obs = 0, w_mov = 0, w_smooth = 0, w_acc = 0, max_norm = 0;
+  float step = 0; int n_iter = 0;   // (the cost kernel reads neither, nor the pins)
+  HardConds hc;
+};
+// n_iter iterations in ONE launch, one block per row; n_iter == 0 launches nothing
+int launch_guide_step_moving(const MovingGuideArgs& a, hipStream_t s);
+// terms (B, 4) doubles = {C_obs, C_mov, C_smooth, C_acc} unweighted of the rows as they are (NaN for a scene index outside the table)
+int launch_guide_cost_moving(const MovingGuideArgs& a, double* terms, hipStream_t s);
+// dst[0..n) = src[0..n) as a kernel node (the tap of a guided replan inside its captured graph)
+int launch_copy_f32(float* dst, const float* src, long n, hipStream_t s);
 int launch_replan_select(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                          float* best, int* result, int B, int H, int S, hipStream_t s);
 // one block per scene of a many-scene batch (rows [traj_first[s], traj_first[s + 1])): result (n_scenes, 4) with the row in the whole

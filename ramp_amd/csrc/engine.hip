@@ -196,6 +196,11 @@ struct ramp_ctx {
   size_t e_cap_B = 0, e_cap_E = 0, e_cap_static = 0, e_cap_dyn = 0, e_cap_cost = 0, e_cap_extra = 0; int e_best_E = 0;
   hipGraphExec_t e_graph[2] = {nullptr, nullptr}; std::string e_key;
   bool e_calibrated = false;
+  // cost guidance inside the replans (ramp_replan_guided, ramp_replan_episodes_guided): the static guide clouds (sum P, 2), their offsets
+  // (n_scenes + 1), the moving clouds (n_scenes, n_mov, 2) and their tracks (n_scenes, H, 2), copied here before the launch -- data of a replay
+  // -- and the tap (2, B, H, S).  Scalars, counts, step sizes, n_mov, the clouds' total and the tap's presence are in the graph key
+  float *rg_cloud = nullptr, *rg_mov = nullptr, *rg_track = nullptr, *rg_tap = nullptr; int* rg_off = nullptr;
+  size_t rg_cloud_cap = 0, rg_mov_cap = 0, rg_track_cap = 0, rg_tap_cap = 0, rg_off_cap = 0;
   // scene-encoder scratch
   float* scene_ws = nullptr; size_t scene_ws_cap = 0;
   int* enc_tab = nullptr; size_t enc_tab_cap = 0;      // ramp_encode_scenes: the pass-local CSR and tile tables of every pass of the call
@@ -2565,8 +2570,11 @@ int ramp_sample_steered(ramp_ctx* c, const ramp_sample_params* p, const ramp_res
 // caller BEFORE the replan: the reference hands the environment x[:, stepp, :2], which is the pinned executed state.
 // ej != nullptr: the replan of many episodes (ramp_replan_episodes) -- the same sequence on the episode forms of the kernels and the e_*
 // buffers: row b reads the record, history, clean plan, clouds and goal of its own episode
+// rg != nullptr: the cost guide (checked by the entry, its tables staged by stage_replan_guide): on step j with n_guide[j] > 0 ONE launch on x0, behind the CFG
+// combination and, on the last step, behind both APF passes and the goal copy, in front of the DDIM update
 struct EpisodeJob { int E, P_static, P_cost; };      // episodes; points of the concatenated static APF clouds / of the cost segments
-static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, bool calibrate, const EpisodeJob* ej = nullptr) {
+static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, bool calibrate, const EpisodeJob* ej = nullptr,
+                       const ramp_replan_guide* rg = nullptr) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S;
   HardConds hc; hc.idx = ej ? c->e_hard_idx : c->r_hard_idx; hc.val = ej ? c->e_hard_val : c->r_hard_val; hc.n = p->n_hard;
@@ -2581,6 +2589,14 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
   }
   const std::array<float, 3> comb = comb_weights(p->n_rp, p->w, 0.0);
   const bool shared = p->n_rp > 1 && c->share_prefix;
+  MovingGuideArgs ga; int j_tap = -1;
+  if (rg) {
+    ga = moving_guide_args(rg, c->s_x0, B, H, S);
+    ga.cloud = c->rg_cloud; ga.cloud_off = c->rg_off; ga.mov = c->rg_mov; ga.track = c->rg_track; ga.hc = hc;
+    if (ej) { ga.scene = c->e_row_ep; ga.est = c->e_state; ga.hist = c->e_hist; ga.x_clean = c->e_xclean; }
+    else { ga.rst = c->r_state; ga.hist = c->r_hist; ga.x_clean = c->r_xclean; }
+    if (rg->tap_out) for (int j = 0; j < p->n_steps; ++j) if (rg->n_guide[j] > 0) j_tap = j;
+  }
   for (int j = 0; j < p->n_steps; ++j) {
     const bool last = p->t[j] == 0;                       // the reference's `i == 0`: smoothing + APF on the final step
     if (last && ej) CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
@@ -2611,6 +2627,13 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
       CK(launch_apf_dynamic(a, s));
       CK(launch_replan_goal(c->s_x0, c->s_x, B, H, S, s));
     }
+    if (rg && rg->n_guide[j] > 0) {
+      const long n_tap = (long)B * H * S;
+      if (j == j_tap) CK(launch_copy_f32(c->rg_tap, c->s_x0, n_tap, s));
+      ga.n_iter = rg->n_guide[j]; ga.step = rg->step[j];
+      CK(launch_guide_step_moving(ga, s));
+      if (j == j_tap) CK(launch_copy_f32(c->rg_tap + n_tap, c->s_x0, n_tap, s));
+    }
     CK(launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], none,
                           c->s_x, nullptr, B, H, S, s));
     if (ej) CK(launch_replan_pin_episodes(c->s_x, hc, c->e_hist, c->e_xclean, et, B, H, S, s));
@@ -2630,9 +2653,50 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
   return 0;
 }
 
+// The guide of a replan: checked for the entry `who` (*active is false for rg == NULL or a guide without an iteration anywhere, which is the
+// unguided call), its buffers grown with the job's other buffers (before staging_done), its tables copied with the job's other inputs
+static int check_replan_job_guide(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_guide* rg, int n_scenes, const char* who, bool* active) {
+  *active = false;
+  if (!rg) return 0;
+  int total = 0;
+  CK(check_replan_guide(rg, n_scenes, c->cfg.horizon, c->cfg.state_dim, p->n_steps, who, &total));
+  *active = total > 0;
+  return 0;
+}
+static int grow_replan_guide(ramp_ctx* c, const ramp_replan_guide* rg, int B) {
+  const size_t HS = (size_t)c->cfg.horizon * c->cfg.state_dim;
+  CK(grow(c, c->rg_cloud, c->rg_cloud_cap, std::max<size_t>(4, (size_t)rg->cloud_offset_host[rg->n_scenes] * 2)));
+  CK(grow(c, c->rg_off, c->rg_off_cap, (size_t)rg->n_scenes + 1));
+  CK(grow(c, c->rg_mov, c->rg_mov_cap, std::max<size_t>(4, (size_t)rg->n_scenes * rg->n_mov * 2)));
+  CK(grow(c, c->rg_track, c->rg_track_cap, std::max<size_t>(4, (size_t)rg->n_scenes * c->cfg.horizon * 2)));
+  if (rg->tap_out) CK(grow(c, c->rg_tap, c->rg_tap_cap, 2 * (size_t)B * HS));
+  return 0;
+}
+static int stage_replan_guide(ramp_ctx* c, const ramp_replan_guide* rg, hipStream_t s) {
+  const size_t P = (size_t)rg->cloud_offset_host[rg->n_scenes];
+  if (P) RAMP_HIP_CHECK(hipMemcpyAsync(c->rg_cloud, rg->cloud_points, P * 8, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->rg_off, rg->cloud_offset_host, ((size_t)rg->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
+  if (rg->n_mov) {
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->rg_mov, rg->mov_points_host, (size_t)rg->n_scenes * rg->n_mov * 8, hipMemcpyHostToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->rg_track, rg->mov_track_host, (size_t)rg->n_scenes * c->cfg.horizon * 8, hipMemcpyHostToDevice, s));
+  }
+  return 0;
+}
+// what a guide adds to a replan's graph key
+static void key_replan_guide(Key& key, const ramp_replan_guide* rg, int n_steps) {
+  key.put(rg->n_scenes); key.put(rg->n_mov); key.put(rg->cloud_offset_host[rg->n_scenes]);
+  key.put(rg->radius); key.put(rg->radius_mov); key.put(rg->w_obs); key.put(rg->w_mov); key.put(rg->w_smooth); key.put(rg->w_acc);
+  key.put(rg->max_norm); key.put(rg->n_guide, n_steps); key.put(rg->step, n_steps); key.put((int)(rg->tap_out != nullptr));
+}
+
 int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_state* st, float* best_out, float* batch_out,
                 int32_t* mask_out, ramp_replan_result* result_host, void* stream) {
-  RAMP_REQUIRE(c && p && st && result_host, "null argument");
+  return ramp_replan_guided(c, p, st, nullptr, best_out, batch_out, mask_out, result_host, stream);
+}
+
+int ramp_replan_guided(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_state* st, const ramp_replan_guide* rg, float* best_out,
+                       float* batch_out, int32_t* mask_out, ramp_replan_result* result_host, void* stream) {
+  RAMP_REQUIRE(c && p && st && result_host, rg ? "ramp_replan_guided: null argument" : "null argument");
   RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
@@ -2643,10 +2707,14 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   RAMP_REQUIRE(st->dyn_pts_host && (st->near == 0 || p->n_extra == 0 || st->extra_pts_host), "missing pursuer points");
   RAMP_REQUIRE(st->x_clean || c->r_best, "no current plan: pass x_clean on the first replan");
   for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
+  bool guided = false;
+  CK(check_replan_job_guide(c, p, rg, 1, "ramp_replan_guided", &guided));
+  if (!guided) rg = nullptr;
   hipStream_t s = as_stream(stream);
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   // ---- fixed buffers the graphs read
   CK(ensure_sampler_buffers(c, B, p->n_rp, 0, false));
+  if (rg) CK(grow_replan_guide(c, rg, B));
   if (!c->r_state) {
     CK(renew(c, c->r_state, 1)); CK(renew(c, c->r_result, 8)); CK(renew(c, c->r_hard_idx, 16));
     CK(renew(c, c->r_hist, HS)); CK(renew(c, c->r_xclean, HS)); CK(renew(c, c->r_best, HS));
@@ -2680,12 +2748,13 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   }
   ReplanState hs{}; hs.n_hist = st->n_hist; hs.stepp = st->stepp; hs.pursuer[0] = st->pursuer[0]; hs.pursuer[1] = st->pursuer[1];
   RAMP_HIP_CHECK(hipMemcpyAsync(c->r_state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
+  if (rg) CK(stage_replan_guide(c, rg, s));
   c->launches = 0;
   invalidate_calibrations(c, CAL_SCORE);      // (the replans carry their maxima in TABLE_REPLAN_CARRY: the sampling jobs' canonical table survives)
   c->e_calibrated = false;                    // (a many-episode replan that follows finds this batch's maxima in the carried table, not its own)
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   auto run = [&](bool calibrate) -> int {
-    if (!p->use_graph) return replan_body(c, p, s, calibrate);
+    if (!p->use_graph) return replan_body(c, p, s, calibrate, nullptr, rg);
     Key key;      // (every r_* buffer exists before the first capture: nothing here is optional in renew()'s sense)
     key.put(p->B); key.put(p->n_steps); key.put(p->w); key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps);
     key.put(p->sqrt_recipm1, p->n_steps); key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps);
@@ -2694,8 +2763,9 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
     key.put(p->sm_max_vel); key.put(p->n_static); key.put(p->n_dyn); key.put(p->thr_static); key.put(p->thr_pred);
     key.put(p->strength_static); key.put(p->strength_pred); key.put(p->window_static); key.put(p->n_cost); key.put(p->n_extra);
     key.put(p->cost_thr); key.put(p->w_smooth); key.put(p->w_len); key.put(c->force_x6);
+    if (rg) key_replan_guide(key, rg, p->n_steps);
     if (key.bytes != c->r_key) { drop_graphs(c->r_graph, 2); c->r_key = key.bytes; }
-    return replay(&c->r_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate); });
+    return replay(&c->r_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, nullptr, rg); });
   };
   // a one-step replan has no second table to carry its maxima in (its only evaluation reads and clears TABLE_REPLAN_CARRY): it always
   // calibrates, on the bf16x6 kernels, instead of running fp16x3 from an empty table
@@ -2710,7 +2780,7 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
     // an operand left the range the delayed scaling assumed: repeat THIS replan (same inputs) on the bf16x6 kernels and
     // start the next one with a calibration evaluation
     c->force_x6 = 1;
-    int rc = replan_body(c, p, s, false);
+    int rc = replan_body(c, p, s, false, nullptr, rg);
     c->force_x6 = 0;
     CK(rc);
     RAMP_HIP_CHECK(hipMemcpyAsync(back, c->r_result, 12, hipMemcpyDeviceToHost, s));
@@ -2724,6 +2794,7 @@ int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_stat
   if (best_out) RAMP_HIP_CHECK(hipMemcpyAsync(best_out, c->r_best, HS * 4, hipMemcpyDeviceToDevice, s));
   if (batch_out) RAMP_HIP_CHECK(hipMemcpyAsync(batch_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   if (mask_out) RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->r_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  if (rg && rg->tap_out) RAMP_HIP_CHECK(hipMemcpyAsync(rg->tap_out, c->rg_tap, 2 * n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
@@ -2740,7 +2811,13 @@ static int check_offsets(const int32_t* off, int E, const char* what, int* total
 
 int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, float* best_out, float* batch_out,
                          int32_t* mask_out, int32_t* results_host, ramp_replan_result* result_host, void* stream) {
-  RAMP_REQUIRE(c && p && ep && results_host && result_host, "null argument");
+  return ramp_replan_episodes_guided(c, p, ep, nullptr, best_out, batch_out, mask_out, results_host, result_host, stream);
+}
+
+int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, const ramp_replan_guide* rg,
+                                float* best_out, float* batch_out, int32_t* mask_out, int32_t* results_host,
+                                ramp_replan_result* result_host, void* stream) {
+  RAMP_REQUIRE(c && p && ep && results_host && result_host, rg ? "ramp_replan_episodes_guided: null argument" : "null argument");
   RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
   const int B = p->B, E = ep->n_episodes, H = c->cfg.horizon, S = c->cfg.state_dim;
   RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
@@ -2765,11 +2842,15 @@ int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_ep
   RAMP_REQUIRE(!any_near || p->n_extra == 0 || ep->extra_pts_host, "missing pursuer points");
   RAMP_REQUIRE(ep->x_clean || (c->e_best && c->e_best_E == E), "no current plans: pass x_clean on the first call");
   for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
+  bool guided = false;
+  CK(check_replan_job_guide(c, p, rg, E, "ramp_replan_episodes_guided", &guided));
+  if (!guided) rg = nullptr;
   hipStream_t s = as_stream(stream);
   const size_t HS = (size_t)H * S, n = (size_t)B * HS, nE = (size_t)E * HS;
   const int P_cost = n_cost + E * p->n_extra;
   // ---- fixed buffers the graphs read
   CK(ensure_sampler_buffers(c, B, p->n_rp, 0, false));
+  if (rg) CK(grow_replan_guide(c, rg, B));
   if (!c->e_hard_idx) CK(renew(c, c->e_hard_idx, 16));
   if ((size_t)B > c->e_cap_B) {
     CK(renew(c, c->e_noise, n)); CK(renew(c, c->e_plen, B)); CK(renew(c, c->e_smooth, B));
@@ -2821,13 +2902,14 @@ int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_ep
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hard_val, p->hard_val, (size_t)p->n_hard * B * S * 4, hipMemcpyDeviceToDevice, s));
   }
+  if (rg) CK(stage_replan_guide(c, rg, s));
   c->launches = 0;
   invalidate_calibrations(c, CAL_SCORE);
   c->r_calibrated = false;                    // (the carried table now holds this batch's maxima)
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const EpisodeJob ej{E, P_static, P_cost};
   auto run = [&](bool calibrate) -> int {
-    if (!p->use_graph) return replan_body(c, p, s, calibrate, &ej);
+    if (!p->use_graph) return replan_body(c, p, s, calibrate, &ej, rg);
     Key key;      // everything baked into the nodes: ramp_replan's fields, the episode count, the row table and the clouds' totals
     key.put(p->B); key.put(p->n_steps); key.put(p->w); key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps);
     key.put(p->sqrt_recipm1, p->n_steps); key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps);
@@ -2837,8 +2919,9 @@ int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_ep
     key.put(p->strength_static); key.put(p->strength_pred); key.put(p->window_static); key.put(p->n_extra);
     key.put(p->cost_thr); key.put(p->w_smooth); key.put(p->w_len); key.put(c->force_x6);
     key.put(E); key.put(ep->traj_first_host, (size_t)E + 1); key.put(P_static); key.put(P_cost);
+    if (rg) key_replan_guide(key, rg, p->n_steps);
     if (key.bytes != c->e_key) { drop_graphs(c->e_graph, 2); c->e_key = key.bytes; }
-    return replay(&c->e_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, &ej); });
+    return replay(&c->e_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, &ej, rg); });
   };
   CK(run(h3 && (!c->e_calibrated || p->n_steps == 1)));
   // ---- the one read-back: E result records + the range flag
@@ -2852,7 +2935,7 @@ int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_ep
     // winners in e_best: back to the plans it started from first, which is what an episode that selects nothing keeps
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_best, c->e_xclean, nE * 4, hipMemcpyDeviceToDevice, s));
     c->force_x6 = 1;
-    int rc = replan_body(c, p, s, false, &ej);
+    int rc = replan_body(c, p, s, false, &ej, rg);
     c->force_x6 = 0;
     CK(rc);
     const int flag = back[4 * E];
@@ -2870,6 +2953,7 @@ int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_ep
   if (best_out) RAMP_HIP_CHECK(hipMemcpyAsync(best_out, c->e_best, nE * 4, hipMemcpyDeviceToDevice, s));
   if (batch_out) RAMP_HIP_CHECK(hipMemcpyAsync(batch_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   if (mask_out) RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->e_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  if (rg && rg->tap_out) RAMP_HIP_CHECK(hipMemcpyAsync(rg->tap_out, c->rg_tap, 2 * n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

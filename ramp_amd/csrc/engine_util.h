@@ -131,6 +131,48 @@ GuideArgs guide_args(const ramp_cost_guide* cg, float* traj, int B, int H, int S
   return a;
 }
 
+// what the guided replans, ramp_guide_step_moving and ramp_guide_cost_moving (`who`) require of a replan guide on (H, S) rows: host checks
+// only, made before anything is staged or launched.  n_scenes > 0: the scene count the job asks for; n_steps > 0: a job, whose n_guide /
+// step tables are checked too and whose guide iterations are counted into *total
+int check_replan_guide(const ramp_replan_guide* rg, int n_scenes, int H, int S, int n_steps, const char* who, int* total = nullptr) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(rg, w + "null replan guide");
+  RAMP_REQUIRE(H <= 128, w + "the guide kernel serves horizons up to 128");
+  RAMP_REQUIRE(S >= 2, w + "state_dim must be at least 2");
+  RAMP_REQUIRE(rg->n_mov >= 0 && rg->n_mov <= 1024, w + "n_mov outside 0 .. 1024");
+  RAMP_REQUIRE(rg->n_scenes >= 1 && (n_scenes <= 0 || rg->n_scenes == n_scenes), w + "the guide's n_scenes must be 1 for one episode and the episode count for many");
+  RAMP_REQUIRE(std::isfinite(rg->radius) && std::isfinite(rg->radius_mov) && std::isfinite(rg->w_obs) && std::isfinite(rg->w_mov) &&
+               std::isfinite(rg->w_smooth) && std::isfinite(rg->w_acc) && std::isfinite(rg->max_norm),
+               w + "radius, radius_mov, w_obs, w_mov, w_smooth, w_acc and max_norm must be finite");
+  RAMP_REQUIRE(rg->w_obs == 0.0 || rg->radius > 0.0, w + "radius must be positive where w_obs != 0");
+  RAMP_REQUIRE(rg->w_mov == 0.0 || rg->n_mov == 0 || rg->radius_mov > 0.0, w + "radius_mov must be positive where w_mov != 0 and n_mov > 0");
+  RAMP_REQUIRE(rg->cloud_offset_host && rg->cloud_offset_host[0] == 0, w + "bad cloud table (offsets from 0)");
+  for (int i = 0; i < rg->n_scenes; ++i)
+    RAMP_REQUIRE(rg->cloud_offset_host[i + 1] >= rg->cloud_offset_host[i], w + "cloud offsets must be non-decreasing");
+  RAMP_REQUIRE(rg->cloud_offset_host[rg->n_scenes] == 0 || rg->cloud_points, w + "null cloud_points with a non-empty table");
+  RAMP_REQUIRE(rg->n_mov == 0 || (rg->mov_points_host && rg->mov_track_host), w + "null moving points or track with n_mov > 0");
+  if (n_steps > 0) {
+    RAMP_REQUIRE(rg->n_guide && rg->step, w + "missing n_guide / step arrays");
+    int sum = 0;
+    for (int j = 0; j < n_steps; ++j) {
+      RAMP_REQUIRE(rg->n_guide[j] >= 0 && rg->n_guide[j] <= RAMP_GUIDE_MAX_STEPS, w + "n_guide outside 0 .. RAMP_GUIDE_MAX_STEPS");
+      RAMP_REQUIRE(std::isfinite(rg->step[j]), w + "step sizes must be finite");
+      sum += rg->n_guide[j];
+    }
+    if (total) *total = sum;
+  }
+  return 0;
+}
+// the kernel's arguments from a checked replan guide; the table pointers (clouds, offsets, moving points, track, scene), the pins and the
+// hard conditions are the caller's to fill
+MovingGuideArgs moving_guide_args(const ramp_replan_guide* rg, float* traj, int B, int H, int S) {
+  MovingGuideArgs a; a.traj = traj; a.B = B; a.H = H; a.S = S; a.n_scenes = rg->n_scenes; a.n_mov = rg->n_mov;
+  a.P_total = rg->cloud_offset_host[rg->n_scenes];
+  a.radius = (float)rg->radius; a.radius_mov = (float)rg->radius_mov; a.w_obs = (float)rg->w_obs; a.w_mov = (float)rg->w_mov;
+  a.w_smooth = (float)rg->w_smooth; a.w_acc = (float)rg->w_acc; a.max_norm = (float)rg->max_norm;
+  return a;
+}
+
 }  // namespace
 }  // namespace ramp
 

@@ -191,6 +191,55 @@ int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ra
   return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
 }
 
+// the replans' guide kernels on the caller's arrays: offsets | hard-condition indices | moving points | tracks go to the device in one block
+// of their own (synchronises `stream`)
+static int moving_guide_op(MovingGuideArgs a, const ramp_replan_guide* rg, const int32_t* traj_scene, const int32_t* pin_first, int32_t n_hard,
+                           const int32_t* hard_idx_host, const float* hard_val, double* terms_out, hipStream_t s) {
+  static_assert(sizeof(float) == sizeof(int32_t), "one block of 4-byte words");
+  const size_t n_off = (size_t)rg->n_scenes + 1, n_mv = (size_t)rg->n_scenes * rg->n_mov * 2, n_tr = rg->n_mov ? (size_t)rg->n_scenes * a.H * 2 : 0;
+  std::vector<int32_t> blk(n_off + n_hard + n_mv + n_tr);
+  std::memcpy(blk.data(), rg->cloud_offset_host, n_off * 4);
+  if (n_hard) std::memcpy(blk.data() + n_off, hard_idx_host, (size_t)n_hard * 4);
+  if (n_mv) std::memcpy(blk.data() + n_off + n_hard, rg->mov_points_host, n_mv * 4);
+  if (n_tr) std::memcpy(blk.data() + n_off + n_hard + n_mv, rg->mov_track_host, n_tr * 4);
+  int32_t* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, blk.size() * 4));
+  int rc = 0;
+  if (hipMemcpy(d, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("moving guide: copy of the tables failed"); rc = -1; }
+  a.cloud = rg->cloud_points; a.cloud_off = d; a.scene = traj_scene; a.pin_first = pin_first;
+  a.hc.idx = d + n_off; a.hc.val = hard_val; a.hc.n = n_hard;
+  a.mov = reinterpret_cast<const float*>(d + n_off + n_hard); a.track = a.mov + n_mv;
+  if (rc == 0) rc = terms_out ? launch_guide_cost_moving(a, terms_out, s) : launch_guide_step_moving(a, s);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(d);
+  return rc;
+}
+
+int ramp_guide_step_moving(float* traj, int32_t B, int32_t H, int32_t S, const ramp_replan_guide* rg, const int32_t* traj_scene,
+                           const int32_t* pin_first, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
+                           const float* hard_val, void* stream) {
+  RAMP_REQUIRE(traj && rg, "ramp_guide_step_moving: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0, "ramp_guide_step_moving: bad dims");
+  CK(check_replan_guide(rg, 0, H, S, 0, "ramp_guide_step_moving"));
+  RAMP_REQUIRE(n_iter >= 0 && n_iter <= RAMP_GUIDE_MAX_STEPS, "ramp_guide_step_moving: n_iter outside 0 .. RAMP_GUIDE_MAX_STEPS");
+  RAMP_REQUIRE(std::isfinite(step), "ramp_guide_step_moving: step must be finite");
+  RAMP_REQUIRE(n_hard >= 0 && n_hard <= 256 && (n_hard == 0 || (hard_idx_host && hard_val)), "ramp_guide_step_moving: bad hard conditions");
+  for (int j = 0; j < n_hard; ++j) RAMP_REQUIRE(hard_idx_host[j] >= 0 && hard_idx_host[j] < H, "ramp_guide_step_moving: hard index out of range");
+  if (n_iter == 0) return 0;
+  MovingGuideArgs a = moving_guide_args(rg, traj, B, H, S);
+  a.n_iter = n_iter; a.step = step;
+  return moving_guide_op(a, rg, traj_scene, pin_first, n_hard, hard_idx_host, hard_val, nullptr, as_stream(stream));
+}
+
+int ramp_guide_cost_moving(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_replan_guide* rg, const int32_t* traj_scene,
+                           double* terms_out, void* stream) {
+  RAMP_REQUIRE(traj && rg && terms_out, "ramp_guide_cost_moving: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0, "ramp_guide_cost_moving: bad dims");
+  CK(check_replan_guide(rg, 0, H, S, 0, "ramp_guide_cost_moving"));
+  return moving_guide_op(moving_guide_args(rg, const_cast<float*>(traj), B, H, S), rg, traj_scene, nullptr, 0, nullptr, nullptr, terms_out,
+                         as_stream(stream));
+}
+
 // steps 3 and 4 of a resampling event on the caller's arrays, in place: one block of scratch {cum | tmp | x's second buffer | group table |
 // ancestors} of its own (synchronises `stream`)
 int ramp_resample_groups(float* x, int32_t B, int32_t H, int32_t S, double* logw, double* c_prev, const int32_t* group_first_host,

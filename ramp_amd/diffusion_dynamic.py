@@ -283,7 +283,43 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         st.pursuer[0], st.pursuer[1] = float(np.float32(centre[0])), float(np.float32(centre[1]))
         st.near = int(near)
         st.extra_pts_host = extra.ctypes.data if near else None
-        return st, near, (dyn, extra)
+        return st, near, (dyn, extra, centre)
+
+    # ------------------------------------------------------------------ cost guidance inside the replans (replan_guide=)
+    def _replan_guide_setup(self, replan_guide, low, clouds, arrays: _HostArrays):
+        """``replan_guide=`` of an episode (``clouds``: one static cost cloud) or of a many-episode job (one per episode) as a
+        ramp_replan_guide whose moving points and tracks are filled per replan by ``_replan_guide_update``.  Returns None without a guide
+        iteration anywhere (the unguided job), else a namespace (rg, tab, mov, track, prev) that owns every table."""
+        from types import SimpleNamespace
+        from .guide import cloud_table, fill_replan_guide, replan_guide_tables
+        tab = replan_guide_tables(replan_guide, low)
+        self.last_replan_guide = []
+        if tab['total'] == 0:
+            return None
+        E, H = len(clouds), self.model.n_support_points
+        own = tab['cloud']
+        if own is not None:
+            own = list(own) if isinstance(own, (list, tuple)) else [own] * E
+            if len(own) != E:
+                raise ValueError(f"replan_guide=: cloud has {len(own)} entries for {E} episodes")
+            clouds = own
+        points, off, d = cloud_table(clouds, self._device())
+        if d != 2:
+            raise ValueError("replan_guide=: the replanning jobs are 2-D; the guide cloud must be (P, 2)")
+        n_mov = int(self.apf_dynamic['points_per_obstacle'])
+        mov, track = np.zeros((E, n_mov, 2), np.float32), np.zeros((E, H, 2), np.float32)
+        rg = fill_replan_guide(arrays.keep(points), arrays.keep(off), mov, track, tab)
+        rg.n_guide, rg.step = arrays.i32(tab['n_guide']), arrays.f32(tab['step'])
+        return SimpleNamespace(rg=rg, tab=tab, mov=mov, track=track, prev=[None] * E)
+
+    @staticmethod
+    def _replan_guide_update(gs, e, centre, dyn, plan_xy, stepp):
+        """Episode ``e``'s moving cloud (the pursuer's sphere cloud of this environment step, as fp32) and its predicted track, in place in
+        the guide's host tables; no random numbers."""
+        from .guide import predict_track
+        gs.mov[e] = dyn
+        gs.track[e] = predict_track(gs.tab['predict'], centre, gs.prev[e], plan_xy, stepp)
+        gs.prev[e] = np.array(centre, np.float64)
 
     def _replan_from_scratch(self, ep: _Episode, nb, shape, hard_conds, context, traj_normalized, k, cost_cloud):
         """One round of the reference's from-scratch re-plan (:591-605) with ``nb`` candidates: the winner, or None."""
@@ -322,7 +358,7 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1,
-                           max_iteration=60, **sample_kwargs):
+                           max_iteration=60, replan_guide=None, **sample_kwargs):
         """Pursuit-evasion receding-horizon planner (diffusion_model_dynamic.py:495-624), MI355X-shaped: the 10-step
         high-level plan is ONE ``ramp_sample`` job and every replan ONE ``ramp_replan`` graph replay (q_sample of the
         current plan, 5 DDIM steps with the executed history / goal pinned, smoothing, static + pursuer APF on the last
@@ -330,7 +366,11 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         trajectory as the only read-backs.  Host work per replan is what the reference leaves to the environment: the
         pursuer's dynamics callback (fed x[:, stepp, :2], i.e. the pinned executed state, known before the replan starts),
         its re-sampled sphere cloud (numpy RNG, same call order as the reference) and the termination test.
-        ``self.replan_log`` (a list, optional) receives every batch handed to a selection, for the parity tests."""
+        ``self.replan_log`` (a list, optional) receives every batch handed to a selection, for the parity tests.
+        ``replan_guide=`` (a dict, ``ramp_amd.guide.replan_guide_tables``): cost-gradient steps inside every replan's graph
+        (``ramp_replan_guided``) against the static cost cloud and the pursuer's sphere cloud moved along a predicted track;
+        ``self.last_replan_guide`` then lists the (H, 2) track of every replan.  The reference's ``guide`` / ``n_guide_steps`` /
+        ``t_start_guide`` stay accepted and ignored, as there.  The high-level plan and the from-scratch fallback are not guided."""
         from types import SimpleNamespace
         from . import dist as rdist
         import torch.distributed as tdist
@@ -343,6 +383,8 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         # (12 bytes per candidate all-gathered, the winner's owner broadcasts its trajectory: ramp_amd.dist.select_best_sharded),
         # so all ranks execute the same plan and feed the same environment
         sharded = tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1
+        if replan_guide is not None and sharded:
+            raise NotImplementedError("replan_guide= under a multi-rank process group: sharding a guided replan is out of scope")
         # 1. set-up
         ep = _Episode(context, hard_conds, obstacle_pts, device, return_chain)
         cost_cloud = ep.cloud.reshape(-1, 2).to(torch.float32).contiguous()
@@ -357,7 +399,9 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         best_host = x_plan.cpu().numpy()
         # 3. STAGE II: the replan's parameters
         arrays = _HostArrays()
-        p = self._replan_params(B, ts[-self.ddim_num_inference_steps_low:], hard_conds, cost_cloud, ep.thr_low, arrays)
+        low = ts[-self.ddim_num_inference_steps_low:]
+        p = self._replan_params(B, low, hard_conds, cost_cloud, ep.thr_low, arrays)
+        gs = self._replan_guide_setup(replan_guide, low, [cost_cloud], arrays) if replan_guide is not None else None
         x_clean = x_plan.contiguous()
         want_batch = log is not None or sharded
         batch = torch.empty((B, H, S), device=device) if want_batch else None
@@ -365,12 +409,15 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
             # 4. the environment step
             noise = torch.randn_like(xb)                           # q_sample's randn_like(x_start)
             st, near, _host = self._replan_state(p, k, context, ep, B, best_host, noise, x_clean, hist_dev)
+            if gs is not None:
+                self._replan_guide_update(gs, 0, _host[2], _host[0], best_host[:, :2], ep.stepp)
+                self.last_replan_guide.append(gs.track[0].copy())
             # 5. the replan: one graph replay
             res = _lib.RampReplanResult()
             with torch.cuda.device(device):
-                _lib.check(lib.ramp_replan(m.ctx(), C.byref(p), C.byref(st), _lib.ptr(sel.best), _lib.ptr(batch),
-                                           _lib.ptr(sel.mask) if want_batch else None, C.byref(res), _lib.current_stream()),
-                           "ramp_replan")
+                _lib.check(lib.ramp_replan_guided(m.ctx(), C.byref(p), C.byref(st), C.byref(gs.rg) if gs is not None else None,
+                                                  _lib.ptr(sel.best), _lib.ptr(batch), _lib.ptr(sel.mask) if want_batch else None,
+                                                  C.byref(res), _lib.current_stream()), "ramp_replan_guided")
             if res.fell_back:
                 self.range_fallbacks += 1
                 warnings.warn(f"fp16x3 range guard tripped at GEMM call site {res.fell_back - 1}: replan repeated in bf16x6")
@@ -491,7 +538,7 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
 
     @torch.no_grad()
     def run_inference_episodes(self, contexts, hard_conds, obstacle_pts, n_samples=35, rngs=None, return_chain=False,
-                               max_iteration=60, traj_normalized=None):
+                               max_iteration=60, traj_normalized=None, replan_guide=None):
         """MANY pursuit-evasion episodes in ONE job per replan iteration: the loop over contexts and experiments of the reference's
         scripts/inference/inference_dynamic.py (``run_multiple_experiments``: one ``run_inference`` per episode, each up to 60 replans of
         35 candidates) advanced in lock-step, so that a replan is E x n rows wide instead of n.
@@ -511,6 +558,8 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         so the job's scene table is installed again afterwards and the next call calibrates.
         ``self.replan_log`` (a list, optional) receives one entry per selection and episode: ``episode``, ``active``, ``record`` (the
         episode's result record of that call) and, for an active episode, ``batch``, ``npts``, ``idx``, ``free``.
+        ``replan_guide=``: as in ``ddim_p_sample_loop``, one launch per guided DDIM step for all episodes (``ramp_replan_episodes_guided``);
+        ``cloud`` may list one static guide cloud per episode; ``self.last_replan_guide`` lists the (E, H, 2) tracks of every call.
 
         Returns a list with, per episode, what ``run_inference`` returns: ``(chain (iters, 1, H, S), chain_obs, chain_start)`` if
         ``return_chain`` else the final plan (1, H, S).  Raises ``NotImplementedError`` under a multi-rank process group and
@@ -576,6 +625,9 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         arrays = _HostArrays()
         p = self._replan_params(B, ts[-self.ddim_num_inference_steps_low:], hard, cost_cloud, eps[0].thr_low, arrays)
         p.cost_cloud, p.n_cost = None, 0                      # (the clouds come per episode)
+        gs = None
+        if replan_guide is not None:
+            gs = self._replan_guide_setup(replan_guide, ts[-self.ddim_num_inference_steps_low:], clouds, arrays)
         n_dyn, n_extra = p.n_dyn, p.n_extra
         state = (_lib.RampEpisodeState * E)()
         dyn = np.zeros((E, n_dyn, 2), np.float64)
@@ -610,6 +662,10 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
                     extra[e] = extra_e
                 state[e].n_hist, state[e].stepp = len(ep.executed_history), ep.stepp
                 state[e].pursuer[0], state[e].pursuer[1] = float(np.float32(centre[0])), float(np.float32(centre[1]))
+                if gs is not None:
+                    self._replan_guide_update(gs, e, centre, dyn[e], best_host[e][:, :2], ep.stepp)
+            if gs is not None:
+                self.last_replan_guide.append(gs.track.copy())
             if static_pts is None:                                 # (every field exists after the first step: all episodes start active)
                 static_pts = torch.cat([f._static_dev for f in fields]).contiguous()
                 static_off = np.concatenate([[0], np.cumsum([f._static_dev.shape[0] for f in fields])]).astype(np.int32)
@@ -618,9 +674,10 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
             # 5. the replan of all episodes: one graph replay
             rr = _lib.RampReplanResult()
             with torch.cuda.device(device):
-                _lib.check(lib.ramp_replan_episodes(m.ctx(), C.byref(p), C.byref(eb), _lib.ptr(best), _lib.ptr(batch),
-                                                    _lib.ptr(mask) if want_batch else None, results.ctypes.data_as(_lib.c_i32p),
-                                                    C.byref(rr), _lib.current_stream()), "ramp_replan_episodes")
+                _lib.check(lib.ramp_replan_episodes_guided(m.ctx(), C.byref(p), C.byref(eb), C.byref(gs.rg) if gs is not None else None,
+                                                           _lib.ptr(best), _lib.ptr(batch), _lib.ptr(mask) if want_batch else None,
+                                                           results.ctypes.data_as(_lib.c_i32p), C.byref(rr), _lib.current_stream()),
+                           "ramp_replan_episodes_guided")
             if rr.fell_back:
                 self.range_fallbacks += 1
                 warnings.warn(f"fp16x3 range guard tripped at GEMM call site {rr.fell_back - 1}: replan repeated in bf16x6")
@@ -664,7 +721,7 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
         if sample_kwargs.get('mcmc') is not None:
             raise NotImplementedError("mcmc=: DynamicGaussianDiffusionModel has no Langevin refinement (the replanning jobs are out of scope)")
         if sample_kwargs.get('cost_guide') is not None:
-            raise NotImplementedError("cost_guide=: DynamicGaussianDiffusionModel has no cost guide (the replanning jobs are out of scope)")
+            raise NotImplementedError("cost_guide=: DynamicGaussianDiffusionModel has no cost guide of the sampling jobs' kind (the replanning jobs take replan_guide=)")
         if sample_kwargs.get('resample') is not None:
             raise NotImplementedError("resample=: DynamicGaussianDiffusionModel has no resampling (the replanning jobs are out of scope)")
         for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):

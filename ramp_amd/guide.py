@@ -1,6 +1,10 @@
 """Cost-gradient guidance on the HIP kernels: thin wrappers of ``ramp_guide_step`` / ``ramp_guide_cost`` and the cloud table that
 ``ramp_cost_guide`` carries (include/ramp_hip.h states the cost and one guide iteration).  Inside a sampling job the same kernel runs through
-``cost_guide=`` of ``run_inference*`` (``ramp_amd.diffusion.guide_tables``, ``ramp_sample_guided``)."""
+``cost_guide=`` of ``run_inference*`` (``ramp_amd.diffusion.guide_tables``, ``ramp_sample_guided``).
+
+The replanning jobs have a guide of their own (``ramp_replan_guide``: a moving-cloud term with a per-waypoint track, per-episode pins):
+``moving_guide_step`` / ``moving_guide_terms`` wrap its kernel-level entries, ``replan_guide_tables`` and ``predict_track`` are the host side of
+``replan_guide=`` of the dynamic model's entry points."""
 from __future__ import annotations
 
 import ctypes as C
@@ -99,4 +103,157 @@ def cost_guide_terms(x: torch.Tensor, cloud_or_clouds: Union[torch.Tensor, Seque
     with torch.cuda.device(dev):
         _lib.check(_lib.load().ramp_guide_cost(_lib.ptr(xx), B, H, S, C.byref(cg), _lib.ptr(ts), _lib.ptr(out), _lib.current_stream()),
                    "ramp_guide_cost")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- the replanning jobs' guide
+REPLAN_GUIDE_SCALARS = ('radius', 'radius_mov', 'w_obs', 'w_mov', 'w_smooth', 'w_acc', 'max_norm')
+REPLAN_GUIDE_KEYS = ('radius', 'step', 'radius_moving', 'w_obs', 'w_moving', 'w_smooth', 'w_acc', 'max_norm', 'n_steps', 't_start', 'cloud', 'predict')
+PREDICTORS = ('hold', 'constant_velocity')
+
+
+def replan_guide_tables(g, low_steps: Sequence[int]) -> dict:
+    """``replan_guide=`` checked and expanded over the low-level DDIM steps ``low_steps`` of a replan: the seven scalars, ``n_guide`` /
+    ``step`` per DDIM step (``n_steps`` iterations on the steps with ``t < t_start``; the default ``t_start = 1`` guides the last step only),
+    ``total``, ``predict`` and ``cloud``."""
+    if not isinstance(g, dict):
+        raise TypeError(f"replan_guide= takes a dict; got {type(g).__name__}")
+    unknown = sorted(set(g) - set(REPLAN_GUIDE_KEYS))
+    if unknown:
+        raise ValueError(f"replan_guide=: unknown keys {unknown}; known: {list(REPLAN_GUIDE_KEYS)}")
+    for k in ('radius', 'step'):
+        if g.get(k) is None:
+            raise ValueError(f"replan_guide=: {k}= is required")
+    tab = dict(radius=float(g['radius']), radius_mov=float(g.get('radius_moving', g['radius'])), w_obs=float(g.get('w_obs', 1.0)),
+               w_mov=float(g.get('w_moving', 1.0)), w_smooth=float(g.get('w_smooth', 0.0)), w_acc=float(g.get('w_acc', 0.0)),
+               max_norm=float(g.get('max_norm', 0.0)))
+    step, n_steps, t_start = float(g['step']), int(g.get('n_steps', 1)), float(g.get('t_start', 1))
+    if not all(np.isfinite(v) for v in tab.values()) or not np.isfinite(step):
+        raise ValueError("replan_guide=: the scalars and step must be finite")
+    if (tab['w_obs'] != 0 and tab['radius'] <= 0) or (tab['w_mov'] != 0 and tab['radius_mov'] <= 0):
+        raise ValueError("replan_guide=: radius (radius_moving) must be positive where w_obs (w_moving) is not 0")
+    if not 0 <= n_steps <= _lib.GUIDE_MAX_STEPS:
+        raise ValueError(f"replan_guide=: n_steps outside 0 .. {_lib.GUIDE_MAX_STEPS}")
+    if np.isnan(t_start):
+        raise ValueError("replan_guide=: t_start must not be NaN")
+    predict = g.get('predict', 'constant_velocity')
+    if not callable(predict) and predict not in PREDICTORS:
+        raise ValueError(f"replan_guide=: unknown predict {predict!r}; known: {list(PREDICTORS)} or a callable")
+    tab['n_guide'] = [n_steps if t < t_start else 0 for t in low_steps]
+    tab['step'] = [step] * len(low_steps)
+    tab['total'] = sum(tab['n_guide'])
+    tab['predict'], tab['cloud'] = predict, g.get('cloud')
+    return tab
+
+
+def predict_track(predict, centre_now, centre_prev, plan_xy, stepp: int) -> np.ndarray:
+    """The track (H, 2) float32 of a moving cloud: its displacement at waypoint h of the plan ``plan_xy`` (H, 2) whose waypoint ``stepp`` is now.
+    'hold': zeros.  'constant_velocity': max(0, h - stepp) (centre_now - centre_prev), zeros without a previous centre (an episode's first
+    replan).  A callable ``(centre_now, centre_prev or None, plan_xy, stepp) -> (H, 2)``.  Draws no random numbers."""
+    H = int(np.asarray(plan_xy).shape[0])
+    if callable(predict):
+        tr = np.asarray(predict(centre_now, centre_prev, plan_xy, stepp))
+        if tr.shape != (H, 2):
+            raise ValueError(f"replan_guide=: predict returned shape {tuple(tr.shape)}; wanted ({H}, 2)")
+        if not np.isfinite(tr).all():
+            raise ValueError("replan_guide=: predict returned non-finite displacements")
+        return np.ascontiguousarray(tr, np.float32)
+    if predict == 'hold' or (predict == 'constant_velocity' and centre_prev is None):
+        return np.zeros((H, 2), np.float32)
+    if predict != 'constant_velocity':
+        raise ValueError(f"replan_guide=: unknown predict {predict!r}; known: {list(PREDICTORS)} or a callable")
+    v = np.asarray(centre_now, np.float64)[:2] - np.asarray(centre_prev, np.float64)[:2]
+    ahead = np.maximum(0, np.arange(H) - int(stepp)).astype(np.float64)
+    return np.ascontiguousarray(ahead[:, None] * v[None, :], np.float32)
+
+
+def fill_replan_guide(points, offsets: np.ndarray, moving: Optional[np.ndarray], track: Optional[np.ndarray],
+                      scalars: Dict[str, float]) -> _lib.RampReplanGuide:
+    """``ramp_replan_guide`` without its per-step tables and tap: ``points`` device (sum P, 2) or None, ``offsets`` host int32
+    (n_scenes + 1), ``moving`` host float32 (n_scenes, n_mov, 2) or None, ``track`` host float32 (n_scenes, H, 2) or None; the caller keeps all
+    four alive for the call."""
+    rg = _lib.RampReplanGuide()
+    rg.n_scenes = len(offsets) - 1
+    rg.n_mov = 0 if moving is None else int(moving.shape[1])
+    rg.cloud_points = _lib.ptr(points)
+    rg.cloud_offset_host = offsets.ctypes.data_as(_lib.c_i32p)
+    if rg.n_mov:
+        assert moving.dtype == np.float32 and track.dtype == np.float32 and moving.flags.c_contiguous and track.flags.c_contiguous
+        assert moving.shape[0] == rg.n_scenes and track.shape[0] == rg.n_scenes
+        rg.mov_points_host = moving.ctypes.data_as(_lib.c_f32p)
+        rg.mov_track_host = track.ctypes.data_as(_lib.c_f32p)
+    for k in REPLAN_GUIDE_SCALARS:
+        setattr(rg, k, float(scalars.get(k, 0.0)))
+    return rg
+
+
+def _moving_tables(clouds, moving, track, H: int, dev):
+    points, off, d = cloud_table(clouds, dev)
+    if d != 2:
+        raise ValueError("moving guide: the replanning jobs are 2-D; every cloud must be (P, 2)")
+    n_scenes = len(off) - 1
+    mv = tr = None
+    if moving is not None:
+        mv = np.ascontiguousarray(torch.as_tensor(moving).detach().cpu().numpy(), np.float32)
+        mv = mv[None] if mv.ndim == 2 else mv
+        if mv.ndim != 3 or mv.shape[0] != n_scenes or mv.shape[2] != 2:
+            raise ValueError(f"moving guide: moving must be ({n_scenes}, M, 2); got {tuple(mv.shape)}")
+        if mv.shape[1] == 0:
+            mv = None
+    if mv is not None:
+        tr = np.zeros((n_scenes, H, 2), np.float32) if track is None else np.ascontiguousarray(torch.as_tensor(track).detach().cpu().numpy(), np.float32)
+        tr = tr[None] if tr.ndim == 2 else tr
+        if tr.shape != (n_scenes, H, 2):
+            raise ValueError(f"moving guide: track must be ({n_scenes}, {H}, 2); got {tuple(tr.shape)}")
+    return points, off, mv, tr
+
+
+@torch.no_grad()
+def moving_guide_step(x: torch.Tensor, cloud_or_clouds, moving, track, radius: float, step: float, radius_moving: Optional[float] = None,
+                      w_obs: float = 1.0, w_moving: float = 1.0, w_smooth: float = 0.0, w_acc: float = 0.0, n_steps: int = 1,
+                      max_norm: float = 0.0, hard_conds: Optional[Dict[int, torch.Tensor]] = None, traj_scene=None, pin_first=None) -> torch.Tensor:
+    """``n_steps`` iterations of the replans' guide (one launch, ``ramp_guide_step_moving``) on a copy of the (B, H, S) rows ``x``.
+    ``cloud_or_clouds``: one static (P, 2) cloud or one per scene with ``traj_scene`` (B,); ``moving`` (n_scenes, M, 2) (or (M, 2) for one
+    scene, None = no moving term) the moving clouds now, ``track`` (n_scenes, H, 2) their displacement per waypoint (None = zeros).
+    ``pin_first`` (B,) int: waypoints below it and waypoint H - 1 are pinned, with those of ``hard_conds`` (whose values win in the working
+    copy; later entries win)."""
+    dev = x.device
+    out = x.detach().to(torch.float32).contiguous().clone()
+    B, H, S = out.shape
+    points, off, mv, tr = _moving_tables(_as_clouds(cloud_or_clouds), moving, track, H, dev)
+    rg = fill_replan_guide(points, off, mv, tr, dict(radius=radius, radius_mov=radius if radius_moving is None else radius_moving, w_obs=w_obs,
+                                                     w_mov=w_moving, w_smooth=w_smooth, w_acc=w_acc, max_norm=max_norm))
+    ts = _scene_table(traj_scene, B, rg.n_scenes, dev)
+    pf = None
+    if pin_first is not None:
+        pf = torch.as_tensor(pin_first).to(dev, torch.int32).contiguous()
+        if tuple(pf.shape) != (B,):
+            raise ValueError(f"pin_first must be ({B},); got {tuple(pf.shape)}")
+    idx, val = None, None
+    hard_conds = hard_conds or {}
+    if hard_conds:
+        idx = (C.c_int32 * len(hard_conds))(*[int(k) if k >= 0 else H + int(k) for k in hard_conds])
+        vals = [torch.as_tensor(v).to(dev, torch.float32) for v in hard_conds.values()]
+        val = torch.stack([v.unsqueeze(0).expand(B, -1) if v.dim() == 1 else v for v in vals]).contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_guide_step_moving(_lib.ptr(out), B, H, S, C.byref(rg), _lib.ptr(ts), _lib.ptr(pf), int(n_steps), float(step),
+                                                      len(hard_conds), C.cast(idx, _lib.c_i32p) if idx is not None else None, _lib.ptr(val),
+                                                      _lib.current_stream()), "ramp_guide_step_moving")
+    return out
+
+
+@torch.no_grad()
+def moving_guide_terms(x: torch.Tensor, cloud_or_clouds, moving, track, radius: float, radius_moving: Optional[float] = None,
+                       traj_scene=None) -> torch.Tensor:
+    """(B, 4) float64 = the unweighted (C_obs, C_mov, C_smooth, C_acc) of each row (``ramp_guide_cost_moving``)."""
+    dev = x.device
+    xx = x.detach().to(torch.float32).contiguous()
+    B, H, S = xx.shape
+    points, off, mv, tr = _moving_tables(_as_clouds(cloud_or_clouds), moving, track, H, dev)
+    rg = fill_replan_guide(points, off, mv, tr, dict(radius=radius, radius_mov=radius if radius_moving is None else radius_moving))
+    ts = _scene_table(traj_scene, B, rg.n_scenes, dev)
+    out = torch.empty((B, 4), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_guide_cost_moving(_lib.ptr(xx), B, H, S, C.byref(rg), _lib.ptr(ts), _lib.ptr(out), _lib.current_stream()),
+                   "ramp_guide_cost_moving")
     return out

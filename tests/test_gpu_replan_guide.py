@@ -1,0 +1,579 @@
+"""Cost guidance inside the replanning jobs, with a moving-pursuer term: the kernel alone (``ramp_guide_step_moving``), the cost terms
+(``ramp_guide_cost_moving``), "off is off", the wiring into ``ramp_replan_guided`` / ``ramp_replan_episodes_guided`` by the tap (bit-exact
+against the kernel applied to the tapped x0), the many-episode job against single calls, stale graphs and ``replan_guide=`` end to end.
+
+The truth is the float64 numpy restatement of the definition in include/ramp_hip.h (tests/test_replan_guide_host.py: ``moving_iterate`` /
+``moving_terms``).  The same code in float32 is the yardstick: every bar that is not an exact statement is 4 x the float32 restatement's
+distance from the float64 one on the test's own inputs, computed on the CPU inside the test, never from the HIP result (the convention of
+test_gpu_guide.py).  The scalars and the step are fp32-representable, so both sides compute with the same numbers."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import test_replan_guide_host as R
+from ramp_amd import _lib
+from ramp_amd.apf_dynamic import generate_box_points, generate_sphere_points
+from ramp_amd.diffusion import _HostArrays
+from ramp_amd.guide import cloud_table, fill_replan_guide
+from ramp_amd.scenes import build_episode_tables
+from util import FAKE_BOX_CENTRES, GOLDEN, NoiseInjector, build_unet, dev, make_fake_pursuit_env
+
+pytestmark = pytest.mark.gpu
+
+F32 = lambda v: float(np.float32(v))      # noqa: E731
+SC = dict(radius=F32(0.35), radius_mov=F32(0.3), w_obs=1.0, w_mov=0.75, w_smooth=0.5, w_acc=0.25, max_norm=0.0)
+STEP = F32(2e-3)
+
+
+def uniform(shape, seed, lo=-1.0, hi=1.0):
+    return np.random.default_rng(seed).uniform(lo, hi, size=shape).astype(np.float32)
+
+
+def restate(x, clouds, mov, track, ts, pf, hard, sc, step, n_iter, dtype, log=None):
+    return R.moving_iterate(x, clouds, mov, track, ts, pf, hard, sc["radius"], sc["radius_mov"], sc["w_obs"], sc["w_mov"], sc["w_smooth"],
+                            sc["w_acc"], step, n_iter, sc["max_norm"], dtype, log=log)
+
+
+def guide_struct(keep, clouds, mov, track, sc):
+    """ramp_replan_guide on device clouds (list of (P, 2) arrays) and host moving points (n_scenes, M, 2) / tracks (n_scenes, H, 2)."""
+    pts, off, d = cloud_table([torch.from_numpy(np.ascontiguousarray(c, np.float32)) for c in clouds], "cuda")
+    mv = np.ascontiguousarray(mov, np.float32) if mov is not None and mov.shape[1] else None
+    tr = np.ascontiguousarray(track, np.float32) if mv is not None else None
+    keep += [pts, off, mv, tr]
+    return fill_replan_guide(pts, off, mv, tr, sc)
+
+
+def run_moving(x, clouds, mov, track, ts, pf, hard, sc, step, n_iter):
+    """ramp_guide_step_moving on a copy of x; hard = list of (waypoint, (B, S) values), in table order (a waypoint may come twice)."""
+    keep = []
+    rg = guide_struct(keep, clouds, mov, track, sc)
+    xx = dev(np.ascontiguousarray(x, np.float32)).clone()
+    B, H, S = xx.shape
+    idx = (C.c_int32 * max(1, len(hard)))(*[int(h) for h, _ in hard])
+    val = dev(np.stack([np.asarray(v, np.float32) for _, v in hard])) if hard else None
+    ts_d = None if ts is None else dev(np.asarray(ts, np.int32))
+    pf_d = None if pf is None else dev(np.asarray(pf, np.int32))
+    _lib.check(_lib.load().ramp_guide_step_moving(_lib.ptr(xx), B, H, S, C.byref(rg), _lib.ptr(ts_d), _lib.ptr(pf_d), n_iter, step, len(hard),
+                                                  C.cast(idx, _lib.c_i32p), _lib.ptr(val), _lib.current_stream()), "ramp_guide_step_moving")
+    torch.cuda.synchronize()
+    return xx.cpu().numpy()
+
+
+def run_terms(x, clouds, mov, track, ts, sc):
+    keep = []
+    rg = guide_struct(keep, clouds, mov, track, sc)
+    xx = dev(np.ascontiguousarray(x, np.float32))
+    B, H, S = xx.shape
+    out = torch.empty((B, 4), device="cuda", dtype=torch.float64)
+    _lib.check(_lib.load().ramp_guide_cost_moving(_lib.ptr(xx), B, H, S, C.byref(rg), _lib.ptr(dev(np.asarray(ts, np.int32))), _lib.ptr(out),
+                                                  _lib.current_stream()), "ramp_guide_cost_moving")
+    torch.cuda.synchronize()
+    return out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------------ 1: the kernel alone
+# (H, static P of the 3 scenes, n_mov, n_iter): every H, P, n_mov and n_iter of the issue's lists; scene 2 has no rows
+KERNEL_CASES = [(5, (0, 1, 1023), 1, 16), (48, (1024, 1025, 1), 64, 3), (128, (2049, 1023, 1024), 1024, 1), (48, (1025, 2049, 0), 0, 3)]
+TS = np.array([0] * 5 + [1] * 8, np.int32)
+_CASE = {}
+
+
+def kernel_case(case):
+    """Inputs and both restatements of one case, computed once: B = 13 rows in [-1, 1] over 3 scenes with 5, 8 and 0 rows, S = 4, uniform
+    clouds, tracks in [-0.3, 0.3], pin_first 1 / 4 / H - 1 by row, a hard condition that names waypoint H // 2 twice, max_norm the
+    geometric mean of the smallest and the largest first-iteration gradient norm (some rows clipped, others not)."""
+    if case not in _CASE:
+        H, Ps, n_mov, n_iter = case
+        seed = 3000 + KERNEL_CASES.index(case)
+        x = uniform((13, H, 4), seed)
+        clouds = [uniform((P, 2), seed + 10 + i) for i, P in enumerate(Ps)]
+        mov, track = uniform((3, n_mov, 2), seed + 20), uniform((3, H, 2), seed + 30, -0.3, 0.3)
+        pf = np.array([[1, 4, H - 1][b % 3] for b in range(13)], np.int32)
+        hard = [(H // 2, uniform((13, 4), seed + 40)), (H // 2, uniform((13, 4), seed + 41))]
+        log0 = []
+        restate(x, clouds, mov, track, TS, pf, hard, SC, STEP, 1, np.float64, log=log0)
+        norms = [n for _, _, _, n in log0 if n > 0]
+        sc = dict(SC, max_norm=F32(np.sqrt(min(norms) * max(norms))))
+        log = []
+        y64 = restate(x, clouds, mov, track, TS, pf, hard, sc, STEP, n_iter, np.float64, log=log)
+        y32 = restate(x, clouds, mov, track, TS, pf, hard, sc, STEP, n_iter, np.float32)
+        _CASE[case] = dict(x=x, clouds=clouds, mov=mov, track=track, pf=pf, hard=hard, sc=sc, y64=y64, y32=y32, log=log)
+    return _CASE[case]
+
+
+@pytest.mark.parametrize("case", KERNEL_CASES, ids=lambda c: "H%d_P%s_M%d_it%d" % (c[0], "-".join(map(str, c[1])), c[2], c[3]))
+def test_kernel_against_float64(case):
+    """ramp_guide_step_moving against the float64 restatement; bar 4 x the float32 restatement's distance (printed).  Channels 2:4 and the
+    pinned waypoints keep their bits, a row with pin_first = H - 1 comes back bit-equal, the later of two hard conditions on one waypoint
+    wins (the restatement's rule; its first would give other neighbours through the stencils), max_norm binds for some rows and not for
+    others (asserted from the float64 log), and a pair at distance exactly 0 in either cloud gives finite output."""
+    H, Ps, n_mov, n_iter = case
+    c = kernel_case(case)
+    s_first = [s for b, it, s, n in c["log"] if it == 0 and n > 0]
+    assert min(s_first) < 1.0 and max(s_first) == 1.0, s_first
+    moved, d32 = float(np.abs(c["y64"] - c["x"]).max()), float(np.abs(c["y32"] - c["y64"]).max())
+    assert moved > 1e-3 and d32 > 0
+    y = run_moving(c["x"], c["clouds"], c["mov"], c["track"], TS, c["pf"], c["hard"], c["sc"], STEP, n_iter)
+    err = float(np.abs(y - c["y64"]).max())
+    print(f"moving guide {case}: HIP {err:.2e}, float32 restatement {d32:.2e} (bar {4 * d32:.2e}); moved {moved:.2e}")
+    xb, yb = c["x"].view(np.uint32), y.view(np.uint32)
+    assert np.array_equal(yb[:, :, 2:], xb[:, :, 2:])
+    for b in range(13):
+        pinned = sorted(set(range(int(c["pf"][b]))) | {H - 1, H // 2})
+        assert np.array_equal(yb[b, pinned], xb[b, pinned]), b
+        if c["pf"][b] == H - 1:
+            assert np.array_equal(yb[b], xb[b]), b
+    n_free_rows = sum(1 for b in range(13) if c["pf"][b] < H - 1)
+    assert (yb[:, :, :2] != xb[:, :, :2]).any(axis=(1, 2)).sum() == n_free_rows >= 5      # the rows with a free waypoint did move
+    assert err <= 4 * d32
+    # a pair at distance exactly 0: a static point copied from a free waypoint of row 0, a moving point equal to fl(p - delta) there
+    clouds, mov = [cl.copy() for cl in c["clouds"]], c["mov"].copy()
+    h0 = 1 if H // 2 != 1 else 3
+    if Ps[0]:
+        clouds[0][0] = c["x"][0, h0, :2]
+    if n_mov:
+        mov[0, 0] = c["x"][0, h0, :2] - c["track"][0, h0]
+    if Ps[0] or n_mov:
+        assert np.isfinite(run_moving(c["x"], clouds, mov, c["track"], TS, c["pf"], c["hard"], c["sc"], STEP, n_iter)).all()
+
+
+# ------------------------------------------------------------------------------------------------ 2: the track
+def test_the_track_is_read_per_episode_and_per_waypoint():
+    """w_obs = w_smooth = w_acc = 0, 13 rows along the x axis (y = 0.02 b), a 16-point moving cluster at (10, 10) in both scenes and a track
+    that is zero except on waypoints 20 .. 24 of scene 1, where it carries the cluster onto the path.  Only the rows of scene 1 change, only
+    at waypoints 20 .. 24, within the bar of the float64 restatement; with the track zeroed nothing changes (exact); with the two scenes'
+    tracks swapped the effect moves to the rows of scene 0."""
+    H = 48
+    x = np.zeros((13, H, 4), np.float32)
+    x[:, :, 0] = np.linspace(-1, 1, H, dtype=np.float32)[None]
+    x[:, :, 1] = (0.02 * np.arange(13, dtype=np.float32))[:, None]
+    x += uniform(x.shape, 1, -1e-3, 1e-3)
+    mov = np.tile((np.float32([10.0, 10.0]) + uniform((16, 2), 2, -0.05, 0.05))[None], (3, 1, 1))
+    track = np.zeros((3, H, 2), np.float32)
+    for h in range(20, 25):
+        track[1, h] = np.float32([x[0, h, 0] + 0.03 - 10.0, 0.13 - 10.0])
+    clouds = [np.zeros((0, 2), np.float32)] * 3
+    sc = dict(SC, w_obs=0.0, w_smooth=0.0, w_acc=0.0)
+    pf, hard, n_iter = np.ones(13, np.int32), [], 3
+    xb = x.view(np.uint32)
+    for tr, rows, still in ((track, slice(5, 13), slice(0, 5)), (track[[1, 0, 2]], slice(0, 5), slice(5, 13))):
+        y64 = restate(x, clouds, mov, tr, TS, pf, hard, sc, STEP, n_iter, np.float64)
+        d32 = float(np.abs(restate(x, clouds, mov, tr, TS, pf, hard, sc, STEP, n_iter, np.float32) - y64).max())
+        y = run_moving(x, clouds, mov, tr, TS, pf, hard, sc, STEP, n_iter)
+        changed = (y.view(np.uint32) != xb).any(axis=2)
+        assert not changed[still].any() and not changed[:, :20].any() and not changed[:, 25:].any()
+        assert changed[rows, 20:25].all()
+        assert float(np.abs(y64 - x)[rows, 20:25].max()) > 1e-4 and d32 > 0
+        err = float(np.abs(y - y64).max())
+        print(f"track: HIP {err:.2e}, float32 restatement {d32:.2e}")
+        assert err <= 4 * d32
+    y0 = run_moving(x, clouds, mov, np.zeros_like(track), TS, pf, hard, sc, STEP, n_iter)
+    assert np.array_equal(y0.view(np.uint32), xb)
+
+
+# ------------------------------------------------------------------------------------------------ 3: batch independence
+def test_a_row_alone_is_the_row_in_the_batch():
+    case = KERNEL_CASES[1]
+    c = kernel_case(case)
+    y = run_moving(c["x"], c["clouds"], c["mov"], c["track"], TS, c["pf"], c["hard"], c["sc"], STEP, case[3])
+    b = 7
+    alone = run_moving(c["x"][b:b + 1], c["clouds"], c["mov"], c["track"], TS[b:b + 1], c["pf"][b:b + 1], [(h, v[b:b + 1]) for h, v in c["hard"]],
+                       c["sc"], STEP, case[3])
+    assert (alone.view(np.uint32) != c["x"][b:b + 1].view(np.uint32)).any()
+    assert np.array_equal(alone.view(np.uint32), y[b:b + 1].view(np.uint32))
+
+
+# ------------------------------------------------------------------------------------------------ 4: the cost terms
+@pytest.mark.parametrize("case", KERNEL_CASES, ids=lambda c: "H%d_M%d" % (c[0], c[2]))
+def test_cost_terms_against_float64(case):
+    """ramp_guide_cost_moving on the inputs of test 1 (row 3 with a scene index outside the table: NaN).  Bar, as in test 1: the largest
+    distance over the (B, 4) array <= 4 x the float32 restatement's largest distance from the float64 one.  With n_mov = 0 columns 0, 2, 3
+    are ramp_guide_cost's bits.
+    Per column (printed) the two stencil columns reproduce the float32 restatement to every digit; the two pair columns do not: the kernels'
+    square root is guide.hip's __fsqrt_rn, which hipcc maps to the hardware's v_sqrt_f32 (1 ulp, not correctly rounded like numpy's), and its
+    error does not average out over 1e4 .. 1e5 pairs.  Measured on an MI355X, C_obs column, HIP / float32 restatement: 1.3e-6 / 2.1e-7
+    (H = 48, M = 64), 6.3e-6 / 3.1e-7 (H = 128), 2.7e-6 / 2.1e-7 (H = 48, M = 0) on sums of order 1e2 -- inside the array's bar (8.3e-6,
+    1.4e-5, 7.2e-6, set by the C_acc column), outside a per-column one.  The bit-equality with ramp_guide_cost fixes the square root."""
+    H, Ps, n_mov, n_iter = case
+    c = kernel_case(case)
+    ts = TS.copy(); ts[3] = 3
+    got = run_terms(c["x"], c["clouds"], c["mov"], c["track"], ts, c["sc"])
+    assert got.dtype == np.float64 and got.shape == (13, 4)
+    assert np.isnan(got[3]).all()
+    rows = [b for b in range(13) if b != 3]
+    t64, t32 = [], []
+    for b in rows:
+        e = int(ts[b])
+        for dt, acc in ((np.float64, t64), (np.float32, t32)):
+            acc.append(R.moving_terms(c["x"][b, :, :2].astype(dt), c["clouds"][e].astype(dt), c["mov"][e].astype(dt), c["track"][e].astype(dt),
+                                      c["sc"]["radius"], c["sc"]["radius_mov"]))
+    t64, t32 = np.array(t64), np.array(t32)
+    d32, err = np.abs(t32 - t64).max(0), np.abs(got[rows] - t64).max(0)
+    print(f"cost terms {case}: HIP {err} (max {err.max():.2e}), float32 restatement {d32} (bar {4 * d32.max():.2e})")
+    assert d32.max() > 0 and err.max() <= 4 * d32.max()
+    assert (t64[:, 2:] > 0).all()
+    if n_mov == 0:
+        from ramp_amd.guide import cost_guide_terms
+        ts[3] = 0
+        got = run_terms(c["x"], c["clouds"], c["mov"], c["track"], ts, c["sc"])
+        old = cost_guide_terms(dev(c["x"]), [dev(cl) for cl in c["clouds"]], c["sc"]["radius"], traj_scene=dev(ts)).cpu().numpy()
+        assert np.array_equal(got[:, [0, 2, 3]].view(np.uint64), old.view(np.uint64)) and (got[:, 1] == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ the two-episode job
+H, S = 48, 4
+COUNTS = [5, 8]
+JOB_SC = dict(radius=F32(0.2), radius_mov=F32(0.3), w_obs=1.0, w_mov=1.0, w_smooth=0.5, w_acc=0.0, max_norm=F32(4.0))
+JOB_STEP = F32(0.02)
+
+
+class TwoEpisodes:
+    """The set-up of test_one_call_of_unequal_episodes_against_the_single_episode_path (test_gpu_episodes.py): E = 2 with 5 and 8
+    candidates, stepp (0, 3), n_hist (1, 4), replan_chain.npz's cloud and a second one, episode 1's pursuer near its evader.  The guide: the
+    episodes' cost clouds, their pursuer clouds (64 points, fp32) and tracks that carry each cloud along its episode's plan, 0.06 beside it,
+    so that the moving cloud crosses every free waypoint; guide iterations on the last DDIM step."""
+
+    def __init__(self, gemm_mode="default", noise_seed=10):
+        from ramp_amd.models import DynamicGaussianDiffusionModel
+        g = np.load(f"{GOLDEN}/replan_chain.npz")
+        self.E, self.B = len(COUNTS), sum(COUNTS)
+        u = build_unet(4, 48, False, max_rows=2 * self.B, gemm_mode=gemm_mode)
+        self.dm = DynamicGaussianDiffusionModel(model=u, n_diffusion_steps=100, predict_epsilon=True).eval().to("cuda")
+        dm, self.m, self.lib, device = self.dm, u, _lib.load(), torch.device("cuda")
+        rng = np.random.RandomState(5)
+        self.clouds = [dev(g["cloud"]), dev(np.stack([generate_box_points(c, (0.16, 0.16), 64, rng=rng) for c in FAKE_BOX_CENTRES[:5]]).astype(np.float32))]
+        self.cost = [c.reshape(-1, 2).contiguous() for c in self.clouds]
+        self.static = [dev(np.vstack([generate_box_points(c, (0.16, 0.16), n, rng=rng) for c in FAKE_BOX_CENTRES[:k]])) for k, n in ((4, 64), (3, 32))]
+        ends = [(g["hard0"], g["hardN"]), (np.float32([-0.8, 0.0, 0, 0]), np.float32([0.8, 0.1, 0, 0]))]
+        self.stepp, self.n_hist = [0, 3], [1, 4]
+        w = np.linspace(0, 1, H, dtype=np.float32)[:, None]
+        line = (1 - w) * ends[1][0][None] + w * ends[1][1][None]
+        line[1:-1, 2:] = (ends[1][1][:2] - ends[1][0][:2]) / (0.1 * (H - 1))
+        self.plans = [g["cost0/best"].astype(np.float32), line.astype(np.float32)]
+        self.x_clean = dev(np.stack(self.plans))
+        self.hist = torch.zeros((self.E, H, S), device=device)
+        for e in range(self.E):
+            self.hist[e, :self.n_hist[e]] = self.x_clean[e, :self.n_hist[e]]
+        self.centres = [self.plans[0][0, :2].astype(np.float64) + [0.7, 0.7], self.plans[1][3, :2].astype(np.float64) + [0.15, 0.1]]
+        self.near = np.array([0, 1], np.int32)
+        self.dyn = np.stack([generate_sphere_points(c, 0.1, 64, rng=rng) for c in self.centres])
+        self.extra = np.stack([generate_sphere_points(c, 0.1, 64, rng=rng) for c in self.centres]).astype(np.float32)
+        self.noise = torch.randn((self.B, H, S), device=device, generator=torch.Generator(device).manual_seed(noise_seed))
+        self.hard_e = [{0: dev(a).repeat(n, 1), H - 1: dev(b).repeat(n, 1)} for (a, b), n in zip(ends, COUNTS)]
+        self.tab = build_episode_tables(COUNTS, [dm._row_pattern(n) for n in COUNTS])
+        self.first = self.tab["traj_first"]
+        ts = [int(i) for i in dm.ddim_set_timesteps(dm.ddim_num_inference_steps_high)]
+        self.low = ts[-dm.ddim_num_inference_steps_low:]
+        self.m.prepare_time_table(dm.n_diffusion_steps)
+        self.latents = None
+        # the guide's tables
+        self.mov = np.ascontiguousarray(self.dyn, np.float32)
+        off = np.float32([[0.05, 0.03], [-0.04, 0.05]])
+        self.track = np.stack([self.plans[e][:, :2] - np.float32(self.centres[e])[None] + off[e][None] for e in range(self.E)]).astype(np.float32)
+
+    def guide(self, keep, episodes, n_iter=3, step=JOB_STEP, tap=True, mov=None, track=None, clouds=None, n_guide=None):
+        """(ramp_replan_guide, tap tensor) for the listed episodes."""
+        mov, track = self.mov if mov is None else mov, self.track if track is None else track
+        clouds = [c.cpu().numpy() for c in self.cost] if clouds is None else clouds
+        rg = guide_struct(keep, [clouds[e] for e in episodes], mov[episodes], track[episodes], JOB_SC)
+        n_guide = [0] * (len(self.low) - 1) + [n_iter] if n_guide is None else n_guide
+        arrays = _HostArrays(); keep.append(arrays)
+        rg.n_guide, rg.step = arrays.i32(n_guide), arrays.f32([step] * len(self.low))
+        rows = sum(COUNTS[e] for e in episodes)
+        tp = torch.full((2, rows, H, S), float("nan"), device="cuda") if tap else None
+        rg.tap_out = _lib.ptr(tp)
+        return rg, tp
+
+    def single(self, e, rg=None, entry="guided", fresh_scene=True):
+        """One ramp_replan_guided (or ramp_replan) call for episode e, its scene installed first (so the call calibrates)."""
+        dm, n = self.dm, COUNTS[e]
+        if fresh_scene:
+            self.m.scene_cache.clear(); self.m.invalidate_scene()
+            dm._prepare_scene(self.clouds[e], n)
+        arrays = _HostArrays()
+        p = dm._replan_params(n, self.low, self.hard_e[e], self.cost[e], 0.05, arrays)
+        p.static_pts, p.n_static = _lib.ptr(self.static[e]), self.static[e].shape[0]
+        st = _lib.RampReplanState()
+        nz = self.noise[self.first[e]:self.first[e + 1]].contiguous()
+        st.noise, st.x_clean, st.history = _lib.ptr(nz), _lib.ptr(self.x_clean[e]), _lib.ptr(self.hist[e])
+        st.n_hist, st.stepp = self.n_hist[e], self.stepp[e]
+        d, x = np.ascontiguousarray(self.dyn[e]), np.ascontiguousarray(self.extra[e])
+        st.dyn_pts_host, st.near, st.extra_pts_host = d.ctypes.data, int(self.near[e]), x.ctypes.data if self.near[e] else None
+        st.pursuer[0], st.pursuer[1] = float(np.float32(self.centres[e][0])), float(np.float32(self.centres[e][1]))
+        best, batch, mask = torch.empty((H, S), device="cuda"), torch.empty((n, H, S), device="cuda"), torch.empty(n, dtype=torch.int32, device="cuda")
+        res = _lib.RampReplanResult()
+        ctx, s = self.m.ctx(), _lib.current_stream()
+        if entry == "plain":
+            _lib.check(self.lib.ramp_replan(ctx, C.byref(p), C.byref(st), _lib.ptr(best), _lib.ptr(batch), _lib.ptr(mask), C.byref(res), s), "ramp_replan")
+        else:
+            _lib.check(self.lib.ramp_replan_guided(ctx, C.byref(p), C.byref(st), C.byref(rg) if rg is not None else None, _lib.ptr(best),
+                                                   _lib.ptr(batch), _lib.ptr(mask), C.byref(res), s), "ramp_replan_guided")
+        torch.cuda.synchronize()
+        assert res.fell_back == 0
+        return best.cpu().numpy(), batch.cpu().numpy(), mask.cpu().numpy(), [res.n_free, res.best_rank, res.best_row]
+
+    def many(self, rg=None, entry="guided", active=(1, 1)):
+        """One call for both episodes, the job's scene table installed first."""
+        dm, E, B = self.dm, self.E, self.B
+        if self.latents is None:
+            self.latents = torch.cat([self.m.encode_scene(c) for c in self.clouds] + [torch.zeros(1, self.m.context_dim, device="cuda")])
+        self.m.set_scenes(self.latents, self.tab["row_variant"])
+        hard = {k: torch.cat([h[k] for h in self.hard_e]).contiguous() for k in self.hard_e[0]}
+        cost_all, static_all = torch.cat(self.cost).contiguous(), torch.cat(self.static).contiguous()
+        cost_off, static_off = np.array([0, 384, 704], np.int32), np.array([0, 256, 352], np.int32)
+        arrays = _HostArrays()
+        p = dm._replan_params(B, self.low, hard, cost_all, 0.05, arrays)
+        p.cost_cloud, p.n_cost = None, 0
+        state = (_lib.RampEpisodeState * E)()
+        for e in range(E):
+            state[e].n_hist, state[e].stepp, state[e].active = self.n_hist[e], self.stepp[e], int(active[e])
+            state[e].pursuer[0], state[e].pursuer[1] = float(np.float32(self.centres[e][0])), float(np.float32(self.centres[e][1]))
+        eb = _lib.RampEpisodeBatch()
+        eb.n_episodes, eb.traj_first_host, eb.state_host = E, self.first.ctypes.data_as(_lib.c_i32p), state
+        eb.noise, eb.x_clean, eb.history = _lib.ptr(self.noise), _lib.ptr(self.x_clean), _lib.ptr(self.hist)
+        eb.static_pts, eb.static_offset_host = _lib.ptr(static_all), static_off.ctypes.data_as(_lib.c_i32p)
+        eb.cost_cloud, eb.cost_offset_host = _lib.ptr(cost_all), cost_off.ctypes.data_as(_lib.c_i32p)
+        eb.dyn_pts_host, eb.near_host, eb.extra_pts_host = self.dyn.ctypes.data, self.near.ctypes.data_as(_lib.c_i32p), self.extra.ctypes.data
+        best, batch, mask = torch.empty((E, H, S), device="cuda"), torch.empty((B, H, S), device="cuda"), torch.empty(B, dtype=torch.int32, device="cuda")
+        results, rr = np.zeros((E, 4), np.int32), _lib.RampReplanResult()
+        ctx, s = self.m.ctx(), _lib.current_stream()
+        if entry == "plain":
+            _lib.check(self.lib.ramp_replan_episodes(ctx, C.byref(p), C.byref(eb), _lib.ptr(best), _lib.ptr(batch), _lib.ptr(mask),
+                                                     results.ctypes.data_as(_lib.c_i32p), C.byref(rr), s), "ramp_replan_episodes")
+        else:
+            _lib.check(self.lib.ramp_replan_episodes_guided(ctx, C.byref(p), C.byref(eb), C.byref(rg) if rg is not None else None, _lib.ptr(best),
+                                                            _lib.ptr(batch), _lib.ptr(mask), results.ctypes.data_as(_lib.c_i32p), C.byref(rr), s),
+                       "ramp_replan_episodes_guided")
+        torch.cuda.synchronize()
+        assert rr.fell_back == 0
+        return best.cpu().numpy(), batch.cpu().numpy(), mask.cpu().numpy(), results.copy()
+
+    def kernel_on_tap(self, tap0, e, n_iter=3, step=JOB_STEP, track=None, mov=None):
+        """ramp_guide_step_moving on the rows of episode e as the job guides them: pin_first = n_hist, the job's hard conditions extended by
+        the history rows and the clean plan's goal (the values the job pins)."""
+        n = tap0.shape[0]
+        hard = [(0, self.hard_e[e][0].cpu().numpy()), (H - 1, self.hard_e[e][H - 1].cpu().numpy())]
+        hist = self.hist[e].cpu().numpy()
+        hard += [(h, np.tile(hist[h][None], (n, 1))) for h in range(self.n_hist[e])]
+        hard += [(H - 1, np.tile(self.x_clean[e, H - 1].cpu().numpy()[None], (n, 1)))]
+        mov, track = self.mov if mov is None else mov, self.track if track is None else track
+        return run_moving(tap0, [self.cost[e].cpu().numpy()], mov[e:e + 1], track[e:e + 1], np.zeros(n, np.int32),
+                          np.full(n, self.n_hist[e], np.int32), hard, JOB_SC, step, n_iter)
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+_TWO = {}
+
+
+def two(gemm_mode="default"):
+    if gemm_mode not in _TWO:
+        _TWO[gemm_mode] = TwoEpisodes(gemm_mode)
+    return _TWO[gemm_mode]
+
+
+# ------------------------------------------------------------------------------------------------ 5: off is off
+def test_off_is_off():
+    """rg = NULL and a guide whose n_guide is zero on every step return best, batch, mask and record bit-equal to ramp_replan /
+    ramp_replan_episodes (every call right after its scene is installed: the same calibration state)."""
+    t = two()
+    keep = []
+    for e in range(t.E):
+        ref = t.single(e, entry="plain")
+        rg0, _ = t.guide(keep, [e], tap=False, n_guide=[0] * len(t.low))
+        for rg in (None, rg0):
+            got = t.single(e, rg)
+            assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(got[:3], ref[:3])) and got[3] == ref[3], e
+    ref = t.many(entry="plain")
+    rg0, _ = t.guide(keep, [0, 1], tap=False, n_guide=[0] * len(t.low))
+    for rg in (None, rg0):
+        got = t.many(rg)
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(got, ref))
+
+
+# ------------------------------------------------------------------------------------------------ 6: wiring, by the tap
+def test_wiring_by_the_tap_single_episode():
+    """ramp_replan_guided with 3 guide iterations on the last DDIM step: the kernel applied to tap[0] reproduces tap[1] bit for bit; tap[0]
+    is the tap[0] of a run whose guide has step 0 (the guide sits behind the APF passes and the goal copy and feeds nothing before them);
+    the batch handed to the selection differs from the unguided replan's by more than 1e-3 on a free waypoint."""
+    t = two()
+    keep = []
+    for e in range(t.E):
+        rg, tap = t.guide(keep, [e])
+        _, batch, _, _ = t.single(e, rg)
+        tap = tap.cpu().numpy()
+        assert np.isfinite(tap).all()
+        assert np.array_equal(bits(t.kernel_on_tap(tap[0], e)), bits(tap[1])), e
+        assert float(np.abs(tap[1] - tap[0]).max()) > 1e-3
+        rg_z, tap_z = t.guide(keep, [e], step=0.0)
+        t.single(e, rg_z)
+        tap_z = tap_z.cpu().numpy()
+        assert np.array_equal(bits(tap_z[0]), bits(tap[0])) and np.array_equal(bits(tap_z[1]), bits(tap_z[0])), e
+        _, plain, _, _ = t.single(e, entry="plain")
+        free = slice(t.n_hist[e] + 3, H - 1)      # (beyond the history and the final smoothing's window)
+        moved = float(np.abs(batch - plain)[:, free, :2].max())
+        print(f"   episode {e}: guided batch differs from the unguided one by {moved:.3e}")
+        assert moved > 1e-3
+
+
+def test_wiring_by_the_tap_many_episodes():
+    """The same for ramp_replan_episodes_guided: per episode the kernel on that episode's rows of tap[0], with ITS pins, cloud, moving
+    points and track, reproduces tap[1] bit for bit -- and with the other episode's track it does not; the rows of an episode with
+    active = 0 have tap[1] bit-equal to tap[0]."""
+    t = two()
+    keep = []
+    rg, tap = t.guide(keep, [0, 1])
+    _, batch, _, _ = t.many(rg)
+    tap = tap.cpu().numpy()
+    assert np.isfinite(tap).all()
+    for e in range(t.E):
+        sl = slice(t.first[e], t.first[e + 1])
+        assert np.array_equal(bits(t.kernel_on_tap(tap[0, sl], e)), bits(tap[1, sl])), e
+        assert not np.array_equal(bits(t.kernel_on_tap(tap[0, sl], e, track=t.track[::-1])), bits(tap[1, sl])), e
+        assert float(np.abs(tap[1, sl] - tap[0, sl]).max()) > 1e-3
+    rg_z, tap_z = t.guide(keep, [0, 1], step=0.0)
+    t.many(rg_z)
+    assert np.array_equal(bits(tap_z.cpu().numpy()[0]), bits(tap[0]))
+    _, plain, _, _ = t.many(entry="plain")
+    assert float(np.abs(batch - plain)[:, 8:H - 1, :2].max()) > 1e-3
+    rg_a, tap_a = t.guide(keep, [0, 1])
+    t.many(rg_a, active=(1, 0))
+    tap_a = tap_a.cpu().numpy()
+    s0, s1 = slice(t.first[0], t.first[1]), slice(t.first[1], t.first[2])
+    assert np.array_equal(bits(tap_a[1, s1]), bits(tap_a[0, s1]))
+    assert not np.array_equal(bits(tap_a[1, s0]), bits(tap_a[0, s0]))
+
+
+# ------------------------------------------------------------------------------------------------ 7: episodes against single calls
+def test_guided_episodes_against_guided_single_calls():
+    """The guided two-episode job against one ramp_replan_guided call per episode on the same noise rows: batches within 1.5e-4 (the
+    project's bar for equal candidates at different batch positions, test_gpu_episodes.py), records and winners equal, masks equal for
+    every candidate whose smallest distance to its cost cloud in the single path's batch is more than 1e-3 away from cost_thr = 0.05; at most
+    2 of the 13 candidates may be exempt.  The noise seed (10, test_gpu_episodes.py's) was kept after looking at the single path's distances
+    only.  Measured on an MI355X: 0 of 13 candidates exempt (closest margin to cost_thr 6.5e-3), batches 8.9e-7 (episode 0) and 3.8e-6
+    (episode 1) apart; DESIGN.md section 5."""
+    t = two()
+    keep = []
+    ref = []
+    for e in range(t.E):
+        rg, _ = t.guide(keep, [e], tap=False)
+        ref.append(t.single(e, rg))
+    rg, _ = t.guide(keep, [0, 1], tap=False)
+    best, batch, mask, results = t.many(rg)
+    exempt = 0
+    for e in range(t.E):
+        r_best, r_batch, r_mask, (n_free, rank, row) = ref[e]
+        sl = slice(t.first[e], t.first[e + 1])
+        cloud = t.cost[e].cpu().numpy()
+        if t.near[e]:
+            cloud = np.concatenate([cloud, t.extra[e]])
+        dmin = np.sqrt(((r_batch[:, :, None, :2] - cloud[None, None]) ** 2).sum(-1)).min(axis=(1, 2))
+        sure = np.abs(dmin - 0.05) > 1e-3
+        exempt += int((~sure).sum())
+        dist = float(np.abs(batch[sl] - r_batch).max())
+        print(f"   episode {e}: record {results[e].tolist()}, single {[n_free, rank, row]}, max |batch - single path's| {dist:.3e}, "
+              f"exempt {int((~sure).sum())}, closest margin {float(np.abs(dmin - 0.05).min()):.3e}")
+        assert dist < 1.5e-4
+        assert np.array_equal(mask[sl][sure], r_mask[sure]), (e, mask[sl], r_mask)
+        assert results[e].tolist() == [n_free, rank, row + t.first[e] if n_free else -1, 0], (e, results[e], ref[e][3])
+        if n_free:
+            assert float(np.abs(best[e] - r_best).max()) < 1.5e-4
+    print(f"   exempt candidates: {exempt} of 13")
+    assert exempt <= 2
+
+
+# ------------------------------------------------------------------------------------------------ 8: stale graph
+def test_other_contents_of_equal_sizes_replay_the_graph_and_are_honoured():
+    """Two guided replans on one context (bf16x6 arithmetic: a replan carries no calibration state, so every call is in the same one) with
+    equal sizes and other contents of the track, the moving points and the static cloud: the second call's tap is that of a fresh context
+    given the second inputs, bit for bit, and differs from the first call's; a call with another n_guide table (captured anew) is right too."""
+    a, b = TwoEpisodes("bf16x6"), TwoEpisodes("bf16x6")
+    keep, e = [], 1
+    track2, mov2 = a.track.copy(), a.mov.copy()
+    track2[e] += np.float32([0.03, -0.02]); mov2[e] += np.float32(0.01)
+    clouds2 = [c.cpu().numpy() + np.float32(0.02) for c in a.cost]
+    rg1, tap1 = a.guide(keep, [e])
+    a.single(e, rg1)
+    rg2, tap2 = a.guide(keep, [e], mov=mov2, track=track2, clouds=clouds2)
+    a.single(e, rg2, fresh_scene=False)                      # (installing a scene would drop the graph: this call replays it)
+    rgf, tapf = b.guide(keep, [e], mov=mov2, track=track2, clouds=clouds2)
+    b.single(e, rgf)
+    tap1, tap2, tapf = tap1.cpu().numpy(), tap2.cpu().numpy(), tapf.cpu().numpy()
+    assert np.array_equal(bits(tap2), bits(tapf))
+    assert np.array_equal(bits(tap2[0]), bits(tap1[0])) and not np.array_equal(bits(tap2[1]), bits(tap1[1]))
+    n_guide = [0] * (len(a.low) - 2) + [2, 1]
+    rg3, tap3 = a.guide(keep, [e], mov=mov2, track=track2, clouds=clouds2, n_guide=n_guide)
+    a.single(e, rg3, fresh_scene=False)
+    rgf3, tapf3 = b.guide(keep, [e], mov=mov2, track=track2, clouds=clouds2, n_guide=n_guide)
+    b.single(e, rgf3, fresh_scene=False)
+    tap3, tapf3 = tap3.cpu().numpy(), tapf3.cpu().numpy()
+    assert np.array_equal(bits(tap3), bits(tapf3))
+    assert not np.array_equal(bits(tap3[0]), bits(tap2[0]))  # (the step before the last was guided: the last step starts elsewhere)
+
+
+def test_job_level_refusals_name_the_job_entry():
+    """With a live context: a scene-count mismatch, n_guide out of range, a non-finite step and NULL tables come back non-zero with the
+    job entry's name, before any launch."""
+    t = two()
+    keep = []
+
+    def refused(call, name, word):
+        with pytest.raises(_lib.RampHipError, match=name) as ei:
+            call()
+        assert word in str(ei.value), str(ei.value)
+
+    rg, _ = t.guide(keep, [0, 1], tap=False)
+    refused(lambda: t.single(0, rg), "ramp_replan_guided", "n_scenes")
+    rg, _ = t.guide(keep, [0], tap=False)
+    refused(lambda: t.many(rg), "ramp_replan_episodes_guided", "n_scenes")
+    for entry, eps, name in ((lambda r: t.single(0, r), [0], "ramp_replan_guided"), (lambda r: t.many(r), [0, 1], "ramp_replan_episodes_guided")):
+        rg, _ = t.guide(keep, eps, tap=False, n_guide=[0, 0, 0, 0, 17])
+        refused(lambda: entry(rg), name, "n_guide")
+        rg, _ = t.guide(keep, eps, tap=False, step=float("nan"))
+        refused(lambda: entry(rg), name, "step")
+        rg, _ = t.guide(keep, eps, tap=False)
+        rg.n_guide = None
+        refused(lambda: entry(rg), name, "n_guide")
+        rg, _ = t.guide(keep, eps, tap=False)
+        rg.n_mov = 1025
+        refused(lambda: entry(rg), name, "n_mov")
+
+
+# ------------------------------------------------------------------------------------------------ 9: end to end
+def test_replan_guide_end_to_end():
+    """run_inference(..., replan_guide=dict(radius, step, predict='hold')) on the fixture episode of test_gpu_episodes.py (fake environment,
+    max_iteration = 3): it runs, the result is finite, last_replan_guide holds one (H, 2) track per replan, and the host RNG state afterwards
+    is the unguided run's.  run_inference_episodes with 3 copies gives three plans, each within 1.5e-4 of the single-episode guided run."""
+    from test_gpu_episodes import fixture_episode, make_dynamic
+    g = np.load(f"{GOLDEN}/replan_chain.npz")
+    K = min(3, int(g["n_iter"])); B0 = g["noise"].shape[1]
+    guide = dict(radius=F32(0.1), step=F32(0.01), predict='hold')
+    dm = make_dynamic(2 * 3 * B0)
+    state = {}
+    for name, rgd in (("guided", guide), ("plain", None)):
+        ctx, sphere, hard, cloud, _rng = fixture_episode(g, None)
+        np.random.seed(23)
+        with NoiseInjector(list(g["noise"][:1 + K])) as inj:
+            out = dm.run_inference(context=ctx, hard_conds=hard, n_samples=B0, obstacle_pts=cloud, max_iteration=K,
+                                   **({} if rgd is None else dict(replan_guide=rgd)))
+        assert inj.used == 1 + K
+        state[name] = (np.random.get_state()[1].copy(), np.random.get_state()[2], out.cpu().numpy())
+        if rgd is not None:
+            tracks = list(dm.last_replan_guide)
+    single = state["guided"][2]
+    assert single.shape == (1, H, S) and np.isfinite(single).all()
+    assert np.array_equal(state["guided"][0], state["plain"][0]) and state["guided"][1] == state["plain"][1]
+    assert len(tracks) == K and all(tr.shape == (H, 2) and not tr.any() for tr in tracks)
+    made = [fixture_episode(g, None) for _ in range(3)]
+    with NoiseInjector([np.tile(n, (3, 1, 1)) for n in g["noise"][:1 + K]]):
+        plans = dm.run_inference_episodes([m[0] for m in made], [m[2] for m in made], [m[3] for m in made], n_samples=B0,
+                                          rngs=[m[4] for m in made], max_iteration=K, replan_guide=guide)
+    assert len(plans) == 3 and len(dm.last_replan_guide) == K and dm.last_replan_guide[0].shape == (3, H, 2)
+    for pl in plans:
+        d = float(np.abs(pl.cpu().numpy() - single).max())
+        print(f"   many-episode guided plan vs the single-episode one: {d:.3e}")
+        assert d < 1.5e-4
