@@ -17,6 +17,9 @@ sample gets its own cond / uncond pair, so ``--n-samples N`` equals N independen
 ``DIR/data/EnvSmall3D/0/{obstacle_points.pt, box_centers.npy, sphere_centers.npy, metadata.yaml}`` and the checkpoint.
 
     python examples/inference3d.py --make-synthetic /tmp/ramp_exp3d --n-samples 8
+
+``--evaluate`` (opt-in; the reference only plots the boxes and spheres) tests the final batch against them, at the waypoints and on the
+segments between them, and picks a free trajectory: ``Metrics3d.evaluate_scenes`` + ``select_best_clear_scenes``, one more JSON line.
 """
 from __future__ import annotations
 
@@ -134,6 +137,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=Config3d.unet_input_dim)
     ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=Config3d.unet_dim_mults_option)
+    ap.add_argument("--evaluate", action="store_true",
+                    help="evaluate the batch against the experiment's boxes and spheres, waypoints and segments (Metrics3d), and pick a winner")
     args = ap.parse_args(argv)
     cfg = Config3d(); cfg.n_samples, cfg.n_diffusion_steps, cfg.model_id, cfg.seed = args.n_samples, args.n_diffusion_steps, args.model_id, args.seed
     cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
@@ -175,7 +180,27 @@ def main(argv=None):
     out = {"n_chain_states": int(trajs_normalized_iters.shape[0]), "n_samples": int(pos_final.shape[0]), "total_time": elapsed,
            "start_error": float((pos_final[:, 0] - start_state_pos).abs().max()), "goal_error": float((pos_final[:, -1] - goal_state_pos).abs().max())}
     print(json.dumps(out))
+    if args.evaluate:
+        out["evaluation"] = evaluate(trajs_iters[-1], data)
+        print(json.dumps({"evaluation": out["evaluation"]}))
     return out, trajs_normalized_iters
+
+
+def evaluate(trajs_final, data, threshold: float = 0.01):
+    """What the reference's script leaves out: are the sampled trajectories free of the experiment's boxes and spheres -- at the
+    waypoints and on the segments between them -- and which free one to execute."""
+    from ramp_amd.cost import select_best_clear_scenes
+    from ramp_amd.metrics import Metrics3d
+    boxes = (torch.as_tensor(data["box_centers"]), torch.as_tensor(data["box_sizes"]))
+    spheres = (torch.as_tensor(data["sphere_centers"]), torch.as_tensor(data["sphere_radii"]))
+    n = trajs_final.shape[0]
+    per_scene, free = Metrics3d.evaluate_scenes(trajs_final, [n], [boxes], [spheres], threshold=threshold, swept=True)
+    _, n_free, _, best_row, _ = select_best_clear_scenes(trajs_final, [n], boxes=boxes, spheres=spheres, point_dim=3, swept=True,
+                                                         intensity_threshold=threshold)
+    m = per_scene[0]
+    return {"success": m["success"], "collision_intensity": m["collision_intensity"],
+            "swept_collision_intensity": m["swept_collision_intensity"], "n_free_trajectories": m["n_free_trajectories"],
+            "path_length": m["path_length"], "best_row": int(best_row[0]), "n_free_selected": int(n_free[0])}
 
 
 if __name__ == "__main__":

@@ -701,6 +701,58 @@ int ramp_select_best_scenes(const float* traj, int32_t B, int32_t H, int32_t S, 
                             const float* cloud, const int32_t* cloud_offset, int32_t n_points_total, float threshold, float w_smooth,
                             float w_len, int32_t* mask, float* path_len, float* smooth, float* best_out, int32_t* result_dev,
                             void* stream);
+/* ramp_scene_summary with the pairwise waypoint distance of the variance taken over the first point_dim (2 or 3, <= S) state entries.
+ * point_dim = 2 is ramp_scene_summary, bit for bit.  Refusals name "ramp_scene_summary_nd". */
+int ramp_scene_summary_nd(const float* traj, int32_t B, int32_t H, int32_t S, int32_t point_dim, const int32_t* traj_first,
+                          int32_t n_scenes, const float* intensity, const float* path_len, float threshold, double* scratch,
+                          double* summary, int32_t* free_mask, void* stream);
+/* The selection of ramp_select_best_scenes alone, on per-row arrays the caller already holds: mask device (B) int32, 1 = colliding (as
+ * ramp_select_best_scenes writes it), path_len / smooth device (B).  Same result layout, same NaN block for a scene without a free row. */
+int ramp_select_scored_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                              const int32_t* mask, const float* path_len, const float* smooth, float w_smooth, float w_len,
+                              float* best_out, int32_t* result_dev, void* stream);
+
+/* ---- swept collision checks and clearances, 2-D and 3-D ----
+ * Position p_h of waypoint h = the first D = point_dim (2 or 3, <= S) entries of the state; margin >= 0 is the robot's radius.  Every
+ * trajectory meets only the primitives of its own scene (traj_first as above; the three offset tables may repeat a value: a scene may lack
+ * any kind of primitive; spans are clamped to the totals).
+ *   box k      the closed set lower_d <= x_d <= upper_d, d < D, lower = c - s / 2 - margin, upper = c + s / 2 + margin (fp32, s / 2.f;
+ *              at margin 0 the comparisons of ramp_traj_metrics)
+ *   sphere k   |x - c| <= r + margin
+ *   wp_hits    waypoints inside any box or sphere
+ *   seg_hits   segments [p_h, p_{h+1}], h < H - 1, that meet any box or sphere.  Box: slab clipping of t in [0, 1] per axis (an axis with a
+ *              zero direction component passes iff the start lies inside the slab, inclusive), hit iff the clipped interval is not empty.
+ *              Sphere: distance from the centre to the segment, t = clamp((c - a).(b - a) / |b - a|^2, 0, 1), t = 0 for a zero-length
+ *              segment; hit iff it is <= r + margin.  Both are OR-ed with the two endpoint tests: a segment's flag is never below either
+ *              endpoint's.
+ *   clear_wp   min over waypoints and cloud points of |p_h - q|; clear_seg the min over segments and points of the point-segment
+ *              distance (the same t), min-ed with every endpoint distance: clear_seg <= clear_wp always.  +inf for a scene without cloud
+ *              points.  A caller's collision test is clear < threshold, strict (cost.py:45-49).
+ *   path_len   sum_h |p_{h+1} - p_h| over the D position entries; smooth: sum_h of the norm of the difference of the entries >= D (0 when
+ *              S == D).  Per-segment values are added serially in fp32, ramp_traj_costs's order: at D = 2 the same bits.
+ * A trajectory with a non-finite position coordinate gets wp_hits = H, seg_hits = H - 1 and NaN clearances: it is never free. */
+typedef struct ramp_obstacles {
+  int32_t point_dim;               /* 2 or 3, <= S */
+  int32_t n_scenes;                /* 1 for a single scene */
+  const float* box_centers;        /* device (n_boxes_total, D) */
+  const float* box_sizes;          /* device (n_boxes_total, D): full side lengths */
+  const float* sphere_centers;     /* device (n_spheres_total, D) */
+  const float* sphere_radii;       /* device (n_spheres_total) */
+  const float* cloud;              /* device (n_points_total, D) */
+  const int32_t* box_offset;       /* DEVICE int32 (n_scenes + 1) each */
+  const int32_t* sphere_offset;
+  const int32_t* cloud_offset;
+  int32_t n_boxes_total, n_spheres_total, n_points_total;
+  float margin;
+} ramp_obstacles;
+/* Outputs are device (B): wp_hits / seg_hits int32, the rest fp32; any of them may be NULL.  swept == 0 skips all segment work and leaves
+ * seg_hits / clear_seg untouched.  One launch, one 256-thread block per trajectory; asynchronous on `stream`, capturable, no copies, no
+ * float atomics; a scene's rows do not depend on the rest of the batch.  Refused on the host before any launch (non-zero,
+ * "ramp_traj_clearance" in ramp_last_error): point_dim outside {2, 3} or > S, H < 2 or H > 128, a negative margin, a missing table, a
+ * total > 0 with a NULL array. */
+int ramp_traj_clearance(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_obstacles* ob, const int32_t* traj_first,
+                        int32_t swept, int32_t* wp_hits, int32_t* seg_hits, float* clear_wp, float* clear_seg, float* path_len,
+                        float* smooth, void* stream);
 /* one p_mean_variance evaluation given eps (diffusion_model_static.py:161-172); predict_x0 != 0: predict_epsilon=False,
  * x0 = the combined network output (diffusion_model_static.py:109-118) */
 int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, double w0, double w1,

@@ -75,6 +75,14 @@ class RampReplanGuide(C.Structure):
                 ("w_acc", C.c_double), ("max_norm", C.c_double), ("n_guide", c_i32p), ("step", c_f32p), ("tap_out", C.c_void_p)]
 
 
+class RampObstacles(C.Structure):
+    """ramp_obstacles: the boxes, spheres and cloud points of the scenes ramp_traj_clearance tests trajectories against."""
+    _fields_ = [("point_dim", C.c_int32), ("n_scenes", C.c_int32), ("box_centers", C.c_void_p), ("box_sizes", C.c_void_p),
+                ("sphere_centers", C.c_void_p), ("sphere_radii", C.c_void_p), ("cloud", C.c_void_p), ("box_offset", C.c_void_p),
+                ("sphere_offset", C.c_void_p), ("cloud_offset", C.c_void_p), ("n_boxes_total", C.c_int32), ("n_spheres_total", C.c_int32),
+                ("n_points_total", C.c_int32), ("margin", C.c_float)]
+
+
 RESAMPLE_MAX_EVENTS = 64   # RAMP_RESAMPLE_MAX_EVENTS
 c_f64p = C.POINTER(C.c_double)
 
@@ -233,6 +241,12 @@ PROTOTYPES = {
     "ramp_select_best_scenes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                           C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "ramp_scene_summary_nd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_select_scored_scenes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_traj_clearance": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampObstacles), C.c_void_p, C.c_int32] +
+                            [C.c_void_p] * 7),
     "ramp_cfg_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,
                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),

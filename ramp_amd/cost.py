@@ -94,3 +94,37 @@ def compute_trajectory_costs_scenes(trajs, counts_or_traj_scene, clouds, smoothn
             float(collision_threshold), float(smoothness_weight), float(path_length_weight), _lib.ptr(mask), _lib.ptr(plen),
             _lib.ptr(smooth), _lib.ptr(best), _lib.ptr(res), _lib.current_stream()), "ramp_select_best_scenes")
     return best, res[:, 0], res[:, 1], res[:, 2], ~mask.bool()
+
+
+def select_best_clear_scenes(trajs, counts_or_traj_scene, clouds=None, boxes=None, spheres=None, *, point_dim=None, margin=0.0, swept=True,
+                             collision_threshold=0.0, intensity_threshold=0.0, smoothness_weight=.1, path_length_weight=.9):
+    """``compute_trajectory_costs_scenes`` with the collision test of ``trajectory_clearance``: 2-D or 3-D, against cost clouds, boxes
+    and spheres (each one entry or a list per scene, as ``trajectory_clearance`` takes them), on the segments between the waypoints
+    too (``swept``).  A row is colliding iff its (swept) cloud clearance ``< collision_threshold`` or its (swept) primitive intensity
+    ``> intensity_threshold``; a row with a non-finite position always is.  Selection: ramp_select_scored_scenes, the rule of
+    ``compute_trajectory_costs`` per scene.
+
+    Returns the tuple of ``compute_trajectory_costs_scenes`` -- ``best`` (n_scenes, H, S), ``n_free``, ``best_index``, ``best_row``,
+    ``collision_free_mask`` (B) -- all device tensors, without a host sync.  With 2-D clouds alone, ``swept=False`` and the same
+    thresholds it is ``compute_trajectory_costs_scenes`` bit for bit."""
+    from .clearance import _per_scene, trajectory_clearance
+    if trajs.device.type != "cuda":
+        raise _lib.RampHipError("trajectory costs: tensors must live on a HIP device (no CPU path)")
+    t = trajs.detach().to(torch.float32).contiguous()
+    B, H, S = t.shape
+    lists = [v for v in (_per_scene("clouds", clouds, False), _per_scene("boxes", boxes, True), _per_scene("spheres", spheres, True))
+             if v is not None]
+    n_scenes = len(lists[0]) if lists else 1
+    counts = scene_counts(counts_or_traj_scene, n_scenes, B)
+    r = trajectory_clearance(t, boxes, spheres, clouds, counts, point_dim=point_dim, margin=margin, swept=swept)
+    mask = r.colliding(intensity_threshold, collision_threshold, swept).to(torch.int32)
+    dev = t.device
+    first = r.traj_first
+    best = torch.empty(n_scenes, H, S, device=dev)
+    res = torch.empty(n_scenes, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_select_scored_scenes(
+            _lib.ptr(t), B, H, S, first.data_ptr(), n_scenes, _lib.ptr(mask), _lib.ptr(r.path_length), _lib.ptr(r.smoothness),
+            float(smoothness_weight), float(path_length_weight), _lib.ptr(best), _lib.ptr(res), _lib.current_stream()),
+            "ramp_select_scored_scenes")
+    return best, res[:, 0], res[:, 1], res[:, 2], ~mask.bool()

@@ -201,7 +201,8 @@ int launch_traj_metrics_scenes(const float* traj, int B, int H, int S, const int
                                const float* sizes, const int* box_off, int n_boxes_total, float* intensity, float* path_len,
                                float* smooth, hipStream_t s);
 // per-scene records of 6 doubles {n_traj, n_free, mean intensity, mean and unbiased std of the free path lengths, waypoint variance
-// of the free rows} and the (B) free mask.  scratch: 2 * H * W + n_scenes + 1 doubles, W = ceil(B / 256) + n_scenes
+// of the free rows} and the (B) free mask.  scratch: 2 * H * W + n_scenes + 1 doubles, W = ceil(B / 256) + n_scenes.  D = 2 or 3: the
+// position coordinates the pairwise waypoint distance is taken over
 int launch_scene_summary(const float* traj, int B, int H, int S, const int* traj_first, int n_scenes, const float* intensity,
-                         const float* path_len, float thr, double* scratch, double* summary, int* free_mask, hipStream_t s);
+                         const float* path_len, float thr, double* scratch, double* summary, int* free_mask, hipStream_t s, int D = 2);
 }  // namespace ramp

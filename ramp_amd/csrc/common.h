@@ -11,3 +11,4 @@
 #include "args_sampler.h"
 #include "args_resample.h"
 #include "args_scene.h"
+#include "args_clearance.h"

@@ -204,11 +204,14 @@ void scene_tiles_kernel(const int* __restrict__ traj_first, int n_scenes, int* _
 // stage 1: block (w, h) = rows [256 t, 256 t + 256) of scene s (w = tile_first[s] + t) at waypoint h: sums of d_ij and d_ij^2
 // over the pairs i in the tile, j > i in the scene, both free -- waypoint_pairs_kernel with the free test in place of a
 // compaction.  A j-tile in fp32, j-tiles in fp64, as there.
+// D = 2 or 3 position coordinates; D = 2 is the code ramp_scene_summary has always run (no z value is loaded or used there)
+template <int D>
 __global__ __launch_bounds__(256)
 void scene_pairs_kernel(const float* __restrict__ traj, int B, int H, int S, const int* __restrict__ traj_first, int n_scenes,
                         const int* __restrict__ tile_first, const float* __restrict__ intensity, float thr,
                         double* __restrict__ partial) {
   __shared__ float2 tile[256];
+  __shared__ float tilez[D == 3 ? 256 : 1];
   __shared__ int tfree[256];
   __shared__ double red[2][4];
   const int w = blockIdx.x, h = blockIdx.y;
@@ -217,20 +220,24 @@ void scene_pairs_kernel(const float* __restrict__ traj, int B, int H, int S, con
   const int first = min(max(traj_first[s], 0), B), end = min(max(traj_first[s + 1], first), B);
   const int i0 = first + (w - tile_first[s]) * 256, i = i0 + threadIdx.x;
   float2 pi = {0.f, 0.f};
+  float piz = 0.f;
   bool fi = false;
   if (i < end) { pi = {traj[((long)i * H + h) * S], traj[((long)i * H + h) * S + 1]}; fi = intensity[i] <= thr; }
+  if (D == 3 && i < end) piz = traj[((long)i * H + h) * S + 2];
   double s1 = 0.0, s2 = 0.0;
   for (int j0 = i0; j0 < end; j0 += 256) {                  // tiles left of the diagonal hold no pair with j > i
     const int j = j0 + threadIdx.x;
     __syncthreads();
     tile[threadIdx.x] = j < end ? float2{traj[((long)j * H + h) * S], traj[((long)j * H + h) * S + 1]} : float2{0.f, 0.f};
+    if (D == 3) tilez[threadIdx.x] = j < end ? traj[((long)j * H + h) * S + 2] : 0.f;
     tfree[threadIdx.x] = j < end && intensity[j] <= thr;
     __syncthreads();
     const int n = min(256, end - j0);
     float a1 = 0.f, a2 = 0.f;
     for (int jj = 0; jj < n; ++jj) {
       const float dx = pi.x - tile[jj].x, dy = pi.y - tile[jj].y;
-      const float d2 = dx * dx + dy * dy;
+      float d2 = dx * dx + dy * dy;
+      if (D == 3) { const float dz = piz - tilez[jj]; d2 += dz * dz; }
       const bool use = (j0 + jj > i) && fi && tfree[jj];
       a1 += use ? sqrtf(d2) : 0.f;
       a2 += use ? d2 : 0.f;
@@ -308,13 +315,16 @@ int launch_traj_metrics_scenes(const float* traj, int B, int H, int S, const int
   return 0;
 }
 int launch_scene_summary(const float* traj, int B, int H, int S, const int* traj_first, int n_scenes, const float* intensity,
-                         const float* path_len, float thr, double* scratch, double* summary, int* free_mask, hipStream_t s) {
+                         const float* path_len, float thr, double* scratch, double* summary, int* free_mask, hipStream_t s, int D) {
   RAMP_REQUIRE(B > 0 && H > 0 && H <= 65535 && S >= 2 && n_scenes > 0 && n_scenes <= B, "bad metric dims");
+  RAMP_REQUIRE((D == 2 || D == 3) && D <= S, "point_dim must be 2 or 3 and at most S");
   const long W = summary_tiles(B, n_scenes);
   int* tile_first = reinterpret_cast<int*>(scratch + 2 * H * W);
   hipLaunchKernelGGL(scene_tiles_kernel, dim3(1), dim3(256), 0, s, traj_first, n_scenes, tile_first);
-  hipLaunchKernelGGL(scene_pairs_kernel, dim3((unsigned)W, H), dim3(256), 0, s, traj, B, H, S, traj_first, n_scenes, tile_first,
-                     intensity, thr, scratch);
+  if (D == 3) hipLaunchKernelGGL(scene_pairs_kernel<3>, dim3((unsigned)W, H), dim3(256), 0, s, traj, B, H, S, traj_first, n_scenes, tile_first,
+                                 intensity, thr, scratch);
+  else hipLaunchKernelGGL(scene_pairs_kernel<2>, dim3((unsigned)W, H), dim3(256), 0, s, traj, B, H, S, traj_first, n_scenes, tile_first,
+                          intensity, thr, scratch);
   hipLaunchKernelGGL(scene_summary_kernel, dim3(n_scenes), dim3(256), 0, s, B, H, (int)W, traj_first, tile_first, intensity, path_len, thr,
                      scratch, summary, free_mask);
   RAMP_HIP_CHECK(hipGetLastError());

@@ -366,6 +366,51 @@ int ramp_select_best_scenes(const float* traj, int32_t B, int32_t H, int32_t S, 
   return launch_select_scenes(traj, mask, path_len, smooth, w_smooth, w_len, traj_first, n_scenes, best_out, result_dev, B, H, S, s);
 }
 
+int ramp_scene_summary_nd(const float* traj, int32_t B, int32_t H, int32_t S, int32_t point_dim, const int32_t* traj_first, int32_t n_scenes,
+                          const float* intensity, const float* path_len, float threshold, double* scratch, double* summary,
+                          int32_t* free_mask, void* stream) {
+  RAMP_REQUIRE(traj && intensity && path_len && scratch && summary && free_mask, "ramp_scene_summary_nd: null argument");
+  RAMP_REQUIRE(traj_first, "ramp_scene_summary_nd: null scene table");
+  RAMP_REQUIRE((point_dim == 2 || point_dim == 3) && point_dim <= S, "ramp_scene_summary_nd: point_dim must be 2 or 3 and at most S");
+  RAMP_REQUIRE_SCENES(B, S, n_scenes);
+  return launch_scene_summary(traj, B, H, S, traj_first, n_scenes, intensity, path_len, threshold, scratch, summary, free_mask,
+                              as_stream(stream), point_dim);
+}
+int ramp_select_scored_scenes(const float* traj, int32_t B, int32_t H, int32_t S, const int32_t* traj_first, int32_t n_scenes,
+                              const int32_t* mask, const float* path_len, const float* smooth, float w_smooth, float w_len,
+                              float* best_out, int32_t* result_dev, void* stream) {
+  RAMP_REQUIRE(traj && mask && path_len && smooth && best_out && result_dev, "ramp_select_scored_scenes: null argument");
+  RAMP_REQUIRE(traj_first, "ramp_select_scored_scenes: null scene table");
+  RAMP_REQUIRE(B > 0 && H > 0 && S >= 2 && n_scenes > 0 && n_scenes <= B, "ramp_select_scored_scenes: bad dims (B, H > 0, S >= 2, 1 <= n_scenes <= B)");
+  return launch_select_scenes(traj, mask, path_len, smooth, w_smooth, w_len, traj_first, n_scenes, best_out, result_dev, B, H, S,
+                              as_stream(stream));
+}
+// every refusal of ramp_traj_clearance is made here, on the host, before anything is launched
+int ramp_traj_clearance(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_obstacles* ob, const int32_t* traj_first,
+                        int32_t swept, int32_t* wp_hits, int32_t* seg_hits, float* clear_wp, float* clear_seg, float* path_len,
+                        float* smooth, void* stream) {
+  const std::string w = "ramp_traj_clearance: ";
+  RAMP_REQUIRE(traj && ob, w + "null trajectories or obstacles");
+  RAMP_REQUIRE(B > 0 && S >= 2, w + "empty batch or states narrower than 2");
+  RAMP_REQUIRE((ob->point_dim == 2 || ob->point_dim == 3) && ob->point_dim <= S, w + "point_dim must be 2 or 3 and at most S");
+  RAMP_REQUIRE(H >= 2 && H <= 128, w + "the horizon must be 2 .. 128");
+  RAMP_REQUIRE(ob->margin >= 0.f && std::isfinite(ob->margin), w + "margin must be finite and not negative");
+  RAMP_REQUIRE(ob->n_scenes >= 1 && ob->n_scenes <= B, w + "n_scenes must be 1 .. B");
+  RAMP_REQUIRE(traj_first && ob->box_offset && ob->sphere_offset && ob->cloud_offset, w + "missing table (traj_first, box_offset, sphere_offset, cloud_offset)");
+  RAMP_REQUIRE(ob->n_boxes_total >= 0 && ob->n_spheres_total >= 0 && ob->n_points_total >= 0, w + "negative total");
+  RAMP_REQUIRE(ob->n_boxes_total == 0 || (ob->box_centers && ob->box_sizes), w + "null boxes with n_boxes_total > 0");
+  RAMP_REQUIRE(ob->n_spheres_total == 0 || (ob->sphere_centers && ob->sphere_radii), w + "null spheres with n_spheres_total > 0");
+  RAMP_REQUIRE(ob->n_points_total == 0 || ob->cloud, w + "null cloud with n_points_total > 0");
+  ClearanceArgs a;
+  a.traj = traj; a.B = B; a.H = H; a.S = S; a.D = ob->point_dim; a.traj_first = traj_first; a.n_scenes = ob->n_scenes;
+  a.box_c = ob->box_centers; a.box_s = ob->box_sizes; a.box_off = ob->box_offset; a.n_boxes = ob->n_boxes_total;
+  a.sph_c = ob->sphere_centers; a.sph_r = ob->sphere_radii; a.sph_off = ob->sphere_offset; a.n_spheres = ob->n_spheres_total;
+  a.cloud = ob->cloud; a.cloud_off = ob->cloud_offset; a.n_points = ob->n_points_total;
+  a.margin = ob->margin; a.swept = swept != 0;
+  a.wp_hits = wp_hits; a.seg_hits = seg_hits; a.clear_wp = clear_wp; a.clear_seg = clear_seg; a.plen = path_len; a.smooth = smooth;
+  return launch_traj_clearance(a, as_stream(stream));
+}
+
 int ramp_cfg_mean(const float* x, const float* eps, int32_t B, int32_t HS, int32_t n_rp, double w0, double w1,
                   float sqrt_recip, float sqrt_recipm1, float coef1, float coef2, int32_t clip, int32_t predict_x0, float* x0_out,
                   float* mean_out, float* ecomb_out, void* stream) {

@@ -174,6 +174,106 @@ class Metrics:
         return out, free_mask
 
 
+class Metrics3d(Metrics):
+    """``Metrics`` over D = 3 positions (the first three state entries), with spheres beside the boxes and an optional swept
+    (segment) test: the evaluation of the Maze3D experiments, whose boxes and spheres the reference's inference3d.py only plots.
+    ``trajectory_success_and_metrics`` is inherited and runs on the 3-D path length and waypoint variance below."""
+
+    @staticmethod
+    def compute_collision_intensity(trajs, box_centers, box_sizes, sphere_centers=None, sphere_radii=None, swept=False, margin=0.0):
+        """Fraction of the waypoints (``swept``: of the segments) of each trajectory that meet any box or sphere widened by ``margin``."""
+        from .clearance import trajectory_clearance
+        boxes = None if box_centers is None else (torch.as_tensor(box_centers), torch.as_tensor(box_sizes))
+        spheres = None if sphere_centers is None else (torch.as_tensor(sphere_centers), torch.as_tensor(sphere_radii))
+        r = trajectory_clearance(trajs, boxes, spheres, point_dim=3, margin=margin, swept=swept)
+        return r.swept_intensity if swept else r.intensity
+
+    @staticmethod
+    def compute_path_length(trajectories):
+        from .clearance import trajectory_clearance
+        assert trajectories.ndim == 3
+        if len(trajectories) == 0:
+            return torch.tensor(0.0, device=trajectories.device)
+        return trajectory_clearance(trajectories, point_dim=3, swept=False).path_length
+
+    @staticmethod
+    def compute_smoothness(trajs, trajs_vel=None):
+        from .clearance import trajectory_clearance
+        if trajs_vel is not None:                      # velocities given separately: pad three position columns
+            assert trajs_vel.ndim == 3
+            trajs = torch.cat([torch.zeros_like(trajs_vel[..., :1]).repeat(1, 1, 3), trajs_vel], dim=-1)
+        return trajectory_clearance(trajs, point_dim=3, swept=False).smoothness
+
+    @staticmethod
+    def compute_variance_waypoints(trajs, eps=1e-8):
+        """``Metrics.compute_variance_waypoints`` with the pairwise distance over three coordinates (ramp_scene_summary_nd on one
+        scene whose rows are all free)."""
+        t = _dev_traj(trajs)
+        B, H, S = t.shape
+        if B < 2:
+            return torch.tensor(float("nan"), device=t.device)
+        first = torch.tensor([0, B], dtype=torch.int32).to(t.device)
+        zeros = torch.zeros(2, B, device=t.device)
+        scratch = torch.empty(2 * H * ((B + 255) // 256 + 1) + 2, dtype=torch.float64, device=t.device)
+        summary = torch.empty(1, 6, dtype=torch.float64, device=t.device)
+        mask = torch.empty(B, dtype=torch.int32, device=t.device)
+        with torch.cuda.device(t.device):
+            _lib.check(_lib.load().ramp_scene_summary_nd(_lib.ptr(t), B, H, S, 3, first.data_ptr(), 1, zeros[0].data_ptr(),
+                                                         zeros[1].data_ptr(), 0.0, _lib.ptr(scratch), _lib.ptr(summary), _lib.ptr(mask),
+                                                         _lib.current_stream()), "ramp_scene_summary_nd")
+        return summary[0, 5].to(torch.float32)
+
+    @staticmethod
+    def evaluate_scenes(trajs, counts_or_traj_scene, boxes_list, spheres_list=None, threshold: float = 0.01, swept: bool = True,
+                        margin: float = 0.0):
+        """``Metrics.evaluate_scenes`` for 3-D scenes of boxes and spheres: scene i's trajectories meet ``boxes_list[i]`` =
+        ``(centers (n, 3), sizes (n, 3) or (n,))`` and ``spheres_list[i]`` = ``(centers (m, 3), radii (m,))`` (either may be None).
+        ``swept``: a trajectory is free when the fraction of its SEGMENTS that meet a primitive is ``<= threshold``; otherwise the
+        fraction of its waypoints, the reference's rule.
+
+        Returns what ``Metrics.evaluate_scenes`` returns -- the same keys, ``SceneMetrics`` and (B) bool device free mask --, with
+        ``collision_intensity`` the waypoint intensity in percent and one more key, ``swept_collision_intensity`` (percent; None with
+        ``swept=False``).  Uploads first, then ramp_traj_clearance + ramp_scene_summary_nd; the call ends in its only
+        device-to-host copy, the (n_scenes, 7) records."""
+        from .clearance import trajectory_clearance
+        t = _dev_traj(trajs)
+        B, H, S = t.shape
+        n_scenes = len(boxes_list)
+        if spheres_list is not None and len(spheres_list) != n_scenes:
+            raise ValueError(f"{n_scenes} box entries but {len(spheres_list)} sphere entries")
+        counts = scene_counts(counts_or_traj_scene, n_scenes, B)
+        dev = t.device
+        r = trajectory_clearance(t, list(boxes_list), None if spheres_list is None else list(spheres_list), counts=counts,
+                                 point_dim=3, margin=margin, swept=swept)
+        first = r.traj_first
+        decide = (r.swept_intensity if swept else r.intensity).contiguous()
+        W = (B + 255) // 256 + n_scenes
+        scratch = torch.empty(2 * H * W + n_scenes + 1, dtype=torch.float64, device=dev)
+        summary = torch.empty(n_scenes, 6, dtype=torch.float64, device=dev)
+        mask = torch.empty(B, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().ramp_scene_summary_nd(_lib.ptr(t), B, H, S, 3, first.data_ptr(), n_scenes, _lib.ptr(decide),
+                                                         _lib.ptr(r.path_length), float(threshold), _lib.ptr(scratch), _lib.ptr(summary),
+                                                         _lib.ptr(mask), _lib.current_stream()), "ramp_scene_summary_nd")
+        # the per-scene mean of the waypoint intensity (the record's own mean is of the deciding intensity): differences of a running sum
+        run = torch.cat([torch.zeros(1, dtype=torch.float64, device=dev), r.intensity.to(torch.float64).cumsum(0)])
+        idx = first.long()
+        wp_mean = (run[idx[1:]] - run[idx[:-1]]) / (idx[1:] - idx[:-1]).to(torch.float64)
+        free_mask = mask.bool()
+        rec = torch.cat([summary, wp_mean[:, None]], dim=1).cpu().numpy()               # the one device-to-host copy
+        out, b = [], 0
+        for i in range(n_scenes):
+            n_traj, n_free, ci, pl, sd, var, wp = rec[i]
+            out.append(SceneMetrics({'success': 1 if n_free > 0 else 0, 'collision_intensity': float(wp) * 100,
+                                     'swept_collision_intensity': float(ci) * 100 if swept else None,
+                                     'path_length': None if np.isnan(pl) else float(pl),
+                                     'path_length_std': None if np.isnan(sd) else float(sd),
+                                     'waypoint_variance': None if np.isnan(var) else float(var),
+                                     'n_free_trajectories': int(n_free)}, trajs, free_mask, slice(b, b + counts[i])))
+            b += counts[i]
+        return out, free_mask
+
+
 class DynamicMetrics(Metrics):
     """metrics.py:128-170: host-side bookkeeping over the executed states of one pursuit-evasion episode."""
 

@@ -221,6 +221,28 @@ def build_eval_tables(counts: Sequence[int], box_counts: Optional[Sequence[int]]
     return out
 
 
+def build_clearance_tables(counts: Sequence[int], box_counts: Optional[Sequence[int]] = None,
+                           sphere_counts: Optional[Sequence[int]] = None,
+                           cloud_sizes: Optional[Sequence[int]] = None) -> Dict[str, np.ndarray]:
+    """Tables of ``ramp_traj_clearance`` (``trajectory_clearance``) for the layout ``build_scene_tables`` produces: a scene's
+    trajectories adjacent, scenes in order.
+
+    counts         trajectories of each scene, at least one each
+    box_counts / sphere_counts / cloud_sizes  boxes, spheres and cloud points of each scene, or None = none in any scene; 0 is
+                   allowed everywhere: a scene may lack any kind of primitive
+
+    Returns int32 arrays of ``n_scenes + 1`` entries: ``traj_first`` (strictly increasing, ``[-1] = B``) and ``box_offset``,
+    ``sphere_offset``, ``cloud_offset`` (each may repeat a value) into the primitives concatenated over scenes."""
+    n_scenes = len(counts)
+    if n_scenes == 0:
+        raise ValueError("no scenes given")
+    out = {"traj_first": _offsets("trajectory counts", counts, n_scenes, allow_empty=False)}
+    for key, what, vals in (("box_offset", "box counts", box_counts), ("sphere_offset", "sphere counts", sphere_counts),
+                            ("cloud_offset", "cloud sizes", cloud_sizes)):
+        out[key] = _offsets(what, [0] * n_scenes if vals is None else vals, n_scenes, allow_empty=True)
+    return out
+
+
 def build_encode_tables(shapes: Sequence[Sequence[int]]) -> Dict[str, np.ndarray]:
     """CSR tables of a ragged batch of scenes for the scene encoder (``TemporalUnetInference.encode_scenes`` ->
     ``ramp_encode_scenes``), the clouds concatenated point by point in scene order.
