@@ -431,6 +431,58 @@ int ramp_sample_steered(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_r
  * Synchronises `stream`. */
 int ramp_resample_groups(float* x, int32_t B, int32_t H, int32_t S, double* logw, double* c_prev, const int32_t* group_first_host,
                          int32_t n_groups, const float* u, double ess_frac, int32_t* ancestor_out, double* ess_out, void* stream);
+/* ---- plans longer than the network's horizon: stitched windows in one job ----
+ * The score network serves whole samples of H <= 64 waypoints.  A long trajectory of L waypoints is sampled as W overlapping windows of H
+ * waypoints that sit in adjacent rows of one batch and are made to agree, after every reverse step, on the waypoints they share
+ * (MultiDiffusion / DiffStitch-style fusion of overlapping diffusion windows, here on trajectories).
+ * Layout: W >= 1 windows per chain, overlap O with 1 <= O <= H / 2, stride st = H - O, L = H + (W - 1) st.  A job of C chains has B = C W
+ * rows; row c W + w is window w of chain c and covers the long waypoints [w st, w st + H).  O <= H / 2: a long waypoint lies in at most two
+ * windows.  With W == 1 the overlap is not read and L = H.
+ * Stitch of an array a (B, H, S):
+ *   blend  for w < W - 1, k < O, channel s: l = a[c W + w, st + k, s], q = a[c W + w + 1, k, s], m = l + alpha_k (q - l) in fp32, the
+ *          difference, the product and the sum rounded once each; both locations receive m.  q == l returns l itself (bit for bit; for
+ *          zeros of either sign, l's).  alpha: O floats in [0, 1].
+ *   pins   pin i = 0 .. n_pin - 1 names a long waypoint idx_i in [0, L) and values val[i, c, :]: every window w with 0 <= idx_i - w st < H
+ *          gets a[c W + w, idx_i - w st, :] = val[i, c, :].  Later pins win; pins win over the blend.
+ * One launch; no element is written twice; nothing else of the array is touched.  Assemble: long[c, l, :] comes from the window with the
+ * smallest w that covers l (after a stitch the other window holds the same bits).
+ * The job: wherever the plain job applies its hard conditions, the stitched job runs the stitch, and it runs it on the array the hooks work on:
+ *   noise  every noise block of the job (0 .. n_steps on DDPM, block 0 on DDIM) is stitched in the context's own buffer with alpha = 0 and
+ *          no pins, behind the Philox draw (noise_mode 1) resp. the copy-in (noise_mode 0): an overlapping waypoint receives ONE draw, the
+ *          left window's -- an average of two would shrink the variance there.  The caller's array is never written.
+ *   start  x_T = noise[0], then stitch: chain block 0.
+ *   iteration j: evaluation and guidance combination as ever; stitch of the posterior mean (DDPM) / x0 (DDIM); APF hook and cost guide as
+ *          ever, per window, each window against the cloud of its own scene (on DDIM the stitch takes the place of the hard conditioning
+ *          between APF passes); if either hook ran, one more stitch; the DDPM / DDIM update without hard conditions, then stitch of x: chain
+ *          block j + 1.  (That last blend is the identity: equal inputs went through one elementwise expression; only the pins act.)
+ * The job carries no hard conditions of its own: the cost guide therefore pins nothing, sees the pinned values in its target and may move
+ * them; the stitch behind it restores them.
+ * alpha and the pin values are copied into buffers of the context before the launch and the captured graph reads those: other values of the
+ * same shape replay the same graph and are honoured.  n_windows, overlap, n_pin and the pin indices are part of the graph key. */
+#define RAMP_STITCH_MAX_PINS 64
+typedef struct ramp_stitch {
+  int32_t n_windows;                 /* W >= 1; p->B must be a multiple of it                                      */
+  int32_t overlap;                   /* O, 1 .. H / 2 (not read with W == 1)                                        */
+  const float* alpha_host;           /* host (O) blend weights in [0, 1]; may be NULL with W == 1                    */
+  int32_t n_pin;                     /* 0 .. RAMP_STITCH_MAX_PINS                                                    */
+  int32_t reserved;
+  const int32_t* pin_idx_host;       /* host (n_pin): long waypoint of each pin, in [0, L)                           */
+  const float* pin_val;              /* device (n_pin, C, S), C = B / W                                              */
+} ramp_stitch;
+/* ramp_sample_guided (without MCMC and composed weights) on stitched windows.  st == NULL IS ramp_sample_guided(p, cg, NULL, NULL, scenes,
+ * ...), bit for bit.  long_out: device (C, L, S), the assembled final trajectories, or NULL; chain_out / x_out hold the windows.
+ * Refused on the host before any launch (non-zero, "ramp_sample_stitched" in ramp_last_error): n_windows < 1; B no multiple of n_windows;
+ * overlap outside 1 .. H / 2 with n_windows > 1; an alpha outside [0, 1] or non-finite; n_pin outside 0 .. RAMP_STITCH_MAX_PINS; a pin index
+ * outside [0, L); a NULL table where one is needed; p->n_hard != 0 (the pins are the job's conditions); a sharded job (p->philox_total != 0:
+ * the windows of a chain must sit in one shard); and what ramp_sample_guided refuses. */
+int ramp_sample_stitched(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_stitch* st, const ramp_cost_guide* cg,
+                         const ramp_scene_batch* scenes, const float* noise, float* chain_out, float* x_out, float* long_out, void* stream);
+/* the operation alone on x (C W, H, S) in place, the counterpart of ramp_guide_step.  Refusals as above, with "ramp_stitch_windows".
+ * Synchronises `stream`. */
+int ramp_stitch_windows(float* x, int32_t C, int32_t W, int32_t H, int32_t S, const ramp_stitch* st, void* stream);
+/* long_out device (C, L, S) from the windows x (C W, H, S); O is not read with W == 1.  Refused with "ramp_stitch_assemble": bad dims, O
+ * outside 1 .. H / 2 with W > 1, a NULL array.  Synchronises `stream`. */
+int ramp_stitch_assemble(const float* x, int32_t C, int32_t W, int32_t H, int32_t S, int32_t O, float* long_out, void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from

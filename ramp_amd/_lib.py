@@ -66,6 +66,15 @@ class RampCostGuide(C.Structure):
                 ("n_guide", c_i32p), ("step", c_f32p)]
 
 
+STITCH_MAX_PINS = 64        # RAMP_STITCH_MAX_PINS
+
+
+class RampStitch(C.Structure):
+    """ramp_stitch: the stitch table of a job on stitched windows (ramp_sample_stitched) and of the kernel-level ramp_stitch_windows."""
+    _fields_ = [("n_windows", C.c_int32), ("overlap", C.c_int32), ("alpha_host", c_f32p), ("n_pin", C.c_int32), ("reserved", C.c_int32),
+                ("pin_idx_host", c_i32p), ("pin_val", C.c_void_p)]
+
+
 class RampReplanGuide(C.Structure):
     """ramp_replan_guide: the cost guide of the replanning jobs (ramp_replan_guided, ramp_replan_episodes_guided) and of the kernel-level
     ramp_guide_step_moving / ramp_guide_cost_moving."""
@@ -194,6 +203,10 @@ PROTOTYPES = {
     "ramp_guide_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_int32, C.c_float,
                                   C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
     "ramp_guide_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_sample_stitched": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampStitch), C.POINTER(RampCostGuide),
+                                       C.POINTER(RampSceneBatch)] + [C.c_void_p] * 5),
+    "ramp_stitch_windows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampStitch), C.c_void_p]),
+    "ramp_stitch_assemble": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "ramp_score_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "ramp_row_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "ramp_combine_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -100,6 +100,21 @@ struct GuideArgs {
 int launch_guide_step(const GuideArgs& a, hipStream_t s);
 // terms (B, 3) doubles = {C_obs, C_smooth, C_acc} unweighted (NaN for a trajectory whose scene index is outside the table)
 int launch_guide_cost(const GuideArgs& a, double* terms, hipStream_t s);
+// ---- stitched windows (stitch.hip; ramp_stitch in ramp_hip.h) ---------------------------------------
+constexpr int STITCH_MAX_PINS = 64;
+struct StitchArgs {
+  float* x = nullptr;               // (C W, H, S) in place: row c W + w is window w of chain c
+  int C = 0, W = 1, H = 0, S = 0;
+  int O = 0;                        // overlap, 1 .. H / 2 (not read with W == 1); stride H - O
+  const float* alpha = nullptr;     // device (O) blend weights in [0, 1]
+  int n_pin = 0;                    // 0 .. STITCH_MAX_PINS
+  const float* pin_val = nullptr;   // device (n_pin, C, S)
+  int pin_idx[STITCH_MAX_PINS] = {};// long waypoint of each pin, in [0, H + (W - 1)(H - O)): a kernel argument, baked into a captured node
+};
+// blend and pins in ONE launch, no element written twice; nothing to do (W == 1 and no pin) launches nothing
+int launch_stitch(const StitchArgs& a, hipStream_t s);
+// out (C, L, S): every long waypoint from the window with the smallest w that covers it
+int launch_stitch_assemble(const float* x, float* out, int C, int W, int H, int S, int O, hipStream_t s);
 struct ApfDynArgs {
   float* traj = nullptr;          // (B,H,S) in place (xy only)
   const double* points = nullptr; // (P,2) float64

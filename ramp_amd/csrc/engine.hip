@@ -157,6 +157,10 @@ struct ramp_ctx {
   int* rs_anc = nullptr; size_t rs_anc_cap = 0; double* rs_ess = nullptr; size_t rs_ess_cap = 0; double* rs_cost = nullptr; size_t rs_cost_cap = 0;
   float* rs_u = nullptr; size_t rs_u_cap = 0; int* rs_gf = nullptr; size_t rs_gf_cap = 0;
   float* rs_cloud = nullptr; size_t rs_cloud_cap = 0; int* rs_off = nullptr; size_t rs_off_cap = 0;
+  // stitched windows inside a sampling job (ramp_sample_stitched): {alpha | zeros} (2 O floats; the zeros are the noise stitch's table) and the
+  // pin values (n_pin, C, S), copied here before the launch -- data of a replay.  Windows, overlap, n_pin and the pin indices are kernel
+  // arguments, hence part of the graph key
+  float* st_alpha = nullptr; size_t st_alpha_cap = 0; float* st_pin_val = nullptr; size_t st_pin_val_cap = 0;
   // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
   // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
   hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
@@ -1988,6 +1992,8 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
 // The cost guide of a job (ramp_sample_guided), checked by the entry; only a guide with n_guide > 0 somewhere becomes one
 struct GuideJob { const ramp_cost_guide* cg; };
+// The stitch table of a job (ramp_sample_stitched), checked by the entry
+struct StitchJob { const ramp_stitch* st; };
 // The resampling events of a job (ramp_sample_steered), checked by the entry; only a table with a flag set somewhere becomes one.  The injected
 // uniforms (noise_mode 0) and the four outputs travel with it
 struct ResampleJob {
@@ -1998,10 +2004,12 @@ struct ResampleJob {
 // mj != nullptr: K_j = mj->n_inner[j] inner steps (propose -> one evaluation at x' -> accept) follow the evaluation of iteration j, and the reverse
 // step uses the cached combined gradient of the state they ended on; every evaluation, inner ones included, is one link of the calibration chain
 // gj != nullptr: on iteration j with n_guide[j] > 0 ONE launch runs that many guide iterations on the posterior mean (DDPM) / x0 (DDIM), behind the APF hook
+// sj != nullptr: stitched windows -- the stitch runs wherever the plain job applies its hard conditions (the job carries none: hc.n == 0) and on the
+// array the hooks work on, in front of them and (where one ran) behind them; every noise block is stitched with alpha = 0 first
 // rj != nullptr: on iteration j with resample[j] != 0 the cost of that array (behind the guide) updates the log-weights, and at the end of the
 // iteration every group is resampled: three launches and the copy back, unconditional (identity where nothing resampled), so the graph has no branch
 static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1,
-                       const McmcJob* mj = nullptr, const GuideJob* gj = nullptr, const ResampleJob* rj = nullptr) {
+                       const McmcJob* mj = nullptr, const GuideJob* gj = nullptr, const ResampleJob* rj = nullptr, const StitchJob* sj = nullptr) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -2019,9 +2027,25 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_philox_uniform_sharded(c->m_u, mj->total, B, ((long)p->n_steps + 1 + mj->total) * total * (long)(HS / 4),
                                                                  (long)p->philox_sample0, total, c->s_philox, s));
   }
+  StitchArgs sa;
+  if (sj) {
+    sa = stitch_args(sj->st, B, H, S);
+    sa.alpha = c->st_alpha; sa.pin_val = c->st_pin_val;
+    // the noise blocks are (blocks, C W, H, S): blocks * C chains of W windows; the right window takes the left window's draws
+    StitchArgs na = sa;
+    na.x = c->s_noise; na.C = (p->ddim ? 1 : p->n_steps + 1) * sa.C; na.alpha = c->st_alpha + sa.O; na.n_pin = 0;
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_stitch(na, s));
+  }
+  // the stitch of `target` (blend and pins), in the places of the plain job's hard conditioning
+  auto stitch_at = [&](float* target) -> int {
+    sa.x = target;
+    LAUNCH(c, s, CAT_SAMPLER, 0, launch_stitch(sa, s));
+    return 0;
+  };
   // x_T = noise[0]; apply_hard_conditioning; chain[0]
   RAMP_HIP_CHECK(hipMemcpyAsync(c->s_x, c->s_noise, n * 4, hipMemcpyDeviceToDevice, s));
-  LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x, hc, B, H, S, s));
+  if (sj) CK(stitch_at(c->s_x));
+  else LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x, hc, B, H, S, s));
   if (chain) RAMP_HIP_CHECK(hipMemcpyAsync(c->s_chain, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   ApfArgs ap; ap.cloud = c->s_cloud; ap.window = c->s_window; ap.B = B; ap.H = H; ap.S = S; ap.P = p->apf.n_points;
   ap.win = p->apf.window; ap.thr = p->apf.threshold; ap.strength = p->apf.strength;
@@ -2141,28 +2165,42 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     m.w0 = (float)p->w0; m.w1 = (float)p->w1; m.w0p1 = (float)(1.0 + p->w0);
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
     float* chain_j = chain ? c->s_chain + (size_t)(j + 1) * n : nullptr;
+    float* chain_fin = sj ? nullptr : chain_j;      // (a stitched job's chain block is the state after the closing stitch)
     const bool apf = (p->apf.cloud != nullptr || sc_apf) && p->apply_apf && p->apply_apf[j];
+    const bool hooked = sj && (apf || (gj && gj->cg->n_guide[j] > 0));      // a hook moves the array on this iteration: one more stitch behind it
     // the guidance step: the shared prefix has combined the rows already (one row left); otherwise by the job's scalars or its weight table
     const bool by_table = c->g_weight_cur && !combined;
     if (!p->ddim) {
       m.coef1 = p->coef1[j]; m.coef2 = p->coef2[j]; m.mean = c->s_mean; m.x0 = nullptr;
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
+      if (sj) CK(stitch_at(c->s_mean));
       if (apf) { ap.traj = c->s_mean; for (int q = 0; q < std::max(1, p->apf.passes); ++q) LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); }
       CK(guide_at(j, c->s_mean));
+      if (hooked) CK(stitch_at(c->s_mean));
       CK(weigh_at(j, c->s_mean));
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddpm_finish(c->s_mean, c->s_noise + (size_t)(j + 1) * n, p->stdv[j], p->noise_scale ? p->noise_scale[j] : 1.f, p->use_noise[j],
-                            hc, c->s_x, chain_j, B, H, S, s));
+                            hc, c->s_x, chain_fin, B, H, S, s));
     } else {
       m.mean = nullptr; m.x0 = c->s_x0;
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
+      if (sj) CK(stitch_at(c->s_x0));
       if (apf) {
         ap.traj = c->s_x0;
-        for (int q = 0; q < std::max(1, p->apf.passes); ++q) { LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x0, hc, B, H, S, s)); }
+        for (int q = 0; q < std::max(1, p->apf.passes); ++q) {
+          LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s));
+          if (sj) CK(stitch_at(c->s_x0));
+          else LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x0, hc, B, H, S, s));
+        }
       }
       CK(guide_at(j, c->s_x0));      // (the hard conditioning that follows is ddim_finish's own)
+      if (hooked) CK(stitch_at(c->s_x0));
       CK(weigh_at(j, c->s_x0));
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], hc,
-                            c->s_x, chain_j, B, H, S, s));
+                            c->s_x, chain_fin, B, H, S, s));
+    }
+    if (sj) {      // the update ran without hard conditions: the blend is the identity here, the pins act
+      CK(stitch_at(c->s_x));
+      if (chain_j) RAMP_HIP_CHECK(hipMemcpyAsync(chain_j, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
     }
     CK(resample_at(j, chain_j));
   }
@@ -2223,7 +2261,7 @@ static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, 
 static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
                       void* stream, const ramp_guidance_rows* g = nullptr, const McmcJob* mj = nullptr, const float* mcmc_noise = nullptr,
                       const float* mcmc_u = nullptr, int32_t* accept_out = nullptr, const GuideJob* gj = nullptr,
-                      const ResampleJob* rj = nullptr) {
+                      const ResampleJob* rj = nullptr, const StitchJob* sj = nullptr) {
   RAMP_REQUIRE(c && p, "null argument");
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
@@ -2307,6 +2345,17 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     }
   }
+  if (sj) {      // {alpha | zeros} and the pin values
+    const ramp_stitch* st = sj->st;
+    const int O = st->n_windows > 1 ? st->overlap : 0;
+    std::vector<float> al(2 * (size_t)O, 0.f);
+    for (int k = 0; k < O; ++k) al[k] = st->alpha_host[k];
+    const size_t pv = (size_t)st->n_pin * (B / st->n_windows) * S;
+    CK(grow(c, c->st_alpha, c->st_alpha_cap, std::max<size_t>(4, al.size())));
+    CK(grow(c, c->st_pin_val, c->st_pin_val_cap, std::max<size_t>(4, pv)));
+    if (O) RAMP_HIP_CHECK(hipMemcpyAsync(c->st_alpha, al.data(), al.size() * 4, hipMemcpyHostToDevice, s));      // (pageable host memory: staged before the call returns)
+    if (pv) RAMP_HIP_CHECK(hipMemcpyAsync(c->st_pin_val, st->pin_val, pv * 4, hipMemcpyDeviceToDevice, s));
+  }
   std::vector<float> g_host;      // the weights on the host: part of the canonical calibration's key below
   if (g) {
     const size_t nw = (size_t)B * p->n_rp;
@@ -2370,6 +2419,11 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     const double sc5[5] = {rs->ess_frac, rc->radius, rc->w_obs, rc->w_smooth, rc->w_acc}; key.put(sc5, 5);
     key.put(rs->resample, p->n_steps); key.put(rs->lambda, p->n_steps);
   }
+  if (sj) {      // (st_alpha / st_pin_val exist only for such a job; the layout and the pin indices are kernel arguments of the captured nodes)
+    const ramp_stitch* st = sj->st;
+    const int tag[4] = {0x53544348 /* "STCH" */, st->n_windows, st->n_windows > 1 ? st->overlap : 0, st->n_pin}; key.put(tag, 4);
+    if (st->n_pin) key.put(st->pin_idx_host, st->n_pin);
+  }
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
@@ -2407,7 +2461,7 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
   c->last_job_steps = h3 ? n_evals : 0;
   if (!p->use_graph) {
-    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj, gj, rj));
+    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj, gj, rj, sj));
   } else {
     if (key.bytes != c->graph_key) { drop_graphs(c->s_graph, 3); c->graph_key = key.bytes; c->graph_rerun_key.clear(); }
     hipGraphExec_t* slot = &c->s_graph[steady ? 1 : 0];
@@ -2417,7 +2471,7 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       if (rk.bytes != c->graph_rerun_key) drop_graphs(slot, 1);
       c->graph_rerun_key = rk.bytes;
     }
-    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj, gj, rj); }));
+    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj, gj, rj, sj); }));
   }
   if (mj && accept_out) RAMP_HIP_CHECK(hipMemcpyAsync(accept_out, c->m_flag, (size_t)mj->total * B * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (rj) {
@@ -2474,7 +2528,7 @@ int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_gu
 static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
                           const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
                           const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who,
-                          ResampleJob* rj = nullptr) {
+                          ResampleJob* rj = nullptr, const StitchJob* sj = nullptr) {
   const std::string w = std::string(who) + ": ";
   const int kind = m ? m->kind : 0;
   RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");
@@ -2530,7 +2584,7 @@ static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_c
   }
   // (kind 0, or no inner step anywhere: the plain job; no guide iteration anywhere: the unguided job)
   const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g, mj.total > 0 ? &mj : nullptr, mcmc_noise, mcmc_u, accept_out,
-                            guide_total > 0 ? &gj : nullptr, rj);
+                            guide_total > 0 ? &gj : nullptr, rj, sj);
   c->g_weight_cur = nullptr;
   return rc;
 }
@@ -2561,6 +2615,25 @@ int ramp_sample_steered(ramp_ctx* c, const ramp_sample_params* p, const ramp_res
     return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
   RAMP_REQUIRE(rs->cost, "ramp_sample_steered: null cost table");
   return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_steered", &rj);
+}
+
+// ramp_sample_guided (no MCMC, no composed weights) on stitched windows.  st == NULL is that entry itself
+int ramp_sample_stitched(ramp_ctx* c, const ramp_sample_params* p, const ramp_stitch* st, const ramp_cost_guide* cg, const ramp_scene_batch* scenes,
+                         const float* noise, float* chain_out, float* x_out, float* long_out, void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_stitched: null argument");
+  if (!st) {
+    RAMP_REQUIRE(!long_out, "ramp_sample_stitched: long_out needs a stitch table");
+    return sample_refined(c, p, cg, nullptr, nullptr, scenes, noise, nullptr, nullptr, chain_out, x_out, nullptr, stream, "ramp_sample_guided");
+  }
+  const int H = c->cfg.horizon, S = c->cfg.state_dim;
+  CK(check_stitch(st, p->B, H, "ramp_sample_stitched"));
+  RAMP_REQUIRE(p->n_hard == 0, "ramp_sample_stitched: p->n_hard must be 0 (the pins are the job's conditions)");
+  RAMP_REQUIRE(p->philox_total == 0, "ramp_sample_stitched: a sharded job is not served (the windows of a chain must sit in one shard)");
+  StitchJob sj{st};
+  CK(sample_refined(c, p, cg, nullptr, nullptr, scenes, noise, nullptr, nullptr, chain_out, x_out, nullptr, stream, "ramp_sample_stitched", nullptr, &sj));
+  if (long_out)
+    CK(launch_stitch_assemble(c->s_x, long_out, p->B / st->n_windows, st->n_windows, H, S, st->overlap, as_stream(stream)));
+  return 0;
 }
 
 // ---- receding-horizon replanning --------------------------------------------------------------------

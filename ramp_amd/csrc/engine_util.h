@@ -131,6 +131,34 @@ GuideArgs guide_args(const ramp_cost_guide* cg, float* traj, int B, int H, int S
   return a;
 }
 
+// what ramp_sample_stitched and ramp_stitch_windows (`who`) require of a stitch table on B rows of H waypoints: host checks only, made before
+// anything is staged or launched
+int check_stitch(const ramp_stitch* st, int B, int H, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(st, w + "null stitch table");
+  const int W = st->n_windows, O = st->overlap;
+  RAMP_REQUIRE(W >= 1, w + "n_windows must be at least 1");
+  RAMP_REQUIRE(B > 0 && B % W == 0, w + "the batch must be a multiple of n_windows (B = C * W rows)");
+  if (W > 1) {
+    RAMP_REQUIRE(O >= 1 && 2 * O <= H, w + "overlap outside 1 .. H / 2");
+    RAMP_REQUIRE(st->alpha_host, w + "null alpha table");
+    for (int k = 0; k < O; ++k)
+      RAMP_REQUIRE(std::isfinite(st->alpha_host[k]) && st->alpha_host[k] >= 0.f && st->alpha_host[k] <= 1.f, w + "alpha must be finite and lie in [0, 1]");
+  }
+  RAMP_REQUIRE(st->n_pin >= 0 && st->n_pin <= RAMP_STITCH_MAX_PINS, w + "n_pin outside 0 .. RAMP_STITCH_MAX_PINS");
+  RAMP_REQUIRE(st->n_pin == 0 || (st->pin_idx_host && st->pin_val), w + "null pin table");
+  const int L = H + (W - 1) * (H - (W > 1 ? O : 0));
+  for (int i = 0; i < st->n_pin; ++i) RAMP_REQUIRE(st->pin_idx_host[i] >= 0 && st->pin_idx_host[i] < L, w + "pin index outside [0, L)");
+  return 0;
+}
+// the kernel's arguments from a checked table; x, alpha and pin_val are the caller's to fill
+StitchArgs stitch_args(const ramp_stitch* st, int B, int H, int S) {
+  static_assert(STITCH_MAX_PINS == RAMP_STITCH_MAX_PINS, "one pin limit");
+  StitchArgs a; a.W = st->n_windows; a.C = B / a.W; a.H = H; a.S = S; a.O = a.W > 1 ? st->overlap : 0; a.n_pin = st->n_pin;
+  for (int i = 0; i < st->n_pin; ++i) a.pin_idx[i] = st->pin_idx_host[i];
+  return a;
+}
+
 // what the guided replans, ramp_guide_step_moving and ramp_guide_cost_moving (`who`) require of a replan guide on (H, S) rows: host checks
 // only, made before anything is staged or launched.  n_scenes > 0: the scene count the job asks for; n_steps > 0: a job, whose n_guide /
 // step tables are checked too and whose guide iterations are counted into *total

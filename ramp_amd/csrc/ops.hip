@@ -191,6 +191,38 @@ int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ra
   return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
 }
 
+// the stitch on the caller's array: the blend weights go to the device in a block of their own (synchronises `stream`)
+int ramp_stitch_windows(float* x, int32_t C, int32_t W, int32_t H, int32_t S, const ramp_stitch* st, void* stream) {
+  RAMP_REQUIRE(x && st, "ramp_stitch_windows: null argument");
+  RAMP_REQUIRE(C > 0 && W >= 1 && H > 0 && S > 0 && (long)C * W * H * S < (1l << 31), "ramp_stitch_windows: bad dims");
+  RAMP_REQUIRE(st->n_windows == W, "ramp_stitch_windows: W differs from the table's n_windows");
+  CK(check_stitch(st, C * W, H, "ramp_stitch_windows"));
+  hipStream_t s = as_stream(stream);
+  StitchArgs a = stitch_args(st, C * W, H, S);
+  a.x = x; a.pin_val = st->pin_val;
+  float* d = nullptr;
+  int rc = 0;
+  if (W > 1) {
+    RAMP_HIP_CHECK(hipMalloc(&d, (size_t)a.O * 4));
+    if (hipMemcpy(d, st->alpha_host, (size_t)a.O * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("ramp_stitch_windows: copy of the blend table failed"); rc = -1; }
+    a.alpha = d;
+  }
+  if (rc == 0) rc = launch_stitch(a, s);
+  (void)hipStreamSynchronize(s);
+  if (d) (void)hipFree(d);
+  return rc;
+}
+
+int ramp_stitch_assemble(const float* x, int32_t C, int32_t W, int32_t H, int32_t S, int32_t O, float* long_out, void* stream) {
+  RAMP_REQUIRE(x && long_out, "ramp_stitch_assemble: null argument");
+  RAMP_REQUIRE(C > 0 && W >= 1 && H > 0 && S > 0 && (long)C * W * H * S < (1l << 31), "ramp_stitch_assemble: bad dims");
+  RAMP_REQUIRE(W == 1 || (O >= 1 && 2 * O <= H), "ramp_stitch_assemble: overlap outside 1 .. H / 2");
+  hipStream_t s = as_stream(stream);
+  const int rc = launch_stitch_assemble(x, long_out, C, W, H, S, O, s);
+  (void)hipStreamSynchronize(s);
+  return rc;
+}
+
 // the replans' guide kernels on the caller's arrays: offsets | hard-condition indices | moving points | tracks go to the device in one block
 // of their own (synchronises `stream`)
 static int moving_guide_op(MovingGuideArgs a, const ramp_replan_guide* rg, const int32_t* traj_scene, const int32_t* pin_first, int32_t n_hard,

@@ -607,15 +607,20 @@ class _GaussianDiffusionBase(nn.Module):
 
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
                 return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None,
-                mcmc: Optional[dict] = None, cost_guide: Optional[dict] = None, resample: Optional[dict] = None):
+                mcmc: Optional[dict] = None, cost_guide: Optional[dict] = None, resample: Optional[dict] = None,
+                stitch: Optional[dict] = None):
         """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
         (``ramp_sample_scenes``); ``obstacle_pts`` is not read then.  ``guidance`` (with a ``scene_job``): a composed job
         (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``.
         ``mcmc``: Langevin refinement inside the job (``ramp_sample_mcmc``, the one entry for all three kinds of job; ``mcmc_tables``);
         the accept flags land in ``self.last_mcmc``.  ``cost_guide``: cost-gradient guidance inside the job (``ramp_sample_guided``, the
         same one entry with the guide added; ``guide_tables``).  ``resample``: resampling events inside the job (``ramp_sample_steered``;
-        ``resample_tables``); ancestors, ESS, costs and final log-weights land in ``self.last_resample``."""
+        ``resample_tables``); ancestors, ESS, costs and final log-weights land in ``self.last_resample``.  ``stitch`` (with a ``scene_job``
+        and empty ``hard_conds``): stitched windows (``ramp_sample_stitched``) -- the dict of ``run_inference_stitched``: ``n_windows``,
+        ``overlap``, ``alpha`` (O) float32, ``pin_idx`` (n_pin) int32, ``pin_val`` device (n_pin, C, S) or None."""
         m = self.model
+        if stitch is not None and (mcmc is not None or resample is not None or guidance is not None or hard_conds):
+            raise NotImplementedError("stitched windows take no mcmc=, resample=, composed weights or hard conditions of their own")
         rtab = resample_tables(resample, steps) if resample is not None else None
         if rtab is not None:
             if self._philox_shard is not None:
@@ -691,6 +696,8 @@ class _GaussianDiffusionBase(nn.Module):
             p.noise_mode = 1
             p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim, tab['total'] if tab else 0,
                                                                                                      n_ev * rs.n_groups if n_ev else 0)
+            if stitch is not None:      # (never a shard: the entry takes a whole job, spelled 0 / 0)
+                p.philox_sample0, p.philox_total = 0, 0
         else:
             noise = noise.contiguous()
             if tab and tab['total']:      # the inner steps' draws, behind the loop's own in call order
@@ -705,7 +712,13 @@ class _GaussianDiffusionBase(nn.Module):
             lib = _lib.load()
 
             def job():
-                if rs is not None:
+                if stitch is not None:
+                    from .stitch import fill_stitch
+                    st = fill_stitch(stitch['n_windows'], stitch['overlap'], stitch['alpha'], stitch['pin_idx'], stitch['pin_val'])
+                    _lib.check(lib.ramp_sample_stitched(m.ctx(), C.byref(p), C.byref(st), C.byref(cg) if cg is not None else None,
+                                                        C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(chain),
+                                                        _lib.ptr(x_out), None, _lib.current_stream()), "ramp_sample_stitched")
+                elif rs is not None:
                     _lib.check(lib.ramp_sample_steered(m.ctx(), C.byref(p), C.byref(rs), C.byref(cg) if cg is not None else None,
                                                        C.byref(mp) if mp is not None else None, C.byref(rows) if rows is not None else None,
                                                        C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
@@ -763,7 +776,7 @@ class _GaussianDiffusionBase(nn.Module):
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
                       noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, cost_guide=None, resample=None,
-                      **sample_kwargs):
+                      stitch=None, **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
@@ -775,6 +788,8 @@ class _GaussianDiffusionBase(nn.Module):
                 raise NotImplementedError("cost_guide= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if resample is not None:
                 raise NotImplementedError("resample= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
+            if stitch is not None:
+                raise NotImplementedError("run_inference_stitched runs the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if scene_job is not None:
                 raise NotImplementedError("run_inference_scenes runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
                                           "scene's batch at a time -- use run_inference per scene")
@@ -797,7 +812,7 @@ class _GaussianDiffusionBase(nn.Module):
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
                                     cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide,
-                                    resample=resample)
+                                    resample=resample, stitch=stitch)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -839,7 +854,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
-                           guidance=None, mcmc=None, cost_guide=None, resample=None, **sample_kwargs):
+                           guidance=None, mcmc=None, cost_guide=None, resample=None, stitch=None, **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
         B = shape[0]
@@ -849,7 +864,7 @@ class _GaussianDiffusionBase(nn.Module):
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
                                     return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide,
-                                    resample=resample)
+                                    resample=resample, stitch=stitch)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -967,6 +982,66 @@ class _GaussianDiffusionBase(nn.Module):
                                                   **diffusion_kwargs)
         chain = chain.permute(1, 0, 2, 3)
         return (chain if return_chain else chain[-1]), job['traj_scene']
+
+    @torch.no_grad()
+    def run_inference_stitched(self, scenes, hard_conds, n_windows, overlap, n_samples=1, blend='ramp', return_chain=False,
+                               return_windows=False, cost_guide=None, **diffusion_kwargs):
+        """Plans LONGER than the network's horizon in one job: every one of the ``n_samples`` long trajectories of
+        ``L = H + (n_windows - 1)(H - overlap)`` waypoints is ``n_windows`` overlapping windows of ``H`` waypoints in adjacent rows of the batch,
+        made to agree on the waypoints they share after every reverse step (``ramp_sample_stitched``; include/ramp_hip.h states the stitch
+        and its places in the job, ``ramp_amd.stitch`` its numpy reference).
+
+        scenes      one ``obstacle_pts`` tensor for every window, or a list of ``n_windows`` tensors: window w is conditioned on (and, with
+                    APF or ``cost_guide``, avoids the cloud of) its own scene
+        hard_conds  ONE dict {long waypoint index: (S,) or (n_samples, S)}, negative indices counted from L -- typically {0: start, -1: goal}
+        overlap     1 .. H / 2 shared waypoints of neighbouring windows (not read with one window)
+        blend       'ramp' | 'mean' | 'left' (``stitch.blend_weights``) or the (overlap,) weights in [0, 1] themselves
+        cost_guide  as in ``run_inference_scenes``, one cloud per window scene.  The job has no hard conditions of its own: the guide sees
+                    the pinned values in its target and may move them; the stitch behind it restores them
+
+        Returns (n_samples, L, S); with ``return_chain`` (steps + 1, n_samples, L, S); with ``return_windows`` a pair whose second entry is
+        the (..., n_samples * n_windows, H, S) windows.  Sampler choice, Philox or torch noise, the repeat of a flagged job and ``guide`` /
+        ``n_guide_steps`` / ``t_start_guide`` are ``run_inference_scenes``'.  Not supported (NotImplementedError): ``mcmc=``, ``resample=``,
+        compose, a caller-supplied ``sample_fn``, a noise shard or multi-rank process group, the dynamic planner.  No claim is made about
+        plan quality: the network's checkpoints were trained on single windows."""
+        import torch.distributed as tdist
+        from . import stitch as _st
+        if not self._scenes_supported:
+            raise NotImplementedError(f"{type(self).__name__} has no stitched job")
+        if self.compose:
+            raise NotImplementedError("run_inference_stitched: compose is not supported (composed weights with stitching are out of scope)")
+        for k in ('mcmc', 'resample'):
+            if diffusion_kwargs.get(k) is not None:
+                raise NotImplementedError(f"run_inference_stitched: {k}= is not supported (its proposals / ancestors would have to be chain-wise)")
+        if not self._is_fused_ddpm_step(diffusion_kwargs.get('sample_fn')):
+            raise NotImplementedError("run_inference_stitched runs the fused job only: a caller-supplied sample_fn steps on its own")
+        if self._philox_shard is not None:
+            raise NotImplementedError("run_inference_stitched: a noise shard (set_noise_shard) is not supported -- the windows of a chain must sit in one shard")
+        if tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
+            raise NotImplementedError("run_inference_stitched under a multi-rank process group: sharding a stitched job is out of scope")
+        dev, m = self._device(), self.model
+        H, S, W, Cn = m.n_support_points, self.state_dim, int(n_windows), int(n_samples)
+        scene_list = list(scenes) if isinstance(scenes, (list, tuple)) else [scenes]
+        if isinstance(scenes, (list, tuple)) and len(scene_list) != W:
+            raise ValueError(f"run_inference_stitched: {len(scene_list)} scenes for {W} windows; one tensor for all windows or one per window")
+        use_cloud = bool(self.APF and self._supports_apf)
+        tab = _st.build_stitch_tables(H, W, overlap, Cn, len(scene_list), list(hard_conds.keys()),
+                                      [int(s.numel() // 2) for s in scene_list] if use_cloud else None)
+        O = int(overlap) if W > 1 else 0
+        sd = {'n_windows': W, 'overlap': O, 'alpha': _st.blend_table(blend, O),'pin_idx': tab['pin_idx'], 'pin_val': _st.pin_values(hard_conds, Cn, S, dev)}
+        m.ctx()
+        lat = torch.cat([m.encode_scenes([s.to(dev) for s in scene_list]), torch.zeros(1, m.context_dim, device=dev)])
+        m.set_scenes(lat, tab['row_variant'])
+        job = {'n_scenes': len(scene_list), 'traj_scene': torch.from_numpy(tab['traj_scene']).to(dev), 'cloud_offset': tab.get('cloud_offset'),
+               'cloud_points': (torch.cat([s.reshape(-1, 2).to(dev, torch.float32) for s in scene_list]).contiguous() if use_cloud else None)}
+        for k in ('guide', 'n_guide_steps', 't_start_guide'):
+            diffusion_kwargs.pop(k, None)
+        _samples, chain = self.conditional_sample({}, batch_size=tab['B'], ddim=False, return_chain=True, obstacle_pts=None, scene_job=job,
+                                                  stitch=sd, cost_guide=cost_guide, **diffusion_kwargs)
+        windows = chain.permute(1, 0, 2, 3)
+        windows = (windows if return_chain else windows[-1]).contiguous()
+        long = _st.assemble(windows, W, O)
+        return (long, windows) if return_windows else long
 
     @torch.no_grad()
     def _prepare_composed_job(self, scenes, hard_conds, n_samples, weights=None, apf_clouds=None):
