@@ -20,6 +20,8 @@ sample gets its own cond / uncond pair, so ``--n-samples N`` equals N independen
 
 ``--evaluate`` (opt-in; the reference only plots the boxes and spheres) tests the final batch against them, at the waypoints and on the
 segments between them, and picks a free trajectory: ``Metrics3d.evaluate_scenes`` + ``select_best_clear_scenes``, one more JSON line.
+``--guide-obstacles`` (opt-in; the reference's guide is a stub) guides the samples against the same boxes and spheres inside the job, segments
+included, with the margin ``--evaluate`` uses: the swept primitive term of ``cost_guide=`` (``obstacle_guide`` below).
 """
 from __future__ import annotations
 
@@ -139,6 +141,9 @@ def main(argv=None):
     ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=Config3d.unet_dim_mults_option)
     ap.add_argument("--evaluate", action="store_true",
                     help="evaluate the batch against the experiment's boxes and spheres, waypoints and segments (Metrics3d), and pick a winner")
+    ap.add_argument("--guide-obstacles", action="store_true",
+                    help="guide the samples away from the experiment's boxes and spheres inside the job: the swept primitive term of cost_guide= "
+                         "(segments included, the margin --evaluate uses)")
     args = ap.parse_args(argv)
     cfg = Config3d(); cfg.n_samples, cfg.n_diffusion_steps, cfg.model_id, cfg.seed = args.n_samples, args.n_diffusion_steps, args.model_id, args.seed
     cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
@@ -170,6 +175,8 @@ def main(argv=None):
     context = {'dataset': dataset}
     t_start_guide = ceil(cfg.start_guide_steps_fraction * model.n_diffusion_steps)
     sample_fn_kwargs = dict(guide=None, n_guide_steps=cfg.n_guide_steps, t_start_guide=t_start_guide, noise_std_extra_schedule_fn=lambda x: 0.5)
+    if args.guide_obstacles:
+        sample_fn_kwargs["cost_guide"] = obstacle_guide(data, dataset.normalizer, t_start=t_start_guide)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     trajs_normalized_iters = model.run_inference(context, hard_conds, n_samples=cfg.n_samples, horizon=n_support_points, return_chain=True,
                                                  traj_normalized=traj_normalized, obstacle_pts=obstacle_pts, sample_fn=ddpm_sample_fn,
@@ -186,6 +193,27 @@ def main(argv=None):
     return out, trajs_normalized_iters
 
 
+EVAL_MARGIN = 0.0      # the robot radius --evaluate widens the boxes and spheres by; --guide-obstacles guides against the same
+
+
+def obstacle_guide(data, normalizer, margin: float = EVAL_MARGIN, band: float = 0.05, step: float = 0.5, n_steps: int = 8, n_sub: int = 4,
+                   t_start: float = float("inf")) -> dict:
+    """``cost_guide=`` against the experiment's own boxes and spheres (the primitives-only guide: no cloud term), in the normalised
+    coordinates the sampler works in: the limits normaliser is x -> 2 (x - lo) / (hi - lo) - 1 per axis, so a box keeps its shape; a sphere
+    does only where the three position axes share one scale, which is asked for.  ``t_start``: the reverse steps with t < t_start are
+    guided -- the script hands over the t_start_guide the reference computes and never uses."""
+    lo, hi = (torch.as_tensor(v, dtype=torch.float32).cpu()[:3] for v in (normalizer.mins, normalizer.maxs))
+    scale = 2.0 / (hi - lo)
+    if not torch.allclose(scale, scale[0].expand(3)):
+        raise NotImplementedError("--guide-obstacles: the normaliser scales the position axes differently (spheres would become ellipsoids)")
+    norm = lambda c: (torch.as_tensor(c, dtype=torch.float32) - lo) * scale - 1.0      # noqa: E731
+    sizes = torch.as_tensor(data["box_sizes"], dtype=torch.float32)
+    boxes = (norm(data["box_centers"]), sizes * (scale if sizes.dim() == 2 else scale[0]))
+    spheres = (norm(data["sphere_centers"]), torch.as_tensor(data["sphere_radii"], dtype=torch.float32) * scale[0])
+    return dict(cloud=None, w_obs=0.0, boxes=boxes, spheres=spheres, margin=margin * float(scale[0]), band=band, step=step, n_steps=n_steps,
+                n_sub=n_sub, t_start=t_start)
+
+
 def evaluate(trajs_final, data, threshold: float = 0.01):
     """What the reference's script leaves out: are the sampled trajectories free of the experiment's boxes and spheres -- at the
     waypoints and on the segments between them -- and which free one to execute."""
@@ -194,7 +222,7 @@ def evaluate(trajs_final, data, threshold: float = 0.01):
     boxes = (torch.as_tensor(data["box_centers"]), torch.as_tensor(data["box_sizes"]))
     spheres = (torch.as_tensor(data["sphere_centers"]), torch.as_tensor(data["sphere_radii"]))
     n = trajs_final.shape[0]
-    per_scene, free = Metrics3d.evaluate_scenes(trajs_final, [n], [boxes], [spheres], threshold=threshold, swept=True)
+    per_scene, free = Metrics3d.evaluate_scenes(trajs_final, [n], [boxes], [spheres], threshold=threshold, swept=True, margin=EVAL_MARGIN)
     _, n_free, _, best_row, _ = select_best_clear_scenes(trajs_final, [n], boxes=boxes, spheres=spheres, point_dim=3, swept=True,
                                                          intensity_threshold=threshold)
     m = per_scene[0]

@@ -371,6 +371,68 @@ int ramp_guide_step(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cos
  * Synchronises `stream`. */
 int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene,
                     double* terms_out, void* stream);
+/* ---- swept box and sphere terms in the cost guide, 2-D and 3-D ----
+ * ramp_traj_clearance counts waypoints AND the segments between them against the boxes and spheres of a trajectory's scene, widened by a
+ * robot margin; ramp_cost_guide's obstacle term sees waypoints and cloud points only.  This term lets the guide push on what is counted
+ * afterwards: a signed-distance hinge on the scene's primitives at n_sub samples per segment, its gradient handed back to the segment's two
+ * waypoints (the collision cost on interpolated points of motion-planning diffusion; the reference's configs carry
+ * factor_num_interpolated_points_for_collision for it and its code never reads it).
+ * For one trajectory x (H, S): D = point_dim in {2, 3}, p_h = x[h, 0:D], n = n_sub in 1 .. 8.
+ *   Samples   u_{h,m} = p_h + t_m (p_{h+1} - p_h), t_m = m / n, for h < H - 1 and m = 0 .. n - 1, and u_{H-1,0} = p_{H-1}; m = 0 is the
+ *             waypoint itself, bit for bit.  (H - 1) n + 1 samples, at most 1017.
+ *   Box k     (centre c, full sides s, margin >= 0): half_d = s_d / 2 + margin, q_d = |x_d - c_d| - half_d.  If any q_d > 0:
+ *             phi = sqrt(sum_d max(q_d, 0)^2), grad phi_d = sign(x_d - c_d) max(q_d, 0) / phi.  Otherwise phi = max_d q_d and
+ *             grad phi = sign(x_k - c_k) e_k for the lowest index k that attains the maximum, sign(0) = +1.  phi <= 0 is
+ *             ramp_traj_clearance's "inside the widened box".
+ *   Sphere k  (centre c, radius r): phi = |x - c| - (r + margin), grad phi = (x - c) / |x - c|; a sample at the centre contributes cost and
+ *             no gradient.
+ *   Cost      C_prim = sum over samples u and primitives k with phi_k(u) < band of 1/2 (band - phi_k(u))^2, band >= 0 (band = 0 penalises
+ *             penetration only).  The gradient at a sample: g_u = - sum_k (band - phi_k) grad phi_k, boxes then spheres, in table order.
+ *   Hand-back for h < H - 1: g_prim[h] = sum_{m=0}^{n-1} (1 - t_m) g_{u_{h,m}}; for h = H - 1: g_prim[h] = g_{u_{H-1,0}}; then, for h >= 1,
+ *             + sum_{m=1}^{n-1} t_m g_{u_{h-1,m}}, in this order.
+ *   Total     C = w_obs C_obs + w_prim C_prim + w_smooth C_smooth + w_acc C_acc.  One iteration is ramp_cost_guide's six steps with
+ *             g = w_obs g_obs + (w_prim g_prim + (w_smooth g_s + w_acc g_a)).
+ * All fp32 (margin, band and w_prim rounded to fp32 once), every product and sum rounded as written, the square roots and quotients
+ * correctly rounded; |g|^2 in fp64.  The result for a trajectory does not depend on the rest of the batch.  A trajectory whose scene has no
+ * primitive, and any trajectory with w_prim == 0, gets ramp_cost_guide's arithmetic, bit for bit.
+ * The struct travels WITH a ramp_cost_guide, which keeps supplying the cloud term (possibly an empty table with w_obs = 0), w_smooth, w_acc,
+ * max_norm, n_guide[] and step[].  The four arrays and the two offset tables are copied into buffers of the context before the launch and the
+ * captured graph reads those: other centres, sizes or radii with the same counts replay the same graph and are honoured.  n_scenes, the two
+ * totals, n_sub, margin, band and w_prim are part of the graph key. */
+#define RAMP_PRIM_GUIDE_MAX_SUB 8
+typedef struct ramp_prim_guide {
+  int32_t point_dim;                 /* 2 or 3, <= state_dim, the cost guide's                                    */
+  int32_t n_scenes;                  /* the cost guide's                                                          */
+  const float* box_centers;          /* device (sum n_boxes, point_dim), scenes concatenated                      */
+  const float* box_sizes;            /* device (sum n_boxes, point_dim), full sides                               */
+  const float* sphere_centers;       /* device (sum n_spheres, point_dim)                                         */
+  const float* sphere_radii;         /* device (sum n_spheres)                                                    */
+  const int32_t* box_offset_host;    /* host (n_scenes + 1), [0] = 0, non-decreasing (a scene may have no box)    */
+  const int32_t* sphere_offset_host; /* host (n_scenes + 1), [0] = 0, non-decreasing (a scene may have no sphere) */
+  double margin, band, w_prim;       /* margin >= 0, band >= 0, all finite                                        */
+  int32_t n_sub;                     /* samples per segment, 1 .. RAMP_PRIM_GUIDE_MAX_SUB                         */
+  int32_t reserved;
+} ramp_prim_guide;
+/* ramp_sample_guided plus the primitive term: plain, many-scene, composed and MCMC jobs.  pg == NULL, w_prim == 0 or no primitive in any
+ * scene IS ramp_sample_guided, bit for bit.  The bf16x6 repeat of a flagged job runs the same guide.  ramp_sample_steered and
+ * ramp_sample_stitched keep their signatures and take no primitives.
+ * Refused on the host before any launch (non-zero, "ramp_sample_guided_prims" in ramp_last_error): pg without cg; point_dim outside {2, 3}
+ * or > state_dim or different from cg's; n_sub outside 1 .. 8; H > 128; a negative or non-finite margin or band; a non-finite w_prim; offsets
+ * that are missing or not non-decreasing from 0; a total > 0 with a NULL array; pg->n_scenes different from cg's or the scene batch's; and
+ * what ramp_sample_guided refuses. */
+int ramp_sample_guided_prims(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
+                             const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                             const float* mcmc_noise, const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream);
+/* the kernel alone, the counterpart of ramp_guide_step: its arguments plus pg (NULL = ramp_guide_step).  Refusals as above, with
+ * "ramp_guide_step_prims".  Synchronises `stream`. */
+int ramp_guide_step_prims(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
+                          const int32_t* traj_scene, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
+                          const float* hard_val, void* stream);
+/* terms_out device (B, 4) doubles = {C_obs, C_smooth, C_acc, C_prim} unweighted of the trajectories as they are: columns 0 .. 2 are
+ * ramp_guide_cost's bits, column 3 sums the fp32 values 1/2 (band - phi)^2 in fp64 in a fixed order (0 with pg == NULL; NaN for a scene
+ * index outside the table).  Refusals as above, with "ramp_guide_cost_prims".  Synchronises `stream`. */
+int ramp_guide_cost_prims(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
+                          const int32_t* traj_scene, double* terms_out, void* stream);
 /* ---- resampling trajectories by cost inside the sampling job (SMC steering) ----
  * A job draws B candidates per scene and ranks them when it has finished; sequential Monte Carlo steering (Feynman-Kac steering, twisted SMC
  * for diffusion) weights every candidate at chosen noise levels by a potential on the job's current clean estimate and resamples within the

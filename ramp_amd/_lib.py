@@ -66,6 +66,17 @@ class RampCostGuide(C.Structure):
                 ("n_guide", c_i32p), ("step", c_f32p)]
 
 
+PRIM_GUIDE_MAX_SUB = 8      # RAMP_PRIM_GUIDE_MAX_SUB
+
+
+class RampPrimGuide(C.Structure):
+    """ramp_prim_guide: the swept box and sphere terms that travel with a ramp_cost_guide (ramp_sample_guided_prims) and the kernel-level
+    ramp_guide_step_prims / ramp_guide_cost_prims."""
+    _fields_ = [("point_dim", C.c_int32), ("n_scenes", C.c_int32), ("box_centers", C.c_void_p), ("box_sizes", C.c_void_p),
+                ("sphere_centers", C.c_void_p), ("sphere_radii", C.c_void_p), ("box_offset_host", c_i32p), ("sphere_offset_host", c_i32p),
+                ("margin", C.c_double), ("band", C.c_double), ("w_prim", C.c_double), ("n_sub", C.c_int32), ("reserved", C.c_int32)]
+
+
 STITCH_MAX_PINS = 64        # RAMP_STITCH_MAX_PINS
 
 
@@ -203,6 +214,12 @@ PROTOTYPES = {
     "ramp_guide_step": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_int32, C.c_float,
                                   C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
     "ramp_guide_cost": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_sample_guided_prims": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampCostGuide), C.POINTER(RampPrimGuide),
+                                           C.POINTER(RampMcmcParams), C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
+    "ramp_guide_step_prims": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.POINTER(RampPrimGuide), C.c_void_p,
+                                        C.c_int32, C.c_float, C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
+    "ramp_guide_cost_prims": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.POINTER(RampPrimGuide), C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "ramp_sample_stitched": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampStitch), C.POINTER(RampCostGuide),
                                        C.POINTER(RampSceneBatch)] + [C.c_void_p] * 5),
     "ramp_stitch_windows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampStitch), C.c_void_p]),

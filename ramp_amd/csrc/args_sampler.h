@@ -100,6 +100,23 @@ struct GuideArgs {
 int launch_guide_step(const GuideArgs& a, hipStream_t s);
 // terms (B, 3) doubles = {C_obs, C_smooth, C_acc} unweighted (NaN for a trajectory whose scene index is outside the table)
 int launch_guide_cost(const GuideArgs& a, double* terms, hipStream_t s);
+// ---- swept box and sphere terms of the cost guide (guide_prims.hip; ramp_prim_guide in ramp_hip.h) ---------------
+// GuideArgs plus the scenes' boxes and spheres: C_prim over n_sub samples per segment, handed back to the segment's two waypoints.  The scene
+// of a trajectory is g.scene's; the spans of both tables are clamped to their totals
+struct PrimGuideArgs {
+  GuideArgs g;
+  const float* box_c = nullptr; const float* box_s = nullptr;   // (n_boxes, D) centres and full sides, scenes concatenated
+  const float* sph_c = nullptr; const float* sph_r = nullptr;   // (n_spheres, D) centres, (n_spheres) radii
+  const int* box_off = nullptr; const int* sph_off = nullptr;   // device (g.n_scenes + 1) each
+  int n_boxes = 0, n_spheres = 0;                               // totals
+  float margin = 0, band = 0, w_prim = 0;
+  int n_sub = 1;                                                // 1 .. 8
+};
+// n_iter guide iterations in ONE launch, one block per trajectory; n_iter == 0 launches nothing.  Without a primitive in the trajectory's
+// scene, or with w_prim == 0, a block's arithmetic is guide_step_kernel's
+int launch_guide_prims_step(const PrimGuideArgs& a, hipStream_t s);
+// terms (B, 4) doubles = {C_obs, C_smooth, C_acc, C_prim} unweighted (NaN for a trajectory whose scene index is outside the table)
+int launch_guide_prims_cost(const PrimGuideArgs& a, double* terms, hipStream_t s);
 // ---- stitched windows (stitch.hip; ramp_stitch in ramp_hip.h) ---------------------------------------
 constexpr int STITCH_MAX_PINS = 64;
 struct StitchArgs {

@@ -149,6 +149,11 @@ struct ramp_ctx {
   // copied here before the launch -- the captured graph reads these buffers, so the clouds' contents are data of a replay.  The iteration
   // counts, step sizes and the five scalars are kernel arguments, hence part of the graph key
   float* cg_cloud = nullptr; size_t cg_cloud_cap = 0; int* cg_off = nullptr; size_t cg_off_cap = 0;
+  // its swept box and sphere terms (ramp_sample_guided_prims): centres, sizes / radii and the two offset tables, copied here before the launch
+  // like the clouds -- data of a replay.  The counts, n_sub, margin, band and w_prim are kernel arguments, hence part of the graph key
+  float* pg_boxc = nullptr; size_t pg_boxc_cap = 0; float* pg_boxs = nullptr; size_t pg_boxs_cap = 0;
+  float* pg_sphc = nullptr; size_t pg_sphc_cap = 0; float* pg_sphr = nullptr; size_t pg_sphr_cap = 0;
+  int* pg_boff = nullptr; size_t pg_boff_cap = 0; int* pg_soff = nullptr; size_t pg_soff_cap = 0;
   // resampling inside a sampling job (ramp_sample_steered): per trajectory {logw | c_prev | cum | tmp} (4 B doubles) and the cost terms (3 B), the
   // gather's second buffer, and per event the ancestors, ESS, costs and uniforms; the group table, the uniforms (noise_mode 0) and the potential's
   // clouds are copied here before the launch -- data of a replay.  Flags, lambda, ess_frac and the potential's scalars are in the graph key
@@ -1991,7 +1996,8 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 // The Langevin refinement of a job (ramp_sample_mcmc), checked by the entry: kind 1 ULA / 2 MALA, total = sum of n_inner > 0
 struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
 // The cost guide of a job (ramp_sample_guided), checked by the entry; only a guide with n_guide > 0 somewhere becomes one
-struct GuideJob { const ramp_cost_guide* cg; };
+// pg != nullptr: its swept box and sphere terms (ramp_sample_guided_prims), checked by the entry; only a table that changes the guide becomes one
+struct GuideJob { const ramp_cost_guide* cg; const ramp_prim_guide* pg; };
 // The stitch table of a job (ramp_sample_stitched), checked by the entry
 struct StitchJob { const ramp_stitch* st; };
 // The resampling events of a job (ramp_sample_steered), checked by the entry; only a table with a flag set somewhere becomes one.  The injected
@@ -2056,11 +2062,17 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     ga = guide_args(gj->cg, nullptr, B, H, S);
     ga.cloud = c->cg_cloud; ga.cloud_off = c->cg_off; ga.scene = sc ? c->s_traj_scene : nullptr; ga.hc = hc;
   }
-  // the guide's launch of iteration j on `target`, if it has one
+  // the guide's launch of iteration j on `target`, if it has one: with primitives the kernel that carries their term, the guide's own otherwise
   auto guide_at = [&](int j, float* target) -> int {
     if (!gj || gj->cg->n_guide[j] <= 0) return 0;
     ga.traj = target; ga.n_iter = gj->cg->n_guide[j]; ga.step = gj->cg->step[j];
-    LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_step(ga, s));
+    if (gj->pg) {
+      PrimGuideArgs pa = prim_guide_args(gj->pg, ga);
+      pa.box_c = c->pg_boxc; pa.box_s = c->pg_boxs; pa.sph_c = c->pg_sphc; pa.sph_r = c->pg_sphr; pa.box_off = c->pg_boff; pa.sph_off = c->pg_soff;
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_prims_step(pa, s));
+    } else {
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_step(ga, s));
+    }
     return 0;
   };
   GuideArgs ra;
@@ -2324,6 +2336,25 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
     }
   }
+  int pg_boxes = 0, pg_spheres = 0;
+  if (gj && gj->pg) {      // the primitive tables, staged like the clouds
+    const ramp_prim_guide* pg = gj->pg;
+    const size_t D = pg->point_dim, no = (size_t)pg->n_scenes + 1;
+    pg_boxes = pg->box_offset_host[pg->n_scenes]; pg_spheres = pg->sphere_offset_host[pg->n_scenes];
+    CK(grow(c, c->pg_boxc, c->pg_boxc_cap, std::max<size_t>(4, pg_boxes * D))); CK(grow(c, c->pg_boxs, c->pg_boxs_cap, std::max<size_t>(4, pg_boxes * D)));
+    CK(grow(c, c->pg_sphc, c->pg_sphc_cap, std::max<size_t>(4, pg_spheres * D))); CK(grow(c, c->pg_sphr, c->pg_sphr_cap, std::max<size_t>(4, (size_t)pg_spheres)));
+    CK(grow(c, c->pg_boff, c->pg_boff_cap, no)); CK(grow(c, c->pg_soff, c->pg_soff_cap, no));
+    if (pg_boxes) {
+      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_boxc, pg->box_centers, pg_boxes * D * 4, hipMemcpyDeviceToDevice, s));
+      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_boxs, pg->box_sizes, pg_boxes * D * 4, hipMemcpyDeviceToDevice, s));
+    }
+    if (pg_spheres) {
+      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_sphc, pg->sphere_centers, pg_spheres * D * 4, hipMemcpyDeviceToDevice, s));
+      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_sphr, pg->sphere_radii, (size_t)pg_spheres * 4, hipMemcpyDeviceToDevice, s));
+    }
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_boff, pg->box_offset_host, no * 4, hipMemcpyHostToDevice, s));
+    RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_soff, pg->sphere_offset_host, no * 4, hipMemcpyHostToDevice, s));
+  }
   int rj_points = 0;
   if (rj) {      // the potential's own cloud table, the group table and (noise_mode 0) the uniforms
     const ramp_resample_params* rs = rj->rs;
@@ -2410,6 +2441,11 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     const int tag[5] = {0x47554944 /* "GUID" */, cg->point_dim, cg->n_scenes, gj_points, sc ? 1 : 0}; key.put(tag, 5);
     const double sc5[5] = {cg->radius, cg->w_obs, cg->w_smooth, cg->w_acc, cg->max_norm}; key.put(sc5, 5);
     key.put(cg->n_guide, p->n_steps); key.put(cg->step, p->n_steps);
+    if (gj->pg) {      // (the pg_* buffers exist only for such a job; counts, n_sub and the three scalars are kernel arguments of the captured nodes)
+      const ramp_prim_guide* pg = gj->pg;
+      const int ptag[5] = {0x5052494d /* "PRIM" */, pg->n_scenes, pg_boxes, pg_spheres, pg->n_sub}; key.put(ptag, 5);
+      const double sc3[3] = {pg->margin, pg->band, pg->w_prim}; key.put(sc3, 3);
+    }
   }
   if (rj) {      // (the rs_* buffers exist only for such a job; flags, lambda, ess_frac, the scalars and the Philox group fields are kernel arguments)
     const ramp_resample_params* rs = rj->rs;
@@ -2528,7 +2564,7 @@ int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_gu
 static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
                           const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
                           const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who,
-                          ResampleJob* rj = nullptr, const StitchJob* sj = nullptr) {
+                          ResampleJob* rj = nullptr, const StitchJob* sj = nullptr, const ramp_prim_guide* pg = nullptr) {
   const std::string w = std::string(who) + ": ";
   const int kind = m ? m->kind : 0;
   RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");
@@ -2549,8 +2585,14 @@ static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_c
       RAMP_REQUIRE(kind != 2 || mcmc_u, w + "null mcmc_u (noise_mode 0 injects MALA's uniforms)");
     }
   }
-  GuideJob gj{cg};
+  GuideJob gj{cg, nullptr};
   int guide_total = 0;
+  if (pg) {      // (next to the cost guide it travels with)
+    RAMP_REQUIRE(cg, w + "a primitive table needs its cost guide");
+    CK(check_cost_guide(cg, c->cfg.state_dim, who));
+    CK(check_prim_guide(pg, cg, c->cfg.horizon, c->cfg.state_dim, who));
+    if (prim_guide_active(pg)) gj.pg = pg;
+  }
   if (cg) {
     CK(check_cost_guide(cg, c->cfg.state_dim, who));
     RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the guide kernel serves horizons up to 128");
@@ -2601,6 +2643,15 @@ int ramp_sample_guided(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost
                        const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_guided: null argument");
   return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
+}
+
+// ramp_sample_guided with the swept box and sphere terms.  pg == NULL, w_prim == 0 or no primitive anywhere is that entry itself
+int ramp_sample_guided_prims(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
+                             const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                             const float* mcmc_noise, const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_guided_prims: null argument");
+  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided_prims", nullptr,
+                        nullptr, pg);
 }
 
 // The one entry for every kind of job: ramp_sample_guided plus the resampling events.  rs == NULL or no flag set is that entry itself

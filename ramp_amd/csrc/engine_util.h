@@ -131,6 +131,41 @@ GuideArgs guide_args(const ramp_cost_guide* cg, float* traj, int B, int H, int S
   return a;
 }
 
+// what ramp_sample_guided_prims, ramp_guide_step_prims and ramp_guide_cost_prims (`who`) require of a primitive table next to the checked cost
+// guide cg, on (H, S) trajectories: host checks only, made before anything is staged or launched
+int check_prim_guide(const ramp_prim_guide* pg, const ramp_cost_guide* cg, int H, int S, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(pg && cg, w + "null primitive table or cost guide");
+  RAMP_REQUIRE((pg->point_dim == 2 || pg->point_dim == 3) && pg->point_dim <= S, w + "the primitives' point_dim must be 2 or 3 and at most state_dim");
+  RAMP_REQUIRE(pg->point_dim == cg->point_dim, w + "the primitives' point_dim differs from the cost guide's");
+  RAMP_REQUIRE(pg->n_sub >= 1 && pg->n_sub <= RAMP_PRIM_GUIDE_MAX_SUB, w + "n_sub outside 1 .. RAMP_PRIM_GUIDE_MAX_SUB");
+  RAMP_REQUIRE(H <= 128, w + "the primitive guide kernel serves horizons up to 128");
+  RAMP_REQUIRE(std::isfinite(pg->margin) && pg->margin >= 0.0 && std::isfinite(pg->band) && pg->band >= 0.0,
+               w + "margin and band must be finite and not negative");
+  RAMP_REQUIRE(std::isfinite(pg->w_prim), w + "w_prim must be finite");
+  RAMP_REQUIRE(pg->n_scenes >= 1 && pg->n_scenes == cg->n_scenes, w + "the primitives' n_scenes differs from the cost guide's");
+  RAMP_REQUIRE(pg->box_offset_host && pg->sphere_offset_host && pg->box_offset_host[0] == 0 && pg->sphere_offset_host[0] == 0,
+               w + "bad primitive offsets (both tables, from 0)");
+  for (int i = 0; i < pg->n_scenes; ++i)
+    RAMP_REQUIRE(pg->box_offset_host[i + 1] >= pg->box_offset_host[i] && pg->sphere_offset_host[i + 1] >= pg->sphere_offset_host[i],
+                 w + "primitive offsets must be non-decreasing");
+  RAMP_REQUIRE(pg->box_offset_host[pg->n_scenes] == 0 || (pg->box_centers && pg->box_sizes), w + "null box_centers / box_sizes with a non-empty table");
+  RAMP_REQUIRE(pg->sphere_offset_host[pg->n_scenes] == 0 || (pg->sphere_centers && pg->sphere_radii),
+               w + "null sphere_centers / sphere_radii with a non-empty table");
+  return 0;
+}
+// true: the table changes the guide (a primitive somewhere and w_prim != 0); otherwise the call is the cost guide's own
+bool prim_guide_active(const ramp_prim_guide* pg) {
+  return pg && pg->w_prim != 0.0 && (float)pg->w_prim != 0.f && (pg->box_offset_host[pg->n_scenes] > 0 || pg->sphere_offset_host[pg->n_scenes] > 0);
+}
+// the kernel's arguments from a checked table; the array and offset pointers are the caller's to fill
+PrimGuideArgs prim_guide_args(const ramp_prim_guide* pg, const GuideArgs& g) {
+  PrimGuideArgs a; a.g = g;
+  a.n_boxes = pg->box_offset_host[pg->n_scenes]; a.n_spheres = pg->sphere_offset_host[pg->n_scenes];
+  a.margin = (float)pg->margin; a.band = (float)pg->band; a.w_prim = (float)pg->w_prim; a.n_sub = pg->n_sub;
+  return a;
+}
+
 // what ramp_sample_stitched and ramp_stitch_windows (`who`) require of a stitch table on B rows of H waypoints: host checks only, made before
 // anything is staged or launched
 int check_stitch(const ramp_stitch* st, int B, int H, const char* who) {

@@ -191,6 +191,63 @@ int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ra
   return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
 }
 
+// the primitive guide's kernels on the caller's arrays: cloud offsets | box offsets | sphere offsets | hard-condition indices go to the device in
+// one block of their own (synchronises `stream`)
+static int prim_guide_op(GuideArgs g, const ramp_cost_guide* cg, const ramp_prim_guide* pg, const int32_t* traj_scene, int32_t n_hard,
+                         const int32_t* hard_idx_host, const float* hard_val, double* terms_out, hipStream_t s) {
+  const size_t no = (size_t)cg->n_scenes + 1;
+  std::vector<int32_t> blk(cg->cloud_offset_host, cg->cloud_offset_host + no);
+  blk.insert(blk.end(), pg->box_offset_host, pg->box_offset_host + no);
+  blk.insert(blk.end(), pg->sphere_offset_host, pg->sphere_offset_host + no);
+  blk.insert(blk.end(), hard_idx_host, hard_idx_host + n_hard);
+  int32_t* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, blk.size() * 4));
+  int rc = 0;
+  if (hipMemcpy(d, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("primitive guide: copy of the tables failed"); rc = -1; }
+  g.cloud = cg->cloud_points; g.cloud_off = d; g.scene = traj_scene;
+  g.hc.idx = d + 3 * no; g.hc.val = hard_val; g.hc.n = n_hard;
+  PrimGuideArgs a = prim_guide_args(pg, g);
+  a.box_c = pg->box_centers; a.box_s = pg->box_sizes; a.sph_c = pg->sphere_centers; a.sph_r = pg->sphere_radii;
+  a.box_off = d + no; a.sph_off = d + 2 * no;
+  if (rc == 0) rc = terms_out ? launch_guide_prims_cost(a, terms_out, s) : launch_guide_prims_step(a, s);
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(d);
+  return rc;
+}
+
+int ramp_guide_step_prims(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
+                          const int32_t* traj_scene, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
+                          const float* hard_val, void* stream) {
+  RAMP_REQUIRE(traj && cg, "ramp_guide_step_prims: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_step_prims: bad dims (H up to 128)");
+  CK(check_cost_guide(cg, S, "ramp_guide_step_prims"));
+  if (pg) CK(check_prim_guide(pg, cg, H, S, "ramp_guide_step_prims"));
+  RAMP_REQUIRE(n_iter >= 0 && n_iter <= RAMP_GUIDE_MAX_STEPS, "ramp_guide_step_prims: n_iter outside 0 .. RAMP_GUIDE_MAX_STEPS");
+  RAMP_REQUIRE(std::isfinite(step), "ramp_guide_step_prims: step must be finite");
+  RAMP_REQUIRE(n_hard >= 0 && n_hard <= 256 && (n_hard == 0 || (hard_idx_host && hard_val)), "ramp_guide_step_prims: bad hard conditions");
+  for (int j = 0; j < n_hard; ++j) RAMP_REQUIRE(hard_idx_host[j] >= 0 && hard_idx_host[j] < H, "ramp_guide_step_prims: hard index out of range");
+  if (n_iter == 0) return 0;
+  GuideArgs a = guide_args(cg, traj, B, H, S);
+  a.n_iter = n_iter; a.step = step;
+  if (!prim_guide_active(pg)) return guide_op(a, cg, traj_scene, n_hard, hard_idx_host, hard_val, nullptr, as_stream(stream));
+  return prim_guide_op(a, cg, pg, traj_scene, n_hard, hard_idx_host, hard_val, nullptr, as_stream(stream));
+}
+
+int ramp_guide_cost_prims(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
+                          const int32_t* traj_scene, double* terms_out, void* stream) {
+  RAMP_REQUIRE(traj && cg && terms_out, "ramp_guide_cost_prims: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_cost_prims: bad dims (H up to 128)");
+  CK(check_cost_guide(cg, S, "ramp_guide_cost_prims"));
+  if (pg) CK(check_prim_guide(pg, cg, H, S, "ramp_guide_cost_prims"));
+  GuideArgs a = guide_args(cg, const_cast<float*>(traj), B, H, S);
+  if (pg) return prim_guide_op(a, cg, pg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
+  // no table: an empty one of the guide's shape (C_prim = 0)
+  std::vector<int32_t> zero((size_t)cg->n_scenes + 1, 0);
+  ramp_prim_guide none{};
+  none.point_dim = cg->point_dim; none.n_scenes = cg->n_scenes; none.box_offset_host = zero.data(); none.sphere_offset_host = zero.data(); none.n_sub = 1;
+  return prim_guide_op(a, cg, &none, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
+}
+
 // the stitch on the caller's array: the blend weights go to the device in a block of their own (synchronises `stream`)
 int ramp_stitch_windows(float* x, int32_t C, int32_t W, int32_t H, int32_t S, const ramp_stitch* st, void* stream) {
   RAMP_REQUIRE(x && st, "ramp_stitch_windows: null argument");

@@ -120,7 +120,13 @@ def mcmc_tables(mcmc: dict, steps, alphas_cumprod) -> dict:
     return {'kind': _lib.MCMC_KINDS[kind], 'n_inner': K, 'step_size': eta, 'sigma': sigma, 'total': int(sum(K))}
 
 
-GUIDE_KEYS = {'cloud', 'clouds', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'step', 'n_steps', 't_start', 'max_norm', 'scale_by_variance'}
+GUIDE_PRIM_KEYS = {'boxes', 'spheres', 'margin', 'band', 'w_prim', 'n_sub'}      # the swept box and sphere terms (ramp_prim_guide)
+GUIDE_KEYS = {'cloud', 'clouds', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'step', 'n_steps', 't_start', 'max_norm', 'scale_by_variance'} | GUIDE_PRIM_KEYS
+
+
+def guide_has_prims(cost_guide) -> bool:
+    """True when a ``cost_guide=`` dict carries any key of the swept box and sphere terms."""
+    return isinstance(cost_guide, dict) and bool(GUIDE_PRIM_KEYS & set(cost_guide))
 
 
 def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
@@ -135,8 +141,14 @@ def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
       t_start            only iterations with t < t_start are guided (default inf: all)
       max_norm           clip of the trajectory's gradient norm, 0 = off (default)
       scale_by_variance  multiply the step of iteration j by posterior_variance[t_j] (default False)
+      boxes, spheres     the swept primitive term (ramp_prim_guide): per scene a ``(centres, sizes)`` / ``(centres, radii)`` pair or None --
+                         one entry for a plain job, the per-scene list ``clearance.trajectory_clearance`` takes for a scene / composed job;
+                         ``cloud=None`` with ``w_obs=0`` is the primitives-only guide
+      margin, band, w_prim, n_sub   the robot margin (default 0), the hinge's band (required with primitives), the term's weight (default 1)
+                         and the samples per segment, 1 .. 8 (default 4)
 
-    Returns ``{'n_guide': [...], 'step': [...], 'radius', 'w_obs', 'w_smooth', 'w_acc', 'max_norm', 'total': sum n_guide}``."""
+    Returns ``{'n_guide': [...], 'step': [...], 'radius', 'w_obs', 'w_smooth', 'w_acc', 'max_norm', 'total': sum n_guide}`` and, with any
+    of the primitive keys, ``'prim': {'margin', 'band', 'w_prim', 'n_sub'}``."""
     if not isinstance(cost_guide, dict):
         raise TypeError("cost_guide= takes a dict(cloud= | clouds=, radius=, step=, w_obs=, w_smooth=, w_acc=, n_steps=, t_start=, max_norm=, "
                         "scale_by_variance=)")
@@ -175,6 +187,11 @@ def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
     if not all(np.isfinite(v) for v in st):
         raise ValueError("cost_guide=: step sizes must be finite")
     out.update(n_guide=K, step=st, total=int(sum(K)))
+    if guide_has_prims(cost_guide):
+        from .guide import prim_scalars
+        if cost_guide.get('boxes') is None and cost_guide.get('spheres') is None:
+            raise ValueError("cost_guide=: margin / band / w_prim / n_sub need boxes= or spheres=")
+        out['prim'] = prim_scalars(cost_guide.get('margin', 0.0), cost_guide.get('band'), cost_guide.get('w_prim', 1.0), cost_guide.get('n_sub', 4))
     return out
 
 
@@ -509,20 +526,36 @@ class _GaussianDiffusionBase(nn.Module):
         mp.n_inner, mp.step_size, mp.sigma = arrays.i32(tab['n_inner']), arrays.f32(tab['step_size']), arrays.f32(tab['sigma'])
         return mp
 
-    def _fill_guide(self, arrays: _HostArrays, tab: dict, cost_guide: dict, scene_job: Optional[dict]):
+    def _fill_guide(self, arrays: _HostArrays, tab: dict, cost_guide: dict, scene_job: Optional[dict], ptab: Optional[dict] = None):
         """ramp_cost_guide from the tables of ``guide_tables`` and the guide's clouds: one for a plain job, one per scene for a scene /
-        composed job (a single ``cloud`` then serves every scene)."""
+        composed job (a single ``cloud`` then serves every scene).  A cloud that is None is an empty one; ``ptab``: what ``_prim_tables``
+        returned."""
         from .guide import cloud_table, fill_cost_guide
         n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
         clouds = [cost_guide['cloud']] * n_scenes if 'cloud' in cost_guide else list(cost_guide['clouds'])
         if len(clouds) != n_scenes:
             raise ValueError(f"cost_guide clouds: {len(clouds)} entries for {n_scenes} scene(s)")
+        if any(c is None for c in clouds):      # None = an empty cloud, as wide as the other clouds' or the primitives' points (2 without either)
+            d0 = next((int(torch.as_tensor(c).shape[-1]) for c in clouds if c is not None), ptab['D'] if ptab is not None else 2)
+            clouds = [torch.zeros(0, d0) if c is None else c for c in clouds]
         points, off, d = cloud_table(clouds, self._device())
         if d > self.state_dim:
             raise ValueError(f"cost_guide: {d}-D points on {self.state_dim}-wide states")
+        if ptab is not None and ptab['D'] != d:
+            raise ValueError(f"cost_guide: {d}-D cloud points with {ptab['D']}-D boxes / spheres")
         cg = fill_cost_guide(arrays.keep(points), arrays.keep(off), d, tab)
         cg.n_guide, cg.step = arrays.i32(tab['n_guide']), arrays.f32(tab['step'])
         return cg
+
+    def _prim_tables(self, arrays: _HostArrays, tab: dict, cost_guide: dict, scene_job: Optional[dict]):
+        """The box and sphere tables (``ramp_amd.guide.prim_table``) of a guide whose dict carries the primitive keys, None otherwise."""
+        if 'prim' not in tab:
+            return None
+        from .guide import prim_table
+        n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
+        clouds = [cost_guide['cloud']] if 'cloud' in cost_guide else list(cost_guide['clouds'])
+        d_cloud = next((int(torch.as_tensor(c).shape[-1]) for c in clouds if c is not None), None)
+        return arrays.keep(prim_table(cost_guide.get('boxes'), cost_guide.get('spheres'), n_scenes, d_cloud, self._device()))
 
     def _fill_resample(self, arrays: _HostArrays, tab: dict, resample: dict, scene_job: Optional[dict], hard_conds, B: int):
         """ramp_resample_params from the tables of ``resample_tables``: one group for a plain job, one per scene for a scene / composed job,
@@ -562,6 +595,15 @@ class _GaussianDiffusionBase(nn.Module):
         rs.ess_frac = tab['ess_frac']
         rs.cost = C.pointer(cost)
         return rs, cost, gf
+
+    @staticmethod
+    def _refuse_prims_outside_the_guide(cost_guide, resample, stitch):
+        """The swept primitive term lives in ``cost_guide=`` of plain, scene, composed and MCMC jobs only: host check, before any device call."""
+        if guide_has_prims(resample):
+            raise NotImplementedError("resample=: the potential takes no boxes= / spheres= (the swept primitive term belongs to cost_guide=)")
+        if guide_has_prims(cost_guide) and (stitch is not None or resample is not None):
+            raise NotImplementedError("cost_guide=: boxes= / spheres= (the swept primitive term) are not served on stitched windows or with "
+                                      "resample= (ramp_sample_stitched and ramp_sample_steered take no primitives)")
 
     def _run_guarded(self, job):
         """Run ``job`` under the fp16x3 range-guard policy: a flagged result is discarded and the same job (same noise) repeated, never
@@ -621,6 +663,7 @@ class _GaussianDiffusionBase(nn.Module):
         m = self.model
         if stitch is not None and (mcmc is not None or resample is not None or guidance is not None or hard_conds):
             raise NotImplementedError("stitched windows take no mcmc=, resample=, composed weights or hard conditions of their own")
+        self._refuse_prims_outside_the_guide(cost_guide, resample, stitch)
         rtab = resample_tables(resample, steps) if resample is not None else None
         if rtab is not None:
             if self._philox_shard is not None:
@@ -665,7 +708,12 @@ class _GaussianDiffusionBase(nn.Module):
         chain = torch.empty((n_steps + 1, B, H, S), device=dev, dtype=torch.float32) if return_chain else None
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
         mp = z_in = u_in = accept = None
-        cg = self._fill_guide(arrays, gtab, cost_guide, scene_job) if gtab is not None else None
+        cg = pg = None
+        if gtab is not None:
+            from .guide import fill_prim_guide
+            ptab = self._prim_tables(arrays, gtab, cost_guide, scene_job)
+            cg = self._fill_guide(arrays, gtab, cost_guide, scene_job, ptab)
+            pg = fill_prim_guide(ptab, gtab['prim']) if ptab is not None else None
         rs = ru = r_anc = r_ess = r_cost = r_logw = None
         n_ev = len(rtab['events']) if rtab is not None else 0
         if n_ev:
@@ -725,6 +773,12 @@ class _GaussianDiffusionBase(nn.Module):
                                                        _lib.ptr(u_in), _lib.ptr(ru), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
                                                        _lib.ptr(r_anc), _lib.ptr(r_ess), _lib.ptr(r_cost), _lib.ptr(r_logw),
                                                        _lib.current_stream()), "ramp_sample_steered")
+                elif pg is not None:
+                    _lib.check(lib.ramp_sample_guided_prims(m.ctx(), C.byref(p), C.byref(cg), C.byref(pg), C.byref(mp) if mp is not None else None,
+                                                            C.byref(rows) if rows is not None else None,
+                                                            C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
+                                                            _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
+                                                            _lib.current_stream()), "ramp_sample_guided_prims")
                 elif cg is not None:
                     _lib.check(lib.ramp_sample_guided(m.ctx(), C.byref(p), C.byref(cg), C.byref(mp) if mp is not None else None,
                                                       C.byref(rows) if rows is not None else None,
@@ -874,6 +928,7 @@ class _GaussianDiffusionBase(nn.Module):
                            obstacle_pts=None, **sample_kwargs):
         horizon = horizon or self.model.n_support_points
         shape = (batch_size, horizon, self.state_dim)
+        self._refuse_prims_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'))
         if self.ddim:
             if sample_kwargs.get('mcmc') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
                 raise NotImplementedError("mcmc= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
@@ -1013,6 +1068,8 @@ class _GaussianDiffusionBase(nn.Module):
         for k in ('mcmc', 'resample'):
             if diffusion_kwargs.get(k) is not None:
                 raise NotImplementedError(f"run_inference_stitched: {k}= is not supported (its proposals / ancestors would have to be chain-wise)")
+        if guide_has_prims(cost_guide):
+            raise NotImplementedError("run_inference_stitched: cost_guide= takes no boxes= / spheres= here (ramp_sample_stitched takes no primitives)")
         if not self._is_fused_ddpm_step(diffusion_kwargs.get('sample_fn')):
             raise NotImplementedError("run_inference_stitched runs the fused job only: a caller-supplied sample_fn steps on its own")
         if self._philox_shard is not None:

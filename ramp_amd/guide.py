@@ -2,6 +2,11 @@
 ``ramp_cost_guide`` carries (include/ramp_hip.h states the cost and one guide iteration).  Inside a sampling job the same kernel runs through
 ``cost_guide=`` of ``run_inference*`` (``ramp_amd.diffusion.guide_tables``, ``ramp_sample_guided``).
 
+The swept box and sphere terms that travel with that guide (``ramp_prim_guide``: a signed-distance hinge at ``n_sub`` samples per segment,
+against the primitives ``ramp_amd.clearance`` evaluates): ``prim_table`` builds their device arrays and host offsets, ``prim_guide_step`` /
+``prim_guide_terms`` wrap ``ramp_guide_step_prims`` / ``ramp_guide_cost_prims``; inside a job they are the ``boxes=`` / ``spheres=`` keys of
+``cost_guide=`` (``ramp_sample_guided_prims``).
+
 The replanning jobs have a guide of their own (``ramp_replan_guide``: a moving-cloud term with a per-waypoint track, per-episode pins):
 ``moving_guide_step`` / ``moving_guide_terms`` wrap its kernel-level entries, ``replan_guide_tables`` and ``predict_track`` are the host side of
 ``replan_guide=`` of the dynamic model's entry points."""
@@ -103,6 +108,152 @@ def cost_guide_terms(x: torch.Tensor, cloud_or_clouds: Union[torch.Tensor, Seque
     with torch.cuda.device(dev):
         _lib.check(_lib.load().ramp_guide_cost(_lib.ptr(xx), B, H, S, C.byref(cg), _lib.ptr(ts), _lib.ptr(out), _lib.current_stream()),
                    "ramp_guide_cost")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------- swept box and sphere terms
+PRIM_KEYS = ('boxes', 'spheres', 'margin', 'band', 'w_prim', 'n_sub')
+
+
+def prim_table(boxes, spheres, n_scenes: int, point_dim: Optional[int], device) -> dict:
+    """The scenes' boxes and spheres as ``ramp_prim_guide`` wants them.  ``boxes``: per scene a ``(centres (n, D), sizes (n, D) or (n,))`` pair
+    or None, a single pair for one scene, or None; ``spheres`` likewise with ``(centres (n, D), radii (n,))`` -- the lists
+    ``clearance.trajectory_clearance`` takes.  Returns ``{'D', 'n_scenes', 'box_centers', 'box_sizes', 'sphere_centers', 'sphere_radii'`` (device
+    float32 or None when the table is empty), ``'box_offset', 'sphere_offset'`` (host int32 (n_scenes + 1)), ``'n_boxes', 'n_spheres'}``."""
+    from .clearance import _f32, _per_scene
+    bl, sl = _per_scene("boxes", boxes, True), _per_scene("spheres", spheres, True)
+    for what, v in (("boxes", bl), ("spheres", sl)):
+        if v is not None and len(v) != n_scenes:
+            raise ValueError(f"cost guide {what}: {len(v)} entries for {n_scenes} scene(s)")
+    D = point_dim
+    for v in (bl, sl):
+        e = next((e for e in (v or []) if e is not None), None)
+        if e is not None and D is None:
+            D = int(torch.as_tensor(e[0]).shape[-1])
+    if D is None:
+        raise ValueError("cost guide: point_dim cannot be inferred (no cloud, boxes or spheres were given)")
+    D = int(D)
+    if D not in (2, 3):
+        raise ValueError(f"cost guide: primitives must be 2-D or 3-D; got {D}")
+    bc, bs, sc, sr = [], [], [], []
+    nb, ns = [0] * n_scenes, [0] * n_scenes
+    for i in range(n_scenes):
+        if bl is not None and bl[i] is not None:
+            c, z = _f32(bl[i][0]), _f32(bl[i][1])
+            if c.dim() < 1 or c.shape[-1] != D:
+                raise ValueError(f"scene {i}: box centres must be (n, {D}); got shape {tuple(c.shape)}")
+            c = c.reshape(-1, D)
+            if z.dim() == 1:
+                z = z.unsqueeze(-1).repeat(1, D)
+            z = z.reshape(-1, D)
+            if z.shape[0] != c.shape[0]:
+                raise ValueError(f"scene {i}: {c.shape[0]} box centres but {z.shape[0]} box sizes")
+            bc.append(c); bs.append(z); nb[i] = int(c.shape[0])
+        if sl is not None and sl[i] is not None:
+            c, r = _f32(sl[i][0]), _f32(sl[i][1]).reshape(-1)
+            if c.dim() < 1 or c.shape[-1] != D:
+                raise ValueError(f"scene {i}: sphere centres must be (n, {D}); got shape {tuple(c.shape)}")
+            c = c.reshape(-1, D)
+            if r.shape[0] != c.shape[0]:
+                raise ValueError(f"scene {i}: {c.shape[0]} sphere centres but {r.shape[0]} radii")
+            sc.append(c); sr.append(r); ns[i] = int(c.shape[0])
+    for what, parts in (("box centres", bc), ("box sizes", bs), ("sphere centres", sc), ("sphere radii", sr)):
+        if any(not bool(torch.isfinite(p).all()) for p in parts):
+            raise ValueError(f"cost guide: non-finite {what}")
+    if any(bool((p < 0).any()) for p in bs + sr):
+        raise ValueError("cost guide: box sizes and sphere radii must not be negative")
+    boff, soff = np.zeros(n_scenes + 1, np.int32), np.zeros(n_scenes + 1, np.int32)
+    boff[1:], soff[1:] = np.cumsum(nb), np.cumsum(ns)
+
+    def cat(parts):
+        return torch.cat([p.to(device) for p in parts]).contiguous() if parts and sum(int(p.shape[0]) for p in parts) else None
+    return dict(D=D, n_scenes=n_scenes, box_centers=cat(bc), box_sizes=cat(bs), sphere_centers=cat(sc), sphere_radii=cat(sr),
+                box_offset=boff, sphere_offset=soff, n_boxes=int(boff[-1]), n_spheres=int(soff[-1]))
+
+
+def prim_scalars(margin=0.0, band=None, w_prim=1.0, n_sub=4) -> dict:
+    """margin, band, w_prim and n_sub of a primitive term, checked as the C entries check them."""
+    if band is None:
+        raise ValueError("cost guide: band= is required with boxes= / spheres=")
+    out = dict(margin=float(margin), band=float(band), w_prim=float(w_prim), n_sub=int(n_sub))
+    if not (np.isfinite(out['margin']) and out['margin'] >= 0 and np.isfinite(out['band']) and out['band'] >= 0):
+        raise ValueError("cost guide: margin and band must be finite and not negative")
+    if not np.isfinite(out['w_prim']):
+        raise ValueError("cost guide: w_prim must be finite")
+    if not 1 <= out['n_sub'] <= _lib.PRIM_GUIDE_MAX_SUB:
+        raise ValueError(f"cost guide: n_sub outside 1 .. {_lib.PRIM_GUIDE_MAX_SUB}")
+    return out
+
+
+def fill_prim_guide(tab: dict, scalars: dict) -> _lib.RampPrimGuide:
+    """``ramp_prim_guide`` from ``prim_table`` and ``prim_scalars``; the caller keeps ``tab`` alive for the call."""
+    pg = _lib.RampPrimGuide()
+    pg.point_dim, pg.n_scenes = tab['D'], tab['n_scenes']
+    pg.box_centers, pg.box_sizes = _lib.ptr(tab['box_centers']), _lib.ptr(tab['box_sizes'])
+    pg.sphere_centers, pg.sphere_radii = _lib.ptr(tab['sphere_centers']), _lib.ptr(tab['sphere_radii'])
+    pg.box_offset_host = tab['box_offset'].ctypes.data_as(_lib.c_i32p)
+    pg.sphere_offset_host = tab['sphere_offset'].ctypes.data_as(_lib.c_i32p)
+    pg.margin, pg.band, pg.w_prim, pg.n_sub = scalars['margin'], scalars['band'], scalars['w_prim'], scalars['n_sub']
+    return pg
+
+
+def _prim_setup(x, cloud_or_clouds, boxes, spheres, radius, scalars, cost_scalars, traj_scene):
+    """The two structs of a kernel-level call on x (B, H, S): clouds None = an empty cloud per scene of the primitive lists."""
+    from .clearance import _per_scene
+    dev = x.device
+    B, H, S = x.shape
+    lists = [v for v in (_per_scene("boxes", boxes, True), _per_scene("spheres", spheres, True)) if v is not None]
+    n_scenes = len(_as_clouds(cloud_or_clouds)) if cloud_or_clouds is not None else (len(lists[0]) if lists else 1)
+    d = None if cloud_or_clouds is None else int(torch.as_tensor(_as_clouds(cloud_or_clouds)[0]).shape[-1])
+    tab = prim_table(boxes, spheres, n_scenes, d, dev)
+    clouds = _as_clouds(cloud_or_clouds) if cloud_or_clouds is not None else [torch.zeros(0, tab['D'])] * n_scenes
+    points, off, d = cloud_table(clouds, dev)
+    if d != tab['D']:
+        raise ValueError(f"cost guide: {d}-D cloud points with {tab['D']}-D primitives")
+    cg = fill_cost_guide(points, off, d, dict(cost_scalars, radius=radius))
+    pg = fill_prim_guide(tab, scalars)
+    ts = _scene_table(traj_scene, B, cg.n_scenes, dev)
+    return cg, pg, ts, (points, off, tab)
+
+
+@torch.no_grad()
+def prim_guide_step(x: torch.Tensor, boxes=None, spheres=None, *, band: float, step: float, margin: float = 0.0, w_prim: float = 1.0,
+                    n_sub: int = 4, cloud_or_clouds=None, radius: float = 0.0, w_obs: float = 0.0, w_smooth: float = 0.0, w_acc: float = 0.0,
+                    n_steps: int = 1, max_norm: float = 0.0, hard_conds: Optional[Dict[int, torch.Tensor]] = None, traj_scene=None) -> torch.Tensor:
+    """``n_steps`` guide iterations with the swept box and sphere terms (one launch, ``ramp_guide_step_prims``) on a copy of the (B, H, S)
+    trajectories ``x``.  ``boxes`` / ``spheres``: a ``(centres, sizes)`` / ``(centres, radii)`` pair, or one per scene (None = the scene has
+    none) with ``traj_scene`` (B,); ``cloud_or_clouds``, ``radius`` and ``w_obs`` add ``cost_guide_step``'s cloud term (default: none);
+    ``hard_conds`` as there."""
+    dev = x.device
+    out = x.detach().to(torch.float32).contiguous().clone()
+    B, H, S = out.shape
+    cg, pg, ts, keep = _prim_setup(out, cloud_or_clouds, boxes, spheres, radius, prim_scalars(margin, band, w_prim, n_sub),
+                                   dict(w_obs=w_obs, w_smooth=w_smooth, w_acc=w_acc, max_norm=max_norm), traj_scene)
+    idx, val = None, None
+    hard_conds = hard_conds or {}
+    if hard_conds:
+        idx = (C.c_int32 * len(hard_conds))(*[int(k) if k >= 0 else H + int(k) for k in hard_conds])
+        vals = [torch.as_tensor(v).to(dev, torch.float32) for v in hard_conds.values()]
+        val = torch.stack([v.unsqueeze(0).expand(B, -1) if v.dim() == 1 else v for v in vals]).contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_guide_step_prims(_lib.ptr(out), B, H, S, C.byref(cg), C.byref(pg), _lib.ptr(ts), int(n_steps), float(step),
+                                                     len(hard_conds), C.cast(idx, _lib.c_i32p) if idx is not None else None, _lib.ptr(val),
+                                                     _lib.current_stream()), "ramp_guide_step_prims")
+    return out
+
+
+@torch.no_grad()
+def prim_guide_terms(x: torch.Tensor, boxes=None, spheres=None, *, band: float, margin: float = 0.0, n_sub: int = 4, cloud_or_clouds=None,
+                     radius: float = 0.0, traj_scene=None) -> torch.Tensor:
+    """(B, 4) float64 = the unweighted (C_obs, C_smooth, C_acc, C_prim) of each trajectory (``ramp_guide_cost_prims``)."""
+    dev = x.device
+    xx = x.detach().to(torch.float32).contiguous()
+    B, H, S = xx.shape
+    cg, pg, ts, keep = _prim_setup(xx, cloud_or_clouds, boxes, spheres, radius, prim_scalars(margin, band, 1.0, n_sub), {}, traj_scene)
+    out = torch.empty((B, 4), device=dev, dtype=torch.float64)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_guide_cost_prims(_lib.ptr(xx), B, H, S, C.byref(cg), C.byref(pg), _lib.ptr(ts), _lib.ptr(out),
+                                                     _lib.current_stream()), "ramp_guide_cost_prims")
     return out
 
 
