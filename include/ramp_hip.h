@@ -1007,6 +1007,24 @@ int ramp_op_geglu(const float* ag, float* hg, int32_t n_tok, int32_t F, void* st
 int ramp_op_geglu_bwd(const float* dhg, const float* ag, float* dag, int32_t n_tok, int32_t F, void* stream);
 int ramp_op_attention(const float* qkv, float* o, int32_t R, int32_t L, void* stream);
 int ramp_op_attention_bwd(const float* qkv, const float* dout, float* dqkv, int32_t R, int32_t L, void* stream);
+/* The scene encoders' kernels that look across tokens, one launch each (what ramp_encode_scene / ramp_encode_scenes schedule); every
+ * table is a DEVICE int32 array.  Refused on the host before any launch (non-zero, the entry's name in ramp_last_error): a null
+ * pointer, a non-positive size, dh outside {16, 64}, mode outside {0, 1}, ldo < C.
+ *   attention   qkv (T, 3 heads dh) = [q | k | v], head h at column h dh; o (T, heads dh) = softmax(scale q k^T) v per head.
+ *               _seg: tiles (n_tiles, 3) = {scene's first row, scene's row count, first query of the tile inside the scene}, one tile
+ *               per 64 queries of a scene; a query attends to its own scene's keys only
+ *   colreduce   x (n_seg seglen, C) -> out (n_seg, C): mode 0 the mean, 1 the maximum over each segment's rows.
+ *               _seg: segment s owns the rows [first[s], first[s + 1]); out has row stride ldo >= C, the gap columns are not written
+ *   enc2d_prep  cloud (No, Np, 2) -> centers (No, 2) the mean point, maxd (No) the largest |coordinate - centre| of each obstacle.
+ *               _seg: obstacle o owns the points [obstacle_first[o], obstacle_first[o + 1]) */
+int ramp_op_scene_attention(const float* qkv, float* o, int32_t T, int32_t heads, int32_t dh, float scale, void* stream);
+int ramp_op_scene_attention_seg(const float* qkv, float* o, const int32_t* tiles, int32_t n_tiles, int32_t heads, int32_t dh, float scale,
+                                void* stream);
+int ramp_op_scene_colreduce(const float* x, float* out, int32_t n_seg, int32_t seglen, int32_t C, int32_t mode, void* stream);
+int ramp_op_scene_colreduce_seg(const float* x, float* out, const int32_t* first, int32_t n_seg, int32_t C, int32_t ldo, int32_t mode,
+                                void* stream);
+int ramp_op_scene_enc2d_prep(const float* cloud, int32_t No, int32_t Np, float* centers, float* maxd, void* stream);
+int ramp_op_scene_enc2d_prep_seg(const float* cloud, const int32_t* obstacle_first, int32_t No, float* centers, float* maxd, void* stream);
 
 /* debug taps (cfg.debug_taps = 1): kind "out" = module output, "gout" = dE/d(module output) of
  * the last ramp_score call; module names as in the reference ("downs.0.3", "mid_block1", ...).

@@ -14,6 +14,7 @@ What is captured:
   unet2d_h48.npz              forward_no_energy, eps, per-module outputs + output-grads (N=4 rows)
   unet3d_h48.npz / h64        same for the 3-D net (N=2 rows: cond, uncond)
   scene_latents.npz           2-D 6x64 / 16x64 clouds, 3-D 5x50 / 20x200 clouds
+  scene_latents_edges.npz     2-D 1x7 / 5x13 / 1x65 clouds, 3-D 1x1 / 65x2 clouds (`scene_edges`)
   chain_ddpm_*.npz            full T=25 DDPM chains, B=4, with / without APF, with extra no-noise steps
   chain_ddim_*.npz            DDIM-5 of T=100 chains, with / without APF
   chain3d_ddpm.npz            3-D DDPM T=25: B independent n_samples=1 runs stacked
@@ -208,6 +209,27 @@ def gen_scene_latents(m2, m3):
         arrs[f"cloud3d_{no}x{npnt}"] = c
         arrs[f"lat3d_{no}x{npnt}"] = m3.scene_encoder(torch.from_numpy(c)[None])[0].detach().numpy()
     save("scene_latents.npz", **arrs)
+
+
+def gen_scene_latents_edges(m2, m3):
+    """The reference's latents at the scene encoders' edge shapes, on the clouds of tests/scene_ref.py (latent_cloud): fewer tokens than one
+    64-token attention tile, a partial tile behind a full one, one point, more than 64 obstacles."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import scene_ref
+    arrs = {}
+    for no, npnt in ((1, 7), (5, 13), (1, 65)):
+        enc = ObstacleEncoderSet(num_obstacles=no, num_points=npnt)
+        enc.load_state_dict(m2.scene_encoder.state_dict())
+        enc.eval()
+        c = scene_ref.latent_cloud(False, no, npnt)
+        arrs[f"cloud2d_{no}x{npnt}"] = c
+        with torch.no_grad():
+            arrs[f"lat2d_{no}x{npnt}"] = enc(torch.from_numpy(c)[None])[0].numpy()
+    for no, npnt in ((1, 1), (65, 2)):
+        c = scene_ref.latent_cloud(True, no, npnt)
+        arrs[f"cloud3d_{no}x{npnt}"] = c
+        arrs[f"lat3d_{no}x{npnt}"] = m3.scene_encoder(torch.from_numpy(c)[None])[0].detach().numpy()
+    save("scene_latents_edges.npz", **arrs)
 
 
 def run_static(unet, sp, T, B, cloud, noise, ddim, use_apf, n_without_noise=0):
@@ -847,6 +869,10 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "dynamic":
         m2, sp2, _ = build_unet(4, 48, False)
         gen_dynamic(m2, sp2); return
+    if len(sys.argv) > 1 and sys.argv[1] == "scene_edges":
+        m2, _, _ = build_unet(4, 48, False)
+        m3, _, _ = build_unet(6, 48, True)
+        gen_scene_latents_edges(m2, m3); return
     if len(sys.argv) > 1 and sys.argv[1] == "compat":
         gen_compat(); return
     if len(sys.argv) > 1 and sys.argv[1] == "metrics":
@@ -891,7 +917,7 @@ def main():
     gen_unet("2d_h48", m2, sp2, synth.make_cloud(6, 64, 2, seed=42), 4, 7, seed=10)
     gen_unet("3d_h48", m3, sp3, synth.make_cloud(5, 50, 3, seed=44), 2, 3, seed=11)
     gen_unet("3d_h64", m3b, sp3b, synth.make_cloud(5, 50, 3, seed=44), 2, 20, seed=12)
-    print("scene latents"); gen_scene_latents(m2, m3)
+    print("scene latents"); gen_scene_latents(m2, m3); gen_scene_latents_edges(m2, m3)
     print("apf"); gen_apf()
     print("cost"); gen_cost()
     print("chains 2-D"); gen_chains(m2, sp2)

@@ -827,5 +827,43 @@ int ramp_op_attention_bwd(const float* qkv, const float* dout, float* dqkv, int3
   return launch_attn_bwd(qkv, dout, dqkv, R, L, as_stream(stream));
 }
 
+// ---- the scene encoders' kernels that look across tokens (scene.hip), single-scene and segmented; every table a device int32 array ----
+int ramp_op_scene_attention(const float* qkv, float* o, int32_t T, int32_t heads, int32_t dh, float scale, void* stream) {
+  RAMP_REQUIRE(qkv && o, "ramp_op_scene_attention: null argument");
+  RAMP_REQUIRE(T > 0 && heads > 0, "ramp_op_scene_attention: T and heads must be positive");
+  RAMP_REQUIRE(dh == 16 || dh == 64, "ramp_op_scene_attention: dh must be 16 or 64");
+  return scene_attention(qkv, o, T, heads, dh, scale, as_stream(stream));
+}
+int ramp_op_scene_attention_seg(const float* qkv, float* o, const int32_t* tiles, int32_t n_tiles, int32_t heads, int32_t dh, float scale,
+                                void* stream) {
+  RAMP_REQUIRE(qkv && o && tiles, "ramp_op_scene_attention_seg: null argument");
+  RAMP_REQUIRE(n_tiles > 0 && heads > 0, "ramp_op_scene_attention_seg: n_tiles and heads must be positive");
+  RAMP_REQUIRE(dh == 16 || dh == 64, "ramp_op_scene_attention_seg: dh must be 16 or 64");
+  return scene_attention_seg(qkv, o, tiles, n_tiles, heads, dh, scale, as_stream(stream));
+}
+int ramp_op_scene_colreduce(const float* x, float* out, int32_t n_seg, int32_t seglen, int32_t C, int32_t mode, void* stream) {
+  RAMP_REQUIRE(x && out, "ramp_op_scene_colreduce: null argument");
+  RAMP_REQUIRE(n_seg > 0 && seglen > 0 && C > 0, "ramp_op_scene_colreduce: n_seg, seglen and C must be positive");
+  RAMP_REQUIRE(mode == 0 || mode == 1, "ramp_op_scene_colreduce: mode must be 0 (mean) or 1 (max)");
+  return scene_colreduce(x, out, n_seg, seglen, C, mode, as_stream(stream));
+}
+int ramp_op_scene_colreduce_seg(const float* x, float* out, const int32_t* first, int32_t n_seg, int32_t C, int32_t ldo, int32_t mode,
+                                void* stream) {
+  RAMP_REQUIRE(x && out && first, "ramp_op_scene_colreduce_seg: null argument");
+  RAMP_REQUIRE(n_seg > 0 && C > 0 && ldo >= C, "ramp_op_scene_colreduce_seg: n_seg and C must be positive, ldo at least C");
+  RAMP_REQUIRE(mode == 0 || mode == 1, "ramp_op_scene_colreduce_seg: mode must be 0 (mean) or 1 (max)");
+  return scene_colreduce_seg(x, out, first, n_seg, C, ldo, mode, as_stream(stream));
+}
+int ramp_op_scene_enc2d_prep(const float* cloud, int32_t No, int32_t Np, float* centers, float* maxd, void* stream) {
+  RAMP_REQUIRE(cloud && centers && maxd, "ramp_op_scene_enc2d_prep: null argument");
+  RAMP_REQUIRE(No > 0 && Np > 0, "ramp_op_scene_enc2d_prep: No and Np must be positive");
+  return scene_enc2d_prep(cloud, No, Np, centers, maxd, as_stream(stream));
+}
+int ramp_op_scene_enc2d_prep_seg(const float* cloud, const int32_t* obstacle_first, int32_t No, float* centers, float* maxd, void* stream) {
+  RAMP_REQUIRE(cloud && obstacle_first && centers && maxd, "ramp_op_scene_enc2d_prep_seg: null argument");
+  RAMP_REQUIRE(No > 0, "ramp_op_scene_enc2d_prep_seg: No must be positive");
+  return scene_enc2d_prep_seg(cloud, obstacle_first, No, centers, maxd, as_stream(stream));
+}
+
 
 }  // extern "C"
