@@ -21,7 +21,8 @@ TOOLS_SOURCES = ["bench.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-DRAMP_DEFAULT_GEMM_MODE=2"]
 # sampler.hip mirrors the reference's elementwise fp32 expressions rounding for rounding: hipcc's default
 # -ffp-contract=fast would fuse a*b - c*d into an FMA (HIP's __fmul_rn is a plain multiply), so it is off there.
-# guide.hip, guide_replan.hip and guide_prims.hip (the cost guides' kernels) state their fp32 arithmetic the same way and are built under the same flag.
+# guide.hip, guide_replan.hip and guide_prims.hip (the cost guides' kernels) state their fp32 arithmetic the same way and are built under the same
+# flag; so must be every file that includes guide_core.h, the device code the three share.
 # resample.hip (the resampling kernels) states its fp64 weight arithmetic the same way.
 # clearance.hip (swept collision checks) repeats traj_costs_block's path-length arithmetic bit for bit and is built under the same flag.
 # stitch.hip (stitched windows) states its blend l + alpha (q - l) the same way.

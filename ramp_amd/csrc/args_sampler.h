@@ -84,10 +84,12 @@ struct ApfArgs {
   int n_scenes = 0;
 };
 int launch_apf(const ApfArgs& a, hipStream_t s);
-// ---- cost-gradient guidance (guide.hip; ramp_cost_guide in ramp_hip.h) -----------------------------
+// ---- cost-gradient guidance (guide.hip, device code shared with the two families below in guide_core.h; ramp_cost_guide in ramp_hip.h) ----
+constexpr int GUIDE_TILE = 1024;    // points of a cloud tile in LDS; also the most points of a moving cloud
+constexpr int GUIDE_MAX_H = 128;    // the longest horizon the guide kernels serve
 struct GuideArgs {
   float* traj = nullptr;            // (B,H,S): channels [0, D) of the free waypoints are updated in place (the cost kernel only reads)
-  int B = 0, H = 0, S = 0, D = 2;   // D = point_dim, 2 or 3, <= S; H <= 128
+  int B = 0, H = 0, S = 0, D = 2;   // D = point_dim, 2 or 3, <= S; H <= GUIDE_MAX_H
   const float* cloud = nullptr;     // (P_total, D): the scenes' clouds, concatenated
   const int* cloud_off = nullptr;   // device (n_scenes + 1): first point of each scene's cloud (an empty span is allowed; spans are clamped to P_total)
   const int* scene = nullptr;       // (B) scene of each trajectory, or null = scene 0 for all; an index outside the table leaves the trajectory alone
@@ -100,7 +102,7 @@ struct GuideArgs {
 int launch_guide_step(const GuideArgs& a, hipStream_t s);
 // terms (B, 3) doubles = {C_obs, C_smooth, C_acc} unweighted (NaN for a trajectory whose scene index is outside the table)
 int launch_guide_cost(const GuideArgs& a, double* terms, hipStream_t s);
-// ---- swept box and sphere terms of the cost guide (guide_prims.hip; ramp_prim_guide in ramp_hip.h) ---------------
+// ---- swept box and sphere terms of the cost guide (guide_prims.hip + guide_core.h; ramp_prim_guide in ramp_hip.h) ---------------
 // GuideArgs plus the scenes' boxes and spheres: C_prim over n_sub samples per segment, handed back to the segment's two waypoints.  The scene
 // of a trajectory is g.scene's; the spans of both tables are clamped to their totals
 struct PrimGuideArgs {
@@ -179,15 +181,15 @@ int launch_episode_cost_segments(float* dst, const float* cloud, const float* ex
 // and in both cases the episode's `best` block stays as it is
 int launch_select_episodes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                            const int* traj_first, EpisodeTable ep, float* best, int* result, int B, int H, int S, hipStream_t s);
-// ---- the cost guide of the replanning jobs (guide_replan.hip; ramp_replan_guide in ramp_hip.h) -------------------
-// The static term of GuideArgs (2-D) plus a moving cloud of n_mov <= 1024 points per scene displaced by a per-waypoint track, and pins that
+// ---- the cost guide of the replanning jobs (guide_replan.hip + guide_core.h; ramp_replan_guide in ramp_hip.h) -------------------
+// The static term of GuideArgs (2-D) plus a moving cloud of n_mov <= GUIDE_TILE points per scene displaced by a per-waypoint track, and pins that
 // differ from row to row: waypoints < n_first(b), waypoint H - 1 and the hard-conditioned ones.  n_first(b) = pin_first[b], or the n_hist of
 // the row's episode record (est, with its `active` switch: a row of an ended episode is left alone) or of the single replan's record (rst).
 // The working copy's pinned values: the hard condition's (later entries win), then -- only with hist / x_clean, the replans' buffers
 // (n_scenes, H, S) -- the history rows and the clean plan's goal, replan_pin_row's order; a pinned waypoint nothing names keeps the array's own
 struct MovingGuideArgs {
   float* traj = nullptr;            // (B,H,S): channels 0:2 of the free waypoints are updated in place (the cost kernel only reads)
-  int B = 0, H = 0, S = 0;          // H <= 128, S >= 2
+  int B = 0, H = 0, S = 0;          // H <= GUIDE_MAX_H, S >= 2
   const float* cloud = nullptr;     // (P_total, 2): the scenes' static clouds, concatenated
   const int* cloud_off = nullptr;   // device (n_scenes + 1); an empty span is allowed, spans are clamped to P_total
   const float* mov = nullptr;       // device (n_scenes, n_mov, 2): every scene's moving cloud now

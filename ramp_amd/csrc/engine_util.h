@@ -139,7 +139,7 @@ int check_prim_guide(const ramp_prim_guide* pg, const ramp_cost_guide* cg, int H
   RAMP_REQUIRE((pg->point_dim == 2 || pg->point_dim == 3) && pg->point_dim <= S, w + "the primitives' point_dim must be 2 or 3 and at most state_dim");
   RAMP_REQUIRE(pg->point_dim == cg->point_dim, w + "the primitives' point_dim differs from the cost guide's");
   RAMP_REQUIRE(pg->n_sub >= 1 && pg->n_sub <= RAMP_PRIM_GUIDE_MAX_SUB, w + "n_sub outside 1 .. RAMP_PRIM_GUIDE_MAX_SUB");
-  RAMP_REQUIRE(H <= 128, w + "the primitive guide kernel serves horizons up to 128");
+  RAMP_REQUIRE(H <= GUIDE_MAX_H, w + "the primitive guide kernel serves horizons up to 128");
   RAMP_REQUIRE(std::isfinite(pg->margin) && pg->margin >= 0.0 && std::isfinite(pg->band) && pg->band >= 0.0,
                w + "margin and band must be finite and not negative");
   RAMP_REQUIRE(std::isfinite(pg->w_prim), w + "w_prim must be finite");
@@ -200,9 +200,9 @@ StitchArgs stitch_args(const ramp_stitch* st, int B, int H, int S) {
 int check_replan_guide(const ramp_replan_guide* rg, int n_scenes, int H, int S, int n_steps, const char* who, int* total = nullptr) {
   const std::string w = std::string(who) + ": ";
   RAMP_REQUIRE(rg, w + "null replan guide");
-  RAMP_REQUIRE(H <= 128, w + "the guide kernel serves horizons up to 128");
+  RAMP_REQUIRE(H <= GUIDE_MAX_H, w + "the guide kernel serves horizons up to 128");
   RAMP_REQUIRE(S >= 2, w + "state_dim must be at least 2");
-  RAMP_REQUIRE(rg->n_mov >= 0 && rg->n_mov <= 1024, w + "n_mov outside 0 .. 1024");
+  RAMP_REQUIRE(rg->n_mov >= 0 && rg->n_mov <= GUIDE_TILE, w + "n_mov outside 0 .. 1024");
   RAMP_REQUIRE(rg->n_scenes >= 1 && (n_scenes <= 0 || rg->n_scenes == n_scenes), w + "the guide's n_scenes must be 1 for one episode and the episode count for many");
   RAMP_REQUIRE(std::isfinite(rg->radius) && std::isfinite(rg->radius_mov) && std::isfinite(rg->w_obs) && std::isfinite(rg->w_mov) &&
                std::isfinite(rg->w_smooth) && std::isfinite(rg->w_acc) && std::isfinite(rg->max_norm),

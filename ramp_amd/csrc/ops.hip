@@ -171,7 +171,7 @@ static int guide_op(GuideArgs a, const ramp_cost_guide* cg, const int32_t* traj_
 int ramp_guide_step(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene, int32_t n_iter,
                     float step, int32_t n_hard, const int32_t* hard_idx_host, const float* hard_val, void* stream) {
   RAMP_REQUIRE(traj && cg, "ramp_guide_step: null argument");
-  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_step: bad dims (H up to 128)");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_step: bad dims (H up to 128)");
   CK(check_cost_guide(cg, S, "ramp_guide_step"));
   RAMP_REQUIRE(n_iter >= 0 && n_iter <= RAMP_GUIDE_MAX_STEPS, "ramp_guide_step: n_iter outside 0 .. RAMP_GUIDE_MAX_STEPS");
   RAMP_REQUIRE(std::isfinite(step), "ramp_guide_step: step must be finite");
@@ -186,7 +186,7 @@ int ramp_guide_step(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cos
 int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const int32_t* traj_scene,
                     double* terms_out, void* stream) {
   RAMP_REQUIRE(traj && cg && terms_out, "ramp_guide_cost: null argument");
-  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_cost: bad dims (H up to 128)");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_cost: bad dims (H up to 128)");
   CK(check_cost_guide(cg, S, "ramp_guide_cost"));
   return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
 }
@@ -219,7 +219,7 @@ int ramp_guide_step_prims(float* traj, int32_t B, int32_t H, int32_t S, const ra
                           const int32_t* traj_scene, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
                           const float* hard_val, void* stream) {
   RAMP_REQUIRE(traj && cg, "ramp_guide_step_prims: null argument");
-  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_step_prims: bad dims (H up to 128)");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_step_prims: bad dims (H up to 128)");
   CK(check_cost_guide(cg, S, "ramp_guide_step_prims"));
   if (pg) CK(check_prim_guide(pg, cg, H, S, "ramp_guide_step_prims"));
   RAMP_REQUIRE(n_iter >= 0 && n_iter <= RAMP_GUIDE_MAX_STEPS, "ramp_guide_step_prims: n_iter outside 0 .. RAMP_GUIDE_MAX_STEPS");
@@ -236,7 +236,7 @@ int ramp_guide_step_prims(float* traj, int32_t B, int32_t H, int32_t S, const ra
 int ramp_guide_cost_prims(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
                           const int32_t* traj_scene, double* terms_out, void* stream) {
   RAMP_REQUIRE(traj && cg && terms_out, "ramp_guide_cost_prims: null argument");
-  RAMP_REQUIRE(B > 0 && H > 0 && H <= 128 && S > 0, "ramp_guide_cost_prims: bad dims (H up to 128)");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_cost_prims: bad dims (H up to 128)");
   CK(check_cost_guide(cg, S, "ramp_guide_cost_prims"));
   if (pg) CK(check_prim_guide(pg, cg, H, S, "ramp_guide_cost_prims"));
   GuideArgs a = guide_args(cg, const_cast<float*>(traj), B, H, S);

@@ -21,7 +21,7 @@ from util import NoiseInjector, dev
 
 pytestmark = pytest.mark.gpu
 
-TILE = 1024      # GUIDE_TILE of ramp_amd/csrc/guide.hip
+TILE = 1024      # GUIDE_TILE of ramp_amd/csrc/args_sampler.h
 F32 = lambda v: float(np.float32(v))      # noqa: E731
 RADIUS = F32(0.35)
 

@@ -139,6 +139,57 @@ def test_kernel_against_float64(case):
         assert np.isfinite(run_moving(c["x"], clouds, mov, c["track"], TS, c["pf"], c["hard"], c["sc"], STEP, n_iter)).all()
 
 
+# ------------------------------------------------------------------------------------------------ 1b: without a moving term
+def run_static(x, clouds, ts, hard, sc, step, n_iter):
+    """ramp_guide_step (the sampling jobs' kernel) on a copy of x, with run_moving's table of hard conditions."""
+    from ramp_amd.guide import fill_cost_guide
+    pts, off, d = cloud_table([torch.from_numpy(np.ascontiguousarray(c, np.float32)) for c in clouds], "cuda")
+    cg = fill_cost_guide(pts, off, d, sc)
+    xx = dev(np.ascontiguousarray(x, np.float32)).clone()
+    B, H, S = xx.shape
+    idx = (C.c_int32 * len(hard))(*[int(h) for h, _ in hard])
+    val = dev(np.stack([np.asarray(v, np.float32) for _, v in hard]))
+    _lib.check(_lib.load().ramp_guide_step(_lib.ptr(xx), B, H, S, C.byref(cg), _lib.ptr(dev(np.asarray(ts, np.int32))), n_iter, step, len(hard),
+                                           C.cast(idx, _lib.c_i32p), _lib.ptr(val), _lib.current_stream()), "ramp_guide_step")
+    torch.cuda.synchronize()
+    return xx.cpu().numpy()
+
+
+# (H, static P of the 3 scenes, pin_first of every row, n_iter): stencils at both ends, an empty cloud and a part tile; reload across tiles
+# and a tile edge; every thread of the stencil pass busy and an exactly full tile
+STATIC_CASES = [(5, (0, 1, 1023), 1, 16), (48, (1025, 2049, 0), 4, 3), (128, (1024, 1, 1025), 1, 1)]
+
+
+@pytest.mark.parametrize("case", STATIC_CASES, ids=lambda c: "H%d_P%s_k%d_it%d" % (c[0], "-".join(map(str, c[1])), c[2], c[3]))
+def test_without_a_moving_term_it_is_the_cost_guide_bit_for_bit(case):
+    """ramp_guide_step_moving with n_mov = 0 and pin_first = k for every row against ramp_guide_step on the same rows, whose hard conditions
+    name waypoints 0 .. k - 1 and H - 1 with the rows' own values in front of the doubled condition on H // 2: the same pins, the same pinned
+    values and the same gradient sum, so the outputs are equal as uint32.  The rows, their scenes (scene 2 has none) and the choice of
+    max_norm are kernel_case's: some rows are clipped on the first iteration and others are not (asserted from the float64 log)."""
+    H, Ps, k, n_iter = case
+    seed = 3100 + STATIC_CASES.index(case)
+    x = uniform((13, H, 4), seed)
+    clouds = [uniform((P, 2), seed + 10 + i) for i, P in enumerate(Ps)]
+    mov, track = np.zeros((3, 0, 2), np.float32), np.zeros((3, H, 2), np.float32)
+    pf = np.full(13, k, np.int32)
+    doubled = [(H // 2, uniform((13, 4), seed + 40)), (H // 2, uniform((13, 4), seed + 41))]
+    log0 = []
+    restate(x, clouds, mov, track, TS, pf, doubled, SC, STEP, 1, np.float64, log=log0)
+    norms = [n for _, _, _, n in log0 if n > 0]
+    sc = dict(SC, max_norm=F32(np.sqrt(min(norms) * max(norms))))
+    log = []
+    restate(x, clouds, mov, track, TS, pf, doubled, sc, STEP, 1, np.float64, log=log)
+    s_first = [s for b, it, s, n in log if it == 0 and n > 0]
+    assert min(s_first) < 1.0 and max(s_first) == 1.0, s_first
+    moving = run_moving(x, clouds, mov, track, TS, pf, doubled, sc, STEP, n_iter)
+    named = [(h, x[:, h]) for h in list(range(k)) + [H - 1]]
+    static = run_static(x, clouds, TS, named + doubled, sc, STEP, n_iter)
+    n_moved = int((bits(moving)[:, :, :2] != bits(x)[:, :, :2]).any(axis=(1, 2)).sum())
+    print(f"no moving term {case}: {n_moved} of 13 rows moved, max_norm {sc['max_norm']:.3e}")
+    assert n_moved >= 5
+    assert np.array_equal(bits(moving), bits(static))
+
+
 # ------------------------------------------------------------------------------------------------ 2: the track
 def test_the_track_is_read_per_episode_and_per_waypoint():
     """w_obs = w_smooth = w_acc = 0, 13 rows along the x axis (y = 0.02 b), a 16-point moving cluster at (10, 10) in both scenes and a track
