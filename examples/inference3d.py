@@ -144,7 +144,13 @@ def main(argv=None):
     ap.add_argument("--guide-obstacles", action="store_true",
                     help="guide the samples away from the experiment's boxes and spheres inside the job: the swept primitive term of cost_guide= "
                          "(segments included, the margin --evaluate uses)")
+    ap.add_argument("--alternatives", type=int, default=0, metavar="K",
+                    help="with --evaluate: K free plans that are pairwise at least --min-sep apart, cheapest first, and how many free samples "
+                         "are nearest to each (select_diverse_clear_scenes)")
+    ap.add_argument("--min-sep", type=float, default=0.1, help="mean waypoint distance two of the --alternatives keep from each other")
     args = ap.parse_args(argv)
+    if args.alternatives and not args.evaluate:
+        ap.error("--alternatives goes with --evaluate")
     cfg = Config3d(); cfg.n_samples, cfg.n_diffusion_steps, cfg.model_id, cfg.seed = args.n_samples, args.n_diffusion_steps, args.model_id, args.seed
     cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
     if args.make_synthetic:
@@ -188,7 +194,7 @@ def main(argv=None):
            "start_error": float((pos_final[:, 0] - start_state_pos).abs().max()), "goal_error": float((pos_final[:, -1] - goal_state_pos).abs().max())}
     print(json.dumps(out))
     if args.evaluate:
-        out["evaluation"] = evaluate(trajs_iters[-1], data)
+        out["evaluation"] = evaluate(trajs_iters[-1], data, alternatives=args.alternatives, min_sep=args.min_sep)
         print(json.dumps({"evaluation": out["evaluation"]}))
     return out, trajs_normalized_iters
 
@@ -214,10 +220,11 @@ def obstacle_guide(data, normalizer, margin: float = EVAL_MARGIN, band: float = 
                 n_sub=n_sub, t_start=t_start)
 
 
-def evaluate(trajs_final, data, threshold: float = 0.01):
+def evaluate(trajs_final, data, threshold: float = 0.01, alternatives: int = 0, min_sep: float = 0.1):
     """What the reference's script leaves out: are the sampled trajectories free of the experiment's boxes and spheres -- at the
-    waypoints and on the segments between them -- and which free one to execute."""
-    from ramp_amd.cost import select_best_clear_scenes
+    waypoints and on the segments between them -- and which free one to execute.  ``alternatives`` = K > 0 adds the rows of K free plans
+    that are pairwise at least ``min_sep`` apart (the first is ``best_row``) and the number of free samples nearest to each."""
+    from ramp_amd.cost import select_best_clear_scenes, select_diverse_clear_scenes
     from ramp_amd.metrics import Metrics3d
     boxes = (torch.as_tensor(data["box_centers"]), torch.as_tensor(data["box_sizes"]))
     spheres = (torch.as_tensor(data["sphere_centers"]), torch.as_tensor(data["sphere_radii"]))
@@ -226,9 +233,15 @@ def evaluate(trajs_final, data, threshold: float = 0.01):
     _, n_free, _, best_row, _ = select_best_clear_scenes(trajs_final, [n], boxes=boxes, spheres=spheres, point_dim=3, swept=True,
                                                          intensity_threshold=threshold)
     m = per_scene[0]
-    return {"success": m["success"], "collision_intensity": m["collision_intensity"],
-            "swept_collision_intensity": m["swept_collision_intensity"], "n_free_trajectories": m["n_free_trajectories"],
-            "path_length": m["path_length"], "best_row": int(best_row[0]), "n_free_selected": int(n_free[0])}
+    ev = {"success": m["success"], "collision_intensity": m["collision_intensity"],
+          "swept_collision_intensity": m["swept_collision_intensity"], "n_free_trajectories": m["n_free_trajectories"],
+          "path_length": m["path_length"], "best_row": int(best_row[0]), "n_free_selected": int(n_free[0])}
+    if alternatives:
+        sel = select_diverse_clear_scenes(trajs_final, [n], boxes=boxes, spheres=spheres, k=alternatives, min_sep=min_sep, point_dim=3,
+                                          swept=True, intensity_threshold=threshold)
+        ev["alternative_rows"] = sel.rows[0].tolist()
+        ev["mode_count"] = sel.mode_count[0].tolist()
+    return ev
 
 
 if __name__ == "__main__":

@@ -70,6 +70,8 @@ class StaticConfig:
     start_guide_steps_fraction = 0.07
     n_diffusion_steps_without_noise = 5
     sampler = None           # None = the reference's hard-coded default (DDIM-5); 'ddpm' for the full chain
+    alternatives = 0         # not the reference's: K > 0 stores K distinct plans per experiment next to best_trajectory (--all-envs)
+    min_sep = 0.1            # the mean waypoint distance two of them keep from each other
 
 
 def make_synthetic_experiment(root: str, cfg: StaticConfig, n_obstacles: int = 6, n_points: int = 64, seed: int = 42) -> None:
@@ -197,8 +199,15 @@ class StaticInference:
         out, free_mask = self.metrics_calculator.evaluate_scenes(trajs, counts, [d['box_centers'] for d in datas],
                                                                  [d['box_sizes'] for d in datas])
         best = cost.compute_trajectory_costs_scenes(trajs, counts, [d['obstacle_points'] for d in datas])[0]
+        alt = None
+        if cfg.alternatives:                    # K plans per experiment that keep min_sep from each other, cheapest first
+            alt = cost.select_diverse_clear_scenes(trajs, counts, clouds=[d['obstacle_points'] for d in datas], k=cfg.alternatives,
+                                                   min_sep=cfg.min_sep, point_dim=2, swept=False)
         for i, m in enumerate(out):                            # m['free_trajectories'] is gathered when read (SceneMetrics)
             m['best_trajectory'] = best[i]
+            if alt is not None:
+                m['alternative_trajectories'], m['alternative_rows'], m['mode_count'] = alt.best[i], alt.rows[i], alt.mode_count[i]
+                m['n_alternatives'] = int(alt.n_selected[i])
             m['env'], m['total_time_all_envs'] = int(dirs[i]), elapsed
         self.last_trajectories = trajs
         return out
@@ -218,8 +227,14 @@ def main(argv=None):
     ap.add_argument("--n-steps-without-noise", type=int, default=StaticConfig.n_diffusion_steps_without_noise)
     ap.add_argument("--unet-input-dim", type=int, choices=[16, 32, 64], default=StaticConfig.unet_input_dim)
     ap.add_argument("--unet-dim-mults-option", type=int, choices=sorted(UNET_DIM_MULTS), default=StaticConfig.unet_dim_mults_option)
+    ap.add_argument("--alternatives", type=int, default=0, metavar="K",
+                    help="with --all-envs: K plans per experiment that are pairwise at least --min-sep apart, next to best_trajectory")
+    ap.add_argument("--min-sep", type=float, default=0.1, help="mean waypoint distance two of the --alternatives keep from each other")
     args = ap.parse_args(argv)
+    if args.alternatives and not args.all_envs:
+        ap.error("--alternatives goes with --all-envs")
     cfg = StaticConfig()
+    cfg.alternatives, cfg.min_sep = args.alternatives, args.min_sep
     cfg.n_samples, cfg.n_diffusion_steps, cfg.sampler, cfg.use_apf = args.n_samples, args.n_diffusion_steps, args.sampler, args.use_apf
     cfg.dataset_subdir, cfg.model_id = args.dataset_subdir, args.model_id
     cfg.n_diffusion_steps_without_noise = args.n_steps_without_noise

@@ -826,6 +826,36 @@ int ramp_select_scored_scenes(const float* traj, int32_t B, int32_t H, int32_t S
                               const int32_t* mask, const float* path_len, const float* smooth, float w_smooth, float w_len,
                               float* best_out, int32_t* result_dev, void* stream);
 
+/* ---- K distinct plans per scene: the K cheapest collision-free trajectories that are pairwise at least min_sep apart, and the mode
+ * (the nearest of them) of every other free row.  Per scene s over its rows [traj_first[s], traj_first[s + 1]); traj_first device
+ * (n_scenes + 1), non-decreasing (an empty scene is allowed), spans clamped to [0, B].  Free rows: mask[b] == 0.
+ * Order.  That of ramp_select_scored_scenes: tot = w_smooth sm + w_len pl on path_len and smooth min-max normalised over the scene's free
+ *   rows, fp32 with one rounding per operation.  Row a comes before row b if tot_a is NaN and (tot_b is not NaN or a < b), or if neither
+ *   is NaN and (tot_a < tot_b, or tot_a == tot_b and a < b).  A scene whose free rows all tie (0 / 0) is therefore ordered by row.
+ * Distance.  D = point_dim (2 or 3, <= S), p_{b,h} = traj[b, h, 0:D].  metric 0: d = (1 / H) sum_h |p_{a,h} - p_{b,h}|; metric 1:
+ *   d = max_h |p_{a,h} - p_{b,h}|.  Per waypoint the differences, the squares (added in coordinate order) and the root are fp32; metric 0 adds
+ *   the norms in fp64 in ascending h, divides by H in fp64 and rounds to fp32 once; metric 1 is NaN as soon as one norm is.  The value of
+ *   a pair depends on the two rows alone.
+ * Selection.  rep_0 = the first free row in the order; rep_k = the first free row in the order with d(b, rep_j) >= min_sep for every j < k:
+ *   a row with d < min_sep, or a NaN d, to an earlier representative is suppressed.  It stops at K representatives or when no row is left;
+ *   min_sep = 0 returns the K first rows of the order (NaN distances aside), and slot 0 is always the row ramp_select_scored_scenes picks.
+ * Modes.  Every free row belongs to the slot j with the smallest d(b, rep_j), the lowest j on a tie; a NaN distance never wins; a
+ *   representative belongs to its own slot.  Colliding rows, rows of no scene and free rows whose every distance is NaN get -1.
+ * Outputs (all device, all required): best_out (n_scenes, K, H, S) the representatives unmodified, NaN in the slots nothing fills;
+ *   rows_out (n_scenes, K) their rows in the whole batch, -1 padded; result_dev (n_scenes, 4) = {n_free, n_selected, rows_out[s][0], 0};
+ *   mode_of (B) the slot of every row; sep_out (B) its distance to that slot's representative, NaN where mode_of is -1;
+ *   mode_count (n_scenes, K) rows per slot.
+ * scratch: device, 2 * B + n_scenes 32-bit words (row states, totals, the passes' picks); nothing is allocated inside the call.
+ * 2 K + 1 launches whatever n_scenes, B and the data; asynchronous on `stream`, capturable, no copies, no host reads, no float atomics; a
+ * scene's outputs depend on that scene's rows alone.  Refused on the host before any launch (non-zero, "ramp_select_diverse_scenes" in
+ * ramp_last_error): K outside 1 .. RAMP_DIVERSE_MAX_K, min_sep negative or NaN, metric outside {0, 1}, point_dim outside {2, 3} or > S,
+ * H outside 1 .. 128, B < 0, n_scenes < 1, a NULL pointer (stream aside). */
+#define RAMP_DIVERSE_MAX_K 16
+int ramp_select_diverse_scenes(const float* traj, int32_t B, int32_t H, int32_t S, int32_t point_dim, const int32_t* traj_first,
+                               int32_t n_scenes, const int32_t* mask, const float* path_len, const float* smooth, float w_smooth,
+                               float w_len, int32_t K, float min_sep, int32_t metric, float* best_out, int32_t* rows_out,
+                               int32_t* result_dev, int32_t* mode_of, float* sep_out, int32_t* mode_count, void* scratch, void* stream);
+
 /* ---- swept collision checks and clearances, 2-D and 3-D ----
  * Position p_h of waypoint h = the first D = point_dim (2 or 3, <= S) entries of the state; margin >= 0 is the robot's radius.  Every
  * trajectory meets only the primitives of its own scene (traj_first as above; the three offset tables may repeat a value: a scene may lack

@@ -275,6 +275,9 @@ PROTOTYPES = {
                                         C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ramp_select_scored_scenes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ramp_select_diverse_scenes": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_int32] +
+                                   [C.c_void_p] * 8),
     "ramp_traj_clearance": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampObstacles), C.c_void_p, C.c_int32] +
                             [C.c_void_p] * 7),
     "ramp_cfg_mean": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double,

@@ -45,8 +45,9 @@ class Clearance:
     distance of the waypoints / segments to the nearest cloud point (+inf without a cloud), ``path_length``, ``smoothness``;
     ``seg_hits`` and ``swept_clearance`` are None when the call skipped the segment work (``swept=False``)."""
 
-    def __init__(self, H, wp_hits, seg_hits, clearance, swept_clearance, path_length, smoothness, traj_first=None):
+    def __init__(self, H, wp_hits, seg_hits, clearance, swept_clearance, path_length, smoothness, traj_first=None, point_dim=None):
         self.H, self.wp_hits, self.seg_hits = H, wp_hits, seg_hits
+        self.point_dim = point_dim                            # the position entries the call used (2 or 3)
         self.traj_first = traj_first                          # device int32 (n_scenes + 1): first row of each scene
         self.clearance, self.swept_clearance, self.path_length, self.smoothness = clearance, swept_clearance, path_length, smoothness
 
@@ -170,4 +171,4 @@ def trajectory_clearance(trajs, boxes=None, spheres=None, clouds=None, counts=No
             _lib.ptr(t), B, H, S, C.byref(ob), tables.data_ptr(), 1 if swept else 0, hits[0].data_ptr(),
             hits[1].data_ptr() if swept else None, vals[0].data_ptr(), vals[1].data_ptr() if swept else None, vals[2].data_ptr(),
             vals[3].data_ptr(), _lib.current_stream()), "ramp_traj_clearance")
-    return Clearance(H, hits[0], hits[1] if swept else None, vals[0], vals[1] if swept else None, vals[2], vals[3], tables[:n1])
+    return Clearance(H, hits[0], hits[1] if swept else None, vals[0], vals[1] if swept else None, vals[2], vals[3], tables[:n1], D)

@@ -214,6 +214,25 @@ int launch_replan_select(const float* traj, const int* mask, const float* plen, 
 // batch, best (n_scenes, H, S) the winner unmodified; a scene without a free row gets {0, -1, -1, 0} and a NaN block
 int launch_select_scenes(const float* traj, const int* mask, const float* plen, const float* smooth, float w_s, float w_l,
                          const int* traj_first, int n_scenes, float* best, int* result, int B, int H, int S, hipStream_t s);
+// ---- K distinct plans per scene (sampler.hip; ramp_select_diverse_scenes in ramp_hip.h states the definition) --------------------------
+constexpr int DIVERSE_MAX_K = 16;
+struct DiverseArgs {
+  const float* traj = nullptr;      // (B,H,S)
+  int B = 0, H = 0, S = 0, D = 2;   // D = point_dim, 2 or 3, <= S; 1 <= H <= 128
+  const int* traj_first = nullptr;  // device (n_scenes + 1), non-decreasing; spans are clamped to [0, B], an empty span is allowed
+  int n_scenes = 1;
+  const int* mask = nullptr; const float* plen = nullptr; const float* smooth = nullptr;   // (B) each; mask 1 = colliding
+  float w_s = 0, w_l = 0;
+  int K = 1; float min_sep = 0; int metric = 0;   // 1 <= K <= DIVERSE_MAX_K; metric 0 = mean, 1 = maximum waypoint distance
+  float* best = nullptr;            // (n_scenes, K, H, S), NaN in the slots nothing fills
+  int* rows = nullptr;              // (n_scenes, K) rows in the whole batch, -1 padded
+  int* result = nullptr;            // (n_scenes, 4) = {n_free, n_selected, rows[s][0], 0}
+  int* mode_of = nullptr; float* sep = nullptr;   // (B): every row's slot and its distance to that representative (-1 / NaN); the passes' working arrays
+  int* mode_count = nullptr;        // (n_scenes, K)
+  int* state = nullptr; float* tot = nullptr; int* pick = nullptr;   // scratch: (B) row states, (B) totals of the free rows, (n_scenes) the pass's pick
+};
+// 2 K + 1 launches: K x (pick per scene, update per row), then the counts; nothing is allocated, copied or read back
+int launch_select_diverse(const DiverseArgs& a, hipStream_t s);
 // mask[b] = any_{h,p} ||xy - p|| < thr ; plen[b], smooth[b]
 int launch_traj_costs(const float* traj, const float* cloud, int B, int H, int S, int P, float thr,
                       int* mask, float* plen, float* smooth, hipStream_t s);

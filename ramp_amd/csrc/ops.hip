@@ -474,6 +474,30 @@ int ramp_select_scored_scenes(const float* traj, int32_t B, int32_t H, int32_t S
   return launch_select_scenes(traj, mask, path_len, smooth, w_smooth, w_len, traj_first, n_scenes, best_out, result_dev, B, H, S,
                               as_stream(stream));
 }
+static_assert(RAMP_DIVERSE_MAX_K == DIVERSE_MAX_K, "ramp_hip.h and args_sampler.h state the same K limit");
+// every refusal of ramp_select_diverse_scenes is made here, on the host, before anything is launched
+int ramp_select_diverse_scenes(const float* traj, int32_t B, int32_t H, int32_t S, int32_t point_dim, const int32_t* traj_first,
+                               int32_t n_scenes, const int32_t* mask, const float* path_len, const float* smooth, float w_smooth,
+                               float w_len, int32_t K, float min_sep, int32_t metric, float* best_out, int32_t* rows_out,
+                               int32_t* result_dev, int32_t* mode_of, float* sep_out, int32_t* mode_count, void* scratch, void* stream) {
+  const std::string w = "ramp_select_diverse_scenes: ";
+  RAMP_REQUIRE(traj && mask && path_len && smooth, w + "null trajectories, mask, path_len or smooth");
+  RAMP_REQUIRE(traj_first, w + "null scene table");
+  RAMP_REQUIRE(best_out && rows_out && result_dev && mode_of && sep_out && mode_count, w + "null output");
+  RAMP_REQUIRE(scratch, w + "null scratch");
+  RAMP_REQUIRE(B >= 0 && n_scenes >= 1, w + "B must not be negative and n_scenes must be at least 1");
+  RAMP_REQUIRE(H >= 1 && H <= 128, w + "the horizon must be 1 .. 128");
+  RAMP_REQUIRE((point_dim == 2 || point_dim == 3) && point_dim <= S, w + "point_dim must be 2 or 3 and at most S");
+  RAMP_REQUIRE(K >= 1 && K <= RAMP_DIVERSE_MAX_K, w + "K must be 1 .. RAMP_DIVERSE_MAX_K");
+  RAMP_REQUIRE(min_sep >= 0.f, w + "min_sep must not be negative or NaN");
+  RAMP_REQUIRE(metric == 0 || metric == 1, w + "metric must be 0 (mean) or 1 (maximum)");
+  DiverseArgs a;
+  a.traj = traj; a.B = B; a.H = H; a.S = S; a.D = point_dim; a.traj_first = traj_first; a.n_scenes = n_scenes;
+  a.mask = mask; a.plen = path_len; a.smooth = smooth; a.w_s = w_smooth; a.w_l = w_len; a.K = K; a.min_sep = min_sep; a.metric = metric;
+  a.best = best_out; a.rows = rows_out; a.result = result_dev; a.mode_of = mode_of; a.sep = sep_out; a.mode_count = mode_count;
+  a.state = static_cast<int*>(scratch); a.tot = reinterpret_cast<float*>(a.state + B); a.pick = a.state + 2 * (size_t)B;
+  return launch_select_diverse(a, as_stream(stream));
+}
 // every refusal of ramp_traj_clearance is made here, on the host, before anything is launched
 int ramp_traj_clearance(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_obstacles* ob, const int32_t* traj_first,
                         int32_t swept, int32_t* wp_hits, int32_t* seg_hits, float* clear_wp, float* clear_seg, float* path_len,

@@ -423,20 +423,14 @@ __global__ __launch_bounds__(256) void replan_goal_kernel(float* __restrict__ x0
   const int b = idx / S, si = idx - b * S;
   x0[((long)b * H + H - 1) * S + si] = x[((long)b * H + H - 1) * S + si];
 }
-// compute_trajectory_costs (cost.py:56-88) over the B per-trajectory scalars: min-max normalisation over the
-// collision-free ones, total = w_s * smooth + w_l * length, first minimum; the winner is gathered with x[0, 2:] = 0
-// (diffusion_model_dynamic.py:607).  One block of 1024 threads over rows [0, B) of the arrays it is given.
-// result: {n_free, rank of the winner among the free ones, its row + row0, 0}.  SCENES: the static flow of a many-scene batch --
-// the winner is copied unmodified, a block with no free row gets a NaN `best` and {0, -1, -1, 0}.  EPISODE: one episode of a many-episode
-// replan -- the replan's rule on the winner (x[0, 2:] = 0), result[3] = 0 written, and without a free row `best` stays as it is.
-template <bool SCENES, bool EPISODE = false>
-__device__ __forceinline__ void select_block(const float* __restrict__ traj, const int* __restrict__ mask,
-                                             const float* __restrict__ plen, const float* __restrict__ smooth,
-                                             float w_s, float w_l, float* __restrict__ best,
-                                             int* __restrict__ result, int B, int H, int S, int row0) {
-  __shared__ float r_min[2][16], r_max[2][16];
-  __shared__ float r_tot[16]; __shared__ int r_idx[16], r_cnt[16];
-  __shared__ float s_lo[2], s_hi[2]; __shared__ int s_best, s_free;
+// The order of a selection, stated once for select_block and the diverse selection below (ramp_select_diverse_scenes in ramp_hip.h).
+// select_ranges: the ranges of the min-max normalisation over the free rows of [0, B) and their number, block-wide (1024 threads; every
+// thread gets the same record)
+struct SelectRanges { float pl_lo, pl_rng, sm_lo, sm_rng; int n_free; };
+__device__ __forceinline__ SelectRanges select_ranges(const int* __restrict__ mask, const float* __restrict__ plen,
+                                                      const float* __restrict__ smooth, int B) {
+  __shared__ float r_min[2][16], r_max[2][16]; __shared__ int r_cnt[16];
+  __shared__ float s_lo[2], s_hi[2]; __shared__ int s_free;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float lo0 = INFINITY, hi0 = -INFINITY, lo1 = INFINITY, hi1 = -INFINITY; int cnt = 0;
   for (int b = tid; b < B; b += 1024)
@@ -454,38 +448,63 @@ __device__ __forceinline__ void select_block(const float* __restrict__ traj, con
     s_lo[0] = a0; s_hi[0] = b0; s_lo[1] = a1; s_hi[1] = b1; s_free = c;
   }
   __syncthreads();
-  const float pl_lo = s_lo[0], pl_rng = sub(s_hi[0], s_lo[0]), sm_lo = s_lo[1], sm_rng = sub(s_hi[1], s_lo[1]);
-  float bt = INFINITY; int bi = 0x7fffffff;
-  for (int b = tid; b < B; b += 1024) {
-    if (mask[b]) continue;
-    const float pl = __fdiv_rn(sub(plen[b], pl_lo), pl_rng), sm = __fdiv_rn(sub(smooth[b], sm_lo), sm_rng);
-    const float tot = add(mul(w_s, sm), mul(w_l, pl));
-    // a NaN total (0 / 0 when every free trajectory ties) ranks first, as in torch.argmin
-    const bool better = (tot != tot) ? !(bt != bt) || b < bi : (!(bt != bt) && (tot < bt || (tot == bt && b < bi)));
-    if (bi == 0x7fffffff || better) { bt = tot; bi = b; }
-  }
+  return {s_lo[0], sub(s_hi[0], s_lo[0]), s_lo[1], sub(s_hi[1], s_lo[1]), s_free};
+}
+// total of a free row: w_s sm + w_l pl on the normalised values, one fp32 rounding per operation
+__device__ __forceinline__ float select_total(float pl_b, float sm_b, const SelectRanges& r, float w_s, float w_l) {
+  const float pl = __fdiv_rn(sub(pl_b, r.pl_lo), r.pl_rng), sm = __fdiv_rn(sub(sm_b, r.sm_lo), r.sm_rng);
+  return add(mul(w_s, sm), mul(w_l, pl));
+}
+// row (ot, oi) comes before row (bt, bi): a NaN total (0 / 0 when every free trajectory ties) ranks first, as in torch.argmin, then the
+// smaller total, then the lower row
+__device__ __forceinline__ bool select_before(float ot, int oi, float bt, int bi) {
+  return (ot != ot) ? (!(bt != bt) || oi < bi) : (!(bt != bt) && (ot < bt || (ot == bt && oi < bi)));
+}
+constexpr int SELECT_NONE = 0x7fffffff;     // "no row yet" of a running first-in-order
+__device__ __forceinline__ void select_take(float ot, int oi, float& bt, int& bi) {
+  if (oi == SELECT_NONE) return;
+  if (bi == SELECT_NONE || select_before(ot, oi, bt, bi)) { bt = ot; bi = oi; }
+}
+// the first row in the order among the 1024 threads' running firsts, handed to every thread (SELECT_NONE: no thread has one); one use per kernel
+__device__ __forceinline__ int select_first_in_block(float bt, int bi) {
+  __shared__ float r_tot[16]; __shared__ int r_idx[16]; __shared__ int s_best;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) {
     const float ot = __shfl_xor(bt, m); const int oi = __shfl_xor(bi, m);
-    if (oi == 0x7fffffff) continue;
-    const bool better = (ot != ot) ? (!(bt != bt) || oi < bi) : (!(bt != bt) && (ot < bt || (ot == bt && oi < bi)));
-    if (bi == 0x7fffffff || better) { bt = ot; bi = oi; }
+    select_take(ot, oi, bt, bi);
   }
   if (lane == 0) { r_tot[wave] = bt; r_idx[wave] = bi; }
   __syncthreads();
   if (tid == 0) {
-    float t = INFINITY; int i = 0x7fffffff;
-    for (int w = 0; w < 16; ++w) {
-      const float ot = r_tot[w]; const int oi = r_idx[w];
-      if (oi == 0x7fffffff) continue;
-      const bool better = (ot != ot) ? (!(t != t) || oi < i) : (!(t != t) && (ot < t || (ot == t && oi < i)));
-      if (i == 0x7fffffff || better) { t = ot; i = oi; }
-    }
+    float t = INFINITY; int i = SELECT_NONE;
+    for (int w = 0; w < 16; ++w) select_take(r_tot[w], r_idx[w], t, i);
     s_best = i;
   }
   __syncthreads();
-  const int bb = s_best;
-  if (bb == 0x7fffffff) {
+  return s_best;
+}
+// compute_trajectory_costs (cost.py:56-88) over the B per-trajectory scalars: min-max normalisation over the
+// collision-free ones, total = w_s * smooth + w_l * length, first minimum; the winner is gathered with x[0, 2:] = 0
+// (diffusion_model_dynamic.py:607).  One block of 1024 threads over rows [0, B) of the arrays it is given.
+// result: {n_free, rank of the winner among the free ones, its row + row0, 0}.  SCENES: the static flow of a many-scene batch --
+// the winner is copied unmodified, a block with no free row gets a NaN `best` and {0, -1, -1, 0}.  EPISODE: one episode of a many-episode
+// replan -- the replan's rule on the winner (x[0, 2:] = 0), result[3] = 0 written, and without a free row `best` stays as it is.
+template <bool SCENES, bool EPISODE = false>
+__device__ __forceinline__ void select_block(const float* __restrict__ traj, const int* __restrict__ mask,
+                                             const float* __restrict__ plen, const float* __restrict__ smooth,
+                                             float w_s, float w_l, float* __restrict__ best,
+                                             int* __restrict__ result, int B, int H, int S, int row0) {
+  __shared__ int r_cnt[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const SelectRanges rg = select_ranges(mask, plen, smooth, B);
+  float bt = INFINITY; int bi = SELECT_NONE;
+  for (int b = tid; b < B; b += 1024) {
+    if (mask[b]) continue;
+    select_take(select_total(plen[b], smooth[b], rg, w_s, w_l), b, bt, bi);
+  }
+  const int bb = select_first_in_block(bt, bi);
+  if (bb == SELECT_NONE) {
     if (tid == 0) { result[0] = 0; result[1] = -1; result[2] = -1; if (SCENES || EPISODE) result[3] = 0; }
     if (SCENES) for (int e = tid; e < H * S; e += 1024) best[e] = __int_as_float(0x7fc00000);
     return;
@@ -496,7 +515,7 @@ __device__ __forceinline__ void select_block(const float* __restrict__ traj, con
   for (int m = 32; m >= 1; m >>= 1) rank += __shfl_xor(rank, m);
   if (lane == 0) r_cnt[wave] = rank;
   __syncthreads();
-  if (tid == 0) { int r = 0; for (int w = 0; w < 16; ++w) r += r_cnt[w]; result[0] = s_free; result[1] = r; result[2] = bb + row0; if (SCENES || EPISODE) result[3] = 0; }
+  if (tid == 0) { int r = 0; for (int w = 0; w < 16; ++w) r += r_cnt[w]; result[0] = rg.n_free; result[1] = r; result[2] = bb + row0; if (SCENES || EPISODE) result[3] = 0; }
   if (traj == nullptr) return;                            // selection from gathered costs only (multi-GPU merge): the winner's owner holds the row
   for (int e = tid; e < H * S; e += 1024) {
     float v = traj[(long)bb * H * S + e];
@@ -534,6 +553,127 @@ __global__ __launch_bounds__(1024) void select_episodes_kernel(const float* __re
   const int first = min(max(traj_first[e], 0), B), end = min(max(traj_first[e + 1], first), B);
   select_block<false, true>(traj + (long)first * H * S, mask + first, plen + first, smooth + first, w_s, w_l, best + (long)e * H * S,
                             result + 4 * e, end - first, H, S, first);
+}
+
+// ---- K cheapest free rows per scene that are pairwise >= min_sep apart, and the mode of every free row (ramp_select_diverse_scenes in
+// ramp_hip.h states the definition).  Pass k = one pick launch (one block per scene: the first row in select_block's order among the
+// scene's candidates) and one update launch (one wave per row of the batch: its distance to that pick; suppressed flag, nearest slot and
+// nearest distance).  Nothing is handed between blocks inside a launch: a pick reads what the update before it wrote, an update what
+// the pick before it wrote.  A row's state in scratch: candidate, suppressed, representative or colliding.
+enum { DIV_CANDIDATE = 0, DIV_SUPPRESSED = 1, DIV_REP = 2, DIV_COLLIDING = 3 };
+// FIRST (pass 0): the scene's ranges and totals, as select_block forms them, and every row's state
+template <bool FIRST>
+__global__ __launch_bounds__(1024) void diverse_pick_kernel(DiverseArgs a, int k) {
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int first = min(max(a.traj_first[s], 0), a.B), end = min(max(a.traj_first[s + 1], first), a.B), n = end - first;
+  int* state = a.state + first; float* tot = a.tot + first;
+  if (FIRST) {
+    const SelectRanges rg = select_ranges(a.mask + first, a.plen + first, a.smooth + first, n);
+    for (int b = tid; b < n; b += 1024) {             // (thread tid reads back only what it wrote here)
+      const bool hit = a.mask[first + b] != 0;
+      state[b] = hit ? DIV_COLLIDING : DIV_CANDIDATE;
+      if (!hit) tot[b] = select_total(a.plen[first + b], a.smooth[first + b], rg, a.w_s, a.w_l);
+    }
+    if (tid == 0) a.result[4 * s] = rg.n_free;
+  }
+  float bt = INFINITY; int bi = SELECT_NONE;
+  for (int b = tid; b < n; b += 1024)
+    if (state[b] == DIV_CANDIDATE) select_take(tot[b], b, bt, bi);
+  const int bb = select_first_in_block(bt, bi);
+  const long slot = (long)s * a.K + k;
+  if (tid == 0) { a.pick[s] = bb == SELECT_NONE ? -1 : first + bb; a.rows[slot] = bb == SELECT_NONE ? -1 : first + bb; }
+  float* best = a.best + slot * a.H * a.S;
+  const float* row = a.traj + (long)(first + (bb == SELECT_NONE ? 0 : bb)) * a.H * a.S;
+  for (int e = tid; e < a.H * a.S; e += 1024) best[e] = bb == SELECT_NONE ? __int_as_float(0x7fc00000) : row[e];
+}
+// a NaN on either side stays a NaN (fmaxf would drop it)
+__device__ __forceinline__ float max_keep_nan(float x, float y) { return x != x ? x : (y != y ? y : fmaxf(x, y)); }
+// d(b, r) of the definition, the same value in every lane of the wave: per-waypoint norm over D coordinates in fp32 (differences, squares
+// added in coordinate order, root); metric 0: the norms added in fp64 in ascending h, over H, rounded to fp32 once; metric 1: their maximum
+template <int D>
+__device__ __forceinline__ float diverse_distance(const float* __restrict__ pb, const float* __restrict__ pr, int H, int S, int metric,
+                                                  int lane) {
+  float nrm[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {                        // H <= 128: waypoints lane and lane + 64
+    const int h = lane + 64 * i;
+    nrm[i] = 0.f;
+    if (h < H) {
+      const float dx = sub(pb[h * S], pr[h * S]), dy = sub(pb[h * S + 1], pr[h * S + 1]);
+      float d2 = add(mul(dx, dx), mul(dy, dy));
+      if (D == 3) { const float dz = sub(pb[h * S + 2], pr[h * S + 2]); d2 = add(d2, mul(dz, dz)); }
+      nrm[i] = __fsqrt_rn(d2);
+    }
+  }
+  if (metric == 1) {
+    float m = max_keep_nan(nrm[0], nrm[1]);            // (norms are >= 0: the 0 of a waypoint past H changes nothing)
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) m = max_keep_nan(m, __shfl_xor(m, o));
+    return m;
+  }
+  double acc = 0.0;
+  for (int h = 0; h < min(H, 64); ++h) acc += (double)__shfl(nrm[0], h);
+  for (int h = 64; h < H; ++h) acc += (double)__shfl(nrm[1], h - 64);
+  return (float)(acc / (double)H);
+}
+// one wave per row b of the batch, 4 rows per block; the row's scene by bisection of the clamped table (non-decreasing)
+template <int D>
+__global__ __launch_bounds__(256) void diverse_update_kernel(DiverseArgs a, int k) {
+  const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= a.B) return;                                 // (uniform over the wave; the kernel has no block-wide step)
+  if (k == 0 && lane == 0) { a.mode_of[b] = -1; a.sep[b] = __int_as_float(0x7fc00000); }
+  int lo = 0, hi = a.n_scenes;                          // the first i in [1, n_scenes] with traj_first[i] > b, or n_scenes + 1; s = i - 1
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (min(max(a.traj_first[mid + 1], 0), a.B) > b) hi = mid; else lo = mid + 1;
+  }
+  const int s = lo;
+  if (s >= a.n_scenes || min(max(a.traj_first[s], 0), a.B) > b) return;      // a row of no scene
+  const int st = a.state[b];
+  if (st >= DIV_REP) return;
+  const int r = a.pick[s];
+  if (r < 0) return;                                    // the scene has run out of candidates
+  const float d = diverse_distance<D>(a.traj + (long)b * a.H * a.S, a.traj + (long)r * a.H * a.S, a.H, a.S, a.metric, lane);
+  if (lane != 0) return;
+  if (b == r) { a.state[b] = DIV_REP; a.mode_of[b] = k; a.sep[b] = d; return; }      // a representative belongs to its own slot
+  if (st == DIV_CANDIDATE && !(d >= a.min_sep)) a.state[b] = DIV_SUPPRESSED;          // (a NaN distance suppresses)
+  if (d == d && (a.mode_of[b] < 0 || d < a.sep[b])) { a.mode_of[b] = k; a.sep[b] = d; }   // the lowest slot keeps a tie; a NaN never wins
+}
+// rows per slot, and the scene's record
+__global__ __launch_bounds__(256) void diverse_finish_kernel(DiverseArgs a) {
+  __shared__ int cnt[DIVERSE_MAX_K];
+  const int s = blockIdx.x, tid = threadIdx.x;
+  const int first = min(max(a.traj_first[s], 0), a.B), end = min(max(a.traj_first[s + 1], first), a.B);
+  if (tid < DIVERSE_MAX_K) cnt[tid] = 0;
+  __syncthreads();
+  for (int b = first + tid; b < end; b += 256) {
+    const int m = a.mode_of[b];
+    if (m >= 0 && m < a.K) atomicAdd(&cnt[m], 1);
+  }
+  __syncthreads();
+  if (tid < a.K) a.mode_count[(long)s * a.K + tid] = cnt[tid];
+  if (tid == 0) {
+    int n_sel = 0;
+    for (int j = 0; j < a.K; ++j) n_sel += a.rows[(long)s * a.K + j] >= 0;
+    a.result[4 * s + 1] = n_sel; a.result[4 * s + 2] = a.rows[(long)s * a.K]; a.result[4 * s + 3] = 0;
+  }
+}
+// 2 K + 1 launches whatever the scenes, the rows and the data
+int launch_select_diverse(const DiverseArgs& a, hipStream_t s) {
+  RAMP_REQUIRE(a.B >= 0 && a.H >= 1 && a.H <= 128 && (a.D == 2 || a.D == 3) && a.D <= a.S && a.n_scenes >= 1 && a.K >= 1 &&
+               a.K <= DIVERSE_MAX_K, "bad diverse selection dims");
+  const dim3 rows((a.B + 3) / 4 > 0 ? (a.B + 3) / 4 : 1);
+  for (int k = 0; k < a.K; ++k) {
+    if (k == 0) hipLaunchKernelGGL(diverse_pick_kernel<true>, dim3(a.n_scenes), dim3(1024), 0, s, a, k);
+    else hipLaunchKernelGGL(diverse_pick_kernel<false>, dim3(a.n_scenes), dim3(1024), 0, s, a, k);
+    RAMP_HIP_CHECK(hipGetLastError());
+    if (a.D == 3) hipLaunchKernelGGL(diverse_update_kernel<3>, rows, dim3(256), 0, s, a, k);
+    else hipLaunchKernelGGL(diverse_update_kernel<2>, rows, dim3(256), 0, s, a, k);
+    RAMP_HIP_CHECK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(diverse_finish_kernel, dim3(a.n_scenes), dim3(256), 0, s, a);
+  RAMP_HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 int launch_replan_init(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
