@@ -616,7 +616,8 @@ typedef struct ramp_replan_result {
 } ramp_replan_result;
 
 /* best_out device (H,S) or NULL; batch_out device (B,H,S) or NULL (the batch handed to the selection); mask_out device
- * (B) int32 or NULL (1 = in collision).  Synchronises `stream` (the result record is in host memory on return). */
+ * (B) int32 or NULL (1 = in collision).  Without a collision-free candidate (n_free == 0) best_out holds the plan the replan started from.
+ * Synchronises `stream` (the result record is in host memory on return). */
 int ramp_replan(ramp_ctx* ctx, const ramp_replan_params* p, const ramp_replan_state* st, float* best_out, float* batch_out,
                 int32_t* mask_out, ramp_replan_result* result_host, void* stream);
 /* ---- many episodes replanned in lock-step: the evaluation campaign of scripts/inference/inference_dynamic.py (run_multiple_experiments:

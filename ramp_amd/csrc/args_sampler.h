@@ -151,18 +151,11 @@ struct ApfDynArgs {
   int n_episodes = 0;
 };
 int launch_apf_dynamic(const ApfDynArgs& a, hipStream_t s);
-// receding-horizon replanning (sampler.hip): what changes from replan to replan, resident on the device
-struct ReplanState { int n_hist; int stepp; int pad0; int pad1; float pursuer[2]; float pad2[2]; };
-int launch_replan_init(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
-                       const ReplanState* st, int B, int H, int S, hipStream_t s);
-int launch_replan_pin(float* x, HardConds hc, const float* hist, const float* x_clean, const ReplanState* st, int B, int H,
-                      int S, hipStream_t s);
-int launch_replan_sm(float* x, const ReplanState* st, int window, float dt, float max_vel, int B, int H, int S, hipStream_t s);
-int launch_replan_near(const float* x, const ReplanState* st, float thr, int* en, int B, int H, int S, hipStream_t s);
 int launch_replan_goal(float* x0, const float* x, int B, int H, int S, hipStream_t s);
-// The same four kernels for a batch of many episodes advancing in lock-step (ramp_replan_episodes): row b belongs to episode
-// row_ep[b] and reads that episode's record, history (E,H,S) and clean plan (E,H,S); per row the arithmetic is the single-episode
-// kernels' own.  `active` = 0 marks an episode that has ended: its rows still run (from its last plan), its selection is skipped.
+// receding-horizon replanning (sampler.hip) of a batch of episodes advancing in lock-step (ramp_replan_episodes; ramp_replan is one
+// episode): what changes from replan to replan is resident on the device, one record per episode.  Row b belongs to episode row_ep[b]
+// and reads that episode's record, history (E,H,S) and clean plan (E,H,S).  `active` = 0 marks an episode that has ended: its rows
+// still run (from its last plan), its selection is skipped.
 struct EpisodeState { int n_hist; int stepp; int active; int pad0; float pursuer[2]; float pad1[2]; };
 struct EpisodeTable { const EpisodeState* st = nullptr; const int* row_ep = nullptr; int n_episodes = 0; };
 int launch_replan_init_episodes(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
@@ -184,7 +177,7 @@ int launch_select_episodes(const float* traj, const int* mask, const float* plen
 // ---- the cost guide of the replanning jobs (guide_replan.hip + guide_core.h; ramp_replan_guide in ramp_hip.h) -------------------
 // The static term of GuideArgs (2-D) plus a moving cloud of n_mov <= GUIDE_TILE points per scene displaced by a per-waypoint track, and pins that
 // differ from row to row: waypoints < n_first(b), waypoint H - 1 and the hard-conditioned ones.  n_first(b) = pin_first[b], or the n_hist of
-// the row's episode record (est, with its `active` switch: a row of an ended episode is left alone) or of the single replan's record (rst).
+// the row's episode record (est, with its `active` switch: a row of an ended episode is left alone).
 // The working copy's pinned values: the hard condition's (later entries win), then -- only with hist / x_clean, the replans' buffers
 // (n_scenes, H, S) -- the history rows and the clean plan's goal, replan_pin_row's order; a pinned waypoint nothing names keeps the array's own
 struct MovingGuideArgs {
@@ -196,7 +189,7 @@ struct MovingGuideArgs {
   const float* track = nullptr;     // device (n_scenes, H, 2): its displacement at waypoint h
   const int* scene = nullptr;       // (B) scene (episode) of each row, or null = 0 for all; an index outside the table leaves the row alone
   int n_scenes = 1, P_total = 0, n_mov = 0;
-  const int* pin_first = nullptr; const EpisodeState* est = nullptr; const ReplanState* rst = nullptr;   // where n_first(b) comes from (all null: 0)
+  const int* pin_first = nullptr; const EpisodeState* est = nullptr;   // where n_first(b) comes from (both null: 0)
   const float* hist = nullptr; const float* x_clean = nullptr;
   float radius = 0, radius_mov = 0, w_obs = 0, w_mov = 0, w_smooth = 0, w_acc = 0, max_norm = 0;
   float step = 0; int n_iter = 0;   // (the cost kernel reads neither, nor the pins)

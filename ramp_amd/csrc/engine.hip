@@ -183,19 +183,11 @@ struct ramp_ctx {
   bool c_cal_valid = false; std::string c_cal_key; unsigned long long* c_cal_rec = nullptr;
   std::map<std::string, float*> c_cal_saved;     // canonical tables already computed, by key: switching between job shapes copies 4 KB instead of re-evaluating
   std::vector<float*> c_cal_free;                // their buffers after an invalidation (scene / plan change), for reuse
-  // receding-horizon replanning (ramp_replan): fixed device buffers the captured graphs read, the graph of a replan whose
-  // first evaluation calibrates ([0]) and of one that continues from the previous replan's operand maxima ([1], TABLE_REPLAN_CARRY)
-  float *r_noise = nullptr, *r_hist = nullptr, *r_xclean = nullptr, *r_best = nullptr, *r_plen = nullptr, *r_smooth = nullptr,
-        *r_cost = nullptr, *r_hard_val = nullptr;
-  double *r_static = nullptr, *r_dyn = nullptr;
-  int *r_mask = nullptr, *r_en = nullptr, *r_result = nullptr, *r_hard_idx = nullptr;
-  ReplanState* r_state = nullptr;
-  size_t r_cap_B = 0, r_cap_static = 0, r_cap_dyn = 0, r_cap_cost = 0;
-  hipGraphExec_t r_graph[2] = {nullptr, nullptr}; std::string r_key;
-  bool r_calibrated = false;
-  // many episodes in lock-step (ramp_replan_episodes): the same roles per episode, in buffers, graphs and a key of their own.  e_cap_B
-  // rows, e_cap_E episodes, the clouds in points; e_best_E: the episode count e_best holds winners (or plans) for.  The carried
-  // operand maxima share TABLE_REPLAN_CARRY with ramp_replan: each of the two invalidates the other's calibration
+  // receding-horizon replanning: ONE job, the replan of E episodes in lock-step (ramp_replan_episodes); ramp_replan is its one-episode
+  // case.  Fixed device buffers the captured graphs read -- per row (e_cap_B rows), per episode (e_cap_E episodes) and the episodes'
+  // concatenated clouds (in points; e_extra is staging only) --, the graph of a replan whose first evaluation calibrates ([0]) and of one
+  // that continues from the previous replan's operand maxima ([1], TABLE_REPLAN_CARRY), and their key.  e_best_E: the episode count e_best
+  // holds winners (or plans) for
   float *e_noise = nullptr, *e_hist = nullptr, *e_xclean = nullptr, *e_best = nullptr, *e_plen = nullptr, *e_smooth = nullptr,
         *e_cost = nullptr, *e_extra = nullptr, *e_hard_val = nullptr;
   double *e_static = nullptr, *e_dyn = nullptr;
@@ -204,7 +196,10 @@ struct ramp_ctx {
   EpisodeState* e_state = nullptr;
   size_t e_cap_B = 0, e_cap_E = 0, e_cap_static = 0, e_cap_dyn = 0, e_cap_cost = 0, e_cap_extra = 0; int e_best_E = 0;
   hipGraphExec_t e_graph[2] = {nullptr, nullptr}; std::string e_key;
-  bool e_calibrated = false;
+  // which entry ran the previous replan (whose winners e_best holds: x_clean == NULL continues the same entry's only), and which one's
+  // operand maxima TABLE_REPLAN_CARRY holds (a call of the other entry, or after an invalidation, calibrates)
+  enum ReplanEntry { REPLAN_NOBODY = 0, REPLAN_SINGLE, REPLAN_EPISODES };
+  ReplanEntry replan_last = REPLAN_NOBODY, replan_carry = REPLAN_NOBODY;
   // cost guidance inside the replans (ramp_replan_guided, ramp_replan_episodes_guided): the static guide clouds (sum P, 2), their offsets
   // (n_scenes + 1), the moving clouds (n_scenes, n_mov, 2) and their tracks (n_scenes, H, 2), copied here before the launch -- data of a replay
   // -- and the tap (2, B, H, S).  Scalars, counts, step sizes, n_mov, the clouds' total and the tap's presence are in the graph key
@@ -501,7 +496,7 @@ struct Run {
   //   tkc          tkc_min_rows               plain k = 5 conv, tkc_applicable (tkc.hip), 32-bit row offsets; ramp_ctx::tkc_w     1, 2
   //   tkw          tkw_min_rows               plain k = 5 conv + its GroupNorm, tkw_applicable (tkw.hip); h3                      2
   // No predicate tests force_x6: phase is non-zero only where the caller has established gemm_mode == 2 && !force_x6 first (ramp_score,
-  // sample_body, replan_body, and the steady jobs' canonical_calibration), and ramp_replan raises force_x6 only around a phase-0 repeat --
+  // sample_body, replan_body, and the steady jobs' canonical_calibration), and replan_job raises force_x6 only around a phase-0 repeat --
   // so the !force_x6 that tkc_planes and use_tkw used to carry was implied by their phase test.
   bool steady() const { return c->gemm_mode == 2 && c->phase == 2 && c->x6_pipe; }
   static bool from(int min_rows, int M) { return min_rows > 0 && M >= min_rows; }
@@ -1286,7 +1281,7 @@ template <class T> int grow(ramp_ctx* c, T*& p, size_t& cap, size_t n) {
   return 0;
 }
 void staging_done(ramp_ctx* c) {
-  if (c->buffers_moved) { c->graph_key.clear(); c->r_key.clear(); c->e_key.clear(); c->buffers_moved = false; }
+  if (c->buffers_moved) { c->graph_key.clear(); c->e_key.clear(); c->buffers_moved = false; }
 }
 
 int ensure_sampler_buffers(ramp_ctx* c, int B, int n_rp, int n_steps, bool chain) {
@@ -1400,8 +1395,12 @@ struct Key {
 enum { CAL_SCORE = 1, CAL_REPLAN = 2, CAL_CANONICAL = 4, CAL_ALL = 7 };
 void invalidate_calibrations(ramp_ctx* c, int what) {
   if (what & CAL_SCORE) c->score_calibrated = false;
-  if (what & CAL_REPLAN) c->r_calibrated = c->e_calibrated = false;
+  if (what & CAL_REPLAN) c->replan_carry = ramp_ctx::REPLAN_NOBODY;
   if (what & CAL_CANONICAL) c->c_cal_valid = false;
+}
+// ramp_score's evaluations end the single entry's carried calibration and leave the episode entry's: an asymmetry inherited as it is
+void forget_single_replan_carry(ramp_ctx* c) {
+  if (c->replan_carry == ramp_ctx::REPLAN_SINGLE) c->replan_carry = ramp_ctx::REPLAN_NOBODY;
 }
 
 }  // namespace
@@ -1487,7 +1486,7 @@ int ramp_set_launch_plan(ramp_ctx* c, const ramp_launch_plan* p) {
   c->atk_min_rows = p->atk_rows; c->tkc_min_rows = p->tkc_rows; c->tkw_min_rows = p->tkw_rows;
   c->three_blocks = p->three_blocks != 0; c->x6_pipe = p->x6_pipe != 0; c->mfma16 = p->mfma16 != 0;
   if (changed && c->finalized) {   // other kernels from here on: captured graphs and kept calibrations belong to the old plan
-    c->graph_key.clear(); c->r_key.clear();
+    c->graph_key.clear(); c->e_key.clear();
     invalidate_calibrations(c, CAL_ALL);
   }
   return 0;
@@ -1496,7 +1495,7 @@ int ramp_set_launch_plan(ramp_ctx* c, const ramp_launch_plan* p) {
 int ramp_destroy(ramp_ctx* c) {
   if (!c) return 0;
   drop_graphs(c->s_graph, 3);
-  drop_graphs(c->r_graph, 2);
+  drop_graphs(c->e_graph, 2);
   if (c->d_ptr_tables) (void)hipFree(c->d_ptr_tables);
   delete c;
   return 0;
@@ -1827,7 +1826,6 @@ static int set_scene_table(ramp_ctx* c, const float* latents, int n_variants, co
   c->rv_rows = n_rows;
   c->scene_epoch++;
   c->graph_key.clear();     // scene changed: cross_bias pointer may have moved
-  c->r_key.clear();
   c->e_key.clear();
   invalidate_calibrations(c, CAL_ALL);
   return rc;
@@ -1942,12 +1940,12 @@ int ramp_score(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, int32_t t, 
     int flag = 0;
     RAMP_HIP_CHECK(hipMemcpyAsync(&flag, c->range_flag, sizeof(int), hipMemcpyDeviceToHost, s));
     RAMP_HIP_CHECK(hipStreamSynchronize(s));
-    c->r_calibrated = false;
+    forget_single_replan_carry(c);
     if (!flag) { c->score_parity ^= 1; c->score_last_mode = 2; c->score_calibrated_bwd = eps_out != nullptr; return 0; }
   }
   CK(guarded_eval(c, 1, t_in, t_out, x, B, n_rp, t, f_out, eps_out, s));
   c->score_calibrated = true; c->score_calibrated_bwd = eps_out != nullptr; c->score_parity ^= 1; c->score_last_mode = 1;
-  c->r_calibrated = false;
+  forget_single_replan_carry(c);
   return 0;
 }
 
@@ -2692,20 +2690,18 @@ int ramp_sample_stitched(ramp_ctx* c, const ramp_sample_params* p, const ramp_st
 // graph: q_sample of the current plan -> n_steps x [score, CFG + x0, (last step: static + pursuer APF), DDIM update,
 // pinned waypoints] -> smoothing -> collision mask / costs -> selection.  The pursuer's new position is computed by the
 // caller BEFORE the replan: the reference hands the environment x[:, stepp, :2], which is the pinned executed state.
-// ej != nullptr: the replan of many episodes (ramp_replan_episodes) -- the same sequence on the episode forms of the kernels and the e_*
-// buffers: row b reads the record, history, clean plan, clouds and goal of its own episode
+// The job is the replan of E episodes in lock-step: row b reads the record, history, clean plan, clouds and goal of its own episode
+// (the e_* buffers); ramp_replan's single episode is E = 1, where every row reads episode 0's.
 // rg != nullptr: the cost guide (checked by the entry, its tables staged by stage_replan_guide): on step j with n_guide[j] > 0 ONE launch on x0, behind the CFG
 // combination and, on the last step, behind both APF passes and the goal copy, in front of the DDIM update
 struct EpisodeJob { int E, P_static, P_cost; };      // episodes; points of the concatenated static APF clouds / of the cost segments
-static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, bool calibrate, const EpisodeJob* ej = nullptr,
-                       const ramp_replan_guide* rg = nullptr) {
+static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, bool calibrate, const EpisodeJob& ej, const ramp_replan_guide* rg) {
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S;
-  HardConds hc; hc.idx = ej ? c->e_hard_idx : c->r_hard_idx; hc.val = ej ? c->e_hard_val : c->r_hard_val; hc.n = p->n_hard;
+  HardConds hc; hc.idx = c->e_hard_idx; hc.val = c->e_hard_val; hc.n = p->n_hard;
   HardConds none;
-  EpisodeTable et; if (ej) { et.st = c->e_state; et.row_ep = c->e_row_ep; et.n_episodes = ej->E; }
-  if (ej) CK(launch_replan_init_episodes(c->s_x, c->e_xclean, c->e_noise, p->q_sqrt_a, p->q_sqrt_1m_a, c->e_hist, et, B, H, S, s));
-  else CK(launch_replan_init(c->s_x, c->r_xclean, c->r_noise, p->q_sqrt_a, p->q_sqrt_1m_a, c->r_hist, c->r_state, B, H, S, s));
+  EpisodeTable et; et.st = c->e_state; et.row_ep = c->e_row_ep; et.n_episodes = ej.E;
+  CK(launch_replan_init_episodes(c->s_x, c->e_xclean, c->e_noise, p->q_sqrt_a, p->q_sqrt_1m_a, c->e_hist, et, B, H, S, s));
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   if (h3) {
     hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, s, reinterpret_cast<unsigned*>(c->range_flag), 1);
@@ -2717,17 +2713,15 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
   if (rg) {
     ga = moving_guide_args(rg, c->s_x0, B, H, S);
     ga.cloud = c->rg_cloud; ga.cloud_off = c->rg_off; ga.mov = c->rg_mov; ga.track = c->rg_track; ga.hc = hc;
-    if (ej) { ga.scene = c->e_row_ep; ga.est = c->e_state; ga.hist = c->e_hist; ga.x_clean = c->e_xclean; }
-    else { ga.rst = c->r_state; ga.hist = c->r_hist; ga.x_clean = c->r_xclean; }
+    ga.scene = c->e_row_ep; ga.est = c->e_state; ga.hist = c->e_hist; ga.x_clean = c->e_xclean;
     if (rg->tap_out) for (int j = 0; j < p->n_steps; ++j) if (rg->n_guide[j] > 0) j_tap = j;
   }
   for (int j = 0; j < p->n_steps; ++j) {
     const bool last = p->t[j] == 0;                       // the reference's `i == 0`: smoothing + APF on the final step
-    if (last && ej) CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
-    else if (last) CK(launch_replan_sm(c->s_x, c->r_state, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
+    if (last) CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_last, p->sm_dt, p->sm_max_vel, B, H, S, s));
     // delayed-scaling tables: evaluation j writes table j & 1, the last one TABLE_REPLAN_CARRY, which the first evaluation of the
     // NEXT replan reads: every steady-state replan sees the same pointers, so its graph is captured once
-    // (no flag log: a flagged replan is repeated whole by ramp_replan, and the sampling jobs' log stays theirs)
+    // (no flag log: a flagged replan is repeated whole by replan_job, and the sampling jobs' log stays theirs)
     const int t_out = j + 1 == p->n_steps ? TABLE_REPLAN_CARRY : (j & 1) ? TABLE_ODD : TABLE_EVEN;
     const int t_in = j == 0 ? TABLE_REPLAN_CARRY : (j & 1) ? TABLE_EVEN : TABLE_ODD;
     CK(guarded_eval(c, !h3 ? 0 : (calibrate && j == 0) ? 1 : 2, t_in, t_out, c->s_x, B, p->n_rp, p->t[j], nullptr, c->s_eps, s,
@@ -2738,16 +2732,14 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
     m.mean = nullptr; m.x0 = c->s_x0;
     CK(launch_cfg_mean(m, s));
     if (last) {
-      if (ej) CK(launch_replan_near_episodes(c->s_x, et, (float)p->thr_pred, c->e_en, B, H, S, s));
-      else CK(launch_replan_near(c->s_x, c->r_state, (float)p->thr_pred, c->r_en, B, H, S, s));
+      CK(launch_replan_near_episodes(c->s_x, et, (float)p->thr_pred, c->e_en, B, H, S, s));
       ApfDynArgs a; a.traj = c->s_x0; a.B = B; a.H = H; a.S = S;
-      a.points = c->r_static; a.P = p->n_static; a.window = p->window_static; a.affected = H;
+      a.points = c->e_static; a.P = ej.P_static; a.window = p->window_static; a.affected = H;
       a.thr_query = p->thr_static; a.thr_force = p->thr_static; a.strength = p->strength_static;
-      if (ej) { a.points = c->e_static; a.P = ej->P_static; a.episode = c->e_row_ep; a.ep_off = c->e_static_off; a.n_episodes = ej->E; }
+      a.episode = c->e_row_ep; a.ep_off = c->e_static_off; a.n_episodes = ej.E;
       CK(launch_apf_dynamic(a, s));
-      a.points = c->r_dyn; a.P = p->n_dyn; a.window = -1; a.affected = H; a.thr_query = p->thr_pred;
-      a.strength = p->strength_pred; a.goal = c->s_x + (size_t)(H - 1) * S; a.enable = c->r_en;
-      if (ej) { a.points = c->e_dyn; a.ep_off = nullptr; a.enable = c->e_en; }      // (n_dyn points per episode; every row its own goal)
+      a.points = c->e_dyn; a.P = p->n_dyn; a.ep_off = nullptr; a.window = -1; a.affected = H; a.thr_query = p->thr_pred;      // (n_dyn points per episode;
+      a.strength = p->strength_pred; a.goal = c->s_x + (size_t)(H - 1) * S; a.enable = c->e_en;                              // every row its own goal)
       CK(launch_apf_dynamic(a, s));
       CK(launch_replan_goal(c->s_x0, c->s_x, B, H, S, s));
     }
@@ -2760,20 +2752,13 @@ static int replan_body(ramp_ctx* c, const ramp_replan_params* p, hipStream_t s, 
     }
     CK(launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], none,
                           c->s_x, nullptr, B, H, S, s));
-    if (ej) CK(launch_replan_pin_episodes(c->s_x, hc, c->e_hist, c->e_xclean, et, B, H, S, s));
-    else CK(launch_replan_pin(c->s_x, hc, c->r_hist, c->r_xclean, c->r_state, B, H, S, s));
+    CK(launch_replan_pin_episodes(c->s_x, hc, c->e_hist, c->e_xclean, et, B, H, S, s));
   }
-  if (ej) {
-    CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_final, p->sm_dt, p->sm_max_vel, B, H, S, s));
-    CK(launch_traj_costs_scenes(c->s_x, c->e_cost, c->e_first, c->e_cost_off, ej->E, ej->P_cost, B, H, S, p->cost_thr, c->e_mask, c->e_plen,
-                                c->e_smooth, s));
-    CK(launch_select_episodes(c->s_x, c->e_mask, c->e_plen, c->e_smooth, p->w_smooth, p->w_len, c->e_first, et, c->e_best, c->e_result, B,
-                              H, S, s));
-    return 0;
-  }
-  CK(launch_replan_sm(c->s_x, c->r_state, p->sm_window_final, p->sm_dt, p->sm_max_vel, B, H, S, s));
-  CK(launch_traj_costs(c->s_x, c->r_cost, B, H, S, p->n_cost + p->n_extra, p->cost_thr, c->r_mask, c->r_plen, c->r_smooth, s));
-  CK(launch_replan_select(c->s_x, c->r_mask, c->r_plen, c->r_smooth, p->w_smooth, p->w_len, c->r_best, c->r_result, B, H, S, s));
+  CK(launch_replan_sm_episodes(c->s_x, et, p->sm_window_final, p->sm_dt, p->sm_max_vel, B, H, S, s));
+  CK(launch_traj_costs_scenes(c->s_x, c->e_cost, c->e_first, c->e_cost_off, ej.E, ej.P_cost, B, H, S, p->cost_thr, c->e_mask, c->e_plen,
+                              c->e_smooth, s));
+  CK(launch_select_episodes(c->s_x, c->e_mask, c->e_plen, c->e_smooth, p->w_smooth, p->w_len, c->e_first, et, c->e_best, c->e_result, B,
+                            H, S, s));
   return 0;
 }
 
@@ -2813,163 +2798,16 @@ static void key_replan_guide(Key& key, const ramp_replan_guide* rg, int n_steps)
   key.put(rg->max_norm); key.put(rg->n_guide, n_steps); key.put(rg->step, n_steps); key.put((int)(rg->tap_out != nullptr));
 }
 
-int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_state* st, float* best_out, float* batch_out,
-                int32_t* mask_out, ramp_replan_result* result_host, void* stream) {
-  return ramp_replan_guided(c, p, st, nullptr, best_out, batch_out, mask_out, result_host, stream);
-}
-
-int ramp_replan_guided(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_state* st, const ramp_replan_guide* rg, float* best_out,
-                       float* batch_out, int32_t* mask_out, ramp_replan_result* result_host, void* stream) {
-  RAMP_REQUIRE(c && p && st && result_host, rg ? "ramp_replan_guided: null argument" : "null argument");
-  RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
-  const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
-  RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
-  RAMP_REQUIRE(p->t && p->sqrt_recip && p->sqrt_recipm1 && p->sqrt_a_t && p->sqrt_1m_a_t && p->sqrt_a_prev && p->dir_coef, "missing schedule arrays");
-  RAMP_REQUIRE(p->n_hard >= 0 && p->n_hard <= 16 && (p->n_hard == 0 || (p->hard_idx_host && p->hard_val)), "bad hard conditions");
-  RAMP_REQUIRE(p->static_pts && p->n_static > 0 && p->n_dyn > 0 && p->cost_cloud && p->n_cost > 0 && p->n_extra >= 0, "bad clouds");
-  RAMP_REQUIRE(st->noise && st->history && st->n_hist >= 1 && st->n_hist <= H && st->stepp >= 0 && st->stepp < H, "bad replan state");
-  RAMP_REQUIRE(st->dyn_pts_host && (st->near == 0 || p->n_extra == 0 || st->extra_pts_host), "missing pursuer points");
-  RAMP_REQUIRE(st->x_clean || c->r_best, "no current plan: pass x_clean on the first replan");
-  for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
-  bool guided = false;
-  CK(check_replan_job_guide(c, p, rg, 1, "ramp_replan_guided", &guided));
-  if (!guided) rg = nullptr;
-  hipStream_t s = as_stream(stream);
-  const size_t HS = (size_t)H * S, n = (size_t)B * HS;
-  // ---- fixed buffers the graphs read
-  CK(ensure_sampler_buffers(c, B, p->n_rp, 0, false));
-  if (rg) CK(grow_replan_guide(c, rg, B));
-  if (!c->r_state) {
-    CK(renew(c, c->r_state, 1)); CK(renew(c, c->r_result, 8)); CK(renew(c, c->r_hard_idx, 16));
-    CK(renew(c, c->r_hist, HS)); CK(renew(c, c->r_xclean, HS)); CK(renew(c, c->r_best, HS));
-  }
-  if ((size_t)B > c->r_cap_B) {
-    CK(renew(c, c->r_noise, n)); CK(renew(c, c->r_plen, B)); CK(renew(c, c->r_smooth, B));
-    CK(renew(c, c->r_mask, B)); CK(renew(c, c->r_en, B));
-    CK(renew(c, c->r_hard_val, (size_t)16 * B * S));
-    c->r_cap_B = B;
-  }
-  CK(grow(c, c->r_static, c->r_cap_static, (size_t)p->n_static * 2));
-  CK(grow(c, c->r_dyn, c->r_cap_dyn, (size_t)p->n_dyn * 2));
-  CK(grow(c, c->r_cost, c->r_cap_cost, (size_t)(p->n_cost + p->n_extra) * 2));
-  staging_done(c);
-  // ---- this replan's inputs
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_noise, st->noise, n * 4, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_hist, st->history, (size_t)st->n_hist * S * 4, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_xclean, st->x_clean ? st->x_clean : c->r_best, HS * 4, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_static, p->static_pts, (size_t)p->n_static * 16, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_cost, p->cost_cloud, (size_t)p->n_cost * 8, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_dyn, st->dyn_pts_host, (size_t)p->n_dyn * 16, hipMemcpyHostToDevice, s));
-  std::vector<float> far((size_t)p->n_extra * 2, 1.0e9f);     // (alive until the synchronisation below)
-  if (p->n_extra) {
-    // the pursuer's sphere points join the cost cloud only when it is near the evader; otherwise far-away fillers
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->r_cost + (size_t)p->n_cost * 2, st->near ? st->extra_pts_host : far.data(),
-                                  (size_t)p->n_extra * 8, hipMemcpyHostToDevice, s));
-  }
-  if (p->n_hard) {
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->r_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->r_hard_val, p->hard_val, (size_t)p->n_hard * B * S * 4, hipMemcpyDeviceToDevice, s));
-  }
-  ReplanState hs{}; hs.n_hist = st->n_hist; hs.stepp = st->stepp; hs.pursuer[0] = st->pursuer[0]; hs.pursuer[1] = st->pursuer[1];
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->r_state, &hs, sizeof(hs), hipMemcpyHostToDevice, s));
-  if (rg) CK(stage_replan_guide(c, rg, s));
-  c->launches = 0;
-  invalidate_calibrations(c, CAL_SCORE);      // (the replans carry their maxima in TABLE_REPLAN_CARRY: the sampling jobs' canonical table survives)
-  c->e_calibrated = false;                    // (a many-episode replan that follows finds this batch's maxima in the carried table, not its own)
-  const bool h3 = c->gemm_mode == 2 && !c->force_x6;
-  auto run = [&](bool calibrate) -> int {
-    if (!p->use_graph) return replan_body(c, p, s, calibrate, nullptr, rg);
-    Key key;      // (every r_* buffer exists before the first capture: nothing here is optional in renew()'s sense)
-    key.put(p->B); key.put(p->n_steps); key.put(p->w); key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps);
-    key.put(p->sqrt_recipm1, p->n_steps); key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps);
-    key.put(p->sqrt_a_prev, p->n_steps); key.put(p->dir_coef, p->n_steps); key.put(p->q_sqrt_a); key.put(p->q_sqrt_1m_a);
-    key.put(p->clip_denoised); key.put(p->predict_x0); key.put(p->n_hard); key.put(p->sm_window_last); key.put(p->sm_window_final); key.put(p->sm_dt);
-    key.put(p->sm_max_vel); key.put(p->n_static); key.put(p->n_dyn); key.put(p->thr_static); key.put(p->thr_pred);
-    key.put(p->strength_static); key.put(p->strength_pred); key.put(p->window_static); key.put(p->n_cost); key.put(p->n_extra);
-    key.put(p->cost_thr); key.put(p->w_smooth); key.put(p->w_len); key.put(c->force_x6);
-    if (rg) key_replan_guide(key, rg, p->n_steps);
-    if (key.bytes != c->r_key) { drop_graphs(c->r_graph, 2); c->r_key = key.bytes; }
-    return replay(&c->r_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, nullptr, rg); });
-  };
-  // a one-step replan has no second table to carry its maxima in (its only evaluation reads and clears TABLE_REPLAN_CARRY): it always
-  // calibrates, on the bf16x6 kernels, instead of running fp16x3 from an empty table
-  CK(run(h3 && (!c->r_calibrated || p->n_steps == 1)));
-  // ---- the one read-back of a replan: {n_free, rank, row} + the range flag
-  int back[4] = {0, 0, 0, 0};
-  RAMP_HIP_CHECK(hipMemcpyAsync(back, c->r_result, 12, hipMemcpyDeviceToHost, s));
-  if (h3) RAMP_HIP_CHECK(hipMemcpyAsync(back + 3, c->range_flag, 4, hipMemcpyDeviceToHost, s));
-  RAMP_HIP_CHECK(hipStreamSynchronize(s));
-  result_host->fell_back = 0;
-  if (h3 && back[3]) {
-    // an operand left the range the delayed scaling assumed: repeat THIS replan (same inputs) on the bf16x6 kernels and
-    // start the next one with a calibration evaluation
-    c->force_x6 = 1;
-    int rc = replan_body(c, p, s, false, nullptr, rg);
-    c->force_x6 = 0;
-    CK(rc);
-    RAMP_HIP_CHECK(hipMemcpyAsync(back, c->r_result, 12, hipMemcpyDeviceToHost, s));
-    RAMP_HIP_CHECK(hipStreamSynchronize(s));
-    c->r_calibrated = false;
-    result_host->fell_back = back[3];
-  } else if (h3) {
-    c->r_calibrated = true;
-  }
-  result_host->n_free = back[0]; result_host->best_rank = back[1]; result_host->best_row = back[2];
-  if (best_out) RAMP_HIP_CHECK(hipMemcpyAsync(best_out, c->r_best, HS * 4, hipMemcpyDeviceToDevice, s));
-  if (batch_out) RAMP_HIP_CHECK(hipMemcpyAsync(batch_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
-  if (mask_out) RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->r_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-  if (rg && rg->tap_out) RAMP_HIP_CHECK(hipMemcpyAsync(rg->tap_out, c->rg_tap, 2 * n * 4, hipMemcpyDeviceToDevice, s));
-  return 0;
-}
-
 static_assert(sizeof(ramp_episode_state) == sizeof(EpisodeState) && sizeof(EpisodeState) == 32, "the host record is copied as the device record");
 static_assert(offsetof(ramp_episode_state, active) == offsetof(EpisodeState, active) && offsetof(ramp_episode_state, pursuer) == offsetof(EpisodeState, pursuer), "the host record is copied as the device record");
 
-// (E + 1) first-entry table of host memory: [0] = 0, strictly increasing; returns the total through *total
-static int check_offsets(const int32_t* off, int E, const char* what, int* total) {
-  RAMP_REQUIRE(off && off[0] == 0, std::string(what) + ": the offset table must start at 0");
-  for (int e = 0; e < E; ++e) RAMP_REQUIRE(off[e + 1] > off[e], std::string(what) + ": the offset table must be strictly increasing");
-  *total = off[E];
-  return 0;
-}
-
-int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, float* best_out, float* batch_out,
-                         int32_t* mask_out, int32_t* results_host, ramp_replan_result* result_host, void* stream) {
-  return ramp_replan_episodes_guided(c, p, ep, nullptr, best_out, batch_out, mask_out, results_host, result_host, stream);
-}
-
-int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, const ramp_replan_guide* rg,
-                                float* best_out, float* batch_out, int32_t* mask_out, int32_t* results_host,
-                                ramp_replan_result* result_host, void* stream) {
-  RAMP_REQUIRE(c && p && ep && results_host && result_host, rg ? "ramp_replan_episodes_guided: null argument" : "null argument");
-  RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
+// The replan of both entries behind their argument checks (`who` ran them, rg is an active guide or null, the tables of `ep` are sound
+// and end at P_static / n_cost points): buffers, staging, graph key, run, the one read-back, the bf16x6 repeat of a flagged call and the
+// outputs.  hist_floats: what `ep->history` holds -- whole (H, S) blocks per episode, or the single entry's n_hist rows.
+static int replan_job(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, const ramp_replan_guide* rg, ramp_ctx::ReplanEntry who,
+                      int P_static, int n_cost, size_t hist_floats, float* best_out, float* batch_out, int32_t* mask_out, int32_t* results_host,
+                      ramp_replan_result* result_host, hipStream_t s) {
   const int B = p->B, E = ep->n_episodes, H = c->cfg.horizon, S = c->cfg.state_dim;
-  RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
-  RAMP_REQUIRE(E >= 1 && E <= B && E <= 65536, "bad episode count (1 .. min(B, 65536))");
-  RAMP_REQUIRE(c->rv_rows >= B * p->n_rp, "the row -> latent table of a many-episode replan comes from ramp_set_scenes (B * n_rp rows)");
-  RAMP_REQUIRE(p->t && p->sqrt_recip && p->sqrt_recipm1 && p->sqrt_a_t && p->sqrt_1m_a_t && p->sqrt_a_prev && p->dir_coef, "missing schedule arrays");
-  RAMP_REQUIRE(p->n_hard >= 0 && p->n_hard <= 16 && (p->n_hard == 0 || (p->hard_idx_host && p->hard_val)), "bad hard conditions");
-  RAMP_REQUIRE(p->n_dyn > 0 && p->n_extra >= 0 && p->n_dyn <= (1 << 20) && p->n_extra <= (1 << 20), "bad clouds");
-  RAMP_REQUIRE(ep->noise && ep->history && ep->state_host && ep->static_pts && ep->dyn_pts_host && ep->cost_cloud && ep->near_host, "missing episode inputs");
-  int n_rows = 0, P_static = 0, n_cost = 0;
-  CK(check_offsets(ep->traj_first_host, E, "traj_first", &n_rows));
-  RAMP_REQUIRE(n_rows == B, "traj_first must end at the batch size");
-  CK(check_offsets(ep->static_offset_host, E, "static clouds", &P_static));
-  CK(check_offsets(ep->cost_offset_host, E, "cost clouds", &n_cost));
-  RAMP_REQUIRE((long)n_cost + (long)E * p->n_extra < (1l << 31) && (long)E * p->n_dyn < (1l << 30), "the concatenated clouds do not fit 32-bit offsets");
-  bool any_near = false;
-  for (int e = 0; e < E; ++e) {
-    const ramp_episode_state& st = ep->state_host[e];
-    RAMP_REQUIRE(st.n_hist >= 1 && st.n_hist <= H && st.stepp >= 0 && st.stepp < H, "bad episode state");
-    any_near |= ep->near_host[e] != 0;
-  }
-  RAMP_REQUIRE(!any_near || p->n_extra == 0 || ep->extra_pts_host, "missing pursuer points");
-  RAMP_REQUIRE(ep->x_clean || (c->e_best && c->e_best_E == E), "no current plans: pass x_clean on the first call");
-  for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
-  bool guided = false;
-  CK(check_replan_job_guide(c, p, rg, E, "ramp_replan_episodes_guided", &guided));
-  if (!guided) rg = nullptr;
-  hipStream_t s = as_stream(stream);
   const size_t HS = (size_t)H * S, n = (size_t)B * HS, nE = (size_t)E * HS;
   const int P_cost = n_cost + E * p->n_extra;
   // ---- fixed buffers the graphs read
@@ -2995,7 +2833,7 @@ int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const 
   staging_done(c);
   // ---- this call's inputs.  Host staging lives until the synchronisation below.
   std::vector<int> row_ep(B), cost_off(E + 1);
-  std::vector<float> extra((size_t)E * p->n_extra * 2, 1.0e9f);      // far-away fillers, as in ramp_replan, where the pursuer is not near
+  std::vector<float> extra((size_t)E * p->n_extra * 2, 1.0e9f);      // far-away fillers where the pursuer is not near
   for (int e = 0; e < E; ++e) {
     for (int b = ep->traj_first_host[e]; b < ep->traj_first_host[e + 1]; ++b) row_ep[b] = e;
     cost_off[e] = ep->cost_offset_host[e] + e * p->n_extra;
@@ -3004,14 +2842,14 @@ int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const 
   }
   cost_off[E] = P_cost;
   RAMP_HIP_CHECK(hipMemcpyAsync(c->e_noise, ep->noise, n * 4, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hist, ep->history, nE * 4, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(c->e_hist, ep->history, hist_floats * 4, hipMemcpyDeviceToDevice, s));
   if (ep->x_clean) {      // (also what `best` holds for an episode that selects nothing in this call)
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_xclean, ep->x_clean, nE * 4, hipMemcpyDeviceToDevice, s));
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_best, ep->x_clean, nE * 4, hipMemcpyDeviceToDevice, s));
   } else {
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_xclean, c->e_best, nE * 4, hipMemcpyDeviceToDevice, s));
   }
-  c->e_best_E = E;
+  c->e_best_E = E; c->replan_last = who;
   RAMP_HIP_CHECK(hipMemcpyAsync(c->e_row_ep, row_ep.data(), (size_t)B * 4, hipMemcpyHostToDevice, s));
   RAMP_HIP_CHECK(hipMemcpyAsync(c->e_first, ep->traj_first_host, ((size_t)E + 1) * 4, hipMemcpyHostToDevice, s));
   RAMP_HIP_CHECK(hipMemcpyAsync(c->e_state, ep->state_host, (size_t)E * sizeof(EpisodeState), hipMemcpyHostToDevice, s));
@@ -3028,13 +2866,13 @@ int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const 
   }
   if (rg) CK(stage_replan_guide(c, rg, s));
   c->launches = 0;
-  invalidate_calibrations(c, CAL_SCORE);
-  c->r_calibrated = false;                    // (the carried table now holds this batch's maxima)
+  invalidate_calibrations(c, CAL_SCORE);      // (the replans carry their maxima in TABLE_REPLAN_CARRY: the sampling jobs' canonical table survives)
+  if (c->replan_carry != who) c->replan_carry = ramp_ctx::REPLAN_NOBODY;      // (the other entry's maxima are not continued from)
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const EpisodeJob ej{E, P_static, P_cost};
   auto run = [&](bool calibrate) -> int {
-    if (!p->use_graph) return replan_body(c, p, s, calibrate, &ej, rg);
-    Key key;      // everything baked into the nodes: ramp_replan's fields, the episode count, the row table and the clouds' totals
+    if (!p->use_graph) return replan_body(c, p, s, calibrate, ej, rg);
+    Key key;      // everything baked into the nodes: the params' fields, the episode count, the row table and the clouds' totals
     key.put(p->B); key.put(p->n_steps); key.put(p->w); key.put(p->t, p->n_steps); key.put(p->sqrt_recip, p->n_steps);
     key.put(p->sqrt_recipm1, p->n_steps); key.put(p->sqrt_a_t, p->n_steps); key.put(p->sqrt_1m_a_t, p->n_steps);
     key.put(p->sqrt_a_prev, p->n_steps); key.put(p->dir_coef, p->n_steps); key.put(p->q_sqrt_a); key.put(p->q_sqrt_1m_a);
@@ -3043,32 +2881,37 @@ int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const 
     key.put(p->strength_static); key.put(p->strength_pred); key.put(p->window_static); key.put(p->n_extra);
     key.put(p->cost_thr); key.put(p->w_smooth); key.put(p->w_len); key.put(c->force_x6);
     key.put(E); key.put(ep->traj_first_host, (size_t)E + 1); key.put(P_static); key.put(P_cost);
+    key.put((int)who);      // (a one-episode call of the episode entry would replay the single entry's graph unharmed; each keeps capturing its own,
+                            // so that the launch count after a call says what it said when the two had a graph pair each)
     if (rg) key_replan_guide(key, rg, p->n_steps);
     if (key.bytes != c->e_key) { drop_graphs(c->e_graph, 2); c->e_key = key.bytes; }
-    return replay(&c->e_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, &ej, rg); });
+    return replay(&c->e_graph[(h3 && !calibrate) ? 1 : 0], s, [&](hipStream_t cs) { return replan_body(c, p, cs, calibrate, ej, rg); });
   };
-  CK(run(h3 && (!c->e_calibrated || p->n_steps == 1)));
-  // ---- the one read-back: E result records + the range flag
+  // a one-step replan has no second table to carry its maxima in (its only evaluation reads and clears TABLE_REPLAN_CARRY): it always
+  // calibrates, on the bf16x6 kernels, instead of running fp16x3 from an empty table
+  CK(run(h3 && (c->replan_carry != who || p->n_steps == 1)));
+  // ---- the one read-back: E result records {n_free, rank, row, 0} + the range flag
   std::vector<int> back((size_t)4 * E + 1, 0);
   RAMP_HIP_CHECK(hipMemcpyAsync(back.data(), c->e_result, (size_t)E * 16, hipMemcpyDeviceToHost, s));
   if (h3) RAMP_HIP_CHECK(hipMemcpyAsync(back.data() + 4 * E, c->range_flag, 4, hipMemcpyDeviceToHost, s));
   RAMP_HIP_CHECK(hipStreamSynchronize(s));
   result_host->fell_back = 0;
   if (h3 && back[4 * E]) {
-    // as in ramp_replan: the whole call again (same inputs) on the bf16x6 kernels, and the next one calibrates.  The flagged run left
-    // winners in e_best: back to the plans it started from first, which is what an episode that selects nothing keeps
+    // an operand left the range the delayed scaling assumed: the whole call again (same inputs) on the bf16x6 kernels, and the next one
+    // calibrates.  The flagged run left winners in e_best: back to the plans it started from first, which is what an episode that
+    // selects nothing keeps
     RAMP_HIP_CHECK(hipMemcpyAsync(c->e_best, c->e_xclean, nE * 4, hipMemcpyDeviceToDevice, s));
     c->force_x6 = 1;
-    int rc = replan_body(c, p, s, false, &ej, rg);
+    int rc = replan_body(c, p, s, false, ej, rg);
     c->force_x6 = 0;
     CK(rc);
     const int flag = back[4 * E];
     RAMP_HIP_CHECK(hipMemcpyAsync(back.data(), c->e_result, (size_t)E * 16, hipMemcpyDeviceToHost, s));
     RAMP_HIP_CHECK(hipStreamSynchronize(s));
-    c->e_calibrated = false;
+    c->replan_carry = ramp_ctx::REPLAN_NOBODY;
     result_host->fell_back = flag;
   } else if (h3) {
-    c->e_calibrated = true;
+    c->replan_carry = who;
   }
   int n_free = 0;
   for (int e = 0; e < E; ++e) if (back[4 * e] > 0) n_free += back[4 * e];
@@ -3079,6 +2922,90 @@ int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const 
   if (mask_out) RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->e_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
   if (rg && rg->tap_out) RAMP_HIP_CHECK(hipMemcpyAsync(rg->tap_out, c->rg_tap, 2 * n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
+}
+
+int ramp_replan(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_state* st, float* best_out, float* batch_out,
+                int32_t* mask_out, ramp_replan_result* result_host, void* stream) {
+  return ramp_replan_guided(c, p, st, nullptr, best_out, batch_out, mask_out, result_host, stream);
+}
+
+// the one-episode job: the table of `p` and `st` as a ramp_episode_batch on the stack, the result from record 0.  It runs on whatever row ->
+// latent table ramp_set_scene installed
+int ramp_replan_guided(ramp_ctx* c, const ramp_replan_params* p, const ramp_replan_state* st, const ramp_replan_guide* rg, float* best_out,
+                       float* batch_out, int32_t* mask_out, ramp_replan_result* result_host, void* stream) {
+  RAMP_REQUIRE(c && p && st && result_host, rg ? "ramp_replan_guided: null argument" : "null argument");
+  RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
+  const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
+  RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
+  RAMP_REQUIRE(p->t && p->sqrt_recip && p->sqrt_recipm1 && p->sqrt_a_t && p->sqrt_1m_a_t && p->sqrt_a_prev && p->dir_coef, "missing schedule arrays");
+  RAMP_REQUIRE(p->n_hard >= 0 && p->n_hard <= 16 && (p->n_hard == 0 || (p->hard_idx_host && p->hard_val)), "bad hard conditions");
+  RAMP_REQUIRE(p->static_pts && p->n_static > 0 && p->n_dyn > 0 && p->cost_cloud && p->n_cost > 0 && p->n_extra >= 0, "bad clouds");
+  RAMP_REQUIRE(st->noise && st->history && st->n_hist >= 1 && st->n_hist <= H && st->stepp >= 0 && st->stepp < H, "bad replan state");
+  RAMP_REQUIRE(st->dyn_pts_host && (st->near == 0 || p->n_extra == 0 || st->extra_pts_host), "missing pursuer points");
+  RAMP_REQUIRE(st->x_clean || c->replan_last == ramp_ctx::REPLAN_SINGLE, "no current plan: pass x_clean on the first replan");
+  for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
+  bool guided = false;
+  CK(check_replan_job_guide(c, p, rg, 1, "ramp_replan_guided", &guided));
+  if (!guided) rg = nullptr;
+  const int32_t traj_first[2] = {0, B}, static_off[2] = {0, p->n_static}, cost_off[2] = {0, p->n_cost}, near = st->near;
+  ramp_episode_state es{}; es.n_hist = st->n_hist; es.stepp = st->stepp; es.active = 1; es.pursuer[0] = st->pursuer[0]; es.pursuer[1] = st->pursuer[1];
+  ramp_episode_batch ep{};
+  ep.n_episodes = 1; ep.traj_first_host = traj_first; ep.noise = st->noise; ep.x_clean = st->x_clean; ep.history = st->history; ep.state_host = &es;
+  ep.static_pts = p->static_pts; ep.static_offset_host = static_off; ep.dyn_pts_host = st->dyn_pts_host;
+  ep.cost_cloud = p->cost_cloud; ep.cost_offset_host = cost_off; ep.near_host = &near; ep.extra_pts_host = st->extra_pts_host;
+  int32_t record[4];
+  CK(replan_job(c, p, &ep, rg, ramp_ctx::REPLAN_SINGLE, p->n_static, p->n_cost, (size_t)st->n_hist * S, best_out, batch_out, mask_out, record,
+                result_host, as_stream(stream)));
+  result_host->n_free = record[0]; result_host->best_rank = record[1]; result_host->best_row = record[2];
+  return 0;
+}
+
+// (E + 1) first-entry table of host memory: [0] = 0, strictly increasing; returns the total through *total
+static int check_offsets(const int32_t* off, int E, const char* what, int* total) {
+  RAMP_REQUIRE(off && off[0] == 0, std::string(what) + ": the offset table must start at 0");
+  for (int e = 0; e < E; ++e) RAMP_REQUIRE(off[e + 1] > off[e], std::string(what) + ": the offset table must be strictly increasing");
+  *total = off[E];
+  return 0;
+}
+
+int ramp_replan_episodes(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, float* best_out, float* batch_out,
+                         int32_t* mask_out, int32_t* results_host, ramp_replan_result* result_host, void* stream) {
+  return ramp_replan_episodes_guided(c, p, ep, nullptr, best_out, batch_out, mask_out, results_host, result_host, stream);
+}
+
+int ramp_replan_episodes_guided(ramp_ctx* c, const ramp_replan_params* p, const ramp_episode_batch* ep, const ramp_replan_guide* rg,
+                                float* best_out, float* batch_out, int32_t* mask_out, int32_t* results_host,
+                                ramp_replan_result* result_host, void* stream) {
+  RAMP_REQUIRE(c && p && ep && results_host && result_host, rg ? "ramp_replan_episodes_guided: null argument" : "null argument");
+  RAMP_REQUIRE(c->finalized && c->cross_bias, "context not ready (weights / scene)");
+  const int B = p->B, E = ep->n_episodes, H = c->cfg.horizon;
+  RAMP_REQUIRE(B > 0 && p->n_rp == 2 && p->n_steps >= 1 && p->n_steps <= 64, "bad replan dims");
+  RAMP_REQUIRE(E >= 1 && E <= B && E <= 65536, "bad episode count (1 .. min(B, 65536))");
+  RAMP_REQUIRE(c->rv_rows >= B * p->n_rp, "the row -> latent table of a many-episode replan comes from ramp_set_scenes (B * n_rp rows)");
+  RAMP_REQUIRE(p->t && p->sqrt_recip && p->sqrt_recipm1 && p->sqrt_a_t && p->sqrt_1m_a_t && p->sqrt_a_prev && p->dir_coef, "missing schedule arrays");
+  RAMP_REQUIRE(p->n_hard >= 0 && p->n_hard <= 16 && (p->n_hard == 0 || (p->hard_idx_host && p->hard_val)), "bad hard conditions");
+  RAMP_REQUIRE(p->n_dyn > 0 && p->n_extra >= 0 && p->n_dyn <= (1 << 20) && p->n_extra <= (1 << 20), "bad clouds");
+  RAMP_REQUIRE(ep->noise && ep->history && ep->state_host && ep->static_pts && ep->dyn_pts_host && ep->cost_cloud && ep->near_host, "missing episode inputs");
+  int n_rows = 0, P_static = 0, n_cost = 0;
+  CK(check_offsets(ep->traj_first_host, E, "traj_first", &n_rows));
+  RAMP_REQUIRE(n_rows == B, "traj_first must end at the batch size");
+  CK(check_offsets(ep->static_offset_host, E, "static clouds", &P_static));
+  CK(check_offsets(ep->cost_offset_host, E, "cost clouds", &n_cost));
+  RAMP_REQUIRE((long)n_cost + (long)E * p->n_extra < (1l << 31) && (long)E * p->n_dyn < (1l << 30), "the concatenated clouds do not fit 32-bit offsets");
+  bool any_near = false;
+  for (int e = 0; e < E; ++e) {
+    const ramp_episode_state& st = ep->state_host[e];
+    RAMP_REQUIRE(st.n_hist >= 1 && st.n_hist <= H && st.stepp >= 0 && st.stepp < H, "bad episode state");
+    any_near |= ep->near_host[e] != 0;
+  }
+  RAMP_REQUIRE(!any_near || p->n_extra == 0 || ep->extra_pts_host, "missing pursuer points");
+  RAMP_REQUIRE(ep->x_clean || (c->replan_last == ramp_ctx::REPLAN_EPISODES && c->e_best_E == E), "no current plans: pass x_clean on the first call");
+  for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
+  bool guided = false;
+  CK(check_replan_job_guide(c, p, rg, E, "ramp_replan_episodes_guided", &guided));
+  if (!guided) rg = nullptr;
+  return replan_job(c, p, ep, rg, ramp_ctx::REPLAN_EPISODES, P_static, n_cost, (size_t)E * H * c->cfg.state_dim, best_out, batch_out, mask_out,
+                    results_host, result_host, as_stream(stream));
 }
 
 /* compute_trajectory_costs + the winner (cost.py:56-88) for a finished batch, e.g. the high-level plan */
@@ -3098,11 +3025,11 @@ int ramp_select_from_costs(const int32_t* mask, const float* path_len, const flo
 }
 
 int ramp_replan_costs(ramp_ctx* c, int32_t B, int32_t* mask_out, float* path_len_out, float* smooth_out, void* stream) {
-  RAMP_REQUIRE(c && c->r_mask && mask_out && path_len_out && smooth_out && B > 0 && (size_t)B <= c->r_cap_B, "no replan of this size has run on the context");
+  RAMP_REQUIRE(c && c->e_mask && mask_out && path_len_out && smooth_out && B > 0 && (size_t)B <= c->e_cap_B, "no replan of this size has run on the context");
   hipStream_t s = as_stream(stream);
-  RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->r_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(path_len_out, c->r_plen, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-  RAMP_HIP_CHECK(hipMemcpyAsync(smooth_out, c->r_smooth, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(mask_out, c->e_mask, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(path_len_out, c->e_plen, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipMemcpyAsync(smooth_out, c->e_smooth, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 

@@ -42,7 +42,7 @@ __global__ __launch_bounds__(256) void guide_step_moving_kernel(MovingGuideArgs 
   if (!guide_scene(a, 2, b, &sp)) return;
   const int e = sp.sc;
   if (a.est && a.est[e].active == 0) return;                     // an ended episode's rows stay as they are (uniform over the block)
-  const int n_first = a.pin_first ? a.pin_first[b] : a.est ? a.est[e].n_hist : a.rst ? a.rst->n_hist : 0;
+  const int n_first = a.pin_first ? a.pin_first[b] : a.est ? a.est[e].n_hist : 0;
   float* tr = a.traj + (size_t)b * H * S;
   const bool obs = a.w_obs != 0.f && sp.P > 0, mov = a.w_mov != 0.f && a.n_mov > 0;
   if (tid < H) {

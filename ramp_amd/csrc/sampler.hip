@@ -308,9 +308,9 @@ int launch_apf(const ApfArgs& a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------
 // x = q_sample(repeat(x_clean), t) = sqrt_ac[t] * x_clean + sqrt_1m_ac[t] * noise (diffusion_model_dynamic.py:671-680),
 // then x[:, 0, 2:] = 0, the executed history, and the goal waypoint of the clean plan (:540-546).
-// Each of the four steps below is ONE per-row rule (replan_*_row) behind two kernels: the single-episode one, whose rows all read
-// the same record / history / clean plan, and the many-episode one (ramp_replan_episodes), whose row b reads those of episode
-// row_ep[b].  x_clean, hist: the (H,S) blocks of the row's own episode.
+// Each of the four steps below is a per-row rule (replan_*_row) and its kernel over a batch of episodes: row b reads the record,
+// history and clean plan of episode row_ep[b] (ramp_replan's single episode: every row reads episode 0's).  x_clean, hist: the (H,S)
+// blocks of the row's own episode.
 __device__ __forceinline__ float replan_init_value(const float* __restrict__ x_clean, const float* __restrict__ hist, float nz,
                                                    float sa, float s1a, int n_hist, int h, int si, int H, int S) {
   float v = add(mul(sa, x_clean[h * S + si]), mul(s1a, nz));
@@ -318,17 +318,6 @@ __device__ __forceinline__ float replan_init_value(const float* __restrict__ x_c
   if (h < n_hist) v = hist[h * S + si];
   if (h == H - 1) v = x_clean[h * S + si];
   return v;
-}
-__global__ __launch_bounds__(256) void replan_init_kernel(float* __restrict__ x, const float* __restrict__ x_clean,
-                                                           const float* __restrict__ noise, float sa, float s1a,
-                                                           const float* __restrict__ hist, const ReplanState* __restrict__ st,
-                                                           int B, int H, int S) {
-  const int n_hist = st->n_hist;
-  const long n = (long)B * H * S;
-  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (long)gridDim.x * 256) {
-    const int si = (int)(idx % S); const int h = (int)((idx / S) % H);
-    x[idx] = replan_init_value(x_clean, hist, noise[idx], sa, s1a, n_hist, h, si, H, S);
-  }
 }
 __global__ __launch_bounds__(256) void replan_init_episodes_kernel(float* __restrict__ x, const float* __restrict__ x_clean,
                                                                     const float* __restrict__ noise, float sa, float s1a,
@@ -348,15 +337,6 @@ __device__ __forceinline__ void replan_pin_row(float* __restrict__ xb, const Har
   for (int h = 0; h < n_hist; ++h) xb[h * S + si] = hist[h * S + si];
   xb[(H - 1) * S + si] = x_clean[(H - 1) * S + si];
   if (si >= 2) xb[si] = 0.f;
-}
-__global__ __launch_bounds__(256) void replan_pin_kernel(float* __restrict__ x, HardConds hc, const float* __restrict__ hist,
-                                                          const float* __restrict__ x_clean, const ReplanState* __restrict__ st,
-                                                          int B, int H, int S) {
-  const int n_hist = st->n_hist;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= B * S) return;
-  const int b = idx / S, si = idx - b * S;
-  replan_pin_row(x + (long)b * H * S, hc, hist, x_clean, n_hist, b, si, B, H, S);
 }
 __global__ __launch_bounds__(256) void replan_pin_episodes_kernel(float* __restrict__ x, HardConds hc, const float* __restrict__ hist,
                                                                    const float* __restrict__ x_clean, EpisodeTable ep, int B, int H, int S) {
@@ -386,12 +366,6 @@ __device__ __forceinline__ void replan_sm_row(float* __restrict__ xb, int stepp,
     o[2] = vx; o[3] = vy;
   }
 }
-__global__ __launch_bounds__(256) void replan_sm_kernel(float* __restrict__ x, const ReplanState* __restrict__ st, int window,
-                                                         float dt, float max_vel, int B, int H, int S) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  replan_sm_row(x + (long)b * H * S, st->stepp, window, dt, max_vel, H, S);
-}
 __global__ __launch_bounds__(256) void replan_sm_episodes_kernel(float* __restrict__ x, EpisodeTable ep, int window, float dt,
                                                                   float max_vel, int B, int H, int S) {
   const int b = blockIdx.x * 256 + threadIdx.x;
@@ -403,12 +377,6 @@ __global__ __launch_bounds__(256) void replan_sm_episodes_kernel(float* __restri
 __device__ __forceinline__ int replan_near_row(const float* __restrict__ q, const float* __restrict__ pursuer, float thr) {
   const float dx = sub(q[0], pursuer[0]), dy = sub(q[1], pursuer[1]);
   return sqrtf(add(mul(dx, dx), mul(dy, dy))) < thr;
-}
-__global__ __launch_bounds__(256) void replan_near_kernel(const float* __restrict__ x, const ReplanState* __restrict__ st,
-                                                           float thr, int* __restrict__ en, int B, int H, int S) {
-  const int b = blockIdx.x * 256 + threadIdx.x;
-  if (b >= B) return;
-  en[b] = replan_near_row(x + ((long)b * H + st->stepp) * S, st->pursuer, thr);
 }
 __global__ __launch_bounds__(256) void replan_near_episodes_kernel(const float* __restrict__ x, EpisodeTable ep, float thr,
                                                                     int* __restrict__ en, int B, int H, int S) {
@@ -676,29 +644,6 @@ int launch_select_diverse(const DiverseArgs& a, hipStream_t s) {
   return 0;
 }
 
-int launch_replan_init(float* x, const float* x_clean, const float* noise, float sa, float s1a, const float* hist,
-                       const ReplanState* st, int B, int H, int S, hipStream_t s) {
-  hipLaunchKernelGGL(replan_init_kernel, dim3(ew_grid((long)B * H * S)), dim3(256), 0, s, x, x_clean, noise, sa, s1a, hist, st, B, H, S);
-  RAMP_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-int launch_replan_pin(float* x, HardConds hc, const float* hist, const float* x_clean, const ReplanState* st, int B, int H,
-                      int S, hipStream_t s) {
-  hipLaunchKernelGGL(replan_pin_kernel, dim3((B * S + 255) / 256), dim3(256), 0, s, x, hc, hist, x_clean, st, B, H, S);
-  RAMP_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-int launch_replan_sm(float* x, const ReplanState* st, int window, float dt, float max_vel, int B, int H, int S, hipStream_t s) {
-  RAMP_REQUIRE(S >= 4 && window >= 1, "sm needs (x, y, vx, vy) states");
-  hipLaunchKernelGGL(replan_sm_kernel, dim3((B + 255) / 256), dim3(256), 0, s, x, st, window, dt, max_vel, B, H, S);
-  RAMP_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-int launch_replan_near(const float* x, const ReplanState* st, float thr, int* en, int B, int H, int S, hipStream_t s) {
-  hipLaunchKernelGGL(replan_near_kernel, dim3((B + 255) / 256), dim3(256), 0, s, x, st, thr, en, B, H, S);
-  RAMP_HIP_CHECK(hipGetLastError());
-  return 0;
-}
 static int check_episode_table(const EpisodeTable& ep, int B) {
   RAMP_REQUIRE(ep.st && ep.row_ep && ep.n_episodes > 0 && ep.n_episodes <= B, "bad episode table");
   return 0;

@@ -239,7 +239,7 @@ def test_graphs_survive_buffer_growth():
 
 
 def test_replan_graphs_survive_buffer_growth():
-    """The one case in which a captured graph's KEY outlives a move of the buffers its nodes point at: the replan graphs (r_key: the
+    """The one case in which a captured graph's KEY outlives a move of the buffers its nodes point at: the replan graphs (e_key: the
     replan's own parameters) read s_x, s_eps and s_x0, which a larger SAMPLING job on the same context reallocates.  The reference
     planner run of replan_chain.npz (B = 6: one ramp_sample + one captured ramp_replan graph per replan), then a B = 12 sampling job
     on the same context -- same cloud and row pattern, so no scene change drops anything -- then the same planner run again.  Without
