@@ -242,9 +242,7 @@ void ffx_kernel(FfxArgs f, int n_mt) {
         xv[2 * s + 1] = *reinterpret_cast<const f32x4*>(xrow + 16 * s + 4);
       }
       if (!BWD) {
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) sum += (xv[i][0] + xv[i][1]) + (xv[i][2] + xv[i][3]);
+        float sum = tree_sum4(xv);                          // (a constant row's mean is exact: tokmma.h)
         sum += __shfl_xor(sum, 32);
         const float mean = sum * (1.f / 256.f);
         float ss = 0.f;

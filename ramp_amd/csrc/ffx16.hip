@@ -284,12 +284,7 @@ __device__ __forceinline__ void ffx16_body(const FfxArgs& f, int n_mt) {
       if (!BWD) {
         float sum[NT], ss[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-          float a = 0.f;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) a += (xv[t][i][0] + xv[t][i][1]) + (xv[t][i][2] + xv[t][i][3]);
-          sum[t] = a;
-        }
+        for (int t = 0; t < NT; ++t) sum[t] = tree_sum4(xv[t]);      // (a constant row's mean is exact: tokmma.h)
 #pragma unroll
         for (int t = 0; t < NT; ++t) sum[t] = gsum(sum[t]);
 #pragma unroll

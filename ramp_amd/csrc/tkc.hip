@@ -134,9 +134,11 @@ void tkc_kernel(TkcArgs a, int n_tiles) {
     tc_wave_sync();
     if (lane < 8 * n_smp) {                                 // one lane per (group, sample): the sample's L tokens
       const int grp = lane / n_smp, sm = lane - grp * n_smp;
-      float q = 0.f;
-      for (int u = 0; u < a.L; ++u) q += wscr[grp * T + sm * a.L + u];
-      wscr[8 * T + lane] = q / (float)(a.L * gsz);
+      // (in double: the L per-token sums add exactly and the mean is rounded once, so a (sample, group) of equal values -- a flat sample's
+      // stash is its bias -- has exactly that value as its mean; a float running sum is several ulp off, which rstd = eps^-1/2 multiplies by 300)
+      double q = 0.0;
+      for (int u = 0; u < a.L; ++u) q += (double)wscr[grp * T + sm * a.L + u];
+      wscr[8 * T + lane] = (float)(q / (double)(a.L * gsz));
     }
     tc_wave_sync();
 #pragma unroll

@@ -165,9 +165,7 @@ void tkl_kernel(TklArgs a, int n_mt) {
     // ---- the wave's 32 tokens -> B-operand planes (through LayerNorm) --------------------------------------------------------
     {
       if (LN) {
-        float sum = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) sum += (xn[i][0] + xn[i][1]) + (xn[i][2] + xn[i][3]);
+        float sum = tree_sum4(xn);                          // (a constant row's mean is exact: tokmma.h)
         sum += __shfl_xor(sum, 32);
         const float mean = sum * (1.f / 256.f);
         float ss = 0.f;

@@ -178,12 +178,7 @@ void tkl16_kernel(TklArgs a, int n_mt) {
       if (LN) {
         float sum[2], ss[2];
 #pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          float v = 0.f;
-#pragma unroll
-          for (int i = 0; i < 16; ++i) v += (xn[t][i][0] + xn[t][i][1]) + (xn[t][i][2] + xn[t][i][3]);
-          sum[t] = v;
-        }
+        for (int t = 0; t < 2; ++t) sum[t] = tree_sum4(xn[t]);      // (a constant row's mean is exact: tokmma.h)
         sum[0] = gsum(sum[0]); sum[1] = gsum(sum[1]);
         const float mean0 = sum[0] * (1.f / 256.f), mean1 = sum[1] * (1.f / 256.f);
 #pragma unroll

@@ -341,7 +341,7 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
         const int poff = EPI == 2 ? pass * 256 : 0;          // first channel of the pass = prm's channel 0
         const int gsz = a.N >> 3;                            // channels of a group: 32 (MB = 2) or 16 (MB = 1)
         const int n_smp = TW_TB / a.L;
-        const float inv_cnt = 1.f / (float)(a.L * gsz);
+        const double inv_cnt = 1.0 / (double)(a.L * gsz);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -372,22 +372,27 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
           for (int gi = 0; gi < NGW; ++gi)
 #pragma unroll
             for (int tg = 0; tg < TW_NT; ++tg) {
+              // (the mean's sums exact on equal values, here and -- in double -- over the sample's tokens below: a (sample, group) of equal values -- a
+              // flat sample's stash is its bias -- then has exactly that value as its mean; running float sums are several ulp off, which
+              // rstd = eps^-1/2 multiplies by 300.  The variance keeps its running sum: about an exact mean its terms are exact zeros there.)
+              constexpr int NS = EPI == 2 ? 16 * MB : (MB == 2 ? 16 : 8);
               float s = 0.f;
-              if constexpr (EPI == 2) {
+              if (rnd == 0 && EPI == 2) {                   // (in double, not as a tree of 32 temporaries: the 512-channel epilogue has no registers to spare)
+                double sd = 0.0;
 #pragma unroll
-                for (int mb = 0; mb < MB; ++mb)
+                for (int i = 0; i < NS; ++i) sd += (double)acc[i >> 4][tg][i & 15];
+                s = (float)sd;
+              } else if (rnd == 0) {                        // (a balanced tree, tokmma.h: exact on equal values like the double sum, and no slower than the running sum was)
+                float p[NS];
 #pragma unroll
-                  for (int i = 0; i < 16; ++i) {
-                    const float d = rnd == 0 ? acc[mb][tg][i] : acc[mb][tg][i] - mean_t[gi][tg];
-                    s += rnd == 0 ? d : d * d;
-                  }
+                for (int i = 0; i < NS; ++i) p[i] = MB == 2 ? acc[gi][tg][i] : acc[0][tg][8 * gi + i];
+                s = tree_sum(p);
               } else {
 #pragma unroll
-              for (int i = 0; i < (MB == 2 ? 16 : 8); ++i) {
-                const float c = MB == 2 ? acc[gi][tg][i] : acc[0][tg][8 * gi + i];
-                const float d = rnd == 0 ? c : c - mean_t[gi][tg];
-                s += rnd == 0 ? d : d * d;
-              }
+                for (int i = 0; i < NS; ++i) {
+                  const float d = (EPI == 2 ? acc[i >> 4][tg][i & 15] : (MB == 2 ? acc[gi][tg][i] : acc[0][tg][8 * gi + i])) - mean_t[gi][tg];
+                  s += d * d;
+                }
               }
               s += __shfl_xor(s, 32);
               if (kh == 0) wscr[gi * TW_TB + 32 * tg + tok] = s;      // per-token sums of the group
@@ -395,9 +400,9 @@ __device__ __forceinline__ void tkw_body(const TkwArgs& a, int n_tiles, int kc32
           tw_wave_sync();
           if (lane < NGW * n_smp) {                         // one lane per (group, sample): the sample's L tokens
             const int gi = lane / n_smp, sm = lane - gi * n_smp;
-            float s = 0.f;
-            for (int u = 0; u < a.L; ++u) s += wscr[gi * TW_TB + sm * a.L + u];
-            s *= inv_cnt;
+            double sd = 0.0;
+            for (int u = 0; u < a.L; ++u) sd += (double)wscr[gi * TW_TB + sm * a.L + u];
+            const float s = (float)(sd * inv_cnt);          // (1 / count to 2^-53: the product of an exact sum rounds to the exact mean)
             wscr[192 + lane] = s;
             if (rnd == 0) my_mean = s; else my_var = s;
           }

@@ -76,6 +76,32 @@ __device__ __forceinline__ void split4(const f32x4 a, unsigned& h0, unsigned& h1
   h0 = __builtin_bit_cast(unsigned, x0); h1 = __builtin_bit_cast(unsigned, x1);
   l0 = __builtin_bit_cast(unsigned, y0); l1 = __builtin_bit_cast(unsigned, y1);
 }
+// Sum of the N float4 registers a lane holds of a row (N a power of two), as a balanced tree: as many additions as a running sum, but a
+// row of equal values sums EXACTLY (every node doubles its operand; the cross-lane steps behind it are butterflies and double
+// too), so LayerNorm's mean of a constant row is the row's value and x - mean is 0.  A running sum rounds from its third term on: 2 ulp
+// of the mean of a row of 0.7, which rstd = eps^-1/2 turns into 4e-5 of every normalised element, all with one sign.
+template <int N>
+__device__ __forceinline__ float tree_sum4(const f32x4 (&x)[N]) {
+  static_assert((N & (N - 1)) == 0, "a power of two");
+  float p[N];
+#pragma unroll
+  for (int i = 0; i < N; ++i) p[i] = (x[i][0] + x[i][1]) + (x[i][2] + x[i][3]);
+#pragma unroll
+  for (int w = N / 2; w > 0; w >>= 1)
+#pragma unroll
+    for (int i = 0; i < w; ++i) p[i] += p[i + w];
+  return p[0];
+}
+// The same for N plain values (overwritten).
+template <int N>
+__device__ __forceinline__ float tree_sum(float (&p)[N]) {
+  static_assert((N & (N - 1)) == 0, "a power of two");
+#pragma unroll
+  for (int w = N / 2; w > 0; w >>= 1)
+#pragma unroll
+    for (int i = 0; i < w; ++i) p[i] += p[i + w];
+  return p[0];
+}
 __device__ __forceinline__ float amax4(const f32x4 v, float m) {
   m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), m);
   return fmaxf(fmaxf(fabsf(v[2]), fabsf(v[3])), m);
