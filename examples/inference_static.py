@@ -21,6 +21,13 @@ state-dict keys -- and then runs the experiment on it, exactly as it would on th
 
     python examples/inference_static.py --make-synthetic /tmp/ramp_exp --n-samples 64
     python examples/inference_static.py --dataset-path /data/ramp --dataset-subdir EnvSimple2D --model-id my_run --env 3
+
+Not the reference's: ``--agents A --team-sep d`` plans for TEAMS of A robots per experiment (``ramp_amd.team``): every experiment directory
+is a scene, ``--n-samples`` counts teams, the A start / goal pairs are the context's pair turned about its midpoint (their straight lines
+cross), the robots are coupled through the separation term of the cost guide, and the best conflict-free team is picked.  The run reports,
+per scene, the free teams and the winner's swept separation, next to the same figures of the job without the team term.
+
+    python examples/inference_static.py --make-synthetic /tmp/ramp_exp --n-samples 16 --agents 2 --team-sep 0.1
 """
 from __future__ import annotations
 
@@ -72,6 +79,11 @@ class StaticConfig:
     sampler = None           # None = the reference's hard-coded default (DDIM-5); 'ddpm' for the full chain
     alternatives = 0         # not the reference's: K > 0 stores K distinct plans per experiment next to best_trajectory (--all-envs)
     min_sep = 0.1            # the mean waypoint distance two of them keep from each other
+    agents = 0               # not the reference's: A > 1 plans for teams of A robots per experiment (--agents)
+    team_sep = 0.1           # the separation two robots of a team must keep (--team-sep)
+    team_radius = None       # the radius of the guide's separation term; default 1.5 team_sep
+    team_guide = dict(radius=0.1, step=0.05, w_obs=1.0, w_smooth=2.0, n_steps=16, max_norm=2.0)  # the cost guide the team term travels with
+    team_guide_fraction = 1.0   # the guide runs on the iterations with t < this fraction of the diffusion steps
 
 
 def make_synthetic_experiment(root: str, cfg: StaticConfig, n_obstacles: int = 6, n_points: int = 64, seed: int = 42) -> None:
@@ -213,6 +225,75 @@ class StaticInference:
         return out
 
 
+    @staticmethod
+    def team_endpoints(start, goal, agents: int):
+        """(starts (A, 2), goals (A, 2)): the context's pair turned about its midpoint by a pi / A, so that the A straight lines cross there."""
+        start, goal = start.reshape(-1)[:2].cpu().double(), goal.reshape(-1)[:2].cpu().double()
+        mid, half = (start + goal) / 2, (goal - start) / 2
+        starts, goals = [], []
+        for a in range(agents):
+            c, sn = np.cos(np.pi * a / agents), np.sin(np.pi * a / agents)
+            v = torch.stack([c * half[0] - sn * half[1], sn * half[0] + c * half[1]])
+            starts.append(mid - v); goals.append(mid + v)
+        return torch.stack(starts).float(), torch.stack(goals).float()
+
+    def run_team_experiments(self, context_idx: int):
+        """Opt-in (--agents A): teams of A robots in every experiment directory of the tree, as ONE job (``team.run_inference_teams``), once
+        with the separation term and once without it (same seed).  Returns one dict per experiment: the free teams, the winner's team and
+        its swept separation, the smallest swept separation over the scene's teams -- and the same under ``without_team_term``."""
+        from ramp_amd import team
+        from ramp_amd.clearance import trajectory_clearance
+        cfg = self.config
+        if cfg.compose or cfg.state_dim != 4:
+            raise ValueError("--agents plans 2-D point robots without compose")
+        torch.cuda.set_device(0)
+        A = cfg.agents
+        base = os.path.join(cfg.dataset_path, cfg.dataset_subdir)
+        dirs = sorted((d for d in os.listdir(base) if d.isdigit()), key=int)
+        datas = [compat.load_environment_dir(os.path.join(base, d)) for d in dirs]
+        H = cfg.n_support_points
+        diffusion_configs = dict(variance_schedule=cfg.variance_schedule, n_diffusion_steps=cfg.n_diffusion_steps,
+                                 predict_epsilon=cfg.predict_epsilon, compose=False, use_apf=cfg.use_apf)
+        if cfg.sampler is not None:
+            diffusion_configs['sampler'] = cfg.sampler
+        unet_configs = dict(state_dim=cfg.state_dim, n_support_points=H, unet_input_dim=cfg.unet_input_dim,
+                            dim_mults=UNET_DIM_MULTS[cfg.unet_dim_mults_option])
+        self.model = get_model(model_class=cfg.diffusion_model_class,
+                               model=TemporalUnetInference(max_rows=2 * cfg.n_samples * A * len(dirs), **unet_configs),
+                               tensor_args=self.tensor_args, **diffusion_configs, **unet_configs)
+        compat.load_checkpoint(self.model, cfg.trained_models_dir, cfg.model_id, use_ema=cfg.use_ema, device="cpu")
+        self.model.eval()
+        starts, goals = [], []
+        for d in dirs:
+            start, goal = self.context_manager.load_context(os.path.join(base, d, 'contexts'), context_idx, self.device)
+            s2, g2 = self.team_endpoints(start, goal, A)
+            starts.append(torch.cat([s2, torch.zeros(A, cfg.state_dim - 2)], 1)); goals.append(torch.cat([g2, torch.zeros(A, cfg.state_dim - 2)], 1))
+        clouds = [d['obstacle_points'].reshape(-1, 2) for d in datas]
+        r_t = cfg.team_radius if cfg.team_radius is not None else 1.5 * cfg.team_sep
+        counts = [cfg.n_samples * A] * len(dirs)
+        out = [dict(env=int(d), agents=A, team_sep=cfg.team_sep, team_radius=r_t) for d in dirs]
+        for name, w in (("with_team_term", 1.0), ("without_team_term", 0.0)):
+            guide = dict(cfg.team_guide, clouds=clouds, t_start=ceil(cfg.team_guide_fraction * self.model.n_diffusion_steps),
+                         team=dict(size=A, radius=r_t, w=w))
+            torch.manual_seed(0)
+            teams, team_first = team.run_inference_teams(self.model, [d['obstacle_points'] for d in datas], starts, goals, cfg.n_samples, guide,
+                                                         horizon=H, sample_fn=ddpm_sample_fn, noise_std_extra_schedule_fn=lambda x: 0.5,
+                                                         n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise)
+            rows = teams.reshape(-1, H, cfg.state_dim)
+            r = trajectory_clearance(rows, clouds=clouds, counts=counts, point_dim=2, swept=False)
+            tc = team.team_clearance(rows, A, cfg.team_sep, 2, True, r.colliding(0.0, 0.0, swept=False), r.path_length, r.smoothness)
+            winners, res = cost.select_best_teams_scenes(rows, A, team_first, tc['team_mask'], tc['team_len'], tc['team_smooth'])
+            res, sep = res.cpu().numpy(), tc['sep_seg'].cpu().numpy()
+            for i, m in enumerate(out):
+                mine = sep[team_first[i]:team_first[i + 1]]
+                m[name] = dict(n_teams=int(len(mine)), free_teams=int(res[i, 0]), winner=int(res[i, 2]),
+                               winner_sep_seg=float(sep[res[i, 2]]) if res[i, 2] >= 0 else None, min_sep_seg=float(np.nanmin(mine)))
+                if w:
+                    m['best_team'] = winners[i]
+        self.last_trajectories = teams
+        return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--make-synthetic", metavar="DIR", help="write a synthetic experiment tree (reference layout) to DIR and run on it")
@@ -230,11 +311,17 @@ def main(argv=None):
     ap.add_argument("--alternatives", type=int, default=0, metavar="K",
                     help="with --all-envs: K plans per experiment that are pairwise at least --min-sep apart, next to best_trajectory")
     ap.add_argument("--min-sep", type=float, default=0.1, help="mean waypoint distance two of the --alternatives keep from each other")
+    ap.add_argument("--agents", type=int, default=0, metavar="A", help="plan for teams of A robots (2 .. 8) per experiment; --n-samples counts teams")
+    ap.add_argument("--team-sep", type=float, default=StaticConfig.team_sep, help="the separation two robots of a team must keep")
+    ap.add_argument("--team-radius", type=float, default=None, help="radius of the guide's separation term (default 1.5 x --team-sep)")
     args = ap.parse_args(argv)
+    if args.agents and not 2 <= args.agents <= 8:
+        ap.error("--agents takes 2 .. 8")
     if args.alternatives and not args.all_envs:
         ap.error("--alternatives goes with --all-envs")
     cfg = StaticConfig()
     cfg.alternatives, cfg.min_sep = args.alternatives, args.min_sep
+    cfg.agents, cfg.team_sep, cfg.team_radius = args.agents, args.team_sep, args.team_radius
     cfg.n_samples, cfg.n_diffusion_steps, cfg.sampler, cfg.use_apf = args.n_samples, args.n_diffusion_steps, args.sampler, args.use_apf
     cfg.dataset_subdir, cfg.model_id = args.dataset_subdir, args.model_id
     cfg.n_diffusion_steps_without_noise = args.n_steps_without_noise
@@ -248,6 +335,11 @@ def main(argv=None):
             ap.error("--dataset-path and --trained-models-dir (or --make-synthetic DIR) are required")
         cfg.dataset_path, cfg.trained_models_dir = args.dataset_path, args.trained_models_dir
     runner = StaticInference(cfg)
+    if args.agents:
+        per_env = runner.run_team_experiments(args.context)
+        for m in per_env:
+            print(json.dumps({k: v for k, v in m.items() if not torch.is_tensor(v)}))
+        return per_env, runner
     if args.all_envs:
         per_env = runner.run_all_experiments(args.context)
         for m in per_env:

@@ -433,6 +433,70 @@ int ramp_guide_step_prims(float* traj, int32_t B, int32_t H, int32_t S, const ra
  * index outside the table).  Refusals as above, with "ramp_guide_cost_prims".  Synchronises `stream`. */
 int ramp_guide_cost_prims(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_prim_guide* pg,
                           const int32_t* traj_scene, double* terms_out, void* stream);
+/* ---- teams of robots in one job: separation guide, swept check, selection ----
+ * Every row of a sampling job is one robot alone in its scene.  Several robots that share a scene are sampled in one batch with the
+ * single-robot model and coupled only through a separation cost inside the guide (how multi-robot diffusion planners compose single-robot
+ * models); the joint plan is then checked for conflicts and the best conflict-free team is picked.
+ * Layout.  A job of B rows with team size A: 1 <= A <= RAMP_TEAM_MAX, B % A == 0, row b is agent b % A of team b / A; a team's rows are
+ * adjacent and belong to one scene.  D = point_dim, p_{a,h} = x[row a, h, 0:D]; the same h means the same time for every agent.
+ *   Team term  C_team = sum_{a<a'} sum_h 1/2 max(0, r_t - |p_{a,h} - p_{a',h}|)^2, r_t = radius_team > 0.
+ *              g_team[a][h] = dC_team/dp_{a,h} with exactly the arithmetic of the cloud term, the teammate's waypoint in the place of a cloud
+ *              point: fp32 dx, d2 in coordinate order, the filter d2 < (r_t r_t) 1.00001f in front of the cloud term's square root, the
+ *              test d < r_t && d > 0, f = (r_t - d) / d correctly rounded, sum_c -= f dx_c; teammates in ascending a', skipping a, added
+ *              serially in fp32.  A pair at distance 0 contributes cost and no gradient.
+ *   Iteration  Jacobi: every agent's gradient is taken from the positions all agents had at the start of the iteration, then all agents
+ *              move.  Per agent the step is ramp_cost_guide's six steps with g = w_obs g_obs + (w_team g_team + (w_smooth g_s + w_acc g_a));
+ *              the norm, the clip and the step are taken per agent trajectory, not per team.  A pinned waypoint holds its conditioned value
+ *              and pushes on its teammates; it receives no gradient and its memory is not written.  Channels >= D keep their bits.  Each
+ *              agent's cloud term reads the cloud of that row's own scene.  A team in which any row's scene index lies outside the table is
+ *              left unchanged as a whole.
+ * With team_size == 1, w_team == 0 or tg == NULL the result is ramp_guide_step / ramp_sample_guided, bit for bit (the same kernel is
+ * launched).  A team's result does not depend on the rest of the batch.  team_size, radius_team and w_team are kernel arguments and part of
+ * the graph key; the team term draws no random numbers, the Philox layout is unchanged (a shard must hold whole teams: philox_sample0 % A
+ * == 0). */
+#define RAMP_TEAM_MAX 8
+typedef struct ramp_team_guide {
+  int32_t team_size;                 /* A, 1 .. RAMP_TEAM_MAX, a divisor of B */
+  int32_t reserved;
+  double radius_team, w_team;        /* r_t > 0 and finite where w_team != 0; w_team finite */
+} ramp_team_guide;
+/* ramp_sample_guided with the team term: plain, many-scene, composed and MCMC jobs; the guide belongs to the reverse step as there.
+ * Refused on the host before any launch (non-zero, "ramp_sample_guided_team" in ramp_last_error): tg without cg; team_size outside
+ * 1 .. RAMP_TEAM_MAX; B % team_size != 0; radius_team <= 0 or non-finite with w_team != 0; a non-finite w_team; H > 128; a sharded job with
+ * philox_sample0 % team_size != 0; and what ramp_sample_guided refuses.  ramp_sample_guided_prims, ramp_sample_steered and
+ * ramp_sample_stitched keep their signatures and take no team. */
+int ramp_sample_guided_team(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_team_guide* tg,
+                            const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                            const float* mcmc_noise, const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream);
+/* the kernel alone, the counterpart of ramp_guide_step: its arguments plus tg (NULL = ramp_guide_step).  Refusals as above, with
+ * "ramp_guide_step_team".  Synchronises `stream`. */
+int ramp_guide_step_team(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_team_guide* tg,
+                         const int32_t* traj_scene, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
+                         const float* hard_val, void* stream);
+/* terms_out device (B, 4) doubles: columns 0 .. 2 are ramp_guide_cost's bits; column 3 of a row is sum_{a' != a} sum_h 1/2 (r_t - d)^2,
+ * fp32 values (d = the correctly rounded root) summed in fp64 in a fixed order (per waypoint over a' ascending, then over the waypoints in
+ * the order of the other columns' reduction), 0 with tg == NULL.  A team's C_team is half the sum of its rows' column 3.  Every row of a team with a scene index outside
+ * the table gets NaN.  Refusals as above, with "ramp_guide_cost_team".  Synchronises `stream`. */
+int ramp_guide_cost_team(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_team_guide* tg,
+                         const int32_t* traj_scene, double* terms_out, void* stream);
+/* The joint check of teams, synchronous swept, closed form.  For a pair a < a' and h < H - 1: D0 = p_{a,h} - p_{a',h},
+ * D1 = p_{a,h+1} - p_{a',h+1}, e = D1 - D0, t = clamp(-(D0 . e) / |e|^2, 0, 1) with t = 0 when |e|^2 == 0, d_seg = |D0 + t e| min-ed with
+ * |D0| and |D1| (so sep_seg <= sep_wp always, the rule of ramp_traj_clearance).  Per team: sep_wp = min over pairs and waypoints of |D_h|,
+ * sep_seg = min over pairs and segments of d_seg, wp_conflicts = #(pair, h) with |D_h| < min_sep, seg_conflicts = #(pair, segment) with
+ * d_seg < min_sep (both strict).  All fp32, rounded as written.  A team with a non-finite position coordinate gets NaN separations, all
+ * counts at their maximum and is never free; team_size == 1 gives +inf separations and zero counts.
+ * The reduction for the selection, in the same launch, from the optional per-row arrays of ramp_traj_clearance, ramp_traj_costs_scenes or
+ * ramp_traj_metrics_scenes: team_mask = 1 if any member's row_mask is non-zero or the conflict count `swept` chooses (1: seg_conflicts,
+ * 0: wp_conflicts) is non-zero; team_len / team_smooth = the members' values added serially in fp32 in agent order (0 without the array).
+ * Selection is then ramp_select_scored_scenes on the team-level arrays with the trajectories viewed as (B / A, A H, S) and
+ * team_first = traj_first / A.
+ * All arrays on the device: the inputs (B) or NULL, the outputs (B / team_size), any of them NULL.  Asynchronous on `stream`, capturable,
+ * one launch.  Refused on the host before any launch ("ramp_team_clearance" in ramp_last_error): NULL traj, B <= 0, H outside 2 .. 128,
+ * point_dim outside {2, 3} or > S, team_size outside 1 .. RAMP_TEAM_MAX, B % team_size != 0, a negative or NaN min_sep. */
+int ramp_team_clearance(const float* traj, int32_t B, int32_t H, int32_t S, int32_t point_dim, int32_t team_size, float min_sep,
+                        int32_t swept, const int32_t* row_mask, const float* row_len, const float* row_smooth, float* sep_wp,
+                        float* sep_seg, int32_t* wp_conflicts, int32_t* seg_conflicts, int32_t* team_mask, float* team_len,
+                        float* team_smooth, void* stream);
 /* ---- resampling trajectories by cost inside the sampling job (SMC steering) ----
  * A job draws B candidates per scene and ranks them when it has finished; sequential Monte Carlo steering (Feynman-Kac steering, twisted SMC
  * for diffusion) weights every candidate at chosen noise levels by a potential on the job's current clean estimate and resamples within the

@@ -77,6 +77,15 @@ class RampPrimGuide(C.Structure):
                 ("margin", C.c_double), ("band", C.c_double), ("w_prim", C.c_double), ("n_sub", C.c_int32), ("reserved", C.c_int32)]
 
 
+TEAM_MAX = 8                # RAMP_TEAM_MAX
+
+
+class RampTeamGuide(C.Structure):
+    """ramp_team_guide: the separation term between the rows of a team that travels with a ramp_cost_guide (ramp_sample_guided_team) and the
+    kernel-level ramp_guide_step_team / ramp_guide_cost_team."""
+    _fields_ = [("team_size", C.c_int32), ("reserved", C.c_int32), ("radius_team", C.c_double), ("w_team", C.c_double)]
+
+
 STITCH_MAX_PINS = 64        # RAMP_STITCH_MAX_PINS
 
 
@@ -220,6 +229,13 @@ PROTOTYPES = {
                                         C.c_int32, C.c_float, C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
     "ramp_guide_cost_prims": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.POINTER(RampPrimGuide), C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "ramp_sample_guided_team": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampCostGuide), C.POINTER(RampTeamGuide),
+                                          C.POINTER(RampMcmcParams), C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch)] + [C.c_void_p] * 7),
+    "ramp_guide_step_team": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.POINTER(RampTeamGuide), C.c_void_p,
+                                       C.c_int32, C.c_float, C.c_int32, c_i32p, C.c_void_p, C.c_void_p]),
+    "ramp_guide_cost_team": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampCostGuide), C.POINTER(RampTeamGuide), C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "ramp_team_clearance": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_int32] + [C.c_void_p] * 11),
     "ramp_sample_stitched": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampStitch), C.POINTER(RampCostGuide),
                                        C.POINTER(RampSceneBatch)] + [C.c_void_p] * 5),
     "ramp_stitch_windows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampStitch), C.c_void_p]),

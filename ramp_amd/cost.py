@@ -301,3 +301,41 @@ def select_best_clear_scenes(trajs, counts_or_traj_scene, clouds=None, boxes=Non
             float(smoothness_weight), float(path_length_weight), _lib.ptr(best), _lib.ptr(res), _lib.current_stream()),
             "ramp_select_scored_scenes")
     return best, res[:, 0], res[:, 1], res[:, 2], ~mask.bool()
+
+
+def select_best_teams_scenes(x, size, team_first, team_mask, team_len, team_smooth, w_smooth=.1, w_len=.9):
+    """The best conflict-free TEAM of every scene (``ramp_amd.team``): ``x`` (B, H, S) rows in team layout or (B / size, size, H, S),
+    ``team_first`` (n_scenes + 1) the first team of each scene (``traj_first / size``), and the team-level arrays of
+    ``team.team_clearance`` -- ``team_mask`` (1 = a member collides or the team has a conflict), ``team_len``, ``team_smooth``.  The
+    selection is ramp_select_scored_scenes on the trajectories viewed as (B / size, size * H, S): a team's rows are adjacent.
+
+    Returns ``(winners, result)``: (n_scenes, size, H, S), NaN for a scene without a free team, and the int32 (n_scenes, 4) table
+    ``{n_free, winner's index among the scene's free teams, winner's team in the batch, 0}`` (``{0, -1, -1, 0}`` for none) -- device
+    tensors, without a host sync."""
+    if x.device.type != "cuda":
+        raise _lib.RampHipError("team selection: tensors must live on a HIP device (no CPU path)")
+    size = int(size)
+    t = x.detach().to(torch.float32).contiguous()
+    if t.dim() == 4:
+        t = t.reshape(-1, t.shape[-2], t.shape[-1])
+    B, H, S = t.shape
+    if size < 1 or B % size:
+        raise ValueError(f"team selection: {B} rows are no multiple of the team size {size}")
+    n = B // size
+    dev = t.device
+    first = torch.as_tensor(team_first).to(dev, torch.int32).contiguous()
+    if first.dim() != 1 or first.numel() < 2:
+        raise ValueError("team_first must hold n_scenes + 1 >= 2 entries")
+    n_scenes = first.numel() - 1
+    m = (torch.as_tensor(team_mask).to(dev) != 0).to(torch.int32).contiguous()
+    plen = torch.as_tensor(team_len).to(dev, torch.float32).contiguous()
+    smooth = torch.as_tensor(team_smooth).to(dev, torch.float32).contiguous()
+    if not (m.numel() == plen.numel() == smooth.numel() == n):
+        raise ValueError(f"team_mask, team_len and team_smooth must hold one entry per team ({n})")
+    best = torch.empty(n_scenes, size * H, S, device=dev)
+    res = torch.empty(n_scenes, 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().ramp_select_scored_scenes(
+            _lib.ptr(t), n, size * H, S, first.data_ptr(), n_scenes, _lib.ptr(m), _lib.ptr(plen), _lib.ptr(smooth), float(w_smooth),
+            float(w_len), _lib.ptr(best), _lib.ptr(res), _lib.current_stream()), "ramp_select_scored_scenes")
+    return best.reshape(n_scenes, size, H, S), res

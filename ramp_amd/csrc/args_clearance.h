@@ -22,4 +22,18 @@ struct ClearanceArgs {
 // one block per trajectory; the dims are the caller's to check (ramp_traj_clearance does)
 int launch_traj_clearance(const ClearanceArgs& a, hipStream_t s);
 
+// ---- robot-robot separation of teams (team.hip; ramp_team_clearance in ramp_hip.h) ----
+struct TeamClearanceArgs {
+  const float* traj = nullptr;        // (B,H,S); positions are channels [0, D); row b is agent b % team of team b / team
+  int B = 0, H = 0, S = 0, D = 2;     // D = point_dim, 2 or 3, <= S; 2 <= H <= 128
+  int team = 1;                       // 1 .. 8, B % team == 0
+  float min_sep = 0.f;
+  int swept = 1;                      // which count decides team_mask: 1 = seg_conflicts, 0 = wp_conflicts
+  const int* row_mask = nullptr; const float* row_len = nullptr; const float* row_smooth = nullptr;   // (B) each, or null
+  float* sep_wp = nullptr; float* sep_seg = nullptr; int* wp_conflicts = nullptr; int* seg_conflicts = nullptr;   // (B / team) each; any may be null
+  int* team_mask = nullptr; float* team_len = nullptr; float* team_smooth = nullptr;                  // (B / team) each; any may be null
+};
+// one block per team, one launch; the dims are the caller's to check (ramp_team_clearance does)
+int launch_team_clearance(const TeamClearanceArgs& a, hipStream_t s);
+
 }  // namespace ramp

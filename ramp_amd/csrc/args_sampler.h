@@ -119,6 +119,21 @@ struct PrimGuideArgs {
 int launch_guide_prims_step(const PrimGuideArgs& a, hipStream_t s);
 // terms (B, 4) doubles = {C_obs, C_smooth, C_acc, C_prim} unweighted (NaN for a trajectory whose scene index is outside the table)
 int launch_guide_prims_cost(const PrimGuideArgs& a, double* terms, hipStream_t s);
+// ---- teams of robots in one job: the separation term of the cost guide (guide_team.hip + guide_core.h; ramp_team_guide in ramp_hip.h) ----
+// GuideArgs plus the team layout: row b is agent b % team of team b / team, a team's rows are adjacent; C_team couples the rows of a team at
+// equal waypoint index.  One block owns a whole team (positions of all its agents in LDS), so nothing crosses a block
+constexpr int TEAM_MAX = 8;         // the largest team (RAMP_TEAM_MAX)
+struct TeamGuideArgs {
+  GuideArgs g;
+  int team = 1;                     // 1 .. TEAM_MAX, g.B % team == 0
+  float radius_team = 0, w_team = 0;
+};
+// n_iter Jacobi iterations in ONE launch, one block per team; n_iter == 0 launches nothing.  team == 1 or w_team == 0 launches
+// guide_step_kernel itself
+int launch_guide_team_step(const TeamGuideArgs& a, hipStream_t s);
+// terms (B, 4) doubles = {C_obs, C_smooth, C_acc, the row's share of C_team} unweighted (NaN for every row of a team with a scene index
+// outside the table)
+int launch_guide_team_cost(const TeamGuideArgs& a, double* terms, hipStream_t s);
 // ---- stitched windows (stitch.hip; ramp_stitch in ramp_hip.h) ---------------------------------------
 constexpr int STITCH_MAX_PINS = 64;
 struct StitchArgs {

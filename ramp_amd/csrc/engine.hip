@@ -1995,7 +1995,9 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
 struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
 // The cost guide of a job (ramp_sample_guided), checked by the entry; only a guide with n_guide > 0 somewhere becomes one
 // pg != nullptr: its swept box and sphere terms (ramp_sample_guided_prims), checked by the entry; only a table that changes the guide becomes one
-struct GuideJob { const ramp_cost_guide* cg; const ramp_prim_guide* pg; };
+// tg != nullptr: the separation term between the rows of a team (ramp_sample_guided_team), checked by the entry; only a table that changes the guide
+// (more than one agent, w_team != 0) becomes one
+struct GuideJob { const ramp_cost_guide* cg; const ramp_prim_guide* pg; const ramp_team_guide* tg; };
 // The stitch table of a job (ramp_sample_stitched), checked by the entry
 struct StitchJob { const ramp_stitch* st; };
 // The resampling events of a job (ramp_sample_steered), checked by the entry; only a table with a flag set somewhere becomes one.  The injected
@@ -2064,7 +2066,9 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   auto guide_at = [&](int j, float* target) -> int {
     if (!gj || gj->cg->n_guide[j] <= 0) return 0;
     ga.traj = target; ga.n_iter = gj->cg->n_guide[j]; ga.step = gj->cg->step[j];
-    if (gj->pg) {
+    if (gj->tg) {      // one block per team; a job carries a team or primitives, never both
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_team_step(team_guide_args(gj->tg, ga), s));
+    } else if (gj->pg) {
       PrimGuideArgs pa = prim_guide_args(gj->pg, ga);
       pa.box_c = c->pg_boxc; pa.box_s = c->pg_boxs; pa.sph_c = c->pg_sphc; pa.sph_r = c->pg_sphr; pa.box_off = c->pg_boff; pa.sph_off = c->pg_soff;
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_prims_step(pa, s));
@@ -2444,6 +2448,10 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       const int ptag[5] = {0x5052494d /* "PRIM" */, pg->n_scenes, pg_boxes, pg_spheres, pg->n_sub}; key.put(ptag, 5);
       const double sc3[3] = {pg->margin, pg->band, pg->w_prim}; key.put(sc3, 3);
     }
+    if (gj->tg) {      // (no buffer of its own; the team size and the two scalars are kernel arguments of the captured nodes)
+      const int ttag[2] = {0x5445414d /* "TEAM" */, gj->tg->team_size}; key.put(ttag, 2);
+      const double sc2[2] = {gj->tg->radius_team, gj->tg->w_team}; key.put(sc2, 2);
+    }
   }
   if (rj) {      // (the rs_* buffers exist only for such a job; flags, lambda, ess_frac, the scalars and the Philox group fields are kernel arguments)
     const ramp_resample_params* rs = rj->rs;
@@ -2562,7 +2570,8 @@ int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_gu
 static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
                           const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
                           const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who,
-                          ResampleJob* rj = nullptr, const StitchJob* sj = nullptr, const ramp_prim_guide* pg = nullptr) {
+                          ResampleJob* rj = nullptr, const StitchJob* sj = nullptr, const ramp_prim_guide* pg = nullptr,
+                          const ramp_team_guide* tg = nullptr) {
   const std::string w = std::string(who) + ": ";
   const int kind = m ? m->kind : 0;
   RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");
@@ -2583,8 +2592,15 @@ static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_c
       RAMP_REQUIRE(kind != 2 || mcmc_u, w + "null mcmc_u (noise_mode 0 injects MALA's uniforms)");
     }
   }
-  GuideJob gj{cg, nullptr};
+  GuideJob gj{cg, nullptr, nullptr};
   int guide_total = 0;
+  if (tg) {      // (next to the cost guide it travels with)
+    RAMP_REQUIRE(cg, w + "a team table needs its cost guide");
+    CK(check_cost_guide(cg, c->cfg.state_dim, who));
+    CK(check_team_guide(tg, p->B, c->cfg.horizon, who));
+    RAMP_REQUIRE(p->philox_total == 0 || p->philox_sample0 % tg->team_size == 0, w + "a shard must hold whole teams (philox_sample0 % team_size == 0)");
+    if (team_guide_active(tg)) gj.tg = tg;
+  }
   if (pg) {      // (next to the cost guide it travels with)
     RAMP_REQUIRE(cg, w + "a primitive table needs its cost guide");
     CK(check_cost_guide(cg, c->cfg.state_dim, who));
@@ -2650,6 +2666,15 @@ int ramp_sample_guided_prims(ramp_ctx* c, const ramp_sample_params* p, const ram
   RAMP_REQUIRE(c && p, "ramp_sample_guided_prims: null argument");
   return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided_prims", nullptr,
                         nullptr, pg);
+}
+
+// ramp_sample_guided with the separation term between the rows of a team.  tg == NULL, one agent per team or w_team == 0 is that entry itself
+int ramp_sample_guided_team(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_team_guide* tg,
+                            const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                            const float* mcmc_noise, const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_guided_team: null argument");
+  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided_team", nullptr,
+                        nullptr, nullptr, tg);
 }
 
 // The one entry for every kind of job: ramp_sample_guided plus the resampling events.  rs == NULL or no flag set is that entry itself

@@ -166,6 +166,28 @@ PrimGuideArgs prim_guide_args(const ramp_prim_guide* pg, const GuideArgs& g) {
   return a;
 }
 
+// what ramp_sample_guided_team, ramp_guide_step_team and ramp_guide_cost_team (`who`) require of a team table next to the checked cost guide, on
+// B rows of H waypoints: host checks only, made before anything is staged or launched
+int check_team_guide(const ramp_team_guide* tg, int B, int H, const char* who) {
+  static_assert(TEAM_MAX == RAMP_TEAM_MAX, "one team limit");
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(tg, w + "null team table");
+  RAMP_REQUIRE(tg->team_size >= 1 && tg->team_size <= RAMP_TEAM_MAX, w + "team_size outside 1 .. RAMP_TEAM_MAX");
+  RAMP_REQUIRE(B > 0 && B % tg->team_size == 0, w + "the batch must be a multiple of team_size");
+  RAMP_REQUIRE(std::isfinite(tg->w_team), w + "w_team must be finite");
+  RAMP_REQUIRE(tg->w_team == 0.0 || (std::isfinite(tg->radius_team) && tg->radius_team > 0.0), w + "radius_team must be positive and finite where w_team != 0");
+  RAMP_REQUIRE(H <= GUIDE_MAX_H, w + "the team guide kernel serves horizons up to 128");
+  return 0;
+}
+// true: the table changes the guide (more than one agent and w_team != 0); otherwise the call is the cost guide's own
+bool team_guide_active(const ramp_team_guide* tg) { return tg && tg->team_size > 1 && tg->w_team != 0.0 && (float)tg->w_team != 0.f; }
+// the kernel's arguments from a checked table (tg may be null: no team term) around the filled guide arguments
+TeamGuideArgs team_guide_args(const ramp_team_guide* tg, const GuideArgs& g) {
+  TeamGuideArgs a; a.g = g;
+  if (tg) { a.team = tg->team_size; a.radius_team = (float)tg->radius_team; a.w_team = (float)tg->w_team; }
+  return a;
+}
+
 // what ramp_sample_stitched and ramp_stitch_windows (`who`) require of a stitch table on B rows of H waypoints: host checks only, made before
 // anything is staged or launched
 int check_stitch(const ramp_stitch* st, int B, int H, const char* who) {

@@ -152,8 +152,9 @@ int ramp_apf_scenes(float* traj, int32_t B, int32_t H, int32_t S, const ramp_apf
 }
 
 // the guide's kernels on the caller's arrays: offsets | hard-condition indices go to the device in one block of their own (synchronises `stream`)
+// team != nullptr: the kernels of guide_team.hip with these team arguments around `a` (terms_out is then (B, 4))
 static int guide_op(GuideArgs a, const ramp_cost_guide* cg, const int32_t* traj_scene, int32_t n_hard, const int32_t* hard_idx_host,
-                    const float* hard_val, double* terms_out, hipStream_t s) {
+                    const float* hard_val, double* terms_out, hipStream_t s, const TeamGuideArgs* team = nullptr) {
   std::vector<int32_t> blk(cg->cloud_offset_host, cg->cloud_offset_host + cg->n_scenes + 1);
   blk.insert(blk.end(), hard_idx_host, hard_idx_host + n_hard);
   int32_t* d = nullptr;
@@ -162,7 +163,12 @@ static int guide_op(GuideArgs a, const ramp_cost_guide* cg, const int32_t* traj_
   if (hipMemcpy(d, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error("guide: copy of the tables failed"); rc = -1; }
   a.cloud = cg->cloud_points; a.cloud_off = d; a.scene = traj_scene;
   a.hc.idx = d + cg->n_scenes + 1; a.hc.val = hard_val; a.hc.n = n_hard;
-  if (rc == 0) rc = terms_out ? launch_guide_cost(a, terms_out, s) : launch_guide_step(a, s);
+  if (rc == 0 && team) {
+    TeamGuideArgs t = *team; t.g = a;
+    rc = terms_out ? launch_guide_team_cost(t, terms_out, s) : launch_guide_team_step(t, s);
+  } else if (rc == 0) {
+    rc = terms_out ? launch_guide_cost(a, terms_out, s) : launch_guide_step(a, s);
+  }
   (void)hipStreamSynchronize(s);
   (void)hipFree(d);
   return rc;
@@ -189,6 +195,58 @@ int ramp_guide_cost(const float* traj, int32_t B, int32_t H, int32_t S, const ra
   RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_cost: bad dims (H up to 128)");
   CK(check_cost_guide(cg, S, "ramp_guide_cost"));
   return guide_op(guide_args(cg, const_cast<float*>(traj), B, H, S), cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream));
+}
+
+// ramp_guide_step with the team term of ramp_team_guide.  tg == NULL, one agent per team or w_team == 0 is that entry itself
+int ramp_guide_step_team(float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_team_guide* tg,
+                         const int32_t* traj_scene, int32_t n_iter, float step, int32_t n_hard, const int32_t* hard_idx_host,
+                         const float* hard_val, void* stream) {
+  RAMP_REQUIRE(traj && cg, "ramp_guide_step_team: null argument (a team table needs its cost guide)");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_step_team: bad dims (H up to 128)");
+  CK(check_cost_guide(cg, S, "ramp_guide_step_team"));
+  if (tg) CK(check_team_guide(tg, B, H, "ramp_guide_step_team"));
+  RAMP_REQUIRE(n_iter >= 0 && n_iter <= RAMP_GUIDE_MAX_STEPS, "ramp_guide_step_team: n_iter outside 0 .. RAMP_GUIDE_MAX_STEPS");
+  RAMP_REQUIRE(std::isfinite(step), "ramp_guide_step_team: step must be finite");
+  RAMP_REQUIRE(n_hard >= 0 && n_hard <= 256 && (n_hard == 0 || (hard_idx_host && hard_val)), "ramp_guide_step_team: bad hard conditions");
+  for (int j = 0; j < n_hard; ++j) RAMP_REQUIRE(hard_idx_host[j] >= 0 && hard_idx_host[j] < H, "ramp_guide_step_team: hard index out of range");
+  if (n_iter == 0) return 0;
+  GuideArgs a = guide_args(cg, traj, B, H, S);
+  a.n_iter = n_iter; a.step = step;
+  if (!team_guide_active(tg)) return guide_op(a, cg, traj_scene, n_hard, hard_idx_host, hard_val, nullptr, as_stream(stream));
+  const TeamGuideArgs t = team_guide_args(tg, a);
+  return guide_op(a, cg, traj_scene, n_hard, hard_idx_host, hard_val, nullptr, as_stream(stream), &t);
+}
+
+int ramp_guide_cost_team(const float* traj, int32_t B, int32_t H, int32_t S, const ramp_cost_guide* cg, const ramp_team_guide* tg,
+                         const int32_t* traj_scene, double* terms_out, void* stream) {
+  RAMP_REQUIRE(traj && cg && terms_out, "ramp_guide_cost_team: null argument (a team table needs its cost guide)");
+  RAMP_REQUIRE(B > 0 && H > 0 && H <= GUIDE_MAX_H && S > 0, "ramp_guide_cost_team: bad dims (H up to 128)");
+  CK(check_cost_guide(cg, S, "ramp_guide_cost_team"));
+  if (tg) CK(check_team_guide(tg, B, H, "ramp_guide_cost_team"));
+  const GuideArgs a = guide_args(cg, const_cast<float*>(traj), B, H, S);
+  const TeamGuideArgs t = team_guide_args(tg, a);      // (no table: teams of one, column 3 = 0)
+  return guide_op(a, cg, traj_scene, 0, nullptr, nullptr, terms_out, as_stream(stream), &t);
+}
+
+// every refusal of ramp_team_clearance is made here, on the host, before anything is launched
+int ramp_team_clearance(const float* traj, int32_t B, int32_t H, int32_t S, int32_t point_dim, int32_t team_size, float min_sep,
+                        int32_t swept, const int32_t* row_mask, const float* row_len, const float* row_smooth, float* sep_wp,
+                        float* sep_seg, int32_t* wp_conflicts, int32_t* seg_conflicts, int32_t* team_mask, float* team_len,
+                        float* team_smooth, void* stream) {
+  const std::string w = "ramp_team_clearance: ";
+  RAMP_REQUIRE(traj, w + "null trajectories");
+  RAMP_REQUIRE(B > 0 && S > 0 && (long)B * H * S < (1l << 31), w + "bad dims");
+  RAMP_REQUIRE(H >= 2 && H <= 128, w + "the horizon must be 2 .. 128");
+  RAMP_REQUIRE((point_dim == 2 || point_dim == 3) && point_dim <= S, w + "point_dim must be 2 or 3 and at most S");
+  RAMP_REQUIRE(team_size >= 1 && team_size <= RAMP_TEAM_MAX, w + "team_size outside 1 .. RAMP_TEAM_MAX");
+  RAMP_REQUIRE(B % team_size == 0, w + "the batch must be a multiple of team_size");
+  RAMP_REQUIRE(min_sep >= 0.f, w + "min_sep must not be negative or NaN");
+  TeamClearanceArgs a;
+  a.traj = traj; a.B = B; a.H = H; a.S = S; a.D = point_dim; a.team = team_size; a.min_sep = min_sep; a.swept = swept != 0;
+  a.row_mask = row_mask; a.row_len = row_len; a.row_smooth = row_smooth;
+  a.sep_wp = sep_wp; a.sep_seg = sep_seg; a.wp_conflicts = wp_conflicts; a.seg_conflicts = seg_conflicts;
+  a.team_mask = team_mask; a.team_len = team_len; a.team_smooth = team_smooth;
+  return launch_team_clearance(a, as_stream(stream));
 }
 
 // the primitive guide's kernels on the caller's arrays: cloud offsets | box offsets | sphere offsets | hard-condition indices go to the device in

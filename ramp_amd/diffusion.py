@@ -121,12 +121,18 @@ def mcmc_tables(mcmc: dict, steps, alphas_cumprod) -> dict:
 
 
 GUIDE_PRIM_KEYS = {'boxes', 'spheres', 'margin', 'band', 'w_prim', 'n_sub'}      # the swept box and sphere terms (ramp_prim_guide)
-GUIDE_KEYS = {'cloud', 'clouds', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'step', 'n_steps', 't_start', 'max_norm', 'scale_by_variance'} | GUIDE_PRIM_KEYS
+GUIDE_KEYS = {'cloud', 'clouds', 'radius', 'w_obs', 'w_smooth', 'w_acc', 'step', 'n_steps', 't_start', 'max_norm', 'scale_by_variance',
+              'team'} | GUIDE_PRIM_KEYS
 
 
 def guide_has_prims(cost_guide) -> bool:
     """True when a ``cost_guide=`` dict carries any key of the swept box and sphere terms."""
     return isinstance(cost_guide, dict) and bool(GUIDE_PRIM_KEYS & set(cost_guide))
+
+
+def guide_has_team(cost_guide) -> bool:
+    """True when a ``cost_guide=`` dict carries the ``team=`` key (rows coupled in teams of robots, ramp_team_guide)."""
+    return isinstance(cost_guide, dict) and cost_guide.get('team') is not None
 
 
 def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
@@ -146,9 +152,11 @@ def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
                          ``cloud=None`` with ``w_obs=0`` is the primitives-only guide
       margin, band, w_prim, n_sub   the robot margin (default 0), the hinge's band (required with primitives), the term's weight (default 1)
                          and the samples per segment, 1 .. 8 (default 4)
+      team               dict(size=A, radius=r_t, w=1.0): the rows of the job are teams of A robots that share a scene, row b agent b % A of
+                         team b / A, coupled through the separation term of ``ramp_team_guide`` (``ramp_amd.team.team_scalars``)
 
     Returns ``{'n_guide': [...], 'step': [...], 'radius', 'w_obs', 'w_smooth', 'w_acc', 'max_norm', 'total': sum n_guide}`` and, with any
-    of the primitive keys, ``'prim': {'margin', 'band', 'w_prim', 'n_sub'}``."""
+    of the primitive keys, ``'prim': {'margin', 'band', 'w_prim', 'n_sub'}``; with ``team=``, ``'team': {'size', 'radius', 'w'}``."""
     if not isinstance(cost_guide, dict):
         raise TypeError("cost_guide= takes a dict(cloud= | clouds=, radius=, step=, w_obs=, w_smooth=, w_acc=, n_steps=, t_start=, max_norm=, "
                         "scale_by_variance=)")
@@ -192,6 +200,11 @@ def guide_tables(cost_guide: dict, steps, posterior_variance) -> dict:
         if cost_guide.get('boxes') is None and cost_guide.get('spheres') is None:
             raise ValueError("cost_guide=: margin / band / w_prim / n_sub need boxes= or spheres=")
         out['prim'] = prim_scalars(cost_guide.get('margin', 0.0), cost_guide.get('band'), cost_guide.get('w_prim', 1.0), cost_guide.get('n_sub', 4))
+    if guide_has_team(cost_guide):
+        from .team import team_scalars
+        if guide_has_prims(cost_guide):
+            raise NotImplementedError("cost_guide=: team= with boxes= / spheres= is not served (ramp_sample_guided_prims takes no team)")
+        out['team'] = team_scalars(cost_guide['team'])
     return out
 
 
@@ -605,6 +618,24 @@ class _GaussianDiffusionBase(nn.Module):
             raise NotImplementedError("cost_guide=: boxes= / spheres= (the swept primitive term) are not served on stitched windows or with "
                                       "resample= (ramp_sample_stitched and ramp_sample_steered take no primitives)")
 
+    @staticmethod
+    def _refuse_team_outside_the_guide(cost_guide, resample, stitch, counts=None):
+        """Teams of robots live in ``cost_guide=`` of plain, scene, composed and MCMC jobs only, and every scene's rows must be whole teams
+        (``counts``: the rows per scene, where the caller knows them): host checks, before any device call."""
+        if not guide_has_team(cost_guide):
+            return
+        from .team import team_scalars
+        A = team_scalars(cost_guide['team'])['size']
+        if guide_has_prims(cost_guide):
+            raise NotImplementedError("cost_guide=: team= with boxes= / spheres= is not served (ramp_sample_guided_prims takes no team)")
+        if resample is not None:
+            raise NotImplementedError("cost_guide=: team= with resample= is not served (a resampled row would leave its team)")
+        if stitch is not None:
+            raise NotImplementedError("cost_guide=: team= is not served on stitched windows (ramp_sample_stitched takes no team)")
+        for i, n in enumerate(counts or []):
+            if int(n) % A:
+                raise ValueError(f"cost_guide team=: {int(n)} rows in scene {i} are no multiple of the team size {A} (n_samples counts rows)")
+
     def _run_guarded(self, job):
         """Run ``job`` under the fp16x3 range-guard policy: a flagged result is discarded and the same job (same noise) repeated, never
         a silently degraded answer.  First IN fp16x3 with the evaluation that raised the guard run as a calibrating one (range-free,
@@ -664,6 +695,7 @@ class _GaussianDiffusionBase(nn.Module):
         if stitch is not None and (mcmc is not None or resample is not None or guidance is not None or hard_conds):
             raise NotImplementedError("stitched windows take no mcmc=, resample=, composed weights or hard conditions of their own")
         self._refuse_prims_outside_the_guide(cost_guide, resample, stitch)
+        self._refuse_team_outside_the_guide(cost_guide, resample, stitch, [B])
         rtab = resample_tables(resample, steps) if resample is not None else None
         if rtab is not None:
             if self._philox_shard is not None:
@@ -708,7 +740,10 @@ class _GaussianDiffusionBase(nn.Module):
         chain = torch.empty((n_steps + 1, B, H, S), device=dev, dtype=torch.float32) if return_chain else None
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
         mp = z_in = u_in = accept = None
-        cg = pg = None
+        cg = pg = tg = None
+        if gtab is not None and gtab.get('team') is not None:
+            from .team import fill_team_guide
+            tg = fill_team_guide(gtab['team'])
         if gtab is not None:
             from .guide import fill_prim_guide
             ptab = self._prim_tables(arrays, gtab, cost_guide, scene_job)
@@ -779,6 +814,12 @@ class _GaussianDiffusionBase(nn.Module):
                                                             C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
                                                             _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
                                                             _lib.current_stream()), "ramp_sample_guided_prims")
+                elif tg is not None:
+                    _lib.check(lib.ramp_sample_guided_team(m.ctx(), C.byref(p), C.byref(cg), C.byref(tg), C.byref(mp) if mp is not None else None,
+                                                           C.byref(rows) if rows is not None else None,
+                                                           C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
+                                                           _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
+                                                           _lib.current_stream()), "ramp_sample_guided_team")
                 elif cg is not None:
                     _lib.check(lib.ramp_sample_guided(m.ctx(), C.byref(p), C.byref(cg), C.byref(mp) if mp is not None else None,
                                                       C.byref(rows) if rows is not None else None,
@@ -929,6 +970,7 @@ class _GaussianDiffusionBase(nn.Module):
         horizon = horizon or self.model.n_support_points
         shape = (batch_size, horizon, self.state_dim)
         self._refuse_prims_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'))
+        self._refuse_team_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'), [batch_size])
         if self.ddim:
             if sample_kwargs.get('mcmc') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
                 raise NotImplementedError("mcmc= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
@@ -962,6 +1004,7 @@ class _GaussianDiffusionBase(nn.Module):
     def run_inference(self, context=None, hard_conds=None, n_samples=1, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, **diffusion_kwargs):
         """diffusion_model_static.py:437-463: returns (steps+1, B, H, S) if return_chain else (B, H, S)."""
+        self._refuse_team_outside_the_guide(diffusion_kwargs.get('cost_guide'), diffusion_kwargs.get('resample'), None, [n_samples])
         hard_conds = copy(hard_conds)
         for k, v in hard_conds.items():
             hard_conds[k] = v.to(self._device()).unsqueeze(0).expand(n_samples, -1) if v.dim() == 1 else v
@@ -1030,6 +1073,8 @@ class _GaussianDiffusionBase(nn.Module):
         the model's setting, not by its ``ddim`` argument) and ``guide`` / ``n_guide_steps`` / ``t_start_guide`` are accepted and
         unused.  Not supported: compose (``run_inference_composed`` is the composed many-scene job), the dynamic planner,
         a caller-supplied ``sample_fn``."""
+        self._refuse_team_outside_the_guide(diffusion_kwargs.get('cost_guide'), diffusion_kwargs.get('resample'), None,
+                                            [n_samples] * len(scenes) if np.isscalar(n_samples) else list(n_samples))
         job, hc, B = self._prepare_scene_job(scenes, hard_conds, n_samples)
         for k in ('guide', 'n_guide_steps', 't_start_guide'):
             diffusion_kwargs.pop(k, None)
@@ -1070,6 +1115,8 @@ class _GaussianDiffusionBase(nn.Module):
                 raise NotImplementedError(f"run_inference_stitched: {k}= is not supported (its proposals / ancestors would have to be chain-wise)")
         if guide_has_prims(cost_guide):
             raise NotImplementedError("run_inference_stitched: cost_guide= takes no boxes= / spheres= here (ramp_sample_stitched takes no primitives)")
+        if guide_has_team(cost_guide):
+            raise NotImplementedError("run_inference_stitched: cost_guide= takes no team= here (ramp_sample_stitched takes no team)")
         if not self._is_fused_ddpm_step(diffusion_kwargs.get('sample_fn')):
             raise NotImplementedError("run_inference_stitched runs the fused job only: a caller-supplied sample_fn steps on its own")
         if self._philox_shard is not None:
@@ -1171,6 +1218,8 @@ class _GaussianDiffusionBase(nn.Module):
         if not self._is_fused_ddpm_step(diffusion_kwargs.get('sample_fn')):
             raise NotImplementedError("run_inference_composed runs the fused job only (ddpm_sample_fn): a custom sample_fn steps one "
                                       "scene's batch at a time")
+        self._refuse_team_outside_the_guide(diffusion_kwargs.get('cost_guide'), diffusion_kwargs.get('resample'), None,
+                                            [n_samples] * len(scenes) if np.isscalar(n_samples) else list(n_samples))
         job, guidance, hc, B = self._prepare_composed_job(scenes, hard_conds, n_samples, weights, apf_clouds)
         for k in ('guide', 'n_guide_steps', 't_start_guide'):
             diffusion_kwargs.pop(k, None)
