@@ -1280,6 +1280,13 @@ template <class T> int grow(ramp_ctx* c, T*& p, size_t& cap, size_t n) {
   if (n > cap) { CK(renew(c, p, n)); cap = n; }
   return 0;
 }
+// a job's table of n elements into its grow-only buffer (at least `floor` elements, so that an empty table has an address too); a copy from
+// pageable host memory is staged before the call returns
+template <class T> int stage_table(ramp_ctx* c, T*& p, size_t& cap, const T* src, size_t n, size_t floor, hipMemcpyKind kind, hipStream_t s) {
+  CK(grow(c, p, cap, std::max(floor, n)));
+  if (n) RAMP_HIP_CHECK(hipMemcpyAsync(p, src, n * sizeof(T), kind, s));
+  return 0;
+}
 void staging_done(ramp_ctx* c) {
   if (c->buffers_moved) { c->graph_key.clear(); c->e_key.clear(); c->buffers_moved = false; }
 }
@@ -1989,33 +1996,47 @@ int ramp_score_rows(ramp_ctx* c, const float* x, int32_t B, int32_t n_rp, const 
   return rc;
 }
 
-// sc != nullptr: a job of many scenes (ramp_sample_scenes) -- the APF of trajectory b runs against the cloud of scene traj_scene[b]
-// c->g_weight_cur != nullptr: a composed job (ramp_sample_composed) -- the rows' weights in e_comb come from that device table
-// The Langevin refinement of a job (ramp_sample_mcmc), checked by the entry: kind 1 ULA / 2 MALA, total = sum of n_inner > 0
+// The Langevin refinement of a job (ramp_sample_mcmc): kind 1 ULA / 2 MALA, total = sum of n_inner (filled by check_mcmc)
 struct McmcJob { int kind; const int32_t* n_inner; const float* step_size; const float* sigma; int total; };
-// The cost guide of a job (ramp_sample_guided), checked by the entry; only a guide with n_guide > 0 somewhere becomes one
-// pg != nullptr: its swept box and sphere terms (ramp_sample_guided_prims), checked by the entry; only a table that changes the guide becomes one
-// tg != nullptr: the separation term between the rows of a team (ramp_sample_guided_team), checked by the entry; only a table that changes the guide
-// (more than one agent, w_team != 0) becomes one
-struct GuideJob { const ramp_cost_guide* cg; const ramp_prim_guide* pg; const ramp_team_guide* tg; };
-// The stitch table of a job (ramp_sample_stitched), checked by the entry
-struct StitchJob { const ramp_stitch* st; };
-// The resampling events of a job (ramp_sample_steered), checked by the entry; only a table with a flag set somewhere becomes one.  The injected
-// uniforms (noise_mode 0) and the four outputs travel with it
+// The resampling events of a job (ramp_sample_steered): n_events = flags set in rs->resample.  The injected uniforms (noise_mode 0) and the four
+// outputs travel with it
 struct ResampleJob {
   const ramp_resample_params* rs; int n_events;
   const float* u; int32_t* ancestor_out; double* ess_out; double* cost_out; double* logw_out;
 };
+// One sampling job, stated once: what its entry was given, named after the entry (`who`, for the messages).  The entry fills it, run_sample
+// checks every option and switches off what changes nothing, sample_job stages and keys it, sample_body enqueues it.
+// sc: a job of many scenes (ramp_sample_scenes) -- the APF of trajectory b runs against the cloud of scene traj_scene[b]
+// g: a composed job (ramp_sample_composed) -- n_rp up to RAMP_MAX_ROWS_PER_TRAJ, the rows' weights in e_comb come from its device table
+// (c->g_weight_cur while the job runs), p->w0 / p->w1 are not read
+// mj: behind the checks active (mcmc()) only with an inner step somewhere; mcmc_noise / mcmc_u are its injected draws (noise_mode 0),
+// accept_out (sum K, B) its accept flags
+// cg: the cost guide (ramp_sample_guided); behind the checks set only with n_guide > 0 somewhere.  pg: its swept box and sphere terms
+// (ramp_sample_guided_prims), tg: the separation term between the rows of a team (ramp_sample_guided_team): behind the checks each is set only
+// next to such a guide and where its table changes the guide (a primitive with w_prim != 0; more than one agent with w_team != 0)
+// rj: active (resampling()) only with an event somewhere;  st: stitched windows (ramp_sample_stitched)
+struct SampleJob {
+  const char* who; const ramp_sample_params* p; const ramp_scene_batch* sc;
+  const float* noise; float* chain_out; float* x_out;
+  const ramp_guidance_rows* g = nullptr; const ramp_cost_guide* cg = nullptr;
+  McmcJob mj = {0, nullptr, nullptr, nullptr, 0}; const float* mcmc_noise = nullptr; const float* mcmc_u = nullptr; int32_t* accept_out = nullptr;
+  const ramp_prim_guide* pg = nullptr; const ramp_team_guide* tg = nullptr;
+  ResampleJob rj = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
+  const ramp_stitch* st = nullptr;
+  const McmcJob* mcmc() const { return mj.total > 0 ? &mj : nullptr; }
+  const ResampleJob* resampling() const { return rj.n_events > 0 ? &rj : nullptr; }
+};
 
 // mj != nullptr: K_j = mj->n_inner[j] inner steps (propose -> one evaluation at x' -> accept) follow the evaluation of iteration j, and the reverse
 // step uses the cached combined gradient of the state they ended on; every evaluation, inner ones included, is one link of the calibration chain
-// gj != nullptr: on iteration j with n_guide[j] > 0 ONE launch runs that many guide iterations on the posterior mean (DDPM) / x0 (DDIM), behind the APF hook
-// sj != nullptr: stitched windows -- the stitch runs wherever the plain job applies its hard conditions (the job carries none: hc.n == 0) and on the
+// cg != nullptr: on iteration j with n_guide[j] > 0 ONE launch runs that many guide iterations on the posterior mean (DDPM) / x0 (DDIM), behind the APF hook
+// st != nullptr: stitched windows -- the stitch runs wherever the plain job applies its hard conditions (the job carries none: hc.n == 0) and on the
 // array the hooks work on, in front of them and (where one ran) behind them; every noise block is stitched with alpha = 0 first
 // rj != nullptr: on iteration j with resample[j] != 0 the cost of that array (behind the guide) updates the log-weights, and at the end of the
 // iteration every group is resampled: three launches and the copy back, unconditional (identity where nothing resampled), so the graph has no branch
-static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, hipStream_t s, bool chain, bool steady, int cal_eval = -1,
-                       const McmcJob* mj = nullptr, const GuideJob* gj = nullptr, const ResampleJob* rj = nullptr, const StitchJob* sj = nullptr) {
+static int sample_body(ramp_ctx* c, const SampleJob& job, hipStream_t s, bool chain, bool steady, int cal_eval) {
+  const ramp_sample_params* p = job.p; const ramp_scene_batch* sc = job.sc; const ramp_cost_guide* cg = job.cg; const ramp_stitch* st = job.st;
+  const McmcJob* mj = job.mcmc(); const ResampleJob* rj = job.resampling();
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -2034,8 +2055,8 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
                                                                  (long)p->philox_sample0, total, c->s_philox, s));
   }
   StitchArgs sa;
-  if (sj) {
-    sa = stitch_args(sj->st, B, H, S);
+  if (st) {
+    sa = stitch_args(st, B, H, S);
     sa.alpha = c->st_alpha; sa.pin_val = c->st_pin_val;
     // the noise blocks are (blocks, C W, H, S): blocks * C chains of W windows; the right window takes the left window's draws
     StitchArgs na = sa;
@@ -2050,7 +2071,7 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   };
   // x_T = noise[0]; apply_hard_conditioning; chain[0]
   RAMP_HIP_CHECK(hipMemcpyAsync(c->s_x, c->s_noise, n * 4, hipMemcpyDeviceToDevice, s));
-  if (sj) CK(stitch_at(c->s_x));
+  if (st) CK(stitch_at(c->s_x));
   else LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x, hc, B, H, S, s));
   if (chain) RAMP_HIP_CHECK(hipMemcpyAsync(c->s_chain, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   ApfArgs ap; ap.cloud = c->s_cloud; ap.window = c->s_window; ap.B = B; ap.H = H; ap.S = S; ap.P = p->apf.n_points;
@@ -2058,18 +2079,18 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
   const bool sc_apf = sc && sc->cloud_points;
   if (sc_apf) { ap.scene = c->s_traj_scene; ap.scene_off = c->s_scene_off; ap.n_scenes = sc->n_scenes; ap.P = 0; }
   GuideArgs ga;
-  if (gj) {
-    ga = guide_args(gj->cg, nullptr, B, H, S);
+  if (cg) {
+    ga = guide_args(cg, nullptr, B, H, S);
     ga.cloud = c->cg_cloud; ga.cloud_off = c->cg_off; ga.scene = sc ? c->s_traj_scene : nullptr; ga.hc = hc;
   }
   // the guide's launch of iteration j on `target`, if it has one: with primitives the kernel that carries their term, the guide's own otherwise
   auto guide_at = [&](int j, float* target) -> int {
-    if (!gj || gj->cg->n_guide[j] <= 0) return 0;
-    ga.traj = target; ga.n_iter = gj->cg->n_guide[j]; ga.step = gj->cg->step[j];
-    if (gj->tg) {      // one block per team; a job carries a team or primitives, never both
-      LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_team_step(team_guide_args(gj->tg, ga), s));
-    } else if (gj->pg) {
-      PrimGuideArgs pa = prim_guide_args(gj->pg, ga);
+    if (!cg || cg->n_guide[j] <= 0) return 0;
+    ga.traj = target; ga.n_iter = cg->n_guide[j]; ga.step = cg->step[j];
+    if (job.tg) {      // one block per team; a job carries a team or primitives, never both
+      LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_team_step(team_guide_args(job.tg, ga), s));
+    } else if (job.pg) {
+      PrimGuideArgs pa = prim_guide_args(job.pg, ga);
       pa.box_c = c->pg_boxc; pa.box_s = c->pg_boxs; pa.sph_c = c->pg_sphc; pa.sph_r = c->pg_sphr; pa.box_off = c->pg_boff; pa.sph_off = c->pg_soff;
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_guide_prims_step(pa, s));
     } else {
@@ -2179,15 +2200,15 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     m.w0 = (float)p->w0; m.w1 = (float)p->w1; m.w0p1 = (float)(1.0 + p->w0);
     m.sqrt_recip = p->sqrt_recip[j]; m.sqrt_recipm1 = p->sqrt_recipm1[j]; m.clip = p->clip_denoised; m.predict_x0 = p->predict_x0 != 0;
     float* chain_j = chain ? c->s_chain + (size_t)(j + 1) * n : nullptr;
-    float* chain_fin = sj ? nullptr : chain_j;      // (a stitched job's chain block is the state after the closing stitch)
+    float* chain_fin = st ? nullptr : chain_j;     // (a stitched job's chain block is the state after the closing stitch)
     const bool apf = (p->apf.cloud != nullptr || sc_apf) && p->apply_apf && p->apply_apf[j];
-    const bool hooked = sj && (apf || (gj && gj->cg->n_guide[j] > 0));      // a hook moves the array on this iteration: one more stitch behind it
+    const bool hooked = st && (apf || (cg && cg->n_guide[j] > 0));      // a hook moves the array on this iteration: one more stitch behind it
     // the guidance step: the shared prefix has combined the rows already (one row left); otherwise by the job's scalars or its weight table
     const bool by_table = c->g_weight_cur && !combined;
     if (!p->ddim) {
       m.coef1 = p->coef1[j]; m.coef2 = p->coef2[j]; m.mean = c->s_mean; m.x0 = nullptr;
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
-      if (sj) CK(stitch_at(c->s_mean));
+      if (st) CK(stitch_at(c->s_mean));
       if (apf) { ap.traj = c->s_mean; for (int q = 0; q < std::max(1, p->apf.passes); ++q) LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s)); }
       CK(guide_at(j, c->s_mean));
       if (hooked) CK(stitch_at(c->s_mean));
@@ -2197,12 +2218,12 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
     } else {
       m.mean = nullptr; m.x0 = c->s_x0;
       LAUNCH(c, s, CAT_SAMPLER, 0, by_table ? launch_cfg_mean_rows(m, c->g_weight_cur, s) : launch_cfg_mean(m, s));
-      if (sj) CK(stitch_at(c->s_x0));
+      if (st) CK(stitch_at(c->s_x0));
       if (apf) {
         ap.traj = c->s_x0;
         for (int q = 0; q < std::max(1, p->apf.passes); ++q) {
           LAUNCH(c, s, CAT_SAMPLER, 0, launch_apf(ap, s));
-          if (sj) CK(stitch_at(c->s_x0));
+          if (st) CK(stitch_at(c->s_x0));
           else LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x0, hc, B, H, S, s));
         }
       }
@@ -2212,7 +2233,7 @@ static int sample_body(ramp_ctx* c, const ramp_sample_params* p, const ramp_scen
       LAUNCH(c, s, CAT_SAMPLER, 0, launch_ddim_finish(c->s_x, c->s_x0, p->sqrt_a_t[j], p->sqrt_1m_a_t[j], p->sqrt_a_prev[j], p->dir_coef[j], hc,
                             c->s_x, chain_fin, B, H, S, s));
     }
-    if (sj) {      // the update ran without hard conditions: the blend is the identity here, the pins act
+    if (st) {      // the update ran without hard conditions: the blend is the identity here, the pins act
       CK(stitch_at(c->s_x));
       if (chain_j) RAMP_HIP_CHECK(hipMemcpyAsync(chain_j, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
     }
@@ -2267,16 +2288,242 @@ static int stage_apf(ramp_ctx* c, const ramp_apf_params& a, const float* cloud, 
   return 0;
 }
 
-// g != nullptr: a composed job (ramp_sample_composed; its arguments are checked there) -- n_rp up to RAMP_MAX_ROWS_PER_TRAJ, p->w0 / p->w1 not read
-// mj != nullptr: Langevin refinement (ramp_sample_mcmc; its arguments are checked there) -- mcmc_noise / mcmc_u the injected draws (noise_mode 0),
-// accept_out (sum K, B) the accept flags
-// gj != nullptr: cost-gradient guidance (ramp_sample_guided; its arguments are checked there)
-// rj != nullptr: resampling events (ramp_sample_steered; its arguments are checked there)
-static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* sc, const float* noise, float* chain_out, float* x_out,
-                      void* stream, const ramp_guidance_rows* g = nullptr, const McmcJob* mj = nullptr, const float* mcmc_noise = nullptr,
-                      const float* mcmc_u = nullptr, int32_t* accept_out = nullptr, const GuideJob* gj = nullptr,
-                      const ResampleJob* rj = nullptr, const StitchJob* sj = nullptr) {
-  RAMP_REQUIRE(c && p, "null argument");
+// ---- the options of a sampling job.  Per option: its check for the entry job.who (beside check_cost_guide / check_prim_guide / check_team_guide /
+// check_stitch in engine_util.h; every refusal is a host check made before anything is staged or launched), the staging of its buffers (grown
+// with the job's other buffers, before staging_done) and what it adds to the graph key.  A key_ function carries everything of its option that
+// is baked into the captured nodes, and whatever decides that the job touches a buffer that may not exist yet: renew() relies on that when it
+// lets a first allocation pass without dropping the graphs.  A new option brings its own four functions and one field of SampleJob.
+
+// what a guidance table must satisfy, for every entry that takes one (`who` names the entry in the message)
+static int check_guidance(ramp_ctx* c, const ramp_sample_params* p, const ramp_guidance_rows* g, const char* who) {
+  const std::string w = std::string(who) + ": ";
+  RAMP_REQUIRE(g->row_weight, w + "null row_weight");
+  RAMP_REQUIRE(g->n_rp >= 2 && g->n_rp <= RAMP_MAX_ROWS_PER_TRAJ, w + "n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ");
+  RAMP_REQUIRE(g->n_rp == p->n_rp, w + "the guidance table's n_rp differs from the job's");
+  RAMP_REQUIRE(p->B > 0 && (long)p->B * p->n_rp <= (1l << 24), w + "bad batch");
+  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the guidance step moves four elements per access)");
+  RAMP_REQUIRE(c->rv_rows > 0, w + "the row -> latent table comes from ramp_set_scenes (none is in place)");
+  RAMP_REQUIRE(c->rv_rows >= p->B * p->n_rp, w + "the ramp_set_scenes table is shorter than B * n_rp rows");
+  return 0;
+}
+// the weight table onto the device; g_host: the weights on the host, where the canonical calibration's key carries them
+static int stage_guidance(ramp_ctx* c, const SampleJob& job, hipStream_t s, std::vector<float>& g_host) {
+  const size_t nw = (size_t)job.p->B * job.p->n_rp;
+  CK(stage_table(c, c->g_weight, c->g_weight_cap, job.g->row_weight, nw, 0, hipMemcpyDeviceToDevice, s));
+  if (c->gemm_mode == 2 && !c->force_x6 && c->cal_reuse) {
+    g_host.resize(nw);
+    RAMP_HIP_CHECK(hipMemcpyAsync(g_host.data(), c->g_weight, nw * 4, hipMemcpyDeviceToHost, s));
+    RAMP_HIP_CHECK(hipStreamSynchronize(s));      // (the key reads g_host)
+  }
+  c->g_weight_cur = c->g_weight;      // (run_sample clears it when the job returns)
+  return 0;
+}
+
+// The scene batch: its APF clouds where it brings them, and the trajectory -> scene table for every kernel that indexes by scene (the APF, the
+// guide, the potential)
+static int stage_scenes(ramp_ctx* c, const SampleJob& job, hipStream_t s) {
+  const ramp_scene_batch* sc = job.sc;
+  if (sc->cloud_points) {
+    CK(stage_apf(c, job.p->apf, sc->cloud_points, sc->cloud_offset_host[sc->n_scenes], s));
+    CK(stage_table(c, c->s_scene_off, c->s_scene_off_cap, sc->cloud_offset_host, (size_t)sc->n_scenes + 1, 0, hipMemcpyHostToDevice, s));
+  }
+  if (sc->cloud_points || job.cg || job.resampling())
+    CK(stage_table(c, c->s_traj_scene, c->s_traj_scene_cap, sc->traj_scene, (size_t)job.p->B, 0, hipMemcpyDeviceToDevice, s));
+  return 0;
+}
+// (a single-scene job's key has no such tail.  With clouds the job reads s_scene_off, and s_cloud holds that many points of that many scenes:
+// kernel arguments; s_traj_scene exists with them, or with the `scenes` word of key_guide / key_resample)
+static void key_scenes(Key& key, const ramp_scene_batch* sc) {
+  const int tag[3] = {0x5343454e /* "SCEN" */, sc->cloud_points ? sc->n_scenes : 0, sc->cloud_points ? sc->cloud_offset_host[sc->n_scenes] : 0}; key.put(tag, 3);
+}
+
+// Langevin refinement (ramp_sample_mcmc).  kind 0, or no inner step anywhere, is the plain job: mj.total stays 0
+static int check_mcmc(SampleJob& job) {
+  const std::string w = std::string(job.who) + ": ";
+  const ramp_sample_params* p = job.p; const McmcJob* m = &job.mj; const float *mcmc_noise = job.mcmc_noise, *mcmc_u = job.mcmc_u;
+  const int kind = m->kind;
+  if (kind == 0) return 0;      // (off)
+  RAMP_REQUIRE(p->predict_x0 == 0, w + "predict_x0 != 0 -- the combined network output is then x0, not a score: there is no density to correct");
+  RAMP_REQUIRE(p->n_steps > 0 && m->n_inner && m->step_size && m->sigma, w + "missing n_inner / step_size / sigma arrays");
+  for (int j = 0; j < p->n_steps; ++j) {
+    RAMP_REQUIRE(m->n_inner[j] >= 0 && m->n_inner[j] <= RAMP_MCMC_MAX_INNER, w + "n_inner outside 0 .. 16");
+    if (m->n_inner[j] == 0) continue;
+    RAMP_REQUIRE(std::isfinite(m->step_size[j]) && m->step_size[j] > 0.f, w + "step_size must be positive and finite where n_inner > 0");
+    RAMP_REQUIRE(std::isfinite(m->sigma[j]) && m->sigma[j] > 0.f, w + "sigma must be positive and finite where n_inner > 0");
+    job.mj.total += m->n_inner[j];
+  }
+  if (job.mj.total > 0 && p->noise_mode == 0) {
+    RAMP_REQUIRE(mcmc_noise, w + "null mcmc_noise (noise_mode 0 injects the inner steps' normals)");
+    RAMP_REQUIRE(kind != 2 || mcmc_u, w + "null mcmc_u (noise_mode 0 injects MALA's uniforms)");
+  }
+  return 0;
+}
+static int grow_mcmc(ramp_ctx* c, const ramp_sample_params* p, const McmcJob* mj) {
+  const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
+  const size_t n = (size_t)B * H * S, nk = (size_t)mj->total, rows = (size_t)B * p->n_rp;
+  if ((size_t)B > c->m_cap_B) { CK(renew(c, c->m_xp, n)); CK(renew(c, c->m_eps, n)); CK(renew(c, c->m_eps_p, n)); c->m_cap_B = B; }
+  CK(grow(c, c->m_noise, c->m_noise_cap, nk * n));
+  if (nk * B > c->m_u_cap) { CK(renew(c, c->m_u, nk * B)); CK(renew(c, c->m_flag, nk * B)); c->m_u_cap = nk * B; }
+  if (mj->kind == 2) {      // MALA alone asks for energies: f of every row, the rows' energies, the combined energy of state and proposal
+    CK(grow(c, c->m_f, c->m_f_cap, rows * H * S));
+    CK(grow(c, c->m_Erows, c->m_Erows_cap, rows));
+    if ((size_t)B > c->m_E_cap) { CK(renew(c, c->m_E, (size_t)B)); CK(renew(c, c->m_Ep, (size_t)B)); c->m_E_cap = B; }
+  }
+  return 0;
+}
+// (the m_* buffers exist only for such a job, the energies' only for kind 2; the counts and step sizes are kernel arguments of the captured nodes)
+static void key_mcmc(Key& key, const McmcJob* mj, int n_steps) {
+  const int tag[2] = {0x4d434d43 /* "MCMC" */, mj->kind}; key.put(tag, 2);
+  key.put(mj->n_inner, n_steps); key.put(mj->step_size, n_steps); key.put(mj->sigma, n_steps);
+}
+
+// The cost guide and the two tables that travel with it, tried in the order team, primitives, guide.  A table that does not change the guide
+// (one agent per team or w_team == 0; no primitive or w_prim == 0) is dropped, and a guide without an iteration anywhere is the unguided job
+static int check_guide(ramp_ctx* c, SampleJob& job) {
+  const std::string w = std::string(job.who) + ": ";
+  const ramp_sample_params* p = job.p; const ramp_scene_batch* scenes = job.sc;
+  const ramp_cost_guide* cg = job.cg; const ramp_prim_guide* pg = job.pg; const ramp_team_guide* tg = job.tg;
+  if (tg) {
+    RAMP_REQUIRE(cg, w + "a team table needs its cost guide");
+    CK(check_cost_guide(cg, c->cfg.state_dim, job.who));
+    CK(check_team_guide(tg, p->B, c->cfg.horizon, job.who));
+    RAMP_REQUIRE(p->philox_total == 0 || p->philox_sample0 % tg->team_size == 0, w + "a shard must hold whole teams (philox_sample0 % team_size == 0)");
+    if (!team_guide_active(tg)) job.tg = nullptr;
+  }
+  if (pg) {
+    RAMP_REQUIRE(cg, w + "a primitive table needs its cost guide");
+    CK(check_cost_guide(cg, c->cfg.state_dim, job.who));
+    CK(check_prim_guide(pg, cg, c->cfg.horizon, c->cfg.state_dim, job.who));
+    if (!prim_guide_active(pg)) job.pg = nullptr;
+  }
+  if (!cg) return 0;
+  int guide_total = 0;
+  CK(check_cost_guide(cg, c->cfg.state_dim, job.who));
+  RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the guide kernel serves horizons up to 128");
+  RAMP_REQUIRE(scenes ? cg->n_scenes == scenes->n_scenes : cg->n_scenes == 1,
+               w + "the guide's n_scenes must equal the scene batch's (1 without a scene batch)");
+  RAMP_REQUIRE(p->n_steps > 0 && cg->n_guide && cg->step, w + "missing n_guide / step arrays");
+  for (int j = 0; j < p->n_steps; ++j) {
+    RAMP_REQUIRE(cg->n_guide[j] >= 0 && cg->n_guide[j] <= RAMP_GUIDE_MAX_STEPS, w + "n_guide outside 0 .. RAMP_GUIDE_MAX_STEPS");
+    RAMP_REQUIRE(std::isfinite(cg->step[j]), w + "step must be finite");
+    guide_total += cg->n_guide[j];
+  }
+  if (guide_total == 0) { job.cg = nullptr; job.pg = nullptr; job.tg = nullptr; }
+  return 0;
+}
+// a table of per-scene clouds -- device points (points, point_dim), host offsets (n_scenes + 1) -- into one of the context's buffer pairs: the
+// guide's own cloud table and the potential's (the trajectory -> scene table is the scene batch's, stage_scenes)
+static int stage_cloud_table(ramp_ctx* c, const ramp_cost_guide* t, float*& cloud, size_t& cloud_cap, int*& off, size_t& off_cap, hipStream_t s) {
+  const size_t points = (size_t)t->cloud_offset_host[t->n_scenes];
+  CK(stage_table(c, cloud, cloud_cap, t->cloud_points, points * t->point_dim, 4, hipMemcpyDeviceToDevice, s));
+  return stage_table(c, off, off_cap, t->cloud_offset_host, (size_t)t->n_scenes + 1, 0, hipMemcpyHostToDevice, s);
+}
+static int stage_guide(ramp_ctx* c, const SampleJob& job, hipStream_t s) {
+  CK(stage_cloud_table(c, job.cg, c->cg_cloud, c->cg_cloud_cap, c->cg_off, c->cg_off_cap, s));
+  const ramp_prim_guide* pg = job.pg;
+  if (!pg) return 0;      // with primitives: their tables, staged like the clouds
+  const size_t D = pg->point_dim, no = (size_t)pg->n_scenes + 1;
+  const size_t boxes = pg->box_offset_host[pg->n_scenes], spheres = pg->sphere_offset_host[pg->n_scenes];
+  CK(stage_table(c, c->pg_boxc, c->pg_boxc_cap, pg->box_centers, boxes * D, 4, hipMemcpyDeviceToDevice, s));
+  CK(stage_table(c, c->pg_boxs, c->pg_boxs_cap, pg->box_sizes, boxes * D, 4, hipMemcpyDeviceToDevice, s));
+  CK(stage_table(c, c->pg_sphc, c->pg_sphc_cap, pg->sphere_centers, spheres * D, 4, hipMemcpyDeviceToDevice, s));
+  CK(stage_table(c, c->pg_sphr, c->pg_sphr_cap, pg->sphere_radii, spheres, 4, hipMemcpyDeviceToDevice, s));
+  CK(stage_table(c, c->pg_boff, c->pg_boff_cap, pg->box_offset_host, no, 0, hipMemcpyHostToDevice, s));
+  return stage_table(c, c->pg_soff, c->pg_soff_cap, pg->sphere_offset_host, no, 0, hipMemcpyHostToDevice, s);
+}
+static void key_guide(Key& key, const SampleJob& job) {
+  // (cg_cloud / cg_off exist only for such a job, s_traj_scene with `scenes`; counts, step sizes and scalars are kernel arguments of the captured nodes)
+  const ramp_cost_guide* cg = job.cg;
+  const int tag[5] = {0x47554944 /* "GUID" */, cg->point_dim, cg->n_scenes, cg->cloud_offset_host[cg->n_scenes], job.sc ? 1 : 0}; key.put(tag, 5);
+  const double sc5[5] = {cg->radius, cg->w_obs, cg->w_smooth, cg->w_acc, cg->max_norm}; key.put(sc5, 5);
+  key.put(cg->n_guide, job.p->n_steps); key.put(cg->step, job.p->n_steps);
+  if (const ramp_prim_guide* pg = job.pg) {      // (the pg_* buffers exist only for such a job; counts, n_sub and the three scalars are kernel arguments of the captured nodes)
+    const int ptag[5] = {0x5052494d /* "PRIM" */, pg->n_scenes, pg->box_offset_host[pg->n_scenes], pg->sphere_offset_host[pg->n_scenes], pg->n_sub}; key.put(ptag, 5);
+    const double sc3[3] = {pg->margin, pg->band, pg->w_prim}; key.put(sc3, 3);
+  }
+  if (const ramp_team_guide* tg = job.tg) {      // (no buffer of its own; the team size and the two scalars are kernel arguments of the captured nodes)
+    const int ttag[2] = {0x5445414d /* "TEAM" */, tg->team_size}; key.put(ttag, 2);
+    const double sc2[2] = {tg->radius_team, tg->w_team}; key.put(sc2, 2);
+  }
+}
+
+// Resampling events (ramp_sample_steered); the entry hands over only a table with a flag set
+static int check_resample(ramp_ctx* c, const SampleJob& job) {
+  const ResampleJob* rj = job.resampling();
+  if (!rj) return 0;
+  const std::string w = std::string(job.who) + ": ";
+  const ramp_sample_params* p = job.p; const ramp_scene_batch* scenes = job.sc; const ramp_resample_params* rs = rj->rs; const McmcJob& mj = job.mj;
+  RAMP_REQUIRE(resample_group_table_fault(rs->group_first_host, rs->n_groups, p->B) == 0,
+               w + "malformed group table (n_groups >= 1, [0] = 0, strictly increasing, [n_groups] = B)");
+  RAMP_REQUIRE(resample_ess_frac_ok(rs->ess_frac), w + "ess_frac must be finite and lie in [0, 2]");
+  RAMP_REQUIRE(rs->lambda, w + "missing lambda array");
+  for (int j = 0; j < p->n_steps; ++j) RAMP_REQUIRE(std::isfinite(rs->lambda[j]), w + "lambda must be finite");
+  RAMP_REQUIRE(rj->n_events <= RAMP_RESAMPLE_MAX_EVENTS, w + "more than RAMP_RESAMPLE_MAX_EVENTS events");
+  RAMP_REQUIRE(!p->ddim || mj.total > 0, w + "DDIM (eta = 0) never separates duplicates: resampling needs MCMC inner steps there");
+  RAMP_REQUIRE(p->predict_x0 == 0, w + "predict_x0 != 0 is not served with resampling");
+  CK(check_cost_guide(rs->cost, c->cfg.state_dim, job.who));
+  RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the cost kernel serves horizons up to 128");
+  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the gather moves four elements per access)");
+  RAMP_REQUIRE(scenes ? rs->cost->n_scenes == scenes->n_scenes : rs->cost->n_scenes == 1,
+               w + "the potential's n_scenes must equal the scene batch's (1 without a scene batch)");
+  RAMP_REQUIRE(rs->group0 >= 0 && rs->groups_total >= 0 && (rs->groups_total == 0 ? rs->group0 == 0 : rs->group0 + rs->n_groups <= rs->groups_total),
+               w + "group0 + n_groups must lie inside groups_total");
+  RAMP_REQUIRE(p->noise_mode != 0 || rj->u, w + "null resample_u (noise_mode 0 injects the events' uniforms)");
+  return 0;
+}
+// the potential's own cloud table, the group table and (noise_mode 0) the uniforms
+static int stage_resample(ramp_ctx* c, const SampleJob& job, hipStream_t s) {
+  const ResampleJob* rj = job.resampling(); const ramp_resample_params* rs = rj->rs;
+  const size_t B = (size_t)job.p->B, n = B * c->cfg.horizon * c->cfg.state_dim, ne = (size_t)rj->n_events, ng = (size_t)rs->n_groups;
+  CK(grow(c, c->rs_state, c->rs_state_cap, 4 * B)); CK(grow(c, c->rs_terms, c->rs_terms_cap, 3 * B));
+  CK(grow(c, c->rs_xtmp, c->rs_xtmp_cap, n));
+  CK(grow(c, c->rs_anc, c->rs_anc_cap, ne * B)); CK(grow(c, c->rs_ess, c->rs_ess_cap, ne * ng)); CK(grow(c, c->rs_cost, c->rs_cost_cap, ne * B));
+  CK(grow(c, c->rs_u, c->rs_u_cap, ne * ng));
+  CK(stage_cloud_table(c, rs->cost, c->rs_cloud, c->rs_cloud_cap, c->rs_off, c->rs_off_cap, s));
+  if (job.p->noise_mode == 0) RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_u, rj->u, ne * ng * 4, hipMemcpyDeviceToDevice, s));
+  return stage_table(c, c->rs_gf, c->rs_gf_cap, rs->group_first_host, ng + 1, 0, hipMemcpyHostToDevice, s);
+}
+// (the rs_* buffers exist only for such a job, s_traj_scene with `scenes`; flags, lambda, ess_frac, the scalars and the Philox group fields are
+// kernel arguments of the captured nodes)
+static void key_resample(Key& key, const SampleJob& job) {
+  const ResampleJob* rj = job.resampling(); const ramp_resample_params* rs = rj->rs; const ramp_cost_guide* rc = rs->cost;
+  const int tag[9] = {0x52534d50 /* "RSMP" */, rs->n_groups, rj->n_events, rs->group0, rs->groups_total, rc->point_dim, rc->n_scenes,
+                      rc->cloud_offset_host[rc->n_scenes], job.sc ? 1 : 0}; key.put(tag, 9);
+  const double sc5[5] = {rs->ess_frac, rc->radius, rc->w_obs, rc->w_smooth, rc->w_acc}; key.put(sc5, 5);
+  key.put(rs->resample, job.p->n_steps); key.put(rs->lambda, job.p->n_steps);
+}
+
+// Stitched windows (ramp_sample_stitched, the only entry that brings a table)
+static int check_stitch_job(ramp_ctx* c, const SampleJob& job) {
+  const ramp_stitch* st = job.st; const ramp_sample_params* p = job.p;
+  if (!st) return 0;
+  const std::string w = std::string(job.who) + ": ";
+  CK(check_stitch(st, p->B, c->cfg.horizon, job.who));
+  RAMP_REQUIRE(p->n_hard == 0, w + "p->n_hard must be 0 (the pins are the job's conditions)");
+  RAMP_REQUIRE(p->philox_total == 0, w + "a sharded job is not served (the windows of a chain must sit in one shard)");
+  return 0;
+}
+// {alpha | zeros} and the pin values
+static int stage_stitch(ramp_ctx* c, const SampleJob& job, hipStream_t s) {
+  const ramp_stitch* st = job.st;
+  const int O = st->n_windows > 1 ? st->overlap : 0;
+  std::vector<float> al(2 * (size_t)O, 0.f);
+  for (int k = 0; k < O; ++k) al[k] = st->alpha_host[k];
+  const size_t pv = (size_t)st->n_pin * (job.p->B / st->n_windows) * c->cfg.state_dim;
+  // (al is pageable host memory: its copy is staged before the call returns, so the vector may go out of scope)
+  CK(stage_table(c, c->st_alpha, c->st_alpha_cap, (const float*)al.data(), al.size(), 4, hipMemcpyHostToDevice, s));
+  return stage_table(c, c->st_pin_val, c->st_pin_val_cap, st->pin_val, pv, 4, hipMemcpyDeviceToDevice, s);
+}
+// (st_alpha / st_pin_val exist only for such a job; the layout and the pin indices are kernel arguments of the captured nodes)
+static void key_stitch(Key& key, const ramp_stitch* st) {
+  const int tag[4] = {0x53544348 /* "STCH" */, st->n_windows, st->n_windows > 1 ? st->overlap : 0, st->n_pin}; key.put(tag, 4);
+  if (st->n_pin) key.put(st->pin_idx_host, st->n_pin);
+}
+
+// A checked job (run_sample): parameter checks, buffers, staging, the canonical calibration, the graph and the copy-out
+static int sample_job(ramp_ctx* c, const SampleJob& job, void* stream) {
+  const ramp_sample_params* p = job.p; const ramp_scene_batch* sc = job.sc; const ramp_guidance_rows* g = job.g; const float* noise = job.noise;
+  const McmcJob* mj = job.mcmc(); const ResampleJob* rj = job.resampling();
   RAMP_REQUIRE(p->noise_mode == 0 || p->noise_mode == 1, "noise_mode must be 0 (injected) or 1 (Philox inside the job)");
   RAMP_REQUIRE(p->philox_total == 0 || (p->philox_sample0 >= 0 && p->philox_sample0 + p->B <= p->philox_total), "philox shard outside the job (philox_sample0 + B <= philox_total)");
   RAMP_REQUIRE(p->noise_mode == 0 || (c->cfg.horizon * c->cfg.state_dim) % 4 == 0, "noise_mode 1 needs H * S to be a multiple of 4");
@@ -2288,137 +2535,41 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   RAMP_REQUIRE(p->n_hard == 0 || (p->hard_idx_host && p->hard_val), "missing hard conditions");
   hipStream_t s = as_stream(stream);
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
-  const size_t n = (size_t)B * H * S;
-  const bool chain = chain_out != nullptr;
-  const size_t n_noise = (p->ddim ? 1 : (size_t)p->n_steps + 1) * n;
+  const size_t n = (size_t)B * H * S, n_noise = (p->ddim ? 1 : (size_t)p->n_steps + 1) * n;
+  const bool chain = job.chain_out != nullptr;
   CK(ensure_sampler_buffers(c, B, p->n_rp, p->n_steps, chain));
   const int n_evals = p->n_steps + (mj ? mj->total : 0);
   CK(grow(c, c->trip_log, c->trip_log_cap, (size_t)std::max(256, n_evals)));
-  if (mj) {
-    const size_t nk = (size_t)mj->total, rows = (size_t)B * p->n_rp;
-    if ((size_t)B > c->m_cap_B) { CK(renew(c, c->m_xp, n)); CK(renew(c, c->m_eps, n)); CK(renew(c, c->m_eps_p, n)); c->m_cap_B = B; }
-    CK(grow(c, c->m_noise, c->m_noise_cap, nk * n));
-    if (nk * B > c->m_u_cap) { CK(renew(c, c->m_u, nk * B)); CK(renew(c, c->m_flag, nk * B)); c->m_u_cap = nk * B; }
-    if (mj->kind == 2) {      // MALA alone asks for energies: f of every row, the rows' energies, the combined energy of state and proposal
-      CK(grow(c, c->m_f, c->m_f_cap, rows * H * S));
-      CK(grow(c, c->m_Erows, c->m_Erows_cap, rows));
-      if ((size_t)B > c->m_E_cap) { CK(renew(c, c->m_E, (size_t)B)); CK(renew(c, c->m_Ep, (size_t)B)); c->m_E_cap = B; }
-    }
-  }
+  if (mj) CK(grow_mcmc(c, p, mj));
   for (int j = 0; j < p->n_hard; ++j) RAMP_REQUIRE(p->hard_idx_host[j] >= 0 && p->hard_idx_host[j] < H, "hard index out of range");
   if (!c->s_hard_idx) CK(renew(c, c->s_hard_idx, 256));
   RAMP_REQUIRE(p->n_hard <= 256, "too many hard conditions");
-  const size_t hv = (size_t)p->n_hard * B * S;
-  CK(grow(c, c->s_hard_val, c->s_hard_val_cap, hv));
   if (p->apf.cloud) CK(stage_apf(c, p->apf, p->apf.cloud, p->apf.n_points, s));
-  const bool sc_apf = sc && sc->cloud_points;
-  int sc_points = 0;
   if (sc) {
     RAMP_REQUIRE(!p->apf.cloud, "ramp_sample_scenes: apf.cloud must be NULL (the clouds come with the scene batch)");
-    CK(check_scene_batch(sc, sc_apf, "ramp_sample_scenes"));
+    CK(check_scene_batch(sc, sc->cloud_points != nullptr, "ramp_sample_scenes"));
+    CK(stage_scenes(c, job, s));
   }
-  if (sc_apf) {
-    sc_points = sc->cloud_offset_host[sc->n_scenes];
-    CK(stage_apf(c, p->apf, sc->cloud_points, sc_points, s));
-    CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));
-    CK(grow(c, c->s_scene_off, c->s_scene_off_cap, (size_t)sc->n_scenes + 1));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_scene_off, sc->cloud_offset_host, ((size_t)sc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
-  }
-  int gj_points = 0;
-  if (gj) {      // the guide's own cloud table; the trajectory -> scene table is the scene batch's
-    const ramp_cost_guide* cg = gj->cg;
-    gj_points = cg->cloud_offset_host[cg->n_scenes];
-    CK(grow(c, c->cg_cloud, c->cg_cloud_cap, std::max<size_t>(4, (size_t)gj_points * cg->point_dim)));
-    CK(grow(c, c->cg_off, c->cg_off_cap, (size_t)cg->n_scenes + 1));
-    if (gj_points) RAMP_HIP_CHECK(hipMemcpyAsync(c->cg_cloud, cg->cloud_points, (size_t)gj_points * cg->point_dim * 4, hipMemcpyDeviceToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->cg_off, cg->cloud_offset_host, ((size_t)cg->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
-    if (sc && !sc_apf) {
-      CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));
-      RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    }
-  }
-  int pg_boxes = 0, pg_spheres = 0;
-  if (gj && gj->pg) {      // the primitive tables, staged like the clouds
-    const ramp_prim_guide* pg = gj->pg;
-    const size_t D = pg->point_dim, no = (size_t)pg->n_scenes + 1;
-    pg_boxes = pg->box_offset_host[pg->n_scenes]; pg_spheres = pg->sphere_offset_host[pg->n_scenes];
-    CK(grow(c, c->pg_boxc, c->pg_boxc_cap, std::max<size_t>(4, pg_boxes * D))); CK(grow(c, c->pg_boxs, c->pg_boxs_cap, std::max<size_t>(4, pg_boxes * D)));
-    CK(grow(c, c->pg_sphc, c->pg_sphc_cap, std::max<size_t>(4, pg_spheres * D))); CK(grow(c, c->pg_sphr, c->pg_sphr_cap, std::max<size_t>(4, (size_t)pg_spheres)));
-    CK(grow(c, c->pg_boff, c->pg_boff_cap, no)); CK(grow(c, c->pg_soff, c->pg_soff_cap, no));
-    if (pg_boxes) {
-      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_boxc, pg->box_centers, pg_boxes * D * 4, hipMemcpyDeviceToDevice, s));
-      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_boxs, pg->box_sizes, pg_boxes * D * 4, hipMemcpyDeviceToDevice, s));
-    }
-    if (pg_spheres) {
-      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_sphc, pg->sphere_centers, pg_spheres * D * 4, hipMemcpyDeviceToDevice, s));
-      RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_sphr, pg->sphere_radii, (size_t)pg_spheres * 4, hipMemcpyDeviceToDevice, s));
-    }
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_boff, pg->box_offset_host, no * 4, hipMemcpyHostToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->pg_soff, pg->sphere_offset_host, no * 4, hipMemcpyHostToDevice, s));
-  }
-  int rj_points = 0;
-  if (rj) {      // the potential's own cloud table, the group table and (noise_mode 0) the uniforms
-    const ramp_resample_params* rs = rj->rs;
-    const ramp_cost_guide* rc = rs->cost;
-    const size_t ne = (size_t)rj->n_events, ng = (size_t)rs->n_groups;
-    rj_points = rc->cloud_offset_host[rc->n_scenes];
-    CK(grow(c, c->rs_state, c->rs_state_cap, 4 * (size_t)B)); CK(grow(c, c->rs_terms, c->rs_terms_cap, 3 * (size_t)B));
-    CK(grow(c, c->rs_xtmp, c->rs_xtmp_cap, n));
-    CK(grow(c, c->rs_anc, c->rs_anc_cap, ne * B)); CK(grow(c, c->rs_ess, c->rs_ess_cap, ne * ng)); CK(grow(c, c->rs_cost, c->rs_cost_cap, ne * B));
-    CK(grow(c, c->rs_u, c->rs_u_cap, ne * ng)); CK(grow(c, c->rs_gf, c->rs_gf_cap, ng + 1));
-    CK(grow(c, c->rs_cloud, c->rs_cloud_cap, std::max<size_t>(4, (size_t)rj_points * rc->point_dim)));
-    CK(grow(c, c->rs_off, c->rs_off_cap, (size_t)rc->n_scenes + 1));
-    if (rj_points) RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_cloud, rc->cloud_points, (size_t)rj_points * rc->point_dim * 4, hipMemcpyDeviceToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_off, rc->cloud_offset_host, ((size_t)rc->n_scenes + 1) * 4, hipMemcpyHostToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_gf, rs->group_first_host, (ng + 1) * 4, hipMemcpyHostToDevice, s));
-    if (p->noise_mode == 0) RAMP_HIP_CHECK(hipMemcpyAsync(c->rs_u, rj->u, ne * ng * 4, hipMemcpyDeviceToDevice, s));
-    if (sc && !sc_apf && !gj) {
-      CK(grow(c, c->s_traj_scene, c->s_traj_scene_cap, (size_t)B));
-      RAMP_HIP_CHECK(hipMemcpyAsync(c->s_traj_scene, sc->traj_scene, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
-    }
-  }
-  if (sj) {      // {alpha | zeros} and the pin values
-    const ramp_stitch* st = sj->st;
-    const int O = st->n_windows > 1 ? st->overlap : 0;
-    std::vector<float> al(2 * (size_t)O, 0.f);
-    for (int k = 0; k < O; ++k) al[k] = st->alpha_host[k];
-    const size_t pv = (size_t)st->n_pin * (B / st->n_windows) * S;
-    CK(grow(c, c->st_alpha, c->st_alpha_cap, std::max<size_t>(4, al.size())));
-    CK(grow(c, c->st_pin_val, c->st_pin_val_cap, std::max<size_t>(4, pv)));
-    if (O) RAMP_HIP_CHECK(hipMemcpyAsync(c->st_alpha, al.data(), al.size() * 4, hipMemcpyHostToDevice, s));      // (pageable host memory: staged before the call returns)
-    if (pv) RAMP_HIP_CHECK(hipMemcpyAsync(c->st_pin_val, st->pin_val, pv * 4, hipMemcpyDeviceToDevice, s));
-  }
-  std::vector<float> g_host;      // the weights on the host: part of the canonical calibration's key below
-  if (g) {
-    const size_t nw = (size_t)B * p->n_rp;
-    CK(grow(c, c->g_weight, c->g_weight_cap, nw));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->g_weight, g->row_weight, nw * 4, hipMemcpyDeviceToDevice, s));
-    if (c->gemm_mode == 2 && !c->force_x6 && c->cal_reuse) {
-      g_host.resize(nw);
-      RAMP_HIP_CHECK(hipMemcpyAsync(g_host.data(), c->g_weight, nw * 4, hipMemcpyDeviceToHost, s));
-      RAMP_HIP_CHECK(hipStreamSynchronize(s));
-    }
-    c->g_weight_cur = c->g_weight;      // (the entry point clears it when this function returns)
-  }
-  if (p->n_hard) {
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
-    RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_val, p->hard_val, hv * 4, hipMemcpyDeviceToDevice, s));
-  }
+  if (job.cg) CK(stage_guide(c, job, s));
+  if (rj) CK(stage_resample(c, job, s));
+  if (job.st) CK(stage_stitch(c, job, s));
+  std::vector<float> g_host;      // a composed job's weights on the host: part of the canonical calibration's key below
+  if (g) CK(stage_guidance(c, job, s, g_host));
+  if (p->n_hard) RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
+  CK(stage_table(c, c->s_hard_val, c->s_hard_val_cap, p->hard_val, (size_t)p->n_hard * B * S, 0, hipMemcpyDeviceToDevice, s));
   if (p->noise_mode == 1) {
     if (!c->s_philox) CK(renew(c, c->s_philox, 2));
     const unsigned long long rec[2] = {p->philox_seed, p->philox_offset};
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_philox, rec, 16, hipMemcpyHostToDevice, s));     // (pageable host memory: the copy is staged before the call returns)
   } else {
     RAMP_HIP_CHECK(hipMemcpyAsync(c->s_noise, noise, n_noise * 4, hipMemcpyDeviceToDevice, s));
-    if (mj) RAMP_HIP_CHECK(hipMemcpyAsync(c->m_noise, mcmc_noise, (size_t)mj->total * n * 4, hipMemcpyDeviceToDevice, s));
-    if (mj && mj->kind == 2) RAMP_HIP_CHECK(hipMemcpyAsync(c->m_u, mcmc_u, (size_t)mj->total * B * 4, hipMemcpyDeviceToDevice, s));
+    if (mj) RAMP_HIP_CHECK(hipMemcpyAsync(c->m_noise, job.mcmc_noise, (size_t)mj->total * n * 4, hipMemcpyDeviceToDevice, s));
+    if (mj && mj->kind == 2) RAMP_HIP_CHECK(hipMemcpyAsync(c->m_u, job.mcmc_u, (size_t)mj->total * B * 4, hipMemcpyDeviceToDevice, s));
   }
   c->launches = 0;
   invalidate_calibrations(c, CAL_SCORE | CAL_REPLAN);      // the loop below overwrites the delayed-scaling tables
-  // key: everything baked into the captured nodes.  It also carries whatever decides that the job touches a buffer that may not exist yet
-  // (s_chain: ch; s_cloud / s_window: has_apf and apply_apf; s_hard_val: n_hard; s_philox: noise_mode; the scene tables: the SCEN tag; g_weight: the COMP tag) --
-  // renew() relies on that when it lets a first allocation pass without dropping the graphs: add the field here with any new optional buffer
+  // key: everything baked into the captured nodes, and whatever decides that the job touches a buffer that may not exist yet (s_chain: ch;
+  // s_cloud / s_window: has_apf and apply_apf; s_hard_val: n_hard; s_philox: noise_mode; g_weight: the COMP tag); the options add their own
   Key key;
   const double kw0 = g ? 0.0 : p->w0, kw1 = g ? 0.0 : p->w1;      // (a composed job's weights are data of the graph, not part of its shape)
   key.put(p->B); key.put(p->n_rp); key.put(p->n_steps); key.put(p->ddim); key.put(kw0); key.put(kw1);
@@ -2432,40 +2583,12 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
   const int has_apf = p->apf.cloud != nullptr; key.put(has_apf);
   key.put(p->apf.n_points); key.put(p->apf.window); key.put(p->apf.threshold); key.put(p->apf.strength); key.put(p->apf.passes);
   const int ch = chain; key.put(ch); key.put(c->force_x6); key.put(p->noise_mode);
-  if (sc) { const int tag[3] = {0x5343454e /* "SCEN" */, sc_apf ? sc->n_scenes : 0, sc_points}; key.put(tag, 3); }      // (a single-scene job's key has no such tail)
   if (g) { const int tag = 0x434f4d50 /* "COMP" */; key.put(tag); }
-  if (mj) {      // (the m_* buffers exist only for such a job; the step sizes are kernel arguments of the captured nodes)
-    const int tag[2] = {0x4d434d43 /* "MCMC" */, mj->kind}; key.put(tag, 2);
-    key.put(mj->n_inner, p->n_steps); key.put(mj->step_size, p->n_steps); key.put(mj->sigma, p->n_steps);
-  }
-  if (gj) {      // (cg_cloud / cg_off exist only for such a job; counts, step sizes and scalars are kernel arguments of the captured nodes)
-    const ramp_cost_guide* cg = gj->cg;
-    const int tag[5] = {0x47554944 /* "GUID" */, cg->point_dim, cg->n_scenes, gj_points, sc ? 1 : 0}; key.put(tag, 5);
-    const double sc5[5] = {cg->radius, cg->w_obs, cg->w_smooth, cg->w_acc, cg->max_norm}; key.put(sc5, 5);
-    key.put(cg->n_guide, p->n_steps); key.put(cg->step, p->n_steps);
-    if (gj->pg) {      // (the pg_* buffers exist only for such a job; counts, n_sub and the three scalars are kernel arguments of the captured nodes)
-      const ramp_prim_guide* pg = gj->pg;
-      const int ptag[5] = {0x5052494d /* "PRIM" */, pg->n_scenes, pg_boxes, pg_spheres, pg->n_sub}; key.put(ptag, 5);
-      const double sc3[3] = {pg->margin, pg->band, pg->w_prim}; key.put(sc3, 3);
-    }
-    if (gj->tg) {      // (no buffer of its own; the team size and the two scalars are kernel arguments of the captured nodes)
-      const int ttag[2] = {0x5445414d /* "TEAM" */, gj->tg->team_size}; key.put(ttag, 2);
-      const double sc2[2] = {gj->tg->radius_team, gj->tg->w_team}; key.put(sc2, 2);
-    }
-  }
-  if (rj) {      // (the rs_* buffers exist only for such a job; flags, lambda, ess_frac, the scalars and the Philox group fields are kernel arguments)
-    const ramp_resample_params* rs = rj->rs;
-    const ramp_cost_guide* rc = rs->cost;
-    const int tag[9] = {0x52534d50 /* "RSMP" */, rs->n_groups, rj->n_events, rs->group0, rs->groups_total, rc->point_dim, rc->n_scenes, rj_points, sc ? 1 : 0};
-    key.put(tag, 9);
-    const double sc5[5] = {rs->ess_frac, rc->radius, rc->w_obs, rc->w_smooth, rc->w_acc}; key.put(sc5, 5);
-    key.put(rs->resample, p->n_steps); key.put(rs->lambda, p->n_steps);
-  }
-  if (sj) {      // (st_alpha / st_pin_val exist only for such a job; the layout and the pin indices are kernel arguments of the captured nodes)
-    const ramp_stitch* st = sj->st;
-    const int tag[4] = {0x53544348 /* "STCH" */, st->n_windows, st->n_windows > 1 ? st->overlap : 0, st->n_pin}; key.put(tag, 4);
-    if (st->n_pin) key.put(st->pin_idx_host, st->n_pin);
-  }
+  if (sc) key_scenes(key, sc);
+  if (mj) key_mcmc(key, mj, p->n_steps);
+  if (job.cg) key_guide(key, job);
+  if (rj) key_resample(key, job);
+  if (job.st) key_stitch(key, job.st);
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
@@ -2499,11 +2622,11 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       c->launches = 0;
     }
   }
-  staging_done(c);
+  staging_done(c);      // (after the last grow, before the graph key is compared)
   const int cal_eval = (h3 && c->rerun) ? c->trip_eval : -1;
   c->last_job_steps = h3 ? n_evals : 0;
   if (!p->use_graph) {
-    CK(sample_body(c, p, sc, s, chain, steady, cal_eval, mj, gj, rj, sj));
+    CK(sample_body(c, job, s, chain, steady, cal_eval));
   } else {
     if (key.bytes != c->graph_key) { drop_graphs(c->s_graph, 3); c->graph_key = key.bytes; c->graph_rerun_key.clear(); }
     hipGraphExec_t* slot = &c->s_graph[steady ? 1 : 0];
@@ -2513,9 +2636,9 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
       if (rk.bytes != c->graph_rerun_key) drop_graphs(slot, 1);
       c->graph_rerun_key = rk.bytes;
     }
-    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, p, sc, cs, chain, steady, cal_eval, mj, gj, rj, sj); }));
+    CK(replay(slot, s, [&](hipStream_t cs) { return sample_body(c, job, cs, chain, steady, cal_eval); }));
   }
-  if (mj && accept_out) RAMP_HIP_CHECK(hipMemcpyAsync(accept_out, c->m_flag, (size_t)mj->total * B * sizeof(int), hipMemcpyDeviceToDevice, s));
+  if (mj && job.accept_out) RAMP_HIP_CHECK(hipMemcpyAsync(job.accept_out, c->m_flag, (size_t)mj->total * B * sizeof(int), hipMemcpyDeviceToDevice, s));
   if (rj) {
     const size_t ne = (size_t)rj->n_events, ng = (size_t)rj->rs->n_groups;
     if (rj->ancestor_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->ancestor_out, c->rs_anc, ne * B * sizeof(int), hipMemcpyDeviceToDevice, s));
@@ -2523,140 +2646,70 @@ static int sample_job(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene
     if (rj->cost_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->cost_out, c->rs_cost, ne * B * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (rj->logw_out) RAMP_HIP_CHECK(hipMemcpyAsync(rj->logw_out, c->rs_state, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, s));
   }
-  if (chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
-  if (x_out) RAMP_HIP_CHECK(hipMemcpyAsync(x_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
+  if (job.chain_out) RAMP_HIP_CHECK(hipMemcpyAsync(job.chain_out, c->s_chain, (size_t)(p->n_steps + 1) * n * 4, hipMemcpyDeviceToDevice, s));
+  if (job.x_out) RAMP_HIP_CHECK(hipMemcpyAsync(job.x_out, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
   return 0;
 }
 
-int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, float* chain_out, float* x_out,
-                void* stream) {
-  return sample_job(c, p, nullptr, noise, chain_out, x_out, stream);
+// The one runner behind the nine entries (each has made its own null checks): plain (g, scenes NULL), many-scene (scenes) and composed (g)
+// jobs with whatever options the entry has a slot for.  The option checks run in the order in which refusals have always been tried (the first
+// message wins) and switch off what changes nothing; a job whose options are all off is the plain entry's, bit for bit.
+static int run_sample(ramp_ctx* c, const SampleJob& stated, void* stream) {
+  SampleJob job = stated;
+  const std::string w = std::string(job.who) + ": ";
+  const int kind = job.mj.kind;
+  const int rc = [&]() -> int {
+    CK(check_stitch_job(c, job));
+    RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");      // (in front of the guidance table's checks)
+    if (job.g) CK(check_guidance(c, job.p, job.g, job.who));
+    CK(check_mcmc(job)); CK(check_guide(c, job)); CK(check_resample(c, job));
+    return sample_job(c, job, stream);
+  }();
+  c->g_weight_cur = nullptr;      // on every return path
+  return rc;
+}
+// what the entries of the ramp_sample_mcmc family have in common
+static SampleJob refined_job(const char* who, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
+                             const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
+                             const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out) {
+  const McmcJob mj = m ? McmcJob{m->kind, m->n_inner, m->step_size, m->sigma, 0} : McmcJob{0, nullptr, nullptr, nullptr, 0};
+  return SampleJob{who, p, scenes, noise, chain_out, x_out, g, cg, mj, mcmc_noise, mcmc_u, accept_out};
 }
 
-int ramp_sample_scenes(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* scenes, const float* noise, float* chain_out,
-                       float* x_out, void* stream) {
+int ramp_sample(ramp_ctx* c, const ramp_sample_params* p, const float* noise, float* chain_out, float* x_out, void* stream) {
+  RAMP_REQUIRE(c && p, "null argument");
+  return run_sample(c, SampleJob{"ramp_sample", p, nullptr, noise, chain_out, x_out}, stream);
+}
+
+int ramp_sample_scenes(ramp_ctx* c, const ramp_sample_params* p, const ramp_scene_batch* scenes, const float* noise, float* chain_out, float* x_out, void* stream) {
   RAMP_REQUIRE(scenes, "null scene batch");
-  return sample_job(c, p, scenes, noise, chain_out, x_out, stream);
-}
-
-// what a guidance table must satisfy, for both entries that take one (`who` names the entry in the message)
-static int check_guidance(ramp_ctx* c, const ramp_sample_params* p, const ramp_guidance_rows* g, const char* who) {
-  const std::string w = std::string(who) + ": ";
-  RAMP_REQUIRE(g->row_weight, w + "null row_weight");
-  RAMP_REQUIRE(g->n_rp >= 2 && g->n_rp <= RAMP_MAX_ROWS_PER_TRAJ, w + "n_rp outside 2 .. RAMP_MAX_ROWS_PER_TRAJ");
-  RAMP_REQUIRE(g->n_rp == p->n_rp, w + "the guidance table's n_rp differs from the job's");
-  RAMP_REQUIRE(p->B > 0 && (long)p->B * p->n_rp <= (1l << 24), w + "bad batch");
-  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the guidance step moves four elements per access)");
-  RAMP_REQUIRE(c->rv_rows > 0, w + "the row -> latent table comes from ramp_set_scenes (none is in place)");
-  RAMP_REQUIRE(c->rv_rows >= p->B * p->n_rp, w + "the ramp_set_scenes table is shorter than B * n_rp rows");
-  return 0;
+  RAMP_REQUIRE(c && p, "null argument");
+  return run_sample(c, SampleJob{"ramp_sample_scenes", p, scenes, noise, chain_out, x_out}, stream);
 }
 
 // Composition over any number of obstacle sets (diffusion_model_static.py:188-229; diffusion_model_3d.py:163-182, three sets at :165-174) and many
-// scenes per job: rows and weights are data.  Every refusal is a host check made before anything is staged or launched.
+// scenes per job: rows and weights are data.
 int ramp_sample_composed(ramp_ctx* c, const ramp_sample_params* p, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
                          float* chain_out, float* x_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_composed: null argument");
   RAMP_REQUIRE(g, "ramp_sample_composed: null guidance table");
-  CK(check_guidance(c, p, g, "ramp_sample_composed"));
-  const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g);
-  c->g_weight_cur = nullptr;
-  return rc;
+  return run_sample(c, SampleJob{"ramp_sample_composed", p, scenes, noise, chain_out, x_out, g}, stream);
 }
 
-// Langevin refinement and cost-gradient guidance inside the job: one body behind ramp_sample_mcmc (cg == nullptr) and ramp_sample_guided, for
-// plain (g, scenes NULL), many-scene (scenes) and composed (g) jobs.  kind 0 / no guide iteration anywhere is the matching plain entry, bit for
-// bit.  Every refusal is a host check made before anything is staged or launched; `who` names the entry in the message.
-static int sample_refined(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
-                          const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
-                          const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream, const char* who,
-                          ResampleJob* rj = nullptr, const StitchJob* sj = nullptr, const ramp_prim_guide* pg = nullptr,
-                          const ramp_team_guide* tg = nullptr) {
-  const std::string w = std::string(who) + ": ";
-  const int kind = m ? m->kind : 0;
-  RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");
-  if (g) CK(check_guidance(c, p, g, who));
-  McmcJob mj{kind, m ? m->n_inner : nullptr, m ? m->step_size : nullptr, m ? m->sigma : nullptr, 0};
-  if (kind != 0) {
-    RAMP_REQUIRE(p->predict_x0 == 0, w + "predict_x0 != 0 -- the combined network output is then x0, not a score: there is no density to correct");
-    RAMP_REQUIRE(p->n_steps > 0 && m->n_inner && m->step_size && m->sigma, w + "missing n_inner / step_size / sigma arrays");
-    for (int j = 0; j < p->n_steps; ++j) {
-      RAMP_REQUIRE(m->n_inner[j] >= 0 && m->n_inner[j] <= RAMP_MCMC_MAX_INNER, w + "n_inner outside 0 .. 16");
-      if (m->n_inner[j] == 0) continue;
-      RAMP_REQUIRE(std::isfinite(m->step_size[j]) && m->step_size[j] > 0.f, w + "step_size must be positive and finite where n_inner > 0");
-      RAMP_REQUIRE(std::isfinite(m->sigma[j]) && m->sigma[j] > 0.f, w + "sigma must be positive and finite where n_inner > 0");
-      mj.total += m->n_inner[j];
-    }
-    if (mj.total > 0 && p->noise_mode == 0) {
-      RAMP_REQUIRE(mcmc_noise, w + "null mcmc_noise (noise_mode 0 injects the inner steps' normals)");
-      RAMP_REQUIRE(kind != 2 || mcmc_u, w + "null mcmc_u (noise_mode 0 injects MALA's uniforms)");
-    }
-  }
-  GuideJob gj{cg, nullptr, nullptr};
-  int guide_total = 0;
-  if (tg) {      // (next to the cost guide it travels with)
-    RAMP_REQUIRE(cg, w + "a team table needs its cost guide");
-    CK(check_cost_guide(cg, c->cfg.state_dim, who));
-    CK(check_team_guide(tg, p->B, c->cfg.horizon, who));
-    RAMP_REQUIRE(p->philox_total == 0 || p->philox_sample0 % tg->team_size == 0, w + "a shard must hold whole teams (philox_sample0 % team_size == 0)");
-    if (team_guide_active(tg)) gj.tg = tg;
-  }
-  if (pg) {      // (next to the cost guide it travels with)
-    RAMP_REQUIRE(cg, w + "a primitive table needs its cost guide");
-    CK(check_cost_guide(cg, c->cfg.state_dim, who));
-    CK(check_prim_guide(pg, cg, c->cfg.horizon, c->cfg.state_dim, who));
-    if (prim_guide_active(pg)) gj.pg = pg;
-  }
-  if (cg) {
-    CK(check_cost_guide(cg, c->cfg.state_dim, who));
-    RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the guide kernel serves horizons up to 128");
-    RAMP_REQUIRE(scenes ? cg->n_scenes == scenes->n_scenes : cg->n_scenes == 1,
-                 w + "the guide's n_scenes must equal the scene batch's (1 without a scene batch)");
-    RAMP_REQUIRE(p->n_steps > 0 && cg->n_guide && cg->step, w + "missing n_guide / step arrays");
-    for (int j = 0; j < p->n_steps; ++j) {
-      RAMP_REQUIRE(cg->n_guide[j] >= 0 && cg->n_guide[j] <= RAMP_GUIDE_MAX_STEPS, w + "n_guide outside 0 .. RAMP_GUIDE_MAX_STEPS");
-      RAMP_REQUIRE(std::isfinite(cg->step[j]), w + "step must be finite");
-      guide_total += cg->n_guide[j];
-    }
-  }
-  if (rj) {      // (the entry hands over only a table with a flag set)
-    const ramp_resample_params* rs = rj->rs;
-    RAMP_REQUIRE(resample_group_table_fault(rs->group_first_host, rs->n_groups, p->B) == 0,
-                 w + "malformed group table (n_groups >= 1, [0] = 0, strictly increasing, [n_groups] = B)");
-    RAMP_REQUIRE(resample_ess_frac_ok(rs->ess_frac), w + "ess_frac must be finite and lie in [0, 2]");
-    RAMP_REQUIRE(rs->lambda, w + "missing lambda array");
-    for (int j = 0; j < p->n_steps; ++j) RAMP_REQUIRE(std::isfinite(rs->lambda[j]), w + "lambda must be finite");
-    RAMP_REQUIRE(rj->n_events <= RAMP_RESAMPLE_MAX_EVENTS, w + "more than RAMP_RESAMPLE_MAX_EVENTS events");
-    RAMP_REQUIRE(!p->ddim || mj.total > 0, w + "DDIM (eta = 0) never separates duplicates: resampling needs MCMC inner steps there");
-    RAMP_REQUIRE(p->predict_x0 == 0, w + "predict_x0 != 0 is not served with resampling");
-    CK(check_cost_guide(rs->cost, c->cfg.state_dim, who));
-    RAMP_REQUIRE(c->cfg.horizon <= 128, w + "the cost kernel serves horizons up to 128");
-    RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the gather moves four elements per access)");
-    RAMP_REQUIRE(scenes ? rs->cost->n_scenes == scenes->n_scenes : rs->cost->n_scenes == 1,
-                 w + "the potential's n_scenes must equal the scene batch's (1 without a scene batch)");
-    RAMP_REQUIRE(rs->group0 >= 0 && rs->groups_total >= 0 && (rs->groups_total == 0 ? rs->group0 == 0 : rs->group0 + rs->n_groups <= rs->groups_total),
-                 w + "group0 + n_groups must lie inside groups_total");
-    RAMP_REQUIRE(p->noise_mode != 0 || rj->u, w + "null resample_u (noise_mode 0 injects the events' uniforms)");
-  }
-  // (kind 0, or no inner step anywhere: the plain job; no guide iteration anywhere: the unguided job)
-  const int rc = sample_job(c, p, scenes, noise, chain_out, x_out, stream, g, mj.total > 0 ? &mj : nullptr, mcmc_noise, mcmc_u, accept_out,
-                            guide_total > 0 ? &gj : nullptr, rj, sj);
-  c->g_weight_cur = nullptr;
-  return rc;
-}
-
+// Langevin refinement inside the job.  kind 0 / no inner step anywhere is the matching plain entry, bit for bit
 int ramp_sample_mcmc(ramp_ctx* c, const ramp_sample_params* p, const ramp_mcmc_params* m, const ramp_guidance_rows* g,
                      const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise, const float* mcmc_u, float* chain_out,
                      float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p && m, "ramp_sample_mcmc: null argument");
-  return sample_refined(c, p, nullptr, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_mcmc");
+  return run_sample(c, refined_job("ramp_sample_mcmc", p, nullptr, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out), stream);
 }
 
+// ramp_sample_mcmc plus cost-gradient guidance.  cg == NULL / no guide iteration anywhere is that entry itself
 int ramp_sample_guided(ramp_ctx* c, const ramp_sample_params* p, const ramp_cost_guide* cg, const ramp_mcmc_params* m,
                        const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise, const float* mcmc_noise,
                        const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_guided: null argument");
-  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
+  return run_sample(c, refined_job("ramp_sample_guided", p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out), stream);
 }
 
 // ramp_sample_guided with the swept box and sphere terms.  pg == NULL, w_prim == 0 or no primitive anywhere is that entry itself
@@ -2664,8 +2717,9 @@ int ramp_sample_guided_prims(ramp_ctx* c, const ramp_sample_params* p, const ram
                              const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
                              const float* mcmc_noise, const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_guided_prims: null argument");
-  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided_prims", nullptr,
-                        nullptr, pg);
+  SampleJob job = refined_job("ramp_sample_guided_prims", p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out);
+  job.pg = pg;
+  return run_sample(c, job, stream);
 }
 
 // ramp_sample_guided with the separation term between the rows of a team.  tg == NULL, one agent per team or w_team == 0 is that entry itself
@@ -2673,11 +2727,12 @@ int ramp_sample_guided_team(ramp_ctx* c, const ramp_sample_params* p, const ramp
                             const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
                             const float* mcmc_noise, const float* mcmc_u, float* chain_out, float* x_out, int32_t* accept_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_guided_team: null argument");
-  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided_team", nullptr,
-                        nullptr, nullptr, tg);
+  SampleJob job = refined_job("ramp_sample_guided_team", p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out);
+  job.tg = tg;
+  return run_sample(c, job, stream);
 }
 
-// The one entry for every kind of job: ramp_sample_guided plus the resampling events.  rs == NULL or no flag set is that entry itself
+// ramp_sample_guided plus the resampling events.  rs == NULL or no flag set is that entry itself, and reports under its name
 int ramp_sample_steered(ramp_ctx* c, const ramp_sample_params* p, const ramp_resample_params* rs, const ramp_cost_guide* cg,
                         const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
                         const float* mcmc_noise, const float* mcmc_u, const float* resample_u, float* chain_out, float* x_out,
@@ -2685,29 +2740,23 @@ int ramp_sample_steered(ramp_ctx* c, const ramp_sample_params* p, const ramp_res
   RAMP_REQUIRE(c && p, "ramp_sample_steered: null argument");
   ResampleJob rj{rs, 0, resample_u, ancestor_out, ess_out, cost_out, logw_out};
   if (rs && rs->resample) for (int j = 0; j < p->n_steps; ++j) rj.n_events += rs->resample[j] != 0;
-  if (rj.n_events == 0)
-    return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_guided");
-  RAMP_REQUIRE(rs->cost, "ramp_sample_steered: null cost table");
-  return sample_refined(c, p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out, stream, "ramp_sample_steered", &rj);
+  if (rj.n_events) RAMP_REQUIRE(rs->cost, "ramp_sample_steered: null cost table");
+  SampleJob job = refined_job(rj.n_events ? "ramp_sample_steered" : "ramp_sample_guided", p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out,
+                              x_out, accept_out);
+  job.rj = rj;
+  return run_sample(c, job, stream);
 }
 
-// ramp_sample_guided (no MCMC, no composed weights) on stitched windows.  st == NULL is that entry itself
+// ramp_sample_guided (no MCMC, no composed weights) on stitched windows.  st == NULL is that entry itself, and reports under its name
 int ramp_sample_stitched(ramp_ctx* c, const ramp_sample_params* p, const ramp_stitch* st, const ramp_cost_guide* cg, const ramp_scene_batch* scenes,
                          const float* noise, float* chain_out, float* x_out, float* long_out, void* stream) {
   RAMP_REQUIRE(c && p, "ramp_sample_stitched: null argument");
-  if (!st) {
-    RAMP_REQUIRE(!long_out, "ramp_sample_stitched: long_out needs a stitch table");
-    return sample_refined(c, p, cg, nullptr, nullptr, scenes, noise, nullptr, nullptr, chain_out, x_out, nullptr, stream, "ramp_sample_guided");
-  }
-  const int H = c->cfg.horizon, S = c->cfg.state_dim;
-  CK(check_stitch(st, p->B, H, "ramp_sample_stitched"));
-  RAMP_REQUIRE(p->n_hard == 0, "ramp_sample_stitched: p->n_hard must be 0 (the pins are the job's conditions)");
-  RAMP_REQUIRE(p->philox_total == 0, "ramp_sample_stitched: a sharded job is not served (the windows of a chain must sit in one shard)");
-  StitchJob sj{st};
-  CK(sample_refined(c, p, cg, nullptr, nullptr, scenes, noise, nullptr, nullptr, chain_out, x_out, nullptr, stream, "ramp_sample_stitched", nullptr, &sj));
-  if (long_out)
-    CK(launch_stitch_assemble(c->s_x, long_out, p->B / st->n_windows, st->n_windows, H, S, st->overlap, as_stream(stream)));
-  return 0;
+  if (!st) RAMP_REQUIRE(!long_out, "ramp_sample_stitched: long_out needs a stitch table");
+  SampleJob job{st ? "ramp_sample_stitched" : "ramp_sample_guided", p, scenes, noise, chain_out, x_out, nullptr, cg};
+  job.st = st;
+  CK(run_sample(c, job, stream));
+  if (!st || !long_out) return 0;
+  return launch_stitch_assemble(c->s_x, long_out, p->B / st->n_windows, st->n_windows, c->cfg.horizon, c->cfg.state_dim, st->overlap, as_stream(stream));
 }
 
 // ---- receding-horizon replanning --------------------------------------------------------------------

@@ -539,24 +539,51 @@ class _GaussianDiffusionBase(nn.Module):
         mp.n_inner, mp.step_size, mp.sigma = arrays.i32(tab['n_inner']), arrays.f32(tab['step_size']), arrays.f32(tab['sigma'])
         return mp
 
-    def _fill_guide(self, arrays: _HostArrays, tab: dict, cost_guide: dict, scene_job: Optional[dict], ptab: Optional[dict] = None):
-        """ramp_cost_guide from the tables of ``guide_tables`` and the guide's clouds: one for a plain job, one per scene for a scene /
-        composed job (a single ``cloud`` then serves every scene).  A cloud that is None is an empty one; ``ptab``: what ``_prim_tables``
-        returned."""
-        from .guide import cloud_table, fill_cost_guide
+    def _mcmc_draws(self, mcmc: dict, tab: dict, B: int, noise):
+        """The inner steps' injected draws (z, u), behind the loop's own in call order; (None, None) for a job without an inner step or one
+        that draws its own noise (``noise`` None), which takes none."""
+        z_in, u_in = mcmc.get('noise'), mcmc.get('u')
+        if noise is None and (z_in is not None or u_in is not None):
+            raise ValueError("mcmc['noise'] / mcmc['u'] inject the inner steps' draws next to an injected loop noise; with "
+                             "noise_source='philox' the job draws both itself -- leave them out")
+        K, dev, H, S = tab['total'], self._device(), self.model.n_support_points, self.state_dim
+        if noise is None or not K:
+            return None, None
+        z_in = torch.randn((K, B, H, S), device=dev) if z_in is None else z_in.to(dev, torch.float32).contiguous()
+        if u_in is None:
+            u_in = torch.rand((K, B), device=dev).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
+        u_in = u_in.to(dev, torch.float32).contiguous()
+        if tuple(z_in.shape) != (K, B, H, S) or tuple(u_in.shape) != (K, B):
+            raise ValueError(f"mcmc noise / u must be ({K}, {B}, {H}, {S}) / ({K}, {B})")
+        return z_in, u_in
+
+    def _scene_clouds(self, name: str, opt: dict, scene_job: Optional[dict], arrays: Optional[_HostArrays] = None, d_empty: int = 2):
+        """The per-scene clouds of a ``cost_guide=`` / ``resample=`` dict (``name`` in the messages): one for a plain job, one per scene for
+        a scene / composed job (a single ``cloud`` then serves every scene).  A cloud that is None is an empty one, as wide as the other
+        clouds' points (``d_empty`` without any).  Returns ``cloud_table``'s (points, offsets, d), kept in ``arrays`` -- without
+        ``arrays`` (None, None, the width of the first cloud that is not None, or None): the list is checked and nothing is built."""
+        from .guide import cloud_table
         n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
-        clouds = [cost_guide['cloud']] * n_scenes if 'cloud' in cost_guide else list(cost_guide['clouds'])
+        clouds = [opt['cloud']] * n_scenes if 'cloud' in opt else list(opt['clouds'])
         if len(clouds) != n_scenes:
-            raise ValueError(f"cost_guide clouds: {len(clouds)} entries for {n_scenes} scene(s)")
-        if any(c is None for c in clouds):      # None = an empty cloud, as wide as the other clouds' or the primitives' points (2 without either)
-            d0 = next((int(torch.as_tensor(c).shape[-1]) for c in clouds if c is not None), ptab['D'] if ptab is not None else 2)
-            clouds = [torch.zeros(0, d0) if c is None else c for c in clouds]
+            raise ValueError(f"{name} clouds: {len(clouds)} entries for {n_scenes} scene(s)")
+        d_cloud = next((int(torch.as_tensor(c).shape[-1]) for c in clouds if c is not None), None)
+        if arrays is None:
+            return None, None, d_cloud
+        clouds = [torch.zeros(0, d_cloud or d_empty) if c is None else c for c in clouds]
         points, off, d = cloud_table(clouds, self._device())
         if d > self.state_dim:
-            raise ValueError(f"cost_guide: {d}-D points on {self.state_dim}-wide states")
+            raise ValueError(f"{name}: {d}-D points on {self.state_dim}-wide states")
+        return arrays.keep(points), arrays.keep(off), d
+
+    def _fill_guide(self, arrays: _HostArrays, tab: dict, cost_guide: dict, scene_job: Optional[dict], ptab: Optional[dict] = None):
+        """ramp_cost_guide from the tables of ``guide_tables`` and the guide's clouds (``_scene_clouds``; without any, an empty cloud is as
+        wide as the primitives' points).  ``ptab``: what ``_prim_tables`` returned."""
+        from .guide import fill_cost_guide
+        points, off, d = self._scene_clouds('cost_guide', cost_guide, scene_job, arrays, ptab['D'] if ptab is not None else 2)
         if ptab is not None and ptab['D'] != d:
             raise ValueError(f"cost_guide: {d}-D cloud points with {ptab['D']}-D boxes / spheres")
-        cg = fill_cost_guide(arrays.keep(points), arrays.keep(off), d, tab)
+        cg = fill_cost_guide(points, off, d, tab)
         cg.n_guide, cg.step = arrays.i32(tab['n_guide']), arrays.f32(tab['step'])
         return cg
 
@@ -566,14 +593,13 @@ class _GaussianDiffusionBase(nn.Module):
             return None
         from .guide import prim_table
         n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
-        clouds = [cost_guide['cloud']] if 'cloud' in cost_guide else list(cost_guide['clouds'])
-        d_cloud = next((int(torch.as_tensor(c).shape[-1]) for c in clouds if c is not None), None)
+        d_cloud = self._scene_clouds('cost_guide', cost_guide, scene_job)[2]
         return arrays.keep(prim_table(cost_guide.get('boxes'), cost_guide.get('spheres'), n_scenes, d_cloud, self._device()))
 
     def _fill_resample(self, arrays: _HostArrays, tab: dict, resample: dict, scene_job: Optional[dict], hard_conds, B: int):
         """ramp_resample_params from the tables of ``resample_tables``: one group for a plain job, one per scene for a scene / composed job,
         the cost's clouds like the guide's.  Returns (params, its cost table, the host group table)."""
-        from .guide import cloud_table, fill_cost_guide
+        from .guide import fill_cost_guide
         n_scenes = scene_job['n_scenes'] if scene_job is not None else 1
         if scene_job is None:
             gf = np.array([0, B], dtype=np.int32)
@@ -591,13 +617,7 @@ class _GaussianDiffusionBase(nn.Module):
                     if not bool((v[a:b] == v[a:a + 1]).all()):
                         raise ValueError(f"resample=: the values of hard condition {k} differ inside a group (trajectories {a} .. {b - 1}): "
                                          "resampling moves whole rows between them")
-        clouds = [resample['cloud']] * n_scenes if 'cloud' in resample else list(resample['clouds'])
-        if len(clouds) != n_scenes:
-            raise ValueError(f"resample clouds: {len(clouds)} entries for {n_scenes} scene(s)")
-        points, off, d = cloud_table(clouds, self._device())
-        if d > self.state_dim:
-            raise ValueError(f"resample: {d}-D points on {self.state_dim}-wide states")
-        cost = arrays.keep(fill_cost_guide(arrays.keep(points), arrays.keep(off), d, tab))
+        cost = arrays.keep(fill_cost_guide(*self._scene_clouds('resample', resample, scene_job, arrays), tab))
         rs = _lib.RampResampleParams()
         rs.n_groups, rs.group0, rs.groups_total = len(gf) - 1, 0, 0
         gf = arrays.keep(gf)
@@ -608,6 +628,21 @@ class _GaussianDiffusionBase(nn.Module):
         rs.ess_frac = tab['ess_frac']
         rs.cost = C.pointer(cost)
         return rs, cost, gf
+
+    def _resample_draws(self, resample: dict, n_ev: int, G: int, noise):
+        """The events' injected uniforms (n_ev, G); None for a job that draws its own noise (``noise`` None), which takes none."""
+        ru = resample.get('u')
+        if noise is None and ru is not None:
+            raise ValueError("resample['u'] injects the events' uniforms next to an injected loop noise; with noise_source='philox' "
+                             "the job draws them itself -- leave it out")
+        if noise is None:
+            return None
+        if ru is None:
+            ru = torch.rand((n_ev, G), device=self._device()).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
+        ru = torch.as_tensor(ru).to(self._device(), torch.float32).contiguous()
+        if tuple(ru.shape) != (n_ev, G):
+            raise ValueError(f"resample u must be ({n_ev}, {G}); got {tuple(ru.shape)}")
+        return ru
 
     @staticmethod
     def _refuse_prims_outside_the_guide(cost_guide, resample, stitch):
@@ -692,6 +727,7 @@ class _GaussianDiffusionBase(nn.Module):
         and empty ``hard_conds``): stitched windows (``ramp_sample_stitched``) -- the dict of ``run_inference_stitched``: ``n_windows``,
         ``overlap``, ``alpha`` (O) float32, ``pin_idx`` (n_pin) int32, ``pin_val`` device (n_pin, C, S) or None."""
         m = self.model
+        # ---- refusals and the options' host tables, before anything touches the device
         if stitch is not None and (mcmc is not None or resample is not None or guidance is not None or hard_conds):
             raise NotImplementedError("stitched windows take no mcmc=, resample=, composed weights or hard conditions of their own")
         self._refuse_prims_outside_the_guide(cost_guide, resample, stitch)
@@ -714,6 +750,7 @@ class _GaussianDiffusionBase(nn.Module):
         m.prepare_time_table(self.n_diffusion_steps)
         if scene_job is None:      # (run_inference_scenes: the scene table is already set, set_scenes)
             self._prepare_scene(obstacle_pts, B)
+        # ---- the job's params; `arrays` keeps everything the C call reads referenced until it has returned
         p, arrays = _lib.RampSampleParams(), _HostArrays()
         p.B, p.n_rp = B, self._n_rp()
         p.w0, p.w1 = (float(w) for w in (self.compose_weights if self.compose else (self.cfg_weight, 0.0)))
@@ -739,43 +776,31 @@ class _GaussianDiffusionBase(nn.Module):
         p.use_graph = int(self.use_graph)
         chain = torch.empty((n_steps + 1, B, H, S), device=dev, dtype=torch.float32) if return_chain else None
         x_out = torch.empty((B, H, S), device=dev, dtype=torch.float32)
-        mp = z_in = u_in = accept = None
+        # ---- the options: each one's struct, injected draws and outputs
+        from .guide import fill_prim_guide
+        from .team import fill_team_guide
         cg = pg = tg = None
-        if gtab is not None and gtab.get('team') is not None:
-            from .team import fill_team_guide
-            tg = fill_team_guide(gtab['team'])
         if gtab is not None:
-            from .guide import fill_prim_guide
+            tg = fill_team_guide(gtab['team']) if gtab.get('team') is not None else None
             ptab = self._prim_tables(arrays, gtab, cost_guide, scene_job)
             cg = self._fill_guide(arrays, gtab, cost_guide, scene_job, ptab)
             pg = fill_prim_guide(ptab, gtab['prim']) if ptab is not None else None
-        rs = ru = r_anc = r_ess = r_cost = r_logw = None
+        rs = ru = None
+        r_out = (None, None, None, None)      # ancestors, ESS, costs, final log-weights
         n_ev = len(rtab['events']) if rtab is not None else 0
         if n_ev:
             rs, _cost, r_gf = self._fill_resample(arrays, rtab, resample, scene_job, hard_conds, B)
-            G = rs.n_groups
-            r_anc = torch.empty((n_ev, B), device=dev, dtype=torch.int32)
-            r_ess = torch.empty((n_ev, G), device=dev, dtype=torch.float64)
-            r_cost = torch.empty((n_ev, B), device=dev, dtype=torch.float64)
-            r_logw = torch.empty((B,), device=dev, dtype=torch.float64)
-            if noise is None:
-                if resample.get('u') is not None:
-                    raise ValueError("resample['u'] injects the events' uniforms next to an injected loop noise; with noise_source='philox' "
-                                     "the job draws them itself -- leave it out")
-            else:
-                ru = resample.get('u')
-                if ru is None:
-                    ru = torch.rand((n_ev, G), device=dev).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
-                ru = torch.as_tensor(ru).to(dev, torch.float32).contiguous()
-                if tuple(ru.shape) != (n_ev, G):
-                    raise ValueError(f"resample u must be ({n_ev}, {G}); got {tuple(ru.shape)}")
+            r_out = (torch.empty((n_ev, B), device=dev, dtype=torch.int32), torch.empty((n_ev, rs.n_groups), device=dev, dtype=torch.float64),
+                     torch.empty((n_ev, B), device=dev, dtype=torch.float64), torch.empty((B,), device=dev, dtype=torch.float64))
+            ru = self._resample_draws(resample, n_ev, rs.n_groups, noise)
+        mp = z_in = u_in = accept = None
         if tab is not None:
             mp = self._fill_mcmc(arrays, tab)
             accept = torch.zeros((tab['total'], B), device=dev, dtype=torch.int32)
-        if noise is None:          # the job draws its own
-            if mcmc is not None and (mcmc.get('noise') is not None or mcmc.get('u') is not None):
-                raise ValueError("mcmc['noise'] / mcmc['u'] inject the inner steps' draws next to an injected loop noise; with "
-                                 "noise_source='philox' the job draws both itself -- leave them out")
+            z_in, u_in = self._mcmc_draws(mcmc, tab, B, noise)
+        from .stitch import fill_stitch
+        st = fill_stitch(*(stitch[k] for k in ('n_windows', 'overlap', 'alpha', 'pin_idx', 'pin_val'))) if stitch is not None else None
+        if noise is None:         # the job draws its own, the options' draws included
             p.noise_mode = 1
             p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim, tab['total'] if tab else 0,
                                                                                                      n_ev * rs.n_groups if n_ev else 0)
@@ -783,65 +808,35 @@ class _GaussianDiffusionBase(nn.Module):
                 p.philox_sample0, p.philox_total = 0, 0
         else:
             noise = noise.contiguous()
-            if tab and tab['total']:      # the inner steps' draws, behind the loop's own in call order
-                z_in, u_in = mcmc.get('noise'), mcmc.get('u')
-                z_in = torch.randn((tab['total'], B, H, S), device=dev) if z_in is None else z_in.to(dev, torch.float32).contiguous()
-                if u_in is None:
-                    u_in = torch.rand((tab['total'], B), device=dev).clamp_(min=2.0 ** -24, max=1.0 - 2.0 ** -24)
-                u_in = u_in.to(dev, torch.float32).contiguous()
-                if tuple(z_in.shape) != (tab['total'], B, H, S) or tuple(u_in.shape) != (tab['total'], B):
-                    raise ValueError(f"mcmc noise / u must be ({tab['total']}, {B}, {H}, {S}) / ({tab['total']}, {B})")
+
+        # ---- the call: the job's options choose the entry and its leading structs; the rest is shared
+        opt = lambda x: C.byref(x) if x is not None else None      # noqa: E731
+        middle = (opt(mp), opt(rows), opt(batch), _lib.ptr(noise), _lib.ptr(z_in), _lib.ptr(u_in))
+        plain = (_lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out))
+        outs = (_lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept))
+        if st is not None:
+            entry, args = "ramp_sample_stitched", (C.byref(st), opt(cg), opt(batch)) + plain + (None,)
+        elif rs is not None:
+            entry, args = "ramp_sample_steered", (C.byref(rs), opt(cg)) + middle + (_lib.ptr(ru),) + outs + tuple(_lib.ptr(t) for t in r_out)
+        elif pg is not None:
+            entry, args = "ramp_sample_guided_prims", (C.byref(cg), C.byref(pg)) + middle + outs
+        elif tg is not None:
+            entry, args = "ramp_sample_guided_team", (C.byref(cg), C.byref(tg)) + middle + outs
+        elif cg is not None:
+            entry, args = "ramp_sample_guided", (C.byref(cg),) + middle + outs
+        elif mp is not None:
+            entry, args = "ramp_sample_mcmc", middle + outs
+        elif rows is not None:
+            entry, args = "ramp_sample_composed", (C.byref(rows), C.byref(batch)) + plain
+        elif batch is not None:
+            entry, args = "ramp_sample_scenes", (C.byref(batch),) + plain
+        else:
+            entry, args = "ramp_sample", plain
         with torch.cuda.device(dev):
-            lib = _lib.load()
-
-            def job():
-                if stitch is not None:
-                    from .stitch import fill_stitch
-                    st = fill_stitch(stitch['n_windows'], stitch['overlap'], stitch['alpha'], stitch['pin_idx'], stitch['pin_val'])
-                    _lib.check(lib.ramp_sample_stitched(m.ctx(), C.byref(p), C.byref(st), C.byref(cg) if cg is not None else None,
-                                                        C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(chain),
-                                                        _lib.ptr(x_out), None, _lib.current_stream()), "ramp_sample_stitched")
-                elif rs is not None:
-                    _lib.check(lib.ramp_sample_steered(m.ctx(), C.byref(p), C.byref(rs), C.byref(cg) if cg is not None else None,
-                                                       C.byref(mp) if mp is not None else None, C.byref(rows) if rows is not None else None,
-                                                       C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
-                                                       _lib.ptr(u_in), _lib.ptr(ru), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
-                                                       _lib.ptr(r_anc), _lib.ptr(r_ess), _lib.ptr(r_cost), _lib.ptr(r_logw),
-                                                       _lib.current_stream()), "ramp_sample_steered")
-                elif pg is not None:
-                    _lib.check(lib.ramp_sample_guided_prims(m.ctx(), C.byref(p), C.byref(cg), C.byref(pg), C.byref(mp) if mp is not None else None,
-                                                            C.byref(rows) if rows is not None else None,
-                                                            C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
-                                                            _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
-                                                            _lib.current_stream()), "ramp_sample_guided_prims")
-                elif tg is not None:
-                    _lib.check(lib.ramp_sample_guided_team(m.ctx(), C.byref(p), C.byref(cg), C.byref(tg), C.byref(mp) if mp is not None else None,
-                                                           C.byref(rows) if rows is not None else None,
-                                                           C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
-                                                           _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
-                                                           _lib.current_stream()), "ramp_sample_guided_team")
-                elif cg is not None:
-                    _lib.check(lib.ramp_sample_guided(m.ctx(), C.byref(p), C.byref(cg), C.byref(mp) if mp is not None else None,
-                                                      C.byref(rows) if rows is not None else None,
-                                                      C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
-                                                      _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
-                                                      _lib.current_stream()), "ramp_sample_guided")
-                elif mp is not None:
-                    _lib.check(lib.ramp_sample_mcmc(m.ctx(), C.byref(p), C.byref(mp), C.byref(rows) if rows is not None else None,
-                                                    C.byref(batch) if batch is not None else None, _lib.ptr(noise), _lib.ptr(z_in),
-                                                    _lib.ptr(u_in), _lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept),
-                                                    _lib.current_stream()), "ramp_sample_mcmc")
-                elif rows is not None:
-                    _lib.check(lib.ramp_sample_composed(m.ctx(), C.byref(p), C.byref(rows), C.byref(batch), _lib.ptr(noise), _lib.ptr(chain),
-                                                        _lib.ptr(x_out), _lib.current_stream()), "ramp_sample_composed")
-                elif batch is not None:
-                    _lib.check(lib.ramp_sample_scenes(m.ctx(), C.byref(p), C.byref(batch), _lib.ptr(noise), _lib.ptr(chain),
-                                                      _lib.ptr(x_out), _lib.current_stream()), "ramp_sample_scenes")
-                else:
-                    _lib.check(lib.ramp_sample(m.ctx(), C.byref(p), _lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out),
-                                               _lib.current_stream()), "ramp_sample")
-
-            self._run_guarded(job)
+            fn = getattr(_lib.load(), entry)
+            self._run_guarded(lambda: _lib.check(fn(m.ctx(), C.byref(p), *args, _lib.current_stream()), entry))
+        # ---- results
+        r_anc, r_ess, r_cost, r_logw = r_out
         if tab is not None:      # one copy back
             acc = accept.cpu()
             rate, k0 = [], 0
@@ -972,12 +967,9 @@ class _GaussianDiffusionBase(nn.Module):
         self._refuse_prims_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'))
         self._refuse_team_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'), [batch_size])
         if self.ddim:
-            if sample_kwargs.get('mcmc') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
-                raise NotImplementedError("mcmc= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
-            if sample_kwargs.get('cost_guide') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
-                raise NotImplementedError("cost_guide= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
-            if sample_kwargs.get('resample') is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
-                raise NotImplementedError("resample= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
+            for k in ('mcmc', 'cost_guide', 'resample'):
+                if sample_kwargs.get(k) is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
+                    raise NotImplementedError(f"{k}= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
             for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
                 sample_kwargs.pop(k, None)      # silently ignored by the reference's DDIM loop
             return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized,
