@@ -148,9 +148,14 @@ def main(argv=None):
                     help="with --evaluate: K free plans that are pairwise at least --min-sep apart, cheapest first, and how many free samples "
                          "are nearest to each (select_diverse_clear_scenes)")
     ap.add_argument("--min-sep", type=float, default=0.1, help="mean waypoint distance two of the --alternatives keep from each other")
+    ap.add_argument("--warm-start", default=None, metavar="{line,FILE}",
+                    help="start from a prior instead of pure noise: the straight line from start to goal, or a .pt file of normalised trajectories")
+    ap.add_argument("--warm-level", type=int, default=None, metavar="T", help="the diffusion level the prior is noised to (0 .. n_diffusion_steps - 1)")
     args = ap.parse_args(argv)
     if args.alternatives and not args.evaluate:
         ap.error("--alternatives goes with --evaluate")
+    if (args.warm_start is None) != (args.warm_level is None):
+        ap.error("--warm-start and --warm-level go together")
     cfg = Config3d(); cfg.n_samples, cfg.n_diffusion_steps, cfg.model_id, cfg.seed = args.n_samples, args.n_diffusion_steps, args.model_id, args.seed
     cfg.unet_input_dim, cfg.unet_dim_mults_option = args.unet_input_dim, args.unet_dim_mults_option
     if args.make_synthetic:
@@ -183,6 +188,11 @@ def main(argv=None):
     sample_fn_kwargs = dict(guide=None, n_guide_steps=cfg.n_guide_steps, t_start_guide=t_start_guide, noise_std_extra_schedule_fn=lambda x: 0.5)
     if args.guide_obstacles:
         sample_fn_kwargs["cost_guide"] = obstacle_guide(data, dataset.normalizer, t_start=t_start_guide)
+    if args.warm_start is not None:      # (hard_conds holds the normalised start and goal states)
+        from ramp_amd.warm import straight_line_prior
+        prior = (straight_line_prior(hard_conds[0].detach().cpu().numpy(), hard_conds[n_support_points - 1].detach().cpu().numpy(), n_support_points)
+                 if args.warm_start == "line" else torch.load(args.warm_start, map_location="cpu"))
+        sample_fn_kwargs["warm_start"] = dict(prior=prior, level=args.warm_level)
     torch.cuda.synchronize(); t0 = time.perf_counter()
     trajs_normalized_iters = model.run_inference(context, hard_conds, n_samples=cfg.n_samples, horizon=n_support_points, return_chain=True,
                                                  traj_normalized=traj_normalized, obstacle_pts=obstacle_pts, sample_fn=ddpm_sample_fn,

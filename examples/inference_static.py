@@ -84,6 +84,8 @@ class StaticConfig:
     team_radius = None       # the radius of the guide's separation term; default 1.5 team_sep
     team_guide = dict(radius=0.1, step=0.05, w_obs=1.0, w_smooth=2.0, n_steps=16, max_norm=2.0)  # the cost guide the team term travels with
     team_guide_fraction = 1.0   # the guide runs on the iterations with t < this fraction of the diffusion steps
+    warm_start = None        # not the reference's: 'line' or a .pt file of normalised trajectories the job starts from (--warm-start)
+    warm_level = None        # the diffusion level the prior is noised to, 0 .. n_diffusion_steps - 1 (--warm-level)
 
 
 def make_synthetic_experiment(root: str, cfg: StaticConfig, n_obstacles: int = 6, n_points: int = 64, seed: int = 42) -> None:
@@ -120,6 +122,22 @@ class StaticInference:
         self.metrics_calculator = Metrics()
         self.context_manager = compat.ContextManager()
         self.model = None
+
+    def warm_start_kwargs(self, hard_conds_list):
+        """Opt-in (--warm-start {line,FILE} --warm-level T): the ``warm_start=`` keyword of run_inference / run_inference_scenes, or nothing.
+        'line': per experiment the straight line between its start and goal states; FILE: a .pt tensor of normalised trajectories, (H, S)
+        for every row, one per experiment, or one per row (``ramp_amd.warm.prior_rows``)."""
+        cfg = self.config
+        if cfg.warm_start is None:
+            return {}
+        from ramp_amd.warm import straight_line_prior
+        H = cfg.n_support_points
+        if cfg.warm_start == 'line':
+            prior = [straight_line_prior(hc[0].detach().cpu().numpy(), hc[H - 1].detach().cpu().numpy(), H) for hc in hard_conds_list]
+            prior = prior[0] if len(prior) == 1 else prior
+        else:
+            prior = torch.load(cfg.warm_start, map_location='cpu')
+        return dict(warm_start=dict(prior=prior, level=int(cfg.warm_level)))
 
     def run_single_experiment(self, current_dir: int, context_idx: int):
         cfg = self.config
@@ -161,7 +179,7 @@ class StaticInference:
         trajs_normalized_iters = self.model.run_inference(
             context, hard_conds, n_samples=cfg.n_samples, horizon=n_support_points, return_chain=True,
             traj_normalized=traj_normalized, obstacle_pts=obstacle_pts, sample_fn=ddpm_sample_fn, **sample_fn_kwargs,
-            n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise)
+            n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise, **self.warm_start_kwargs([hard_conds]))
         torch.cuda.synchronize(); elapsed = time.perf_counter() - t0
         trajs_final = trajs_normalized_iters[-1]
         collision_intensities = self.metrics_calculator.compute_collision_intensity(trajs_final, box_centers, box_size)
@@ -204,7 +222,7 @@ class StaticInference:
         trajs, traj_scene = self.model.run_inference_scenes(
             [d['obstacle_points'] for d in datas], hard_conds, n_samples=cfg.n_samples, horizon=n_support_points, sample_fn=ddpm_sample_fn,
             guide=None, n_guide_steps=cfg.n_guide_steps, t_start_guide=t_start_guide, noise_std_extra_schedule_fn=lambda x: 0.5,
-            n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise)
+            n_diffusion_steps_without_noise=cfg.n_diffusion_steps_without_noise, **self.warm_start_kwargs(hard_conds))
         torch.cuda.synchronize(); elapsed = time.perf_counter() - t0
         # every experiment scored in one pass (four launches, one copy back) instead of a dozen launches and syncs per directory
         counts = [cfg.n_samples] * len(dirs)
@@ -311,6 +329,9 @@ def main(argv=None):
     ap.add_argument("--alternatives", type=int, default=0, metavar="K",
                     help="with --all-envs: K plans per experiment that are pairwise at least --min-sep apart, next to best_trajectory")
     ap.add_argument("--min-sep", type=float, default=0.1, help="mean waypoint distance two of the --alternatives keep from each other")
+    ap.add_argument("--warm-start", default=None, metavar="{line,FILE}",
+                    help="start from a prior instead of pure noise: the straight line from start to goal, or a .pt file of normalised trajectories")
+    ap.add_argument("--warm-level", type=int, default=None, metavar="T", help="the diffusion level the prior is noised to (0 .. n_diffusion_steps - 1)")
     ap.add_argument("--agents", type=int, default=0, metavar="A", help="plan for teams of A robots (2 .. 8) per experiment; --n-samples counts teams")
     ap.add_argument("--team-sep", type=float, default=StaticConfig.team_sep, help="the separation two robots of a team must keep")
     ap.add_argument("--team-radius", type=float, default=None, help="radius of the guide's separation term (default 1.5 x --team-sep)")
@@ -319,7 +340,12 @@ def main(argv=None):
         ap.error("--agents takes 2 .. 8")
     if args.alternatives and not args.all_envs:
         ap.error("--alternatives goes with --all-envs")
+    if (args.warm_start is None) != (args.warm_level is None):
+        ap.error("--warm-start and --warm-level go together")
+    if args.warm_start is not None and args.agents:
+        ap.error("--warm-start is not wired into --agents")
     cfg = StaticConfig()
+    cfg.warm_start, cfg.warm_level = args.warm_start, args.warm_level
     cfg.alternatives, cfg.min_sep = args.alternatives, args.min_sep
     cfg.agents, cfg.team_sep, cfg.team_radius = args.agents, args.team_sep, args.team_radius
     cfg.n_samples, cfg.n_diffusion_steps, cfg.sampler, cfg.use_apf = args.n_samples, args.n_diffusion_steps, args.sampler, args.use_apf

@@ -609,6 +609,55 @@ int ramp_stitch_windows(float* x, int32_t C, int32_t W, int32_t H, int32_t S, co
 /* long_out device (C, L, S) from the windows x (C W, H, S); O is not read with W == 1.  Refused with "ramp_stitch_assemble": bad dims, O
  * outside 1 .. H / 2 with W > 1, a NULL array.  Synchronises `stream`. */
 int ramp_stitch_assemble(const float* x, int32_t C, int32_t W, int32_t H, int32_t S, int32_t O, float* long_out, void* stream);
+/* ---- warm-started jobs: every row starts from a given plan at a level of its own ----
+ * A sampling job starts at x_T = noise[0] and pays for the whole schedule.  A warm-started job starts every row from a prior plan noised to
+ * an intermediate level (q_sample, as the reference's dynamic planner does at diffusion_model_dynamic.py:256/285/561) and runs only the tail
+ * of the schedule.  The level is a per-row quantity: in one batch some rows have a prior and some do not.  ramp_amd/warm.py states the
+ * definition in numpy (warm_tables, warm_init_reference, warm_hold_reference); in short, for a job whose params p hold the iterations
+ * J .. n - 1 of the model's schedule (p->n_steps = n' = n - J; the caller truncates every per-iteration table of p and of the options):
+ *   start  row b without a prior: x_init[b] = noise[0][b], the same bits.  With one: x_init[b] = (sa[b] * prior[b]) + (s1a[b] * noise[0][b])
+ *          in fp32, two products and a sum rounded once each; sa / s1a are sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod at the
+ *          timestep of the row's first own iteration, p->t[j0[b]].  Then the hard conditioning (the stitch of a stitched job), as on x_T:
+ *          chain block 0, kept as x_init.
+ *   hold   after iteration j (reverse step, hooks, hard conditioning or stitch, chain write) every row with j0[b] > j is x_init[b] again, in
+ *          the state and in chain block j + 1: one launch on each iteration j < n_hold = max_b j0[b], none in a job of uniform levels.  The
+ *          network still evaluates a held row (wasted on it, harmless); no hook result, inner step or accept survives on it.
+ * The noise block is (n' + 1, B, H, S) on DDPM, (1, B, H, S) on DDIM, block 0 the start draw; with noise_mode 1 the job draws it as ever.
+ * prior, the tables and the coefficients are copied into buffers of the context before the launch and the captured graph reads those: the
+ * graph key gains the presence of a warm start and n_hold only, so two jobs that differ in levels at equal n_hold (and equal p) replay one
+ * graph.  The launch count depends on n_hold alone, never on B or the number of scenes. */
+typedef struct ramp_warm_start {
+  const float* prior;                /* device (B, H, S): the rows' plans, normalised; a row without a prior is not read (NULL if no row has one) */
+  const int32_t* j0_host;            /* host (B): the row's first own iteration, 0 .. n_hold; 0 for a row without a prior      */
+  const int32_t* has_prior_host;     /* host (B): 0 = the row starts from noise[0], anything else = from its prior              */
+  const float* sa_host;              /* host (B): sqrt_alphas_cumprod at the row's start timestep (not read without a prior)    */
+  const float* s1a_host;             /* host (B): sqrt_one_minus_alphas_cumprod there                                            */
+  int32_t n_hold;                    /* max_b j0_host[b], 0 .. p->n_steps - 1                                                    */
+  int32_t reserved;
+} ramp_warm_start;
+/* THE entry of the sampling jobs with a warm start: behind ws every option struct a job knows, each of which may be NULL -- st (stitched
+ * windows), rs (resampling events), cg / pg / tg (the cost guide, its primitives, its team), m (Langevin steps), g (composed weights),
+ * scenes -- with the inputs and outputs of the entries that take them (ramp_sample_steered, ramp_sample_stitched).  ws == NULL IS the entry
+ * that takes the same options, bit for bit, and launches what it launches.
+ * Refused on the host before any launch (non-zero, "ramp_sample_warm" in ramp_last_error): a NULL table; j0 outside 0 .. n_hold; n_hold not
+ * max j0 or >= p->n_steps; j0 != 0 on a row without a prior; a NULL prior or coefficient table, or a non-finite coefficient, with a prior
+ * somewhere; H S no multiple of 4; with n_hold > 0 (mixed levels): resampling events (a held row could become an ancestor), a team, stitched
+ * windows; pg and tg together; st together with rs / pg / tg / m / g; and what the entry of the same options refuses. */
+int ramp_sample_warm(ramp_ctx* ctx, const ramp_sample_params* p, const ramp_warm_start* ws, const ramp_stitch* st,
+                     const ramp_resample_params* rs, const ramp_cost_guide* cg, const ramp_prim_guide* pg, const ramp_team_guide* tg,
+                     const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                     const float* mcmc_noise, const float* mcmc_u, const float* resample_u, float* chain_out, float* x_out,
+                     int32_t* accept_out, int32_t* ancestor_out, double* ess_out, double* cost_out, double* logw_out, float* long_out,
+                     void* stream);
+/* the start state alone: x (B, H, S) device, may be noise0 itself; noise0 and prior device (B, H, S), 16-byte aligned; the three tables host
+ * (B).  Neither the hard conditioning nor the stitch is applied.  Refused with "ramp_warm_init": a NULL argument, bad dims, H S no multiple
+ * of 4.  Synchronises `stream`. */
+int ramp_warm_init(float* x, const float* noise0, const float* prior, const float* sa_host, const float* s1a_host,
+                   const int32_t* has_prior_host, int32_t B, int32_t H, int32_t S, void* stream);
+/* the hold behind iteration j alone: rows with j0_host[b] > j become x_init[b] in x and, chain_block != NULL, in chain_block; nothing else is
+ * written.  Refused with "ramp_warm_hold" likewise.  Synchronises `stream`. */
+int ramp_warm_hold(float* x, float* chain_block, const float* x_init, const int32_t* j0_host, int32_t j, int32_t B, int32_t H, int32_t S,
+                   void* stream);
 /* torch.randn stand-in of the throughput jobs (sample_functions.py:36; diffusion_model_static.py:239): out[0..n) ~ N(0, 1),
  * element 4 g + j = output j of philox4x32_10(counter = (lo32(g + offset), hi32(g + offset), 0, 0), key = (lo32(seed),
  * hi32(seed))) through Box-Muller: u = ((r >> 9) + 0.5) 2^-23, (z0, z1) = sqrt(-2 ln u0) (cos, sin)(2 pi u1), (z2, z3) from

@@ -95,6 +95,12 @@ class RampStitch(C.Structure):
                 ("pin_idx_host", c_i32p), ("pin_val", C.c_void_p)]
 
 
+class RampWarmStart(C.Structure):
+    """ramp_warm_start: the rows' priors and levels of a warm-started job (ramp_sample_warm)."""
+    _fields_ = [("prior", C.c_void_p), ("j0_host", c_i32p), ("has_prior_host", c_i32p), ("sa_host", c_f32p), ("s1a_host", c_f32p),
+                ("n_hold", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RampReplanGuide(C.Structure):
     """ramp_replan_guide: the cost guide of the replanning jobs (ramp_replan_guided, ramp_replan_episodes_guided) and of the kernel-level
     ramp_guide_step_moving / ramp_guide_cost_moving."""
@@ -238,7 +244,12 @@ PROTOTYPES = {
     "ramp_team_clearance": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_float, C.c_int32] + [C.c_void_p] * 11),
     "ramp_sample_stitched": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampStitch), C.POINTER(RampCostGuide),
                                        C.POINTER(RampSceneBatch)] + [C.c_void_p] * 5),
-    "ramp_stitch_windows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampStitch), C.c_void_p]),
+    "ramp_sample_warm": (C.c_int, [C.c_void_p, C.POINTER(RampSampleParams), C.POINTER(RampWarmStart), C.POINTER(RampStitch),
+                                   C.POINTER(RampResampleParams), C.POINTER(RampCostGuide), C.POINTER(RampPrimGuide), C.POINTER(RampTeamGuide),
+                                   C.POINTER(RampMcmcParams), C.POINTER(RampGuidanceRows), C.POINTER(RampSceneBatch)] + [C.c_void_p] * 13),
+    "ramp_warm_init": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ramp_warm_hold": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, c_i32p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "ramp_stitch_windows": (C.c_int,[C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RampStitch), C.c_void_p]),
     "ramp_stitch_assemble": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]),
     "ramp_score_energy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "ramp_row_energy": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),

@@ -13,7 +13,7 @@ LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libramp_hip.so")
 TOOLS_LIB = os.path.join(LIBDIR, "libramp_hip_tools.so")
 # the product library: kernels + engine.hip (context, schedule, sampler, graphs) + ops.hip (context-free kernel-level entry points)
-SOURCES = ["gemm.hip", "ffx.hip", "ffx16.hip", "tkl.hip", "tkl16.hip", "atk.hip", "atb.hip", "atl.hip", "tkc.hip", "tkw.hip", "rowops.hip", "attention.hip", "sampler.hip", "guide.hip", "guide_replan.hip", "guide_prims.hip", "guide_team.hip", "stitch.hip", "resample.hip", "clearance.hip", "team.hip", "scene.hip", "metrics.hip", "engine.hip", "ops.hip"]
+SOURCES = ["gemm.hip", "ffx.hip", "ffx16.hip", "tkl.hip", "tkl16.hip", "atk.hip", "atb.hip", "atl.hip", "tkc.hip", "tkw.hip", "rowops.hip", "attention.hip", "sampler.hip", "guide.hip", "guide_replan.hip", "guide_prims.hip", "guide_team.hip", "stitch.hip", "warm.hip", "resample.hip", "clearance.hip", "team.hip", "scene.hip", "metrics.hip", "engine.hip", "ops.hip"]
 # the tools library = the same objects + the micro-benchmark / stress harness (ramp_bench_gemm, ramp_stress_gemm): tests/ and ramp_amd/tools/ only
 TOOLS_SOURCES = ["bench.hip"]
 # default GEMM mode 2 = fp16x3 split with delayed operand scaling, 1 = bf16x6 split (both fp32-accurate, see gemm.hip);
@@ -27,9 +27,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # clearance.hip (swept collision checks) repeats traj_costs_block's path-length arithmetic bit for bit and is built under the same flag;
 # team.hip (the teams' swept separation check) states its fp32 arithmetic the same way.
 # stitch.hip (stitched windows) states its blend l + alpha (q - l) the same way.
+# warm.hip (warm-started jobs) states its start state (sa prior) + (s1a noise) the same way.
 # ffx.hip: hipcc's SLP vectoriser pairs the GEGLU elements into v_pk_* instructions, which issue slower beside MFMAs and
 # bunch the elementwise work in front of a slab's first MFMA
-EXTRA_FLAGS = {"sampler.hip": ["-ffp-contract=off"], "guide.hip": ["-ffp-contract=off"], "guide_replan.hip": ["-ffp-contract=off"], "guide_prims.hip": ["-ffp-contract=off"], "guide_team.hip": ["-ffp-contract=off"], "resample.hip": ["-ffp-contract=off"], "clearance.hip": ["-ffp-contract=off"], "team.hip": ["-ffp-contract=off"], "stitch.hip": ["-ffp-contract=off"], "ffx.hip": ["-fno-slp-vectorize"], "ffx16.hip": ["-fno-slp-vectorize"], "tkl.hip": ["-fno-slp-vectorize"], "tkl16.hip": ["-fno-slp-vectorize"], "atk.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"], "atb.hip": ["-fno-slp-vectorize"], "atl.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"], "tkc.hip": ["-fno-slp-vectorize"], "tkw.hip": ["-fno-slp-vectorize"]}
+EXTRA_FLAGS = {"sampler.hip": ["-ffp-contract=off"], "guide.hip": ["-ffp-contract=off"], "guide_replan.hip": ["-ffp-contract=off"], "guide_prims.hip": ["-ffp-contract=off"], "guide_team.hip": ["-ffp-contract=off"], "resample.hip": ["-ffp-contract=off"], "clearance.hip": ["-ffp-contract=off"], "team.hip": ["-ffp-contract=off"], "stitch.hip": ["-ffp-contract=off"], "warm.hip": ["-ffp-contract=off"], "ffx.hip": ["-fno-slp-vectorize"], "ffx16.hip": ["-fno-slp-vectorize"], "tkl.hip": ["-fno-slp-vectorize"], "tkl16.hip": ["-fno-slp-vectorize"], "atk.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"], "atb.hip": ["-fno-slp-vectorize"], "atl.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form"], "tkc.hip": ["-fno-slp-vectorize"], "tkw.hip": ["-fno-slp-vectorize"]}
 
 
 def _stale(out: str, deps) -> bool:

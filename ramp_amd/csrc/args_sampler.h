@@ -149,6 +149,13 @@ struct StitchArgs {
 int launch_stitch(const StitchArgs& a, hipStream_t s);
 // out (C, L, S): every long waypoint from the window with the smallest w that covers it
 int launch_stitch_assemble(const float* x, float* out, int C, int W, int H, int S, int O, hipStream_t s);
+// ---- warm-started jobs (warm.hip; ramp_warm_start in ramp_hip.h) --------------------------------------
+// x[b] = has_prior[b] ? (sa_row[b] * prior[b]) + (s1a_row[b] * noise0[b]) : noise0[b] (the same bits); every array (B, H, S) and 16-byte
+// aligned, H S a multiple of 4, the three tables device (B).  x may be noise0 (in place); prior is not read for a row without one
+int launch_warm_init(float* x, const float* noise0, const float* prior, const float* sa_row, const float* s1a_row, const int* has_prior,
+                     int B, int H, int S, hipStream_t s);
+// rows with j0[b] > j: x[b] = x_init[b] and, chain_block != nullptr, chain_block[b] = x_init[b]; the other rows are not touched
+int launch_warm_hold(float* x, float* chain_block, const float* x_init, const int* j0, int j, int B, int H, int S, hipStream_t s);
 struct ApfDynArgs {
   float* traj = nullptr;          // (B,H,S) in place (xy only)
   const double* points = nullptr; // (P,2) float64

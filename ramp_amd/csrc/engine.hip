@@ -166,6 +166,11 @@ struct ramp_ctx {
   // pin values (n_pin, C, S), copied here before the launch -- data of a replay.  Windows, overlap, n_pin and the pin indices are kernel
   // arguments, hence part of the graph key
   float* st_alpha = nullptr; size_t st_alpha_cap = 0; float* st_pin_val = nullptr; size_t st_pin_val_cap = 0;
+  // warm-started jobs (ramp_sample_warm): the rows' priors (B, H, S), {j0 | has_prior} (2 B int32) and {sa | s1a} (2 B floats), copied here
+  // before the launch -- data of a replay: levels and priors are not in the graph key -- and x_init (B, H, S), which the job itself writes and
+  // the holds read (it exists only for a job with n_hold > 0; n_hold is in the key)
+  float* w_prior = nullptr; size_t w_prior_cap = 0; int* w_tab = nullptr; size_t w_tab_cap = 0; float* w_coef = nullptr; size_t w_coef_cap = 0;
+  float* w_xinit = nullptr; size_t w_xinit_cap = 0;
   // graph cache: five slots, every one captured and replayed by replay() and released by drop_graphs().  s_graph belongs to graph_key (the job
   // shape): [0] the job whose first evaluation calibrates itself, [1] the steady job, [2] the repeat of a flagged job (graph_rerun_key).
   hipGraphExec_t s_graph[3] = {nullptr, nullptr, nullptr}; std::string graph_key, graph_rerun_key;
@@ -2015,6 +2020,7 @@ struct ResampleJob {
 // (ramp_sample_guided_prims), tg: the separation term between the rows of a team (ramp_sample_guided_team): behind the checks each is set only
 // next to such a guide and where its table changes the guide (a primitive with w_prim != 0; more than one agent with w_team != 0)
 // rj: active (resampling()) only with an event somewhere;  st: stitched windows (ramp_sample_stitched)
+// ws: a warm start (ramp_sample_warm): the rows' priors and levels; p and every option table hold the tail of the schedule only
 struct SampleJob {
   const char* who; const ramp_sample_params* p; const ramp_scene_batch* sc;
   const float* noise; float* chain_out; float* x_out;
@@ -2023,6 +2029,7 @@ struct SampleJob {
   const ramp_prim_guide* pg = nullptr; const ramp_team_guide* tg = nullptr;
   ResampleJob rj = {nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr};
   const ramp_stitch* st = nullptr;
+  const ramp_warm_start* ws = nullptr;
   const McmcJob* mcmc() const { return mj.total > 0 ? &mj : nullptr; }
   const ResampleJob* resampling() const { return rj.n_events > 0 ? &rj : nullptr; }
 };
@@ -2034,9 +2041,11 @@ struct SampleJob {
 // array the hooks work on, in front of them and (where one ran) behind them; every noise block is stitched with alpha = 0 first
 // rj != nullptr: on iteration j with resample[j] != 0 the cost of that array (behind the guide) updates the log-weights, and at the end of the
 // iteration every group is resampled: three launches and the copy back, unconditional (identity where nothing resampled), so the graph has no branch
+// ws != nullptr: the warm init takes the place of the x_T copy, and on iteration j < ws->n_hold ONE launch at the end of the iteration puts
+// every row that has not started yet (j0 > j) back to x_init, in the state and in the chain block
 static int sample_body(ramp_ctx* c, const SampleJob& job, hipStream_t s, bool chain, bool steady, int cal_eval) {
   const ramp_sample_params* p = job.p; const ramp_scene_batch* sc = job.sc; const ramp_cost_guide* cg = job.cg; const ramp_stitch* st = job.st;
-  const McmcJob* mj = job.mcmc(); const ResampleJob* rj = job.resampling();
+  const McmcJob* mj = job.mcmc(); const ResampleJob* rj = job.resampling(); const ramp_warm_start* ws = job.ws;
   const int B = p->B, H = c->cfg.horizon, S = c->cfg.state_dim;
   const size_t HS = (size_t)H * S, n = (size_t)B * HS;
   HardConds hc; hc.idx = c->s_hard_idx; hc.val = c->s_hard_val; hc.n = p->n_hard;
@@ -2069,11 +2078,14 @@ static int sample_body(ramp_ctx* c, const SampleJob& job, hipStream_t s, bool ch
     LAUNCH(c, s, CAT_SAMPLER, 0, launch_stitch(sa, s));
     return 0;
   };
-  // x_T = noise[0]; apply_hard_conditioning; chain[0]
-  RAMP_HIP_CHECK(hipMemcpyAsync(c->s_x, c->s_noise, n * 4, hipMemcpyDeviceToDevice, s));
+  // x_T = noise[0] (a warm start: every row with a prior its prior noised to its own level); apply_hard_conditioning; chain[0]
+  if (ws) LAUNCH(c, s, CAT_SAMPLER, 0, launch_warm_init(c->s_x, c->s_noise, c->w_prior, c->w_coef, c->w_coef + B, c->w_tab + B, B, H, S, s));
+  else RAMP_HIP_CHECK(hipMemcpyAsync(c->s_x, c->s_noise, n * 4, hipMemcpyDeviceToDevice, s));
   if (st) CK(stitch_at(c->s_x));
   else LAUNCH(c, s, CAT_SAMPLER, 0, launch_hard_cond(c->s_x, hc, B, H, S, s));
   if (chain) RAMP_HIP_CHECK(hipMemcpyAsync(c->s_chain, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
+  const int n_hold = ws ? ws->n_hold : 0;
+  if (n_hold > 0) RAMP_HIP_CHECK(hipMemcpyAsync(c->w_xinit, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));      // x_init, for the holds
   ApfArgs ap; ap.cloud = c->s_cloud; ap.window = c->s_window; ap.B = B; ap.H = H; ap.S = S; ap.P = p->apf.n_points;
   ap.win = p->apf.window; ap.thr = p->apf.threshold; ap.strength = p->apf.strength;
   const bool sc_apf = sc && sc->cloud_points;
@@ -2238,6 +2250,7 @@ static int sample_body(ramp_ctx* c, const SampleJob& job, hipStream_t s, bool ch
       if (chain_j) RAMP_HIP_CHECK(hipMemcpyAsync(chain_j, c->s_x, n * 4, hipMemcpyDeviceToDevice, s));
     }
     CK(resample_at(j, chain_j));
+    if (j < n_hold) LAUNCH(c, s, CAT_SAMPLER, 0, launch_warm_hold(c->s_x, chain_j, c->w_xinit, c->w_tab, j, B, H, S, s));
   }
   return 0;
 }
@@ -2520,6 +2533,55 @@ static void key_stitch(Key& key, const ramp_stitch* st) {
   if (st->n_pin) key.put(st->pin_idx_host, st->n_pin);
 }
 
+// A warm start (ramp_sample_warm, the only entry that brings one)
+static int check_warm(ramp_ctx* c, const SampleJob& job) {
+  const ramp_warm_start* ws = job.ws; const ramp_sample_params* p = job.p;
+  if (!ws) return 0;
+  const std::string w = std::string(job.who) + ": ";
+  RAMP_REQUIRE(p->B > 0 && p->n_steps > 0, w + "bad sample dims");
+  RAMP_REQUIRE(ws->j0_host && ws->has_prior_host, w + "null j0 / has_prior table");
+  RAMP_REQUIRE((c->cfg.horizon * c->cfg.state_dim) % 4 == 0, w + "H * S must be a multiple of 4 (the warm start moves four elements per access)");
+  RAMP_REQUIRE(ws->n_hold >= 0 && ws->n_hold < p->n_steps, w + "n_hold outside 0 .. n_steps - 1");
+  int top = 0;
+  for (int b = 0; b < p->B; ++b) {
+    const int j0 = ws->j0_host[b];
+    RAMP_REQUIRE(j0 >= 0 && j0 <= ws->n_hold, w + "j0 outside 0 .. n_hold");
+    top = std::max(top, j0);
+    if (!ws->has_prior_host[b]) { RAMP_REQUIRE(j0 == 0, w + "a row without a prior starts at iteration 0 (j0 != 0)"); continue; }
+    RAMP_REQUIRE(ws->prior && ws->sa_host && ws->s1a_host, w + "null prior / coefficient table with a prior somewhere");
+    RAMP_REQUIRE(std::isfinite(ws->sa_host[b]) && std::isfinite(ws->s1a_host[b]), w + "a start coefficient is not finite");
+  }
+  RAMP_REQUIRE(top == ws->n_hold, w + "n_hold must be the largest j0");
+  if (ws->n_hold > 0) {      // mixed levels
+    RAMP_REQUIRE(!job.resampling(), w + "mixed levels with resampling events are not served (a held row could become an ancestor)");
+    RAMP_REQUIRE(!job.tg, w + "mixed levels with a team are not served (a held agent would face moving team mates)");
+    RAMP_REQUIRE(!job.st, w + "mixed levels on stitched windows are not served (the windows of a chain start together)");
+  }
+  return 0;
+}
+// priors, {j0 | has_prior} and {sa | s1a} into the context; x_init's buffer where a hold will read it
+static int stage_warm(ramp_ctx* c, const SampleJob& job, hipStream_t s) {
+  const ramp_warm_start* ws = job.ws;
+  const size_t B = (size_t)job.p->B, n = B * c->cfg.horizon * c->cfg.state_dim;
+  std::vector<int32_t> tab(2 * B); std::vector<float> coef(2 * B, 0.f);
+  bool any = false;
+  for (size_t b = 0; b < B; ++b) {
+    tab[b] = ws->j0_host[b]; tab[B + b] = ws->has_prior_host[b] != 0;
+    if (tab[B + b]) { coef[b] = ws->sa_host[b]; coef[B + b] = ws->s1a_host[b]; any = true; }
+  }
+  // (tab / coef are pageable host memory: their copies are staged before the call returns, so the vectors may go out of scope)
+  CK(stage_table(c, c->w_tab, c->w_tab_cap, (const int*)tab.data(), tab.size(), 0, hipMemcpyHostToDevice, s));
+  CK(stage_table(c, c->w_coef, c->w_coef_cap, (const float*)coef.data(), coef.size(), 0, hipMemcpyHostToDevice, s));
+  CK(stage_table(c, c->w_prior, c->w_prior_cap, ws->prior, any ? n : 0, n, hipMemcpyDeviceToDevice, s));
+  if (ws->n_hold > 0) CK(grow(c, c->w_xinit, c->w_xinit_cap, n));
+  return 0;
+}
+// (w_prior / w_tab / w_coef exist only for such a job, w_xinit only with a hold; levels, coefficients and priors are data of the graph.  The
+// hold's iteration index is a kernel argument, and n_hold decides how many holds the graph has)
+static void key_warm(Key& key, const ramp_warm_start* ws) {
+  const int tag[2] = {0x5741524d /* "WARM" */, ws->n_hold}; key.put(tag, 2);
+}
+
 // A checked job (run_sample): parameter checks, buffers, staging, the canonical calibration, the graph and the copy-out
 static int sample_job(ramp_ctx* c, const SampleJob& job, void* stream) {
   const ramp_sample_params* p = job.p; const ramp_scene_batch* sc = job.sc; const ramp_guidance_rows* g = job.g; const float* noise = job.noise;
@@ -2553,6 +2615,7 @@ static int sample_job(ramp_ctx* c, const SampleJob& job, void* stream) {
   if (job.cg) CK(stage_guide(c, job, s));
   if (rj) CK(stage_resample(c, job, s));
   if (job.st) CK(stage_stitch(c, job, s));
+  if (job.ws) CK(stage_warm(c, job, s));
   std::vector<float> g_host;      // a composed job's weights on the host: part of the canonical calibration's key below
   if (g) CK(stage_guidance(c, job, s, g_host));
   if (p->n_hard) RAMP_HIP_CHECK(hipMemcpyAsync(c->s_hard_idx, p->hard_idx_host, p->n_hard * 4, hipMemcpyHostToDevice, s));
@@ -2589,6 +2652,7 @@ static int sample_job(ramp_ctx* c, const SampleJob& job, void* stream) {
   if (job.cg) key_guide(key, job);
   if (rj) key_resample(key, job);
   if (job.st) key_stitch(key, job.st);
+  if (job.ws) key_warm(key, job.ws);
   const bool h3 = c->gemm_mode == 2 && !c->force_x6;
   const bool steady = h3 && c->cal_reuse;
   if (steady) {
@@ -2662,7 +2726,7 @@ static int run_sample(ramp_ctx* c, const SampleJob& stated, void* stream) {
     CK(check_stitch_job(c, job));
     RAMP_REQUIRE(kind >= 0 && kind <= 2, w + "kind must be 0 (off), 1 (ULA) or 2 (MALA)");      // (in front of the guidance table's checks)
     if (job.g) CK(check_guidance(c, job.p, job.g, job.who));
-    CK(check_mcmc(job)); CK(check_guide(c, job)); CK(check_resample(c, job));
+    CK(check_mcmc(job)); CK(check_guide(c, job)); CK(check_resample(c, job)); CK(check_warm(c, job));
     return sample_job(c, job, stream);
   }();
   c->g_weight_cur = nullptr;      // on every return path
@@ -2754,6 +2818,27 @@ int ramp_sample_stitched(ramp_ctx* c, const ramp_sample_params* p, const ramp_st
   if (!st) RAMP_REQUIRE(!long_out, "ramp_sample_stitched: long_out needs a stitch table");
   SampleJob job{st ? "ramp_sample_stitched" : "ramp_sample_guided", p, scenes, noise, chain_out, x_out, nullptr, cg};
   job.st = st;
+  CK(run_sample(c, job, stream));
+  if (!st || !long_out) return 0;
+  return launch_stitch_assemble(c->s_x, long_out, p->B / st->n_windows, st->n_windows, c->cfg.horizon, c->cfg.state_dim, st->overlap, as_stream(stream));
+}
+
+// Any job of the family above from a warm start: ws == NULL is the entry that takes the same options, and launches what it launches
+int ramp_sample_warm(ramp_ctx* c, const ramp_sample_params* p, const ramp_warm_start* ws, const ramp_stitch* st,
+                     const ramp_resample_params* rs, const ramp_cost_guide* cg, const ramp_prim_guide* pg, const ramp_team_guide* tg,
+                     const ramp_mcmc_params* m, const ramp_guidance_rows* g, const ramp_scene_batch* scenes, const float* noise,
+                     const float* mcmc_noise, const float* mcmc_u, const float* resample_u, float* chain_out, float* x_out,
+                     int32_t* accept_out, int32_t* ancestor_out, double* ess_out, double* cost_out, double* logw_out, float* long_out,
+                     void* stream) {
+  RAMP_REQUIRE(c && p, "ramp_sample_warm: null argument");
+  RAMP_REQUIRE(!(pg && tg), "ramp_sample_warm: a job carries a team or primitives, never both");
+  RAMP_REQUIRE(!st || !(rs || pg || tg || m || g), "ramp_sample_warm: stitched windows take no resampling, primitives, team, MCMC or composed weights");
+  RAMP_REQUIRE(st || !long_out, "ramp_sample_warm: long_out needs a stitch table");
+  ResampleJob rj{rs, 0, resample_u, ancestor_out, ess_out, cost_out, logw_out};
+  if (rs && rs->resample) for (int j = 0; j < p->n_steps; ++j) rj.n_events += rs->resample[j] != 0;
+  if (rj.n_events) RAMP_REQUIRE(rs->cost, "ramp_sample_warm: null cost table");
+  SampleJob job = refined_job("ramp_sample_warm", p, cg, m, g, scenes, noise, mcmc_noise, mcmc_u, chain_out, x_out, accept_out);
+  job.pg = pg; job.tg = tg; job.rj = rj; job.st = st; job.ws = ws;
   CK(run_sample(c, job, stream));
   if (!st || !long_out) return 0;
   return launch_stitch_assemble(c->s_x, long_out, p->B / st->n_windows, st->n_windows, c->cfg.horizon, c->cfg.state_dim, st->overlap, as_stream(stream));

@@ -5,6 +5,8 @@
 // not the sampler.
 #include "engine_util.h"
 
+#include <functional>
+
 namespace {
 // What every ramp_op_* entry point with a scaled operand does around its own pack call and argument struct.  Device memory lives as long
 // as the call (a DevArena).  begin(), called behind the pack: the slots of `n` operand sites -- previous maxima [0, n), recorded maxima
@@ -336,6 +338,46 @@ int ramp_stitch_assemble(const float* x, int32_t C, int32_t W, int32_t H, int32_
   const int rc = launch_stitch_assemble(x, long_out, C, W, H, S, O, s);
   (void)hipStreamSynchronize(s);
   return rc;
+}
+
+// the warm start's two kernels on the caller's arrays: the per-row tables go to the device in one block of their own (synchronises `stream`)
+static int warm_op(const char* who, const int32_t* ints_host, const float* f0_host, const float* f1_host, int32_t B, hipStream_t s,
+                   const std::function<int(const int*, const float*, const float*)>& launch) {
+  static_assert(sizeof(float) == sizeof(int32_t), "one block of 4-byte words");
+  std::vector<int32_t> blk(3 * (size_t)B, 0);
+  std::memcpy(blk.data(), ints_host, (size_t)B * 4);
+  if (f0_host) std::memcpy(blk.data() + B, f0_host, (size_t)B * 4);
+  if (f1_host) std::memcpy(blk.data() + 2 * (size_t)B, f1_host, (size_t)B * 4);
+  int32_t* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, blk.size() * 4));
+  int rc = 0;
+  if (hipMemcpy(d, blk.data(), blk.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { set_last_error(std::string(who) + ": copy of the tables failed"); rc = -1; }
+  if (rc == 0) rc = launch(d, reinterpret_cast<const float*>(d + B), reinterpret_cast<const float*>(d + 2 * (size_t)B));
+  (void)hipStreamSynchronize(s);
+  (void)hipFree(d);
+  return rc;
+}
+
+int ramp_warm_init(float* x, const float* noise0, const float* prior, const float* sa_host, const float* s1a_host,
+                   const int32_t* has_prior_host, int32_t B, int32_t H, int32_t S, void* stream) {
+  RAMP_REQUIRE(x && noise0 && prior && sa_host && s1a_host && has_prior_host, "ramp_warm_init: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0 && ((long)H * S) % 4 == 0 && (long)B * H * S < (1l << 31),
+               "ramp_warm_init: bad dims (H * S must be a multiple of 4)");
+  hipStream_t s = as_stream(stream);
+  return warm_op("ramp_warm_init", has_prior_host, sa_host, s1a_host, B, s, [&](const int* has, const float* sa, const float* s1a) {
+    return launch_warm_init(x, noise0, prior, sa, s1a, has, B, H, S, s);
+  });
+}
+
+int ramp_warm_hold(float* x, float* chain_block, const float* x_init, const int32_t* j0_host, int32_t j, int32_t B, int32_t H, int32_t S,
+                   void* stream) {
+  RAMP_REQUIRE(x && x_init && j0_host, "ramp_warm_hold: null argument");
+  RAMP_REQUIRE(B > 0 && H > 0 && S > 0 && ((long)H * S) % 4 == 0 && (long)B * H * S < (1l << 31),
+               "ramp_warm_hold: bad dims (H * S must be a multiple of 4)");
+  hipStream_t s = as_stream(stream);
+  return warm_op("ramp_warm_hold", j0_host, nullptr, nullptr, B, s, [&](const int* j0, const float*, const float*) {
+    return launch_warm_hold(x, chain_block, x_init, j0, j, B, H, S, s);
+  });
 }
 
 // the replans' guide kernels on the caller's arrays: offsets | hard-condition indices | moving points | tracks go to the device in one block

@@ -299,6 +299,7 @@ class _GaussianDiffusionBase(nn.Module):
         # draws exactly the elements the unsharded job draws for those samples (set_noise_shard; ramp_sample_params.philox_sample0)
         self._philox_shard = None
         self.last_resample = None               # after a job with resample=: {'ancestors': (n_events, B) int32, 'ess': (n_events, n_groups), 'cost': (n_events, B), 'logw': (B,), 'group_first', 'events'}
+        self.last_warm = None                   # after a job with warm_start=: {'J', 'j0': (B,) int32, 't_row': (B,) int32 (-1: no prior), 'steps': the iterations the job ran}
         self.last_mcmc = None                   # after a job with mcmc=: {'accept': (sum K, B) int32, 'rate': per iteration, 'n_inner': per iteration}
         self.context_model = context_model
         self.n_diffusion_steps = n_diffusion_steps
@@ -713,10 +714,61 @@ class _GaussianDiffusionBase(nn.Module):
             again(1)
             self.last_job_mode = "bf16x6"
 
+    def _warm_job(self, warm_start, B: int, steps_full, scene_job: Optional[dict] = None, stitch: Optional[dict] = None):
+        """``warm_start=dict(prior=, level=, start=None)`` of run_inference* resolved for a job of ``B`` rows on the model's iteration list
+        ``steps_full`` (``ramp_amd.warm`` states the definition): host checks only, before anything of the job touches the device.
+
+          prior   normalised trajectories of the job's rows: (B, H, S), or (H, S) / (1, H, S) for all rows, or one entry per scene of a scene /
+                  composed job (``warm.prior_rows``); rows without a level are not read.  None where no row has a level
+          level   an int (every row), a (B,) sequence with None entries (no prior: the row starts from noise and runs the whole job), or one
+                  entry per scene
+          start   None, or the level the JOB starts at where it must not follow from these rows alone (a sharded caller passes the whole
+                  job's value, so that every shard lays out the same noise block)
+
+        Returns the resolved dict (``J``, ``j0``, ``t_row``, ``n_hold``, the device ``prior`` (B, H, S), ``sa`` / ``s1a`` / ``has``), or its
+        argument where that is one already."""
+        if warm_start is None or (isinstance(warm_start, dict) and warm_start.get('_resolved')):
+            return warm_start
+        from . import warm as W
+        if not self._scenes_supported:
+            raise NotImplementedError(f"warm_start=: {type(self).__name__} keeps its own replanning")
+        if not isinstance(warm_start, dict):
+            raise TypeError("warm_start= takes a dict(prior=, level=, start=None)")
+        unknown = set(warm_start) - {'prior', 'level', 'start'}
+        if unknown:
+            raise ValueError(f"warm_start=: unknown keys {sorted(unknown)}")
+        if 'level' not in warm_start:
+            raise ValueError("warm_start=: level= is required")
+        dev, H, S = self._device(), self.model.n_support_points, self.state_dim
+        counts = [B]
+        if scene_job is not None and stitch is None:      # a scene's rows are adjacent, scenes in order
+            counts = np.bincount(scene_job['traj_scene'].cpu().numpy(), minlength=int(scene_job['n_scenes'])).tolist()
+        levels = W.level_rows(warm_start['level'], counts)
+        tab = W.warm_tables(levels, steps_full, warm_start.get('start'), T=self.n_diffusion_steps)
+        has = tab['t_row'] >= 0
+        prior = warm_start.get('prior')
+        if prior is None:
+            if has.any():
+                raise ValueError("warm_start=: prior= is required where a row has a level")
+            prior = torch.zeros((B, H, S), device=dev)
+        else:
+            if not (torch.is_tensor(prior) or (isinstance(prior, (list, tuple)) and len(prior) and torch.is_tensor(prior[0]))):
+                prior = [np.asarray(v, np.float32) for v in prior] if isinstance(prior, (list, tuple)) else np.asarray(prior, np.float32)
+            prior = W.prior_rows(prior, counts)
+            prior = (prior if torch.is_tensor(prior) else torch.from_numpy(np.array(prior, np.float32))).to(dev, torch.float32).contiguous()
+        if tuple(prior.shape) != (B, H, S):
+            raise ValueError(f"warm_start=: the prior must hold ({B}, {H}, {S}) for the job's rows; got {tuple(prior.shape)}")
+        if has.any() and not bool(torch.isfinite(prior[torch.from_numpy(has).to(dev)]).all()):
+            raise ValueError("warm_start=: the prior is not finite")
+        t_safe = np.where(has, tab['t_row'], 0)
+        sa = self.sqrt_alphas_cumprod.detach().cpu().numpy().astype(np.float32)[t_safe]
+        s1a = self.sqrt_one_minus_alphas_cumprod.detach().cpu().numpy().astype(np.float32)[t_safe]
+        return dict(tab, _resolved=True, prior=prior, sa=sa, s1a=s1a, has=has.astype(np.int32), steps_full=[int(s) for s in steps_full])
+
     def _launch(self, B, noise, hard_conds, obstacle_pts, ddim: bool, steps, apply_apf, noise_scale, apf_cfg,
                 return_chain: bool, ddim_K: Optional[int] = None, scene_job: Optional[dict] = None, guidance: Optional[dict] = None,
                 mcmc: Optional[dict] = None, cost_guide: Optional[dict] = None, resample: Optional[dict] = None,
-                stitch: Optional[dict] = None):
+                stitch: Optional[dict] = None, warm_start: Optional[dict] = None):
         """One fused sampling job (``ramp_sample``).  ``scene_job``: what ``_prepare_scene_job`` returned -- a job of many scenes
         (``ramp_sample_scenes``); ``obstacle_pts`` is not read then.  ``guidance`` (with a ``scene_job``): a composed job
         (``ramp_sample_composed``) -- ``n_rp`` rows per trajectory and the device (B, n_rp) ``row_weight`` table of ``_prepare_composed_job``.
@@ -725,14 +777,35 @@ class _GaussianDiffusionBase(nn.Module):
         same one entry with the guide added; ``guide_tables``).  ``resample``: resampling events inside the job (``ramp_sample_steered``;
         ``resample_tables``); ancestors, ESS, costs and final log-weights land in ``self.last_resample``.  ``stitch`` (with a ``scene_job``
         and empty ``hard_conds``): stitched windows (``ramp_sample_stitched``) -- the dict of ``run_inference_stitched``: ``n_windows``,
-        ``overlap``, ``alpha`` (O) float32, ``pin_idx`` (n_pin) int32, ``pin_val`` device (n_pin, C, S) or None."""
+        ``overlap``, ``alpha`` (O) float32, ``pin_idx`` (n_pin) int32, ``pin_val`` device (n_pin, C, S) or None.  ``warm_start``: the rows start
+        from given plans at levels of their own (``ramp_sample_warm``, the one entry for every job above; ``_warm_job`` / ``ramp_amd.warm``).
+        ``steps`` / ``apply_apf`` / ``noise_scale`` are then still the model's FULL lists: the job runs their tail from iteration J, ``noise``
+        holds that tail's blocks, and ``self.last_warm`` keeps ``J``, ``j0``, ``t_row`` and the job's ``steps``."""
         m = self.model
         # ---- refusals and the options' host tables, before anything touches the device
         if stitch is not None and (mcmc is not None or resample is not None or guidance is not None or hard_conds):
             raise NotImplementedError("stitched windows take no mcmc=, resample=, composed weights or hard conditions of their own")
         self._refuse_prims_outside_the_guide(cost_guide, resample, stitch)
         self._refuse_team_outside_the_guide(cost_guide, resample, stitch, [B])
-        rtab = resample_tables(resample, steps) if resample is not None else None
+        warm = self._warm_job(warm_start, B, steps, scene_job, stitch)
+        rtab = resample_tables(resample, steps) if resample is not None else None      # (flags by iteration index: on the full list)
+        if warm is not None:
+            if warm['n_hold'] > 0:
+                if resample is not None:
+                    raise NotImplementedError("warm_start=: mixed levels with resample= are not served (a held row could become an ancestor)")
+                if guide_has_team(cost_guide):
+                    raise NotImplementedError("warm_start=: mixed levels with cost_guide team= are not served (a held agent would face moving team mates)")
+                if stitch is not None:
+                    raise NotImplementedError("warm_start=: mixed levels inside one stitched chain are not served (the windows of a chain start together)")
+            J = warm['J']      # the job is the tail of the schedule: whatever indexes the full list was computed on it and loses J entries
+            steps, apply_apf = list(steps)[J:], list(apply_apf)[J:]
+            noise_scale = list(noise_scale)[J:] if noise_scale is not None else None
+            if rtab is not None:
+                rtab = dict(rtab, resample=rtab['resample'][J:], events=[j - J for j in rtab['events'] if j >= J])
+                rtab['lambda'] = rtab['lambda'][J:]
+            n_blocks = 1 if ddim else len(steps) + 1
+            if noise is not None and noise.shape[0] != n_blocks:
+                raise ValueError(f"warm_start=: the job runs {len(steps)} iterations and takes {n_blocks} noise blocks; got {noise.shape[0]}")
         if rtab is not None:
             if self._philox_shard is not None:
                 raise NotImplementedError("resample=: a sharded job (set_noise_shard) cannot resample -- a group's trajectories would sit on "
@@ -800,6 +873,12 @@ class _GaussianDiffusionBase(nn.Module):
             z_in, u_in = self._mcmc_draws(mcmc, tab, B, noise)
         from .stitch import fill_stitch
         st = fill_stitch(*(stitch[k] for k in ('n_windows', 'overlap', 'alpha', 'pin_idx', 'pin_val'))) if stitch is not None else None
+        ws = None
+        if warm is not None:
+            ws = _lib.RampWarmStart()
+            ws.prior, ws.n_hold = _lib.ptr(arrays.keep(warm['prior'])), warm['n_hold']
+            ws.j0_host, ws.has_prior_host = arrays.i32(warm['j0']), arrays.i32(warm['has'])
+            ws.sa_host, ws.s1a_host = arrays.f32(warm['sa']), arrays.f32(warm['s1a'])
         if noise is None:         # the job draws its own, the options' draws included
             p.noise_mode = 1
             p.philox_seed, p.philox_offset, p.philox_sample0, p.philox_total = self._philox_block(B, n_steps, ddim, tab['total'] if tab else 0,
@@ -814,7 +893,11 @@ class _GaussianDiffusionBase(nn.Module):
         middle = (opt(mp), opt(rows), opt(batch), _lib.ptr(noise), _lib.ptr(z_in), _lib.ptr(u_in))
         plain = (_lib.ptr(noise), _lib.ptr(chain), _lib.ptr(x_out))
         outs = (_lib.ptr(chain), _lib.ptr(x_out), _lib.ptr(accept))
-        if st is not None:
+        if ws is not None:      # the one entry that takes every option
+            entry = "ramp_sample_warm"
+            args = ((C.byref(ws), opt(st), opt(rs), opt(cg), opt(pg), opt(tg)) + middle + (_lib.ptr(ru),) + outs + tuple(_lib.ptr(t) for t in r_out)
+                    + (None,))
+        elif st is not None:
             entry, args = "ramp_sample_stitched", (C.byref(st), opt(cg), opt(batch)) + plain + (None,)
         elif rs is not None:
             entry, args = "ramp_sample_steered", (C.byref(rs), opt(cg)) + middle + (_lib.ptr(ru),) + outs + tuple(_lib.ptr(t) for t in r_out)
@@ -837,11 +920,17 @@ class _GaussianDiffusionBase(nn.Module):
             self._run_guarded(lambda: _lib.check(fn(m.ctx(), C.byref(p), *args, _lib.current_stream()), entry))
         # ---- results
         r_anc, r_ess, r_cost, r_logw = r_out
+        if warm is not None:
+            self.last_warm = {'J': warm['J'], 'j0': warm['j0'].copy(), 't_row': warm['t_row'].copy(), 'steps': list(steps)}
         if tab is not None:      # one copy back
             acc = accept.cpu()
             rate, k0 = [], 0
-            for K in tab['n_inner']:
-                rate.append(float(acc[k0:k0 + K].float().mean()) if K else float('nan'))
+            held = torch.from_numpy(warm['j0']) if warm is not None and warm['n_hold'] > 0 else None
+            for j, K in enumerate(tab['n_inner']):
+                if held is not None and K:      # a held row's inner steps are undone by the hold: flag -1, left out of the rate
+                    acc[k0:k0 + K, held > j] = -1
+                live = acc[k0:k0 + K][acc[k0:k0 + K] >= 0] if K else None
+                rate.append(float(live.float().mean()) if K and live.numel() else float('nan'))
                 k0 += K
             self.last_mcmc = {'accept': acc, 'rate': rate, 'n_inner': list(tab['n_inner']), 'kind': tab['kind']}
         if rtab is not None:
@@ -866,12 +955,14 @@ class _GaussianDiffusionBase(nn.Module):
     def p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                       obstacle_pts=None, sample_fn=ddpm_sample_fn, n_diffusion_steps_without_noise=0,
                       noise_std_extra_schedule_fn=None, scene_job=None, guidance=None, mcmc=None, cost_guide=None, resample=None,
-                      stitch=None, **sample_kwargs):
+                      stitch=None, warm_start=None, **sample_kwargs):
         """diffusion_model_static.py:232-256 / diffusion_model_3d.py:185-218 (resample_steps = 1).  With the stock
         ``ddpm_sample_fn`` the whole loop is ONE fused job (``ramp_sample``: captured graph, noise and schedule tables on the
         device); any other ``sample_fn`` is honoured the way the reference honours it -- called once per step with the
         reference's arguments -- on the eager loop below."""
         if not self._is_fused_ddpm_step(sample_fn):
+            if warm_start is not None:
+                raise NotImplementedError("warm_start= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if mcmc is not None:
                 raise NotImplementedError("mcmc= runs inside the fused job only (ddpm_sample_fn): a caller-supplied sample_fn steps on its own")
             if cost_guide is not None:
@@ -890,7 +981,8 @@ class _GaussianDiffusionBase(nn.Module):
         philox = self.noise_source == "philox"
         x = None if philox else torch.randn(shape, device=device)
         steps, raw = self._ddpm_steps(n_diffusion_steps_without_noise)
-        noises = [x] + ([] if philox else [torch.randn_like(x) for _ in steps])       # drawn every step, zeroed at t == 0
+        warm = self._warm_job(warm_start, B, steps, scene_job, stitch)      # (a warm-started job draws its tail's blocks only)
+        noises = [x] + ([] if philox else [torch.randn_like(x) for _ in steps[(warm['J'] if warm else 0):]])       # drawn every step, zeroed at t == 0
         if noise_std_extra_schedule_fn is None:
             scales = [1.0] * len(steps)
         else:       # the reference hands the schedule function t[0], a 0-d long tensor on the device (sample_functions.py:24, 41-44)
@@ -902,7 +994,7 @@ class _GaussianDiffusionBase(nn.Module):
         cfg = dict(self.apf_ddpm, passes=1) if any(apf) else None
         x_out, chain = self._launch(B, None if philox else torch.stack(noises), hard_conds, obstacle_pts, False, steps, apf, scales,
                                     cfg, return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide,
-                                    resample=resample, stitch=stitch)
+                                    resample=resample, stitch=stitch, warm_start=warm)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)       # reference stacks along dim=1
         return x_out
@@ -944,7 +1036,7 @@ class _GaussianDiffusionBase(nn.Module):
     @torch.no_grad()
     def ddim_p_sample_loop(self, shape, hard_conds, context=None, return_chain=False, traj_normalized=None,
                            obstacle_pts=None, t_start_guide=float('inf'), guide=None, n_guide_steps=1, scene_job=None,
-                           guidance=None, mcmc=None, cost_guide=None, resample=None, stitch=None, **sample_kwargs):
+                           guidance=None, mcmc=None, cost_guide=None, resample=None, stitch=None, warm_start=None, **sample_kwargs):
         """diffusion_model_static.py:347-384 (eta = 0, use_clipped_model_output)."""
         device = self._device()
         B = shape[0]
@@ -954,7 +1046,7 @@ class _GaussianDiffusionBase(nn.Module):
         cfg = dict(self.apf_ddim) if any(apf) else None
         x_out, chain = self._launch(B, None if x is None else x.unsqueeze(0), hard_conds, obstacle_pts, True, steps, apf, None, cfg,
                                     return_chain, scene_job=scene_job, guidance=guidance, mcmc=mcmc, cost_guide=cost_guide,
-                                    resample=resample, stitch=stitch)
+                                    resample=resample, stitch=stitch, warm_start=warm_start)
         if return_chain:
             return x_out, chain.permute(1, 0, 2, 3)
         return x_out
@@ -967,7 +1059,7 @@ class _GaussianDiffusionBase(nn.Module):
         self._refuse_prims_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'))
         self._refuse_team_outside_the_guide(sample_kwargs.get('cost_guide'), sample_kwargs.get('resample'), sample_kwargs.get('stitch'), [batch_size])
         if self.ddim:
-            for k in ('mcmc', 'cost_guide', 'resample'):
+            for k in ('mcmc', 'cost_guide', 'resample', 'warm_start'):
                 if sample_kwargs.get(k) is not None and not self._is_fused_ddpm_step(sample_kwargs.get('sample_fn')):
                     raise NotImplementedError(f"{k}= runs inside the fused job only: a caller-supplied sample_fn steps on its own")
             for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
@@ -1132,6 +1224,18 @@ class _GaussianDiffusionBase(nn.Module):
                'cloud_points': (torch.cat([s.reshape(-1, 2).to(dev, torch.float32) for s in scene_list]).contiguous() if use_cloud else None)}
         for k in ('guide', 'n_guide_steps', 't_start_guide'):
             diffusion_kwargs.pop(k, None)
+        ws = diffusion_kwargs.pop('warm_start', None)
+        if ws is not None:      # the prior is LONG, (C, L, S) or (L, S): cut into the windows' rows; the windows of a chain start together
+            lv = ws.get('level') if isinstance(ws, dict) else None
+            if not (lv is not None and np.isscalar(lv)):
+                raise NotImplementedError("run_inference_stitched: warm_start= takes one level for the whole job (mixed levels inside one "
+                                          "stitched chain are not served)")
+            pl = ws.get('prior')
+            pl = (pl.detach().cpu().numpy() if torch.is_tensor(pl) else np.asarray(pl)).astype(np.float32)
+            pl = np.broadcast_to(pl[None], (Cn,) + pl.shape) if pl.ndim == 2 else pl
+            if pl.ndim != 3 or pl.shape[0] != Cn or pl.shape[2] != S:
+                raise ValueError(f"run_inference_stitched: the warm-start prior must be ({Cn}, L, {S}) or (L, {S}); got {tuple(pl.shape)}")
+            diffusion_kwargs['warm_start'] = dict(ws, prior=_st.split_long(np.ascontiguousarray(pl), H, W, O))
         _samples, chain = self.conditional_sample({}, batch_size=tab['B'], ddim=False, return_chain=True, obstacle_pts=None, scene_job=job,
                                                   stitch=sd, cost_guide=cost_guide, **diffusion_kwargs)
         windows = chain.permute(1, 0, 2, 3)

@@ -724,6 +724,9 @@ class DynamicGaussianDiffusionModel(_GaussianDiffusionBase):
             raise NotImplementedError("cost_guide=: DynamicGaussianDiffusionModel has no cost guide of the sampling jobs' kind (the replanning jobs take replan_guide=)")
         if sample_kwargs.get('resample') is not None:
             raise NotImplementedError("resample=: DynamicGaussianDiffusionModel has no resampling (the replanning jobs are out of scope)")
+        if sample_kwargs.get('warm_start') is not None:
+            raise NotImplementedError("warm_start=: DynamicGaussianDiffusionModel keeps its own replanning (every replan already starts from "
+                                      "the running plan noised to an intermediate level)")
         for k in ('sample_fn', 'n_diffusion_steps_without_noise', 'noise_std_extra_schedule_fn'):
             sample_kwargs.pop(k, None)
         return self.ddim_p_sample_loop(shape, hard_conds, traj_normalized=traj_normalized, obstacle_pts=obstacle_pts,
