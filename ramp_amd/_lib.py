@@ -359,6 +359,14 @@ TOOL_PROTOTYPES = {
     "ramp_bench_gemm": (C.c_int, [C.c_int32] * 9 + [c_f32p, C.c_void_p]),
     "ramp_stress_gemm": (C.c_int, [C.c_int32] * 8 + [c_i64p, c_f32p, C.c_void_p]),
     "ramp_probe_gemm": (C.c_int, [C.POINTER(RampProbeGemmArgs), C.c_int32, C.c_float, c_f32p, c_i32p, C.c_void_p]),
+    "ramp_probe_conv_in_fwd": (C.c_int, [C.c_void_p] * 7 + [C.c_int32] * 5 + [C.c_void_p]),
+    "ramp_probe_conv_in_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 4 + [C.c_void_p]),
+    "ramp_probe_conv_out": (C.c_int, [C.c_void_p] * 5 + [C.c_int32] * 3 + [C.c_void_p]),
+    "ramp_probe_expand_rows": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ramp_probe_combine_rows": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [c_f32p, C.c_void_p]),
+    "ramp_probe_combine_rows_weighted": (C.c_int, [C.c_void_p] * 2 + [C.c_int32] * 4 + [C.c_void_p, C.c_void_p]),
+    "ramp_probe_cross_bias": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [C.POINTER(C.c_void_p)] * 3 + [C.c_int32, C.c_void_p, C.c_void_p]),
+    "ramp_probe_time_bias": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -456,6 +464,59 @@ def probe_gemm(mode="fp32", a_absmax_prev=0.0, **fields):
         m = tools.ramp_last_error()
         msg = m.decode() if m else ""
     return rc, amax.value, flag.value, msg
+
+
+def _probe(name, *args):
+    """One ramp_probe_* call of the tools library (args before the stream); (rc, error message or None) without raising, so that tests
+    can check refusals too."""
+    tools = load_tools()
+    rc = getattr(tools, name)(*args, current_stream())
+    msg = None
+    if rc != 0:
+        m = tools.ramp_last_error()
+        msg = m.decode() if m else ""
+    return rc, msg
+
+
+def probe_conv_in_fwd(x, W5, b5, W1, b1, c1, res, R, n_rp, H, S, C0):
+    """launch_conv_in_fwd on torch tensors: W5 packed [5][S][C0], W1 [S][C0]."""
+    return _probe("ramp_probe_conv_in_fwd", ptr(x), ptr(W5), ptr(b5), ptr(W1), ptr(b1), ptr(c1), ptr(res), R, n_rp, H, S, C0)
+
+
+def probe_conv_in_bwd(dc1, dy, W5, W1, eps, R, H, S, C0):
+    return _probe("ramp_probe_conv_in_bwd", ptr(dc1), ptr(dy), ptr(W5), ptr(W1), ptr(eps), R, H, S, C0)
+
+
+def probe_conv_out(a, Wf, bf, f, da, n_tok, S, C0):
+    """launch_conv_out: Wf [S][C0]; f or da may be None."""
+    return _probe("ramp_probe_conv_out", ptr(a), ptr(Wf), ptr(bf), ptr(f), ptr(da), n_tok, S, C0)
+
+
+def probe_expand_rows(x, out, R, n_rp, L, Cc, rowbias=None, rb_stride=0, rowvar=None, row0=0):
+    return _probe("ramp_probe_expand_rows", ptr(x), ptr(out), R, n_rp, L, Cc, ptr(rowbias), rb_stride, ptr(rowvar), row0)
+
+
+def probe_combine_rows(x, out, B, n_rp, L, Cc, w):
+    """launch_combine_rows: w the host weights (a sequence of floats)."""
+    wa = (C.c_float * max(len(w), 1))(*[float(v) for v in w])
+    return _probe("ramp_probe_combine_rows", ptr(x), ptr(out), B, n_rp, L, Cc, wa)
+
+
+def probe_combine_rows_weighted(x, out, B, n_rp, L, Cc, row_weight, weight_offset=0):
+    """launch_combine_rows_weighted: row_weight a device tensor, entered `weight_offset` floats in (a chunk's first trajectory)."""
+    return _probe("ramp_probe_combine_rows_weighted", ptr(x), ptr(out), B, n_rp, L, Cc, ptr(row_weight) + 4 * int(weight_offset))
+
+
+def probe_cross_bias(lat, n_var, ctx_dim, wv, wo, bo, out):
+    """launch_cross_bias: wv / wo / bo lists of n_blk device tensors."""
+    n = len(wv)
+    tabs = [(C.c_void_p * n)(*[ptr(t) for t in ts]) for ts in (wv, wo, bo)]
+    return _probe("ramp_probe_cross_bias", ptr(lat), n_var, ctx_dim, *tabs, n, ptr(out))
+
+
+def probe_time_bias(ctx, module, t, out):
+    """Block `module`'s slice of line t of the context's prepared time table into out (device, cout floats)."""
+    return _probe("ramp_probe_time_bias", ctx, module.encode(), int(t), ptr(out), out.numel())
 
 
 def ptr(t) -> Optional[int]:

@@ -1,4 +1,4 @@
-// Launch arguments of the row-wise, resampling, first / last layer and setup kernels (rowops.hip).
+// Launch arguments of the row-wise, first / last layer and setup kernels (rowops.hip).
 #pragma once
 #include "core.h"
 
@@ -44,16 +44,6 @@ int launch_combine_rows_weighted(const float* in, float* out, int B, int n_rp, i
 // GEGLU on ag (n_tok, 2*F): hg = a * gelu(g); backward writes dag (n_tok, 2*F)
 int launch_geglu_fwd(const float* ag, float* hg, int n_tok, int F, hipStream_t s);
 int launch_geglu_bwd(const float* dhg, const float* ag, float* dag, int n_tok, int F, hipStream_t s);
-
-// stride-2 resampling convolutions and their dX, one generic gather kernel.
-//   mode 0: src = 2*o + j - 1          (Downsample1d fwd, Upsample1d dX)      Lout = Lin/2
-//   mode 1: t = o + 1 - j, src = t/2 if t even   (Downsample1d dX, Upsample1d fwd)   Lout = 2*Lin
-// W packed as [taps][Cin][Cout] (Cout contiguous). y = bias + sum + add.
-struct ResampleArgs {
-  const float* x = nullptr; const float* W = nullptr; const float* bias = nullptr; const float* add = nullptr;
-  float* y = nullptr; int R = 0, Lin = 0, Lout = 0, Cin = 0, Cout = 0, taps = 3, mode = 0;
-};
-int launch_resample(const ResampleArgs& a, hipStream_t s);
 
 // first layer: x (B,H,S) -> c1 (R,H,C0) [conv k5] and res (R,H,C0) [1x1], row r reads x[r / n_rp]; C0 in {16, 32, 64}
 int launch_conv_in_fwd(const float* x, const float* W5 /*[5][S][C0]*/, const float* b5, const float* W1 /*[S][C0]*/,

@@ -1,5 +1,6 @@
 // ramp_bench_gemm / ramp_stress_gemm: the micro-benchmark of every kernel family on synthetic operands and the bitwise stress hook behind
-// the soak tests.  DIAGNOSTICS: this translation unit is linked into ramp_amd/lib/libramp_hip_tools.so only (the product library
+// the soak tests; ramp_probe_*: single launches of the GEMM kernels and of the network-edge / row kernels on caller-owned operands for
+// the kernel-level tests.  DIAGNOSTICS: this translation unit is linked into ramp_amd/lib/libramp_hip_tools.so only (the product library
 // libramp_hip.so exports no ramp_bench_* / ramp_stress_*); ramp_amd._lib.load_tools() binds it for tests/ and ramp_amd/tools/.
 #include "engine_util.h"
 #include "../../include/ramp_hip_tools.h"
@@ -551,6 +552,70 @@ int ramp_probe_gemm(const ramp_probe_gemm_args* p, int32_t mode, float a_absmax_
   a.M = p->M; a.N = p->N; a.K = p->K; a.taps = p->taps; a.shift0 = p->shift0; a.shift_step = p->shift_step; a.L = p->L;
   a.a_stride = p->a_stride; a.c_rstride = p->c_rstride; a.c_roff = p->c_roff;
   return op_gemm_packed(a, mode, a_absmax_prev, a_absmax_out, range_flag_out, as_stream(stream));
+}
+
+// probes of the plain-C++ kernels at the network's edges and where the shared prefix fans out (rowops.hip): each one launch of the
+// engine's own launch_* on the caller's device buffers -- the launcher's refusals are the probe's -- and a stream synchronisation
+#define PROBE(call_) do { hipStream_t ps_ = as_stream(stream); CK(call_); RAMP_HIP_CHECK(hipStreamSynchronize(ps_)); return 0; } while (0)
+int ramp_probe_conv_in_fwd(const float* x, const float* W5, const float* b5, const float* W1, const float* b1, float* c1, float* res,
+                           int32_t R, int32_t n_rp, int32_t H, int32_t S, int32_t C0, void* stream) {
+  PROBE(launch_conv_in_fwd(x, W5, b5, W1, b1, c1, res, R, n_rp, H, S, ps_, C0));
+}
+int ramp_probe_conv_in_bwd(const float* dc1, const float* dy, const float* W5, const float* W1, float* eps, int32_t R, int32_t H,
+                           int32_t S, int32_t C0, void* stream) {
+  PROBE(launch_conv_in_bwd(dc1, dy, W5, W1, eps, R, H, S, ps_, C0));
+}
+int ramp_probe_conv_out(const float* a, const float* Wf, const float* bf, float* f, float* da, int32_t n_tok, int32_t S, int32_t C0,
+                        void* stream) {
+  PROBE(launch_conv_out(a, Wf, bf, f, da, n_tok, S, ps_, C0));
+}
+int ramp_probe_expand_rows(const float* in, float* out, int32_t R, int32_t n_rp, int32_t L, int32_t C, const float* rowbias,
+                           int32_t rb_stride, const int32_t* rowvar, int32_t row0, void* stream) {
+  PROBE(launch_expand_rows(in, out, R, n_rp, L, C, rowbias, rb_stride, rowvar, row0, ps_));
+}
+int ramp_probe_combine_rows(const float* in, float* out, int32_t B, int32_t n_rp, int32_t L, int32_t C, const float* w_host,
+                            void* stream) {
+  PROBE(launch_combine_rows(in, out, B, n_rp, L, C, w_host, ps_));
+}
+int ramp_probe_combine_rows_weighted(const float* in, float* out, int32_t B, int32_t n_rp, int32_t L, int32_t C,
+                                     const float* row_weight, void* stream) {
+  PROBE(launch_combine_rows_weighted(in, out, B, n_rp, L, C, row_weight, ps_));
+}
+#undef PROBE
+
+// wv / wo / bo: HOST arrays of n_blk device pointers, marshalled into one device pointer table as set_scene_table (engine.hip) does
+int ramp_probe_cross_bias(const float* lat, int32_t n_var, int32_t ctx_dim, const float* const* wv_host, const float* const* wo_host,
+                          const float* const* bo_host, int32_t n_blk, float* out, void* stream) {
+  RAMP_REQUIRE(lat && wv_host && wo_host && bo_host && out, "null argument");
+  RAMP_REQUIRE(n_blk > 0 && n_blk <= 4096, "bad cross-bias dims (1 .. 4096 blocks)");
+  hipStream_t s = as_stream(stream);
+  const size_t nb = (size_t)n_blk * sizeof(void*);
+  char* d = nullptr;
+  RAMP_HIP_CHECK(hipMalloc(&d, 3 * nb));
+  auto body = [&]() -> int {
+    RAMP_HIP_CHECK(hipMemcpy(d, wv_host, nb, hipMemcpyHostToDevice));
+    RAMP_HIP_CHECK(hipMemcpy(d + nb, wo_host, nb, hipMemcpyHostToDevice));
+    RAMP_HIP_CHECK(hipMemcpy(d + 2 * nb, bo_host, nb, hipMemcpyHostToDevice));
+    CK(launch_cross_bias(lat, n_var, ctx_dim, reinterpret_cast<const float* const*>(d), reinterpret_cast<const float* const*>(d + nb),
+                         reinterpret_cast<const float* const*>(d + 2 * nb), n_blk, out, s));
+    RAMP_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+  };
+  const int rc = body();
+  (void)hipFree(d);
+  return rc;
+}
+
+// block `module_name`'s n = cout floats of line t of a context's prepared time table
+int ramp_probe_time_bias(ramp_ctx* ctx, const char* module_name, int32_t t, float* out, int32_t n, void* stream) {
+  RAMP_REQUIRE(ctx && module_name && out, "null argument");
+  const float* line = nullptr; int cout = 0;
+  CK(ctx_time_line(ctx, module_name, t, &line, &cout));
+  RAMP_REQUIRE(n == cout, "n must be the block's output channels");
+  hipStream_t s = as_stream(stream);
+  RAMP_HIP_CHECK(hipMemcpyAsync(out, line, (size_t)cout * sizeof(float), hipMemcpyDeviceToDevice, s));
+  RAMP_HIP_CHECK(hipStreamSynchronize(s));
+  return 0;
 }
 
 }  // extern "C"

@@ -1797,6 +1797,21 @@ int ramp_time_embedding(ramp_ctx* c, int32_t t, float* out32, void* stream) {
   return 0;
 }
 
+// block `module`'s slice of line t of the prepared time table (the tools library's ramp_probe_time_bias, bench.hip)
+namespace ramp {
+extern "C++" int ctx_time_line(ramp_ctx* c, const char* module, int t, const float** line, int* cout) {
+  RAMP_REQUIRE(c && module && line && cout, "null argument");
+  RAMP_REQUIRE(c->time_table != nullptr && t >= 0 && t < c->tt_T, "timestep outside the prepared time table");
+  for (const RTB& r : c->rtbs)
+    if (r.name == module) {
+      *line = c->time_table + (size_t)t * c->tt_stride + r.tb_off; *cout = r.cout;
+      return 0;
+    }
+  RAMP_REQUIRE(false, std::string("no residual block '") + module + "' in the time table");
+  return 1;
+}
+}  // namespace ramp
+
 // cross-attention constants of `n_variants` latents (cross_bias_kernel) + the row -> variant table: a cyclic pattern over the table's whole
 // capacity (n_rows == 0: ramp_set_scene) or the n_rows explicit entries (ramp_set_scenes); `table` is host memory
 static int set_scene_table(ramp_ctx* c, const float* latents, int n_variants, const int32_t* table, int n_table, int n_rows, hipStream_t s) {

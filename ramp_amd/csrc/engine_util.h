@@ -30,6 +30,10 @@ namespace ramp {
 __attribute__((visibility("hidden"))) int op_gemm_packed(GemmArgs a, int mode, float a_absmax_prev, float* a_absmax_out_host,
                                                          int32_t* range_flag_out_host, hipStream_t s);
 
+// Block `module`'s (a ResidualTemporalBlock's name, as in ramp_debug_read) cout floats of line t of a context's prepared time table
+// (engine.hip), for the tools library's ramp_probe_time_bias (bench.hip); an unknown name or a t outside the table is refused.  Hidden.
+__attribute__((visibility("hidden"))) int ctx_time_line(ramp_ctx* c, const char* module, int t, const float** line, int* cout);
+
 namespace {
 
 inline hipStream_t as_stream(void* s) { return static_cast<hipStream_t>(s); }

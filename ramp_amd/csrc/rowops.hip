@@ -4,7 +4,6 @@
 //   LayerNorm fwd / dX                                 layers_attention_mini.py:137-139
 //   GEGLU fwd / dX                                     layers_attention_mini.py:38-45
 //   (4x64 softmax self-attention lives in attention.hip)
-//   Downsample1d / Upsample1d fwd / dX                 layers.py:262-277
 //   first conv (S -> C0, k5 + 1x1 residual) fwd / dX   layers.py:337-361 for downs.0.0
 //   last conv (C0 -> S, 1x1) fwd + energy-gradient seed  UnetInference.py:142-145, 26-27
 //
@@ -499,43 +498,6 @@ int launch_geglu_bwd(const float* dhg, const float* ag, float* dag, int n_tok, i
   RAMP_REQUIRE(n_tok > 0 && F % 4 == 0, "bad GEGLU dims");
   const long n4 = (long)n_tok * (F / 4);
   hipLaunchKernelGGL(geglu_bwd_kernel, dim3(ew_grid(n4)), dim3(256), 0, s, dhg, ag, dag, n4, F / 4);
-  RAMP_HIP_CHECK(hipGetLastError());
-  return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// stride-2 resampling convolutions (generic gather form, see args_rows.h)
-// ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void resample_kernel(ResampleArgs a) {
-  extern __shared__ float xs[];                         // Lin * Cin
-  const int row = blockIdx.x;
-  const float* xr = a.x + (long)row * a.Lin * a.Cin;
-  for (int e = threadIdx.x; e < a.Lin * a.Cin; e += 256) xs[e] = xr[e];
-  __syncthreads();
-  const int n_out = a.Lout * a.Cout;
-  for (int idx = threadIdx.x; idx < n_out; idx += 256) {
-    const int o = idx / a.Cout, co = idx - o * a.Cout;
-    float acc = 0.f;
-    for (int j = 0; j < a.taps; ++j) {
-      int src;
-      if (a.mode == 0) src = 2 * o + j - 1;
-      else { const int t = o + 1 - j; if (t & 1) continue; src = t >> 1; if (t < 0) continue; }
-      if (src < 0 || src >= a.Lin) continue;
-      const float* w = a.W + (long)j * a.Cin * a.Cout + co;
-      const float* xv = xs + src * a.Cin;
-      for (int ci = 0; ci < a.Cin; ++ci) acc += xv[ci] * w[(long)ci * a.Cout];
-    }
-    if (a.bias) acc += a.bias[co];
-    const long oi = (long)row * n_out + idx;
-    if (a.add) acc += a.add[oi];
-    a.y[oi] = acc;
-  }
-}
-int launch_resample(const ResampleArgs& a, hipStream_t s) {
-  RAMP_REQUIRE(a.R > 0 && a.Lin > 0 && a.Lout > 0 && a.Cin > 0 && a.Cout > 0, "bad resample dims");
-  const size_t lds = (size_t)a.Lin * a.Cin * sizeof(float);
-  RAMP_REQUIRE(lds <= 64 * 1024, "resample row does not fit LDS");
-  hipLaunchKernelGGL(resample_kernel, dim3(a.R), dim3(256), lds, s, a);
   RAMP_HIP_CHECK(hipGetLastError());
   return 0;
 }
